@@ -7,10 +7,20 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch: forward + mechanistic model + masked MSE + VJP
-+ Adam update.  On one GPU that is ONE kernel per step (fused-update mode: the update of step s is
-applied in the prologue of step s+1's kernel and flushed at the end of the timed region); for N > 1
++ Adam update.  On one GPU that is the bitwise reproducible form a seeded train() runs by default (fused_update = 2: at this
+batch the step kernel writes one row of partial sums per workgroup and a reduce kernel folds them in a fixed order and applies
+Adam), so a run with the same arguments computes the same bits every time.  EH_FUSED=1 times the one-kernel form instead (the
+update of step s applied in the prologue of step s+1's kernel, float-atomic sums: faster, not reproducible); --full measures that
+form next to the headline as `float_atomic_step`.  For N > 1
 it is the step kernel, the partial reduction, one RCCL all-reduce of n_theta+2 raw sums and the
 Adam kernel.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value = samples/s, ms_per_step = wall time of one
+timed step).  --full adds the secondary measurements and checks: per-kernel timing and roofline, the N = 1 reference under
+--gpus N, the shuffled epoch, the CPU baselines, the parity replay against the oracle, the mechanistic stage alone, the
+layer-wise network and train() end to end.  --dump-outputs DIR writes what the timed steps produced -- the parameters and the
+Adam state after the last timed step -- as DIR/<name>.npy (float32); the inputs are seeded and the one-GPU step is reproducible,
+so two runs with the same arguments write the same arrays.
 """
 import argparse
 import json
@@ -273,14 +283,21 @@ def main():
     ap.add_argument("--no-specialize", action="store_true",
                     help="never compile a step kernel at run time (the headline descriptor has a kernel specialised ahead of time, csrc/eh_spec.hip, and runs it "
                          "either way; EH_NO_AOT_SPEC=1 takes that one away: then this flag picks the generic kernels over the hiprtc-built ones)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks (roofline / per-kernel timing, N = 1 reference, epoch, CPU baselines, "
+                         "oracle parity, mechanistic stage, layer-wise network, train() end to end); the --no-* flags above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parameters and Adam state they produced as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing in this process has touched a GPU yet (no torch import, no HIP call).
         sys.exit(spawn_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU checker is compiled (gcc: a fork + exec) BEFORE this process touches the GPU -- a process that has initialised
         # HIP must not start other programs on the GPU boxes; once the GPU is up, c_oracle.build() refuses instead of compiling
         from oracle import c_oracle
@@ -320,9 +337,13 @@ def main():
     cols = make_synth_rbq10(NBATCHES * B, seed=42 + rank)           # each rank: its own shard (weak scaling)
     X = np.stack([cols["sw_pot"], cols["dsw_pot"]]).astype(np.float32)
     t_up = [0.0]
+    # one GPU: 2 = the reproducible form (default), 1 = one kernel per step with float-atomic sums, 0 = always the step + reduce pair
+    fused_mode = int(os.environ.get("EH_FUSED", "2"))
+    one_kernel = fused_mode == 1          # (mode 2 runs one kernel per step only where one workgroup covers the batch)
 
-    def new_engine(single):
-        """a fresh engine holding this rank's shard; single: the one-GPU step mode (one kernel per step on the specialised kernel)"""
+    def new_engine(single, mode=None):
+        """a fresh engine holding this rank's shard; single: the one-GPU step mode on the specialised kernel -- fused_update = `mode`,
+        else EH_FUSED (default 2, the reproducible form)"""
         e = model.engine(local)
         e.set_stream(torch.cuda.current_stream().cuda_stream)
         t = time.perf_counter()
@@ -334,9 +355,10 @@ def main():
         if share:
             e.set_option("max_blocks", max(1, 128 // world))          # every rank's kernel has to fit on the shared GPU at once
         if single:
-            # one kernel per step: the optimiser update of step s runs in the prologue of step s+1 and the
-            # partial sums are accumulated with float atomics (opt-in mode)
-            e.set_option("fused_update", int(os.environ.get("EH_FUSED", "1")))
+            # 1: one kernel per step, the optimiser update of step s in the prologue of step s+1, partial sums in float atomics (not
+            # bitwise reproducible); 2: that kernel only where one workgroup covers the batch, else the step kernel + fixed-order reduce
+            # pair (bitwise reproducible, what a seeded train() runs); 0: always the pair
+            e.set_option("fused_update", fused_mode if mode is None else mode)
             if not args.no_specialize:
                 # the "specialize" option: the step kernel is compiled at run time (hiprtc, ~1 s) with this model's descriptor as a
                 # compile-time constant; one forward over one sample builds it here, ahead of the warm-up
@@ -368,7 +390,7 @@ def main():
 
     force_dp = os.environ.get("EH_FORCE_DP", "0") == "1"          # exercise the data-parallel seam on one GPU
     n1_ref = None
-    if world > 1:
+    if args.full and world > 1:
         # the N = 1 figure measured in THIS run, for comparison: every rank runs the one-GPU step mode on its own GPU and shard,
         # same warm-up and step count, no exchange; the slowest rank's time counts (what weak scaling is measured against)
         e1 = new_engine(True)
@@ -400,9 +422,27 @@ def main():
             exchange_cal = dp.calibrate(0, B, 300)
     dt = timed(step, eng)
 
+    if args.dump_outputs and rank == 0:
+        # what the timed steps produced (timed() has drained the stream, so the last step's update is applied); replicas are equal
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        m, v, bt = eng.get_opt_state()
+        for name, a in (("params", eng.get_params()), ("adam_m", m), ("adam_v", v), ("adam_beta_powers", bt)):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.asarray(a, np.float32))
+
+    # --full on one GPU: the secondary figures (roofline, epoch, parity) run the one-kernel float-atomic form, as they always have; when
+    # the headline timed another form, that form is timed first on a fresh engine with the same warm-up and steps (float_atomic_step)
+    feng, fstep, f_one, float_atomic = eng, step, (one_kernel if dp is None else dp.fused), None
+    if args.full and rank == 0 and world == 1 and dp is None and not one_kernel:
+        feng = new_engine(True, mode=1)
+        fstep, f_one = (lambda first: feng.train_step(first, B, want_loss=False)), True
+        dt1 = timed(fstep, feng)
+        float_atomic = {"value": B * args.steps / dt1, "unit": "samples/s", "ms_per_step": 1e3 * dt1 / args.steps,
+                        "what": "fused_update = 1: one kernel per step, float-atomic sums (not bitwise reproducible); same warm-up and steps; "
+                                "roofline, epoch and parity run this form"}
+
     # live kernel timing: more steps with HIP events bracketing the fused step kernel
-    roof = None
-    if rank == 0 or dp is not None:
+    roof, n, ms_step = None, 0, 0.0
+    if args.full and (rank == 0 or dp is not None):
         # one HIP event pair (on the engine's stream) around every burst of BURST consecutive launches: an event
         # between two back-to-back 13 us kernels would add ~2 us to each, a burst measures the steady-state rate.
         # At least five bursts whatever --steps says, so that the percentiles below are over several samples.
@@ -410,19 +450,19 @@ def main():
         # other), with the exchange inside the bracket when it is part of the kernel.
         BURST = 50
         nprof = max(5 * BURST, min(args.steps, 4000) // BURST * BURST)
-        eng.profile_enable(BURST)
+        feng.profile_enable(BURST)
         if dp is None or dp.p2p:
             for s in range(nprof):
-                step((s % NBATCHES) * B)
+                fstep((s % NBATCHES) * B)
         else:
             for s in range(nprof):                                 # local part only: no collective inside the bracket
                 if dp.fused:
                     eng.dp_fused_step((s % NBATCHES) * B, B)
                 else:
                     eng.dp_grad((s % NBATCHES) * B, B)
-        per_launch = eng.profile_samples() / BURST                 # ms per launch, one value per burst
-        n, _, _ = eng.profile_read()
-        eng.profile_enable(False)
+        per_launch = feng.profile_samples() / BURST                # ms per launch, one value per burst
+        n, _, _ = feng.profile_read()
+        feng.profile_enable(False)
         n *= BURST
         ms_step = float(per_launch.mean()) if per_launch.size else 0.0
         if dp is not None and dp.p2p:
@@ -434,18 +474,18 @@ def main():
             traffic, traffic_src = None, None
             try:      # HBM bytes per launch from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, KiB)
                 tj = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
-                if tj.get("batch") == B and tj.get("fused") == (dp is None or dp.fused):
+                if tj.get("batch") == B and tj.get("fused") == f_one:
                     traffic, traffic_src = (2.0 * tj["FETCH_SIZE_KiB"] + tj["WRITE_SIZE_KiB"]) * 1024.0, tj["source"]
             except Exception:
                 pass
             roof = {"bound": "mfma", "achieved": tf, "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s", "frac": tf / PEAK_F32_TFLOPS,
                     "traffic": traffic, "traffic_kind": "static: read from the committed PMC passes, NOT measured in this run (hardware counters need rocprofv3 around the process)" if traffic is not None else None,
                     "traffic_source": traffic_src, "kernel": "eh_step_kernel<NBI=1,NBH=1,NL=2,NT=2,NW=8,tanh,train+p2p,K1|PS> (fused update, peer-to-peer exchange)" if (dp is not None and dp.p2p) else
-                    "eh_step_kernel<NBI=1,NBH=1,NL=2,NT=2,NW=8,tanh,train,K1|PS> (fused update)" if (dp is None or dp.fused) else
+                    "eh_step_kernel<NBI=1,NBH=1,NL=2,NT=2,NW=8,tanh,train,K1|PS> (fused update)" if f_one else
                     "eh_step_kernel<NBI=1,NBH=1,NL=2,NT=2,NW=8,tanh,train,K1|PS> + eh_reduce_kernel", "kernel_build": built, "kernel_ms": ms_step, "launches_timed": n,
                     "bursts_timed": int(per_launch.size),
                     "kernel_ms_p10_p50_p90": [float(np.percentile(per_launch, q)) for q in (10, 50, 90)],
-                    "timing": f"HIP events on the engine stream around bursts of {BURST} launches" + (" (step kernel + reduce kernel per launch)" if (dp is not None and not dp.fused) else "")
+                    "timing": f"HIP events on the engine stream around bursts of {BURST} launches" + (" (step kernel + reduce kernel per launch)" if not f_one else "")
                               + (" (includes the wait for the peer GPUs' sums: the exchange is part of the kernel)" if (dp is not None and dp.p2p) else ""),
                     "algorithmic": {"flop_per_launch": FLOP_PER_SAMPLE * B, "bytes_per_launch": BYTES_PER_SAMPLE * B},
                     "hbm_achieved_GBps": gbs, "hbm_frac": gbs / PEAK_HBM_GBPS}
@@ -456,21 +496,23 @@ def main():
         devices = [None] * world
         dist.all_gather_object(devices, mine)
     fence(eng)
+    if feng is not eng:
+        fence(feng)
 
     # the path train() really runs: a shuffled epoch gathers 16-byte records through a device-side permutation
     # (eh_train_epoch, reference src/data/loaders.jl:1-12 + src/training/epoch.jl:13-33); contiguous epoch beside it
     epoch = None
-    if rank == 0 and world == 1 and dp is None and not args.no_epoch:
+    if args.full and rank == 0 and world == 1 and dp is None and not args.no_epoch:
         try:
             epoch = {}
             for name, shuffle in (("contiguous", False), ("shuffled", True)):
                 for k in range(2):
-                    eng.train_epoch(B, seed=11 + k, shuffle=shuffle, want_loss=False)
-                eng.synchronize()
+                    feng.train_epoch(B, seed=11 + k, shuffle=shuffle, want_loss=False)
+                feng.synchronize()
                 reps, t0 = 8, time.perf_counter()
                 for k in range(reps):
-                    eng.train_epoch(B, seed=100 + k, shuffle=shuffle, want_loss=False)
-                eng.synchronize()
+                    feng.train_epoch(B, seed=100 + k, shuffle=shuffle, want_loss=False)
+                feng.synchronize()
                 per = (time.perf_counter() - t0) / (reps * NBATCHES)
                 epoch[name] = {"us_per_step": 1e6 * per, "samples_per_s": B / per, "algorithmic_GBps": BYTES_PER_SAMPLE * B / per / 1e9}
             epoch["shuffled_over_contiguous"] = epoch["shuffled"]["us_per_step"] / epoch["contiguous"]["us_per_step"]
@@ -495,9 +537,11 @@ def main():
                                              else "one RCCL all-reduce per step" if not share else "one gloo all-reduce per step (EH_BENCH_SHARE_GPU=1: all ranks on one GPU, testing only)"),
                        "gradient_exchange_calibration_us_per_step": exchange_cal,
                        "gradient_exchange_negotiation": getattr(dp, "p2p_report", None) if dp is not None else None, "step_kernel": built,
-                       "step_mode": "one kernel per step (fused_update = 1: float-atomic sums) on the kernel specialised for this descriptor (see step_kernel): what "
-                                    "train(fused_update = True) or an unseeded train() runs; a seeded train() -- the default, bitwise reproducible -- takes the deterministic "
-                                    "step + reduce pair at this batch size (train_e2e: steps_s against steps_s_fused_update_true)" if dp is None else "see step_kernel / gradient_exchange"},
+                       "step_mode": ("one kernel per step (fused_update = 1: float-atomic sums, not bitwise reproducible) on the kernel specialised for this "
+                                     "descriptor (see step_kernel): what train(fused_update = True) or an unseeded train() runs" if one_kernel else
+                                     f"fused_update = {fused_mode}: the bitwise reproducible form a seeded train() -- the default -- runs: at this batch the step kernel "
+                                     "specialised for this descriptor (see step_kernel) writes one row of partial sums per workgroup, a reduce kernel folds them in a "
+                                     "fixed order and applies Adam (float_atomic_step under --full: the faster one-kernel form)") if dp is None else "see step_kernel / gradient_exchange"},
             "roofline": roof,
         }
         if n1_ref is not None:
@@ -506,14 +550,16 @@ def main():
         out["dataset_upload_ms_once"] = 1e3 * t_up[0]
         if epoch is not None:
             out["epoch"] = epoch
-        if world == 1 and not args.no_cpu_baseline:
+        if float_atomic is not None:
+            out["float_atomic_step"] = float_atomic
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B)
             try:
-                out["parity"] = parity_replay(model, lambda: new_engine(dp is None), cols, X, B)
+                out["parity"] = parity_replay(model, lambda: new_engine(dp is None, mode=1 if f_one else None), cols, X, B)
                 out["final_loss"], out["oracle_final_loss"] = out["parity"]["final_loss"], out["parity"]["oracle_final_loss"]
             except Exception as e:
                 out["parity"] = {"error": repr(e)}
-        if world == 1 and dp is None and not args.no_mech_stage:
+        if args.full and world == 1 and dp is None and not args.no_mech_stage:
             # the HBM-bound stage of the path measured as its own kernel (the fused step is compute / latency
             # bound, so the north_star's HBM yardstick applies to the mechanistic + loss + VJP stage alone): eh_mech_loss_vjp on
             # 1 024 resident batches of the headline workload (a working set the Infinity Cache cannot hold).  A secondary figure; `roofline` above stays the step kernel's.
@@ -524,7 +570,7 @@ def main():
                 out["hbm_stage"] = bm.measure("rbq10", 1024 * B, 50)      # 1 GiB of planes: four times the 256 MB Infinity Cache
             except Exception as e:      # never lose the headline line over the secondary measurement
                 out["hbm_stage"] = {"error": repr(e)}
-        if world == 1 and dp is None and not args.no_layerwise:
+        if args.full and world == 1 and dp is None and not args.no_layerwise:
             # the other kernel family of the path: networks no fused kernel holds run layer by layer -- the
             # reference's own GPU tutorial network (docs/literate/tutorials/synthetic_respiration_gpu.jl:79-103: [1024, 512, 256, 128, 64],
             # sigmoid, input BatchNorm, RMSProp) at the tutorial's batch of 64 and at the headline batch.  A secondary figure.
@@ -536,7 +582,7 @@ def main():
                                     "runs": [bl.measure(64, local), bl.measure(B, local)]}
             except Exception as e:
                 out["layerwise"] = {"error": repr(e)}
-        if world == 1 and dp is None and not args.no_train_e2e:
+        if args.full and world == 1 and dp is None and not args.no_train_e2e:
             # what a user runs: eh.train(...) end to end on the reference tutorial's two models and on the headline data set, split into
             # steps / evaluation / host, next to the same work in PyTorch-CPU eager; and the evaluation kernel's own roofline entry
             try:
@@ -547,6 +593,8 @@ def main():
             except Exception as e:
                 out["train_e2e"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
+    if feng is not eng:
+        feng.close()
     eng.close()
     if dist.is_initialized():
         dist.destroy_process_group()

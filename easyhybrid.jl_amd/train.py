@@ -229,7 +229,8 @@ class TrainConfig:
     #                `fused_update=True` buys the difference back).  False: always the deterministic pair.  True: insist on one kernel
     #                per step (raises where it is not built).  (An ORDERED one-kernel form -- fixed-point sums, integer atomics -- was
     #                built and measured in round 6: 13.9 us, and 0.6 us on the float form it shared the kernel with; removed.)
-    # bench.py measures specialize on and fused_update = True at the engine.
+    # bench.py measures specialize on and the reproducible form (fused_update = 2, what "auto" takes when seeded) at the engine;
+    # with --full also fused_update = True.
     specialize: Any = "auto"
     fused_update: Any = "auto"
     # not in the reference: "lazy" (default) = the observed-vs-predicted tables and the physical parameters of the returned model

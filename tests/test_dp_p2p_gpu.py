@@ -132,7 +132,7 @@ def test_bench_gpus_n_launches_its_own_ranks_and_prints_a_self_describing_line(n
         pytest.skip("this process already initialised the GPU; run this file first (or alone)")
     env = dict(os.environ, EH_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "5"], cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "5", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ if [ ! -d "$(dirname "$0")/../dbg/r01" ]; then echo "$0: dbg/r01 is missing (a w
 set -u
 ROOT=$PWD
 OUT=$ROOT/$1; mkdir -p $OUT
-run() { tag=$1; shift; env "$@" python3 bench.py --steps 3000 --warmup 300 --no-cpu-baseline --no-mech-stage --no-epoch > $OUT/$tag.json 2>$OUT/$tag.err
+run() { tag=$1; shift; env EH_FUSED=1 "$@" python3 bench.py --full --steps 3000 --warmup 300 --no-cpu-baseline --no-mech-stage --no-epoch > $OUT/$tag.json 2>$OUT/$tag.err
   python3 -c "
 import json,sys
 try:

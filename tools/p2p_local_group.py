@@ -14,7 +14,9 @@ import sys
 
 # eight streams whose kernels wait for each other must not share a hardware queue (the default is four queues per process: a
 # kernel that spins until a peer's sums arrive would sit IN FRONT of that peer's kernel).  On the node every device has its own.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+# Raised, not only defaulted: an inherited GPU_MAX_HW_QUEUES=4 leaves eight members on four queues and the start-up self-test runs into its
+# deadline.  A caller's larger value stands.
+os.environ["GPU_MAX_HW_QUEUES"] = str(max(24, int(os.environ.get("GPU_MAX_HW_QUEUES") or 0)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 

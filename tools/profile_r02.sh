@@ -11,13 +11,13 @@ cd /tmp
 prof() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$tag -- "$@" > $OUT/$tag.json 2> $OUT/$tag.err; }
 pmc() { tag=$1; ctr=$2; shift 2; timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/pmc_$tag -- "$@" > /dev/null 2> $OUT/pmc_$tag.err; }
 # headline
-prof bench python3 $ROOT/bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-mech-stage
-pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-mech-stage
-pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-mech-stage
-pmc bench_sq "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" python3 $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-mech-stage
-timeout -k 10 300 python3 $ROOT/bench.py --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err
-timeout -k 10 300 python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-mech-stage > $OUT/bench_driver_sized_20steps.json 2>/dev/null
-timeout -k 10 300 python3 $ROOT/bench.py --steps 3000 --warmup 300 --no-cpu-baseline --no-mech-stage --no-specialize > $OUT/bench_3000steps_ahead_of_time_kernels.json 2>/dev/null
+prof bench python3 $ROOT/bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline --no-mech-stage
+pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-mech-stage
+pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-mech-stage
+pmc bench_sq "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" python3 $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-mech-stage
+timeout -k 10 300 python3 $ROOT/bench.py --full --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err
+timeout -k 10 300 python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-mech-stage > $OUT/bench_driver_sized_20steps.json 2>/dev/null
+timeout -k 10 300 python3 $ROOT/bench.py --full --steps 3000 --warmup 300 --no-cpu-baseline --no-mech-stage --no-specialize > $OUT/bench_3000steps_ahead_of_time_kernels.json 2>/dev/null
 # config 5 as BASELINE states it (bf16 forward / fp32 accumulate, 3 forcings; 2 M resident samples here, the 1e7 run below) and its fp32 twin
 for p in bf16_fwd f32; do
   prof c5_$p python3 $ROOT/tools/bench_config.py c5 --precision $p --steps 200 --n 2000000 --specialize 1

@@ -12,17 +12,17 @@ prof() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --stats --out
 pmc() { tag=$1; ctr=$2; shift 2; timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/pmc_$tag -- "$@" > /dev/null 2> $OUT/pmc_$tag.err; }
 B="--no-cpu-baseline --no-mech-stage --no-epoch --no-layerwise"
 # headline
-prof bench python3 $ROOT/bench.py --steps 2000 --warmup 200 $B
-pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 $B
-pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 $B
-pmc bench_sq "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" python3 $ROOT/bench.py --steps 200 --warmup 20 $B
+prof bench python3 $ROOT/bench.py --full --steps 2000 --warmup 200 $B
+pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
+pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
+pmc bench_sq "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
 # the path train() runs: shuffled epochs (records gathered through the device-side permutation), traffic next to the contiguous form
 pmc epoch_shuffled_fetch FETCH_SIZE python3 $ROOT/tools/bench_epoch.py --mode shuffled --epochs 2
 pmc epoch_contiguous_fetch FETCH_SIZE python3 $ROOT/tools/bench_epoch.py --mode contiguous --epochs 2
 timeout -k 10 300 python3 $ROOT/tools/bench_epoch.py > $OUT/bench_epoch.json 2>/dev/null
-timeout -k 10 300 python3 $ROOT/bench.py --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err
-timeout -k 10 300 python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/bench_driver_sized_20steps.json 2>/dev/null
-timeout -k 10 300 python3 $ROOT/bench.py --steps 3000 --warmup 300 $B --no-specialize > $OUT/bench_3000steps_ahead_of_time_kernels.json 2>/dev/null
+timeout -k 10 300 python3 $ROOT/bench.py --full --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err
+timeout -k 10 300 python3 $ROOT/bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_sized_20steps.json 2>/dev/null
+timeout -k 10 300 python3 $ROOT/bench.py --full --steps 3000 --warmup 300 $B --no-specialize > $OUT/bench_3000steps_ahead_of_time_kernels.json 2>/dev/null
 # the stand-alone mechanistic stage (north_star: >= 60 % of HBM for the mechanistic + VJP kernel), 1.07 GB per call
 prof mech_stage python3 $ROOT/tools/bench_mech.py --batch 67108864 --steps 40
 pmc mech_stage_fetch FETCH_SIZE python3 $ROOT/tools/bench_mech.py --batch 67108864 --steps 10

@@ -13,9 +13,9 @@ prof() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --stats --out
 pmc() { tag=$1; ctr=$2; shift 2; timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/pmc_$tag -- "$@" > /dev/null 2> $OUT/pmc_$tag.err; }
 B="--no-cpu-baseline --no-mech-stage --no-epoch --no-layerwise --no-train-e2e"
 # headline (the kernel specialised ahead of time runs by default)
-prof bench python3 $ROOT/bench.py --steps 2000 --warmup 200 $B
-pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 $B
-pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 $B
+prof bench python3 $ROOT/bench.py --full --steps 2000 --warmup 200 $B
+pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
+pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
 echo "progress: headline profiled"
 # config 5 as BASELINE states it (1e7 resident, B = 65 536) in both bf16 modes; config 3
 for p in bf16_fwd bf16; do
@@ -31,11 +31,11 @@ pmc c3_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE SQ_WAVES SQ_
 prof train_e2e python3 $ROOT/tools/bench_train_e2e.py
 echo "progress: end-to-end profiled"
 cd $ROOT
-timeout -k 10 400 python3 bench.py --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 $B > $OUT/bench_driver_sized_20steps.json 2>/dev/null
-timeout -k 10 300 python3 bench.py --steps 3000 --warmup 300 $B --no-specialize > $OUT/bench_3000steps_no_specialize.json 2>/dev/null
-EH_NO_AOT_SPEC=1 timeout -k 10 300 python3 bench.py --steps 3000 --warmup 300 $B > $OUT/bench_3000steps_hiprtc_kernel.json 2>/dev/null
-EH_NO_AOT_SPEC=1 timeout -k 10 300 python3 bench.py --steps 3000 --warmup 300 $B --no-specialize > $OUT/bench_3000steps_generic_kernel.json 2>/dev/null
+timeout -k 10 400 python3 bench.py --full --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 $B > $OUT/bench_driver_sized_20steps.json 2>/dev/null
+timeout -k 10 300 python3 bench.py --full --steps 3000 --warmup 300 $B --no-specialize > $OUT/bench_3000steps_no_specialize.json 2>/dev/null
+EH_NO_AOT_SPEC=1 timeout -k 10 300 python3 bench.py --full --steps 3000 --warmup 300 $B > $OUT/bench_3000steps_hiprtc_kernel.json 2>/dev/null
+EH_NO_AOT_SPEC=1 timeout -k 10 300 python3 bench.py --full --steps 3000 --warmup 300 $B --no-specialize > $OUT/bench_3000steps_generic_kernel.json 2>/dev/null
 echo "progress: headline variants done"
 {
   for p in bf16_fwd bf16 f32; do timeout -k 10 300 python3 tools/bench_config.py c5 --precision $p --steps 300; done

@@ -22,9 +22,9 @@ SQ3="SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS SQ_ACTIVE_INS
 PART=${PART:-all}      # PART=1: traces and counters, PART=2: the un-profiled lines, stamps, primitives, soak (a gpurun call is 20 minutes at most)
 if [ "$PART" != "2" ]; then
 # headline
-prof bench python3 $ROOT/bench.py --steps 2000 --warmup 200 $B
-pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 $B
-pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --steps 200 --warmup 20 $B
+prof bench python3 $ROOT/bench.py --full --steps 2000 --warmup 200 $B
+pmc bench_fetch FETCH_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
+pmc bench_write WRITE_SIZE python3 $ROOT/bench.py --full --steps 200 --warmup 20 $B
 # config 5 as BASELINE states it (1e7 resident, B = 65 536): "bf16" on the sample-owned kernel (default) and on the row-split one, "bf16_fwd"
 prof c5_bf16 $C5 --precision bf16 --steps 200
 EH_NO_SAMPLE_OWNED=1 prof c5_bf16_rowsplit $C5 --precision bf16 --steps 200
@@ -52,8 +52,8 @@ prof multistep python3 $ROOT/tools/multistep_probe.py
 fi
 cd $ROOT
 if [ "$PART" != "1" ]; then
-timeout -k 10 400 python3 bench.py --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err; echo "progress: bench line"
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 $B > $OUT/bench_driver_sized_20steps.json 2>/dev/null
+timeout -k 10 400 python3 bench.py --full --steps 3000 --warmup 300 > $OUT/bench_3000steps.json 2> $OUT/bench_3000.err; echo "progress: bench line"
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 $B > $OUT/bench_driver_sized_20steps.json 2>/dev/null
 {
   for p in bf16_fwd bf16 f32; do timeout -k 10 300 python3 tools/bench_config.py c5 --precision $p --steps 300; done
   EH_NO_SAMPLE_OWNED=1 timeout -k 10 300 python3 tools/bench_config.py c5 --precision bf16 --steps 300

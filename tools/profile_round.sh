@@ -6,15 +6,15 @@ export TMPDIR=/tmp
 TAG=${1:-r01}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 2000 --warmup 200 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > /dev/null 2> $OUT/pmc_fetch.err
-timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > /dev/null 2> $OUT/pmc_write.err
-timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/pmc_sq -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > /dev/null 2> $OUT/pmc_sq.err
-timeout 300 python3 bench.py --steps 3000 --warmup 300 > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > /dev/null 2> $OUT/pmc_fetch.err
+timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > /dev/null 2> $OUT/pmc_write.err
+timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/pmc_sq -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > /dev/null 2> $OUT/pmc_sq.err
+timeout 300 python3 bench.py --full --steps 3000 --warmup 300 > $OUT/bench.json 2> $OUT/bench.err
 # the other BASELINE shapes: kernel trace of the front-door step loop (tools/bench_config.py), run-time specialised kernels like the bench;
 # bench_config_<cfg>_aot.json = the kernels built ahead of time, for comparison
 for cfg in c3 c5; do timeout 120 python3 tools/bench_config.py $cfg --steps 200 --fused 0 --specialize 0 > $OUT/bench_config_${cfg}_aot.json 2>/dev/null; done
-timeout 120 python3 bench.py --steps 3000 --warmup 300 --no-cpu-baseline --no-specialize > $OUT/bench_aot.json 2>/dev/null
+timeout 120 python3 bench.py --full --steps 3000 --warmup 300 --no-cpu-baseline --no-specialize > $OUT/bench_aot.json 2>/dev/null
 for cfg in c3 c5; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$cfg -- python3 tools/bench_config.py $cfg --steps 200 --fused 0 --specialize 1 > $OUT/bench_config_$cfg.json 2> $OUT/trace_$cfg.err
 done
