@@ -6,6 +6,7 @@
 #include <chrono>
 
 #include <algorithm>
+#include <cfloat>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -1209,12 +1210,16 @@ int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, cons
         const long long tot = (long long)n * C;
         hipLaunchKernelGGL(eh_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, pa, sp.recs, (long long)n, net.P, net.F, net.T, planes ? 1 : 0);
         HIPCHK(h, hipGetLastError());
-        // metric shift: mean of the first valid targets, computed from a small host copy
+        // metric shift: mean of the first EH_SHIFT_VALID valid targets, from small host copies (a record that starts with a gap is read on
+        // until that many are found)
         std::vector<float> tmp((size_t)std::min<int64_t>(n, 4096));
         for (int t = 0; t < net.T; ++t) {
-            HIPCHK(h, hipMemcpy(tmp.data(), targets[t], tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
             double s = 0; long long c = 0;
-            for (float vv : tmp) if (!std::isnan(vv)) { s += vv; ++c; }
+            for (int64_t off = 0; off < n && c < EH_SHIFT_VALID; off += (int64_t)tmp.size()) {
+                const size_t m = (size_t)std::min<int64_t>((int64_t)tmp.size(), n - off);
+                HIPCHK(h, hipMemcpy(tmp.data(), targets[t] + off, m * sizeof(float), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < m && c < EH_SHIFT_VALID; ++i) if (!std::isnan(tmp[i])) { s += tmp[i]; ++c; }
+            }
             sp.shift[t] = c ? (float)(s / c) : 0.0f;
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1224,7 +1229,7 @@ int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, cons
         // blocking copy: 56 ms for the headline data set; the one-time cost a user's train() call pays before its first step.)
         for (int t = 0; t < net.T; ++t) {
             double sum = 0; long long c = 0;
-            for (int64_t s = 0; s < std::min<int64_t>(n, 4096); ++s) if (!std::isnan(targets[t][s])) { sum += targets[t][s]; ++c; }
+            for (int64_t s = 0; s < n && c < EH_SHIFT_VALID; ++s) if (!std::isnan(targets[t][s])) { sum += targets[t][s]; ++c; }
             sp.shift[t] = c ? (float)(sum / c) : 0.0f;
         }
         const int64_t CH = std::min<int64_t>(n, (int64_t)1 << 20);
@@ -1373,7 +1378,12 @@ static int eval_grid_for(const eh_handle* h, long long count) {
     int cap = h->max_blocks;
     if (h->eval_blocks > 0) cap = h->eval_blocks;
     else if (!h->arch->wide && h->max_blocks == 256) cap = EH_EVAL_BLOCKS;
-    return (int)std::max<long long>(1, std::min<long long>((ntiles + per - 1) / per, cap));
+    // Every lane sums its samples' statistics sequentially in fp32, the valid count among them, and the workgroup's sum is fp32 too: a
+    // floor on the grid keeps a wave at EH_EVAL_TILES tiles or fewer, whatever cap "eval_blocks" sets, so the count stays exact (a
+    // workgroup's fp32 count is not above 2^24) and the rounding of the sums bounded.  The floor stays within the slab's 4 MB of metric
+    // rows (EH_EVAL_COPY); the default grids of the splits the benchmarks use are above it.
+    const long long floor = std::min<long long>((ntiles + per * EH_EVAL_TILES - 1) / (per * EH_EVAL_TILES), (1LL << 20) / (EH_EVAL_STATS * EH_MAX_TARG));
+    return (int)std::max<long long>(std::max<long long>(1, floor), std::min<long long>((ntiles + per - 1) / per, cap));
 }
 
 // input BatchNorm: statistics of the minibatch [first, first+count) -> a.bn_* (train-mode kernels only)
@@ -2349,11 +2359,16 @@ int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_ta
         eh_target_metrics& o = out[t];
         o.n = n; o.sse = S;
         if (n <= 0) { o.mse = o.rmse = o.mae = o.r2 = o.nse = o.pearson = o.kge = o.pbkge = o.beta = o.alpha = nan; continue; }
-        const double ssy = Syy - Sy * Sy / n, ssh = Shh - Sh * Sh / n, shy = Shy - Sh * Sy / n;
+        // centred sums.  The raw ones are fp32 sums: a centred one below 64 ulp of its raw sum of squares has no correct digit left and
+        // is the zero of a constant selection (one sample, a constant target or prediction), which loss_fn sees exactly.
+        double ssy = Syy - Sy * Sy / n, ssh = Shh - Sh * Sh / n, shy = Shy - Sh * Sy / n;
+        const double tiny = 64.0 * FLT_EPSILON;
+        if (ssy <= tiny * Syy) ssy = 0.0;
+        if (ssh <= tiny * Shh) ssh = 0.0;
         o.mse = S / n; o.rmse = std::sqrt(o.mse); o.mae = A / n;
-        o.r2 = 1.0 - S / ssy;           // loss_fn(Val(:r2)), src/losses/loss_fn.jl:71-73
+        o.r2 = 1.0 - S / ssy;           // loss_fn(Val(:r2)), src/losses/loss_fn.jl:71-73 (a constant target: -Inf, or NaN for S = 0)
         o.nse = o.r2;                   // :nse has the same closed form (:85-86)
-        o.pearson = shy / std::sqrt(ssh * ssy);
+        o.pearson = ssy > 0.0 && ssh > 0.0 ? shy / std::sqrt(ssh * ssy) : nan;      // cor() of a constant vector is NaN
         o.alpha = std::sqrt(ssh / ssy); // std ratio (the n-1 cancels)
         o.beta = (c + Sh / n) / (c + Sy / n);
         o.kge = 1.0 - std::sqrt((o.pearson - 1) * (o.pearson - 1) + (o.alpha - 1) * (o.alpha - 1) + (o.beta - 1) * (o.beta - 1));

@@ -46,6 +46,10 @@ struct EhImg {
 // --------------------------------------------------------------------------------------------
 constexpr int EH_MULTI_MAX = 256;         // steps per launch of the multi-step kernel (EH_MODE_TRAIN_MULTI): bounds a launch to a millisecond or two
 constexpr int EH_EVAL_BLOCKS = 1024;      // evaluation passes of the per-wave kernels: up to four workgroups per CU (eval_grid_for, eh_api.hip)
+constexpr int EH_EVAL_TILES = 64;        // most tiles one wave of an evaluation pass sums into its lanes' fp32 statistics (eval_grid_for: a floor on the grid)
+// the metric shift c_t of a split (eh_set_data): the mean of its first EH_SHIFT_VALID valid values of target t, so that the centred sums of
+// the metrics (sum (y - c)^2 - (sum (y - c))^2 / n) do not cancel in fp32; a target whose record starts with a gap is scanned further
+constexpr long long EH_SHIFT_VALID = 4096;
 
 struct EhSplit {
     float* recs = nullptr;

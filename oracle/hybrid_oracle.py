@@ -45,6 +45,7 @@ What each function follows in the reference (paths relative to /root/reference)
 """
 from __future__ import annotations
 
+import warnings
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -618,6 +619,63 @@ def loss_fn(yhat, y, mask, kind: str):
     if kind == "α":
         return np.std(a, ddof=1) / np.std(b, ddof=1)
     raise ValueError(kind)
+
+
+EVAL_STATS = ("S", "Sy", "Syy", "n", "Sh", "Shh", "Shy", "A")      # eh_device.hpp EH_EVAL_STATS, in that order
+
+
+def eval_sums(yhat, y, mask, shift, dtype=np.float64):
+    """The eight per-target statistics eh_eval's kernels sum (EVAL_STATS), in `dtype`, about the target shift c:
+    sum (yh - y)^2, sum (y - c), sum (y - c)^2, n, sum (yh - c), sum (yh - c)^2, sum (yh - c)(y - c), sum |yh - y|."""
+    dt = np.dtype(dtype).type
+    a, b, c = np.asarray(yhat, dtype)[mask], np.asarray(y, dtype)[mask], dt(np.float32(shift))      # (the shift is an fp32 value)
+    r, cy, ch = a - b, b - c, a - c
+    return np.array([np.sum(r * r, dtype=dtype), np.sum(cy, dtype=dtype), np.sum(cy * cy, dtype=dtype), a.size, np.sum(ch, dtype=dtype),
+                     np.sum(ch * ch, dtype=dtype), np.sum(ch * cy, dtype=dtype), np.sum(np.abs(r), dtype=dtype)], np.float64)
+
+
+def metrics_from_sums(sums, shift):
+    """eh_eval's host fold (csrc/eh_api.hip, eh_eval) restated: the metrics of one target from its eight statistics (EVAL_STATS order)
+    summed about the shift c.  A centred sum of squares within 64 fp32 ulp of its raw sum is taken as the zero of a constant selection."""
+    S, Sy, Syy, n, Sh, Shh, Shy, A = (float(v) for v in sums)
+    c = float(np.float32(shift))
+    nan = float("nan")
+    out = {"n": n, "sse": S}
+    if n <= 0:
+        out.update({k: nan for k in ("mse", "rmse", "mae", "r2", "nse", "pearson", "kge", "pbkge", "beta", "alpha")})
+        return out
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ssy, ssh, shy = Syy - Sy * Sy / n, Shh - Sh * Sh / n, Shy - Sh * Sy / n
+        tiny = 64.0 * float(np.finfo(np.float32).eps)
+        ssy = 0.0 if ssy <= tiny * Syy else ssy
+        ssh = 0.0 if ssh <= tiny * Shh else ssh
+        f = np.float64
+        out["mse"] = S / n
+        out["rmse"] = float(np.sqrt(f(out["mse"])))
+        out["mae"] = A / n
+        out["r2"] = out["nse"] = float(1.0 - f(S) / f(ssy))
+        out["pearson"] = float(f(shy) / np.sqrt(f(ssh) * f(ssy))) if ssy > 0 and ssh > 0 else nan
+        out["alpha"] = float(np.sqrt(f(ssh) / f(ssy)))
+        out["beta"] = float((f(c) + f(Sh) / n) / (f(c) + f(Sy) / n))
+        p, al, be = out["pearson"], out["alpha"], out["beta"]
+        out["kge"] = float(1.0 - np.sqrt((p - 1) ** 2 + (al - 1) ** 2 + (be - 1) ** 2))
+        out["pbkge"] = float(1.0 - np.sqrt((p - 1) ** 2 + (be - 1) ** 2))
+    return out
+
+
+METRIC_KIND = {"mse": "mse", "rmse": "rmse", "mae": "mae", "r2": "r2", "nse": "nse", "pearson": "pearson", "kge": "kge", "pbkge": "pbkge",
+               "beta": "β", "alpha": "α"}      # eh_target_metrics field -> loss_fn kind
+
+
+def metrics_ref(yhat, y, mask):
+    """every eh_target_metrics field from loss_fn on yhat[mask], y[mask] in fp64 (n and sse included)"""
+    a, b = np.asarray(yhat, np.float64), np.asarray(y, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        out = {k: float(loss_fn(a, b, mask, kind)) for k, kind in METRIC_KIND.items()}
+    out["n"] = float(np.count_nonzero(mask))
+    out["sse"] = float(np.sum((a[mask] - b[mask]) ** 2))
+    return out
 
 
 def compute_loss(spec, theta, X, forcings, targets: Dict[str, np.ndarray], dtype=np.float64, kind="mse"):

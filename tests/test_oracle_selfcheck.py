@@ -12,6 +12,7 @@ import pytest
 from oracle import c_oracle as co
 from oracle import hybrid_oracle as ho
 from oracle import torch_twin as tt
+from tests import util
 
 CASES = [(a, s) for a in ("tanh", "sigmoid", "relu", "swish") for s in (False, True)]
 
@@ -380,3 +381,89 @@ def test_weight_l2_terms_gradient_matches_finite_differences():
     # the mean of the squared weights of ONE network: test/test_extract_weights.jl's relation, per network
     m = np.zeros(spec.n_theta, bool); m[:5 * 2] = True; m[5 * 2 + 5:5 * 2 + 5 + 3 * 5] = True; m[5 * 2 + 5 + 3 * 5 + 3:5 * 2 + 5 + 3 * 5 + 3 + 3] = True
     assert vals[0] == pytest.approx(0.3 * np.mean(theta[m] ** 2), rel=1e-12)
+
+
+# ---- eh_eval's host fold (oracle.metrics_from_sums restates it) against loss_fn: the closed forms on their own, edges included ------------
+def _fold_vs_loss_fn(yh, y, mask, shift, dtype=np.float64, tol=1e-9):
+    got = ho.metrics_from_sums(ho.eval_sums(yh, y, mask, shift, dtype), shift)
+    ref = ho.metrics_ref(yh, y, mask)
+    return util.metric_mismatches(got, ref, tol), got, ref
+
+
+@pytest.mark.parametrize("seed", range(4))
+@pytest.mark.parametrize("shift", ["mean", "first", 0.0, -3.25])
+def test_eval_fold_matches_loss_fn_on_random_data(seed, shift):
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(2, 3000))
+    y = (rng.standard_normal(n) * rng.uniform(0.1, 5) + rng.uniform(-10, 10)).astype(np.float32)
+    yh = (y + rng.standard_normal(n) * rng.uniform(0.01, 2) + rng.uniform(-1, 1)).astype(np.float32)
+    y[rng.random(n) < 0.2] = np.nan
+    mask = ~np.isnan(y)
+    c = {"mean": np.nanmean(y[:64]) if mask[:64].any() else 0.0, "first": y[mask][0]}.get(shift, shift)
+    bad, got, ref = _fold_vs_loss_fn(yh, y, mask, c)
+    assert not bad, bad
+    bad32, _, _ = _fold_vs_loss_fn(yh, y, mask, c, np.float32, tol=2e-4)          # the same fold from fp32 sums (the device's): rounding only
+    assert not bad32, bad32
+
+
+def _edge(name):
+    rng = np.random.default_rng(5)
+    y = (rng.standard_normal(200) + 4).astype(np.float32)
+    yh = (y + 0.3 * rng.standard_normal(200)).astype(np.float32)
+    mask = np.ones(200, bool)
+    if name == "n0":
+        mask[:] = False
+    elif name == "n1":
+        mask[:] = False; mask[17] = True
+    elif name == "n2":
+        mask[:] = False; mask[[3, 150]] = True
+    elif name == "const_y":
+        y[:] = np.float32(2.7)
+    elif name == "const_y_exact":                 # prediction = target = constant: r2 0/0
+        y[:] = np.float32(2.7); yh[:] = y
+    elif name == "const_yhat":
+        yh[:] = np.float32(-1.3)
+    elif name == "const_both":
+        y[:] = np.float32(2.7); yh[:] = np.float32(3.1)
+    elif name == "offset50":                      # mean / sd = 50 about a shift of 0
+        y = (rng.standard_normal(200) + 50).astype(np.float32); yh = (y + 0.3 * rng.standard_normal(200)).astype(np.float32)
+    elif name == "negative_means":
+        y = (rng.standard_normal(200) - 6).astype(np.float32); yh = (y + 0.5 + 0.3 * rng.standard_normal(200)).astype(np.float32)
+    elif name == "zero_mean_y":                   # beta = mean(yh) / 0
+        y = (y - np.float32(np.mean(y.astype(np.float64)))).astype(np.float32); y[0] -= np.float32(np.sum(y.astype(np.float64)))
+    return yh, y, mask
+
+
+EDGES = ["n0", "n1", "n2", "const_y", "const_y_exact", "const_yhat", "const_both", "offset50", "negative_means"]
+
+
+@pytest.mark.parametrize("edge", EDGES)
+@pytest.mark.parametrize("shift", [0.0, 2.7, 11.5, "first"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_eval_fold_edges_match_loss_fn(edge, shift, dtype):
+    """n = 0 (all NaN), n = 1 (r2 -Inf, pearson / alpha / kge NaN), a constant target (r2 -Inf, alpha Inf, pearson NaN) or prediction
+    (alpha 0, pearson NaN), a large offset about a zero shift, negative means (beta): loss_fn's values, its NaN and its infinities, from
+    sums in fp64 and from fp32 sums as the device forms them"""
+    yh, y, mask = _edge(edge)
+    c = (y[mask][0] if mask.any() else 0.0) if shift == "first" else shift
+    tol = 1e-9 if dtype == np.float64 else 1e-3          # (fp32 sums: the rounding of two samples or of an offset far from the shift)
+    bad, got, ref = _fold_vs_loss_fn(yh, y, mask, c, dtype, tol)
+    assert not bad, (bad, got, ref)
+    if edge == "n0":
+        assert got["n"] == 0 and all(np.isnan(got[k]) for k in util.METRICS if k != "sse")
+    if edge in ("n1", "const_y", "const_both"):
+        assert got["r2"] == -np.inf and np.isnan(got["pearson"]) and np.isnan(got["kge"])
+    if edge == "negative_means":
+        assert got["beta"] > 0 and got["beta"] == pytest.approx(np.mean(yh.astype(np.float64)) / np.mean(y.astype(np.float64)), rel=1e-6)
+
+
+def test_eval_fold_large_offset_needs_the_shift():
+    """mean / sd = 50: the fold is exact from exact sums at any shift; from fp32 sums about a zero shift r2 loses digits, about the
+    data's own mean it does not -- the reason eh_set_data takes the shift from the first valid targets"""
+    yh, y, mask = _edge("offset50")
+    ref = ho.metrics_ref(yh, y, mask)
+    far = ho.metrics_from_sums(ho.eval_sums(yh, y, mask, 0.0, np.float32), 0.0)
+    near_c = np.float32(np.mean(y[:64].astype(np.float64)))
+    near = ho.metrics_from_sums(ho.eval_sums(yh, y, mask, near_c, np.float32), near_c)
+    assert not util.metric_mismatches(near, ref, 5e-6)
+    assert abs(far["r2"] - ref["r2"]) > 10 * abs(near["r2"] - ref["r2"])

@@ -83,3 +83,28 @@ def rbq10_case(B, act="tanh", scale=False, nan_frac=0.0, seed=42, hidden=(16, 16
     X = (X / np.float32(50.0)).astype(np.float32)      # keep activations out of saturation for a sharp test
     theta = ho.init_theta(spec, theta_seed, np.float32)
     return spec, theta, X, f, y
+
+
+# ---- eh_eval's metrics against a reference set (tests/test_gpu_eval.py, tests/test_oracle_selfcheck.py) --------------------------------
+METRICS = ("mse", "rmse", "mae", "sse", "r2", "nse", "pearson", "kge", "pbkge", "alpha", "beta")
+REL_METRICS = ("mse", "rmse", "mae", "sse", "alpha", "beta")          # relative bars
+ABS_METRICS = ("r2", "nse", "pearson", "kge", "pbkge")                 # absolute bars (values near 0 or 1)
+
+
+def metric_mismatches(got, ref, rel, abs_=None, keys=METRICS):
+    """[(metric, got, ref)] of the metrics outside their bar, n exactly included.  abs_ = None: every metric relative to `rel` (floor
+    1e-12), the ABS_METRICS absolute to `rel`; abs_ given: pytest.approx(ref, rel=rel, abs=abs_) on every metric.  A non-finite reference
+    value must be matched exactly: NaN by NaN, an infinity by the same infinity."""
+    bad = []
+    if float(got["n"]) != float(ref["n"]):
+        bad.append(("n", got["n"], ref["n"]))
+    for k in keys:
+        g, r = float(got[k]), float(ref[k])
+        if not np.isfinite(r) or not np.isfinite(g):
+            if not ((np.isnan(r) and np.isnan(g)) or g == r):
+                bad.append((k, g, r))
+            continue
+        tol = max(rel * abs(r), abs_) if abs_ is not None else (rel if k in ABS_METRICS else max(rel * abs(r), 1e-12))
+        if abs(g - r) > tol:
+            bad.append((k, g, r))
+    return bad
