@@ -58,8 +58,26 @@ int flush_pending(eh_handle* h) {
     }
     return flush_one(h);
 }
+static EhOrd ord_args(const eh_handle* h, int slot, int prev_grid) {
+    EhOrd o{};
+    o.cnt = h->ord;
+    o.rows = reinterpret_cast<float*>(h->ord + 32 * EH_ORD_GROUPS);
+    o.grows = o.rows + (size_t)2 * EH_ORD_ROWS * h->ord_rs;
+    o.rs = h->ord_rs; o.soff = h->ord_soff; o.slot = slot; o.prev_grid = prev_grid;
+    return o;
+}
 static int flush_one(eh_handle* h) {
     const int nt = h->net.n_theta;
+    if (h->pend_ord) {        // an ordered step's sums: its rows and group rows (the step wrote slot h->cur ^ 1, which is what slot h->cur reads)
+        hipLaunchKernelGGL(eh_ord_flush_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, ord_args(h, h->cur, h->ord_grid), nt, TH(h), MM(h), VV(h),
+                           h->sc + 2 * h->sc_sel, h->sc + 2 * (h->sc_sel ^ 1), h->opt, h->pending_loss, h->img, h->net.loss);
+        HIPCHK(h, hipGetLastError());
+        h->sc_sel ^= 1;
+        h->pending = false;
+        h->pend_ord = false;
+        h->pending_loss = nullptr;
+        return EH_OK;
+    }
     const float* g_prev = h->gacc + (size_t)((h->gstep + 2) % 3) * EH_GSHARDS * h->n_acc;
     float* sc_in = h->sc + 2 * h->sc_sel;
     float* sc_out = h->sc + 2 * (h->sc_sel ^ 1);
@@ -399,6 +417,21 @@ static const EhSpecKernel* spec_lookup(const eh_handle* h) {
 }
 
 static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs* a) {
+    if (mode == EH_MODE_TRAIN_ORD) {
+        // the ordered step gives the bits of the step + reduce pair only on the kernel the pair's step runs: the kernel family EH_MODE_TRAIN
+        // picks below, or nothing (hipErrorNotSupported, nothing launched: the caller runs the pair).  A run-time compiled kernel is
+        // taken once the pair's first step has checked it (jit_verify).
+        if (const EhSpecKernel* sk = spec_lookup(h)) {
+            const hipError_t e = sk->launch(mode, grid, h->stream, &h->net, a);
+            if (e == hipSuccess) h->spec_used = sk; else (void)hipGetLastError();
+            return e;
+        }
+        if (jit_wanted(h, EH_MODE_TRAIN)) {
+            eh_handle_s::JitEntry* je = jit_entry(h);
+            if (je) return (je->verified && je->k.fn[EH_MODE_TRAIN_ORD]) ? eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a) : hipErrorNotSupported;
+        }
+        return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
+    }
     if (mode == EH_MODE_TRAIN_MULTI) {     // (built ahead of time only -- specialised for the canonical descriptors, generic otherwise; the caller checked: multi_ok)
         if (const EhSpecKernel* sk = spec_lookup(h)) {
             if (sk->launch(mode, grid, h->stream, &h->net, a) == hipSuccess) { h->spec_used = sk; return hipSuccess; }
@@ -760,6 +793,11 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     if (!lform) {             // (the fused-update accumulators: that mode exists for the per-wave kernels only)
         HIPCHK_C(hipMalloc(&h->gacc, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));      // (+4: the fused prologue reads five tail floats of every shard whatever T is)
         HIPCHK_C(hipMemset(h->gacc, 0, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));
+        h->ord_soff = (n.n_theta + 3) & ~3;
+        h->ord_rs = h->ord_soff + ((h->n_acc - n.n_theta + 3) & ~3);
+        const size_t ob = sizeof(unsigned) * 32 * EH_ORD_GROUPS + sizeof(float) * (size_t)2 * (EH_ORD_ROWS + EH_ORD_GROUPS) * h->ord_rs;
+        HIPCHK_C(hipMalloc(&h->ord, ob));
+        HIPCHK_C(hipMemset(h->ord, 0, ob));      // (the counters start at 0; every launch leaves them there)
     }
     tick("pset / bn / gacc");
     h->slab_rows = lform ? (int)EH_LFORM_ROWS : h->max_blocks;
@@ -847,7 +885,7 @@ int32_t eh_destroy(eh_handle* h) {
     eh_comm_release(h);             // communicator / local group / peer-to-peer mappings and buffers (eh_comm.hip)
     (void)hipSetDevice(h->device);
     (void)hipFree(h->pset);
-    (void)hipFree(h->gacc); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
+    (void)hipFree(h->gacc); (void)hipFree(h->ord); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
     (void)hipFree(h->prog); (void)hipFree(h->l2val); (void)hipFree(h->l2w); (void)hipFree(h->loss_hist); (void)hipFree(h->perm); (void)hipFree(h->out_buf); (void)hipFree(h->idx_buf);
     eval_host_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
@@ -1051,9 +1089,9 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
         HIPCHK(h, hipSetDevice(h->device));
         FLUSH(h);
         h->fused = value != 0;
-        // 2 = "where it is reproducible": one kernel per step only for minibatches ONE workgroup covers -- its sums meet in one fixed order
-        // (several steps per launch with the state in LDS, or one add per accumulator) -- and the deterministic step + reduce pair for
-        // every larger minibatch, whose workgroups' float atomics land in no fixed order.  What train() asks for when random_seed is set
+        // 2 = "where it is reproducible": the float-atomic one-kernel step only for minibatches ONE workgroup covers -- its sums meet in one
+        // fixed order (several steps per launch with the state in LDS, or one add per accumulator) -- and for every larger minibatch the
+        // ordered one-kernel step (EH_MODE_TRAIN_ORD, ord_ok) or, where that is not built, the deterministic step + reduce pair: the same bits.  What train() asks for when random_seed is set
         // (the reference's default, src/config/TrainingConfig.jl:85-86: a seeded CPU run IS reproducible).
         h->fused_det = value == 2;
         return EH_OK;
@@ -1984,7 +2022,9 @@ static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, 
 }
 
 // one fused kernel: prologue applies the previous step's update, epilogue accumulates this step's sums
-static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* loss_slot_for_this_step) {
+static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* loss_slot_for_this_step,
+                         bool ord = false, bool* launched = nullptr) {
+    if (h->pending && h->pend_ord != ord) FLUSH(h);      // (a pending update is applied by a step of its own kind only)
     const bool prof = h->prof && h->ev_used + 3 <= 3 * 8192;
     const bool burst_first = h->prof_k % h->prof_stride == 0, burst_last = h->prof_k % h->prof_stride == h->prof_stride - 1;
     if (prof) {
@@ -2012,9 +2052,23 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
     a.p2p_seq = h->p2p_on ? ++h->p2p_seq : 0u;
     if (int rc = bn_prepare(h, sp, idx, first, count, true, &a)) return rc;
     const int grid = grid_for(h, count);
-    HIPCHK(h, step_launch(h, h->p2p_on ? EH_MODE_TRAIN_P2P : EH_MODE_TRAIN, grid, &a));
-    h->cur ^= 1; h->sc_sel ^= 1; h->gstep++;
+    if (ord) {
+        a.ord = ord_args(h, h->cur, h->pending ? h->ord_grid : 0);
+        const hipError_t e = step_launch(h, EH_MODE_TRAIN_ORD, grid, &a);
+        if (e == hipErrorNotSupported) {          // (no such kernel for this handle: the caller runs the pair)
+            if (prof) h->prof_k--;
+            *launched = false;
+            return EH_OK;
+        }
+        HIPCHK(h, e);
+        *launched = true;
+        h->ord_grid = grid;
+    } else HIPCHK(h, step_launch(h, h->p2p_on ? EH_MODE_TRAIN_P2P : EH_MODE_TRAIN, grid, &a));
+    // (the ordered step leaves the accumulator rotation alone: gstep counts the steps that add into gacc)
+    h->cur ^= 1; h->sc_sel ^= 1;
+    if (!ord) h->gstep++;
     h->pending = true;
+    h->pend_ord = ord;
     h->pending_loss = loss_slot_for_this_step;
     if (prof && burst_last) {
         HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
@@ -2039,6 +2093,7 @@ static bool multi_ok(const eh_handle* h, long long batch) {
     return true;
 }
 static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long batch, long long end, int nsteps, float* loss_slots) {
+    if (h->pending && h->pend_ord) FLUSH(h);
     EhStepArgs a{};
     a.prog = h->prog;
     a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = std::min(batch, end - first);
@@ -2058,6 +2113,16 @@ static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long 
     h->pending = false;
     h->pending_loss = nullptr;
     return EH_OK;
+}
+
+// "fused_update" 2 on a minibatch of several workgroups: the ordered one-kernel step (EH_MODE_TRAIN_ORD) wherever "fused_update" 1 would be
+// allowed and the pair's reduce would run eh_reduce_kernel<true, 16> on slab rows the per-wave kernels wrote -- its bits are that pair's
+static bool ord_ok(const eh_handle* h, int grid) {
+    static const int cw_env = getenv("EH_REDUCE_CW") ? atoi(getenv("EH_REDUCE_CW")) : 0;      // (the A/B switch of do_step)
+    if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS) return false;
+    if (h->lform || h->arch->wide || h->p2p_on || h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
+    if (h->img.l2c != 0.0f || h->img.l2w || two_pass_mask(h->net) || h->dp_weights || h->dp_moments) return false;
+    return h->n_acc < 8192 && (cw_env == 0 || cw_env == 16);
 }
 
 static int ensure_events(eh_handle* h, size_t need) {
@@ -2612,9 +2677,17 @@ int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, i
     } else if ((rc = check_window(h, sp, first, count, "eh_train_step"))) return rc;
     rc = ensure_loss_hist(h, 1);
     if (rc) return rc;
-    if (h->fused && !(h->fused_det && grid_for(h, count) != 1)) {
+    const int grid = grid_for(h, count);
+    bool done = false;
+    if (h->fused && !(h->fused_det && grid != 1)) {
         rc = do_fused_step(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr);
         if (rc) return rc;
+        done = true;
+    } else if (ord_ok(h, grid)) {
+        rc = do_fused_step(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr, true, &done);
+        if (rc) return rc;
+    }
+    if (done) {
         if (loss_out) FLUSH(h);
     } else {
         FLUSH(h);                              // ("fused_update" 2: a one-workgroup step may be pending in front of this larger one)
@@ -2652,7 +2725,7 @@ int32_t eh_graph_begin(eh_handle* h) {
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
     if (h->fused && !h->pending) return fail(h, EH_ESTATE, "eh_graph_begin: fused_update mode: run one training step first (and do not synchronize before capturing)");
-    h->cap = {nullptr, h->fused, (int)(h->gstep % 3), h->cur, h->sc_sel};
+    h->cap = {nullptr, h->fused, (int)(h->gstep % 3), h->cur, h->sc_sel, h->pend_ord, h->pend_ord ? h->ord_grid : 0};
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_loss_hist(h, 1);
     if (rc) return rc;
@@ -2679,7 +2752,8 @@ int32_t eh_graph_end(eh_handle* h, int32_t* graph_id) {
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     if (e != hipSuccess) return fail(h, EH_EHIP, "eh_graph_end: hipGraphInstantiate: %s", hipGetErrorString(e));
-    if (h->fused != h->cap.fused || (int)(h->gstep % 3) != h->cap.gslot || h->cur != h->cap.cur || h->sc_sel != h->cap.sc_sel) {
+    if (h->fused != h->cap.fused || (int)(h->gstep % 3) != h->cap.gslot || h->cur != h->cap.cur || h->sc_sel != h->cap.sc_sel ||
+        h->pend_ord != h->cap.pend_ord || (h->pend_ord ? h->ord_grid : 0) != h->cap.ord_grid) {
         (void)hipGraphExecDestroy(ex);
         return fail(h, EH_EINVAL, "eh_graph_end: the recorded sequence does not bring the engine's rotation state back (record a multiple of 6 steps in fused_update mode, of 2 otherwise)");
     }
@@ -2693,7 +2767,8 @@ int32_t eh_graph_launch(eh_handle* h, int32_t graph_id) {
     if (!h) return EH_EINVAL;
     if (graph_id < 0 || graph_id >= (int32_t)h->graphs.size()) return fail(h, EH_EINVAL, "eh_graph_launch: graph %d", graph_id);
     const eh_handle::GraphRec& g = h->graphs[(size_t)graph_id];
-    if (g.fused != h->fused || g.gslot != (int)(h->gstep % 3) || g.cur != h->cur || g.sc_sel != h->sc_sel || (g.fused && !h->pending))
+    if (g.fused != h->fused || g.gslot != (int)(h->gstep % 3) || g.cur != h->cur || g.sc_sel != h->sc_sel || (g.fused && !h->pending) ||
+        g.pend_ord != h->pend_ord || g.ord_grid != (h->pend_ord ? h->ord_grid : 0))
         return fail(h, EH_ESTATE, "eh_graph_launch: the engine is not in the state the graph was recorded in (steps / synchronize in between: run steps until it is, with an update pending in fused_update mode)");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
@@ -2723,11 +2798,20 @@ int32_t eh_train_epoch(eh_handle* h, int64_t batchsize, uint64_t seed, int32_t s
     } else
     for (long long s = 0; s < steps; ++s) {
         const long long first = s * batchsize, count = std::min<long long>(batchsize, N - first);
-        const bool one_kernel = h->fused && !(h->fused_det && grid_for(h, count) != 1);      // ("fused_update" 2: only where one workgroup covers the minibatch)
-        if (!one_kernel) FLUSH(h);
-        rc = one_kernel ? do_fused_step(h, sp, shuffle ? h->perm : nullptr, first, count, h->loss_hist + s)
-                        : do_step(h, sp, shuffle ? h->perm : nullptr, first, count, true, false, h->loss_hist + s);
-        if (rc) return rc;
+        const int grid = grid_for(h, count);
+        // ("fused_update" 2: the float-atomic one-kernel step only where one workgroup covers the minibatch, the ordered one elsewhere)
+        const bool one_kernel = h->fused && !(h->fused_det && grid != 1);
+        bool done = false;
+        if (one_kernel) {
+            if ((rc = do_fused_step(h, sp, shuffle ? h->perm : nullptr, first, count, h->loss_hist + s))) return rc;
+            done = true;
+        } else if (ord_ok(h, grid)) {
+            if ((rc = do_fused_step(h, sp, shuffle ? h->perm : nullptr, first, count, h->loss_hist + s, true, &done))) return rc;
+        }
+        if (!done) {
+            FLUSH(h);
+            if ((rc = do_step(h, sp, shuffle ? h->perm : nullptr, first, count, true, false, h->loss_hist + s))) return rc;
+        }
     }
     if (mean_loss) FLUSH(h);
     if (n_steps) *n_steps = steps;

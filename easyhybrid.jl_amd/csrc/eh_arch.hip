@@ -17,7 +17,7 @@ struct Var {
     static constexpr size_t LDS_EVAL = sizeof(float) * Geom::TOTAL_FLOATS_EVAL;      // (forward / evaluation kernels: no hidden images, eh_device.hpp)
     static constexpr size_t LDS_EVAL_K1 = sizeof(float) * Geom::TOTAL_FLOATS_EVAL_K1;
     static constexpr bool HASPS = true;      // the P <= 4 kernels (FAST = 3) of every shape built with the fast paths
-    // the cross-GPU (EH_MODE_TRAIN_P2P) kernels are built for the default variant of a shape only
+    // the cross-GPU (EH_MODE_TRAIN_P2P) and the ordered fused-update (EH_MODE_TRAIN_ORD) kernels are built for the default variant of a shape only
 #ifdef EH_EXTRA_VARIANTS
     static constexpr bool HASP2P = NT == 2 && NW == 8;
 #else
@@ -39,6 +39,7 @@ struct Var {
         hipError_t e = prep1<ACT, EH_MODE_TRAIN, 0>();
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_EVAL, 0>();
         if constexpr (HASP2P) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_P2P, 0>(); }
+        if constexpr (HASP2P) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_ORD, 0>(); }
         if (e == hipSuccess) e = prepm<ACT, 0>();                     // several steps of one workgroup per launch (small minibatches)
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN, 4>();      // EH_MECH_PROGRAM kernels (no cross-GPU variant)
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_EVAL, 4>();
@@ -51,6 +52,8 @@ struct Var {
         if constexpr (HASP2P) {
             if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_P2P, 1>();
             if constexpr (HASPS) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_P2P, 3>(); }
+            if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_ORD, 1>();
+            if constexpr (HASPS) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_ORD, 3>(); }
         }
 #endif
         return e;
@@ -91,6 +94,16 @@ struct Var {
             }
             return;
         }
+        if (mode == EH_MODE_TRAIN_ORD) {
+            if constexpr (HASP2P) {
+#ifdef EH_FAST_PATHS
+                if constexpr (HASPS) { if (fast == 3) { EH_GO(EH_MODE_TRAIN_ORD, 3); return; } }
+                if (fast & 1) { EH_GO(EH_MODE_TRAIN_ORD, 1); return; }
+#endif
+                EH_GO(EH_MODE_TRAIN_ORD, 0);
+            }
+            return;
+        }
 #ifdef EH_FAST_PATHS
         if constexpr (HASPS) { if (mode == EH_MODE_TRAIN && fast == 3) { EH_GO(EH_MODE_TRAIN, 3); return; } }
         if (mode == EH_MODE_TRAIN && (fast & 1)) { EH_GO(EH_MODE_TRAIN, 1); return; }
@@ -100,9 +113,9 @@ struct Var {
     }
 #undef EH_GO
     static hipError_t launch(int mode, int act, int fast, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args) {
-        if (mode == EH_MODE_TRAIN_P2P && !HASP2P) return hipErrorNotSupported;
+        if ((mode == EH_MODE_TRAIN_P2P || mode == EH_MODE_TRAIN_ORD) && !HASP2P) return hipErrorNotSupported;
         if (fast == 3 && !HASPS) return hipErrorNotSupported;
-        if ((fast & 4) && (fast != 4 || mode == EH_MODE_TRAIN_P2P || mode == EH_MODE_TRAIN_MULTI)) return hipErrorNotSupported;
+        if ((fast & 4) && (fast != 4 || mode == EH_MODE_TRAIN_P2P || mode == EH_MODE_TRAIN_MULTI || mode == EH_MODE_TRAIN_ORD)) return hipErrorNotSupported;
         if (mode == EH_MODE_TRAIN_MULTI && (grid != 1 || LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc) > EH_LDS_LIMIT)) return hipErrorInvalidValue;
         switch (act) {
             case EH_ACT_TANH: go<EH_ACT_TANH>(mode, fast, grid, stream, net, args); break;

@@ -35,7 +35,8 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { EH_MODE_TRAIN = 0, EH_MODE_EVAL = 1, EH_MODE_TRAIN_P2P = 2, EH_MODE_TRAIN_MULTI = 3 };   // TRAIN_P2P: fused-update step that exchanges its sums with the peer GPUs itself (EhP2P)
+enum { EH_MODE_TRAIN = 0, EH_MODE_EVAL = 1, EH_MODE_TRAIN_P2P = 2, EH_MODE_TRAIN_MULTI = 3, EH_MODE_TRAIN_ORD = 4 };   // TRAIN_P2P: fused-update step that exchanges its sums with the peer GPUs itself (EhP2P)
+                                                                                                                 // TRAIN_ORD: fused-update step whose sums meet in the fixed order of the step + reduce pair (EhOrd)
 
 struct EhNet {
     int P, K, G, T, F;               // predictors, NN outputs (neural params), global params, targets, forcing columns
@@ -140,6 +141,96 @@ struct EhP2P {
                                          // workgroup 0 of the NEXT kernel on the stream (the next step, or the flush) folds and publishes in its prologue
 };
 
+// "Ordered" fused-update step (EH_MODE_TRAIN_ORD, "fused_update" 2 on minibatches of several workgroups): ONE kernel per step, and the
+// same bits as the deterministic step + eh_reduce_kernel<APPLY, 16> pair.  That reduce has 16 row groups: thread q of a column sums the
+// slab rows q, q + 16, q + 32, ... in ascending order from 0, and the column's total is the 16 partials summed in q order from 0.  Here
+// workgroup b stores its row write-through (sc1) into a row slot and takes a ticket on the counter of its group g = b % 16 (a 128-byte
+// line of its own); the workgroup whose add comes last in its group folds the group's rows in that same order into group row g.  The
+// next step's prologue sums the 16 group rows in order (absent groups: + 0, as the pair's idle row groups) and folds the rows' scalars
+// [S | n | Sy | Syy] with the reduce kernel's butterfly, then applies the update as the mode-1 prologue does.  Nobody waits for
+// anybody: no spin, no fence.  Two slots of each (parity `slot`): a fast workgroup of step s + 1 rewrites its row while a slow one
+// still reads step s's rows in its prologue; step s + 2 starts only once step s + 1 (every reader of step s's slot) has ended.
+enum { EH_ORD_GROUPS = 16, EH_ORD_ROWS = 256 };
+struct EhOrd {
+    float* rows;           // [2][EH_ORD_ROWS][rs]: one row per workgroup -- gradient at [0, n_theta), [S | n | Sy | Syy] at soff
+    float* grows;          // [2][EH_ORD_GROUPS][rs]: the group rows (gradient only)
+    unsigned* cnt;         // group g's ticket counter at cnt[32 g]; every group's last arriver sets it back to 0
+    int rs, soff;          // row stride and offset of the scalar block: multiples of 4 floats (16-byte loads of the scalars)
+    int slot;              // this step writes slot `slot`, its prologue reads slot `slot ^ 1`
+    int prev_grid;         // workgroups of the step whose sums are pending (the rows and groups to read)
+};
+__device__ __forceinline__ int eh_ord_pos(int e, int nth, int soff) { return e < nth ? e : soff + (e - nth); }
+// The scalars of the pending step's rows, folded as eh_reduce_kernel folds them: its thread r holds 0 + row r (0 where r >= the row
+// count), four wave butterflies (__shfl_xor 32 ... 1) over rows 0-63, 64-127, ..., then (w0 + w1) + (w2 + w3).  ONE wave does it here,
+// lane l holding rows l, l + 64, l + 128, l + 192: no LDS, no barrier.  eh_ord_scalar_loads issues the loads, eh_ord_scalar_fold folds.
+__device__ __forceinline__ void eh_ord_scalar_loads(const EhOrd& o, int lane, f32x4 (&v)[4]) {
+    const float* const R = o.rows + (long long)(o.slot ^ 1) * EH_ORD_ROWS * o.rs + o.soff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int r = lane + 64 * j;
+        v[j] = r < o.prev_grid ? *(const f32x4*)(R + (long long)r * o.rs) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+}
+__device__ __forceinline__ f32x4 eh_ord_scalar_fold(const EhOrd& o, int lane, const f32x4 (&v)[4]) {
+    float w[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float c = 0.0f;
+            if (lane + 64 * j < o.prev_grid) c += v[j][k];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+            w[j][k] = c;
+        }
+    f32x4 t;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = (w[0][k] + w[1][k]) + (w[2][k] + w[3][k]);
+    return t;                                        // {S, n, Sy, Syy}
+}
+// the pending step's gradient element idx: the 16 group rows in order from 0 (groups the step did not have: + 0)
+__device__ __forceinline__ void eh_ord_group_loads(const EhOrd& o, int idx, float (&g)[EH_ORD_GROUPS]) {
+    const float* const G = o.grows + (long long)(o.slot ^ 1) * EH_ORD_GROUPS * o.rs + idx;
+#pragma unroll
+    for (int k = 0; k < EH_ORD_GROUPS; ++k) g[k] = k < o.prev_grid ? G[(long long)k * o.rs] : 0.0f;
+}
+__device__ __forceinline__ float eh_ord_group_fold(const float (&g)[EH_ORD_GROUPS]) {
+    float t = 0.0f;
+#pragma unroll
+    for (int k = 0; k < EH_ORD_GROUPS; ++k) t += g[k];
+    return t;
+}
+// Called by every thread of every workgroup once its row is stored (write-through: __hip_atomic_store relaxed, agent scope).  The
+// hand-off: every storing wave drains its stores (s_waitcnt vmcnt(0)), a workgroup barrier, ONE lane adds to the group's counter (agent
+// scope); the workgroup whose add returns gsz - 1 reads the group's rows, every load an sc1 one (agent-scope relaxed atomic loads: they
+// bypass the CU's L1, which another CU's stores never refresh), behind a barrier that the adding wave joins.  No fence: the payload never
+// sits dirty in an L2.  The group row goes to the next kernel on the stream, whose start makes it visible.
+__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, float* flag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const unsigned gi = blockIdx.x % EH_ORD_GROUPS, gsz = (gridDim.x - gi + EH_ORD_GROUPS - 1) / EH_ORD_GROUPS;
+    if (tid == 0) {
+        unsigned* const gc = o.cnt + 32 * gi;
+        const bool last = __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsz - 1;
+        if (last) __hip_atomic_store(gc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        flag[0] = last ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    if (flag[0] == 0.0f) return;
+    const float* const R = o.rows + ((long long)o.slot * EH_ORD_ROWS + gi) * o.rs;
+    float* const Gr = o.grows + ((long long)o.slot * EH_ORD_GROUPS + gi) * o.rs;
+    for (int e = tid; e < nth; e += nthr) {
+        float v[EH_ORD_ROWS / EH_ORD_GROUPS];
+#pragma unroll
+        for (int k = 0; k < EH_ORD_ROWS / EH_ORD_GROUPS; ++k)
+            v[k] = (unsigned)k < gsz ? __hip_atomic_load(R + (long long)k * EH_ORD_GROUPS * o.rs + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+        float s = 0.0f;                              // (+ 0 for the rows past the group's end: the sum started at + 0 is never - 0, so x + 0 == x)
+#pragma unroll
+        for (int k = 0; k < EH_ORD_ROWS / EH_ORD_GROUPS; ++k) s += v[k];
+        __hip_atomic_store(Gr + e, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 struct EhFused {
     float* gacc;           // nullptr = two-kernel (deterministic) mode; else [3][EH_GSHARDS][n_acc] rotating accumulators
     float* pset;           // [2][3][n_theta] parameter sets {theta, m, v}, then [2][2] running beta products
@@ -193,6 +284,7 @@ struct EhStepArgs {
     long long ms_end;
     float* ms_loss;
     long long pf_first, pf_count;     // set by the multi-step kernel: the NEXT step's window (pf_count == 0: none) -- its records are fetched behind this step's compute
+    EhOrd ord;            // EH_MODE_TRAIN_ORD only
 };
 enum { EH_LPROG_WORDS = 24 + EH_MAX_PROG };
 
@@ -793,6 +885,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     constexpr int MT = G::MT, SR = G::SR, HP = G::HP, S0 = G::S0, SH = G::SH, NTHR = 64 * NW;
     constexpr bool TRAIN = MODE != EH_MODE_EVAL;
     constexpr bool P2PM = MODE == EH_MODE_TRAIN_P2P;      // its own instantiation: the single-GPU kernel carries none of this
+    constexpr bool ORDM = MODE == EH_MODE_TRAIN_ORD;      // (likewise: EhOrd)
     constexpr bool K1 = (FAST & 1) != 0, PS = (FAST & 2) != 0;
     constexpr bool PROG = (FAST & 4) != 0;                // EH_MECH_PROGRAM: the mechanistic stage interprets a.prog
     static_assert(!PROG || FAST == 4, "the program kernels are generic kernels");
@@ -932,6 +1025,14 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     const bool own_direct = deferred_upd && a.fz.pending && (!P2PM || px_mode == 1);
     float f_sv = 0.0f;      // lane 8 k + sh of every wave: scalar k of shard sh
     float f_gs[EH_GSHARDS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // this thread's element in the eight shards
+    float o_g[ORDM ? EH_ORD_GROUPS : 1];                  // EH_MODE_TRAIN_ORD: this thread's element in the 16 group rows ...
+    f32x4 o_sv[ORDM ? 4 : 1];                              // ... and (wave 0) the scalars of rows lane + 64 j
+    if constexpr (ORDM) {
+#pragma unroll
+        for (int k = 0; k < EH_ORD_GROUPS; ++k) o_g[k] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o_sv[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
     if (deferred_upd) {
         const EhFused& z = a.fz;
         const float* const g_prev = (P2PM ? px_stage : z.gacc) + ((z.gslot + 2) % 3) * (EH_GSHARDS * a.n_acc);
@@ -941,15 +1042,19 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         // loads are back (below, behind the image).  No branch on the target count: a uniform branch here split the prologue's single
         // memory round trip in two (+1.7 us per headline step on the kernels built ahead of time).  (Every thread used to load all forty
         // itself: 40 loads + their addresses in each of the workgroup's waves, ~0.6 us of a prologue that is bound by the instructions it issues.)
-        if (own_direct && lane < 40) f_sv = g_prev[(lane & 7) * a.n_acc + net.n_theta + (lane >> 3)];
+        if constexpr (ORDM) { if (own_direct && wave == 0) eh_ord_scalar_loads(a.ord, lane, o_sv); }
+        else { if (own_direct && lane < 40) f_sv = g_prev[(lane & 7) * a.n_acc + net.n_theta + (lane >> 3)]; }
         const float* const sc_in = z.pset + 6 * net.n_theta + 2 * z.sc_sel;
         f_bt1 = sc_in[0]; f_bt2 = sc_in[1];
         if (tid < net.n_theta) {
             f_th = pin[tid]; f_m = pin[net.n_theta + tid]; f_v = pin[2 * net.n_theta + tid];
             f_map = tid < net.g_off ? z.imap[tid] : 0;
             if (own_direct) {       // (folded below, behind the image: folded here, the loads' round trip would come before the image's)
+                if constexpr (ORDM) eh_ord_group_loads(a.ord, tid, o_g);
+                else {
 #pragma unroll
-                for (int sh = 0; sh < EH_GSHARDS; ++sh) f_gs[sh] = g_prev[sh * a.n_acc + tid];
+                    for (int sh = 0; sh < EH_GSHARDS; ++sh) f_gs[sh] = g_prev[sh * a.n_acc + tid];
+                }
             }
         }
     }
@@ -961,7 +1066,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     // (A first version dealt the world x (n_theta + 4) words round-robin over the threads and parked all of them in LDS: nine address
     //  computations per thread whatever the world, a table walk per rank, two barriers.)
     EH_STAMP_PRO(2);
-    float* const px_T = eh_px_table<P2PM>();
+    float* const px_T = eh_px_table<P2PM || ORDM>();      // (ORDM: the folded scalars [0..3], the publish flag [4])
     const int px_nmain = net.n_theta < NTHR ? net.n_theta : NTHR;
     // (written out rather than through eh_ll_issue / eh_ll_finish: what depends on the rank count only is a scalar branch per rank, so a
     //  small world pays for its own ranks and not for eight -- all waves of the workgroup run this code, and the prologue is bound by
@@ -1009,7 +1114,15 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         }
     }
     if (rec_pending) fetch_rec();
-    if (own_direct) {
+    if (ORDM && own_direct) {
+        if constexpr (ORDM) {
+            f_g = eh_ord_group_fold(o_g);
+            if (wave == 0) {           // (read by every thread behind the workgroup barrier in front of the update below)
+                const f32x4 t = eh_ord_scalar_fold(a.ord, lane, o_sv);
+                if (lane == 0) *(f32x4*)px_T = t;
+            }
+        }
+    } else if (own_direct) {
         f_g = eh_fold8(f_gs[0], f_gs[1], f_gs[2], f_gs[3], f_gs[4], f_gs[5], f_gs[6], f_gs[7]);
         const int svi = __builtin_bit_cast(int, eh_fold8_lanes(f_sv));
         const float S0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(svi, 0)), S1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(svi, 8)),
@@ -1181,6 +1294,9 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         float* const g_zero = (P2PM ? const_cast<float*>(px_stage) : z.gacc) + ((z.gslot + 1) % 3) * (EH_GSHARDS * a.n_acc);
         const float* const pin = z.pset + z.cur * 3 * nth;
         float* const pout = z.pset + (z.cur ^ 1) * 3 * nth;
+        if constexpr (ORDM) {
+            if (own_direct) { const f32x4 t = *(const f32x4*)px_T; f_sse = t[0]; f_cnt = t[1]; f_sy = t[2]; f_syy = t[3]; }
+        }
         const bool upd = z.pending && f_cnt > 0.0f;
         float inv = 0.0f, lossv = __builtin_nanf("");
         if (upd) {
@@ -1214,6 +1330,10 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                         eh_ll_finish(&a.p2pv, ad, a.p2p_seq - 1u, w8, got);
 #pragma unroll
                         for (int sh = 0; sh < EH_GSHARDS; ++sh) gs += (px_mode == 1 && sh == px_rank) ? own : got[sh];      // (rank order on every rank)
+                    } else if constexpr (ORDM) {
+                        float gg[EH_ORD_GROUPS];
+                        eh_ord_group_loads(a.ord, idx, gg);
+                        gs = eh_ord_group_fold(gg);
                     } else {
                         const float* const gq = g_prev + idx;
                         gs = eh_fold8(gq[0], gq[a.n_acc], gq[2 * a.n_acc], gq[3 * a.n_acc], gq[4 * a.n_acc], gq[5 * a.n_acc], gq[6 * a.n_acc], gq[7 * a.n_acc]);
@@ -1236,9 +1356,10 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             float* const sc_out = z.pset + 6 * nth + 2 * (z.sc_sel ^ 1);
             sc_out[0] = upd ? f_bt1 * z.opt.b1 : f_bt1;
             sc_out[1] = upd ? f_bt2 * z.opt.b2 : f_bt2;
-            if (z.loss_slot && z.pending) *z.loss_slot = lossv;
+            if (z.loss_slot && z.pending) *z.loss_slot = (ORDM && upd) ? lossv + 0.0f : lossv;      // (ORDM: as eh_reduce_kernel, which adds its extra-loss term 0)
         }
-        for (int e = blockIdx.x * NTHR + tid; e < EH_GSHARDS * a.n_acc; e += gridDim.x * NTHR) g_zero[e] = 0.0f;
+        if constexpr (!ORDM)       // (ORDM: the shards take no adds)
+            for (int e = blockIdx.x * NTHR + tid; e < EH_GSHARDS * a.n_acc; e += gridDim.x * NTHR) g_zero[e] = 0.0f;
         __syncthreads();
     }
     EH_STAMP(1);
@@ -1846,8 +1967,8 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         __syncthreads();
         EH_STAMP(9);
         const float* const R0 = smem + G::IMG_FLOATS;
-        float* const out = a.slab + (long long)blockIdx.x * a.n_acc;
-        float* const gsh = a.fz.gacc ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
+        float* const out = ORDM ? a.ord.rows + ((long long)a.ord.slot * EH_ORD_ROWS + blockIdx.x) * a.ord.rs : a.slab + (long long)blockIdx.x * a.n_acc;
+        float* const gsh = (!ORDM && a.fz.gacc) ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
         for (int e = tid; e < a.n_acc; e += NTHR) {
             const int code = e == tid ? f_rcode : a.rmap[e], pos = code & 0xFFFFFF, nlan = code >> 24;
             float sum = 0.0f;
@@ -1877,10 +1998,12 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll 1
                 for (int w = 0; w < nlive; ++w) sum += R0[w * AL.rw + pos];
             }
-            if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[e] = sum; else atomicAdd(&gsh[e], sum); }      // (ms_direct: one workgroup, one writer per element)
+            if constexpr (ORDM) __hip_atomic_store(out + eh_ord_pos(e, net.n_theta, a.ord.soff), sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (write-through)
+            else if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[e] = sum; else atomicAdd(&gsh[e], sum); }      // (ms_direct: one workgroup, one writer per element)
             else out[e] = sum;
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);
@@ -1940,8 +2063,12 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         EH_STAMP(13);
         float* const R = smem + G::IMG_FLOATS + wave * G::WAVE_WS;
         const float* const R0 = smem + G::IMG_FLOATS;
-        float* const out = a.slab + (long long)blockIdx.x * a.n_acc;
-        float* const gsh = a.fz.gacc ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
+        float* const out = ORDM ? a.ord.rows + ((long long)a.ord.slot * EH_ORD_ROWS + blockIdx.x) * a.ord.rs : a.slab + (long long)blockIdx.x * a.n_acc;
+        float* const gsh = (!ORDM && a.fz.gacc) ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
+        auto put_out = [&](int e, float v) {
+            if constexpr (ORDM) __hip_atomic_store(out + eh_ord_pos(e, net.n_theta, a.ord.soff), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (write-through)
+            else out[e] = v;
+        };
 #pragma unroll
         for (int rd = 0; rd < NR; ++rd) {
             __syncthreads();                       // the wave workspaces are dead / the previous round has been gathered
@@ -1983,15 +2110,16 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                 for (int u = 0; u < NU; ++u)
                     if (dst[u] >= 0) {
                         if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[dst[u]] = sumv[u]; else atomicAdd(&gsh[dst[u]], sumv[u]); }
-                        else out[dst[u]] = sumv[u];
+                        else put_out(dst[u], sumv[u]);
                     }
                 if (dtail >= 0) {
                     if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[dtail] = sumt; else atomicAdd(&gsh[dtail], sumt); }
-                    else out[dtail] = sumt;
+                    else put_out(dtail, sumt);
                 }
             }
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);

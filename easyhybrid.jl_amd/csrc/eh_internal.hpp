@@ -94,6 +94,11 @@ struct eh_handle_s {
     // fused-update mode
     bool fused = false, pending = false, fused_det = false;   // fused_det ("fused_update" 2): one kernel per step only where one workgroup covers the minibatch
     float* gacc = nullptr;          // [3][EH_GSHARDS][n_acc] rotating gradient accumulators
+    // ordered fused-update step (EH_MODE_TRAIN_ORD: "fused_update" 2 on minibatches of several workgroups; EhOrd, eh_device.hpp)
+    unsigned* ord = nullptr;        // one allocation: the 16 group counters (2 KB), then rows [2][256][ord_rs], then group rows [2][16][ord_rs]
+    int ord_rs = 0, ord_soff = 0;
+    bool pend_ord = false;          // the pending update is an ordered step's (its sums in the row slots, not in gacc)
+    int ord_grid = 0;               // workgroups of that step
     // cross-GPU exchange (EhP2P): an uncached, IPC-exported receive buffer of {value, sequence} words next to gacc
     bool p2p_on = false, p2p_alloc = false;
     unsigned long long* p2p_recv = nullptr;
@@ -171,7 +176,7 @@ struct eh_handle_s {
     float* l2val = nullptr;         // lambda * weight_l2 of the current parameters (device scalar)
     float* l2w = nullptr;           // eh_set_weight_l2_coef: one coefficient per canonical entry (device)
     int n_weights = 0;
-    struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; };
+    struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; bool pend_ord; int ord_grid; };
     std::vector<GraphRec> graphs;         // eh_graph_*: captured step sequences + the rotation state they start (and must end) in
     bool capturing = false;
     GraphRec cap{};

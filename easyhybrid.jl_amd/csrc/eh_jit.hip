@@ -362,12 +362,13 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     hiprtcProgram hp = nullptr;
     if (hiprtcCreateProgram(&hp, src.c_str(), "eh_jit.hip", nh, hsrc, hnames) != HIPRTC_SUCCESS) { *log = "hiprtcCreateProgram failed"; return false; }
     // which kernels: train + eval, the cross-GPU train kernel when asked for, and -- per-wave family, registry model with its descriptor
-    // baked in, one target -- the multi-step train kernel (several one-workgroup steps per launch, eh_device.hpp EH_MODE_TRAIN_MULTI)
-    int modes[4], nmode = 0;
+    // baked in, one target -- the multi-step train kernel (several one-workgroup steps per launch, eh_device.hpp EH_MODE_TRAIN_MULTI) and
+    // the ordered fused-update step (EH_MODE_TRAIN_ORD)
+    int modes[5], nmode = 0;
     modes[nmode++] = EH_MODE_TRAIN; modes[nmode++] = EH_MODE_EVAL;
     if (with_p2p && !A->wide && !prog) modes[nmode++] = EH_MODE_TRAIN_P2P;
-    if (!A->wide && !prog && !loss && !rowact && spec && spec->T == 1 && !(fast & 4)) modes[nmode++] = EH_MODE_TRAIN_MULTI;
-    char name[4][160];
+    if (!A->wide && !prog && !loss && !rowact && spec && spec->T == 1 && !(fast & 4)) { modes[nmode++] = EH_MODE_TRAIN_MULTI; modes[nmode++] = EH_MODE_TRAIN_ORD; }
+    char name[5][160];
     for (int i = 0; i < nmode; ++i) {
         const int m = modes[i];
         if (A->wide && V.so && m == EH_MODE_TRAIN) snprintf(name[i], sizeof name[i], "eh_bfs_kernel<%d, %d, %d, %d, %d, %s, %d>", A->nbi, A->nbh, A->nl, V.nw, act, prog ? "true" : "false", V.bf16 == 2 ? 1 : 3);
@@ -481,7 +482,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
 
 hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args) {
     void* params[] = {const_cast<EhNet*>(net), const_cast<EhStepArgs*>(args)};
-    if (mode < 0 || mode > 3 || !k->fn[mode]) return hipErrorNotSupported;
+    if (mode < 0 || mode > 4 || !k->fn[mode]) return hipErrorNotSupported;
     if (mode == EH_MODE_TRAIN_MULTI) {      // one workgroup; its step-to-step state sits in LDS behind the work space
         const size_t lds_ms = k->lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc);
         if (grid != 1 || lds_ms > EH_LDS_LIMIT) return hipErrorInvalidValue;
@@ -493,5 +494,5 @@ hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t s
 
 void eh_jit_release(EhJitKernel* k) {
     if (k->mod) (void)hipModuleUnload(k->mod);
-    k->mod = nullptr; k->fn[0] = k->fn[1] = k->fn[2] = k->fn[3] = nullptr;
+    k->mod = nullptr; k->fn[0] = k->fn[1] = k->fn[2] = k->fn[3] = k->fn[4] = nullptr;
 }

@@ -11,7 +11,8 @@
 
 struct EhJitKernel {
     hipModule_t mod = nullptr;
-    hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};   // EH_MODE_TRAIN, EH_MODE_EVAL, EH_MODE_TRAIN_P2P (when asked for), EH_MODE_TRAIN_MULTI (per-wave registry models with one target)
+    hipFunction_t fn[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // EH_MODE_TRAIN, EH_MODE_EVAL, EH_MODE_TRAIN_P2P (when asked for), EH_MODE_TRAIN_MULTI and
+                                                                           // EH_MODE_TRAIN_ORD (per-wave registry models with one target)
     int nw = 0;
     size_t lds_bytes = 0;
     size_t lds_eval_bytes = 0;      // forward / evaluation kernel (0: lds_bytes)

@@ -586,6 +586,38 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
     }
 }
 
+// ordered fused-update mode (EhOrd, eh_device.hpp): apply the still-pending step in place -- the 16 group rows in order, the rows'
+// scalars by the reduce kernel's butterfly (every wave folds them itself), then the update as eh_reduce_kernel<true, 16> makes it
+__global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_theta, float* theta, float* m, float* v, const float* sc_in, float* sc_out,
+                                                           EhOpt op, float* loss_slot, EhImg im, int loss_kind) {
+    const int idx = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool own = idx < n_theta;
+    float gv[EH_ORD_GROUPS];
+    f32x4 sv[4];
+    eh_ord_group_loads(o, own ? idx : 0, gv);
+    eh_ord_scalar_loads(o, lane, sv);
+    float th = 0.0f, mm = 0.0f, vv = 0.0f;
+    int mp = -1;
+    if (own) { th = theta[idx]; mm = m[idx]; vv = v[idx]; if (idx < im.g_off && im.imap) mp = im.imap[idx]; }
+    const float bt1 = sc_in[0], bt2 = sc_in[1];
+    const f32x4 t = eh_ord_scalar_fold(o, lane, sv);
+    float inv = 1.0f, lossv = 0.0f;
+    eh_loss_finish(loss_kind, t[0], t[1], t[2], t[3], inv, lossv, im.agg_a);
+    const bool upd = t[1] > 0.0f;
+    if (own && upd) {
+        eh_opt_update(op, eh_ord_group_fold(gv) * inv, bt1, bt2, th, mm, vv);
+        theta[idx] = th; m[idx] = mm; v[idx] = vv;
+    }
+    if (own) {
+        if (idx < im.g_off) { if (mp >= 0) im.image[mp] = th; }
+        else eh_image_store(im, idx, th);
+    }
+    if (idx == 0) {
+        sc_out[0] = upd ? bt1 * op.b1 : bt1;
+        sc_out[1] = upd ? bt2 * op.b2 : bt2;
+        if (loss_slot) *loss_slot = upd ? lossv + 0.0f : __builtin_nanf("");
+    }
+}
 
 // Moment-based training losses (pearsonLoss, kgeLoss, pbkgeLoss; src/losses/loss_fn.jl:75-77,105-174): from the batch
 // moments the forward-only pass left in the slab ([blocks][EH_EVAL_STATS], shifted by c) to the loss value and the
