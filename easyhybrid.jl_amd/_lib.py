@@ -11,6 +11,7 @@ import os
 
 EH_MAX_HIDDEN, EH_MAX_PARAMS, EH_MAX_FORC, EH_MAX_TARG, EH_MAX_NETS = 8, 8, 4, 4, 8
 EH_MAX_PROG, EH_MAX_PROG_CONST, EH_MAX_PROG_OUT = 64, 16, 3
+EH_MAX_OPT_GROUPS = 16
 EH_MECH_PROGRAM = 6
 EH_LOSS_PROGRAM = 7
 EH_OK, EH_EINVAL, EH_EHIP, EH_ENOMEM, EH_EUNSUPPORTED, EH_ESTATE, EH_ERCCL = 0, -1, -2, -3, -4, -5, -6
@@ -77,6 +78,9 @@ SIGNATURES = {
     "eh_opt_init": (C.c_int32, [_H, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "eh_get_opt_state": (C.c_int32, [_H, _F, _F, C.c_int64, _F]),
     "eh_set_opt_state": (C.c_int32, [_H, _F, _F, C.c_int64, _F]),
+    "eh_opt_init_groups": (C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F]),
+    "eh_get_opt_beta_t": (C.c_int32, [_H, _F, C.c_int32]),
+    "eh_set_opt_beta_t": (C.c_int32, [_H, _F, C.c_int32]),
     "eh_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_int64]),
     "eh_comm_init": (C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "eh_comm_init_local": (C.c_int32, [C.POINTER(_H), C.c_int32]),

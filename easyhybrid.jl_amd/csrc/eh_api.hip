@@ -773,9 +773,9 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         HIPCHK_C(hipMemcpy(h->prog, pb.data(), pb.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     }
     const size_t nt = (size_t)n.n_theta;
-    // one allocation: [2][3][n_theta] parameter sets {theta, m, v}, then the [2][2] running beta products
-    HIPCHK_C(hipMalloc(&h->pset, (6 * nt + 4) * sizeof(float)));
-    HIPCHK_C(hipMemset(h->pset, 0, (6 * nt + 4) * sizeof(float)));
+    // one allocation: [2][3][n_theta] parameter sets {theta, m, v}, then the [EH_MAX_OPT_GROUPS][2][2] running beta products (EhOptTab)
+    HIPCHK_C(hipMalloc(&h->pset, (6 * nt + 4 * EH_MAX_OPT_GROUPS) * sizeof(float)));
+    HIPCHK_C(hipMemset(h->pset, 0, (6 * nt + 4 * EH_MAX_OPT_GROUPS) * sizeof(float)));
     for (int k = 0; k < 2; ++k) { h->thb[k] = h->pset + (size_t)k * 3 * nt; h->mb[k] = h->thb[k] + nt; h->vb[k] = h->thb[k] + 2 * nt; }
     h->sc = h->pset + 6 * nt;
     h->bn_on = d->input_batchnorm != 0;
@@ -884,7 +884,7 @@ int32_t eh_destroy(eh_handle* h) {
     for (auto& e : h->jit) { if (e->worker.joinable()) e->worker.join(); eh_jit_release(&e->k); }
     eh_comm_release(h);             // communicator / local group / peer-to-peer mappings and buffers (eh_comm.hip)
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->pset);
+    (void)hipFree(h->pset); (void)hipFree(h->opt_tab);
     (void)hipFree(h->gacc); (void)hipFree(h->ord); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
     (void)hipFree(h->prog); (void)hipFree(h->l2val); (void)hipFree(h->l2w); (void)hipFree(h->loss_hist); (void)hipFree(h->perm); (void)hipFree(h->out_buf); (void)hipFree(h->idx_buf);
     eval_host_release(h);
@@ -2084,7 +2084,7 @@ static bool multi_ok(const eh_handle* h, long long batch) {
     if (!h->fused || !h->multi_step || h->lform || h->arch->wide || h->p2p_on || h->prof || h->capturing) return false;
     if (h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->bn_on && (h->bn_ext || h->bn_no_self || batch > EH_BN_SELF_MAX)) return false;
-    if (h->arch->var[h->variant].lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(h->net.n_theta, h->n_acc) > EH_LDS_LIMIT) return false;
+    if (h->arch->var[h->variant].lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(h->net.n_theta, h->n_acc, h->opt.tab != nullptr) > EH_LDS_LIMIT) return false;
     if (grid_for(h, batch) != 1) return false;
     if (!spec_lookup(h) && jit_wanted(h, EH_MODE_TRAIN)) {      // a model on kernels compiled at run time: its multi-step kernel, or one launch per step
         eh_handle_s::JitEntry* je = jit_entry(const_cast<eh_handle*>(h));      // (a compiled single-step kernel beats the GENERIC multi-step one: 7.4 against 9.0 us)
@@ -2608,7 +2608,8 @@ int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float bet
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->opt = EhOpt{rule, lr, beta1, beta2, eps, weight_decay};
+    h->opt = EhOpt{rule, lr, beta1, beta2, eps, weight_decay, nullptr};
+    h->opt_groups = 1;
     const size_t nt = (size_t)h->net.n_theta;
     HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
     HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
@@ -2616,6 +2617,71 @@ int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float bet
     HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
     h->sc_sel = 0;
     h->opt_ready = true;
+    return EH_OK;
+}
+
+int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, int32_t n_groups, const int32_t* rule, const float* hyper) {
+    if (!h) return EH_EINVAL;
+    if (!group || !rule || !hyper) return fail(h, EH_EINVAL, "eh_opt_init_groups: null table");
+    if (n_theta != h->net.n_theta) return fail(h, EH_EINVAL, "eh_opt_init_groups: n_theta %lld, the model has %d", (long long)n_theta, h->net.n_theta);
+    if (n_groups > EH_MAX_OPT_GROUPS) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_groups: %d groups (at most %d)", n_groups, EH_MAX_OPT_GROUPS);
+    if (n_groups < 1) return fail(h, EH_EINVAL, "eh_opt_init_groups: %d groups", n_groups);
+    for (int k = 0; k < n_groups; ++k)
+        if (rule[k] < EH_OPT_ADAM || rule[k] > EH_OPT_DESCENT) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_groups: group %d: unknown rule %d", k, rule[k]);
+    const size_t nt = (size_t)n_theta;
+    for (size_t i = 0; i < nt; ++i)
+        if (group[i] >= n_groups) return fail(h, EH_EINVAL, "eh_opt_init_groups: element %zu in group %d of %d", i, (int)group[i], n_groups);
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t tab_bytes = offsetof(EhOptTab, gid) + ((nt + 3) & ~(size_t)3);
+    std::vector<unsigned char> host(tab_bytes, 0);
+    EhOptTab* const t = reinterpret_cast<EhOptTab*>(host.data());
+    for (int k = 0; k < n_groups; ++k) {
+        const float* hp = hyper + 5 * k;
+        t->r[k] = EhOpt{rule[k], hp[0], hp[1], hp[2], hp[3], hp[4], nullptr};
+    }
+    t->n = n_groups;
+    memcpy(host.data() + offsetof(EhOptTab, gid), group, nt);
+    if (!h->opt_tab) HIPCHK(h, hipMalloc(&h->opt_tab, tab_bytes));       // (n_theta is fixed for the handle's life)
+    HIPCHK(h, hipMemcpy(h->opt_tab, host.data(), tab_bytes, hipMemcpyHostToDevice));
+    // (the handle's own rule names Adam, so every site moves m and v; its hyper-parameters are group 0's -- the table is what is read)
+    h->opt = EhOpt{EH_OPT_ADAM, t->r[0].lr, t->r[0].b1, t->r[0].b2, t->r[0].eps, t->r[0].wd, h->opt_tab};
+    h->opt_groups = n_groups;
+    HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
+    HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
+    float sc[4 * EH_MAX_OPT_GROUPS] = {};
+    for (int k = 0; k < n_groups; ++k) {       // group k, set s at [4 k + 2 s]; Optimisers.jl starts each product at beta (t = 1)
+        sc[4 * k] = sc[4 * k + 2] = hyper[5 * k + 1];
+        sc[4 * k + 1] = sc[4 * k + 3] = hyper[5 * k + 2];
+    }
+    HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
+    h->sc_sel = 0;
+    h->opt_ready = true;
+    return EH_OK;
+}
+
+int32_t eh_get_opt_beta_t(eh_handle* h, float* bt, int32_t n_groups) {
+    if (!h || !bt) return EH_EINVAL;
+    if (n_groups != h->opt_groups) return fail(h, EH_EINVAL, "eh_get_opt_beta_t: %d groups, the handle has %d", n_groups, h->opt_groups);
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float sc[4 * EH_MAX_OPT_GROUPS];
+    HIPCHK(h, hipMemcpy(sc, h->sc, sizeof sc, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n_groups; ++k) { bt[2 * k] = sc[4 * k + 2 * h->sc_sel]; bt[2 * k + 1] = sc[4 * k + 2 * h->sc_sel + 1]; }
+    return EH_OK;
+}
+
+int32_t eh_set_opt_beta_t(eh_handle* h, const float* bt, int32_t n_groups) {
+    if (!h || !bt) return EH_EINVAL;
+    if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_set_opt_beta_t: call eh_opt_init or eh_opt_init_groups first");
+    if (n_groups != h->opt_groups) return fail(h, EH_EINVAL, "eh_set_opt_beta_t: %d groups, the handle has %d", n_groups, h->opt_groups);
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < n_groups; ++k)
+        HIPCHK(h, hipMemcpy(h->sc + 4 * k + 2 * h->sc_sel, bt + 2 * k, 2 * sizeof(float), hipMemcpyHostToDevice));
     return EH_OK;
 }
 
@@ -2725,7 +2791,7 @@ int32_t eh_graph_begin(eh_handle* h) {
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
     if (h->fused && !h->pending) return fail(h, EH_ESTATE, "eh_graph_begin: fused_update mode: run one training step first (and do not synchronize before capturing)");
-    h->cap = {nullptr, h->fused, (int)(h->gstep % 3), h->cur, h->sc_sel, h->pend_ord, h->pend_ord ? h->ord_grid : 0};
+    h->cap = {nullptr, h->fused, (int)(h->gstep % 3), h->cur, h->sc_sel, h->pend_ord, h->pend_ord ? h->ord_grid : 0, h->opt.tab != nullptr};
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_loss_hist(h, 1);
     if (rc) return rc;
@@ -2753,7 +2819,7 @@ int32_t eh_graph_end(eh_handle* h, int32_t* graph_id) {
     (void)hipGraphDestroy(g);
     if (e != hipSuccess) return fail(h, EH_EHIP, "eh_graph_end: hipGraphInstantiate: %s", hipGetErrorString(e));
     if (h->fused != h->cap.fused || (int)(h->gstep % 3) != h->cap.gslot || h->cur != h->cap.cur || h->sc_sel != h->cap.sc_sel ||
-        h->pend_ord != h->cap.pend_ord || (h->pend_ord ? h->ord_grid : 0) != h->cap.ord_grid) {
+        h->pend_ord != h->cap.pend_ord || (h->pend_ord ? h->ord_grid : 0) != h->cap.ord_grid || (h->opt.tab != nullptr) != h->cap.grouped) {
         (void)hipGraphExecDestroy(ex);
         return fail(h, EH_EINVAL, "eh_graph_end: the recorded sequence does not bring the engine's rotation state back (record a multiple of 6 steps in fused_update mode, of 2 otherwise)");
     }
@@ -2770,6 +2836,10 @@ int32_t eh_graph_launch(eh_handle* h, int32_t graph_id) {
     if (g.fused != h->fused || g.gslot != (int)(h->gstep % 3) || g.cur != h->cur || g.sc_sel != h->sc_sel || (g.fused && !h->pending) ||
         g.pend_ord != h->pend_ord || g.ord_grid != (h->pend_ord ? h->ord_grid : 0))
         return fail(h, EH_ESTATE, "eh_graph_launch: the engine is not in the state the graph was recorded in (steps / synchronize in between: run steps until it is, with an update pending in fused_update mode)");
+    // (the recorded kernels carry the optimiser by value: one rule, or the per-branch table -- whose contents may change, its address does not)
+    if (g.grouped != (h->opt.tab != nullptr))
+        return fail(h, EH_ESTATE, "eh_graph_launch: the graph was recorded with %s, the engine now has %s (eh_opt_init / eh_opt_init_groups)",
+                    g.grouped ? "per-branch optimiser rules" : "one optimiser rule", g.grouped ? "one rule" : "per-branch rules");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
     return EH_OK;

@@ -74,7 +74,7 @@ struct Var {
             return;
         }
         if (mode == EH_MODE_TRAIN_MULTI) {
-            const size_t lds_ms = LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc);
+            const size_t lds_ms = LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, args->fz.opt.tab != nullptr);
 #define EH_GOM(FAST) hipLaunchKernelGGL((eh_step_kernel<EH_NBI, EH_NBH, EH_NL, NT, NW, ACT, EH_MODE_TRAIN_MULTI, FAST>), dim3(1), dim3(64 * NW), lds_ms, stream, *net, *args)
 #ifdef EH_FAST_PATHS
             if constexpr (HASPS) { if (fast == 3) { EH_GOM(3); return; } }
@@ -116,7 +116,7 @@ struct Var {
         if ((mode == EH_MODE_TRAIN_P2P || mode == EH_MODE_TRAIN_ORD) && !HASP2P) return hipErrorNotSupported;
         if (fast == 3 && !HASPS) return hipErrorNotSupported;
         if ((fast & 4) && (fast != 4 || mode == EH_MODE_TRAIN_P2P || mode == EH_MODE_TRAIN_MULTI || mode == EH_MODE_TRAIN_ORD)) return hipErrorNotSupported;
-        if (mode == EH_MODE_TRAIN_MULTI && (grid != 1 || LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc) > EH_LDS_LIMIT)) return hipErrorInvalidValue;
+        if (mode == EH_MODE_TRAIN_MULTI && (grid != 1 || LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, args->fz.opt.tab != nullptr) > EH_LDS_LIMIT)) return hipErrorInvalidValue;
         switch (act) {
             case EH_ACT_TANH: go<EH_ACT_TANH>(mode, fast, grid, stream, net, args); break;
             case EH_ACT_SIGMOID: go<EH_ACT_SIGMOID>(mode, fast, grid, stream, net, args); break;

@@ -67,9 +67,21 @@ enum { EH_TT = 8 };
 // which keeps them out of the scalar register file during the tile loop.
 enum { EH_IMG_PHI = 0, EH_IMG_DPHI = 8, EH_IMG_LO = 16, EH_IMG_SC = 24, EH_IMG_WOFF = 32, EH_IMG_BOFF = 37, EH_IMG_WIDTH = 42, EH_IMG_GPAR = 48, EH_IMG_BNM = 56, EH_IMG_BNR = 88, EH_IMG_META = 120 };
 
+struct EhOptTab;
 struct EhOpt {
     int rule;
     float lr, b1, b2, eps, wd;
+    const EhOptTab* tab;     // nullptr: this one rule for every element; else one rule per group of elements (eh_opt_init_groups)
+};
+// Per-branch rules (TrainConfig.opt as a NamedTuple, src/training/train.jl:78-93): element i of flat theta follows r[gid[i]] and that
+// group's running products.  The products of group k, parameter set s, live at [4 k + 2 s] behind the parameter sets, so sc_in / sc_out
+// (group 0's pair) + 4 k are group k's; one rule uses [0, 4) only, as before.  The handle's own EhOpt then names Adam, so every site moves
+// m and v: a group whose rule keeps less leaves them as they are.
+struct EhOptTab {
+    EhOpt r[EH_MAX_OPT_GROUPS];     // (tab == nullptr in each)
+    int n;
+    int pad[3];
+    unsigned char gid[4];          // [n_theta] (the allocation is as long as that)
 };
 
 // Optimisers.jl rules, fp32 op for op.  bt = {beta1^t, beta2^t} running products (Optimisers keeps
@@ -91,6 +103,25 @@ __device__ __forceinline__ void eh_opt_update(const EhOpt& o, float g, float bt1
         th -= g * (o.lr / (sqrtf(v) + o.eps));
     } else {                                                     // Descent(eta)
         th -= o.lr * g;
+    }
+}
+
+// the update of flat-theta element i: the one rule (o.tab == nullptr: a kernel argument, uniform over the wavefront -- the code above,
+// with the products the caller read), or the rule and products of the element's group (bt: group 0's pair of the set being read)
+template <class PB>
+__device__ __forceinline__ void eh_opt_update_at(const EhOpt& o, PB bt, long long i, float g, float bt1, float bt2, float& th, float& m, float& v) {
+    if (o.tab == nullptr) { eh_opt_update(o, g, bt1, bt2, th, m, v); return; }
+    const int k = o.tab->gid[i];
+    eh_opt_update(o.tab->r[k], g, bt[4 * k], bt[4 * k + 1], th, m, v);
+}
+// the running products of every group one step on (upd: the step had a valid sample; one thread): bt_in -> bt_out (they may be the same)
+template <class PI, class PO>
+__device__ __forceinline__ void eh_opt_advance_groups(const EhOptTab* tab, PI bt_in, PO bt_out, bool upd) {
+    const int n = tab->n;
+    for (int k = 0; k < n; ++k) {
+        const float p1 = bt_in[4 * k], p2 = bt_in[4 * k + 1];
+        bt_out[4 * k] = upd ? p1 * tab->r[k].b1 : p1;
+        bt_out[4 * k + 1] = upd ? p2 * tab->r[k].b2 : p2;
     }
 }
 
@@ -233,7 +264,7 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
 
 struct EhFused {
     float* gacc;           // nullptr = two-kernel (deterministic) mode; else [3][EH_GSHARDS][n_acc] rotating accumulators
-    float* pset;           // [2][3][n_theta] parameter sets {theta, m, v}, then [2][2] running beta products
+    float* pset;           // [2][3][n_theta] parameter sets {theta, m, v}, then the running beta products (EhOptTab)
     const int* imap;       // canonical index -> image offset
     float* loss_slot;      // where the previous step's loss goes (nullable)
     int gslot;             // this step accumulates into gacc[gslot], applies gacc[(gslot+2)%3] when pending, clears gacc[(gslot+1)%3]
@@ -829,6 +860,7 @@ __device__ __forceinline__ void eh_ms_apply(const NET& net, const EhStepArgs& a,
     float th0 = P[idx0], mm0 = P[nth + idx0], vv0 = P[2 * nth + idx0];
     const int mp0 = idx0 < net.g_off ? imap[idx0] : 0;
     const float bt1 = sc[0], bt2 = sc[1];
+    const bool grouped = z.opt.tab != nullptr;
     __syncthreads();                                   // every sum of the step is in gsum
     EH_STAMP_FINE(11);
     const eh_lds_f* const tail = gsum + nth;           // [S | n | Sy | Syy] (one target: the multi-step launch takes no other)
@@ -841,7 +873,7 @@ __device__ __forceinline__ void eh_ms_apply(const NET& net, const EhStepArgs& a,
         if (idx == tid) { th = th0; mm = mm0; vv = vv0; mp = mp0; }
         else { th = P[idx]; mm = P[nth + idx]; vv = P[2 * nth + idx]; mp = idx < net.g_off ? imap[idx] : 0; }
         if (upd) {
-            eh_opt_update(z.opt, gsum[idx] * inv, bt1, bt2, th, mm, vv);
+            eh_opt_update_at(z.opt, sc, idx, gsum[idx] * inv, bt1, bt2, th, mm, vv);
             P[idx] = th; P[nth + idx] = mm; P[2 * nth + idx] = vv;
             if (idx < net.g_off) wl[mp] = th;
             else {
@@ -854,8 +886,10 @@ __device__ __forceinline__ void eh_ms_apply(const NET& net, const EhStepArgs& a,
     }
     // (no second barrier: the beta products were read before the barrier above, and the sums are overwritten -- plain stores, one writer per
     //  element -- only behind the next step's barriers; the multi-step kernel zeroes the array once, when the launch ends)
+    if (grouped) __syncthreads();      // (per-branch rules: the updates above read every group's products from LDS, in place)
     if (tid == 0) {
-        if (upd) { sc[0] = bt1 * z.opt.b1; sc[1] = bt2 * z.opt.b2; }
+        if (grouped) eh_opt_advance_groups(z.opt.tab, sc, sc, upd);
+        else if (upd) { sc[0] = bt1 * z.opt.b1; sc[1] = bt2 * z.opt.b2; }
         if (a.ms_loss) *a.ms_loss = lossv;
     }
 }
@@ -1340,7 +1374,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                     }
                 }
             }
-            if (upd) eh_opt_update(z.opt, gs * inv, f_bt1, f_bt2, th, mm, vv);
+            if (upd) eh_opt_update_at(z.opt, z.pset + 6 * nth + 2 * z.sc_sel, idx, gs * inv, f_bt1, f_bt2, th, mm, vv);
             if (((unsigned)idx & gmask) == blockIdx.x) { pout[idx] = th; pout[nth + idx] = mm; pout[2 * nth + idx] = vv; }   // every workgroup holds the same values: spread the stores
             if (idx < net.g_off) {
                 wl[mp] = th;
@@ -1354,8 +1388,11 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         EH_STAMP_PRO(7);
         if (blockIdx.x == 0 && tid == 0) {
             float* const sc_out = z.pset + 6 * nth + 2 * (z.sc_sel ^ 1);
-            sc_out[0] = upd ? f_bt1 * z.opt.b1 : f_bt1;
-            sc_out[1] = upd ? f_bt2 * z.opt.b2 : f_bt2;
+            if (z.opt.tab) eh_opt_advance_groups(z.opt.tab, z.pset + 6 * nth + 2 * z.sc_sel, sc_out, upd);
+            else {
+                sc_out[0] = upd ? f_bt1 * z.opt.b1 : f_bt1;
+                sc_out[1] = upd ? f_bt2 * z.opt.b2 : f_bt2;
+            }
             if (z.loss_slot && z.pending) *z.loss_slot = (ORDM && upd) ? lossv + 0.0f : lossv;      // (ORDM: as eh_reduce_kernel, which adds its extra-loss term 0)
         }
         if constexpr (!ORDM)       // (ORDM: the shards take no adds)
@@ -2209,7 +2246,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void eh_step_kernel(const Eh
 #else
         const int nth = net.n_theta, g_off = net.g_off;
 #endif
-        const int np = 6 * nth + 4, ng = 3 * EH_GSHARDS * a.n_acc + 4;
+        const int np = 6 * nth + (a.fz.opt.tab ? 4 * EH_MAX_OPT_GROUPS : 4), ng = 3 * EH_GSHARDS * a.n_acc + 4;
         float* const l_pset = eh_ms_smem + G::TOTAL_FLOATS;
         float* const l_gacc = l_pset + ((np + 3) & ~3);
         int* const l_imap = reinterpret_cast<int*>(l_gacc + ((ng + 3) & ~3));      // canonical index -> image offset: read by every step's update (a global round trip per step otherwise)
@@ -2258,7 +2295,10 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void eh_step_kernel(const Eh
     }
 }
 // LDS floats behind the step body's work space that the multi-step kernel keeps its state in (host side: launch size, eligibility)
-__host__ __device__ inline long long eh_ms_extra_floats(int n_theta, int n_acc) { return (long long)((6 * n_theta + 4 + 3) & ~3) + ((3LL * EH_GSHARDS * n_acc + 4 + 3) & ~3LL) + n_theta + 4; }
+// (grouped: per-branch optimiser rules, whose running products take 4 EH_MAX_OPT_GROUPS floats instead of 4)
+__host__ __device__ inline long long eh_ms_extra_floats(int n_theta, int n_acc, bool grouped = false) {
+    return (long long)((6 * n_theta + (grouped ? 4 * EH_MAX_OPT_GROUPS : 4) + 3) & ~3) + ((3LL * EH_GSHARDS * n_acc + 4 + 3) & ~3LL) + n_theta + 4;
+}
 #ifdef EH_SPEC_NS
 }   // namespace EH_SPEC_NS
 using namespace EH_SPEC_NS;

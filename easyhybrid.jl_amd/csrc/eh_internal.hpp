@@ -89,7 +89,9 @@ struct eh_handle_s {
     int C = 0, n_acc = 0, n_par = 0;
     float *thb[2] = {nullptr, nullptr}, *mb[2] = {nullptr, nullptr}, *vb[2] = {nullptr, nullptr};   // parameter sets (fused mode ping-pongs them)
     float* pset = nullptr;          // backing allocation of thb/mb/vb/sc
-    float* sc = nullptr;            // [2][2] running beta products, ping-pong
+    float* sc = nullptr;            // [EH_MAX_OPT_GROUPS][2][2] running beta products per optimiser group, ping-pong (group 0 = the one rule)
+    EhOptTab* opt_tab = nullptr;    // per-branch optimiser rules (eh_opt_init_groups): allocated once, so a recorded graph's pointer stays valid
+    int opt_groups = 1;             // groups of the current rule table; h->opt.tab != nullptr when it came from eh_opt_init_groups
     int cur = 0, sc_sel = 0;
     // fused-update mode
     bool fused = false, pending = false, fused_det = false;   // fused_det ("fused_update" 2): one kernel per step only where one workgroup covers the minibatch
@@ -176,7 +178,7 @@ struct eh_handle_s {
     float* l2val = nullptr;         // lambda * weight_l2 of the current parameters (device scalar)
     float* l2w = nullptr;           // eh_set_weight_l2_coef: one coefficient per canonical entry (device)
     int n_weights = 0;
-    struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; bool pend_ord; int ord_grid; };
+    struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; bool pend_ord; int ord_grid; bool grouped; };
     std::vector<GraphRec> graphs;         // eh_graph_*: captured step sequences + the rotation state they start (and must end) in
     bool capturing = false;
     GraphRec cap{};

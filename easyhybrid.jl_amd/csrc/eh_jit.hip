@@ -484,7 +484,7 @@ hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t s
     void* params[] = {const_cast<EhNet*>(net), const_cast<EhStepArgs*>(args)};
     if (mode < 0 || mode > 4 || !k->fn[mode]) return hipErrorNotSupported;
     if (mode == EH_MODE_TRAIN_MULTI) {      // one workgroup; its step-to-step state sits in LDS behind the work space
-        const size_t lds_ms = k->lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc);
+        const size_t lds_ms = k->lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, args->fz.opt.tab != nullptr);
         if (grid != 1 || lds_ms > EH_LDS_LIMIT) return hipErrorInvalidValue;
         return hipModuleLaunchKernel(k->fn[mode], 1, 1, 1, 64u * (unsigned)k->nw, 1, 1, (unsigned)lds_ms, stream, params, nullptr);
     }

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
                 float g = s[j] * scale;
                 if (l2val && ntot > 0.0f) { const float c2 = eh_l2_coef(im, idx0 + j); if (c2 != 0.0f) g = fmaf(2.0f * c2, th[j], g); }
                 g4[j] = g;
-                if (APPLY && ntot > 0.0f) eh_opt_update(o, g, bt1, bt2, th[j], mm[j], vv[j]);
+                if (APPLY && ntot > 0.0f) eh_opt_update_at(o, sc_in, idx0 + j, g, bt1, bt2, th[j], mm[j], vv[j]);
             }
             *reinterpret_cast<f32x4u*>(gradbuf + idx0) = g4;
             if (APPLY && ntot > 0.0f) {
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
                 if (l2val && ntot > 0.0f) { const float c2 = eh_l2_coef(im, idx); if (c2 != 0.0f) g = fmaf(2.0f * c2, th[j], g); }      // + d/dw (l2c * sum w^2)
                 gradbuf[idx] = g;
                 if (APPLY && ntot > 0.0f) {
-                    eh_opt_update(o, g, bt1, bt2, th[j], mm[j], vv[j]);
+                    eh_opt_update_at(o, sc_in, idx, g, bt1, bt2, th[j], mm[j], vv[j]);
                     theta[idx] = th[j];
                     if (use_m) m[idx] = mm[j];
                     if (use_v) v[idx] = vv[j];
@@ -496,8 +496,11 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
     }
     }
     if (APPLY && blockIdx.x == 0 && tid == 0) {
-        sc_out[0] = ntot > 0.0f ? sc_in[0] * o.b1 : sc_in[0];
-        sc_out[1] = ntot > 0.0f ? sc_in[1] * o.b2 : sc_in[1];
+        if (o.tab) eh_opt_advance_groups(o.tab, sc_in, sc_out, ntot > 0.0f);
+        else {
+            sc_out[0] = ntot > 0.0f ? sc_in[0] * o.b1 : sc_in[0];
+            sc_out[1] = ntot > 0.0f ? sc_in[1] * o.b2 : sc_in[1];
+        }
     }
 }
 
@@ -572,7 +575,7 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
     if (own && cnt > 0.0f) {
         const float gs = p2p ? gs_p2p : eh_fold8(gsv[0], gsv[1], gsv[2], gsv[3], gsv[4], gsv[5], gsv[6], gsv[7]);
         float mm = mm0, vv = vv0;
-        eh_opt_update(o, gs * inv, sc0, sc1, th, mm, vv);
+        eh_opt_update_at(o, sc_in, idx, gs * inv, sc0, sc1, th, mm, vv);
         theta[idx] = th; m[idx] = mm; v[idx] = vv;
     }
     if (own) {
@@ -580,8 +583,11 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
         else eh_image_store(im, idx, th);
     }
     if (idx == 0) {
-        sc_out[0] = cnt > 0.0f ? sc0 * o.b1 : sc0;
-        sc_out[1] = cnt > 0.0f ? sc1 * o.b2 : sc1;
+        if (o.tab) eh_opt_advance_groups(o.tab, sc_in, sc_out, cnt > 0.0f);
+        else {
+            sc_out[0] = cnt > 0.0f ? sc0 * o.b1 : sc0;
+            sc_out[1] = cnt > 0.0f ? sc1 * o.b2 : sc1;
+        }
         if (loss_slot) *loss_slot = lossv;
     }
 }
@@ -605,7 +611,7 @@ __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_
     eh_loss_finish(loss_kind, t[0], t[1], t[2], t[3], inv, lossv, im.agg_a);
     const bool upd = t[1] > 0.0f;
     if (own && upd) {
-        eh_opt_update(op, eh_ord_group_fold(gv) * inv, bt1, bt2, th, mm, vv);
+        eh_opt_update_at(op, sc_in, idx, eh_ord_group_fold(gv) * inv, bt1, bt2, th, mm, vv);
         theta[idx] = th; m[idx] = mm; v[idx] = vv;
     }
     if (own) {
@@ -613,8 +619,11 @@ __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_
         else eh_image_store(im, idx, th);
     }
     if (idx == 0) {
-        sc_out[0] = upd ? bt1 * op.b1 : bt1;
-        sc_out[1] = upd ? bt2 * op.b2 : bt2;
+        if (op.tab) eh_opt_advance_groups(op.tab, sc_in, sc_out, upd);
+        else {
+            sc_out[0] = upd ? bt1 * op.b1 : bt1;
+            sc_out[1] = upd ? bt2 * op.b2 : bt2;
+        }
         if (loss_slot) *loss_slot = upd ? lossv + 0.0f : __builtin_nanf("");
     }
 }
@@ -720,13 +729,16 @@ __global__ __launch_bounds__(256) void eh_apply_kernel(float* gradbuf, int n_the
         float g = gradbuf[idx] * scale;
         float th = theta[idx], mm = m[idx], vv = v[idx];
         if (l2val) { const float c2 = eh_l2_coef(im, idx); if (c2 != 0.0f) g = fmaf(2.0f * c2, th, g); }
-        eh_opt_update(o, g, sc_in[0], sc_in[1], th, mm, vv);
+        eh_opt_update_at(o, sc_in, idx, g, sc_in[0], sc_in[1], th, mm, vv);
         theta[idx] = th; m[idx] = mm; v[idx] = vv;
         eh_image_store(im, idx, th);
     }
     if (idx == 0) {
-        sc_out[0] = cnt > 0.0f ? sc_in[0] * o.b1 : sc_in[0];
-        sc_out[1] = cnt > 0.0f ? sc_in[1] * o.b2 : sc_in[1];
+        if (o.tab) eh_opt_advance_groups(o.tab, sc_in, sc_out, cnt > 0.0f);
+        else {
+            sc_out[0] = cnt > 0.0f ? sc_in[0] * o.b1 : sc_in[0];
+            sc_out[1] = cnt > 0.0f ? sc_in[1] * o.b2 : sc_in[1];
+        }
         if (loss_slot) *loss_slot = lossv;
     }
 }

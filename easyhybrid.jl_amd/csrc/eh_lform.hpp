@@ -53,7 +53,7 @@ struct EhLApply {
     const float* tot;                    // ... or, non-null, their sums [16] (a side job of an earlier launch of the step, EhGemmArgs::job_out)
     unsigned long long* stamps; int stamp_wg;      // diagnostic builds (-DEH_STAMPS): workgroup stamp_wg stamps its phases
 };
-struct EhLApplyS { float* slab; float* theta; float* m; float* v; EhOpt o; float scale, bt1, bt2; int go, use_m, use_v; unsigned long long* stamps; };
+struct EhLApplyS { float* slab; float* theta; float* m; float* v; EhOpt o; float scale, bt1, bt2; int go, use_m, use_v; unsigned long long* stamps; const float* bt; };
 #ifdef EH_STAMPS
 #define EH_LSTAMP(S, i) do { __builtin_amdgcn_sched_barrier(0); if ((S)->stamps && threadIdx.x == 0) { (S)->stamps[2 * (i)] = __builtin_readcyclecounter(); (S)->stamps[2 * (i) + 1] = wall_clock64(); } __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -66,7 +66,7 @@ __device__ __forceinline__ void eh_lapply_one(const EhLApplyS& S, const float* c
     const long long idx = cslot - S.slab;
     eh_gfloat* const tp = (eh_gfloat*)S.theta; eh_gfloat* const mp = (eh_gfloat*)S.m; eh_gfloat* const vp = (eh_gfloat*)S.v;
     float th = tp[idx], mm = S.use_m ? mp[idx] : 0.0f, vv = S.use_v ? vp[idx] : 0.0f;
-    eh_opt_update(S.o, gsum * S.scale, S.bt1, S.bt2, th, mm, vv);
+    eh_opt_update_at(S.o, S.bt, idx, gsum * S.scale, S.bt1, S.bt2, th, mm, vv);
     tp[idx] = th;
     if (S.use_m) mp[idx] = mm;
     if (S.use_v) vp[idx] = vv;
@@ -101,6 +101,15 @@ __device__ __forceinline__ void eh_opt_update_all(const EhOpt& o, const float (&
     else if (o.rule == EH_OPT_ADAMW) eh_opt_update_n<EH_OPT_ADAMW, N>(o, g, bt1, bt2, th, m, v);
     else if (o.rule == EH_OPT_RMSPROP) eh_opt_update_n<EH_OPT_RMSPROP, N>(o, g, bt1, bt2, th, m, v);
     else eh_opt_update_n<EH_OPT_DESCENT, N>(o, g, bt1, bt2, th, m, v);
+}
+// the same for N elements of flat theta at ix[]: one rule -- hoisted as above -- or (per-branch rules) each element by its group's, as a
+// chunk may straddle two groups (the last output bias and the first global parameter)
+template <int N>
+__device__ __forceinline__ void eh_opt_update_all_at(const EhOpt& o, const float* bt, const long long (&ix)[N], const float (&g)[N], float bt1, float bt2,
+                                                     float (&th)[N], float (&m)[N], float (&v)[N]) {
+    if (o.tab == nullptr) { eh_opt_update_all<N>(o, g, bt1, bt2, th, m, v); return; }
+#pragma unroll
+    for (int i = 0; i < N; ++i) eh_opt_update_at(o, bt, ix[i], g[i], bt1, bt2, th[i], m[i], v[i]);
 }
 
 __device__ __forceinline__ float eh_act_rt(int act, float z) {
@@ -353,7 +362,7 @@ __device__ __forceinline__ void eh_gemm_tile(const EhGemmArgs& g, const int bx, 
 #pragma unroll
                     for (int r = 0; r < 16; ++r) gg[r] = acc[i][j][r] * S.scale;
                     EH_LSTAMP(Sp, 3);
-                    eh_opt_update_all<16>(S.o, gg, S.bt1, S.bt2, ap_th, ap_m, ap_v);
+                    eh_opt_update_all_at<16>(S.o, S.bt, ap_ix, gg, S.bt1, S.bt2, ap_th, ap_m, ap_v);
                     asm volatile("" ::: "memory");
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
@@ -486,7 +495,7 @@ __device__ __forceinline__ void eh_thin_gemm_tile(const EhThinArgs& a, const int
 #pragma unroll
                 for (int j = 0; j < 9; ++j) {
                     const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                    if (on) eh_opt_update(S.o, ((red[0][cl][j] + red[1][cl][j]) + (red[2][cl][j] + red[3][cl][j])) * S.scale, S.bt1, S.bt2, th[j], mm[j], vv[j]);
+                    if (on) eh_opt_update_at(S.o, S.bt, ix[j], ((red[0][cl][j] + red[1][cl][j]) + (red[2][cl][j] + red[3][cl][j])) * S.scale, S.bt1, S.bt2, th[j], mm[j], vv[j]);
                 }
                 asm volatile("" ::: "memory");
 #pragma unroll
@@ -1651,7 +1660,7 @@ __global__ __launch_bounds__(256) void eh_dw_apply_kernel(const EhGemmGroup G, c
     eh_loss_finish(ap.loss_kind, tot[8], tot[9], tot[13], tot[14], scale, loss, ap.im.agg_a);      // [grad of the raw globals (8) | S | n_t (4) | Sy | Syy]
     const bool go = tot[9] > 0.0f;
     if (tid == 0) {
-        S.slab = ap.slab; S.theta = ap.theta; S.m = ap.m; S.v = ap.v; S.o = ap.o; S.scale = scale; S.bt1 = ap.sc_in[0]; S.bt2 = ap.sc_in[1];
+        S.slab = ap.slab; S.theta = ap.theta; S.m = ap.m; S.v = ap.v; S.o = ap.o; S.scale = scale; S.bt1 = ap.sc_in[0]; S.bt2 = ap.sc_in[1]; S.bt = ap.sc_in;
         S.go = go ? 1 : 0;
         S.use_m = (ap.o.rule == EH_OPT_ADAM || ap.o.rule == EH_OPT_ADAMW) ? 1 : 0;
         S.use_v = (S.use_m || ap.o.rule == EH_OPT_RMSPROP) ? 1 : 0;
@@ -1669,15 +1678,18 @@ __global__ __launch_bounds__(256) void eh_dw_apply_kernel(const EhGemmGroup G, c
                 if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL && (int)((net.par_idx >> (4 * j)) & 15u) == tid) gsum = tot[j];
             const int idx = net.g_off + tid;
             float th = ap.theta[idx], mm = S.use_m ? ap.m[idx] : 0.0f, vv = S.use_v ? ap.v[idx] : 0.0f;
-            eh_opt_update(ap.o, gsum * scale, S.bt1, S.bt2, th, mm, vv);
+            eh_opt_update_at(ap.o, ap.sc_in, idx, gsum * scale, S.bt1, S.bt2, th, mm, vv);
             ap.theta[idx] = th;
             if (S.use_m) ap.m[idx] = mm;
             if (S.use_v) ap.v[idx] = vv;
             eh_image_store(ap.im, idx, th);
         }
         if (tid == 0) {
-            ap.sc_out[0] = go ? S.bt1 * ap.o.b1 : S.bt1;
-            ap.sc_out[1] = go ? S.bt2 * ap.o.b2 : S.bt2;
+            if (ap.o.tab) eh_opt_advance_groups(ap.o.tab, ap.sc_in, ap.sc_out, go);
+            else {
+                ap.sc_out[0] = go ? S.bt1 * ap.o.b1 : S.bt1;
+                ap.sc_out[1] = go ? S.bt2 * ap.o.b2 : S.bt2;
+            }
             ap.gradbuf[net.n_theta] = loss;                             // (what eh_reduce_kernel leaves behind the gradient: loss, count, Sy, Syy -- the gradient itself is not kept)
             ap.gradbuf[net.n_theta + 1] = tot[9]; ap.gradbuf[net.n_theta + 2] = tot[13]; ap.gradbuf[net.n_theta + 3] = tot[14];
             if (ap.loss_slot) *ap.loss_slot = loss;
@@ -1772,15 +1784,18 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
                 if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL && (int)((net.par_idx >> (4 * j)) & 15u) == tid) gsum = totl[j];
             const int idx = net.g_off + tid;
             float th = ap.theta[idx], mm = use_m ? ap.m[idx] : 0.0f, vv = use_v ? ap.v[idx] : 0.0f;
-            eh_opt_update(ap.o, gsum * scale, bt1, bt2, th, mm, vv);
+            eh_opt_update_at(ap.o, ap.sc_in, idx, gsum * scale, bt1, bt2, th, mm, vv);
             ap.theta[idx] = th;
             if (use_m) ap.m[idx] = mm;
             if (use_v) ap.v[idx] = vv;
             eh_image_store(ap.im, idx, th);
         }
         if (tid == 0) {
-            ap.sc_out[0] = go ? bt1 * ap.o.b1 : bt1;
-            ap.sc_out[1] = go ? bt2 * ap.o.b2 : bt2;
+            if (ap.o.tab) eh_opt_advance_groups(ap.o.tab, ap.sc_in, ap.sc_out, go);
+            else {
+                ap.sc_out[0] = go ? bt1 * ap.o.b1 : bt1;
+                ap.sc_out[1] = go ? bt2 * ap.o.b2 : bt2;
+            }
             ap.gradbuf[net.n_theta] = loss;
             ap.gradbuf[net.n_theta + 1] = totl[9]; ap.gradbuf[net.n_theta + 2] = totl[13]; ap.gradbuf[net.n_theta + 3] = totl[14];
             if (ap.loss_slot) *ap.loss_slot = loss;
@@ -1847,7 +1862,7 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
 #pragma unroll
             for (int j = 0; j < 9; ++j) {
                 const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                if (on) eh_opt_update(ap.o, ((redq[0][cl][j] + redq[1][cl][j]) + (redq[2][cl][j] + redq[3][cl][j])) * scale, bt1, bt2, th[j], mm[j], vv[j]);
+                if (on) eh_opt_update_at(ap.o, ap.sc_in, ix[j], ((redq[0][cl][j] + redq[1][cl][j]) + (redq[2][cl][j] + redq[3][cl][j])) * scale, bt1, bt2, th[j], mm[j], vv[j]);
             }
             asm volatile("" ::: "memory");
 #pragma unroll
@@ -1863,7 +1878,7 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
         if (a.cs_thin && bx == 0 && tid < a.J) {
             const long long idx = (a.cs_thin + tid) - ap.slab;
             float t1 = tp[idx], m1 = use_m ? mp[idx] : 0.0f, v1 = use_v ? vp[idx] : 0.0f;
-            eh_opt_update(ap.o, ((redt[0][tid] + redt[1][tid]) + (redt[2][tid] + redt[3][tid])) * scale, bt1, bt2, t1, m1, v1);
+            eh_opt_update_at(ap.o, ap.sc_in, idx, ((redt[0][tid] + redt[1][tid]) + (redt[2][tid] + redt[3][tid])) * scale, bt1, bt2, t1, m1, v1);
             tp[idx] = t1;
             if (use_m) mp[idx] = m1;
             if (use_v) vp[idx] = v1;
@@ -1948,13 +1963,13 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
         gg[j] = ((red[0][rr][cc] + red[1][rr][cc]) + (red[2][rr][cc] + red[3][rr][cc])) * scale;
     }
     EH_A64(4);
-    eh_opt_update_all<4>(ap.o, gg, bt1, bt2, th, mm, vv);
+    eh_opt_update_all_at<4>(ap.o, ap.sc_in, ix, gg, bt1, bt2, th, mm, vv);
     EH_A64(5);
     if (do_cs && tid < 32 && pcol) {
         float s = 0.0f;
 #pragma unroll
         for (int p = 0; p < 8; ++p) s += csr[p][tid];
-        eh_opt_update(ap.o, s * scale, bt1, bt2, cth, cm, cv);
+        eh_opt_update_at(ap.o, ap.sc_in, cix, s * scale, bt1, bt2, cth, cm, cv);
     }
     asm volatile("" ::: "memory");
 #pragma unroll

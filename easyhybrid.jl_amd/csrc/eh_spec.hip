@@ -77,7 +77,7 @@ hipError_t launch(int mode, int grid, hipStream_t stream, const EhNet* net, cons
     else if (mode == EH_MODE_TRAIN_P2P && HASP2P) hipLaunchKernelGGL((EH_SPEC_KERNEL(EH_MODE_TRAIN_P2P)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
     else if (mode == EH_MODE_TRAIN_ORD && HASORD) hipLaunchKernelGGL((EH_SPEC_KERNEL(EH_MODE_TRAIN_ORD)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
     else if (mode == EH_MODE_TRAIN_MULTI && HASMULTI) {      // several steps of one workgroup per launch, the state between them in LDS behind the work space
-        const size_t lds_ms = LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc);
+        const size_t lds_ms = LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, args->fz.opt.tab != nullptr);
         if (grid != 1 || lds_ms > EH_LDS_LIMIT) return hipErrorInvalidValue;
         hipLaunchKernelGGL((EH_SPEC_KERNEL(EH_MODE_TRAIN_MULTI)), dim3(1), dim3(64 * NW), lds_ms, stream, *net, *args);
     }

@@ -364,13 +364,14 @@ class DataParallel:
         eng = self.engine
         theta = eng.get_params()
         m, v, bt = eng.get_opt_state()
-        pack = np.concatenate([theta, m, v, np.asarray(bt, np.float32)]).astype(np.float32)
+        bt = np.asarray(bt, np.float32)                       # (2,), or (n_groups, 2) under per-branch optimiser rules
+        pack = np.concatenate([theta, m, v, bt.ravel()]).astype(np.float32)
         backend = dist.get_backend(self.group)
         t = torch.from_numpy(pack).to(self._dev if backend == "nccl" else "cpu")
         dist.broadcast(t, src=src, group=self.group)
         pack = t.cpu().numpy()
         n = theta.size
         eng.set_params(pack[:n])
-        eng.set_opt_state(pack[n:2 * n], pack[2 * n:3 * n], pack[3 * n:3 * n + 2])
+        eng.set_opt_state(pack[n:2 * n], pack[2 * n:3 * n], pack[3 * n:3 * n + bt.size].reshape(bt.shape))
         if self.fused:
             self._refresh_gacc()

@@ -224,6 +224,30 @@ class HybridEngine:
         if rule not in L.OPT_RULES:
             raise NotImplementedError(f"optimiser rule {rule} is not implemented on the device")
         self._chk(self._lib.eh_opt_init(self._h, L.OPT_RULES[rule], lr, beta1, beta2, eps, weight_decay))
+        self._opt_groups = 1
+
+    def opt_init_groups(self, group, rules):
+        """A rule per group of flat-theta elements (per-branch TrainConfig.opt; train._opt_groups builds the tables): group[i] in
+        0..len(rules)-1 is the rule of element i, rules[k] = opt_init's keyword arguments of rule k.  Each group keeps its own running
+        beta products.  Taken as given: equal rules are not merged (pass one rule to opt_init for the single-rule path)."""
+        group = np.ascontiguousarray(group, np.uint8)
+        if group.size != self.n_theta:
+            raise ValueError(f"opt_init_groups: {group.size} group ids for {self.n_theta} parameters")
+        rid = np.zeros(len(rules), np.int32)
+        hyper = np.zeros((len(rules), 5), np.float32)
+        for k, r in enumerate(rules):
+            if r.get("rule", "Adam") not in L.OPT_RULES:
+                raise NotImplementedError(f"optimiser rule {r.get('rule')} is not implemented on the device")
+            rid[k] = L.OPT_RULES[r.get("rule", "Adam")]
+            hyper[k] = (r.get("lr", 0.01), r.get("beta1", 0.9), r.get("beta2", 0.999), r.get("eps", 1e-8), r.get("weight_decay", 0.0))
+        self._chk(self._lib.eh_opt_init_groups(self._h, group.ctypes.data, group.size, len(rules),
+                                               rid.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(hyper)))
+        self._opt_groups = len(rules)
+
+    @property
+    def opt_groups(self) -> int:
+        """optimiser groups: 1 after opt_init, len(rules) after opt_init_groups"""
+        return getattr(self, "_opt_groups", 1)
 
     def get_bn_state(self):
         """running (mean, var) of the input BatchNorm layer -- the `st.st_nn` part of the model state"""
@@ -337,14 +361,22 @@ class HybridEngine:
         self._chk(self._lib.eh_set_weight_l2_coef(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), c.size))
 
     def get_opt_state(self):
+        """(m, v, bt): bt = the running (beta1^t, beta2^t), shape (2,) -- or (n_groups, 2), one pair per group, after opt_init_groups"""
         m = np.empty(self.n_theta, np.float32)
         v = np.empty(self.n_theta, np.float32)
         bt = np.empty(2, np.float32)
         self._chk(self._lib.eh_get_opt_state(self._h, _fptr(m), _fptr(v), m.size, _fptr(bt)))
+        if self.opt_groups > 1:
+            bt = np.empty((self.opt_groups, 2), np.float32)
+            self._chk(self._lib.eh_get_opt_beta_t(self._h, _fptr(bt), self.opt_groups))
         return m, v, bt
 
     def set_opt_state(self, m, v, bt):
         m = np.ascontiguousarray(m, np.float32); v = np.ascontiguousarray(v, np.float32); bt = np.ascontiguousarray(bt, np.float32)
+        if bt.ndim == 2:                                      # one pair per group (the engine's own group count)
+            self._chk(self._lib.eh_set_opt_state(self._h, _fptr(m), _fptr(v), m.size, None))
+            self._chk(self._lib.eh_set_opt_beta_t(self._h, _fptr(bt), bt.shape[0]))
+            return
         self._chk(self._lib.eh_set_opt_state(self._h, _fptr(m), _fptr(v), m.size, _fptr(bt)))
 
     def train_step(self, first: int, count: int, want_loss: bool = True, idx=None):

@@ -391,6 +391,19 @@ function get_params(e::HybridEngine)
 end
 opt_init!(e::HybridEngine; rule = 0, eta = 0.01f0, beta = (0.9f0, 0.999f0), epsilon = 1.0f-8, lambda = 0.0f0) =
     check(e, @ccall LIB[].eh_opt_init(e.h::Ptr{Cvoid}, rule::Int32, eta::Float32, beta[1]::Float32, beta[2]::Float32, epsilon::Float32, lambda::Float32)::Int32)
+"one rule per group of flat-θ elements: group[i] ∈ 0:n-1, rules[k] (0 Adam, 1 AdamW, 2 RMSProp, 3 Descent), hyper[:, k] = (eta, beta1, beta2, epsilon, lambda)"
+function opt_init_groups!(e::HybridEngine, group::Vector{UInt8}, rules::Vector{Int32}, hyper::Matrix{Float32})
+    size(hyper) == (5, length(rules)) || throw(ArgumentError("hyper: 5 x $(length(rules))"))
+    check(e, @ccall LIB[].eh_opt_init_groups(e.h::Ptr{Cvoid}, group::Ptr{UInt8}, length(group)::Int64, length(rules)::Int32, rules::Ptr{Int32},
+        hyper::Ptr{Float32})::Int32)
+end
+"every group's running (β1^t, β2^t): a 2 x n matrix"
+function get_opt_beta_t(e::HybridEngine, n::Integer)
+    bt = Matrix{Float32}(undef, 2, n)
+    check(e, @ccall LIB[].eh_get_opt_beta_t(e.h::Ptr{Cvoid}, bt::Ptr{Float32}, n::Int32)::Int32)
+    return bt
+end
+set_opt_beta_t!(e::HybridEngine, bt::Matrix{Float32}) = check(e, @ccall LIB[].eh_set_opt_beta_t(e.h::Ptr{Cvoid}, bt::Ptr{Float32}, size(bt, 2)::Int32)::Int32)
 
 "engine options: :max_blocks, :variant, :fast_paths, :row_split, :fused_update, :training_loss (0 mse, 1 rmse, 2 mae, 3 nseLoss, 4 pearsonLoss, 5 kgeLoss, 6 pbkgeLoss),
 :specialize (1 = step kernels compiled at run time around this model's descriptor, about a second, ~20 % faster small-model steps),
@@ -690,6 +703,48 @@ function _opt_args(o)
     throw(ArgumentError("optimiser $(typeof(o)): the device runs Adam / AdamW / RMSProp / Descent"))
 end
 
+"top-level branches of the parameter tree -> their ranges in flat θ: `:ps` (the network), or one per network of a MultiNN model, then the globals"
+function opt_branches(m::SingleNNHybridModel)
+    br = Pair{Symbol, UnitRange{Int}}[]
+    off = 0
+    if haskey(m.config, :multi)
+        for (name, p, h) in zip(m.neural_param_names, m.config.multi.predictors, m.config.multi.hidden)
+            d = [length(p); h; 1]
+            n = sum(d[i + 1] * d[i] + d[i + 1] for i in 1:(length(d) - 1))
+            push!(br, name => (off + 1):(off + n)); off += n
+        end
+    else
+        n = isempty(m.neural_param_names) ? 0 : sum(o * i + o for (o, i) in m.NN)
+        push!(br, :ps => (off + 1):(off + n)); off += n
+    end
+    for g in m.global_param_names
+        push!(br, g => (off + 1):(off + 1)); off += 1
+    end
+    return br
+end
+"opt::NamedTuple (build_opt_state, src/training/train.jl:78-93): a rule per branch, Adam() for the branches it leaves out, equal rules merged"
+function opt_init_per_branch!(e::HybridEngine, m::SingleNNHybridModel, opt::NamedTuple)
+    br = opt_branches(m)
+    extra = setdiff(collect(keys(opt)), first.(br))
+    isempty(extra) || @warn "Per-branch optimizer keys not found in parameter tree, ignored: $(extra)"
+    group = zeros(UInt8, e.n_theta)
+    keys_ = Any[]
+    for (name, r) in br
+        isempty(r) && continue
+        o = _opt_args(haskey(opt, name) ? opt[name] : Adam(0.001f0))
+        k = findfirst(==(o), keys_)
+        k === nothing && (push!(keys_, o); k = length(keys_))
+        group[r] .= UInt8(k - 1)
+    end
+    length(keys_) <= 16 || throw(ArgumentError("per-branch optimiser: $(length(keys_)) distinct rules, at most 16"))
+    if length(keys_) == 1
+        o = keys_[1]
+        return opt_init!(e; rule = o.rule, eta = o.eta, beta = o.beta, epsilon = o.epsilon, lambda = o.lambda)
+    end
+    hyper = Float32[x for o in keys_ for x in (o.eta, o.beta[1], o.beta[2], o.epsilon, o.lambda)]
+    return opt_init_groups!(e, group, Int32[o.rule for o in keys_], reshape(hyper, 5, length(keys_)))
+end
+
 _col(data, n::Symbol) = Float32.(collect(data isa AbstractDict ? data[n] : getproperty(data, n)))   # NamedTuple / Dict of columns, DataFrame, ...
 
 """
@@ -763,10 +818,14 @@ function train(m::SingleNNHybridModel, data; nepochs = 200, batchsize = 64, opt 
     size(tr[1][1], 2) == 0 && return nothing                                                    # train.jl:186
     e = HybridEngine(m; device)
     set_params!(e, train_from === nothing ? initialparameters(rng, m) : Float32.(train_from))
-    o = _opt_args(opt)
     ((xt, ft), yt), ((xv, fv), yv) = tr, va
     set_data!(e, EH_SPLIT_TRAIN, xt, ft, yt); set_data!(e, EH_SPLIT_VAL, xv, fv, yv)
-    opt_init!(e; rule = o.rule, eta = o.eta, beta = o.beta, epsilon = o.epsilon, lambda = o.lambda)
+    if opt isa NamedTuple
+        opt_init_per_branch!(e, m, opt)
+    else
+        o = _opt_args(opt)
+        opt_init!(e; rule = o.rule, eta = o.eta, beta = o.beta, epsilon = o.epsilon, lambda = o.lambda)
+    end
     set_training_loss!(e, training_loss)
     set_agg!(e, agg)
     aggn = Symbol(agg)

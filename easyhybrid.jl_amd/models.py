@@ -360,6 +360,22 @@ class SingleNNHybridModel:
         glob = {g: theta[off + j:off + j + 1] for j, g in enumerate(self.global_param_names)}
         return ((nets[0] if nets else []) if self.NNs is None else dict(zip(self.neural_param_names, nets))), glob
 
+    def opt_branches(self) -> Dict[str, Tuple[int, int]]:
+        """top-level branches of the parameter tree -> their [lo, hi) in flat theta, in ComponentArray order (what a per-branch
+        TrainConfig.opt names, src/training/train.jl:78-93): the network `ps` of one network (empty without one: the reference's
+        `Chain()`), one branch per network of a MultiNN model, named by its neural parameter, then each global parameter"""
+        out, off = {}, 0
+        names = ["ps"] if self.NNs is None else list(self.neural_param_names)
+        nets = self.nets if self.nets else [[]]
+        for name, net in zip(names, nets):
+            n = sum(o * i + o for o, i in net)
+            out[name] = (off, off + n)
+            off += n
+        for g in self.global_param_names:
+            out[g] = (off, off + 1)
+            off += 1
+        return out
+
     # -- C descriptor ----------------------------------------------------------------------------
     def to_desc(self, device: int = 0, extra_outputs=(), mech: Optional[MechSpec] = None) -> L.ModelDesc:
         ms = mech if mech is not None else self.mechanistic_model      # (mech: the model's closure with the extra loss's entries as outputs of their own)

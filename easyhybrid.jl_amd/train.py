@@ -15,6 +15,7 @@ from __future__ import annotations
 import copy
 import os
 import time
+import warnings
 from dataclasses import dataclass, field, replace
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -66,6 +67,59 @@ def _opt_args(opt):
         return dict(rule="Descent", lr=opt.eta)
     raise NotImplementedError(f"optimiser {opt!r}: only Optimisers.jl-style Adam/AdamW/RMSProp/Descent run on the device "
                               "(the Optimization.jl path, src/training/train_optimization.jl, is out of scope)")
+
+
+_RULES = (Adam, AdamW, RMSProp, Descent)
+_DEFAULT_BRANCH_RULE = Adam(0.001, (0.9, 0.999), 1e-8)          # build_opt_state's default_rule = Optimisers.Adam() (train.jl:78)
+
+
+def _rule_key(a):
+    """the rule as eh_opt_init receives it (float32 hyper-parameters, the engine's defaults filled in): equal keys, equal bits"""
+    f = lambda x: float(np.float32(x))
+    return (a["rule"], f(a["lr"]), f(a.get("beta1", 0.9)), f(a.get("beta2", 0.999)), f(a.get("eps", 1e-8)), f(a.get("weight_decay", 0.0)))
+
+
+def _opt_groups(opt, model):
+    """TrainConfig.opt -> (group, rules): one rule (group None, rules [its eh_opt_init arguments]) or a rule per top-level branch of
+    the parameter tree (build_opt_state, src/training/train.jl:78-93): group[i] = the rule of flat-theta element i, branches with the
+    same rule merged.  `opt` is a rule, or a dict / NamedTuple of branch name -> rule; branches it leaves out take Adam()."""
+    if isinstance(opt, _RULES):
+        return None, [_opt_args(opt)]
+    if isinstance(opt, tuple) and hasattr(opt, "_asdict"):
+        opt = opt._asdict()
+    if not isinstance(opt, dict):
+        return None, [_opt_args(opt)]                                 # (raises NotImplementedError)
+    for k, r in opt.items():
+        if not isinstance(r, _RULES):
+            raise NotImplementedError(f"per-branch optimiser {k!r}: {r!r} -- only Adam/AdamW/RMSProp/Descent rules run on the device "
+                                      "(pre-built Optimisers.setup state trees are not supported)")
+    branches = model.opt_branches()
+    extra = [k for k in opt if k not in branches]
+    if extra:
+        warnings.warn("Per-branch optimizer keys not found in parameter tree, ignored: [" + ", ".join(":" + str(k) for k in extra) + "]")
+    keys, rules = [], []
+    group = np.zeros(model.n_theta, np.uint8)
+    for name, (lo, hi) in branches.items():
+        if hi == lo:
+            continue                                                  # (an empty branch: no element follows its rule)
+        a = _opt_args(opt.get(name, _DEFAULT_BRANCH_RULE))
+        k = _rule_key(a)
+        if k not in keys:
+            keys.append(k); rules.append(a)
+        group[lo:hi] = keys.index(k)
+    if len(rules) > L.EH_MAX_OPT_GROUPS:
+        raise NotImplementedError(f"per-branch optimiser: {len(rules)} distinct rules, the device keeps at most {L.EH_MAX_OPT_GROUPS}")
+    if len(rules) <= 1:
+        return None, rules or [_opt_args(_DEFAULT_BRANCH_RULE)]
+    return group, rules
+
+
+def _opt_setup(eng, opt, model):
+    group, rules = _opt_groups(opt, model)
+    if group is None:
+        eng.opt_init(**rules[0])
+    else:
+        eng.opt_init_groups(group, rules)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -638,7 +692,7 @@ def _train_distributed(model, tc: TrainConfig, rng, train_split, val_split) -> T
         else:
             theta = np.asarray(tc.train_from.ps if isinstance(tc.train_from, TrainResults) else tc.train_from[0], np.float32)
         eng.set_params(theta); ev.set_params(theta)
-        eng.opt_init(**_opt_args(tc.opt))
+        _opt_setup(eng, tc.opt, model)
         eng.set_training_loss(tc.training_loss)
         xterms = _extra_terms(tc.extra_loss)          # functions of the replicated parameters: every rank adds the same terms in eh_dp_apply
         aggn = _agg_name(tc.agg)
@@ -804,7 +858,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         else:
             theta = np.asarray(tc.train_from.ps if isinstance(tc.train_from, TrainResults) else tc.train_from[0], np.float32)
         eng.set_params(theta)
-        eng.opt_init(**_opt_args(tc.opt))
+        _opt_setup(eng, tc.opt, model)
         eng.set_training_loss(tc.training_loss)
         xterms = _extra_terms(tc.extra_loss)
         aggn = _agg_name(tc.agg)

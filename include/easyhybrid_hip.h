@@ -43,6 +43,7 @@ extern "C" {
 #define EH_MAX_PROG 64         /* instructions of a mechanistic program (EH_MECH_PROGRAM) */
 #define EH_MAX_PROG_CONST 16   /* its literal constants */
 #define EH_MAX_PROG_OUT 3      /* its outputs */
+#define EH_MAX_OPT_GROUPS 16   /* optimiser rules of one handle: one per top-level branch of the parameter tree (eh_opt_init_groups) */
 
 typedef enum eh_status {
     EH_OK = 0,
@@ -246,6 +247,15 @@ int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* ru
 int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay);
 int32_t eh_get_opt_state(eh_handle* h, float* m, float* v, int64_t n, float* beta_t /* [2] */);
 int32_t eh_set_opt_state(eh_handle* h, const float* m, const float* v, int64_t n, const float* beta_t);
+/* one rule per top-level branch of the parameter tree (TrainConfig.opt as a NamedTuple, src/training/train.jl:78-93): flat-theta
+ * element i follows rule group[i] (0..n_groups-1) with hyper-parameters hyper[5 * group[i] ..] = {lr, beta1, beta2, eps,
+ * weight_decay} and keeps its own running products (beta1^t, beta2^t), started at (beta1, beta2).  Zero moments, as eh_opt_init.
+ * The tables are taken as given (no merging of equal rules).  n_groups <= EH_MAX_OPT_GROUPS, else EH_EUNSUPPORTED.  eh_opt_init
+ * returns the handle to one rule.  In this mode eh_get_opt_state / eh_set_opt_state read and write group 0's products. */
+int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, int32_t n_groups, const int32_t* rule, const float* hyper);
+/* every group's running products: bt[2 * k], bt[2 * k + 1] for group k < n_groups (n_groups == the handle's count; 1 in one-rule mode) */
+int32_t eh_get_opt_beta_t(eh_handle* h, float* bt, int32_t n_groups);
+int32_t eh_set_opt_beta_t(eh_handle* h, const float* bt, int32_t n_groups);
 
 /* one single_train_step! (src/training/epoch.jl:20-26): fused forward + mechanistic model + masked loss + VJP, then reduce +
  * optimiser update, on one minibatch of the resident train split.
