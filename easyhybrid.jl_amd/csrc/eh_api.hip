@@ -63,6 +63,7 @@ static EhOrd ord_args(const eh_handle* h, int slot, int prev_grid) {
     o.cnt = h->ord;
     o.rows = reinterpret_cast<float*>(h->ord + 32 * EH_ORD_GROUPS);
     o.grows = o.rows + (size_t)2 * EH_ORD_ROWS * h->ord_rs;
+    o.err = h->ord_err;
     o.rs = h->ord_rs; o.soff = h->ord_soff; o.slot = slot; o.prev_grid = prev_grid;
     return o;
 }
@@ -798,6 +799,9 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         const size_t ob = sizeof(unsigned) * 32 * EH_ORD_GROUPS + sizeof(float) * (size_t)2 * (EH_ORD_ROWS + EH_ORD_GROUPS) * h->ord_rs;
         HIPCHK_C(hipMalloc(&h->ord, ob));
         HIPCHK_C(hipMemset(h->ord, 0, ob));      // (the counters start at 0; every launch leaves them there)
+        HIPCHK_C(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(h->ord + 32 * EH_ORD_GROUPS), (int)EH_ORD_EMPTY, (size_t)2 * EH_ORD_ROWS * h->ord_rs));      // (the rows: "not written")
+        HIPCHK_C(hipHostMalloc((void**)&h->ord_err, sizeof(unsigned), hipHostMallocMapped));      // (host memory: eh_synchronize reads it without a copy)
+        *h->ord_err = 0u;
     }
     tick("pset / bn / gacc");
     h->slab_rows = lform ? (int)EH_LFORM_ROWS : h->max_blocks;
@@ -885,7 +889,7 @@ int32_t eh_destroy(eh_handle* h) {
     eh_comm_release(h);             // communicator / local group / peer-to-peer mappings and buffers (eh_comm.hip)
     (void)hipSetDevice(h->device);
     (void)hipFree(h->pset); (void)hipFree(h->opt_tab);
-    (void)hipFree(h->gacc); (void)hipFree(h->ord); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
+    (void)hipFree(h->gacc); (void)hipFree(h->ord); if (h->ord_err) (void)hipHostFree(h->ord_err); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
     (void)hipFree(h->prog); (void)hipFree(h->l2val); (void)hipFree(h->l2w); (void)hipFree(h->loss_hist); (void)hipFree(h->perm); (void)hipFree(h->out_buf); (void)hipFree(h->idx_buf);
     eval_host_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
@@ -918,6 +922,8 @@ int32_t eh_synchronize(eh_handle* h) {
         HIPCHK(h, hipMemcpy(c, h->p2p_ctr, sizeof c, hipMemcpyDeviceToHost));
         if (c[1]) return fail(h, EH_EHIP, "eh_synchronize: a cross-GPU exchange ran into its 2 s deadline (a rank is missing or out of step); results are invalid");
     }
+    if (h->ord_err && *(volatile unsigned*)h->ord_err)
+        return fail(h, EH_EHIP, "eh_synchronize: an ordered step's row of sums did not arrive within its 2 s deadline; results are invalid");
     return EH_OK;
 }
 
@@ -3128,11 +3134,11 @@ int32_t eh_device_buffer(eh_handle* h, int32_t which, void** dev_ptr, int64_t* n
 }
 
 int32_t eh_debug_stamps(eh_handle* h, uint64_t* out, int32_t n) {
-    if (!h || !out || n < 0 || n > 32) return EH_EINVAL;
+    if (!h || !out || n < 0 || n > EH_STAMP_WORDS) return EH_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->stamps) {   // first call arms the buffer; later calls read it
-        HIPCHK(h, hipMalloc(&h->stamps, 32 * sizeof(unsigned long long)));
-        HIPCHK(h, hipMemset(h->stamps, 0, 32 * sizeof(unsigned long long)));
+        HIPCHK(h, hipMalloc(&h->stamps, EH_STAMP_WORDS * sizeof(unsigned long long)));      // (words 32 on: the ordered step's hand-off, EH_ORD_ST_TAIL)
+        HIPCHK(h, hipMemset(h->stamps, 0, EH_STAMP_WORDS * sizeof(unsigned long long)));
         memset(out, 0, (size_t)n * sizeof(uint64_t));
         return EH_OK;
     }

@@ -181,27 +181,48 @@ struct EhP2P {
 // [S | n | Sy | Syy] with the reduce kernel's butterfly, then applies the update as the mode-1 prologue does.  Nobody waits for
 // anybody: no spin, no fence.  Two slots of each (parity `slot`): a fast workgroup of step s + 1 rewrites its row while a slow one
 // still reads step s's rows in its prologue; step s + 2 starts only once step s + 1 (every reader of step s's slot) has ended.
+template <int CTRL> __device__ __forceinline__ float eh_dpp(float v);      // (below: one DPP move)
 enum { EH_ORD_GROUPS = 16, EH_ORD_ROWS = 256 };
 struct EhOrd {
     float* rows;           // [2][EH_ORD_ROWS][rs]: one row per workgroup -- gradient at [0, n_theta), [S | n | Sy | Syy] at soff
     float* grows;          // [2][EH_ORD_GROUPS][rs]: the group rows (gradient only)
     unsigned* cnt;         // group g's ticket counter at cnt[32 g]; every group's last arriver sets it back to 0
+    unsigned* err;         // host-visible word, set when a group's rows did not arrive before the deadline (eh_synchronize reports it)
     int rs, soff;          // row stride and offset of the scalar block: multiples of 4 floats (16-byte loads of the scalars)
     int slot;              // this step writes slot `slot`, its prologue reads slot `slot ^ 1`
     int prev_grid;         // workgroups of the step whose sums are pending (the rows and groups to read)
 };
+// The gradient words of the rows hold EH_ORD_EMPTY whenever no step in flight has written them: the buffer starts so, and every group's
+// last arriver writes it back into each word it has folded.  It is a signalling NaN, a pattern no VALU result has (IEEE mode quiets
+// every NaN result), so a stored sum is never mistaken for it, and a word that still holds it has not arrived yet.  (No step number in
+// the words: a recorded graph would freeze it, and a stale word from an earlier replay with another grid would pass for fresh.)
+#define EH_ORD_EMPTY 0x7FA5A5A5u
+#define EH_ORD_DEADLINE_TICKS 200000000ull      // 2 s of the 100 MHz wall clock for a row store that has been issued to land
+// Diagnostic builds (-DEH_STAMPS, tools/stamps_ord.py): the hand-off, which workgroup 0's stamps do not see.  Thread 0 of every group's
+// last arriver records (shader clock, wall clock) pairs at stamps[EH_ORD_ST_TAIL + 10 g ...]: [0] its row stored, [1] about to take the
+// ticket, [2] the ticket's answer known to the workgroup, [3] the group's rows read and folded, [4] the group row stored (a wait only
+// this build has); workgroup 0 at stamps[EH_ORD_ST_PRO ...]: [0] image staged, [1] the rows' scalars folded (wave 0).
+enum { EH_ORD_ST_TAIL = 32, EH_ORD_ST_PRO = EH_ORD_ST_TAIL + 10 * EH_ORD_GROUPS, EH_STAMP_WORDS = 256 };
+#ifdef EH_STAMPS
+#define EH_ORD_TICK(ts, p)                                                                            \
+    do {                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+        ts[2 * (p)] = __builtin_readcyclecounter(); ts[2 * (p) + 1] = wall_clock64();                  \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+    } while (0)
+#else
+#define EH_ORD_TICK(ts, p)
+#endif
 __device__ __forceinline__ int eh_ord_pos(int e, int nth, int soff) { return e < nth ? e : soff + (e - nth); }
 // The scalars of the pending step's rows, folded as eh_reduce_kernel folds them: its thread r holds 0 + row r (0 where r >= the row
-// count), four wave butterflies (__shfl_xor 32 ... 1) over rows 0-63, 64-127, ..., then (w0 + w1) + (w2 + w3).  ONE wave does it here,
-// lane l holding rows l, l + 64, l + 128, l + 192: no LDS, no barrier.  eh_ord_scalar_loads issues the loads, eh_ord_scalar_fold folds.
-__device__ __forceinline__ void eh_ord_scalar_loads(const EhOrd& o, int lane, f32x4 (&v)[4]) {
-    const float* const R = o.rows + (long long)(o.slot ^ 1) * EH_ORD_ROWS * o.rs + o.soff;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = lane + 64 * j;
-        v[j] = r < o.prev_grid ? *(const f32x4*)(R + (long long)r * o.rs) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-}
+// count), four wave butterflies (__shfl_xor 32 ... 1) over rows 0-63, 64-127, ..., then (w0 + w1) + (w2 + w3).  ONE wave does it here
+// with the same additions: lane 16 q + i holds rows 64 q + i + {0, 16, 32, 48}, so the butterfly's xor 32 and xor 16 are adds in
+// registers, xor 8 ... xor 1 are DPP adds within the lane's row of 16, and four readlanes take the blocks' sums.  (After each butterfly
+// level a lane's value equals its partner's bit for bit -- addition commutes -- which is what lets row_ror:4 stand in for xor 4.)
+// eh_ord_scalar_loads issues the loads, eh_ord_scalar_fold folds; every lane of the wave must be active.
+#ifdef EH_AB_ORD_PARENT
+// (diagnostic A/B: the butterfly written as it reads, lane l holding rows l + 64 j -- 96 ds_bpermute in six dependent levels)
+__device__ __forceinline__ int eh_ord_scalar_row(int lane) { return lane; }
 __device__ __forceinline__ f32x4 eh_ord_scalar_fold(const EhOrd& o, int lane, const f32x4 (&v)[4]) {
     float w[4][4];
 #pragma unroll
@@ -217,7 +238,42 @@ __device__ __forceinline__ f32x4 eh_ord_scalar_fold(const EhOrd& o, int lane, co
     f32x4 t;
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = (w[0][k] + w[1][k]) + (w[2][k] + w[3][k]);
+    return t;
+}
+#else
+__device__ __forceinline__ int eh_ord_scalar_row(int lane) { return 4 * (lane & ~15) + (lane & 15); }
+__device__ __forceinline__ f32x4 eh_ord_scalar_fold(const EhOrd& o, int lane, const f32x4 (&v)[4]) {
+    const int r0 = eh_ord_scalar_row(lane);
+    f32x4 t;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float c[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c[j] = 0.0f;
+            if (r0 + 16 * j < o.prev_grid) c[j] += v[j][k];
+        }
+        float s = (c[0] + c[2]) + (c[1] + c[3]);     // xor 32: rows i, i + 32 and i + 16, i + 48; xor 16
+        s += eh_dpp<0x128>(s);                       // row_ror:8 = xor 8
+        s += eh_dpp<0x124>(s);                       // row_ror:4 (= xor 4 modulo 8, and s repeats every 8 lanes by now)
+        s += eh_dpp<0x4E>(s);                        // quad_perm:[2,3,0,1] = xor 2
+        s += eh_dpp<0xB1>(s);                        // quad_perm:[1,0,3,2] = xor 1
+        const int si = __builtin_bit_cast(int, s);
+        const float w0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 0)), w1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 16)),
+                    w2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 32)), w3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 48));
+        t[k] = (w0 + w1) + (w2 + w3);
+    }
     return t;                                        // {S, n, Sy, Syy}
+}
+#endif
+__device__ __forceinline__ void eh_ord_scalar_loads(const EhOrd& o, int lane, f32x4 (&v)[4]) {
+    const float* const R = o.rows + (long long)(o.slot ^ 1) * EH_ORD_ROWS * o.rs + o.soff;
+    const int r0 = eh_ord_scalar_row(lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int r = r0 + 16 * j;
+        v[j] = r < o.prev_grid ? *(const f32x4*)(R + (long long)r * o.rs) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
 }
 // the pending step's gradient element idx: the 16 group rows in order from 0 (groups the step did not have: + 0)
 __device__ __forceinline__ void eh_ord_group_loads(const EhOrd& o, int idx, float (&g)[EH_ORD_GROUPS]) {
@@ -232,14 +288,25 @@ __device__ __forceinline__ float eh_ord_group_fold(const float (&g)[EH_ORD_GROUP
     return t;
 }
 // Called by every thread of every workgroup once its row is stored (write-through: __hip_atomic_store relaxed, agent scope).  The
-// hand-off: every storing wave drains its stores (s_waitcnt vmcnt(0)), a workgroup barrier, ONE lane adds to the group's counter (agent
-// scope); the workgroup whose add returns gsz - 1 reads the group's rows, every load an sc1 one (agent-scope relaxed atomic loads: they
-// bypass the CU's L1, which another CU's stores never refresh), behind a barrier that the adding wave joins.  No fence: the payload never
-// sits dirty in an L2.  The group row goes to the next kernel on the stream, whose start makes it visible.
-__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, float* flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const unsigned gi = blockIdx.x % EH_ORD_GROUPS, gsz = (gridDim.x - gi + EH_ORD_GROUPS - 1) / EH_ORD_GROUPS;
+// hand-off: a workgroup barrier with no wait for the row stores, then ONE lane adds to the group's counter (agent scope; the wait for
+// its answer also covers that wave's stores).  The workgroup whose add returns gsz - 1 reads the group's rows, every load an sc1 one
+// (agent-scope relaxed atomic loads: they bypass the CU's L1, which another CU's stores never refresh), behind a barrier that the adding
+// wave joins.  Every row store of the group has been issued by then, but some may still be on their way: a gradient word that still
+// holds EH_ORD_EMPTY is read again until it holds the sum (a deadline turns a store that never lands into the error word).  No fence,
+// no drain.  The fold is the one of eh_reduce_kernel's row groups; then EH_ORD_EMPTY goes back into every word read -- nobody reads
+// them before the step that writes them again, two launches on.  The group row goes to the next kernel on the stream, whose start
+// makes it visible.
+__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, float* flag, unsigned long long* st) {
+#ifdef EH_STAMPS
+    unsigned long long ts[10];
+#endif
+    EH_ORD_TICK(ts, 0);
+    const unsigned gi = blockIdx.x % EH_ORD_GROUPS, gsz = (gridDim.x - gi + EH_ORD_GROUPS - 1) / EH_ORD_GROUPS;      // (ahead of the barrier)
+#ifdef EH_AB_ORD_PARENT
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (diagnostic A/B: the drain of the hand-off before the sentinel words)
+#endif
+    __syncthreads();        // (a bare s_barrier: nothing waits for the row stores here)
+    EH_ORD_TICK(ts, 1);
     if (tid == 0) {
         unsigned* const gc = o.cnt + 32 * gi;
         const bool last = __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsz - 1;
@@ -247,19 +314,53 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
         flag[0] = last ? 1.0f : 0.0f;
     }
     __syncthreads();
+    EH_ORD_TICK(ts, 2);
     if (flag[0] == 0.0f) return;
-    const float* const R = o.rows + ((long long)o.slot * EH_ORD_ROWS + gi) * o.rs;
+    unsigned* const R = reinterpret_cast<unsigned*>(o.rows + ((long long)o.slot * EH_ORD_ROWS + gi) * o.rs);
     float* const Gr = o.grows + ((long long)o.slot * EH_ORD_GROUPS + gi) * o.rs;
+    constexpr int NK = EH_ORD_ROWS / EH_ORD_GROUPS;
     for (int e = tid; e < nth; e += nthr) {
-        float v[EH_ORD_ROWS / EH_ORD_GROUPS];
+        unsigned v[NK];
 #pragma unroll
-        for (int k = 0; k < EH_ORD_ROWS / EH_ORD_GROUPS; ++k)
-            v[k] = (unsigned)k < gsz ? __hip_atomic_load(R + (long long)k * EH_ORD_GROUPS * o.rs + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+        for (int k = 0; k < NK; ++k)
+            v[k] = (unsigned)k < gsz ? __hip_atomic_load(R + (long long)k * EH_ORD_GROUPS * o.rs + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        bool in = true;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) in = in && v[k] != EH_ORD_EMPTY;
+        if (!in) {            // (rare: a store of the group still on its way)
+            const unsigned long long t0 = wall_clock64();
+            while (true) {
+                __builtin_amdgcn_s_sleep(1);
+                in = true;
+#pragma unroll
+                for (int k = 0; k < NK; ++k)
+                    if (v[k] == EH_ORD_EMPTY) {
+                        v[k] = __hip_atomic_load(R + (long long)k * EH_ORD_GROUPS * o.rs + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        in = in && v[k] != EH_ORD_EMPTY;
+                    }
+                if (in) break;
+                if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+            }
+        }
         float s = 0.0f;                              // (+ 0 for the rows past the group's end: the sum started at + 0 is never - 0, so x + 0 == x)
 #pragma unroll
-        for (int k = 0; k < EH_ORD_ROWS / EH_ORD_GROUPS; ++k) s += v[k];
+        for (int k = 0; k < NK; ++k) s += __uint_as_float(v[k]);
         __hip_atomic_store(Gr + e, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            if ((unsigned)k < gsz) __hip_atomic_store(R + (long long)k * EH_ORD_GROUPS * o.rs + e, EH_ORD_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+#ifdef EH_STAMPS
+    EH_ORD_TICK(ts, 3);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    EH_ORD_TICK(ts, 4);
+    if (st && tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) st[EH_ORD_ST_TAIL + 10 * gi + k] = ts[k];
+    }
+#else
+    (void)st;
+#endif
 }
 
 struct EhFused {
@@ -1060,7 +1161,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     float f_sv = 0.0f;      // lane 8 k + sh of every wave: scalar k of shard sh
     float f_gs[EH_GSHARDS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // this thread's element in the eight shards
     float o_g[ORDM ? EH_ORD_GROUPS : 1];                  // EH_MODE_TRAIN_ORD: this thread's element in the 16 group rows ...
-    f32x4 o_sv[ORDM ? 4 : 1];                              // ... and (wave 0) the scalars of rows lane + 64 j
+    f32x4 o_sv[ORDM ? 4 : 1];                              // ... and (wave 0) the scalars of rows eh_ord_scalar_row(lane) + 16 j
     if constexpr (ORDM) {
 #pragma unroll
         for (int k = 0; k < EH_ORD_GROUPS; ++k) o_g[k] = 0.0f;
@@ -1150,10 +1251,16 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     if (rec_pending) fetch_rec();
     if (ORDM && own_direct) {
         if constexpr (ORDM) {
+#ifdef EH_STAMPS
+            if (a.stamps && blockIdx.x == 0 && tid == 0) { unsigned long long ts[4]; EH_ORD_TICK(ts, 0); a.stamps[EH_ORD_ST_PRO] = ts[0]; a.stamps[EH_ORD_ST_PRO + 1] = ts[1]; }
+#endif
             f_g = eh_ord_group_fold(o_g);
             if (wave == 0) {           // (read by every thread behind the workgroup barrier in front of the update below)
                 const f32x4 t = eh_ord_scalar_fold(a.ord, lane, o_sv);
                 if (lane == 0) *(f32x4*)px_T = t;
+#ifdef EH_STAMPS
+                if (a.stamps && blockIdx.x == 0 && tid == 0) { unsigned long long ts[4]; EH_ORD_TICK(ts, 1); a.stamps[EH_ORD_ST_PRO + 2] = ts[2]; a.stamps[EH_ORD_ST_PRO + 3] = ts[3]; }
+#endif
             }
         }
     } else if (own_direct) {
@@ -2040,7 +2147,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             else out[e] = sum;
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4);
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4, a.stamps);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);
@@ -2156,7 +2263,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4);
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4, a.stamps);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);

@@ -432,7 +432,8 @@ int32_t eh_profile_read(eh_handle* h, int64_t* n_launches, double* mean_ms_step_
 int32_t eh_profile_samples(eh_handle* h, double* ms, int64_t cap, int64_t* n_out);
 
 /* diagnostic builds (make STAMPS=1) only: in-kernel phase stamps of workgroup 0 as (shader clock, 100 MHz clock)
- * pairs; the first call arms the buffer.  A normal build leaves the buffer zero. */
+ * pairs (words 0-31; from word 32 on, the ordered step's hand-off in every group's last arriver), n <= 256; the first
+ * call arms the buffer.  A normal build leaves the buffer zero. */
 int32_t eh_debug_stamps(eh_handle* h, uint64_t* out, int32_t n);
 
 /* tuning knobs (name/value): "max_blocks" (1..256), "variant" (tile shape), "fast_paths" (0 = generic MFMA kernels), "training_loss" (eh_loss),
