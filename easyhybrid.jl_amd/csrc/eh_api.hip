@@ -70,7 +70,8 @@ static EhOrd ord_args(const eh_handle* h, int slot, int prev_grid) {
 static int flush_one(eh_handle* h) {
     const int nt = h->net.n_theta;
     if (h->pend_ord) {        // an ordered step's sums: its rows and group rows (the step wrote slot h->cur ^ 1, which is what slot h->cur reads)
-        hipLaunchKernelGGL(eh_ord_flush_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, ord_args(h, h->cur, h->ord_grid), nt, TH(h), MM(h), VV(h),
+        // (a workgroup per row of the step at least: each resets the rows it takes, the first ceil(nt / 256) also apply the update)
+        hipLaunchKernelGGL(eh_ord_flush_kernel, dim3(std::max((nt + 255) / 256, h->ord_grid)), dim3(256), 0, h->stream, ord_args(h, h->cur, h->ord_grid), nt, TH(h), MM(h), VV(h),
                            h->sc + 2 * h->sc_sel, h->sc + 2 * (h->sc_sel ^ 1), h->opt, h->pending_loss, h->img, h->net.loss);
         HIPCHK(h, hipGetLastError());
         h->sc_sel ^= 1;
@@ -2128,7 +2129,8 @@ static bool ord_ok(const eh_handle* h, int grid) {
     if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS) return false;
     if (h->lform || h->arch->wide || h->p2p_on || h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->img.l2c != 0.0f || h->img.l2w || two_pass_mask(h->net) || h->dp_weights || h->dp_moments) return false;
-    return h->n_acc < 8192 && (cw_env == 0 || cw_env == 16);
+    // (the step stages its row in LDS over the parameter image before it stores it)
+    return h->n_acc < 8192 && h->ord_rs <= h->arch->img_floats && (cw_env == 0 || cw_env == 16);
 }
 
 static int ensure_events(eh_handle* h, size_t need) {

@@ -175,8 +175,8 @@ struct EhP2P {
 // "Ordered" fused-update step (EH_MODE_TRAIN_ORD, "fused_update" 2 on minibatches of several workgroups): ONE kernel per step, and the
 // same bits as the deterministic step + eh_reduce_kernel<APPLY, 16> pair.  That reduce has 16 row groups: thread q of a column sums the
 // slab rows q, q + 16, q + 32, ... in ascending order from 0, and the column's total is the 16 partials summed in q order from 0.  Here
-// workgroup b stores its row write-through (sc1) into a row slot and takes a ticket on the counter of its group g = b % 16 (a 128-byte
-// line of its own); the workgroup whose add comes last in its group folds the group's rows in that same order into group row g.  The
+// workgroup b stores its row write-through (16-byte sc1 stores) into a row slot and takes a ticket on the counter of its group g = b % 16
+// (a 128-byte line of its own); the workgroup whose add comes last in its group folds the group's rows in that same order into group row g.  The
 // next step's prologue sums the 16 group rows in order (absent groups: + 0, as the pair's idle row groups) and folds the rows' scalars
 // [S | n | Sy | Syy] with the reduce kernel's butterfly, then applies the update as the mode-1 prologue does.  Nobody waits for
 // anybody: no spin, no fence.  Two slots of each (parity `slot`): a fast workgroup of step s + 1 rewrites its row while a slow one
@@ -192,8 +192,9 @@ struct EhOrd {
     int slot;              // this step writes slot `slot`, its prologue reads slot `slot ^ 1`
     int prev_grid;         // workgroups of the step whose sums are pending (the rows and groups to read)
 };
-// The gradient words of the rows hold EH_ORD_EMPTY whenever no step in flight has written them: the buffer starts so, and every group's
-// last arriver writes it back into each word it has folded.  It is a signalling NaN, a pattern no VALU result has (IEEE mode quiets
+// The gradient words of the rows hold EH_ORD_EMPTY whenever no step in flight has written them: the buffer starts so, and the consumer
+// of a pending step's sums (the next ordered step, or eh_ord_flush_kernel) writes it back into that step's rows (eh_ord_reset): off the
+// tail of the step that folds them.  It is a signalling NaN, a pattern no VALU result has (IEEE mode quiets
 // every NaN result), so a stored sum is never mistaken for it, and a word that still holds it has not arrived yet.  (No step number in
 // the words: a recorded graph would freeze it, and a stale word from an earlier replay with another grid would pass for fresh.)
 #define EH_ORD_EMPTY 0x7FA5A5A5u
@@ -287,68 +288,116 @@ __device__ __forceinline__ float eh_ord_group_fold(const float (&g)[EH_ORD_GROUP
     for (int k = 0; k < EH_ORD_GROUPS; ++k) t += g[k];
     return t;
 }
-// Called by every thread of every workgroup once its row is stored (write-through: __hip_atomic_store relaxed, agent scope).  The
-// hand-off: a workgroup barrier with no wait for the row stores, then ONE lane adds to the group's counter (agent scope; the wait for
-// its answer also covers that wave's stores).  The workgroup whose add returns gsz - 1 reads the group's rows, every load an sc1 one
-// (agent-scope relaxed atomic loads: they bypass the CU's L1, which another CU's stores never refresh), behind a barrier that the adding
-// wave joins.  Every row store of the group has been issued by then, but some may still be on their way: a gradient word that still
-// holds EH_ORD_EMPTY is read again until it holds the sum (a deadline turns a store that never lands into the error word).  No fence,
-// no drain.  The fold is the one of eh_reduce_kernel's row groups; then EH_ORD_EMPTY goes back into every word read -- nobody reads
-// them before the step that writes them again, two launches on.  The group row goes to the next kernel on the stream, whose start
-// makes it visible.
-__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, float* flag, unsigned long long* st) {
+// 16-byte write-through accesses of the hand-off buffers: buffer_{load,store}_dwordx4 ... sc1 (the loads bypass the CU's L1, which another
+// CU's stores never refresh; the stores go through to memory).  The compiler tracks their waits, unlike inline asm.  The descriptor's range
+// is the buffer itself: a load past it returns 0 without a memory access, a store past it is dropped.
+typedef unsigned u32x4_ord __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t eh_ord_rsrc(const float* base, int nfloats) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 4 * nfloats, 0x00020000);
+}
+__device__ __forceinline__ f32x4 eh_ord_ld16(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16)); }
+__device__ __forceinline__ void eh_ord_st16(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_ord, v), r, off, 0, 16); }
+enum { EH_ORD_OOB = 0x7FFFFFF0 };       // (a byte offset past any row buffer: the load returns 0)
+// The consumer of a pending ordered step -- the next ordered step's prologue or eh_ord_flush_kernel -- writes EH_ORD_EMPTY back into the
+// gradient words of that step's rows (slot `slot ^ 1`, rows [0, prev_grid)): workgroup b takes rows b, b + nblk, ...; 16-byte stores over
+// [0, soff), the padding included, never the scalar block.  Nobody reads those words before the step two launches on writes them again,
+// and the kernel boundary in between publishes the marker.  (Done whether or not the pending step had a valid target.)
+__device__ __forceinline__ void eh_ord_reset(const EhOrd& o, int b, int nblk, int tid, int nthr) {
+    const __amdgpu_buffer_rsrc_t rr = eh_ord_rsrc(o.rows, 2 * EH_ORD_ROWS * o.rs);
+    const float e = __uint_as_float(EH_ORD_EMPTY);
+    const f32x4 ev = {e, e, e, e};
+    const int nv = o.soff >> 2;
+    for (int r = b; r < o.prev_grid; r += nblk)
+        for (int v = tid; v < nv; v += nthr) eh_ord_st16(rr, 4 * (((o.slot ^ 1) * EH_ORD_ROWS + r) * o.rs) + 16 * v, ev);
+}
+// Called by every thread of every workgroup once its row is staged in LDS at `row`, in its global layout (gradient at [0, n_theta), the
+// scalars at soff).  The hand-off: a workgroup barrier, then wave 0 stores the row write-through as 16-byte vectors -- the gradient's
+// ceil(n_theta / 4) and the scalar vector -- and, with no wait for them, ONE lane adds to the group's counter (agent scope).  The
+// workgroup whose add returns gsz - 1 reads the other rows of its group with 16-byte sc1 loads, behind a barrier that the adding wave
+// joins; its own row it takes from LDS.  Every row store of the group has been issued by then, but some may still be on their way: a
+// gradient word that still holds EH_ORD_EMPTY is read again, its whole vector (a torn read included), until it holds the sum (a deadline
+// turns a store that never lands into the error word).  The padding words past n_theta take no part in the check.  No fence, no drain.
+// The fold is the one of eh_reduce_kernel's row groups, four elements per thread.  The group row goes to the next kernel on the stream,
+// whose start makes it visible; the rows stay as they are until that kernel's workgroups reset them (eh_ord_reset).
+__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, const float* row, float* flag, unsigned long long* st) {
 #ifdef EH_STAMPS
     unsigned long long ts[10];
 #endif
     EH_ORD_TICK(ts, 0);
     const unsigned gi = blockIdx.x % EH_ORD_GROUPS, gsz = (gridDim.x - gi + EH_ORD_GROUPS - 1) / EH_ORD_GROUPS;      // (ahead of the barrier)
+    const __amdgpu_buffer_rsrc_t rr = eh_ord_rsrc(o.rows, 2 * EH_ORD_ROWS * o.rs);
+    const int nv = (nth + 3) >> 2;         // the gradient's vectors; the scalar vector follows at soff
 #ifdef EH_AB_ORD_PARENT
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (diagnostic A/B: the drain of the hand-off before the sentinel words)
 #endif
-    __syncthreads();        // (a bare s_barrier: nothing waits for the row stores here)
-    EH_ORD_TICK(ts, 1);
-    if (tid == 0) {
-        unsigned* const gc = o.cnt + 32 * gi;
-        const bool last = __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsz - 1;
-        if (last) __hip_atomic_store(gc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        flag[0] = last ? 1.0f : 0.0f;
+    __syncthreads();        // the row is staged
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+        const int rb = 4 * ((o.slot * EH_ORD_ROWS + (int)blockIdx.x) * o.rs);
+        for (int v = tid; v <= nv; v += 64) {
+            const int w = v < nv ? 4 * v : o.soff;
+            eh_ord_st16(rr, rb + 4 * w, *(const f32x4*)&row[w]);
+        }
+        EH_ORD_TICK(ts, 1);
+        if (tid == 0) {
+            unsigned* const gc = o.cnt + 32 * gi;
+            const bool last = __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsz - 1;
+            if (last) __hip_atomic_store(gc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            flag[0] = last ? 1.0f : 0.0f;
+        }
     }
     __syncthreads();
     EH_ORD_TICK(ts, 2);
     if (flag[0] == 0.0f) return;
-    unsigned* const R = reinterpret_cast<unsigned*>(o.rows + ((long long)o.slot * EH_ORD_ROWS + gi) * o.rs);
-    float* const Gr = o.grows + ((long long)o.slot * EH_ORD_GROUPS + gi) * o.rs;
     constexpr int NK = EH_ORD_ROWS / EH_ORD_GROUPS;
-    for (int e = tid; e < nth; e += nthr) {
-        unsigned v[NK];
+    const int kown = blockIdx.x / EH_ORD_GROUPS;
+    const int rb = 4 * ((o.slot * EH_ORD_ROWS + (int)gi) * o.rs), rk = 4 * EH_ORD_GROUPS * o.rs;     // bytes: row k of the group at rb + k rk
+    const __amdgpu_buffer_rsrc_t gr = eh_ord_rsrc(o.grows, 2 * EH_ORD_GROUPS * o.rs);
+    const int gb = 4 * ((o.slot * EH_ORD_GROUPS + (int)gi) * o.rs);
+    for (int v = tid; v < nv; v += nthr) {
+        f32x4 r[NK];
 #pragma unroll
-        for (int k = 0; k < NK; ++k)
-            v[k] = (unsigned)k < gsz ? __hip_atomic_load(R + (long long)k * EH_ORD_GROUPS * o.rs + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        bool in = true;
+        for (int k = 0; k < NK; ++k) r[k] = eh_ord_ld16(rr, ((unsigned)k < gsz && k != kown) ? rb + k * rk + 16 * v : (int)EH_ORD_OOB);    // (0 for the rest)
+        const f32x4 own = *(const f32x4*)&row[4 * v];
+        // (+ 0 for the rows past the group's end: the sum started at + 0 is never - 0, so x + 0 == x)
+        auto fold = [&]() {
+            f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int k = 0; k < NK; ++k) in = in && v[k] != EH_ORD_EMPTY;
-        if (!in) {            // (rare: a store of the group still on its way)
-            const unsigned long long t0 = wall_clock64();
-            while (true) {
-                __builtin_amdgcn_s_sleep(1);
-                in = true;
+            for (int k = 0; k < NK; ++k) s += k == kown ? own : r[k];
+            return s;
+        };
+        f32x4 s = fold();
+        // a word that still holds EH_ORD_EMPTY (a signalling NaN) makes its element's sum a NaN: look at the words only then
+        bool nan = false;
 #pragma unroll
-                for (int k = 0; k < NK; ++k)
-                    if (v[k] == EH_ORD_EMPTY) {
-                        v[k] = __hip_atomic_load(R + (long long)k * EH_ORD_GROUPS * o.rs + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        in = in && v[k] != EH_ORD_EMPTY;
-                    }
-                if (in) break;
-                if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+        for (int j = 0; j < 4; ++j) nan = nan || (4 * v + j < nth && s[j] != s[j]);
+        if (nan) {            // (rare: a store of the group still on its way -- or a NaN gradient)
+            auto empty = [&](int k) {
+                bool e = false;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) e = e || (4 * v + j < nth && __float_as_uint(r[k][j]) == EH_ORD_EMPTY);
+                return e;
+            };
+            bool in = true;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) in = in && !empty(k);
+            if (!in) {
+                const unsigned long long t0 = wall_clock64();
+                while (true) {
+                    __builtin_amdgcn_s_sleep(1);
+                    in = true;
+#pragma unroll
+                    for (int k = 0; k < NK; ++k)
+                        if (empty(k)) {
+                            r[k] = eh_ord_ld16(rr, rb + k * rk + 16 * v);
+                            in = in && !empty(k);
+                        }
+                    if (in) break;
+                    if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+                }
+                s = fold();
             }
         }
-        float s = 0.0f;                              // (+ 0 for the rows past the group's end: the sum started at + 0 is never - 0, so x + 0 == x)
-#pragma unroll
-        for (int k = 0; k < NK; ++k) s += __uint_as_float(v[k]);
-        __hip_atomic_store(Gr + e, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int k = 0; k < NK; ++k)
-            if ((unsigned)k < gsz) __hip_atomic_store(R + (long long)k * EH_ORD_GROUPS * o.rs + e, EH_ORD_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        eh_ord_st16(gr, gb + 16 * v, s);
     }
 #ifdef EH_STAMPS
     EH_ORD_TICK(ts, 3);
@@ -1493,6 +1542,9 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
         }
         EH_STAMP_PRO(7);
+        // (the pending step's rows back to EH_ORD_EMPTY: stores issued behind every load of the prologue, so that no wait for a load
+        //  of it waits for them)
+        if constexpr (ORDM) { if (own_direct) eh_ord_reset(a.ord, blockIdx.x, gridDim.x, tid, NTHR); }
         if (blockIdx.x == 0 && tid == 0) {
             float* const sc_out = z.pset + 6 * nth + 2 * (z.sc_sel ^ 1);
             if (z.opt.tab) eh_opt_advance_groups(z.opt.tab, z.pset + 6 * nth + 2 * z.sc_sel, sc_out, upd);
@@ -2111,7 +2163,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         __syncthreads();
         EH_STAMP(9);
         const float* const R0 = smem + G::IMG_FLOATS;
-        float* const out = ORDM ? a.ord.rows + ((long long)a.ord.slot * EH_ORD_ROWS + blockIdx.x) * a.ord.rs : a.slab + (long long)blockIdx.x * a.n_acc;
+        float* const out = a.slab + (long long)blockIdx.x * a.n_acc;      // (EH_MODE_TRAIN_ORD: the row is staged in LDS, over the parameter image -- dead by now)
         float* const gsh = (!ORDM && a.fz.gacc) ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
         for (int e = tid; e < a.n_acc; e += NTHR) {
             const int code = e == tid ? f_rcode : a.rmap[e], pos = code & 0xFFFFFF, nlan = code >> 24;
@@ -2142,12 +2194,12 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll 1
                 for (int w = 0; w < nlive; ++w) sum += R0[w * AL.rw + pos];
             }
-            if constexpr (ORDM) __hip_atomic_store(out + eh_ord_pos(e, net.n_theta, a.ord.soff), sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (write-through)
+            if constexpr (ORDM) wl[eh_ord_pos(e, net.n_theta, a.ord.soff)] = sum;      // (eh_ord_publish stores it write-through)
             else if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[e] = sum; else atomicAdd(&gsh[e], sum); }      // (ms_direct: one workgroup, one writer per element)
             else out[e] = sum;
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4, a.stamps);
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);
@@ -2207,10 +2259,10 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         EH_STAMP(13);
         float* const R = smem + G::IMG_FLOATS + wave * G::WAVE_WS;
         const float* const R0 = smem + G::IMG_FLOATS;
-        float* const out = ORDM ? a.ord.rows + ((long long)a.ord.slot * EH_ORD_ROWS + blockIdx.x) * a.ord.rs : a.slab + (long long)blockIdx.x * a.n_acc;
+        float* const out = a.slab + (long long)blockIdx.x * a.n_acc;      // (EH_MODE_TRAIN_ORD: the row is staged in LDS, over the parameter image -- dead by now)
         float* const gsh = (!ORDM && a.fz.gacc) ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
         auto put_out = [&](int e, float v) {
-            if constexpr (ORDM) __hip_atomic_store(out + eh_ord_pos(e, net.n_theta, a.ord.soff), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (write-through)
+            if constexpr (ORDM) wl[eh_ord_pos(e, net.n_theta, a.ord.soff)] = v;      // (eh_ord_publish stores it write-through)
             else out[e] = v;
         };
 #pragma unroll
@@ -2263,7 +2315,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, px_T + 4, a.stamps);
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);

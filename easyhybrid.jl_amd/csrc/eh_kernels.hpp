@@ -593,9 +593,12 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
 }
 
 // ordered fused-update mode (EhOrd, eh_device.hpp): apply the still-pending step in place -- the 16 group rows in order, the rows'
-// scalars by the reduce kernel's butterfly (every wave folds them itself), then the update as eh_reduce_kernel<true, 16> makes it
+// scalars by the reduce kernel's butterfly (every wave folds them itself), then the update as eh_reduce_kernel<true, 16> makes it.
+// The grid is at least the pending step's: every workgroup resets the rows it takes (eh_ord_reset); those past ceil(n_theta / 256) only that.
 __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_theta, float* theta, float* m, float* v, const float* sc_in, float* sc_out,
                                                            EhOpt op, float* loss_slot, EhImg im, int loss_kind) {
+    eh_ord_reset(o, blockIdx.x, gridDim.x, threadIdx.x, 256);
+    if ((int)blockIdx.x * 256 >= n_theta) return;
     const int idx = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
     const bool own = idx < n_theta;
     float gv[EH_ORD_GROUPS];

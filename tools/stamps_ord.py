@@ -45,7 +45,8 @@ for i in range(args.warmup + args.reps):
     pro = st[ST_PRO:ST_PRO + 4].reshape(2, 2)
     rows.append(dict(
         ngrp=ngrp,
-        # the last-finishing group's tail, in its shader-clock cycles: rows stored -> barrier passed -> ticket known -> rows folded -> row stored
+        # the last-finishing group's tail, in its shader-clock cycles: row staged -> barrier passed and the row's stores issued (wave 0) ->
+        # ticket known -> rows folded -> group row stored
         tail_cyc=np.diff(tail[last, :, 0]),
         tail_ns=np.diff(wall[last]) * 10,
         tail_ns_mean=(np.diff(wall[:ngrp], axis=1) * 10).mean(axis=0),
@@ -57,12 +58,12 @@ for i in range(args.warmup + args.reps):
 eng.close()
 med = lambda k: np.median(np.array([r[k] for r in rows]), axis=0)
 print(f"EH_JIT_DEFINES='{defs}'  B = {B}  groups stamped: {int(med('ngrp'))}  (median of {len(rows)} steps)")
-lab = ["barrier (+ drain)", "ticket", "rows loaded + folded", "group row stored"]
+lab = ["barrier, row stores issued", "ticket", "rows loaded + folded", "group row stored"]
 tc, tn, tm = med("tail_cyc"), med("tail_ns"), med("tail_ns_mean")
 print("  tail of the group that finishes last (cycles / ns; ns mean over the groups):")
 for k, nm in enumerate(lab):
-    print(f"    {nm:24s} {tc[k]:8.0f} cycles {tn[k]:8.0f} ns   {tm[k]:8.0f} ns")
-print(f"    {'sum':24s} {tc.sum():8.0f} cycles {tn.sum():8.0f} ns")
+    print(f"    {nm:26s} {tc[k]:8.0f} cycles {tn[k]:8.0f} ns   {tm[k]:8.0f} ns")
+print(f"    {'sum':26s} {tc.sum():8.0f} cycles {tn.sum():8.0f} ns")
 print(f"  workgroup 0 start -> last group row stored  {med('end_ns'):8.0f} ns   (workgroup 0 start -> its end {med('wg0_ns'):.0f} ns)")
 print(f"  prologue, ordered scalar fold (wave 0)      {med('fold_cyc'):8.0f} cycles {med('fold_ns'):8.0f} ns")
 pc = np.diff(np.array([r["pro_cyc"] for r in rows]), axis=1)
