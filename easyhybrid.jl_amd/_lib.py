@@ -21,6 +21,8 @@ EH_BUF_GRAD, EH_BUF_THETA, EH_BUF_OPT_M, EH_BUF_OPT_V, EH_BUF_GACC, EH_BUF_BNSTA
 
 ACTIVATIONS = {"tanh": 0, "sigmoid": 1, "relu": 2, "swish": 3, "identity": 4}
 EH_ACT_PER_NET = 5        # MultiNN: net k uses net_activation[k]
+EH_LAYER_LSTM = 16        # net_activation[l] of a hidden layer that is Recurrence(LSTMCell) (sequence models)
+EH_MAX_SEQ_WINDOW = 64
 OPT_RULES = {"Adam": 0, "AdamW": 1, "RMSProp": 2, "Descent": 3}
 TRAINING_LOSSES = {"mse": 0, "rmse": 1, "mae": 2, "nseLoss": 3, "pearsonLoss": 4, "kgeLoss": 5, "pbkgeLoss": 6}
 PAR_NEURAL, PAR_GLOBAL, PAR_FIXED = 0, 1, 2
@@ -67,6 +69,7 @@ SIGNATURES = {
     "eh_set_stream": (C.c_int32, [_H, C.c_void_p]),
     "eh_synchronize": (C.c_int32, [_H]),
     "eh_set_data": (C.c_int32, [_H, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32]),
+    "eh_set_sequences": (C.c_int32, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]),
     "eh_set_params": (C.c_int32, [_H, _F, C.c_int64]),
     "eh_get_params": (C.c_int32, [_H, _F, C.c_int64]),
     "eh_forward": (C.c_int32, [_H, C.c_int32, C.c_int64, C.c_int64, _FP, _FP]),

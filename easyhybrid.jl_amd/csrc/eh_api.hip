@@ -23,6 +23,7 @@
 #include "eh_kernels.hpp"
 #include "eh_wide.hpp"
 #include "eh_lform.hpp"
+#include "eh_seq.hpp"
 
 std::string g_create_err;
 
@@ -505,12 +506,39 @@ static void stream_pool_give(int device, hipStream_t s) {
     (void)hipStreamDestroy(s);
 }
 
+// Sequence models (EH_LAYER_LSTM in the per-layer activation slots): 0 = the descriptor has no LSTM layer, 1 = the one shape that is
+// built -- Dense(P -> I) -> LSTM(I -> H) -> Dense(H -> H) -> Dense(H -> K), eh_seq.hpp --, otherwise the status of the refusal.
+static int seq_desc_check(const eh_model_desc* d, const MechInfo& mi) {
+    if (d->activation != EH_ACT_PER_NET) return 0;
+    const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
+    int n_lstm = 0, at = -1;
+    for (int l = 0; l < na; ++l)
+        if (d->net_activation[l] == EH_LAYER_LSTM) { if (at < 0) at = l; ++n_lstm; }
+    if (!n_lstm) return 0;
+    if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a MultiNN sequence model (EH_LAYER_LSTM with n_nets = %d)", d->n_nets);
+    if (at == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_LSTM at hidden layer 0: the LSTM layer takes the Dense layer in front of it");
+    if (n_lstm > 1) return fail(nullptr, EH_EINVAL, "eh_create: %d EH_LAYER_LSTM layers (one, at hidden layer 1: stacked Recurrence layers are not built)", n_lstm);
+    if (d->n_hidden != 3 || at != 1 || d->hidden[2] != d->hidden[1])
+        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for an LSTM layer at hidden layer %d of %d (built: n_hidden = 3, hidden = [I, H, H], the LSTM at layer 1)", at, d->n_hidden);
+    if (d->hidden[0] < 1 || d->hidden[1] < 1) return fail(nullptr, EH_EINVAL, "eh_create: hidden = [%d, %d, ..]", d->hidden[0], d->hidden[1]);
+    if (d->hidden[0] > 32 || d->hidden[1] > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for LSTM widths I = %d, H = %d (built: up to 32 each)", d->hidden[0], d->hidden[1]);
+    if (d->n_predictors > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with P = %d predictors (built: up to 32)", d->n_predictors);
+    if (d->input_batchnorm) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for input BatchNorm on a sequence model (3-D input)");
+    if (d->n_targets > 1) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets (built: one)", d->n_targets);
+    if (d->mech == EH_MECH_PROGRAM || mi.n_out > 1)
+        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model around mechanistic model %d (built: the single-output registry models; no recorded closures)", d->mech);
+    return 1;
+}
+
 int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     if (!d || !out) return fail(nullptr, EH_EINVAL, "eh_create: null argument");
     *out = nullptr;
     if (d->struct_size != (int32_t)sizeof(eh_model_desc)) return fail(nullptr, EH_EINVAL, "eh_create: struct_size %d != %zu", d->struct_size, sizeof(eh_model_desc));
     MechInfo mi;
     if (!mech_info(d->mech, &mi, d)) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown mechanistic model id %d (no silent fallback)", d->mech);
+    const int seqk = (d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS) ? seq_desc_check(d, mi) : 0;
+    if (seqk < 0) return seqk;
+    const bool seq = seqk == 1;
     if (d->mech == EH_MECH_PROGRAM) {
         // every operand must name a slot that holds a value when the instruction runs: the kernel indexes a per-lane array with them
         if (d->n_params < 1 || d->n_params > EH_MAX_PARAMS) return fail(nullptr, EH_EINVAL, "eh_create: a program takes 1..%d parameters, descriptor has %d", EH_MAX_PARAMS, d->n_params);
@@ -549,6 +577,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         if (na < 1 || na > EH_MAX_HIDDEN) return fail(nullptr, EH_EINVAL, "eh_create: per-layer activations need 1..%d hidden layers (n_hidden = %d)", EH_MAX_HIDDEN, d->n_hidden);
         bool same = true;
         for (int k = 0; k < na; ++k) {
+            if (seq && d->net_activation[k] == EH_LAYER_LSTM) { same = false; continue; }
             if (d->net_activation[k] < 0 || d->net_activation[k] > EH_ACT_IDENTITY)
                 return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown activation id %d for %s %d", d->net_activation[k], d->n_nets > 0 ? "net" : "hidden layer", k);
             same = same && d->net_activation[k] == d->net_activation[0];
@@ -635,6 +664,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     if (!arch) arch = wide_arch;
     bool lform = false;
     if (no_nn) { arch = &g_lform_arch; lform = true; }
+    else if (seq) arch = &g_lform_arch;      // (its own kernel family, eh_seq.hpp; of the "architecture" only the PHI block of the image is used)
     else if (!arch) {
         // no fused kernel holds this network: run it layer by layer (eh_lform.hpp) where that form is built
         // (every activation, SingleNN and MultiNN alike: the layer-wise form runs each network as its own chain of products)
@@ -692,6 +722,16 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
             in = o;
         }
     }
+    if (seq) {      // Dense-in | weight_ih, weight_hh, bias_ih, bias_hh | head Dense | output Dense
+        const int P = d->n_predictors, I = d->hidden[0], H = d->hidden[1];
+        int* o = h->seq_off;
+        o[EH_SEQ_WIN] = 0; o[EH_SEQ_BIN] = I * P; o[EH_SEQ_WIH] = o[EH_SEQ_BIN] + I; o[EH_SEQ_WHH] = o[EH_SEQ_WIH] + 4 * H * I;
+        o[EH_SEQ_BIH] = o[EH_SEQ_WHH] + 4 * H * H; o[EH_SEQ_BHH] = o[EH_SEQ_BIH] + 4 * H; o[EH_SEQ_WHD] = o[EH_SEQ_BHH] + 4 * H;
+        o[EH_SEQ_BHD] = o[EH_SEQ_WHD] + H * H; o[EH_SEQ_WOUT] = o[EH_SEQ_BHD] + H; o[EH_SEQ_BOUT] = o[EH_SEQ_WOUT] + K * H;
+        off = o[EH_SEQ_BOUT] + K;
+        h->seq = true; h->seq_I = I; h->seq_H = H; h->seq_nbi = (I + 15) / 16; h->seq_nbh = (H + 15) / 16;
+        h->seq_act_in = d->net_activation[0]; h->seq_act_hd = d->net_activation[2];
+    }
     n.g_off = off;
     n.n_theta = off + G;
     if (lform && !no_nn) {    // Dense layers of every network: shapes and canonical offsets (no network: l_nnets stays 0)
@@ -727,7 +767,11 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     h->C = n.P + n.F + n.T;
     h->n_par = d->n_params;
     h->n_acc = n.n_theta + 1 + n.T + 2;      // [grad | S | n_valid per target | Sy | Syy]
-    if (!lform && !arch_fits(arch, std::max(h->n_acc, EH_EVAL_STATS * n.T))) {
+    if (seq && h->n_acc > eh_seq_row_cap(h->seq_nbi, h->seq_nbh)) {
+        delete h;
+        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model of %d parameters (the slab row is staged in LDS)", n.n_theta);
+    }
+    if (!lform && !seq && !arch_fits(arch, std::max(h->n_acc, EH_EVAL_STATS * n.T))) {
         // the per-wave kernel parks every wave's accumulators in LDS to sum them; the row-split kernel needs no such sum
         if (!wide_arch) {
             delete h;
@@ -737,7 +781,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         h->variant = 0;
         h->fast = 0;
     }
-    h->arch_alt = arch == wide_arch ? nullptr : wide_arch;
+    h->arch_alt = (arch == wide_arch || seq) ? nullptr : wide_arch;
 #define HIPCHK_C(expr)                                                            \
     do {                                                                          \
         hipError_t e_ = (expr);                                                   \
@@ -792,7 +836,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         for (int p = 0; p < 32; ++p) { run0[p] = 0.0f; run0[32 + p] = 1.0f; }     // LuxCore.initialstates(BatchNorm)
         HIPCHK_C(hipMemcpy(h->bn_run, run0, sizeof run0, hipMemcpyHostToDevice));
     }
-    if (!lform) {             // (the fused-update accumulators: that mode exists for the per-wave kernels only)
+    if (!lform && !seq) {     // (the fused-update accumulators: that mode exists for the per-wave kernels only)
         HIPCHK_C(hipMalloc(&h->gacc, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));      // (+4: the fused prologue reads five tail floats of every shard whatever T is)
         HIPCHK_C(hipMemset(h->gacc, 0, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));
         h->ord_soff = (n.n_theta + 3) & ~3;
@@ -816,7 +860,16 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     HIPCHK_C(hipMemset(h->inv_n, 0, EH_TT * EH_MAX_TARG * sizeof(float)));
     HIPCHK_C(hipMemset(h->gradbuf, 0, (size_t)h->n_acc * sizeof(float)));
     tick("slab + small buffers");
-    if (!lform) { if (int rc = build_maps(h, true)) { g_create_err = h->err; eh_destroy(h); return rc; } }
+    if (seq) {                // (extract_weights.jl:69-91 matches the leaves named "weight": the three Dense matrices, not weight_ih / weight_hh)
+        std::vector<unsigned char> wf((size_t)n.n_theta, 0);
+        const int* o = h->seq_off;
+        std::fill(wf.begin() + o[EH_SEQ_WIN], wf.begin() + o[EH_SEQ_BIN], (unsigned char)1);
+        std::fill(wf.begin() + o[EH_SEQ_WHD], wf.begin() + o[EH_SEQ_BHD], (unsigned char)1);
+        std::fill(wf.begin() + o[EH_SEQ_WOUT], wf.begin() + o[EH_SEQ_BOUT], (unsigned char)1);
+        HIPCHK_C(hipMalloc(&h->wflag, wf.size()));
+        HIPCHK_C(hipMemcpy(h->wflag, wf.data(), wf.size(), hipMemcpyHostToDevice));
+    }
+    else if (!lform) { if (int rc = build_maps(h, true)) { g_create_err = h->err; eh_destroy(h); return rc; } }
     else {
         std::vector<unsigned char> wf((size_t)n.n_theta, 0);
         for (int k = 0; k < h->l_nnets; ++k)
@@ -838,7 +891,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
                 for (int i = 0; i < net_w[k][l]; ++i)
                     img0[arch->wh_off + (size_t)(l - 1) * arch->hp * arch->sh + (size_t)(h->net_r0[k][l] + i) * arch->sh + h->net_r0[k][l - 1] + i] = 1.0f;
         auto put_int = [&](int slot, int v) { memcpy(&img0[arch->phi_off + slot], &v, sizeof(int)); };
-        if (!lform) {         // (read by the fused kernels' end-of-kernel reduction only; sized for their four layers)
+        if (!lform && !seq) { // (read by the fused kernels' end-of-kernel reduction only; sized for their four layers)
             for (int l = 0; l <= d->n_hidden; ++l) { put_int(EH_IMG_WOFF + l, lw_off[l]); put_int(EH_IMG_BOFF + l, lb_off[l]); }
             for (int l = 0; l < d->n_hidden; ++l) put_int(EH_IMG_WIDTH + l, tot_w[l]);
         }
@@ -854,7 +907,8 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         HIPCHK_C(hipMemset(h->l2val, 0, sizeof(float)));
         {
             int nw = 0;
-            if (lform) { for (int k = 0; k < h->l_nnets; ++k) for (int l = 0; l < h->l_net[k].nl; ++l) nw += h->l_net[k].in[l] * h->l_net[k].out[l]; }
+            if (seq) nw = (h->seq_off[EH_SEQ_BIN] - h->seq_off[EH_SEQ_WIN]) + (h->seq_off[EH_SEQ_BHD] - h->seq_off[EH_SEQ_WHD]) + (h->seq_off[EH_SEQ_BOUT] - h->seq_off[EH_SEQ_WOUT]);
+            else if (lform) { for (int k = 0; k < h->l_nnets; ++k) for (int l = 0; l < h->l_net[k].nl; ++l) nw += h->l_net[k].in[l] * h->l_net[k].out[l]; }
             else for (const EhEntry& e : enumerate_entries(h)) nw += e.col >= 0 ? 1 : 0;
             h->n_weights = nw;
         }
@@ -871,7 +925,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         tick("synchronize");
     }
 #undef HIPCHK_C
-    if (h->act == EH_ACT_PER_NET && !h->lform && !jit_entry(h)) {         // built now, so that a missing run-time compiler is an error of the constructor
+    if (h->act == EH_ACT_PER_NET && !h->lform && !h->seq && !jit_entry(h)) {         // built now, so that a missing run-time compiler is an error of the constructor
         const std::string log = h->jit_log;
         eh_destroy(h);
         return fail(nullptr, EH_EUNSUPPORTED, "eh_create: per-net activations need the run-time compiled kernel, which failed to build: %.600s", log.c_str());
@@ -895,7 +949,7 @@ int32_t eh_destroy(eh_handle* h) {
     eval_host_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
     (void)hipFree(h->stamps); (void)hipFree(h->image); (void)hipFree(h->imap); (void)hipFree(h->rmap);
-    (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs);
+    (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs); (void)hipFree(h->split[0].starts); (void)hipFree(h->split[1].starts); (void)hipFree(h->seq_ws);
     if (h->own_stream) stream_pool_give(h->device, h->own_stream);      // (drained above; the next handle on this device takes it over)
     delete h;
     return EH_OK;
@@ -931,6 +985,7 @@ int32_t eh_synchronize(eh_handle* h) {
 // target < 0: the program of every target that has none of its own; 0 <= target < T: that target's own
 static int set_loss_program(eh_handle* h, int target, const uint32_t* code, int32_t n_instr, const float* consts, int32_t n_const, int32_t out_slot, const char* who) {
     if (!h || !code || (n_const > 0 && !consts)) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "%s: recorded losses are not built for sequence models", who);
     if (n_instr < 1 || n_instr > EH_MAX_PROG) return fail(h, EH_EUNSUPPORTED, "%s: %d instructions (1..%d)", who, n_instr, EH_MAX_PROG);
     if (n_const < 0 || n_const > EH_MAX_PROG_CONST) return fail(h, EH_EUNSUPPORTED, "%s: %d constants (0..%d)", who, n_const, EH_MAX_PROG_CONST);
     auto slot_ok = [&](unsigned sl, int upto) {
@@ -1047,6 +1102,25 @@ static bool so_allowed(const eh_handle* h) {
 
 int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
     if (!h || !name) return EH_EINVAL;
+    if (h->seq) {                            // sequence models: always the reproducible step + reduce pair on the one fp32 kernel family
+        if (!strcmp(name, "fused_update")) {
+            if (value < 0 || value > 2) return fail(h, EH_EINVAL, "fused_update must be 0, 1 or 2");
+            if (value == 1) return fail(h, EH_EUNSUPPORTED, "fused_update: the one-kernel step is not built for sequence models (they run the step + reduce pair)");
+            return EH_OK;                    // (2 = "where it is reproducible": the pair is)
+        }
+        if (!strcmp(name, "multi_step") || !strcmp(name, "specialize") || !strcmp(name, "precision")) {
+            if (value) return fail(h, EH_EUNSUPPORTED, "%s: not built for sequence models (one fp32 kernel family, one launch per step)", name);
+            return EH_OK;
+        }
+        if (!strcmp(name, "fast_paths") || !strcmp(name, "row_split") || !strcmp(name, "variant") || !strcmp(name, "jit") || !strcmp(name, "aot_spec") || !strcmp(name, "bn_in_kernel")) return EH_OK;
+        if (!strcmp(name, "training_loss")) {
+            if (value < EH_LOSS_MSE || value > EH_LOSS_PROGRAM) return fail(h, EH_EUNSUPPORTED, "training_loss %lld is not implemented on the device", (long long)value);
+            if (value > EH_LOSS_NSELOSS) return fail(h, EH_EUNSUPPORTED, "training_loss %lld: sequence models train on mse, rmse, mae and nseLoss (the two-pass losses and recorded losses are not built for them)", (long long)value);
+            h->net.loss = (int)value;
+            h->net.loss_t = (unsigned)value;
+            return EH_OK;
+        }
+    }
     if (h->lform && (!strcmp(name, "fast_paths") || !strcmp(name, "row_split") || !strcmp(name, "variant") || !strcmp(name, "precision"))) {
         if (!strcmp(name, "precision") && value) return fail(h, EH_EUNSUPPORTED, "precision: the layer-wise form computes in fp32");
         return EH_OK;                        // tile / kernel-family knobs of the fused kernels: nothing to choose in the layer-wise form
@@ -1233,8 +1307,8 @@ int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, cons
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[split];
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(sp.recs);
-    sp.recs = nullptr; sp.n = 0;
+    (void)hipFree(sp.recs); (void)hipFree(sp.starts);
+    sp.recs = nullptr; sp.n = 0; sp.starts = nullptr; sp.nwin = 0;
     if (split == EH_SPLIT_TRAIN) h->perm_valid = false;
     if (n == 0) return EH_OK;
     const int C = h->C;
@@ -1376,6 +1450,30 @@ int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, cons
         HIPCHK(h, err);
     }
     sp.n = n;
+    return EH_OK;
+}
+
+int32_t eh_set_sequences(eh_handle* h, int32_t split, int32_t input_window, int32_t output_window, int32_t lead_time, const int32_t* starts, int64_t n_windows) {
+    if (!h) return EH_EINVAL;
+    if (!h->seq) return fail(h, EH_EUNSUPPORTED, "eh_set_sequences: the model has no LSTM layer (EH_LAYER_LSTM): its samples are single records");
+    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_set_sequences: split %d", split);
+    if (input_window < 1 || input_window > EH_MAX_SEQ_WINDOW) return fail(h, EH_EINVAL, "eh_set_sequences: input_window %d (1..%d)", input_window, EH_MAX_SEQ_WINDOW);
+    if (output_window < 1 || output_window > input_window) return fail(h, EH_EINVAL, "eh_set_sequences: output_window %d (1..input_window = %d)", output_window, input_window);
+    if (lead_time < 0) return fail(h, EH_EINVAL, "eh_set_sequences: lead_time %d", lead_time);
+    if (n_windows < 0 || n_windows > 0x7fffffffLL || (n_windows > 0 && !starts)) return fail(h, EH_EINVAL, "eh_set_sequences: n_windows = %lld", (long long)n_windows);
+    EhSplit& sp = h->split[split];
+    if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "eh_set_sequences: no data set for this split (call eh_set_data first)");
+    const long long last = sp.n - input_window - lead_time;      // (every row a window reads -- inputs, forcings, targets -- lies inside the series)
+    for (int64_t i = 0; i < n_windows; ++i)
+        if (starts[i] < 0 || starts[i] > last) return fail(h, EH_EINVAL, "eh_set_sequences: starts[%lld] = %d outside 0..%lld (series of %lld rows, input_window %d, lead_time %d)", (long long)i, starts[i], last, sp.n, input_window, lead_time);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    (void)hipFree(sp.starts);
+    sp.starts = nullptr; sp.nwin = 0;
+    if (split == EH_SPLIT_TRAIN) h->perm_valid = false;
+    HIPCHK(h, hipMalloc(&sp.starts, (size_t)std::max<int64_t>(n_windows, 1) * sizeof(int)));
+    if (n_windows > 0) HIPCHK(h, hipMemcpy(sp.starts, starts, (size_t)n_windows * sizeof(int), hipMemcpyHostToDevice));
+    sp.nwin = n_windows; sp.W = input_window; sp.ow = output_window; sp.lam = lead_time;
     return EH_OK;
 }
 
@@ -1978,7 +2076,45 @@ static int lform_eval(eh_handle* h, const EhSplit& sp, long long first, long lon
     return EH_OK;
 }
 
+// ---- sequence models (eh_seq.hpp) --------------------------------------------------------------------------------------------
+constexpr long long EH_SEQ_WS_CAP = 256ll << 20;      // bytes of backward workspace at most: fewer workgroups are launched when it binds
+static int seq_grid_for(const eh_handle* h, const EhSplit& sp, long long count, bool train) {
+    const long long ntiles = (count + 15) / 16;
+    long long grid = std::max<long long>(1, std::min<long long>((ntiles + EH_SEQ_NW - 1) / EH_SEQ_NW, std::min(h->max_blocks, h->slab_rows)));
+    if (train) grid = std::max<long long>(1, std::min<long long>(grid, EH_SEQ_WS_CAP / (4 * EH_SEQ_NW * eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow))));
+    return (int)grid;
+}
+static EhSeqArgs seq_args(const eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
+    EhSeqArgs a{};
+    a.recs = sp.recs; a.C = h->C; a.starts = sp.starts; a.idx = idx; a.first = first; a.count = count;
+    a.W = sp.W; a.ow = sp.ow; a.lam = sp.lam;
+    a.theta = TH(h); a.meta = h->image + h->arch->phi_off; a.slab = h->slab; a.n_acc = h->n_acc;
+    a.shift = sp.shift[0];
+    a.I = h->seq_I; a.H = h->seq_H; a.act_in = h->seq_act_in; a.act_hd = h->seq_act_hd;
+    for (int k = 0; k < EH_SEQ_NOFF; ++k) a.off[k] = h->seq_off[k];
+    return a;
+}
+static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out) {
+    if (!sp.starts) return fail(h, EH_ESTATE, "sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
+    const int grid = seq_grid_for(h, sp, count, true);
+    EhSeqArgs a = seq_args(h, sp, idx, first, count);
+    a.ws_wave = eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow);
+    const long long need = (long long)grid * EH_SEQ_NW * a.ws_wave;      // sized by the grid actually launched
+    if (need > h->seq_ws_floats) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->seq_ws);
+        h->seq_ws = nullptr; h->seq_ws_floats = 0;
+        HIPCHK(h, hipMalloc(&h->seq_ws, (size_t)need * sizeof(float)));
+        h->seq_ws_floats = need;
+    }
+    a.ws = h->seq_ws;
+    *grid_out = grid;
+    HIPCHK(h, eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, grid, h->stream, h->net, a));
+    return EH_OK;
+}
+
 static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out, bool bn_update) {
+    if (h->seq) return seq_train(h, sp, idx, first, count, grid_out);
     if (h->lform) return lform_train(h, sp, idx, first, count, grid_out, bn_update);
     const EhNet& net = h->net;
     if (net.T > 1 && !h->dp_weights) {
@@ -2227,7 +2363,7 @@ static int ensure_loss_hist(eh_handle* h, long long need) {
 
 static int check_window(eh_handle* h, const EhSplit& sp, long long first, long long count, const char* who) {
     if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "%s: no data set for this split (call eh_set_data)", who);
-    if (first < 0 || count < 0 || first + count > sp.n) return fail(h, EH_EINVAL, "%s: window [%lld, %lld) outside 0..%lld", who, first, first + count, sp.n);
+    if (first < 0 || count < 0 || first + count > sp.samples()) return fail(h, EH_EINVAL, "%s: window [%lld, %lld) outside 0..%lld", who, first, first + count, sp.samples());
     return EH_OK;
 }
 
@@ -2237,7 +2373,7 @@ static int stage_host_idx(eh_handle* h, const EhSplit& sp, const int32_t* idx, i
     if (count < 0 || first < 0) return fail(h, EH_EINVAL, "%s: first %lld, count %lld", who, (long long)first, (long long)count);
     if (h->capturing) return fail(h, EH_ESTATE, "%s: host indices cannot be recorded into a graph (upload them and pass idx_on_device = 1)", who);
     for (int64_t i = 0; i < count; ++i)
-        if (idx[first + i] < 0 || idx[first + i] >= sp.n) return fail(h, EH_EINVAL, "%s: idx[%lld] = %d outside 0..%lld", who, (long long)(first + i), idx[first + i], sp.n);
+        if (idx[first + i] < 0 || idx[first + i] >= sp.samples()) return fail(h, EH_EINVAL, "%s: idx[%lld] = %d outside 0..%lld", who, (long long)(first + i), idx[first + i], sp.samples());
     if (count > h->idx_cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         (void)hipFree(h->idx_buf);
@@ -2337,6 +2473,43 @@ static int copy_in(eh_handle* h, float* dst_dev, const float* src, size_t n) {
     return EH_OK;
 }
 
+// sequence models: `count` windows, count * ow predictions [window][j]; EVAL leaves one row of shifted sums per workgroup in the slab
+static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count, double* stats, float* const* yhat, float* const* params) {
+    if (!sp.starts) return fail(h, EH_ESTATE, "eh_eval: sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
+    const long long nout = count * sp.ow, need = (long long)((yhat ? 1 : 0) + (params ? h->n_par : 0)) * nout;
+    if (need > h->out_cap) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->out_buf);
+        h->out_buf = nullptr; h->out_cap = 0;
+        HIPCHK(h, hipMalloc(&h->out_buf, (size_t)need * sizeof(float)));
+        h->out_cap = need;
+    }
+    EhSeqArgs a = seq_args(h, sp, nullptr, first, count);
+    a.n_acc = EH_EVAL_STATS;
+    a.yhat = yhat ? h->out_buf : nullptr;
+    a.pout = params ? h->out_buf + (yhat ? nout : 0) : nullptr;
+    a.yld = nout;
+    const int grid = seq_grid_for(h, sp, count, false);
+    HIPCHK(h, eh_seq_launch(h->seq_nbi, h->seq_nbh, stats ? EH_SEQ_EVAL : EH_SEQ_FORWARD, grid, h->stream, h->net, a));
+    std::vector<float> part;
+    if (stats) {
+        part.resize((size_t)grid * EH_EVAL_STATS);
+        HIPCHK(h, hipMemcpyAsync(part.data(), h->slab, part.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (stats)
+        for (int k = 0; k < EH_EVAL_STATS; ++k) {
+            double s = 0;
+            for (int b = 0; b < grid; ++b) s += part[(size_t)b * EH_EVAL_STATS + k];
+            stats[k] = s;
+        }
+    if (yhat && yhat[0]) { if (int rc = copy_out(h, yhat[0], a.yhat, (size_t)nout)) return rc; }
+    if (params)
+        for (int j = 0; j < h->n_par; ++j)
+            if (params[j]) { if (int rc = copy_out(h, params[j], a.pout + (long long)j * nout, (size_t)nout)) return rc; }
+    return EH_OK;
+}
+
 static int do_eval(eh_handle* h, int split, long long first, long long count, double* stats, float* const* yhat, float* const* params) {
     const EhNet& net = h->net;
     EhSplit& sp = h->split[split];
@@ -2344,6 +2517,7 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
     int rc = check_window(h, sp, first, count, "eh_eval");
     if (rc) return rc;
     FLUSH(h);
+    if (h->seq) return seq_eval(h, sp, first, count, stats, yhat, params);
     const long long need = (long long)(yhat ? net.T : 0) * count + (long long)(params ? h->n_par : 0) * count;
     if (need > h->out_cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2453,6 +2627,7 @@ int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_ta
 int32_t eh_mech_loss_vjp(eh_handle* h, int64_t count, int64_t ld, const float* o_dev, const float* const* forcings_dev, const float* const* targets_dev,
                          const int64_t* n_valid_in, float* d_o_dev, float* yhat_dev, float* loss, float* grad_global, int64_t* n_valid) {
     if (!h || !o_dev || !forcings_dev || !targets_dev || !d_o_dev) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: not built for sequence models");
     const EhNet& net = h->net;
     if (net.K == 0) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: the model has no neural parameter (no NN outputs to differentiate by): eh_loss_and_grad / eh_train_step run it whole");
     if (net.loss != EH_LOSS_MSE && net.loss != EH_LOSS_MAE) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: training loss %d (built: mse, mae)", net.loss);
@@ -2739,19 +2914,19 @@ int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, i
             HIPCHK(h, hipMalloc(&bad, 2 * sizeof(unsigned)));
             HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(unsigned), h->stream));
             HIPCHK(h, hipMemsetAsync(bad + 1, 0xFF, sizeof(unsigned), h->stream));      // (position of the first offender: a minimum)
-            hipLaunchKernelGGL(eh_idx_check_kernel, dim3((unsigned)std::min<long long>(1024, (count + 255) / 256)), dim3(256), 0, h->stream, idx, (long long)first, (long long)count, (long long)sp.n, bad);
+            hipLaunchKernelGGL(eh_idx_check_kernel, dim3((unsigned)std::min<long long>(1024, (count + 255) / 256)), dim3(256), 0, h->stream, idx, (long long)first, (long long)count, (long long)sp.samples(), bad);
             unsigned res[2] = {0, 0};
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(res, bad, sizeof res, hipMemcpyDeviceToHost, h->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
             (void)hipFree(bad);
             HIPCHK(h, e);
-            if (res[0]) return fail(h, EH_EINVAL, "eh_train_step: %u of the %lld device-side indices are outside 0..%lld (first offender: idx[%lld])", res[0], (long long)count, (long long)sp.n - 1, (long long)first + (long long)res[1]);
+            if (res[0]) return fail(h, EH_EINVAL, "eh_train_step: %u of the %lld device-side indices are outside 0..%lld (first offender: idx[%lld])", res[0], (long long)count, (long long)sp.samples() - 1, (long long)first + (long long)res[1]);
         }
     } else if ((rc = check_window(h, sp, first, count, "eh_train_step"))) return rc;
     rc = ensure_loss_hist(h, 1);
     if (rc) return rc;
-    const int grid = grid_for(h, count);
+    const int grid = h->seq ? 0 : grid_for(h, count);
     bool done = false;
     if (h->fused && !(h->fused_det && grid != 1)) {
         rc = do_fused_step(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr);
@@ -2795,6 +2970,7 @@ static int make_permutation(eh_handle* h, long long N, uint64_t seed) {
 // ---- hipGraph capture of a sequence of training steps -------------------------------------------------
 int32_t eh_graph_begin(eh_handle* h) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: graph capture is not built for sequence models");
     if (h->capturing) return fail(h, EH_ESTATE, "eh_graph_begin: already capturing");
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
@@ -2860,7 +3036,8 @@ int32_t eh_train_epoch(eh_handle* h, int64_t batchsize, uint64_t seed, int32_t s
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
     if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "eh_train_epoch: no training data");
-    const long long N = sp.n;
+    if (h->seq && !sp.starts) return fail(h, EH_ESTATE, "eh_train_epoch: sequence model: no windows (call eh_set_sequences after eh_set_data)");
+    const long long N = sp.samples();      // (sequence models: the epoch shuffles and batches windows)
     if (shuffle) {
         if (int rc = make_permutation(h, N, seed)) return rc;
         h->perm_valid = false;          // (the data-parallel window order of eh_dp_shuffle is gone)
@@ -2876,7 +3053,7 @@ int32_t eh_train_epoch(eh_handle* h, int64_t batchsize, uint64_t seed, int32_t s
     } else
     for (long long s = 0; s < steps; ++s) {
         const long long first = s * batchsize, count = std::min<long long>(batchsize, N - first);
-        const int grid = grid_for(h, count);
+        const int grid = h->seq ? 0 : grid_for(h, count);
         // ("fused_update" 2: the float-atomic one-kernel step only where one workgroup covers the minibatch, the ordered one elsewhere)
         const bool one_kernel = h->fused && !(h->fused_det && grid != 1);
         bool done = false;
@@ -2937,6 +3114,7 @@ int32_t eh_set_weight_l2_coef(eh_handle* h, const float* coef, int64_t n) {
 
 int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: data parallelism is not built for sequence models");
     HIPCHK(h, hipSetDevice(h->device));
     if (!on) { h->perm_valid = false; return EH_OK; }      // (stream order keeps earlier steps on the old permutation)
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
@@ -2948,6 +3126,7 @@ int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
 
 int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: data parallelism is not built for sequence models");
     if (h->net.T != 1 && !h->tcount_ready) return fail(h, EH_ESTATE, "eh_dp_grad: multi-target model: call eh_dp_counts for this window and all-reduce EH_BUF_TCOUNT first");
     const unsigned tpm_dp = two_pass_mask(h->net);
     if (tpm_dp && h->mom_stage != 2) return fail(h, EH_ESTATE, "eh_dp_grad: rmse (multi-target) / pearson / kge training losses need the moments of the GLOBAL batch's predictions first: eh_dp_moments stage 0, all-reduce EH_BUF_MOMENT, stage 1, all-reduce");
@@ -2979,6 +3158,7 @@ int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
 // The caller all-reduces the 12 floats; eh_dp_grad turns them into the weights 1 / n_t (mse, mae) or 1 / sum (y - ybar)^2 (nseLoss).
 int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: data parallelism is not built for sequence models");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
     int rc = check_window(h, sp, first, count, "eh_dp_counts");
@@ -3004,6 +3184,7 @@ int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
 // keeps its statistics passes inside its own forward).
 int32_t eh_dp_moments(eh_handle* h, int64_t first, int64_t count, int32_t stage) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: data parallelism is not built for sequence models");
     const EhNet& net = h->net;
     if (!two_pass_mask(net)) return fail(h, EH_ESTATE, "eh_dp_moments: the training loss needs no batch moments of the predictions");
     if (h->lform) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: the layer-wise form has no data-parallel seam for the two-pass training losses");
@@ -3053,6 +3234,7 @@ int32_t eh_set_target_shift(eh_handle* h, int32_t split, const float* shift, int
 
 int32_t eh_dp_fused_step(eh_handle* h, int64_t first, int64_t count, int32_t* buffer_index) {
     if (!h || !buffer_index) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: data parallelism is not built for sequence models");
     if (!h->fused) return fail(h, EH_ESTATE, "eh_dp_fused_step: set the fused_update option first");
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: multi-target models need the global per-target counts before the pass: use eh_dp_counts + eh_dp_grad (fused_update off)");
     if (h->bn_on && !h->bn_ext) return fail(h, EH_ESTATE, "eh_dp_fused_step: input BatchNorm needs the global batch statistics: call eh_dp_bn_stats and all-reduce EH_BUF_BNSTAT first");
@@ -3077,6 +3259,7 @@ int32_t eh_set_bn_shift(eh_handle* h, const float* shift, int64_t n) {
 
 int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: data parallelism is not built for sequence models");
     if (!h->bn_on) return fail(h, EH_ESTATE, "eh_dp_bn_stats: the model has no input BatchNorm");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
@@ -3094,6 +3277,7 @@ int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
 
 int32_t eh_dp_apply(eh_handle* h, float* loss_out) {
     if (!h) return EH_EINVAL;
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: data parallelism is not built for sequence models");
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_dp_apply: call eh_opt_init first");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_loss_hist(h, 1);

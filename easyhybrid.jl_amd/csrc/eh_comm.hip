@@ -125,6 +125,7 @@ static size_t p2p_recv_words(const eh_handle* h) { return (size_t)3 * EH_GSHARDS
 static int p2p_alloc(eh_handle* h, int32_t world, int32_t rank, hipIpcMemHandle_t* handle_out, const char* who) {
     // (world == 1 is a loopback: the rank publishes to and reads from itself -- measures the cost of the machinery)
     if (world < 1 || world > EH_GSHARDS || rank < 0 || rank >= world) return fail(h, EH_EINVAL, "%s: world %d (1..%d), rank %d", who, world, EH_GSHARDS, rank);
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "%s: data parallelism is not built for sequence models", who);
     if (!h->fused) return fail(h, EH_ESTATE, "%s: set the fused_update option first", who);
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "%s: the peer-to-peer exchange is built for single-target models (use the all-reduce seam)", who);
     if (h->net.mech == EH_MECH_PROGRAM) return fail(h, EH_EUNSUPPORTED, "%s: the program kernels have no cross-GPU variant (use the all-reduce seam)", who);

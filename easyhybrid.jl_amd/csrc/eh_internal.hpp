@@ -55,6 +55,11 @@ struct EhSplit {
     float* recs = nullptr;
     long long n = 0;
     float shift[EH_MAX_TARG] = {0, 0, 0, 0};
+    // sequence models (eh_set_sequences): sample i of the split is the window of W records from starts[i]
+    int* starts = nullptr;
+    long long nwin = 0;
+    int W = 0, ow = 0, lam = 0;
+    long long samples() const { return starts ? nwin : n; }      // what first / count / idx of the entry points count
 };
 
 // kernel selector handed to EhVariant::launch: the fast-path bits, or 4 = the EH_MECH_PROGRAM kernels
@@ -131,6 +136,12 @@ struct eh_handle_s {
     bool bn_ext = false;            // bn_stat holds the statistics of the step about to run
     bool bn_dp_update = false;
     bool opt_ready = false;
+    // sequence models (eh_seq.hpp): Dense-in -> LSTM -> head Dense -> output Dense over windows (EH_LAYER_LSTM); always the step + reduce pair
+    bool seq = false;
+    int seq_I = 0, seq_H = 0, seq_nbi = 0, seq_nbh = 0, seq_act_in = 0, seq_act_hd = 0;
+    int seq_off[10] = {0};           // canonical offsets of the ten leaves (EH_SEQ_WIN .. EH_SEQ_BOUT)
+    float* seq_ws = nullptr;         // what the backward needs of every step, per wave of the grid (allocated outside graph capture)
+    long long seq_ws_floats = 0;
     // layer-wise execution form (eh_lform.hpp): networks no fused kernel holds
     bool lform = false;
     // one entry per network (SingleNN: one; MultiNN: one single-output network per neural parameter, each on its own predictor rows)

@@ -1,0 +1,478 @@
+// Sequence models: Dense(P -> I, act) -> Recurrence(LSTMCell(I -> H)) -> Dense(H -> H, act) -> Dense(H -> K) over windows of W consecutive
+// records, with back-propagation through time.  eh_step_body's idiom stretched over time:
+//
+//   * one wave owns a tile of 16 windows for the whole forward and backward chain; the window sits on the MFMA N dimension and every
+//     product runs on v_mfma_f32_16x16x4_f32.  A C/D block (lane (n = lane & 15, g = lane >> 4), register r <-> row 4g + r, window n)
+//     is the B operand of the next product when MFMA r of a 16-deep contraction takes k = 4g + r and the weight fragment is read from
+//     LDS in that order (one ds_read_b128 per lane): x_t, h_t and c_t never leave registers in the forward.
+//   * what the backward needs of step t -- the post-activation gates, c_{t-1}, tanh(c_t), and at the head steps the head's
+//     pre-activation and d loss / d o -- is parked in a workspace in global memory, in C/D register layout: every lane reads back only
+//     the 16-byte words it stored itself, so no cache-scope question arises and no fence is needed.  x_t is recomputed from the
+//     predictors (a Dense of P <= 32 inputs) instead of stored; h_{t-1} is o_{t-1} tanh(c_{t-1}) of the record before.
+//   * weight gradients contract over the 16 windows: both operands transposed through a wave-private LDS tile (window on K), the
+//     accumulators stay in registers across all steps and tiles of the wave (128 VGPRs for W_ih and W_hh at I = H = 32).
+//   * the head (head Dense, output Dense, sigma-scaling, mechanistic model, residual) runs only at the `ow` steps the loss reads.
+//   * epilogue: the workgroup's waves are gathered in wave order into one slab row [n_theta gradient | S | n | Sy | Syy]
+//     (eh_reduce_kernel's contract), so the step is bit-reproducible.
+#pragma once
+#include "eh_device.hpp"
+
+enum { EH_SEQ_TRAIN = 0, EH_SEQ_EVAL = 1, EH_SEQ_FORWARD = 2 };
+constexpr int EH_SEQ_NW = 4;                 // waves per workgroup: one per SIMD (the accumulators take most of a wave's 512 registers)
+constexpr int EH_SEQ_TS = 20;                // row stride of the transposition tile (16 windows + 4: 16-byte rows, no two rows in one bank group)
+
+// canonical offsets into flat theta (ComponentArray order) and the LDS layout of the zero-padded parameters
+enum { EH_SEQ_WIN = 0, EH_SEQ_BIN, EH_SEQ_WIH, EH_SEQ_WHH, EH_SEQ_BIH, EH_SEQ_BHH, EH_SEQ_WHD, EH_SEQ_BHD, EH_SEQ_WOUT, EH_SEQ_BOUT, EH_SEQ_NOFF };
+
+struct EhSeqArgs {
+    const float* recs;       // [n][C] records of the split: predictors | forcings | targets
+    int C;
+    const int* starts;       // window w starts at record starts[w]
+    const int* idx;          // minibatch: window idx[first + k], or first + k when null
+    long long first, count;  // in windows
+    int W, ow, lam;
+    const float* theta;      // canonical parameters
+    const float* meta;       // PHI block of the parameter image (globals, bounds)
+    float* slab;             // TRAIN: one row of n_acc floats per workgroup; EVAL: EH_EVAL_STATS floats per workgroup
+    int n_acc;
+    float* ws;               // TRAIN: ws_wave floats per wave of the grid
+    long long ws_wave;
+    float* yhat;             // FORWARD: [count][ow] predictions ...
+    float* pout;             // ... and [n_par][count * ow] parameters
+    long long yld;
+    float shift;
+    int I, H, act_in, act_hd;
+    int off[EH_SEQ_NOFF];
+};
+
+template <int NBI, int NBH>
+struct EhSeqGeom {
+    static constexpr int RI = 16 * NBI, RH = 16 * NBH, SP = 36, SI = RI + 4, SH = RH + 4;
+    static constexpr int L_WIN = 0, L_WIH = L_WIN + RI * SP, L_WHH = L_WIH + 4 * RH * SI, L_WHD = L_WHH + 4 * RH * SH, L_WOUT = L_WHD + RH * SH,
+                         L_BIN = L_WOUT + 16 * SH, L_BG = L_BIN + RI, L_BHD = L_BG + 4 * RH, L_BOUT = L_BHD + RH, L_TILE = L_BOUT + 16,
+                         L_GB = L_TILE + EH_SEQ_NW * 16 * EH_SEQ_TS, L_END = L_GB + EH_SEQ_NW * 4 * RH;
+};
+
+// floats of workspace one wave needs: 6 NBH blocks per step, NBH + 1 per head step, 256 floats a block
+inline long long eh_seq_ws_floats(int nbh, int W, int ow) { return ((long long)W * 6 * nbh + (long long)ow * (nbh + 1)) * 256; }
+int eh_seq_row_cap(int nbi, int nbh);        // accumulators a slab row may hold (the row is staged in LDS over the parameters)
+hipError_t eh_seq_launch(int nbi, int nbh, int mode, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a);
+
+#ifdef EH_SEQ_KERNELS
+// four MFMAs of one 16-deep contraction: MFMA r takes k = 4g + r of both operands
+__device__ __forceinline__ f32x4 eh_seq_mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], b[r], c, 0, 0, 0);
+    return c;
+}
+__device__ __forceinline__ f32x4 eh_seq_act4(int id, const f32x4 z) { return f32x4{eh_act_id(id, z[0]), eh_act_id(id, z[1]), eh_act_id(id, z[2]), eh_act_id(id, z[3])}; }
+__device__ __forceinline__ f32x4 eh_seq_dact4(int id, const f32x4 z) { return f32x4{eh_dact_z_id(id, z[0]), eh_dact_z_id(id, z[1]), eh_dact_z_id(id, z[2]), eh_dact_z_id(id, z[3])}; }
+__device__ __forceinline__ f32x4 eh_seq_sig4(const f32x4 z) { return f32x4{eh_sigmoid(z[0]), eh_sigmoid(z[1]), eh_sigmoid(z[2]), eh_sigmoid(z[3])}; }
+__device__ __forceinline__ f32x4 eh_seq_tanh4(const f32x4 z) { return f32x4{eh_tanh(z[0]), eh_tanh(z[1]), eh_tanh(z[2]), eh_tanh(z[3])}; }
+
+template <int NBI, int NBH, int MODE>
+__global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net, const EhSeqArgs a) {
+    using G = EhSeqGeom<NBI, NBH>;
+    constexpr bool TRAIN = MODE == EH_SEQ_TRAIN;
+    constexpr int RH = G::RH, SP = G::SP, SI = G::SI, SH = G::SH;
+    __shared__ __attribute__((aligned(16))) float lds[G::L_END];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
+    const int P = net.P, I = a.I, H = a.H, K = net.K, C = a.C;
+
+    // ---- parameters -> LDS, row-major, zero-padded to whole blocks (padding rows and columns are structural zeros) -------------
+    for (int e = tid; e < G::L_TILE; e += 64 * EH_SEQ_NW) lds[e] = 0.0f;
+    __syncthreads();
+    {
+        const float* th = a.theta;
+        for (int e = tid; e < I * P; e += 64 * EH_SEQ_NW) lds[G::L_WIN + (e % I) * SP + e / I] = th[a.off[EH_SEQ_WIN] + e];
+        for (int e = tid; e < 4 * H * I; e += 64 * EH_SEQ_NW) { const int rf = e % (4 * H); lds[G::L_WIH + ((rf / H) * RH + rf % H) * SI + e / (4 * H)] = th[a.off[EH_SEQ_WIH] + e]; }
+        for (int e = tid; e < 4 * H * H; e += 64 * EH_SEQ_NW) { const int rf = e % (4 * H); lds[G::L_WHH + ((rf / H) * RH + rf % H) * SH + e / (4 * H)] = th[a.off[EH_SEQ_WHH] + e]; }
+        for (int e = tid; e < H * H; e += 64 * EH_SEQ_NW) lds[G::L_WHD + (e % H) * SH + e / H] = th[a.off[EH_SEQ_WHD] + e];
+        for (int e = tid; e < K * H; e += 64 * EH_SEQ_NW) lds[G::L_WOUT + (e % K) * SH + e / K] = th[a.off[EH_SEQ_WOUT] + e];
+        for (int e = tid; e < I; e += 64 * EH_SEQ_NW) lds[G::L_BIN + e] = th[a.off[EH_SEQ_BIN] + e];
+        for (int e = tid; e < 4 * H; e += 64 * EH_SEQ_NW) lds[G::L_BG + (e / H) * RH + e % H] = th[a.off[EH_SEQ_BIH] + e] + th[a.off[EH_SEQ_BHH] + e];
+        for (int e = tid; e < H; e += 64 * EH_SEQ_NW) lds[G::L_BHD + e] = th[a.off[EH_SEQ_BHD] + e];
+        for (int e = tid; e < K; e += 64 * EH_SEQ_NW) lds[G::L_BOUT + e] = th[a.off[EH_SEQ_BOUT] + e];
+    }
+    __syncthreads();
+
+    float* const TT = lds + G::L_TILE + wave * 16 * EH_SEQ_TS;
+    // the gate biases' gradient: summed over the 16 windows every step and kept in a wave-private LDS row (as per-lane registers they
+    // are 32 more at H = 32, which the W_ih / W_hh accumulators leave no room for)
+    float* const GB = lds + G::L_GB + wave * 4 * RH;
+    for (int e = lane; e < 4 * RH; e += 64) GB[e] = 0.0f;
+    // C/D block -> its transpose as an MFMA operand with the window on K: element r of the result = M[row n][window 4g + r]
+    auto tr = [&](const f32x4 v) -> f32x4 {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) TT[(4 * g + r) * EH_SEQ_TS + n] = v[r];
+        EH_WAVE_SYNC();
+        const f32x4 o = *reinterpret_cast<const f32x4*>(TT + n * EH_SEQ_TS + 4 * g);
+        EH_WAVE_SYNC();
+        return o;
+    };
+    // A fragment of W[row0 + n][k0 + 4g + r] (forward products) and of the transpose, W[row0 + 4g + r][col0 + n] (delta products)
+    auto ldA = [&](int base, int stride, int row0, int k0) -> f32x4 { return *reinterpret_cast<const f32x4*>(lds + base + (row0 + n) * stride + k0 + 4 * g); };
+    auto ldAT = [&](int base, int stride, int row0, int col0) -> f32x4 {
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = lds[base + (row0 + 4 * g + r) * stride + col0 + n];
+        return o;
+    };
+    auto ldB = [&](int base, int row0) -> f32x4 { return *reinterpret_cast<const f32x4*>(lds + base + row0 + 4 * g); };      // a bias in C/D layout
+
+    // Dense-in of one record per window: pre-activation blocks zx
+    auto dense_in = [&](const float* rec, f32x4 (&zx)[NBI]) {
+        f32x4 p[2];
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { const int col = pb * 16 + 4 * g + r; p[pb][r] = col < P ? rec[col] : 0.0f; }
+#pragma unroll
+        for (int ib = 0; ib < NBI; ++ib) {
+            zx[ib] = ldB(G::L_BIN, ib * 16);
+            zx[ib] = eh_seq_mfma4(ldA(G::L_WIN, SP, ib * 16, 0), p[0], zx[ib]);
+            if (P > 16) zx[ib] = eh_seq_mfma4(ldA(G::L_WIN, SP, ib * 16, 16), p[1], zx[ib]);
+        }
+    };
+
+    // ---- accumulators (TRAIN): they live across all steps and tiles of the wave ------------------------------------------------
+    const f32x4 Z4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 gWih[4][NBH][NBI], gWhh[4][NBH][NBH], gWin[NBI][2], gBin[NBI], gWhd[NBH][NBH], gBhd[NBH], gWout[NBH], gBout = Z4;
+    float gp[EH_MAX_PARAMS], est[EH_EVAL_STATS];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int hb = 0; hb < NBH; ++hb) {
+#pragma unroll
+            for (int ib = 0; ib < NBI; ++ib) gWih[q][hb][ib] = Z4;
+#pragma unroll
+            for (int kb = 0; kb < NBH; ++kb) gWhh[q][hb][kb] = Z4;
+        }
+#pragma unroll
+    for (int ib = 0; ib < NBI; ++ib) { gWin[ib][0] = Z4; gWin[ib][1] = Z4; gBin[ib] = Z4; }
+#pragma unroll
+    for (int hb = 0; hb < NBH; ++hb) {
+        gBhd[hb] = Z4; gWout[hb] = Z4;
+#pragma unroll
+        for (int kb = 0; kb < NBH; ++kb) gWhd[hb][kb] = Z4;
+    }
+#pragma unroll
+    for (int j = 0; j < EH_MAX_PARAMS; ++j) gp[j] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < EH_EVAL_STATS; ++k) est[k] = 0.0f;      // TRAIN: [0] S, [1] Sy, [2] Syy, [3] n
+
+    const bool mae = net.loss == EH_LOSS_MAE;
+    const int W = a.W, t_head = a.W - a.ow;
+    const long long ntiles = (a.count + 15) / 16;
+    float* const ws = TRAIN ? a.ws + (long long)(blockIdx.x * EH_SEQ_NW + wave) * a.ws_wave : nullptr;
+    float* const wsh = TRAIN ? ws + (long long)W * 6 * NBH * 256 : nullptr;
+
+    for (long long tile = (long long)blockIdx.x * EH_SEQ_NW + wave; tile < ntiles; tile += (long long)gridDim.x * EH_SEQ_NW) {
+        const long long kwin = tile * 16 + n;
+        const bool live = kwin < a.count;
+        const long long kc = live ? kwin : a.count - 1;       // (a lane past the end repeats the last window; it adds nothing)
+        const int st = a.starts[a.idx ? a.idx[a.first + kc] : (int)(a.first + kc)];
+        int stT[4];                                           // the starts of windows 4g + r (operands with the window on K)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) stT[r] = __shfl(st, 4 * g + r, 64);
+
+        // ================= forward ==================================================================================
+        f32x4 h[NBH], c[NBH];
+#pragma unroll
+        for (int hb = 0; hb < NBH; ++hb) { h[hb] = Z4; c[hb] = Z4; }
+        for (int t = 0; t < W; ++t) {
+            const float* const rec = a.recs + (long long)(st + t) * C;
+            f32x4 x[NBI];
+            dense_in(rec, x);
+#pragma unroll
+            for (int ib = 0; ib < NBI; ++ib) x[ib] = eh_seq_act4(a.act_in, x[ib]);
+            f32x4 hn[NBH];
+#pragma unroll
+            for (int hb = 0; hb < NBH; ++hb) {
+                // the four gate blocks of these 16 rows are independent chains: issued interleaved, each one's dependent MFMA latency
+                // hides behind the issue of the other three
+                f32x4 z[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) z[q] = ldB(G::L_BG, q * RH + hb * 16);
+#pragma unroll
+                for (int ib = 0; ib < NBI; ++ib) {
+                    f32x4 A[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) A[q] = ldA(G::L_WIH, SI, q * RH + hb * 16, ib * 16);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], x[ib][r], z[q], 0, 0, 0);
+                }
+#pragma unroll
+                for (int kb = 0; kb < NBH; ++kb) {
+                    f32x4 A[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) A[q] = ldA(G::L_WHH, SH, q * RH + hb * 16, kb * 16);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], h[kb][r], z[q], 0, 0, 0);
+                }
+                const f32x4 gi = eh_seq_sig4(z[0]), gf = eh_seq_sig4(z[1]), gg = eh_seq_tanh4(z[2]), go = eh_seq_sig4(z[3]);
+                const f32x4 cp = c[hb];
+                c[hb] = gf * cp + gi * gg;
+                const f32x4 tc = eh_seq_tanh4(c[hb]);
+                hn[hb] = go * tc;
+                if constexpr (TRAIN) {
+                    f32x4* const w4 = reinterpret_cast<f32x4*>(ws) + ((long long)(t * NBH + hb) * 6) * 64 + lane;
+                    w4[0] = gi; w4[64] = gf; w4[128] = gg; w4[192] = go; w4[256] = cp; w4[320] = tc;
+                }
+            }
+#pragma unroll
+            for (int hb = 0; hb < NBH; ++hb) h[hb] = hn[hb];
+            if (t < t_head) continue;
+
+            // ---- head: Dense(H -> H, act), Dense(H -> K), sigma-scaling, mechanistic model, residual ----
+            const int j_out = t - t_head;
+            f32x4 z1[NBH], a1[NBH];
+#pragma unroll
+            for (int hb = 0; hb < NBH; ++hb) {
+                z1[hb] = ldB(G::L_BHD, hb * 16);
+#pragma unroll
+                for (int kb = 0; kb < NBH; ++kb) z1[hb] = eh_seq_mfma4(ldA(G::L_WHD, SH, hb * 16, kb * 16), h[kb], z1[hb]);
+                a1[hb] = eh_seq_act4(a.act_hd, z1[hb]);
+            }
+            f32x4 ob = ldB(G::L_BOUT, 0);
+#pragma unroll
+            for (int kb = 0; kb < NBH; ++kb) ob = eh_seq_mfma4(ldA(G::L_WOUT, SH, 0, kb * 16), a1[kb], ob);
+            // one window per lane (the four lane groups repeat it; group 0 does the sums)
+            float par[EH_MAX_PARAMS], sg[EH_MAX_PARAMS], dydp[EH_MAX_PARAMS], frc[EH_MAX_FORC], ovk[EH_MAX_PARAMS];
+#pragma unroll
+            for (int k = 0; k < EH_MAX_PARAMS; ++k) ovk[k] = __shfl(ob[k & 3], (k >> 2) * 16 + n, 64);      // NN output row k of this lane's window
+#pragma unroll
+            for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+                par[j] = a.meta[EH_IMG_PHI + j]; sg[j] = 0.0f; dydp[j] = 0.0f;
+                const int row = (int)((net.par_idx >> (4 * j)) & 15u);
+                float ov = 0.0f;
+#pragma unroll
+                for (int k = 0; k < EH_MAX_PARAMS; ++k) ov = row == k ? ovk[k] : ov;
+                if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_NEURAL) {
+                    if (net.scale_nn) { const float s = eh_sigmoid(ov), sc = a.meta[EH_IMG_SC + j]; par[j] = fmaf(sc, s, a.meta[EH_IMG_LO + j]); sg[j] = sc * s * (1.0f - s); }
+                    else { par[j] = ov; sg[j] = 1.0f; }
+                }
+            }
+#pragma unroll
+            for (int f = 0; f < EH_MAX_FORC; ++f) {
+                const unsigned col = (net.forc_col >> (8 * f)) & 255u;
+                frc[f] = col != 255u ? rec[P + col] : 0.0f;
+            }
+            const float y = eh_mech_eval(net.mech, par, frc, dydp);
+            const float yobs = a.recs[(long long)(st + t + a.lam) * C + P + net.F];
+            const bool valid = live && !__builtin_isnan(yobs);
+            const float r = valid ? y - yobs : 0.0f, cy = valid ? yobs - a.shift : 0.0f;
+            if constexpr (TRAIN) {
+                float d;
+                if (mae) { if (g == 0) est[0] += fabsf(r); d = r > 0.0f ? 1.0f : (r < 0.0f ? -1.0f : 0.0f); }
+                else { if (g == 0) est[0] = fmaf(r, r, est[0]); d = 2.0f * r; }
+                if (g == 0) { est[1] += cy; est[2] = fmaf(cy, cy, est[2]); est[3] += valid ? 1.0f : 0.0f; }
+                float dps[EH_MAX_PARAMS];
+#pragma unroll
+                for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+                    const float dp = valid ? d * dydp[j] : 0.0f;
+                    dps[j] = dp * sg[j];
+                    if (g == 0 && j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL) gp[j] += dp;
+                }
+                f32x4 dob = Z4;                               // d loss / d o in C/D layout: row 4g + r = NN output row
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+                    for (int j = 0; j < EH_MAX_PARAMS; ++j)
+                        if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_NEURAL && (int)((net.par_idx >> (4 * j)) & 15u) == 4 * g + rr) dob[rr] = dps[j];
+                f32x4* const w4 = reinterpret_cast<f32x4*>(wsh) + (long long)j_out * (NBH + 1) * 64 + lane;
+#pragma unroll
+                for (int hb = 0; hb < NBH; ++hb) w4[hb * 64] = z1[hb];
+                w4[NBH * 64] = dob;
+            } else if constexpr (MODE == EH_SEQ_EVAL) {
+                if (valid && g == 0) {
+                    const float ch = y - a.shift;
+                    est[0] = fmaf(r, r, est[0]); est[1] += cy; est[2] = fmaf(cy, cy, est[2]); est[3] += 1.0f;
+                    est[4] += ch; est[5] = fmaf(ch, ch, est[5]); est[6] = fmaf(ch, cy, est[6]); est[7] += fabsf(r);
+                }
+            }
+            if constexpr (!TRAIN) {
+                if (live && g == 0) {
+                    const long long o = kwin * a.ow + j_out;
+                    if (a.yhat) a.yhat[o] = y;
+                    if (a.pout)
+                        for (int j = 0; j < net.n_par; ++j) a.pout[(long long)j * a.yld + o] = par[j];
+                }
+            }
+        }
+        if constexpr (!TRAIN) continue;
+
+        // ================= backward through time ====================================================================
+        f32x4 dh[NBH], dc[NBH];
+#pragma unroll
+        for (int hb = 0; hb < NBH; ++hb) { dh[hb] = Z4; dc[hb] = Z4; }
+        for (int t = W - 1; t >= 0; --t) {
+            const float* const rec = a.recs + (long long)(st + t) * C;
+            const f32x4* const w4 = reinterpret_cast<const f32x4*>(ws) + (long long)t * NBH * 6 * 64 + lane;
+            if (t >= t_head) {
+                // ---- head backward: its delta joins dh of this step ----
+                const f32x4* const wh = reinterpret_cast<const f32x4*>(wsh) + (long long)(t - t_head) * (NBH + 1) * 64 + lane;
+                const f32x4 dob = wh[NBH * 64];
+                f32x4 z1[NBH], hT[NBH];
+#pragma unroll
+                for (int hb = 0; hb < NBH; ++hb) { z1[hb] = wh[hb * 64]; hT[hb] = tr(w4[(hb * 6 + 3) * 64] * w4[(hb * 6 + 5) * 64]); }
+                const f32x4 dobT = tr(dob);
+                gBout += dob;
+#pragma unroll
+                for (int hb = 0; hb < NBH; ++hb) {
+                    gWout[hb] = eh_seq_mfma4(dobT, tr(eh_seq_act4(a.act_hd, z1[hb])), gWout[hb]);
+                    const f32x4 dz1 = eh_seq_mfma4(ldAT(G::L_WOUT, SH, 0, hb * 16), dob, Z4) * eh_seq_dact4(a.act_hd, z1[hb]);
+                    gBhd[hb] += dz1;
+                    const f32x4 dz1T = tr(dz1);
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) {
+                        gWhd[hb][kb] = eh_seq_mfma4(dz1T, hT[kb], gWhd[hb][kb]);
+                        dh[kb] = eh_seq_mfma4(ldAT(G::L_WHD, SH, hb * 16, kb * 16), dz1, dh[kb]);
+                    }
+                }
+            }
+            // ---- the operands of this step's weight gradients, window on K ----
+            f32x4 zx[NBI], xT[NBI], hpT[NBH], dhn[NBH], dx[NBI];
+            dense_in(rec, zx);
+#pragma unroll
+            for (int ib = 0; ib < NBI; ++ib) { xT[ib] = tr(eh_seq_act4(a.act_in, zx[ib])); dx[ib] = Z4; }
+#pragma unroll
+            for (int kb = 0; kb < NBH; ++kb) {
+                f32x4 hp = Z4;
+                if (t > 0) hp = w4[(kb * 6 + 3 - NBH * 6) * 64] * w4[(kb * 6 + 5 - NBH * 6) * 64];      // h_{t-1} = o_{t-1} tanh(c_{t-1})
+                hpT[kb] = tr(hp);
+                dhn[kb] = Z4;
+            }
+#pragma unroll
+            for (int hb = 0; hb < NBH; ++hb) {
+                const f32x4 gi = w4[(hb * 6 + 0) * 64], gf = w4[(hb * 6 + 1) * 64], gg = w4[(hb * 6 + 2) * 64], go = w4[(hb * 6 + 3) * 64],
+                            cp = w4[(hb * 6 + 4) * 64], tc = w4[(hb * 6 + 5) * 64];
+                const f32x4 dcn = dc[hb] + dh[hb] * go * (1.0f - tc * tc);
+                f32x4 dz[4];
+                dz[0] = dcn * gg * gi * (1.0f - gi);
+                dz[1] = dcn * cp * gf * (1.0f - gf);
+                dz[2] = dcn * gi * (1.0f - gg * gg);
+                dz[3] = dh[hb] * tc * go * (1.0f - go);
+                dc[hb] = dcn * gf;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dz[q][r]); if (n == 0) GB[q * RH + hb * 16 + 4 * g + r] += v; }
+                    const f32x4 dzT = tr(dz[q]);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib) gWih[q][hb][ib] = eh_seq_mfma4(dzT, xT[ib], gWih[q][hb][ib]);
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) gWhh[q][hb][kb] = eh_seq_mfma4(dzT, hpT[kb], gWhh[q][hb][kb]);
+                }
+                // dh_{t-1} += W_hh^T dz, dx_t += W_ih^T dz: the four gates as interleaved chains again
+#pragma unroll
+                for (int kb = 0; kb < NBH; ++kb)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) dhn[kb] = eh_seq_mfma4(ldAT(G::L_WHH, SH, q * RH + hb * 16, kb * 16), dz[q], dhn[kb]);
+#pragma unroll
+                for (int ib = 0; ib < NBI; ++ib)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) dx[ib] = eh_seq_mfma4(ldAT(G::L_WIH, SI, q * RH + hb * 16, ib * 16), dz[q], dx[ib]);
+            }
+#pragma unroll
+            for (int kb = 0; kb < NBH; ++kb) dh[kb] = dhn[kb];
+            // ---- Dense-in ----
+#pragma unroll
+            for (int ib = 0; ib < NBI; ++ib) {
+                const f32x4 dzx = dx[ib] * eh_seq_dact4(a.act_in, zx[ib]);
+                gBin[ib] += dzx;
+                const f32x4 dzxT = tr(dzx);
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb)
+                    if (pb * 16 < P) {
+                        f32x4 pT;                              // predictor pb * 16 + n of windows 4g + r
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) pT[r] = pb * 16 + n < P ? a.recs[(long long)(stT[r] + t) * C + pb * 16 + n] : 0.0f;
+                        gWin[ib][pb] = eh_seq_mfma4(dzxT, pT, gWin[ib][pb]);
+                    }
+            }
+        }
+    }
+
+    // ================= epilogue ===========================================================================================
+    __syncthreads();                                           // every wave is through with the parameters: the row takes their place
+    if constexpr (MODE == EH_SEQ_EVAL) {
+#pragma unroll
+        for (int k = 0; k < EH_EVAL_STATS; ++k) { const float v = eh_wave_sum(est[k]); if (lane == 0) lds[wave * EH_EVAL_STATS + k] = v; }
+        __syncthreads();
+        if (tid < EH_EVAL_STATS) {
+            float s = 0.0f;
+            for (int w = 0; w < EH_SEQ_NW; ++w) s += lds[w * EH_EVAL_STATS + tid];
+            a.slab[(long long)blockIdx.x * a.n_acc + tid] = s;
+        }
+    }
+    if constexpr (TRAIN) {
+        float* const row = lds;
+        for (int e = tid; e < a.n_acc; e += 64 * EH_SEQ_NW) row[e] = 0.0f;
+        __syncthreads();
+        float sums[4], gps[EH_MAX_PARAMS];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sums[k] = eh_wave_sum(est[k]);
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) gps[j] = eh_wave_sum(gp[j]) * a.meta[EH_IMG_DPHI + j];
+        // a weight block: register r of lane (n, g) is row r0 + 4g + r (below `lim`), column c0 + n (below `ncol`) of a column-major matrix of `ld` rows
+        auto putW = [&](const f32x4& acc, int off, int ld, int rbase, int lim, int r0, int c0, int ncol) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rl = r0 + 4 * g + r, col = c0 + n;
+                if (rl < lim && col < ncol) row[off + col * ld + rbase + rl] += acc[r];
+            }
+        };
+        // a bias block: the 16 windows of a row summed over its lanes
+        auto putB = [&](const f32x4& acc, int off, int lim, int r0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = eh_row16_sum(acc[r]);
+                const int rl = r0 + 4 * g + r;
+                if (n == 0 && rl < lim) row[off + rl] += v;
+            }
+        };
+        for (int w = 0; w < EH_SEQ_NW; ++w) {                  // wave order: the sums meet in one fixed order
+            if (wave == w) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int hb = 0; hb < NBH; ++hb) {
+#pragma unroll
+                        for (int ib = 0; ib < NBI; ++ib) putW(gWih[q][hb][ib], a.off[EH_SEQ_WIH], 4 * H, q * H, H, hb * 16, ib * 16, I);
+#pragma unroll
+                        for (int kb = 0; kb < NBH; ++kb) putW(gWhh[q][hb][kb], a.off[EH_SEQ_WHH], 4 * H, q * H, H, hb * 16, kb * 16, H);
+                    }
+#pragma unroll
+                for (int ib = 0; ib < NBI; ++ib) {
+                    putW(gWin[ib][0], a.off[EH_SEQ_WIN], I, 0, I, ib * 16, 0, P);
+                    putW(gWin[ib][1], a.off[EH_SEQ_WIN], I, 0, I, ib * 16, 16, P);
+                    putB(gBin[ib], a.off[EH_SEQ_BIN], I, ib * 16);
+                }
+#pragma unroll
+                for (int hb = 0; hb < NBH; ++hb) {
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) putW(gWhd[hb][kb], a.off[EH_SEQ_WHD], H, 0, H, hb * 16, kb * 16, H);
+                    putB(gBhd[hb], a.off[EH_SEQ_BHD], H, hb * 16);
+                    putW(gWout[hb], a.off[EH_SEQ_WOUT], K, 0, K, 0, hb * 16, H);
+                }
+                putB(gBout, a.off[EH_SEQ_BOUT], K, 0);
+                for (int e = lane; e < 4 * RH; e += 64)        // b_ih and b_hh: the same gradient, written to both
+                    if (e % RH < H) { const int o = (e / RH) * H + e % RH; row[a.off[EH_SEQ_BIH] + o] += GB[e]; row[a.off[EH_SEQ_BHH] + o] += GB[e]; }
+                if (lane == 0) {
+                    row[net.n_theta] += sums[0]; row[net.n_theta + 1] += sums[3]; row[net.n_theta + 2] += sums[1]; row[net.n_theta + 3] += sums[2];
+#pragma unroll
+                    for (int j = 0; j < EH_MAX_PARAMS; ++j)
+                        if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL) row[net.g_off + (int)((net.par_idx >> (4 * j)) & 15u)] += gps[j];
+                }
+            }
+            __syncthreads();
+        }
+        for (int e = tid; e < a.n_acc; e += 64 * EH_SEQ_NW) a.slab[(long long)blockIdx.x * a.n_acc + e] = row[e];
+    }
+}
+#endif

@@ -94,6 +94,7 @@ class HybridEngine:
         self.extra_entries = []
         self.param_names = list(param_names)
         self.n_samples = {L.EH_SPLIT_TRAIN: 0, L.EH_SPLIT_VAL: 0}
+        self.seq_ow = {L.EH_SPLIT_TRAIN: 0, L.EH_SPLIT_VAL: 0}      # sequence models: output_window of the split's windows (0: samples are records)
         self.x_sum = _LazySums(lambda X, N: ((np.array([r.sum(dtype=np.float64) for r in X]) if isinstance(X, list) else X.sum(axis=1, dtype=np.float64)), N))
         self.y_sum = _LazySums(lambda ts: np.array([[np.nansum(t, dtype=np.float64), np.count_nonzero(~np.isnan(t))] for t in ts], np.float64))   # (sum, n valid) per target
         if os.environ.get("EH_MAX_BLOCKS"):               # several ranks sharing one GPU (tests): every kernel must fit beside the others
@@ -161,6 +162,17 @@ class HybridEngine:
             xp = (C.c_void_p * max(1, P))(*[r.ctypes.data for r in rows])
             self._chk(self._lib.eh_set_data(self._h, split, N, C.cast(xp, C.c_void_p), fp, tp, 4))
         self.n_samples[split] = N
+        self.seq_ow[split] = 0
+
+    def set_sequences(self, split: int, input_window: int, output_window: int, lead_time: int, starts):
+        """sequence models: sample i of `split` becomes the window of `input_window` rows from row starts[i] of the series set_data loaded
+        (sequences.split_into_sequences gives the starts).  From then on first / count / idx count windows, and forward / eval return
+        (count, output_window) arrays."""
+        starts = np.ascontiguousarray(starts, np.int32)
+        self._chk(self._lib.eh_set_sequences(self._h, split, int(input_window), int(output_window), int(lead_time),
+                                             starts.ctypes.data_as(C.POINTER(C.c_int32)), starts.size))
+        self.n_samples[split] = int(starts.size)
+        self.seq_ow[split] = int(output_window)
 
     def set_data_device(self, split: int, n: int, x_ptr: int, forcing_ptrs: Sequence[int], target_ptrs: Sequence[int], planes: bool = False):
         """Same as set_data with pointers that already live on the handle's device; x as the reference holds it -- (P x N) column-major, N
@@ -181,7 +193,13 @@ class HybridEngine:
         return out
 
     # -- forward / eval --------------------------------------------------------------------------
-    def _outs(self, count, want_yhat, want_params):
+    def _outs(self, count, want_yhat, want_params, ow=0):
+        if ow:                                # sequence models: one value per (window, j), handed back as (count, ow)
+            ys = [np.empty((count, ow), np.float32) for _ in range(self.n_targets_total)] if want_yhat else None
+            ps = [np.empty((count, ow), np.float32) for _ in range(self.n_par)] if want_params else None
+            yp = (_F * len(ys))(*[_fptr(a) for a in ys]) if ys else None
+            pp = (_F * len(ps))(*[_fptr(a) for a in ps]) if ps else None
+            return ys, ps, yp, pp
         ys = [np.empty(count, np.float32) for _ in range(self.n_targets_total)] if want_yhat else None      # (zip with target_names below: the data targets)
         ps = [np.empty(count, np.float32) for _ in range(self.n_par)] if want_params else None
         yp = (_F * len(ys))(*[_fptr(a) for a in ys]) if ys else None
@@ -190,7 +208,7 @@ class HybridEngine:
 
     def forward(self, split: int, first: int = 0, count: Optional[int] = None, params: bool = True):
         count = self.n_samples[split] - first if count is None else count
-        ys, ps, yp, pp = self._outs(count, True, params)
+        ys, ps, yp, pp = self._outs(count, True, params, self.seq_ow[split])
         self._chk(self._lib.eh_forward(self._h, split, first, count, yp, pp))
         out = dict(zip(self.target_names, ys))
         if params:
@@ -200,7 +218,7 @@ class HybridEngine:
     def eval(self, split: int, first: int = 0, count: Optional[int] = None, predictions: bool = False):
         count = self.n_samples[split] - first if count is None else count
         m = (L.TargetMetrics * self.n_targets_total)()
-        ys, _, yp, _ = self._outs(count, predictions, False)
+        ys, _, yp, _ = self._outs(count, predictions, False, self.seq_ow[split])
         self._chk(self._lib.eh_eval(self._h, split, first, count, m, yp, None))
         metrics = [{f: getattr(m[t], f) for f, _ in L.TargetMetrics._fields_} for t in range(len(self.target_names))]
         return metrics, (dict(zip(self.target_names, ys)) if predictions else None)

@@ -14,7 +14,7 @@ module EasyHybridHIP
 using Libdl
 using Random
 
-export PerTarget, set_training_loss!, set_agg!, set_weight_l2!, set_weight_l2_coef!, constructHybridModel, SingleNNHybridModel, MultiNNHybridModel, HybridModel, train, train!, HybridEngine, prepare_data, split_data, initialparameters,
+export PerTarget, set_sequences!, set_training_loss!, set_agg!, set_weight_l2!, set_weight_l2_coef!, constructHybridModel, SingleNNHybridModel, MultiNNHybridModel, HybridModel, train, train!, HybridEngine, prepare_data, split_data, initialparameters,
     Adam, AdamW, RMSProp, Descent, RbQ10, Expo_resp_model,
     LinearHM, Expo2Pool, Rs_components, Rs_components3F, FluxPartModelQ10
 
@@ -476,6 +476,18 @@ end
 dp_grad!(e::HybridEngine, first::Integer, count::Integer) = check(e, @ccall LIB[].eh_dp_grad(e.h::Ptr{Cvoid}, first::Int64, count::Int64)::Int32)
 "multi-target models under DP: this shard's per-target sums into EH_BUF_TCOUNT (buffer 6; all-reduce its 12 floats, then dp_grad!); dp_train_step! does it itself"
 dp_counts!(e::HybridEngine, first::Integer, count::Integer) = check(e, @ccall LIB[].eh_dp_counts(e.h::Ptr{Cvoid}, first::Int64, count::Int64)::Int32)
+"""
+    set_sequences!(e, starts; split, input_window = 10, output_window = 1, lead_time = 1)
+
+Sequence models (`hidden_layers = Chain(Recurrence(LSTMCell(I => H)))`, descriptor layer id `EH_LAYER_LSTM = 16`): sample `i` of `split`
+becomes the window of `input_window` rows that starts at row `starts[i]` (0-based) of the series `set_data!` loaded into that split
+(`src/data/sequences.jl:203-229`).  From then on `first`, `count` and the minibatch indices of the step, epoch, loss-and-gradient, eval and
+forward calls count windows, and the prediction arrays hold `count * output_window` values as `[window][j]`.
+"""
+set_sequences!(e::HybridEngine, starts::Vector{Int32}; split = EH_SPLIT_TRAIN, input_window::Integer = 10, output_window::Integer = 1, lead_time::Integer = 1) =
+    check(e, @ccall LIB[].eh_set_sequences(e.h::Ptr{Cvoid}, split::Int32, input_window::Int32, output_window::Int32, lead_time::Int32,
+                                            starts::Ptr{Int32}, length(starts)::Int64)::Int32)
+
 "common shift of the shifted target sums: every rank passes the same vector (e.g. the global mean of each target) after set_data!"
 set_target_shift!(e::HybridEngine, shift::Vector{Float32}; split = EH_SPLIT_TRAIN) =
     check(e, @ccall LIB[].eh_set_target_shift(e.h::Ptr{Cvoid}, split::Int32, shift::Ptr{Float32}, length(shift)::Int64)::Int32)

@@ -202,6 +202,29 @@ class Dense:
         return f"Dense({self.in_dims} => {self.out_dims}, {self.activation if isinstance(self.activation, str) else getattr(self.activation, '__name__', self.activation)})"
 
 
+class LSTMCell:
+    """Lux `LSTMCell(in => out)` as a DESCRIPTION (defaults only: use_bias = true, train_state = false, zero initial h and c)."""
+
+    def __init__(self, in_dims: int, out_dims: int):
+        self.in_dims, self.out_dims = int(in_dims), int(out_dims)
+
+    def __repr__(self):
+        return f"LSTMCell({self.in_dims} => {self.out_dims})"
+
+
+class Recurrence:
+    """Lux `Recurrence(cell; return_sequence)`.  The reference always runs it with return_sequence = true (NNModels.jl:172-176)."""
+
+    def __init__(self, cell, return_sequence: bool = True):
+        self.cell, self.return_sequence = cell, bool(return_sequence)
+
+    def __repr__(self):
+        return f"Recurrence({self.cell!r})"
+
+
+LSTM_LAYER = "lstm"      # the "activation" of a hidden layer that is Recurrence(LSTMCell): EH_LAYER_LSTM in the descriptor
+
+
 class Chain:
     """`hidden_layers::Chain` (NNModels.jl:145-219): the user gives the HIDDEN layers only; the reference wraps them as
     Dense(in_dim, first_h, activation) -> layers... -> Dense(last_h, out_dim), first_h / last_h read off the chain's own dimensions."""
@@ -220,6 +243,20 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
         ls = hidden_layers.layers
         if not ls:
             raise ValueError("hidden_layers: an empty Chain has no dimensions (NNModels.jl: 'Could not determine input dimension of hidden_layers Chain.')")
+        if any(isinstance(l, Recurrence) for l in ls):
+            # a chain that ends in Recurrence(LSTMCell) gets its sequence head (NNModels.jl:171-211):
+            # Dense(in_dim, I, act) -> Recurrence(LSTMCell(I => H)) -> RecurrenceOutputDense(H => H, act) -> Dense(H, out_dim), per time step
+            if not per_layer:
+                raise NotImplementedError("hidden_layers Chain: Recurrence layers in a MultiNN model have no device kernel (sequence models are single-network)")
+            if len(ls) != 1:
+                raise NotImplementedError(f"hidden_layers Chain: {len(ls)} layers around a Recurrence; the device kernel holds Chain(Recurrence(LSTMCell(I => H))) "
+                                          "alone (stacked or non-final Recurrence layers are not built)")
+            r = ls[0]
+            if not isinstance(r.cell, LSTMCell):
+                raise NotImplementedError(f"hidden_layers Chain: Recurrence({type(r.cell).__name__}); only LSTMCell has a device kernel")
+            if not r.return_sequence:
+                raise NotImplementedError("hidden_layers Chain: Recurrence(return_sequence = false) is not built (the reference always sets it true)")
+            return [r.cell.in_dims, r.cell.out_dims, r.cell.out_dims], [act, LSTM_LAYER, act]
         acts = [act]
         for i, l in enumerate(ls):
             if not isinstance(l, Dense):
@@ -273,8 +310,26 @@ class SingleNNHybridModel:
         return [self.NN] if self.NNs is None else [self.NNs[k] for k in self.neural_param_names]
 
     @property
+    def lstm_layer(self) -> Optional[int]:
+        """index into NN of the layer that is Recurrence(LSTMCell) (sequence models), or None"""
+        la = self.layer_activations
+        return la.index(LSTM_LAYER) if la is not None and LSTM_LAYER in la else None
+
+    def leaves(self):
+        """[(network index, layer index, leaf name, shape)] of the networks in ComponentArray order: Dense layers have `weight` (out, in) and
+        `bias`; the LSTM layer `weight_ih` (4H, I), `weight_hh` (4H, H), `bias_ih`, `bias_hh` (4H), gate blocks [i | f | g | o]"""
+        out, ll = [], self.lstm_layer
+        for k, net in enumerate(self.nets):
+            for li, (o, i) in enumerate(net):
+                if ll is not None and li == ll:
+                    out += [(k, li, "weight_ih", (4 * o, i)), (k, li, "weight_hh", (4 * o, o)), (k, li, "bias_ih", (4 * o,)), (k, li, "bias_hh", (4 * o,))]
+                else:
+                    out += [(k, li, "weight", (o, i)), (k, li, "bias", (o,))]
+        return out
+
+    @property
     def n_nn(self) -> int:
-        return sum(o * i + o for net in self.nets for o, i in net)
+        return sum(int(np.prod(shape)) for _, _, _, shape in self.leaves())
 
     @property
     def n_theta(self) -> int:
@@ -299,6 +354,10 @@ class SingleNNHybridModel:
         parts = []
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
+                if li == self.lstm_layer:      # LSTMCell: every leaf U(+-1/sqrt(H))
+                    bh = 1 / math.sqrt(o)
+                    parts += [rng.uniform(-bh, bh, shape).astype(np.float32).flatten(order="F") for _, l2, _, shape in self.leaves() if l2 == li]
+                    continue
                 gain = _ACT_GAIN[self.activation_of(k, li)] if li < len(net) - 1 else 1.0
                 bw = gain * math.sqrt(3.0 / i)
                 parts.append(rng.uniform(-bw, bw, (o, i)).astype(np.float32).flatten(order="F"))
@@ -314,10 +373,10 @@ class SingleNNHybridModel:
         """True at the flat-theta positions of the Dense weight matrices (the leaves weight_l2 sums, src/utils/extract_weights.jl:69-91)"""
         m = np.zeros(self.n_theta, bool)
         off = 0
-        for net in self.nets:
-            for o, i in net:
-                m[off:off + o * i] = True
-                off += o * i + o
+        for _, _, name, shape in self.leaves():      # (the LSTM's leaves are weight_ih / weight_hh: not matched)
+            n = int(np.prod(shape))
+            m[off:off + n] = name == "weight"
+            off += n
         return m
 
     def l2_mask(self, net=None, key: str = "weight") -> np.ndarray:
@@ -330,12 +389,11 @@ class SingleNNHybridModel:
             raise KeyError(f"weight_l2: no network named {net!r} (networks: {[n for n in names if n is not None]})")
         m = np.zeros(self.n_theta, bool)
         off = 0
-        for name, dims in zip(names, self.nets):
-            for o, i in dims:
-                if net is None or net == name:
-                    if key == "weight": m[off:off + o * i] = True
-                    else: m[off + o * i:off + o * i + o] = True
-                off += o * i + o
+        for k, _, leaf, shape in self.leaves():
+            n = int(np.prod(shape))
+            if (net is None or net == names[k]) and leaf == key:
+                m[off:off + n] = True
+            off += n
         return m
 
     def l2_coefficients(self, terms) -> np.ndarray:
@@ -350,6 +408,16 @@ class SingleNNHybridModel:
     def unpack(self, theta: np.ndarray):
         """flat theta -> (ps = [(weight (out,in), bias)...], {global: raw})"""
         off, nets = 0, []
+        if self.lstm_layer is not None:      # sequence model: the LSTM layer unpacks to a dict of its four leaves
+            layers, cur = [], {}
+            for _, li, name, shape in self.leaves():
+                n = int(np.prod(shape))
+                cur[name] = theta[off:off + n].reshape(shape, order="F") if len(shape) == 2 else theta[off:off + n]
+                off += n
+                if name in ("bias", "bias_hh"):
+                    layers.append(cur if li == self.lstm_layer else (cur["weight"], cur["bias"]))
+                    cur = {}
+            return layers, {g: theta[off + j:off + j + 1] for j, g in enumerate(self.global_param_names)}
         for net in self.nets:
             layers = []
             for o, i in net:
@@ -368,7 +436,7 @@ class SingleNNHybridModel:
         names = ["ps"] if self.NNs is None else list(self.neural_param_names)
         nets = self.nets if self.nets else [[]]
         for name, net in zip(names, nets):
-            n = sum(o * i + o for o, i in net)
+            n = self.n_nn if self.lstm_layer is not None else sum(o * i + o for o, i in net)
             out[name] = (off, off + n)
             off += n
         for g in self.global_param_names:
@@ -406,7 +474,7 @@ class SingleNNHybridModel:
         elif self.layer_activations is not None:   # an activation per hidden layer (n_nets = 0): net_activation[l] is layer l's
             d.activation = L.EH_ACT_PER_NET
             for l, a in enumerate(self.layer_activations):
-                d.net_activation[l] = L.ACTIVATIONS[a]
+                d.net_activation[l] = L.EH_LAYER_LSTM if a == LSTM_LAYER else L.ACTIVATIONS[a]
         else:
             d.activation = L.ACTIVATIONS[self.activation]
         d.scale_nn_outputs = int(self.scale_nn_outputs)

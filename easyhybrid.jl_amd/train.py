@@ -304,12 +304,21 @@ class DataConfig:
     split_data_at: float = 0.8
     folds: Any = None
     val_fold: Optional[int] = None
+    # sequence models (split_data.jl:28): dict(input_window = 10, output_window = 1, output_shift = 1, lead_time = 1) or a part of it; the
+    # series is cut into windows, the windows are filtered (filter_sequences) and THEY are split into training and validation
+    sequence_kwargs: Optional[dict] = None
 
 
-def _apply_step_mode(eng, tc: "TrainConfig"):
+def _apply_step_mode(eng, tc: "TrainConfig", seq: bool = False):
     """TrainConfig.specialize / fused_update -> engine options (single-GPU training)"""
     if tc.fused_update not in (True, False, "auto") or tc.specialize not in (True, False, "auto"):
         raise ValueError("specialize / fused_update must be True, False or 'auto'")
+    if seq:      # sequence models always run the reproducible step + reduce pair on the one kernel family: "auto" is that; True is refused by the engine
+        if tc.fused_update is True:
+            eng.set_option("fused_update", 1)
+        if tc.specialize is True:
+            eng.set_option("specialize", 1)
+        return
     if tc.fused_update is not False:
         try:
             # "auto" in a seeded run: one kernel per step only where that is bitwise reproducible (engine option value 2: minibatches one
@@ -507,8 +516,39 @@ class _EarlyUpload:
         return self.engine
 
 
-def split_data(data, model, cfg: DataConfig = DataConfig(), rng: Optional[np.random.Generator] = None):
-    """split_data.jl:8-79 -> (train, val) each ((X, forcings), targets)."""
+SEQUENCE_DEFAULTS = dict(input_window=10, output_window=1, output_shift=1, lead_time=1)      # split_data.jl:28
+
+
+def _sequence_splits(model, data, cfg: DataConfig, rng: Optional[np.random.Generator] = None):
+    """sequence models (split_data.jl:26-78): the whole series (no row is dropped), its windows filtered, and the surviving WINDOWS split
+    by split_data_at / shuffleobs -> ((X, forcings), targets), train windows, validation windows.  Both splits index the same series."""
+    from .sequences import Sequences, filter_sequences, split_into_sequences
+    kw = dict(SEQUENCE_DEFAULTS)
+    unknown = set(cfg.sequence_kwargs or {}) - set(kw)
+    if unknown:
+        raise TypeError(f"sequence_kwargs: unknown keys {sorted(unknown)} (have {sorted(kw)})")
+    kw.update(cfg.sequence_kwargs or {})
+    if cfg.split_by_id is not None or cfg.folds is not None or cfg.val_fold is not None:
+        raise NotImplementedError("sequence models: split_by_id / folds are not built (windows are split by split_data_at / shuffleobs)")
+    (X, forc), targ = prepare_data(model, data, drop_missing_rows=False)
+    seq = filter_sequences(split_into_sequences(X, np.stack([targ[t] for t in model.targets]), **kw))
+    n = len(seq.starts)
+    k = int(np.clip(round(cfg.split_data_at * n), 0, n))               # MLUtils.splitobs(at = ...)
+    idx = (rng or np.random.default_rng()).permutation(n) if cfg.shuffleobs else np.arange(n)
+
+    def pick(ix):
+        return Sequences(seq.starts[ix], seq.x[:, :, ix], seq.y[:, :, ix], seq.input_window, seq.output_window, seq.lead_time)
+    return ((X, forc), targ), pick(idx[:k]), pick(idx[k:])
+
+
+def split_data(data, model, cfg: DataConfig = DataConfig(), rng: Optional[np.random.Generator] = None, sequence_kwargs: Optional[dict] = None):
+    """split_data.jl:8-79 -> (train, val) each ((X, forcings), targets).  With sequence_kwargs (or a model with an LSTM layer): each
+    ((X, forcings), targets, windows) -- the whole series and the split's windows (sequences.Sequences)."""
+    if sequence_kwargs is not None or cfg.sequence_kwargs is not None or getattr(model, "lstm_layer", None) is not None:
+        if sequence_kwargs is not None:
+            cfg = copy.copy(cfg); cfg.sequence_kwargs = sequence_kwargs
+        series, wtr, wva = _sequence_splits(model, data, cfg, rng)
+        return (series[0], series[1], wtr), (series[0], series[1], wva)
     raw_cols = _columns(data) if not isinstance(data, tuple) else None
     (X, forc), targ = prepare_data(model, data)
     n = X.shape[1]
@@ -565,6 +605,10 @@ def _prediction_tables(eng, model, ytr, yva):
         if eng.n_samples[split] == 0:
             return {}, None
         o = eng.forward(split)
+        if eng.seq_ow[split]:                    # sequence models: one row per (window, j)
+            d = {t: np.asarray(y[t]).reshape(-1) for t in model.targets}
+            d.update({t + "_pred": o[t].reshape(-1) for t in model.targets})
+            return d, {k: v.reshape(-1) for k, v in o["parameters"].items()}
         d = {t: y[t] for t in model.targets}
         d.update({t + "_pred": o[t] for t in model.targets})
         return d, o["parameters"]
@@ -815,7 +859,17 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
     # the caller's float32 columns as they are: views, no stacked copy (4 M rows: 7 -> 1 ms); on a large table the upload starts before the
     # screen for rows to drop has finished (_EarlyUpload)
     fast, early = None, None
-    cv = None if dist_run else _column_views(model, data, dc)
+    is_seq = model.lstm_layer is not None
+    if dc.sequence_kwargs is not None and not is_seq:
+        raise ValueError("sequence_kwargs: the model has no Recurrence layer (hidden_layers = Chain(Recurrence(LSTMCell(I, H))))")
+    if is_seq and (dist_run or xfn is not None):
+        raise NotImplementedError("sequence models: data parallelism and an extra_loss of the predictions are not built")
+    wtr = wva = None
+    if is_seq:
+        ((xs, fs), ys), wtr, wva = _sequence_splits(model, data, dc, rng)
+        if len(wtr.starts) == 0:
+            return None
+    cv = None if (dist_run or is_seq) else _column_views(model, data, dc)
     if cv is not None:
         views = _take_views(model, cv[0], dc, cv[2])
         if own and cv[2] >= (1 << 20) and len(views[0][0][0][0]) > 0 and not os.environ.get("EH_NO_EARLY_UPLOAD"):      # (a large table, a training split that is not empty)
@@ -829,7 +883,10 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         fast = views if ok else None
         if not ok:
             early = None
-    (xtr, ftr, ytr), (xva, fva, yva) = [(a[0][0], a[0][1], a[1]) for a in (fast if fast is not None else split_data(data, model, dc, rng))]
+    if is_seq:       # the series goes to both splits; what the result tables call "observed" is the target of every (window, j)
+        (xtr, ftr, ytr), (xva, fva, yva) = (xs, fs, ys), (xs, fs, ys)
+    else:
+        (xtr, ftr, ytr), (xva, fva, yva) = [(a[0][0], a[0][1], a[1]) for a in (fast if fast is not None else split_data(data, model, dc, rng))]
     if (len(xtr[0]) if isinstance(xtr, list) else xtr.shape[1]) == 0:
         if early is not None:
             engine_early.close()
@@ -850,6 +907,11 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         if early is None:
             eng.set_data(L.EH_SPLIT_TRAIN, xtr, [ftr[f] for f in model.forcing], [ytr[t] for t in model.targets])
             eng.set_data(L.EH_SPLIT_VAL, xva, [fva[f] for f in model.forcing], [yva[t] for t in model.targets])
+        if is_seq:
+            for split, w in ((L.EH_SPLIT_TRAIN, wtr), (L.EH_SPLIT_VAL, wva)):
+                eng.set_sequences(split, w.input_window, w.output_window, w.lead_time, w.starts)
+            ytr = {t: ys[t][wtr.target_rows()] for t in model.targets}
+            yva = {t: ys[t][wva.target_rows()] for t in model.targets}
         if tc.timing:
             eng.synchronize()
         t_up = time.perf_counter()
@@ -863,7 +925,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         xterms = _extra_terms(tc.extra_loss)
         aggn = _agg_name(tc.agg)
         _apply_extra_loss(eng, model, xterms, aggn, eng.n_pseudo)
-        _apply_step_mode(eng, tc)
+        _apply_step_mode(eng, tc, is_seq)
         first_lt = tc.loss_types[0]
 
         def snapshot():

@@ -61,6 +61,14 @@ typedef enum eh_activation { EH_ACT_TANH = 0, EH_ACT_SIGMOID = 1, EH_ACT_RELU = 
                                                    GenericHybridModel.jl:168-176); n_nets == 0: hidden layer l of the single network uses
                                                    net_activation[l] (hidden_layers::Chain of Dense layers with activations of their own,
                                                    src/models/NNModels.jl:145-219); such kernels are compiled at run time */ } eh_activation;
+/* A value of net_activation[l] beside the eh_activation ids (activation == EH_ACT_PER_NET, n_nets == 0): hidden layer l is not a Dense
+ * layer but Recurrence(LSTMCell(hidden[l-1] -> hidden[l])), return_sequence = true (NNModels.jl:171-211).  Built: exactly one such layer,
+ * at l = 1 of n_hidden = 3 with hidden[2] == hidden[1] -- the chain Dense(P -> I, act) -> LSTM(I -> H) -> Dense(H -> H, act) -> Dense(H -> K)
+ * the reference makes of `Chain(Recurrence(LSTMCell(I => H)))`, I and H up to 32, one target, fp32.  Flat theta: Dense-in weight (I x P,
+ * column-major), bias; LSTM weight_ih (4H x I), weight_hh (4H x H), bias_ih (4H), bias_hh (4H), gate blocks [i | f | g | o]; head Dense;
+ * output Dense; globals.  Such a handle works on windows of its records: eh_set_sequences. */
+#define EH_LAYER_LSTM 16
+#define EH_MAX_SEQ_WINDOW 64  /* longest input window of a sequence model */
 
 /* registry of mechanistic models (the reference takes an arbitrary Julia closure,
  * src/models/GenericHybridModel.jl:425; a closure cannot run in a kernel, so the engine ships
@@ -206,6 +214,18 @@ int32_t eh_synchronize(eh_handle* h);
                                * (a DataFrame's), interleaved into the records without ever being stacked into a matrix on the host */
 int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, const float* const* forcings,
                     const float* const* targets, int32_t on_device);
+
+/* sequence models: sample i of `split` becomes the window starting at row starts[i] of the series eh_set_data loaded into that split */
+/* (EH_LAYER_LSTM handles only; after eh_set_data for that split, which also forgets the windows.  A window's inputs and forcings are rows
+ * starts[i] .. starts[i] + input_window - 1; prediction j < output_window is the model's output at input step input_window - output_window
+ * + j, compared with the target at row starts[i] + input_window - output_window + j + lead_time (src/data/sequences.jl:203-229,
+ * compute_loss.jl:104-110).  1 <= output_window <= input_window <= EH_MAX_SEQ_WINDOW, lead_time >= 0, every start in
+ * 0 .. n - input_window - lead_time.  From then on `first`, `count` and `idx` of eh_train_step, eh_train_epoch (which shuffles windows),
+ * eh_loss_and_grad, eh_eval and eh_forward count windows of that split, n_valid counts valid (window, j) pairs, and the prediction /
+ * parameter arrays of eh_forward / eh_eval hold count * output_window values as [window][j]: the head runs only at the steps the loss
+ * reads.) */
+int32_t eh_set_sequences(eh_handle* h, int32_t split, int32_t input_window, int32_t output_window, int32_t lead_time,
+                         const int32_t* starts, int64_t n_windows);
 
 int32_t eh_set_params(eh_handle* h, const float* theta, int64_t n);
 int32_t eh_get_params(eh_handle* h, float* theta, int64_t n);

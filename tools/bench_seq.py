@@ -1,0 +1,70 @@
+"""Time of the sequence-model training step (csrc/eh_seq.hpp): the LSTM tutorial's shape -- P = 2, I = H = 15, input_window 10,
+output_window 1, RbQ10, RMSProp -- at 128 windows per step (the tutorial's batch), 1 024 and 16 384.
+  python tools/bench_seq.py [--steps 300] [--warmup 20] [--windows 128,1024,16384] [--cpu-twin]
+--steps / --warmup as in tools/bench_config.py: `warmup` untimed steps, then `steps` timed ones between two synchronisations.
+The kernels' own time comes from the engine's events (eh_profile_enable) here and, for the record, from ONE run of this script under
+`rocprofv3 --kernel-trace --stats -- python tools/bench_seq.py --windows 128 --steps 200` (profiles/r10/seq_step.txt).
+--cpu-twin: the fp32 step of the torch restatement (tests/seq_twin.py, loss + autograd gradient) on 16 CPU threads, as context.
+One JSON line per window count."""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import easyhybrid_jl_amd as eh
+from easyhybrid_jl_amd.synthetic import RBQ10_PARAMS, make_synth_rbq10
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=300)
+ap.add_argument("--warmup", type=int, default=20)
+ap.add_argument("--windows", default="128,1024,16384")
+ap.add_argument("--input-window", type=int, default=10)
+ap.add_argument("--output-window", type=int, default=1)
+ap.add_argument("--width", type=int, default=15, help="I = H")
+ap.add_argument("--cpu-twin", action="store_true")
+a = ap.parse_args()
+W, ow, lam = a.input_window, a.output_window, 1
+model = eh.constructHybridModel(["sw_pot", "dsw_pot"], ["ta"], ["reco"], eh.RbQ10, dict(RBQ10_PARAMS), ["rb"], ["Q10"],
+                                hidden_layers=eh.Chain(eh.Recurrence(eh.LSTMCell(a.width, a.width))), activation="tanh", scale_nn_outputs=True)
+counts = [int(c) for c in a.windows.split(",")]
+nb = 4                                            # minibatches the steps rotate through
+rows = nb * max(counts) + W + lam
+cols = make_synth_rbq10(rows, 1, 0.05)
+X = np.stack([cols["sw_pot"], cols["dsw_pot"]]) / np.float32(50)
+starts = np.arange(rows - W - lam + 1, dtype=np.int32)
+theta = model.initialparameters(1)
+nbh = (a.width + 15) // 16
+for B in counts:
+    eng = model.engine(0)
+    eng.set_data(0, X, [cols["ta"]], [cols["reco"]])
+    eng.set_sequences(0, W, ow, lam, starts)
+    eng.set_params(theta)
+    eng.opt_init("RMSProp", 0.01)
+
+    def run(n, base=0):
+        for s in range(n):
+            eng.train_step(((base + s) % nb) * B, B, want_loss=False)
+    run(a.warmup); eng.synchronize()
+    t0 = time.perf_counter(); run(a.steps, a.warmup); eng.synchronize(); dt = time.perf_counter() - t0
+    eng.profile_enable(True)
+    run(min(a.steps, 200)); eng.synchronize()
+    _, k_step, k_reduce = eng.profile_read()
+    eng.profile_enable(False)
+    tiles = (B + 15) // 16
+    grid = max(1, min((tiles + 3) // 4, 256))
+    out = {"windows": B, "input_window": W, "output_window": ow, "I": a.width, "H": a.width, "n_theta": model.n_theta, "us_per_step": 1e6 * dt / a.steps,
+           "windows_per_s": B * a.steps / dt, "step_kernel_us": 1e3 * k_step, "reduce_kernel_us": 1e3 * k_reduce, "workgroups": grid,
+           "tiles_per_wave": -(-tiles // (4 * grid)), "workspace_bytes": grid * 4 * (W * 6 * nbh + ow * (nbh + 1)) * 1024, "final_loss": eng.train_step(0, B)}
+    if a.cpu_twin:
+        import torch
+        from tests import seq_twin as tw
+        torch.set_num_threads(16)
+        f = {"ta": cols["ta"]}
+        for _ in range(2):
+            tw.loss_and_grad(model, theta, X, f, cols["reco"], starts[:B], W, ow, lam, "mse", torch.float32)
+        n = 5
+        t0 = time.perf_counter()
+        for _ in range(n):
+            tw.loss_and_grad(model, theta, X, f, cols["reco"], starts[:B], W, ow, lam, "mse", torch.float32)
+        out["cpu_twin_fp32_16_threads_us"] = 1e6 * (time.perf_counter() - t0) / n
+    print(json.dumps(out))
+    eng.close()
