@@ -508,7 +508,7 @@ static void stream_pool_give(int device, hipStream_t s) {
 
 // Sequence models (EH_LAYER_LSTM in the per-layer activation slots): 0 = the descriptor has no LSTM layer, 1 = the one shape that is
 // built -- Dense(P -> I) -> LSTM(I -> H) -> Dense(H -> H) -> Dense(H -> K), eh_seq.hpp --, otherwise the status of the refusal.
-static int seq_desc_check(const eh_model_desc* d, const MechInfo& mi) {
+static int seq_desc_check(const eh_model_desc* d) {
     if (d->activation != EH_ACT_PER_NET) return 0;
     const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
     int n_lstm = 0, at = -1;
@@ -525,9 +525,7 @@ static int seq_desc_check(const eh_model_desc* d, const MechInfo& mi) {
     if (d->n_predictors > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with P = %d predictors (built: up to 32)", d->n_predictors);
     if (d->input_batchnorm) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for input BatchNorm on a sequence model (3-D input)");
     if (d->n_targets > 1) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets (built: one)", d->n_targets);
-    if (d->mech == EH_MECH_PROGRAM || mi.n_out > 1)
-        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model around mechanistic model %d (built: the single-output registry models; no recorded closures)", d->mech);
-    return 1;
+    return 1;                                // (around every mechanistic model: registry, several outputs -- the one target names its output --, recorded closure)
 }
 
 int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
@@ -536,7 +534,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     if (d->struct_size != (int32_t)sizeof(eh_model_desc)) return fail(nullptr, EH_EINVAL, "eh_create: struct_size %d != %zu", d->struct_size, sizeof(eh_model_desc));
     MechInfo mi;
     if (!mech_info(d->mech, &mi, d)) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown mechanistic model id %d (no silent fallback)", d->mech);
-    const int seqk = (d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS) ? seq_desc_check(d, mi) : 0;
+    const int seqk = (d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS) ? seq_desc_check(d) : 0;
     if (seqk < 0) return seqk;
     const bool seq = seqk == 1;
     if (d->mech == EH_MECH_PROGRAM) {
@@ -1112,7 +1110,8 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
             if (value) return fail(h, EH_EUNSUPPORTED, "%s: not built for sequence models (one fp32 kernel family, one launch per step)", name);
             return EH_OK;
         }
-        if (!strcmp(name, "fast_paths") || !strcmp(name, "row_split") || !strcmp(name, "variant") || !strcmp(name, "jit") || !strcmp(name, "aot_spec") || !strcmp(name, "bn_in_kernel")) return EH_OK;
+        if (!strcmp(name, "fast_paths") || !strcmp(name, "row_split") || !strcmp(name, "variant") || !strcmp(name, "aot_spec") || !strcmp(name, "bn_in_kernel")) return EH_OK;
+        if (!strcmp(name, "jit")) { h->jit_on = value != 0; return EH_OK; }      // a recorded closure: 1 = the kernels compiled around the program once built (seq_jit_entry), 0 = the interpreter
         if (!strcmp(name, "training_loss")) {
             if (value < EH_LOSS_MSE || value > EH_LOSS_PROGRAM) return fail(h, EH_EUNSUPPORTED, "training_loss %lld is not implemented on the device", (long long)value);
             if (value > EH_LOSS_NSELOSS) return fail(h, EH_EUNSUPPORTED, "training_loss %lld: sequence models train on mse, rmse, mae and nseLoss (the two-pass losses and recorded losses are not built for them)", (long long)value);
@@ -2092,7 +2091,70 @@ static EhSeqArgs seq_args(const eh_handle* h, const EhSplit& sp, const int* idx,
     a.shift = sp.shift[0];
     a.I = h->seq_I; a.H = h->seq_H; a.act_in = h->seq_act_in; a.act_hd = h->seq_act_hd;
     for (int k = 0; k < EH_SEQ_NOFF; ++k) a.off[k] = h->seq_off[k];
+    a.prog = h->prog;
     return a;
+}
+// A sequence model around a recorded closure: its (NBI, NBH) kernels compiled at run time around the generated program (eh_jit.hpp), built
+// on first use.  nullptr = not wanted ("jit" = 0) or not available: a build that fails is reported by eh_jit_status and the handle goes on
+// with the interpreting kernels built ahead of time.
+static eh_handle_s::JitEntry* seq_jit_entry(eh_handle* h) {
+    if (h->net.mech != EH_MECH_PROGRAM || !h->jit_on || h->jit_failed) return nullptr;
+    if (!h->jit.empty()) return h->jit[0]->state.load(std::memory_order_acquire) > 0 ? h->jit[0].get() : nullptr;
+    h->jit.emplace_back(new eh_handle_s::JitEntry());
+    eh_handle_s::JitEntry* je = h->jit.back().get();
+    je->arch = h->arch; je->variant = 0; je->fast = 0; je->spec = false; je->p2p = false; je->net = h->net; je->loss_gen = 0;
+    const bool ok = eh_jit_build_seq(h->desc, h->seq_nbi, h->seq_nbh, &je->k, &je->log);
+    je->state.store(ok ? 1 : -1, std::memory_order_release);
+    if (!ok) { h->jit_log = je->log; h->jit_failed = true; return nullptr; }
+    return je;
+}
+// The compiled kernels take over from the interpreter once their training pass has agreed with it on a minibatch of the user's own data:
+// both run the pass (nothing but slab and workspace is written), and loss sum, valid count and un-normalised gradient, summed over the
+// slab rows, must agree to 1e-5 of the gradient's largest entry (jit_verify's bar).  The two are the same arithmetic, but the compiled one
+// is another binary from another compiler run, at the register pressure of these kernels (the run-time compiler that ships with PyTorch
+// spills in TRAIN at NBI = NBH = 2, where the one of the build does not); the build's own errors only catch refusals.  On disagreement the
+// handle stays on the interpreter and says so in eh_jit_status.  A minibatch without a valid target decides nothing: the next one does.
+static void seq_jit_verify(eh_handle* h, eh_handle_s::JitEntry* je, int grid, const EhSeqArgs& a) {
+    const EhNet& net = h->net;
+    const size_t n = (size_t)grid * a.n_acc;
+    std::vector<float> part[2] = {std::vector<float>(n), std::vector<float>(n)};
+    bool ran = true;
+    for (int k = 0; k < 2 && ran; ++k) {
+        ran = (k == 0 ? eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a)
+                      : eh_jit_launch_seq(&je->k, EH_SEQ_TRAIN, grid, h->stream, &net, &a)) == hipSuccess &&
+              hipMemcpyAsync(part[k].data(), a.slab, n * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+    }
+    ran = ran && hipStreamSynchronize(h->stream) == hipSuccess;
+    std::string why;
+    if (!ran) { (void)hipGetLastError(); why = "the run-time compiled sequence kernel could not be run next to the interpreter: the handle keeps the interpreter"; }
+    else {
+        auto col = [&](int k, int i) { double s = 0; for (int b = 0; b < grid; ++b) s += part[k][(size_t)b * a.n_acc + i]; return s; };
+        double gmax = 0.0, dmax = 0.0;
+        for (int i = 0; i < net.n_theta; ++i) { const double x = col(0, i), y = col(1, i); gmax = std::max(gmax, fabs(x)); dmax = std::max(dmax, fabs(x - y)); }
+        const double sa = col(0, net.n_theta), sb = col(1, net.n_theta) * (getenv("EH_DEBUG_JIT_SKEW") ? 1.01 : 1.0);      // (tests: the fall-back path)
+        const bool counts = col(0, net.n_theta + 1) == col(1, net.n_theta + 1);
+        if (counts && col(0, net.n_theta + 1) == 0.0) return;
+        if (dmax <= 1e-5 * gmax + 1e-30 && fabs(sa - sb) <= 1e-5 * fabs(sa) + 1e-30 && counts && std::isfinite(gmax)) { je->verified = true; return; }
+        char b[320];
+        snprintf(b, sizeof b, "the sequence kernel compiled at run time disagrees with the interpreter on %lld windows of this model's data (gradient: max |difference| %.3g "
+                 "against a largest entry of %.3g; loss sum %.9g vs %.9g; valid counts %s): the handle keeps the interpreter", a.count, dmax, gmax, sb, sa, counts ? "equal" : "DIFFERENT");
+        why = b;
+    }
+    je->state.store(-1); h->jit_failed = true; h->jit_log = why;
+}
+static hipError_t seq_launch(eh_handle* h, int mode, int grid, const EhSeqArgs& a) {
+    if (eh_handle_s::JitEntry* je = seq_jit_entry(h)) {
+        if (mode == EH_SEQ_TRAIN && !je->verified) seq_jit_verify(h, je, grid, a);
+    }
+    if (eh_handle_s::JitEntry* je = seq_jit_entry(h)) {
+        const hipError_t e = eh_jit_launch_seq(&je->k, mode, grid, h->stream, &h->net, &a);
+        if (e == hipSuccess) return e;
+        (void)hipGetLastError();
+        je->state.store(-1); h->jit_failed = true;
+        h->jit_log = std::string("launch of the run-time compiled sequence kernel failed: ") + hipGetErrorString(e);
+    }
+    const int head = h->net.mech == EH_MECH_PROGRAM ? EH_SEQ_HEAD_PROG : (h->net.n_out > 1 ? EH_SEQ_HEAD_MULTI : EH_SEQ_HEAD_MECH);
+    return eh_seq_launch(h->seq_nbi, h->seq_nbh, mode, head, grid, h->stream, h->net, a);
 }
 static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out) {
     if (!sp.starts) return fail(h, EH_ESTATE, "sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
@@ -2109,7 +2171,7 @@ static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long 
     }
     a.ws = h->seq_ws;
     *grid_out = grid;
-    HIPCHK(h, eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, grid, h->stream, h->net, a));
+    HIPCHK(h, seq_launch(h, EH_SEQ_TRAIN, grid, a));
     return EH_OK;
 }
 
@@ -2490,7 +2552,7 @@ static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count,
     a.pout = params ? h->out_buf + (yhat ? nout : 0) : nullptr;
     a.yld = nout;
     const int grid = seq_grid_for(h, sp, count, false);
-    HIPCHK(h, eh_seq_launch(h->seq_nbi, h->seq_nbh, stats ? EH_SEQ_EVAL : EH_SEQ_FORWARD, grid, h->stream, h->net, a));
+    HIPCHK(h, seq_launch(h, stats ? EH_SEQ_EVAL : EH_SEQ_FORWARD, grid, a));
     std::vector<float> part;
     if (stats) {
         part.resize((size_t)grid * EH_EVAL_STATS);

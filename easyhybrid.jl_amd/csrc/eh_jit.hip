@@ -147,6 +147,29 @@ std::string const_decls(const float* c, int n) {
     }
     return s;
 }
+// hiprtcCompileProgram + what comes out of it: the code object, the lowered names of `names`, the compiler's log; a build that
+// succeeded goes to the disk cache (cpath, may be empty).  false: the compiler refused, `log` says why.
+bool compile_and_cache(hiprtcProgram hp, const std::vector<const char*>& opts, const char* const* names, int n, const std::string& cpath,
+                       std::vector<std::string>* lowered, std::vector<char>* code, std::string* log) {
+    lowered->clear();
+    const hiprtcResult rc = hiprtcCompileProgram(hp, (int)opts.size(), const_cast<const char**>(opts.data()));
+    size_t ls = 0;
+    hiprtcGetProgramLogSize(hp, &ls);
+    if (ls > 1) { log->resize(ls); hiprtcGetProgramLog(hp, &(*log)[0]); }
+    if (rc != HIPRTC_SUCCESS) { *log = std::string("hiprtc: ") + hiprtcGetErrorString(rc) + "\n" + *log; return false; }
+    size_t cs = 0;
+    hiprtcGetCodeSize(hp, &cs);
+    code->resize(cs);
+    hiprtcGetCode(hp, code->data());
+    bool names_ok = true;
+    for (int m = 0; m < n; ++m) {
+        const char* ln = nullptr;
+        names_ok = names_ok && hiprtcGetLoweredName(hp, names[m], &ln) == HIPRTC_SUCCESS && ln;
+        lowered->push_back(ln ? ln : "");
+    }
+    if (names_ok && !cpath.empty()) cache_store(cpath, *lowered, *code);
+    return true;
+}
 }   // namespace
 
 static std::string eh_jit_loss_one(const EhLossProg1& lp, const char* fname) {
@@ -430,13 +453,9 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
         if (at != std::string::npos) fprintf(stderr, "eh_jit: %s\n", src.substr(at, src.find('\n', at) - at).c_str());
     }
     if (!from_cache) {
-        lowered.clear();
-        const hiprtcResult rc = hiprtcCompileProgram(hp, (int)opts.size(), opts.data());
-        size_t ls = 0;
-        hiprtcGetProgramLogSize(hp, &ls);
-        if (ls > 1) { log->resize(ls); hiprtcGetProgramLog(hp, &(*log)[0]); }
-        if (rc != HIPRTC_SUCCESS) {
-            *log = std::string("hiprtc: ") + hiprtcGetErrorString(rc) + "\n" + *log;
+        const char* names[5];
+        for (int m = 0; m < nmode; ++m) names[m] = name[m];
+        if (!compile_and_cache(hp, opts, names, nmode, cpath, &lowered, &code, log)) {
             hiprtcDestroyProgram(&hp);
             const int next = (g_jit_level == 0 && slp_on) ? 1 : (g_jit_level < 2 ? 2 : 3);
             if (next <= 2) {
@@ -450,17 +469,6 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
             }
             return false;
         }
-        size_t cs = 0;
-        hiprtcGetCodeSize(hp, &cs);
-        code.resize(cs);
-        hiprtcGetCode(hp, code.data());
-        bool names_ok = true;
-        for (int m = 0; m < nmode; ++m) {
-            const char* ln = nullptr;
-            names_ok = names_ok && hiprtcGetLoweredName(hp, name[m], &ln) == HIPRTC_SUCCESS && ln;
-            lowered.push_back(ln ? ln : "");
-        }
-        if (names_ok && !cpath.empty()) cache_store(cpath, lowered, code);
     }
     bool ok = hipModuleLoadData(&out->mod, code.data()) == hipSuccess;
     for (int i = 0; i < nmode && ok; ++i) {
@@ -490,6 +498,63 @@ hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t s
     }
     const size_t lds = (mode == EH_MODE_EVAL && k->lds_eval_bytes) ? k->lds_eval_bytes : k->lds_bytes;
     return hipModuleLaunchKernel(k->fn[mode], (unsigned)grid, 1, 1, 64u * (unsigned)k->nw, 1, 1, (unsigned)lds, stream, params, nullptr);
+}
+
+bool eh_jit_build_seq(const eh_model_desc& d, int nbi, int nbh, EhJitKernel* out, std::string* log) {
+    if (d.mech != EH_MECH_PROGRAM) { *log = "eh_jit_build_seq: not a recorded closure"; return false; }
+    const std::string mech = eh_jit_mech_source(d);
+    const std::string src = "typedef signed char int8_t; typedef unsigned char uint8_t; typedef int int32_t; typedef unsigned int uint32_t;\n"
+                            "typedef long long int64_t; typedef unsigned long long uint64_t;\n"
+                            "#define EH_JIT_MECH 1\n#define EH_SEQ_KERNELS 1\n#include \"eh_seq.hpp\"\n";
+    const char* hnames[4] = {"eh_seq.hpp", "eh_device.hpp", "easyhybrid_hip.h", "eh_jit_mech.inc"};
+    const char* hsrc[4] = {eh_src_seq, eh_src_device, eh_src_public, mech.c_str()};
+    hiprtcProgram hp = nullptr;
+    if (hiprtcCreateProgram(&hp, src.c_str(), "eh_jit_seq.hip", 4, hsrc, hnames) != HIPRTC_SUCCESS) { *log = "hiprtcCreateProgram failed"; return false; }
+    const int modes[3] = {EH_SEQ_TRAIN, EH_SEQ_EVAL, EH_SEQ_FORWARD};
+    char name[3][96];
+    for (int i = 0; i < 3; ++i) {
+        snprintf(name[i], sizeof name[i], "eh_seq_kernel<%d, %d, %d, %d>", nbi, nbh, modes[i], (int)EH_SEQ_HEAD_PROG);
+        hiprtcAddNameExpression(hp, name[i]);
+    }
+    const std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17"};      // the flags of the Makefile
+    std::string cpath;
+    {
+        const std::string dir = cache_dir();
+        if (!dir.empty()) {
+            unsigned long long h = 1469598103934665603ull;
+            int ver[2] = {0, 0};
+            hiprtcVersion(&ver[0], &ver[1]);
+            h = fnv(h, ver, sizeof ver);
+            h = fnv(h, src.data(), src.size()); h = fnv(h, mech.data(), mech.size());
+            h = fnv(h, eh_src_seq, sizeof eh_src_seq); h = fnv(h, eh_src_device, sizeof eh_src_device); h = fnv(h, eh_src_public, sizeof eh_src_public);
+            for (int m = 0; m < 3; ++m) h = fnv(h, name[m], strlen(name[m]));
+            for (const char* o : opts) h = fnv(h, o, strlen(o));
+            char fn[64];
+            snprintf(fn, sizeof fn, "/%016llx.eco", h);
+            cpath = dir + fn;
+        }
+    }
+    std::vector<std::string> lowered;
+    std::vector<char> code;
+    const bool from_cache = !cpath.empty() && cache_load(cpath, 3, &lowered, &code);
+    if (getenv("EH_JIT_TRACE")) fprintf(stderr, "eh_jit: %s | %s | cache %s\n", name[0], cpath.c_str(), from_cache ? "hit" : "miss");
+    const char* const names[3] = {name[0], name[1], name[2]};
+    if (!from_cache && !compile_and_cache(hp, opts, names, 3, cpath, &lowered, &code, log)) { hiprtcDestroyProgram(&hp); return false; }
+    bool ok = hipModuleLoadData(&out->mod, code.data()) == hipSuccess;
+    for (int i = 0; i < 3 && ok; ++i) ok = !lowered[i].empty() && hipModuleGetFunction(&out->fn[modes[i]], out->mod, lowered[i].c_str()) == hipSuccess;
+    if (!ok && from_cache) (void)unlink(cpath.c_str());       // a stale or damaged entry: gone, the next build compiles
+    (void)hipGetLastError();
+    hiprtcDestroyProgram(&hp);
+    if (!ok) { *log = "hipModuleLoadData / hipModuleGetFunction failed for the compiled sequence kernels"; eh_jit_release(out); return false; }
+    out->nw = EH_SEQ_NW;
+    out->lds_bytes = out->lds_eval_bytes = 0;                 // (the kernels' LDS is static)
+    return true;
+}
+
+hipError_t eh_jit_launch_seq(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhSeqArgs* args) {
+    void* params[] = {const_cast<EhNet*>(net), const_cast<EhSeqArgs*>(args)};
+    if (mode < EH_SEQ_TRAIN || mode > EH_SEQ_FORWARD || !k->fn[mode]) return hipErrorNotSupported;
+    return hipModuleLaunchKernel(k->fn[mode], (unsigned)grid, 1, 1, 64u * EH_SEQ_NW, 1, 1, 0, stream, params, nullptr);
 }
 
 void eh_jit_release(EhJitKernel* k) {

@@ -12,12 +12,19 @@
 //   * weight gradients contract over the 16 windows: both operands transposed through a wave-private LDS tile (window on K), the
 //     accumulators stay in registers across all steps and tiles of the wave (128 VGPRs for W_ih and W_hh at I = H = 32).
 //   * the head (head Dense, output Dense, sigma-scaling, mechanistic model, residual) runs only at the `ow` steps the loss reads.
+//     Its mechanistic stage comes in three forms (template parameter HEAD): a single-output registry model (eh_mech_eval), a registry
+//     model with several outputs (eh_mech_extra gives the target's output and its Jacobian row), and a recorded closure
+//     (EH_MECH_PROGRAM).  The closure's tape is per lane and lives only within the head step: the reverse sweep runs right there, seeded
+//     with d loss / d yhat at the target's output, and leaves the per-parameter adjoint where d * dydp[j] stands for the registry models
+//     -- nothing of the tape is parked in the workspace.  Built ahead of time the program is interpreted (the tape in scratch memory);
+//     compiled at run time around the generated eh_jit_fwd / eh_jit_rev (eh_jit.hip, EH_JIT_MECH) the tape is registers.
 //   * epilogue: the workgroup's waves are gathered in wave order into one slab row [n_theta gradient | S | n | Sy | Syy]
 //     (eh_reduce_kernel's contract), so the step is bit-reproducible.
 #pragma once
 #include "eh_device.hpp"
 
 enum { EH_SEQ_TRAIN = 0, EH_SEQ_EVAL = 1, EH_SEQ_FORWARD = 2 };
+enum { EH_SEQ_HEAD_MECH = 0, EH_SEQ_HEAD_MULTI = 1, EH_SEQ_HEAD_PROG = 2 };      // the mechanistic stage of the head: see above
 constexpr int EH_SEQ_NW = 4;                 // waves per workgroup: one per SIMD (the accumulators take most of a wave's 512 registers)
 constexpr int EH_SEQ_TS = 20;                // row stride of the transposition tile (16 windows + 4: 16-byte rows, no two rows in one bank group)
 
@@ -43,6 +50,7 @@ struct EhSeqArgs {
     float shift;
     int I, H, act_in, act_hd;
     int off[EH_SEQ_NOFF];
+    const unsigned* prog;    // EH_SEQ_HEAD_PROG: the recorded closure (EhStepArgs::prog layout)
 };
 
 template <int NBI, int NBH>
@@ -53,10 +61,13 @@ struct EhSeqGeom {
                          L_GB = L_TILE + EH_SEQ_NW * 16 * EH_SEQ_TS, L_END = L_GB + EH_SEQ_NW * 4 * RH;
 };
 
+#ifndef __HIPCC_RTC__      // (host side; this header is also compiled at run time, by hiprtc, around a recorded closure: eh_jit.hip)
 // floats of workspace one wave needs: 6 NBH blocks per step, NBH + 1 per head step, 256 floats a block
 inline long long eh_seq_ws_floats(int nbh, int W, int ow) { return ((long long)W * 6 * nbh + (long long)ow * (nbh + 1)) * 256; }
 int eh_seq_row_cap(int nbi, int nbh);        // accumulators a slab row may hold (the row is staged in LDS over the parameters)
-hipError_t eh_seq_launch(int nbi, int nbh, int mode, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a);
+// head: EH_SEQ_HEAD_* of the model (a missing instantiation is an error, never another path)
+hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a);
+#endif
 
 #ifdef EH_SEQ_KERNELS
 // four MFMAs of one 16-deep contraction: MFMA r takes k = 4g + r of both operands
@@ -70,12 +81,14 @@ __device__ __forceinline__ f32x4 eh_seq_dact4(int id, const f32x4 z) { return f3
 __device__ __forceinline__ f32x4 eh_seq_sig4(const f32x4 z) { return f32x4{eh_sigmoid(z[0]), eh_sigmoid(z[1]), eh_sigmoid(z[2]), eh_sigmoid(z[3])}; }
 __device__ __forceinline__ f32x4 eh_seq_tanh4(const f32x4 z) { return f32x4{eh_tanh(z[0]), eh_tanh(z[1]), eh_tanh(z[2]), eh_tanh(z[3])}; }
 
-template <int NBI, int NBH, int MODE>
+template <int NBI, int NBH, int MODE, int HEAD = EH_SEQ_HEAD_MECH>
 __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net, const EhSeqArgs a) {
     using G = EhSeqGeom<NBI, NBH>;
-    constexpr bool TRAIN = MODE == EH_SEQ_TRAIN;
+    constexpr bool TRAIN = MODE == EH_SEQ_TRAIN, PROG = HEAD == EH_SEQ_HEAD_PROG;
     constexpr int RH = G::RH, SP = G::SP, SI = G::SI, SH = G::SH;
-    __shared__ __attribute__((aligned(16))) float lds[G::L_END];
+    // (a closure's tape takes registers at the head step that the registry models leave free: with PROG the gradient of the two head biases
+    //  is summed over the windows at every head step and kept in a wave-private LDS row behind the layout, as the gate biases' is)
+    __shared__ __attribute__((aligned(16))) float lds[G::L_END + (PROG ? EH_SEQ_NW * (RH + 16) : 0)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
     const int P = net.P, I = a.I, H = a.H, K = net.K, C = a.C;
 
@@ -101,6 +114,8 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     // are 32 more at H = 32, which the W_ih / W_hh accumulators leave no room for)
     float* const GB = lds + G::L_GB + wave * 4 * RH;
     for (int e = lane; e < 4 * RH; e += 64) GB[e] = 0.0f;
+    float* const HB = lds + G::L_END + (PROG ? wave * (RH + 16) : 0);      // PROG: [RH] head Dense bias | [16] output Dense bias
+    if constexpr (PROG) { for (int e = lane; e < RH + 16; e += 64) HB[e] = 0.0f; }
     // C/D block -> its transpose as an MFMA operand with the window on K: element r of the result = M[row n][window 4g + r]
     auto tr = [&](const f32x4 v) -> f32x4 {
 #pragma unroll
@@ -238,6 +253,11 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                 for (int kb = 0; kb < NBH; ++kb) z1[hb] = eh_seq_mfma4(ldA(G::L_WHD, SH, hb * 16, kb * 16), h[kb], z1[hb]);
                 a1[hb] = eh_seq_act4(a.act_hd, z1[hb]);
             }
+            if constexpr (TRAIN && PROG) {                    // (parked before the program runs: the tape then has their registers)
+                f32x4* const w4 = reinterpret_cast<f32x4*>(wsh) + (long long)j_out * (NBH + 1) * 64 + lane;
+#pragma unroll
+                for (int hb = 0; hb < NBH; ++hb) w4[hb * 64] = z1[hb];
+            }
             f32x4 ob = ldB(G::L_BOUT, 0);
 #pragma unroll
             for (int kb = 0; kb < NBH; ++kb) ob = eh_seq_mfma4(ldA(G::L_WOUT, SH, 0, kb * 16), a1[kb], ob);
@@ -262,7 +282,34 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                 const unsigned col = (net.forc_col >> (8 * f)) & 255u;
                 frc[f] = col != 255u ? rec[P + col] : 0.0f;
             }
-            const float y = eh_mech_eval(net.mech, par, frc, dydp);
+            float y;
+#ifdef EH_JIT_MECH
+            EhJitTape jtape;                                  // (the generated straight-line program: every slot a named value)
+            if constexpr (PROG) {
+                const int to = (int)(net.targ_out & 3u);
+                float yo[3];
+                eh_jit_fwd(par, frc, jtape, yo[0], yo[1], yo[2]);
+                y = to == 0 ? yo[0] : (to == 1 ? yo[1] : yo[2]);
+            } else {
+#else
+            float pval[PROG ? EH_PROG_SLOTS : 1];             // the interpreter's tape: a per-lane array (scratch memory)
+            if constexpr (PROG) {
+                eh_prog_forward(a.prog, par, frc, pval);
+                y = pval[a.prog[2 + (net.targ_out & 3u)]];
+            } else {
+#endif
+                y = eh_mech_eval(net.mech, par, frc, dydp);
+                if constexpr (HEAD == EH_SEQ_HEAD_MULTI) {    // the target is on output `to`: its value and its Jacobian row
+                    const int to = (int)(net.targ_out & 3u);
+                    float yx[2] = {0.0f, 0.0f}, Jx[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+                    eh_mech_extra(net.mech, par, frc, yx, Jx);
+                    if (to > 0) {
+                        y = to == 1 ? yx[0] : yx[1];
+#pragma unroll
+                        for (int j = 0; j < EH_MAX_PARAMS; ++j) dydp[j] = j < 3 ? (to == 1 ? Jx[0][j] : Jx[1][j]) : 0.0f;
+                    }
+                }
+            }
             const float yobs = a.recs[(long long)(st + t + a.lam) * C + P + net.F];
             const bool valid = live && !__builtin_isnan(yobs);
             const float r = valid ? y - yobs : 0.0f, cy = valid ? yobs - a.shift : 0.0f;
@@ -271,10 +318,28 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                 if (mae) { if (g == 0) est[0] += fabsf(r); d = r > 0.0f ? 1.0f : (r < 0.0f ? -1.0f : 0.0f); }
                 else { if (g == 0) est[0] = fmaf(r, r, est[0]); d = 2.0f * r; }
                 if (g == 0) { est[1] += cy; est[2] = fmaf(cy, cy, est[2]); est[3] += valid ? 1.0f : 0.0f; }
+                // the per-parameter adjoint of a closure: the reverse sweep over the tape of this head step, seeded at the target's output
+#ifdef EH_JIT_MECH
+                float padj[EH_MAX_PARAMS];
+                if constexpr (PROG) {
+                    const int to = (int)(net.targ_out & 3u);
+                    eh_jit_rev(par, frc, jtape, to == 0 ? d : 0.0f, to == 1 ? d : 0.0f, to == 2 ? d : 0.0f, padj);
+                }
+#else
+                float padj[PROG ? EH_PROG_SLOTS : 1];
+                if constexpr (PROG) {
+                    const int nslot = EH_PROG_SLOT_INSTR + (int)a.prog[0];
+                    for (int i = 0; i < nslot; ++i) padj[i] = 0.0f;
+                    padj[a.prog[2 + (net.targ_out & 3u)]] += d;
+                    eh_prog_reverse(a.prog, pval, padj);
+                }
+#endif
                 float dps[EH_MAX_PARAMS];
 #pragma unroll
                 for (int j = 0; j < EH_MAX_PARAMS; ++j) {
-                    const float dp = valid ? d * dydp[j] : 0.0f;
+                    float dp;
+                    if constexpr (PROG) dp = valid ? padj[j] : 0.0f;
+                    else dp = valid ? d * dydp[j] : 0.0f;
                     dps[j] = dp * sg[j];
                     if (g == 0 && j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL) gp[j] += dp;
                 }
@@ -285,8 +350,10 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                     for (int j = 0; j < EH_MAX_PARAMS; ++j)
                         if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_NEURAL && (int)((net.par_idx >> (4 * j)) & 15u) == 4 * g + rr) dob[rr] = dps[j];
                 f32x4* const w4 = reinterpret_cast<f32x4*>(wsh) + (long long)j_out * (NBH + 1) * 64 + lane;
+                if constexpr (!PROG) {
 #pragma unroll
-                for (int hb = 0; hb < NBH; ++hb) w4[hb * 64] = z1[hb];
+                    for (int hb = 0; hb < NBH; ++hb) w4[hb * 64] = z1[hb];
+                }
                 w4[NBH * 64] = dob;
             } else if constexpr (MODE == EH_SEQ_EVAL) {
                 if (valid && g == 0) {
@@ -321,12 +388,18 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
 #pragma unroll
                 for (int hb = 0; hb < NBH; ++hb) { z1[hb] = wh[hb * 64]; hT[hb] = tr(w4[(hb * 6 + 3) * 64] * w4[(hb * 6 + 5) * 64]); }
                 const f32x4 dobT = tr(dob);
-                gBout += dob;
+                if constexpr (PROG) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dob[r]); if (n == 0) HB[RH + 4 * g + r] += v; }
+                } else gBout += dob;
 #pragma unroll
                 for (int hb = 0; hb < NBH; ++hb) {
                     gWout[hb] = eh_seq_mfma4(dobT, tr(eh_seq_act4(a.act_hd, z1[hb])), gWout[hb]);
                     const f32x4 dz1 = eh_seq_mfma4(ldAT(G::L_WOUT, SH, 0, hb * 16), dob, Z4) * eh_seq_dact4(a.act_hd, z1[hb]);
-                    gBhd[hb] += dz1;
+                    if constexpr (PROG) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dz1[r]); if (n == 0) HB[hb * 16 + 4 * g + r] += v; }
+                    } else gBhd[hb] += dz1;
                     const f32x4 dz1T = tr(dz1);
 #pragma unroll
                     for (int kb = 0; kb < NBH; ++kb) {
@@ -457,10 +530,15 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                 for (int hb = 0; hb < NBH; ++hb) {
 #pragma unroll
                     for (int kb = 0; kb < NBH; ++kb) putW(gWhd[hb][kb], a.off[EH_SEQ_WHD], H, 0, H, hb * 16, kb * 16, H);
-                    putB(gBhd[hb], a.off[EH_SEQ_BHD], H, hb * 16);
+                    if constexpr (!PROG) putB(gBhd[hb], a.off[EH_SEQ_BHD], H, hb * 16);
                     putW(gWout[hb], a.off[EH_SEQ_WOUT], K, 0, K, 0, hb * 16, H);
                 }
-                putB(gBout, a.off[EH_SEQ_BOUT], K, 0);
+                if constexpr (PROG) {
+                    for (int e = lane; e < RH + 16; e += 64) {
+                        if (e < H) row[a.off[EH_SEQ_BHD] + e] += HB[e];
+                        else if (e >= RH && e - RH < K) row[a.off[EH_SEQ_BOUT] + e - RH] += HB[e];
+                    }
+                } else putB(gBout, a.off[EH_SEQ_BOUT], K, 0);
                 for (int e = lane; e < 4 * RH; e += 64)        // b_ih and b_hh: the same gradient, written to both
                     if (e % RH < H) { const int o = (e / RH) * H + e % RH; row[a.off[EH_SEQ_BIH] + o] += GB[e]; row[a.off[EH_SEQ_BHH] + o] += GB[e]; }
                 if (lane == 0) {

@@ -5,7 +5,12 @@ output_window 1, RbQ10, RMSProp -- at 128 windows per step (the tutorial's batch
 The kernels' own time comes from the engine's events (eh_profile_enable) here and, for the record, from ONE run of this script under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_seq.py --windows 128 --steps 200` (profiles/r10/seq_step.txt).
 --cpu-twin: the fp32 step of the torch restatement (tests/seq_twin.py, loss + autograd gradient) on 16 CPU threads, as context.
-One JSON line per window count."""
+One JSON line per window count.
+  python tools/bench_seq.py --closure [--steps 300] [--warmup 20] [--rounds 5] [--windows 128,16384] [--output-windows 1,10]
+--closure: the mechanistic model three ways -- RbQ10 of the registry, the same formula as a recorded closure on the interpreter
+("jit" = 0) and on the kernels compiled at run time ("jit" = 1) -- ALTERNATED in one process: `rounds` times round the three engines,
+`steps` timed steps each.  One JSON line per (windows, output_window): per variant the median us / step of the rounds and their
+minimum and maximum (the spread the comparison has to be read against).  profiles/r11/seq_closure_step.txt."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,7 +26,68 @@ ap.add_argument("--input-window", type=int, default=10)
 ap.add_argument("--output-window", type=int, default=1)
 ap.add_argument("--width", type=int, default=15, help="I = H")
 ap.add_argument("--cpu-twin", action="store_true")
+ap.add_argument("--closure", action="store_true")
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--output-windows", default="1,10")
 a = ap.parse_args()
+
+
+def rbq10_closure(*, ta, rb, Q10):
+    """RbQ10 as a user writes it (the reference's LSTM tutorial returns the parameters next to the prediction)"""
+    return dict(reco=rb * Q10 ** (0.1 * (ta - 15.0)), Q10=Q10, rb=rb)
+
+
+def closure_bench():
+    W, lam = a.input_window, 1
+    counts = [int(c) for c in (a.windows if a.windows != "128,1024,16384" else "128,16384").split(",")]
+    nb = 4
+    rows = nb * max(counts) + W + lam
+    cols = make_synth_rbq10(rows, 1, 0.05)
+    X = np.stack([cols["sw_pot"], cols["dsw_pot"]]) / np.float32(50)
+    starts = np.arange(rows - W - lam + 1, dtype=np.int32)
+    chain = lambda: eh.Chain(eh.Recurrence(eh.LSTMCell(a.width, a.width)))
+    mk = lambda mech: eh.constructHybridModel(["sw_pot", "dsw_pot"], ["ta"], ["reco"], mech, dict(RBQ10_PARAMS), ["rb"], ["Q10"], hidden_layers=chain(),
+                                              activation="tanh", scale_nn_outputs=True)
+    variants = [("registry", eh.RbQ10, None), ("closure_interpreted", rbq10_closure, 0), ("closure_compiled", rbq10_closure, 1)]
+    for B in counts:
+        for ow in [int(o) for o in a.output_windows.split(",")]:
+            engs = []
+            for name, mech, jit in variants:
+                model = mk(mech)
+                eng = model.engine(0)
+                if jit is not None:
+                    eng.set_option("jit", jit)
+                eng.set_data(0, X, [cols["ta"]], [cols["reco"]])
+                eng.set_sequences(0, W, ow, lam, starts)
+                eng.set_params(model.initialparameters(1))
+                eng.opt_init("RMSProp", 0.01)
+                for s in range(a.warmup):
+                    eng.train_step((s % nb) * B, B, want_loss=False)
+                eng.synchronize()
+                if eng.jit_status()[0] != (jit or 0):
+                    raise SystemExit(f"{name}: eh_jit_status reports {eng.jit_status()[0]} compiled kernels: {eng.jit_status()[1][:400]}")
+                engs.append(eng)
+            times = {name: [] for name, _, _ in variants}
+            for r in range(a.rounds):
+                for (name, _, _), eng in zip(variants, engs):
+                    t0 = time.perf_counter()
+                    for s in range(a.steps):
+                        eng.train_step(((r * a.steps + s) % nb) * B, B, want_loss=False)
+                    eng.synchronize()
+                    times[name].append(1e6 * (time.perf_counter() - t0) / a.steps)
+            out = {"windows": B, "input_window": W, "output_window": ow, "I": a.width, "H": a.width, "rounds": a.rounds, "steps": a.steps}
+            for name, _, _ in variants:
+                t = sorted(times[name])
+                out[name] = {"us_per_step_median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+            out["final_loss"] = {name: eng.train_step(0, B) for (name, _, _), eng in zip(variants, engs)}
+            print(json.dumps(out), flush=True)
+            for eng in engs:
+                eng.close()
+
+
+if a.closure:
+    closure_bench()
+    sys.exit(0)
 W, ow, lam = a.input_window, a.output_window, 1
 model = eh.constructHybridModel(["sw_pot", "dsw_pot"], ["ta"], ["reco"], eh.RbQ10, dict(RBQ10_PARAMS), ["rb"], ["Q10"],
                                 hidden_layers=eh.Chain(eh.Recurrence(eh.LSTMCell(a.width, a.width))), activation="tanh", scale_nn_outputs=True)
