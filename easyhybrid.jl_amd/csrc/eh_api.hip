@@ -134,6 +134,10 @@ static int build_maps(eh_handle* h, bool with_imap) {
     std::vector<int> imap((size_t)n.n_theta, -1), rmap((size_t)h->n_acc, 0);
     // v2 region[k][g][r][c] where one wave workspace holds a wave's raw accumulators, else v3 region[k][c][g][r] (eh_step_body, workgroup reduction)
     const bool v2 = A->wide || L.rw <= A->var[h->variant].red_floats / A->var[h->variant].nw;
+    // (v2, an element that is a sum over the 16 samples of a row -- nlan == 16 below: its entry is the position of the row's FIRST column,
+    //  lane & 15 == 0, i.e. k * 256 + row * 16 with row = 4 g + r.  The kernel parks such a row as ONE word at k * 256 + row and derives
+    //  that word from the entry, (pos & ~255) | ((pos & 255) >> 4) -- eh_step_body, put_rows and the gather; EH_AB_REDUCE_PARENT reads
+    //  the 16 columns at the entry itself.  nlan is 1 or 16, nothing else; the check below holds both to that.)
     auto at = [v2](int k, int lane, int r) { return v2 ? k * 256 + (lane >> 4) * 64 + r * 16 + (lane & 15) : k * 256 + (lane & 15) * 16 + (lane >> 4) * 4 + r; };
     for (const EhEntry& e : ent) {
         const int m = e.row / 16, g = (e.row % 16) / 4, r = e.row % 4;
@@ -177,7 +181,10 @@ static int build_maps(eh_handle* h, bool with_imap) {
             continue;
         }
         if (k < 0) { rmap[e.canon] = (L.na * 256 + 13) | (1 << 24); }
-        else rmap[e.canon] = at(k, lane, rr) | (nlan << 24);
+        else {
+            if ((nlan != 1 && nlan != 16) || (nlan == 16 && (lane & 15) != 0)) return fail(h, EH_EINVAL, "build_maps: a row-summed accumulator element must start at its row's first column");
+            rmap[e.canon] = at(k, lane, rr) | (nlan << 24);
+        }
     }
     for (int j = 0; j < d.n_params; ++j)
         if (d.param_kind[j] == EH_PAR_GLOBAL) rmap[n.g_off + d.param_index[j]] = (L.na * 256 + j) | (1 << 24);

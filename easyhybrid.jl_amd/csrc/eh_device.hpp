@@ -608,6 +608,28 @@ __device__ __forceinline__ float eh_row16_sum(float v) {   // every lane gets th
     v += eh_dpp<0x128>(v);   // row_ror:8
     return v;
 }
+// Four row sums at once, for the workgroup reduction: v[r] is this lane's partial of row r over its sample column c = lane & 15, and lane
+// c & 3 == r of the row's quads 1 and 3 (c = 4..7, 12..15) gets the sum of v[r] over the 16 columns x[0..15] in the tree that reduction
+// has always used for a parked row: q[j] = (x[j] + x[4 + j]) + (x[8 + j] + x[12 + j]), then (q[0] + q[1]) + (q[2] + q[3]).  (NOT
+// eh_row16_sum's tree.)  row_ror:n hands lane c the value of lane c - n, so after the two rotates lane 4 + j holds
+// (x[4+j] + x[j]) + (x[12+j] + x[8+j]) and lane 12 + j holds (x[12+j] + x[8+j]) + (x[4+j] + x[j]): q[j] bit for bit, addition commutes
+// (lanes j and 8 + j pair the four terms the other way: other bits).  The two quad steps reduce and transpose together: a lane keeps
+// the register of the row it will end up with and hands the other one to its partner, so lane j of a quad holds q_r[j] + q_r[j ^ 1]
+// of the rows r = j & 1 and r = 2 + (j & 1) after the first and (q_j[j] + q_j[j^1]) + (q_j[j^2] + q_j[j^3]) after the second -- three adds where
+// eight would go, and no select behind the last one.  THE OTHER LANES HOLD OTHER BITS; every lane of the wave must be active.
+__device__ __forceinline__ float eh_rows16_tree(const f32x4& v, int c) {
+    float q[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        q[r] = v[r];
+        q[r] += eh_dpp<0x124>(q[r]);   // row_ror:4
+        q[r] += eh_dpp<0x128>(q[r]);   // row_ror:8
+    }
+    const bool o1 = (c & 1) != 0, o2 = (c & 2) != 0;
+    const float t01 = (o1 ? q[1] : q[0]) + eh_dpp<0xB1>(o1 ? q[0] : q[1]);   // quad_perm:[1,0,3,2]
+    const float t23 = (o1 ? q[3] : q[2]) + eh_dpp<0xB1>(o1 ? q[2] : q[3]);
+    return (o2 ? t23 : t01) + eh_dpp<0x4E>(o2 ? t01 : t23);                  // quad_perm:[2,3,0,1]
+}
 __device__ __forceinline__ float eh_wave_sum(float v) {
     const int r = __builtin_bit_cast(int, eh_row16_sum(v));
     return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(r, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(r, 16))) +
@@ -955,6 +977,22 @@ struct EhGeom {
 #define EH_STAMP_FINE(i) EH_STAMP(i)
 #else
 #define EH_STAMP_FINE(i)
+#endif
+// EH_STAMPS_FINE, the workgroup reduction (tools/stamps_reduce.py): thread `thr` of workgroup 0 records at stamps[EH_RED_ST + 2 p ...] --
+// [0] thread 0, its gather done; [1] / [2] thread 64 (wave 1), the gather's start and end.  (One CU: the shader clocks compare.)
+enum { EH_RED_ST = 200 };
+#if defined(EH_STAMPS) && defined(EH_STAMPS_FINE)
+#define EH_STAMP_RED(p, thr)                                                             \
+    do {                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                               \
+        if (a.stamps && blockIdx.x == 0 && threadIdx.x == (thr)) {                       \
+            a.stamps[EH_RED_ST + 2 * (p)] = __builtin_readcyclecounter();                \
+            a.stamps[EH_RED_ST + 2 * (p) + 1] = wall_clock64();                          \
+        }                                                                                \
+        __builtin_amdgcn_sched_barrier(0);                                               \
+    } while (0)
+#else
+#define EH_STAMP_RED(p, thr)
 #endif
 
 // Nothing moves across: keeps a block of LDS requests in front of the MFMA chain it is meant to hide behind.
@@ -2054,19 +2092,27 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         }
         // layer 0: dW0 += dZ_0 * X^T
         if constexpr (PS) {
+            // (columns pp >= P of W0 do not exist: no canonical element reads their accumulators, which stay at zero and are not parked)
+#ifdef EH_AB_REDUCE_PARENT
+            const int npp = 4;
+#else
+            const int npp = net.P;
+#endif
             float xv[4][NT];
 #pragma unroll
             for (int pp = 0; pp < 4; ++pp)
 #pragma unroll
-                for (int t = 0; t < NT; ++t) xv[pp][t] = XS[pp * SR + 16 * t + c];     // rows >= P are zero
+                for (int t = 0; t < NT; ++t) xv[pp][t] = pp < npp ? XS[pp * SR + 16 * t + c] : 0.0f;     // rows >= P are zero
 #pragma unroll
             for (int m = 0; m < NBH; ++m)
 #pragma unroll
                 for (int pp = 0; pp < 4; ++pp)
+                    if (pp < npp) {
 #pragma unroll
-                    for (int t = 0; t < NT; ++t)
+                        for (int t = 0; t < NT; ++t)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) aW0V[m][pp][r] = fmaf(dz[m][t][r], xv[pp][t], aW0V[m][pp][r]);
+                            for (int r = 0; r < 4; ++r) aW0V[m][pp][r] = fmaf(dz[m][t][r], xv[pp][t], aW0V[m][pp][r]);
+                    }
         } else {
             EH_WAVE_SYNC();
             const float* const DZ = HS;
@@ -2104,9 +2150,9 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     constexpr EhAccLayout AL = eh_acc_layout(NBI, NBH, NL, FAST);
     constexpr bool REDV2 = TRAIN && AL.rw <= G::WAVE_WS;
     if constexpr (REDV2) {
-        // v2: every lane parks its raw accumulators with unconditional 16-byte stores; the sums over
-        // the 16 samples of a row, over the waves and the padding removal all happen in the final
-        // gather loop through the host-built rmap (fixed order: deterministic).
+        // v2: every live wave parks its accumulators in its own workspace -- the MFMA-contracted ones raw, the per-sample partials as
+        // row sums (put_rows) -- and the sums over the waves and the padding removal happen in the final gather loop through the
+        // host-built rmap (fixed order: deterministic).
         float tailv[16];
 #pragma unroll
         for (int j = 0; j < EH_MAX_PARAMS; ++j) tailv[j] = (j < net.n_par) ? eh_wave_sum(gacc[j]) * meta[EH_IMG_DPHI + j] : 0.0f;
@@ -2133,12 +2179,27 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll
             for (int r = 0; r < 4; ++r) R[k * 256 + g * 64 + r * 16 + c] = v[r];
         };
+#ifdef EH_AB_REDUCE_PARENT     // (diagnostic A/B: the parking of rounds 5-11 -- per-sample partials are parked column by column, the gather sums them)
+        auto put_rows = put;
+        constexpr int npark = 4;
+#else
+        // accumulators that are per-lane partial sums over the 16 samples of a row (biases; the K1 / PS vectors): the wave sums the 16
+        // columns itself, in the parent gather's tree (eh_rows16_tree), and parks ONE word per row -- region[k][row], row = 4 g + r, from the lane
+        // of the row's last quad whose c & 3 is r.  A sixteenth of the words, one store where four went, and the gather reads one word
+        // per wave for every kind of element.
+        auto put_rows = [&](int k, const f32x4& v) {
+            const float s = eh_rows16_tree(v, c);
+            if (c >= 12) R[k * 256 + g * 4 + (c & 3)] = s;
+        };
+        const int npark = net.P;       // (PS: columns pp >= P of W0 are not accumulated)
+#endif
         if (parks) {
 #pragma unroll
         for (int m = 0; m < NBH; ++m) {
             if constexpr (PS) {
 #pragma unroll
-                for (int pp = 0; pp < 4; ++pp) put(AL.kw0 + m * 4 + pp, aW0V[m][pp]);
+                for (int pp = 0; pp < 4; ++pp)
+                    if (pp < npark) put_rows(AL.kw0 + m * 4 + pp, aW0V[m][pp]);
             } else {
 #pragma unroll
                 for (int n = 0; n < NBI; ++n) put(AL.kw0 + m * NBI + n, aW0[m][n]);
@@ -2147,11 +2208,11 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             for (int l = 0; l < NL - 1; ++l)
 #pragma unroll
                 for (int n = 0; n < NBH; ++n) put(AL.kwh + (l * NBH + m) * NBH + n, aWh[l][m][n]);
-            if constexpr (K1) put(AL.kwo + m, aWoV[m]); else put(AL.kwo + m, aWo[m]);
+            if constexpr (K1) put_rows(AL.kwo + m, aWoV[m]); else put(AL.kwo + m, aWo[m]);
 #pragma unroll
-            for (int l = 0; l < NL; ++l) put(AL.kb + l * NBH + m, aB[l][m]);
+            for (int l = 0; l < NL; ++l) put_rows(AL.kb + l * NBH + m, aB[l][m]);
         }
-        if constexpr (!K1) put(AL.kbo, aBo);
+        if constexpr (!K1) put_rows(AL.kbo, aBo);
         if (lane < 16) {
             float tv = 0.0f;
 #pragma unroll
@@ -2162,12 +2223,29 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         EH_STAMP(12);
         __syncthreads();
         EH_STAMP(9);
+        EH_STAMP_RED(1, 64);
         const float* const R0 = smem + G::IMG_FLOATS;
         float* const out = a.slab + (long long)blockIdx.x * a.n_acc;      // (EH_MODE_TRAIN_ORD: the row is staged in LDS, over the parameter image -- dead by now)
         float* const gsh = (!ORDM && a.fz.gacc) ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
         for (int e = tid; e < a.n_acc; e += NTHR) {
             const int code = e == tid ? f_rcode : a.rmap[e], pos = code & 0xFFFFFF, nlan = code >> 24;
             float sum = 0.0f;
+#ifndef EH_AB_REDUCE_PARENT
+            // every element is one word per live wave (a row sum sits at region[k][row]: the map's position is that of the row's first
+            // column, k 256 + row 16); the waves are added in ascending order from 0.0f, a full workgroup's loads all issued first
+            // (a run-time loop over the live waves otherwise -- predicated loads in an unrolled one became a branch around every load)
+            const int wd = (pos & ~255) | ((pos & 255) >> ((nlan >> 4) << 2));      // (nlan is 16 or 1: no branch)
+            if (nlive == NW) {
+                float v[NW];
+#pragma unroll
+                for (int w = 0; w < NW; ++w) v[w] = R0[w * AL.rw + wd];
+#pragma unroll
+                for (int w = 0; w < NW; ++w) sum += v[w];
+            } else {
+#pragma unroll 1
+                for (int w = 0; w < nlive; ++w) sum += R0[w * AL.rw + wd];
+            }
+#else
             if (nlan == 16) {
                 // (a run-time loop over the live waves -- predicated loads in an unrolled one became a branch around every load)
                 if (nlive == NW) {
@@ -2194,10 +2272,13 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll 1
                 for (int w = 0; w < nlive; ++w) sum += R0[w * AL.rw + pos];
             }
+#endif
             if constexpr (ORDM) wl[eh_ord_pos(e, net.n_theta, a.ord.soff)] = sum;      // (eh_ord_publish stores it write-through)
             else if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[e] = sum; else atomicAdd(&gsh[e], sum); }      // (ms_direct: one workgroup, one writer per element)
             else out[e] = sum;
         }
+        EH_STAMP_RED(0, 0);
+        EH_STAMP_RED(2, 64);
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
         if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps);
         EH_STAMP_FINE(15);
