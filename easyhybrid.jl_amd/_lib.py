@@ -12,6 +12,8 @@ import os
 EH_MAX_HIDDEN, EH_MAX_PARAMS, EH_MAX_FORC, EH_MAX_TARG, EH_MAX_NETS = 8, 8, 4, 4, 8
 EH_MAX_PROG, EH_MAX_PROG_CONST, EH_MAX_PROG_OUT = 64, 16, 3
 EH_MAX_OPT_GROUPS = 16
+EH_MAX_OPT_STAGES = 8
+EH_STAGE_RULE, EH_STAGE_CLIPGRAD, EH_STAGE_CLIPNORM, EH_STAGE_WEIGHTDECAY = 0, 1, 2, 3
 EH_MECH_PROGRAM = 6
 EH_LOSS_PROGRAM = 7
 EH_OK, EH_EINVAL, EH_EHIP, EH_ENOMEM, EH_EUNSUPPORTED, EH_ESTATE, EH_ERCCL = 0, -1, -2, -3, -4, -5, -6
@@ -51,6 +53,10 @@ class TargetMetrics(C.Structure):
                 ("n", "mse", "rmse", "mae", "r2", "nse", "pearson", "kge", "pbkge", "beta", "alpha", "sse")]
 
 
+class OptStage(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("flags", C.c_int32)]
+
+
 LIB_NAME = "libeasyhybrid_hip.so"
 # (EASYHYBRID_HIP_LIB: another build of the same library, e.g. one of tools/ps_variants.sh's diagnostic builds)
 LIB_PATH = os.environ.get("EASYHYBRID_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -82,6 +88,8 @@ SIGNATURES = {
     "eh_get_opt_state": (C.c_int32, [_H, _F, _F, C.c_int64, _F]),
     "eh_set_opt_state": (C.c_int32, [_H, _F, _F, C.c_int64, _F]),
     "eh_opt_init_groups": (C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F]),
+    "eh_opt_init_chain": (C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "eh_opt_chain_status": (C.c_int32, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "eh_get_opt_beta_t": (C.c_int32, [_H, _F, C.c_int32]),
     "eh_set_opt_beta_t": (C.c_int32, [_H, _F, C.c_int32]),
     "eh_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_int64]),

@@ -21,6 +21,7 @@
 
 #include "eh_internal.hpp"
 #include "eh_kernels.hpp"
+#include "eh_chain.hpp"
 #include "eh_wide.hpp"
 #include "eh_lform.hpp"
 #include "eh_seq.hpp"
@@ -954,7 +955,7 @@ int32_t eh_destroy(eh_handle* h) {
     eval_host_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
     (void)hipFree(h->stamps); (void)hipFree(h->image); (void)hipFree(h->imap); (void)hipFree(h->rmap);
-    (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs); (void)hipFree(h->split[0].starts); (void)hipFree(h->split[1].starts); (void)hipFree(h->seq_ws);
+    (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs); (void)hipFree(h->split[0].starts); (void)hipFree(h->split[1].starts); (void)hipFree(h->seq_ws); (void)hipFree(h->chain_part);
     if (h->own_stream) stream_pool_give(h->device, h->own_stream);      // (drained above; the next handle on this device takes it over)
     delete h;
     return EH_OK;
@@ -1173,6 +1174,7 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
         if (value && h->arch->wide) return fail(h, EH_EUNSUPPORTED, "fused_update is not built for hidden widths above 64");
         if (!value && h->p2p_alloc) return fail(h, EH_ESTATE, "fused_update: eh_p2p_disable first");
         if (value < 0 || value > 2) return fail(h, EH_EINVAL, "fused_update must be 0, 1 or 2");
+        if (value == 1 && h->chain.n) return fail(h, EH_EUNSUPPORTED, "fused_update: the one-kernel step is not built for an optimiser chain (ClipNorm needs the norm of the whole gradient before any element moves): 0 or 2 run the step + reduce + chain kernels");
         HIPCHK(h, hipSetDevice(h->device));
         FLUSH(h);
         h->fused = value != 0;
@@ -2293,7 +2295,7 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
 // Several fused-update steps in one launch (EH_MODE_TRAIN_MULTI, eh_device.hpp): minibatches one workgroup covers -- the reference's
 // default batch of 64 among them -- with the step-to-step state in LDS.
 static bool multi_ok(const eh_handle* h, long long batch) {
-    if (!h->fused || !h->multi_step || h->lform || h->arch->wide || h->p2p_on || h->prof || h->capturing) return false;
+    if (!h->fused || !h->multi_step || h->lform || h->arch->wide || h->p2p_on || h->prof || h->capturing || h->chain.n) return false;
     if (h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->bn_on && (h->bn_ext || h->bn_no_self || batch > EH_BN_SELF_MAX)) return false;
     if (h->arch->var[h->variant].lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(h->net.n_theta, h->n_acc, h->opt.tab != nullptr) > EH_LDS_LIMIT) return false;
@@ -2327,11 +2329,37 @@ static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long 
     return EH_OK;
 }
 
+// The chain kernels (eh_chain.hpp) on the gradient in h->gradbuf.  raw: the data-parallel seam's all-reduced sums (eh_dp_apply), whose
+// loss the apply pass writes to loss_slot; otherwise eh_reduce_kernel<false, ...> has written gradient and loss.
+static int launch_chain(eh_handle* h, bool raw, float* sc_in, float* sc_out, float* loss_slot) {
+    static const int one_env = getenv("EH_CHAIN_ONE") ? atoi(getenv("EH_CHAIN_ONE")) : -1;      // (A/B switch of tools/bench_chain.py: the largest n_theta one workgroup takes)
+    const int nt = h->net.n_theta;
+    const bool l2 = raw && (h->img.l2c != 0.0f || h->img.l2w);
+    const unsigned tp = raw ? two_pass_mask(h->net) : 0u;
+    const EhChainSrc src{raw ? 1 : 0, h->net.loss, h->net.T, tp, tp ? h->inv_n : nullptr, l2 ? h->l2val : nullptr};
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(h->chain_part + EH_CHAIN_PARTS);
+    if (h->chain.i_norm < 0) {          // no norm to wait for: one element per thread
+        hipLaunchKernelGGL(eh_chain_apply_kernel<false>, dim3((nt + 255) / 256), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), MM(h), VV(h), sc_in, sc_out, h->opt,
+                           h->chain, src, h->img, h->chain_part, 0, loss_slot, ctr);
+    } else if (nt <= (one_env >= 0 ? one_env : (int)EH_CHAIN_ONE_MAX)) {
+        hipLaunchKernelGGL(eh_chain_apply_kernel<true>, dim3(1), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), MM(h), VV(h), sc_in, sc_out, h->opt,
+                           h->chain, src, h->img, h->chain_part, 0, loss_slot, ctr);
+    } else {
+        const int nb = std::min<int>(EH_CHAIN_PARTS, (nt + 1023) / 1024);
+        hipLaunchKernelGGL(eh_chain_norm_kernel, dim3(nb), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), h->chain, src, h->img, h->chain_part);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(eh_chain_apply_kernel<false>, dim3((nt + 255) / 256), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), MM(h), VV(h), sc_in, sc_out, h->opt,
+                           h->chain, src, h->img, h->chain_part, nb, loss_slot, ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+
 // "fused_update" 2 on a minibatch of several workgroups: the ordered one-kernel step (EH_MODE_TRAIN_ORD) wherever "fused_update" 1 would be
 // allowed and the pair's reduce would run eh_reduce_kernel<true, 16> on slab rows the per-wave kernels wrote -- its bits are that pair's
 static bool ord_ok(const eh_handle* h, int grid) {
     static const int cw_env = getenv("EH_REDUCE_CW") ? atoi(getenv("EH_REDUCE_CW")) : 0;      // (the A/B switch of do_step)
-    if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS) return false;
+    if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS || h->chain.n) return false;
     if (h->lform || h->arch->wide || h->p2p_on || h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->img.l2c != 0.0f || h->img.l2w || two_pass_mask(h->net) || h->dp_weights || h->dp_moments) return false;
     // (the step stages its row in LDS over the parameter image before it stores it)
@@ -2368,17 +2396,31 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     // layer-wise form, few rows: the optimiser may run in the epilogue of the grouped weight-gradient launch (lform_train decides; eh_lform.hpp EhLApply)
     EhLApply lap{};
     h->l_apply = nullptr; h->l_applied = false;
+    const bool chained = apply && h->chain.n != 0;      // an optimiser chain: the reduction leaves the gradient, the chain kernels apply it
     if (h->lform && apply && deferred && !l2 && !moment_loss && net.loss != EH_LOSS_PROGRAM) {
         lap.theta = TH(h); lap.m = MM(h); lap.v = VV(h); lap.sc_in = sc_in; lap.sc_out = sc_out; lap.o = h->opt; lap.loss_slot = loss_slot; lap.gradbuf = h->gradbuf;
         lap.im = h->img; lap.loss_kind = h->net.loss; lap.n_theta = net.n_theta; lap.g_off = net.g_off;
+        if (chained) {
+            // A chain needs the finished gradient, from the SAME products the unchained few-rows step takes (other product kernels sum the
+            // samples in another order: other bits).  The epilogue is handed Descent(-1) on a zeroed "parameter" vector that is gradbuf itself:
+            // 0 - (-1 g) leaves exactly g = sum * scale there, the loss and the counts behind it as always; no moments, no image (g_off = n_theta
+            // and no map: eh_image_store has nothing to store), and the products it advances are written again by the chain's apply pass.
+            HIPCHK(h, hipMemsetAsync(h->gradbuf, 0, (size_t)net.n_theta * sizeof(float), h->stream));
+            lap.theta = h->gradbuf;               // (m, v: Descent keeps none, nobody reads or writes them)
+            lap.o = EhOpt{EH_OPT_DESCENT, -1.0f, 1.0f, 1.0f, 0.0f, 0.0f, nullptr};
+            lap.im.g_off = net.n_theta; lap.im.imap = nullptr;
+        }
         h->l_apply = &lap;
     }
     int rc = launch_train_kernel(h, sp, idx, first, count, &grid, apply);
     h->l_apply = nullptr;
     if (rc) return rc;
     if (prof && !burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
-    if (h->l_applied) {                  // theta, the moments, the loss and the beta products are done
+    if (h->l_applied) {                  // theta, the moments, the loss and the beta products are done (a chain: the gradient is; its kernels follow)
         h->l_applied = false;
+        if (chained) {
+            if (int rcc = launch_chain(h, false, sc_in, sc_out, nullptr)) return rcc;
+        }
         h->sc_sel ^= 1;
         if (prof && burst_last) {
             if (burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
@@ -2403,7 +2445,7 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
 #define EH_REDUCE_GO(AP, ...)                                                                                                                       \
     hipLaunchKernelGGL((eh_reduce_kernel<AP, __VA_ARGS__>), dim3(rgrid), dim3(256), 0, h->stream, h->slab, grid, h->n_acc, net.n_theta, net.T, deferred, h->gradbuf, \
                        TH(h), MM(h), VV(h), sc_in, sc_out, h->opt, loss_slot, h->img, h->net.loss, (moment_loss && !raw) ? h->inv_n : nullptr, l2 ? h->l2val : nullptr, tp_mask)
-    if (apply) {
+    if (apply && !chained) {
         if (tall4) EH_REDUCE_GO(true, 256, 4, true); else if (tall) EH_REDUCE_GO(true, 256); else if (big) EH_REDUCE_GO(true, 64); else EH_REDUCE_GO(true, 16);
         h->sc_sel ^= 1;
     } else {
@@ -2411,6 +2453,10 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     }
 #undef EH_REDUCE_GO
     HIPCHK(h, hipGetLastError());
+    if (chained) {
+        if (int rcc = launch_chain(h, false, sc_in, sc_out, nullptr)) return rcc;
+        h->sc_sel ^= 1;
+    }
     if (prof && burst_last) {
         if (burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
         HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 2], h->stream));
@@ -2862,6 +2908,7 @@ int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float bet
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->opt = EhOpt{rule, lr, beta1, beta2, eps, weight_decay, nullptr};
     h->opt_groups = 1;
+    h->chain = EhChain{}; h->chain_gen = 0;
     const size_t nt = (size_t)h->net.n_theta;
     HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
     HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
@@ -2900,6 +2947,7 @@ int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, 
     // (the handle's own rule names Adam, so every site moves m and v; its hyper-parameters are group 0's -- the table is what is read)
     h->opt = EhOpt{EH_OPT_ADAM, t->r[0].lr, t->r[0].b1, t->r[0].b2, t->r[0].eps, t->r[0].wd, h->opt_tab};
     h->opt_groups = n_groups;
+    h->chain = EhChain{}; h->chain_gen = 0;
     HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
     HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
     float sc[4 * EH_MAX_OPT_GROUPS] = {};
@@ -2910,6 +2958,58 @@ int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, 
     HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
     h->sc_sel = 0;
     h->opt_ready = true;
+    return EH_OK;
+}
+
+int32_t eh_opt_init_chain(eh_handle* h, const eh_opt_stage* stages, int32_t n_stages, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay) {
+    if (!h || !stages) return EH_EINVAL;
+    if (n_stages < 1) return fail(h, EH_EINVAL, "eh_opt_init_chain: %d stages", n_stages);
+    if (n_stages > EH_MAX_OPT_STAGES) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: %d stages (at most %d, nested chains flattened)", n_stages, EH_MAX_OPT_STAGES);
+    if (rule < EH_OPT_ADAM || rule > EH_OPT_DESCENT) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: unknown rule %d", rule);
+    EhChain c{};
+    c.n = n_stages; c.i_norm = -1; c.i_rule = -1; c.p = 2;
+    for (int k = 0; k < n_stages; ++k) {
+        const eh_opt_stage& st = stages[k];
+        c.kind[k] = st.kind; c.a[k] = st.a;
+        if (st.kind == EH_STAGE_RULE) {
+            if (c.i_rule >= 0) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: stage %d: a second rule (a chain holds exactly one of Adam / AdamW / RMSProp / Descent)", k);
+            c.i_rule = k;
+        } else if (st.kind == EH_STAGE_CLIPGRAD) {
+            if (!(st.a >= 0.0f)) return fail(h, EH_EINVAL, "eh_opt_init_chain: stage %d: ClipGrad(delta = %g)", k, (double)st.a);
+        } else if (st.kind == EH_STAGE_WEIGHTDECAY) {
+            if (!(st.a >= 0.0f)) return fail(h, EH_EINVAL, "eh_opt_init_chain: stage %d: WeightDecay(lambda = %g)", k, (double)st.a);
+        } else if (st.kind == EH_STAGE_CLIPNORM) {
+            if (!(st.a > 0.0f)) return fail(h, EH_EINVAL, "eh_opt_init_chain: stage %d: ClipNorm(omega = %g)", k, (double)st.a);
+            if (c.i_norm >= 0) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: stage %d: a second ClipNorm (one norm pass per step is built)", k);
+            if (c.i_rule >= 0) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: stage %d: ClipNorm behind the rule needs the norm of the UPDATE, a second pass over it: not built", k);
+            if (st.b == 1.0f) c.p = 1; else if (st.b == 2.0f) c.p = 2; else if (st.b == INFINITY) c.p = 0;
+            else return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: stage %d: ClipNorm with p = %g (1, 2 and Inf are built)", k, (double)st.b);
+            c.i_norm = k; c.omega = st.a; c.thr = st.flags & 1;
+        } else return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: stage %d: unknown kind %d", k, st.kind);
+    }
+    if (c.i_rule < 0) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: no EH_STAGE_RULE among the stages (a chain holds exactly one rule)");
+    if (h->fused && !h->fused_det) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: the one-kernel step (fused_update 1) is not built for an optimiser chain: switch it to 0 or 2 first");
+    if (h->p2p_alloc) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: the peer-to-peer fused exchange is not built for an optimiser chain: eh_p2p_disable first");
+    int rc = eh_opt_init(h, rule, lr, beta1, beta2, eps, weight_decay);       // (drains the stream; zero moments; the products at beta)
+    if (rc) return rc;
+    if (!h->chain_part) HIPCHK(h, hipMalloc(&h->chain_part, (EH_CHAIN_PARTS + 3) * sizeof(double)));      // here, never inside a capture
+    HIPCHK(h, hipMemset(h->chain_part, 0, (EH_CHAIN_PARTS + 3) * sizeof(double)));
+    static int gen = 0;
+    h->chain = c; h->chain_gen = ++gen;
+    return EH_OK;
+}
+
+int32_t eh_opt_chain_status(eh_handle* h, int64_t* n_applied, int64_t* n_clipped, int64_t* n_nonfinite) {
+    if (!h) return EH_EINVAL;
+    if (!h->chain.n) return fail(h, EH_ESTATE, "eh_opt_chain_status: no optimiser chain (call eh_opt_init_chain first)");
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    unsigned long long ctr[3];
+    HIPCHK(h, hipMemcpy(ctr, h->chain_part + EH_CHAIN_PARTS, sizeof ctr, hipMemcpyDeviceToHost));
+    if (n_applied) *n_applied = (int64_t)ctr[0];
+    if (n_clipped) *n_clipped = (int64_t)ctr[1];
+    if (n_nonfinite) *n_nonfinite = (int64_t)ctr[2];
     return EH_OK;
 }
 
@@ -2997,7 +3097,7 @@ int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, i
     if (rc) return rc;
     const int grid = h->seq ? 0 : grid_for(h, count);
     bool done = false;
-    if (h->fused && !(h->fused_det && grid != 1)) {
+    if (h->fused && !(h->fused_det && grid != 1) && !h->chain.n) {      // (an optimiser chain: always the step + reduce + chain kernels)
         rc = do_fused_step(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr);
         if (rc) return rc;
         done = true;
@@ -3044,7 +3144,7 @@ int32_t eh_graph_begin(eh_handle* h) {
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
     if (h->fused && !h->pending) return fail(h, EH_ESTATE, "eh_graph_begin: fused_update mode: run one training step first (and do not synchronize before capturing)");
-    h->cap = {nullptr, h->fused, (int)(h->gstep % 3), h->cur, h->sc_sel, h->pend_ord, h->pend_ord ? h->ord_grid : 0, h->opt.tab != nullptr};
+    h->cap = {nullptr, h->fused, (int)(h->gstep % 3), h->cur, h->sc_sel, h->pend_ord, h->pend_ord ? h->ord_grid : 0, h->opt.tab != nullptr, h->chain_gen};
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_loss_hist(h, 1);
     if (rc) return rc;
@@ -3093,6 +3193,9 @@ int32_t eh_graph_launch(eh_handle* h, int32_t graph_id) {
     if (g.grouped != (h->opt.tab != nullptr))
         return fail(h, EH_ESTATE, "eh_graph_launch: the graph was recorded with %s, the engine now has %s (eh_opt_init / eh_opt_init_groups)",
                     g.grouped ? "per-branch optimiser rules" : "one optimiser rule", g.grouped ? "one rule" : "per-branch rules");
+    if (g.chain_gen != h->chain_gen)
+        return fail(h, EH_ESTATE, "eh_graph_launch: the graph was recorded %s, the engine now has %s (eh_opt_init / eh_opt_init_chain)",
+                    g.chain_gen ? "with an optimiser chain" : "without an optimiser chain", h->chain_gen ? "another chain" : "none");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
     return EH_OK;
@@ -3124,7 +3227,7 @@ int32_t eh_train_epoch(eh_handle* h, int64_t batchsize, uint64_t seed, int32_t s
         const long long first = s * batchsize, count = std::min<long long>(batchsize, N - first);
         const int grid = h->seq ? 0 : grid_for(h, count);
         // ("fused_update" 2: the float-atomic one-kernel step only where one workgroup covers the minibatch, the ordered one elsewhere)
-        const bool one_kernel = h->fused && !(h->fused_det && grid != 1);
+        const bool one_kernel = h->fused && !(h->fused_det && grid != 1) && !h->chain.n;
         bool done = false;
         if (one_kernel) {
             if ((rc = do_fused_step(h, sp, shuffle ? h->perm : nullptr, first, count, h->loss_hist + s))) return rc;
@@ -3308,6 +3411,7 @@ int32_t eh_dp_fused_step(eh_handle* h, int64_t first, int64_t count, int32_t* bu
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: multi-target models need the global per-target counts before the pass: use eh_dp_counts + eh_dp_grad (fused_update off)");
     if (h->bn_on && !h->bn_ext) return fail(h, EH_ESTATE, "eh_dp_fused_step: input BatchNorm needs the global batch statistics: call eh_dp_bn_stats and all-reduce EH_BUF_BNSTAT first");
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_dp_fused_step: call eh_opt_init first");
+    if (h->chain.n) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: not built for an optimiser chain (the norm needs the all-reduced gradient before the update): use eh_dp_grad + eh_dp_apply");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
     int rc = check_window(h, sp, first, count, "eh_dp_fused_step");
@@ -3359,9 +3463,13 @@ int32_t eh_dp_apply(eh_handle* h, float* loss_out) {
         hipLaunchKernelGGL(eh_weight_l2_kernel, dim3(1), dim3(256), 0, h->stream, TH(h), h->img, h->l2val);
         HIPCHK(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(eh_apply_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), MM(h), VV(h), sc_in, sc_out, h->opt,
-                       h->loss_hist, h->img, h->net.loss, h->net.T, l2 ? h->l2val : nullptr, two_pass_mask(h->net) ? h->inv_n : nullptr, two_pass_mask(h->net));
-    HIPCHK(h, hipGetLastError());
+    if (h->chain.n) {                                          // norm of the all-reduced, globally normalised gradient
+        if ((rc = launch_chain(h, true, sc_in, sc_out, h->loss_hist))) return rc;
+    } else {
+        hipLaunchKernelGGL(eh_apply_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), MM(h), VV(h), sc_in, sc_out, h->opt,
+                           h->loss_hist, h->img, h->net.loss, h->net.T, l2 ? h->l2val : nullptr, two_pass_mask(h->net) ? h->inv_n : nullptr, two_pass_mask(h->net));
+        HIPCHK(h, hipGetLastError());
+    }
     h->sc_sel ^= 1;
     if (loss_out) {
         HIPCHK(h, hipMemcpyAsync(loss_out, h->loss_hist, sizeof(float), hipMemcpyDeviceToHost, h->stream));

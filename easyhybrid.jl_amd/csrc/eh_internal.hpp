@@ -41,6 +41,17 @@ struct EhImg {
     float agg_a, l2s;
 };
 
+// an optimiser chain (eh_opt_init_chain; the kernels are in eh_chain.hpp): handed to them by value
+struct EhChain {
+    int n;                             // stages, the rule among them (0: no chain installed)
+    int kind[EH_MAX_OPT_STAGES];       // EH_STAGE_*
+    float a[EH_MAX_OPT_STAGES];        // CLIPGRAD delta | CLIPNORM omega | WEIGHTDECAY lambda
+    int i_norm, i_rule;                // position of ClipNorm (-1: none; else < i_rule) and of the rule
+    int p;                             // ClipNorm: 1, 2, or 0 = Inf
+    float omega;                       // ... its threshold (= a[i_norm])
+    int thr;                           // ClipNorm(throw = true): a step with a non-finite norm is not applied
+};
+
 // --------------------------------------------------------------------------------------------
 // handle
 // --------------------------------------------------------------------------------------------
@@ -97,6 +108,9 @@ struct eh_handle_s {
     float* sc = nullptr;            // [EH_MAX_OPT_GROUPS][2][2] running beta products per optimiser group, ping-pong (group 0 = the one rule)
     EhOptTab* opt_tab = nullptr;    // per-branch optimiser rules (eh_opt_init_groups): allocated once, so a recorded graph's pointer stays valid
     int opt_groups = 1;             // groups of the current rule table; h->opt.tab != nullptr when it came from eh_opt_init_groups
+    EhChain chain{};                // eh_opt_init_chain: chain.n != 0 -> every step is step kernel + eh_reduce_kernel<false> + the chain kernels
+    int chain_gen = 0;              // 0: no chain; else the number of the eh_opt_init_chain call that installed it (what a recorded graph carries by value)
+    double* chain_part = nullptr;   // [EH_CHAIN_PARTS] partial sums of the norm pass, then the three counters of eh_opt_chain_status (allocated by eh_opt_init_chain)
     int cur = 0, sc_sel = 0;
     // fused-update mode
     bool fused = false, pending = false, fused_det = false;   // fused_det ("fused_update" 2): one kernel per step only where one workgroup covers the minibatch
@@ -190,7 +204,7 @@ struct eh_handle_s {
     float* l2val = nullptr;         // lambda * weight_l2 of the current parameters (device scalar)
     float* l2w = nullptr;           // eh_set_weight_l2_coef: one coefficient per canonical entry (device)
     int n_weights = 0;
-    struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; bool pend_ord; int ord_grid; bool grouped; };
+    struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; bool pend_ord; int ord_grid; bool grouped; int chain_gen; };
     std::vector<GraphRec> graphs;         // eh_graph_*: captured step sequences + the rotation state they start (and must end) in
     bool capturing = false;
     GraphRec cap{};

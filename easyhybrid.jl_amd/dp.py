@@ -104,6 +104,8 @@ class DataParallel:
         self.p2p_report = None                              # set by the negotiation: how far it got on every rank
         if fused and int(engine.desc.n_targets) > 1:        # the per-target weights need the GLOBAL counts before the pass: eh_dp_counts + three-kernel path
             fused = self.fused = False
+        if fused and getattr(engine, "has_chain", False):   # an OptimiserChain takes the norm of the all-reduced gradient: dp_grad, all-reduce, dp_apply
+            fused = self.fused = False
         if fused:
             try:
                 engine.set_option("fused_update", 1)

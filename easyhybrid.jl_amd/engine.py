@@ -243,6 +243,42 @@ class HybridEngine:
             raise NotImplementedError(f"optimiser rule {rule} is not implemented on the device")
         self._chk(self._lib.eh_opt_init(self._h, L.OPT_RULES[rule], lr, beta1, beta2, eps, weight_decay))
         self._opt_groups = 1
+        self._chain = None
+
+    def opt_init_chain(self, stages, rule: str = "Adam", lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999,
+                       eps: float = 1e-8, weight_decay: float = 0.0):
+        """Optimisers.OptimiserChain around one rule (eh_opt_init_chain): `stages` in order, each ("rule",), ("clipgrad", delta),
+        ("clipnorm", omega, p, throw) or ("weightdecay", lambda); the keyword arguments are opt_init's and name the rule.  Taken as given:
+        the engine validates (train._opt_groups flattens nested chains and gives the reasons first)."""
+        if rule not in L.OPT_RULES:
+            raise NotImplementedError(f"optimiser rule {rule} is not implemented on the device")
+        arr = (L.OptStage * max(1, len(stages)))()
+        for k, st in enumerate(stages):
+            kind = st[0]
+            if kind == "rule":
+                arr[k] = L.OptStage(L.EH_STAGE_RULE, 0.0, 0.0, 0)
+            elif kind == "clipgrad":
+                arr[k] = L.OptStage(L.EH_STAGE_CLIPGRAD, st[1], 0.0, 0)
+            elif kind == "clipnorm":
+                arr[k] = L.OptStage(L.EH_STAGE_CLIPNORM, st[1], st[2] if len(st) > 2 else 2.0, 1 if (len(st) < 4 or st[3]) else 0)
+            elif kind == "weightdecay":
+                arr[k] = L.OptStage(L.EH_STAGE_WEIGHTDECAY, st[1], 0.0, 0)
+            else:
+                raise NotImplementedError(f"optimiser chain stage {st!r} is not implemented on the device")
+        self._chk(self._lib.eh_opt_init_chain(self._h, arr, len(stages), L.OPT_RULES[rule], lr, beta1, beta2, eps, weight_decay))
+        self._opt_groups = 1
+        self._chain = tuple(tuple(st) for st in stages)
+
+    @property
+    def has_chain(self) -> bool:
+        """an optimiser chain is installed (opt_init_chain): steps run as step kernel + reduction + chain kernels"""
+        return getattr(self, "_chain", None) is not None
+
+    def chain_status(self):
+        """(steps applied, of them with ClipNorm's factor below 1, steps with a non-finite norm) since opt_init_chain; synchronises"""
+        a, c, n = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.eh_opt_chain_status(self._h, C.byref(a), C.byref(c), C.byref(n)))
+        return int(a.value), int(c.value), int(n.value)
 
     def opt_init_groups(self, group, rules):
         """A rule per group of flat-theta elements (per-branch TrainConfig.opt; train._opt_groups builds the tables): group[i] in
@@ -261,6 +297,7 @@ class HybridEngine:
         self._chk(self._lib.eh_opt_init_groups(self._h, group.ctypes.data, group.size, len(rules),
                                                rid.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(hyper)))
         self._opt_groups = len(rules)
+        self._chain = None
 
     @property
     def opt_groups(self) -> int:

@@ -15,7 +15,7 @@ using Libdl
 using Random
 
 export PerTarget, set_sequences!, set_training_loss!, set_agg!, set_weight_l2!, set_weight_l2_coef!, constructHybridModel, SingleNNHybridModel, MultiNNHybridModel, HybridModel, train, train!, HybridEngine, prepare_data, split_data, initialparameters,
-    Adam, AdamW, RMSProp, Descent, RbQ10, Expo_resp_model,
+    Adam, AdamW, RMSProp, Descent, OptimiserChain, ClipGrad, ClipNorm, WeightDecay, chain_status, RbQ10, Expo_resp_model,
     LinearHM, Expo2Pool, Rs_components, Rs_components3F, FluxPartModelQ10
 
 const LIB = Ref{String}(get(ENV, "EASYHYBRID_HIP_LIB", joinpath(@__DIR__, "..", "..", "..", "libeasyhybrid_hip.so")))
@@ -391,6 +391,24 @@ function get_params(e::HybridEngine)
 end
 opt_init!(e::HybridEngine; rule = 0, eta = 0.01f0, beta = (0.9f0, 0.999f0), epsilon = 1.0f-8, lambda = 0.0f0) =
     check(e, @ccall LIB[].eh_opt_init(e.h::Ptr{Cvoid}, rule::Int32, eta::Float32, beta[1]::Float32, beta[2]::Float32, epsilon::Float32, lambda::Float32)::Int32)
+"eh_opt_stage of include/easyhybrid_hip.h: kind 0 the rule, 1 ClipGrad (a = δ), 2 ClipNorm (a = ω, b = p, flags & 1 = throw), 3 WeightDecay (a = λ)"
+struct EhOptStage
+    kind::Int32
+    a::Float32
+    b::Float32
+    flags::Int32
+end
+"Optimisers.OptimiserChain around one rule (eh_opt_init_chain): the stages in order, the rule's hyper-parameters as opt_init!'s"
+function opt_init_chain!(e::HybridEngine, stages::Vector{EhOptStage}; rule = 0, eta = 0.01f0, beta = (0.9f0, 0.999f0), epsilon = 1.0f-8, lambda = 0.0f0)
+    check(e, @ccall LIB[].eh_opt_init_chain(e.h::Ptr{Cvoid}, stages::Ptr{EhOptStage}, length(stages)::Int32, rule::Int32, eta::Float32, beta[1]::Float32,
+        beta[2]::Float32, epsilon::Float32, lambda::Float32)::Int32)
+end
+"(steps applied, of them with ClipNorm's factor below 1, steps with a non-finite norm) since opt_init_chain!; synchronises"
+function chain_status(e::HybridEngine)
+    a = Ref{Int64}(0); c = Ref{Int64}(0); n = Ref{Int64}(0)
+    check(e, @ccall LIB[].eh_opt_chain_status(e.h::Ptr{Cvoid}, a::Ref{Int64}, c::Ref{Int64}, n::Ref{Int64})::Int32)
+    return (applied = a[], clipped = c[], nonfinite = n[])
+end
 "one rule per group of flat-θ elements: group[i] ∈ 0:n-1, rules[k] (0 Adam, 1 AdamW, 2 RMSProp, 3 Descent), hyper[:, k] = (eta, beta1, beta2, epsilon, lambda)"
 function opt_init_groups!(e::HybridEngine, group::Vector{UInt8}, rules::Vector{Int32}, hyper::Matrix{Float32})
     size(hyper) == (5, length(rules)) || throw(ArgumentError("hyper: 5 x $(length(rules))"))
@@ -705,6 +723,49 @@ AdamW(eta = 0.001f0, beta = (0.9f0, 0.999f0), lambda = 0.0f0) = AdamW(eta, beta,
 struct RMSProp; eta::Float32; rho::Float32; epsilon::Float32; end
 RMSProp(eta = 0.001f0, rho = 0.9f0) = RMSProp(eta, rho, 1.0f-8)
 struct Descent; eta::Float32; end
+# Optimisers.OptimiserChain(ClipNorm(1), Adam(0.01)) and its kin: duck-typed as the rules are (Optimisers' own structs carry the same field
+# names: OptimiserChain.opts, ClipGrad.delta, ClipNorm.omega / .p / .throw, WeightDecay.lambda)
+struct OptimiserChain; opts::Tuple; end
+OptimiserChain(opts...) = OptimiserChain(opts)
+struct ClipGrad; delta::Float32; end
+ClipGrad() = ClipGrad(10.0f0)
+struct ClipNorm; omega::Float32; p::Float32; throw::Bool; end
+ClipNorm(omega = 10.0f0, p = 2.0f0; throw = true) = ClipNorm(omega, p, throw)
+struct WeightDecay; lambda::Float32; end
+WeightDecay() = WeightDecay(5.0f-4)
+_is_chain(o) = nameof(typeof(o)) == :OptimiserChain
+"OptimiserChain -> (stages, the rule's opt_init! arguments); nested chains flatten.  What the device does not run is refused here with the reason (the engine checks again)"
+function _chain_args(chain)
+    stages = EhOptStage[]; rule = nothing
+    function walk(c)
+        for o in c.opts
+            n = nameof(typeof(o))
+            if n == :OptimiserChain
+                walk(o)
+            elseif n == :ClipGrad
+                o.delta >= 0 || throw(ArgumentError("ClipGrad: delta must not be negative"))
+                push!(stages, EhOptStage(1, Float32(o.delta), 0.0f0, 0))
+            elseif n == :ClipNorm
+                o.omega > 0 || throw(ArgumentError("ClipNorm: omega must be positive"))
+                Float32(o.p) in (1.0f0, 2.0f0, Inf32) || throw(ArgumentError("ClipNorm(p = $(o.p)): the device computes the 1-, 2- and Inf-norm"))
+                rule === nothing || throw(ArgumentError("OptimiserChain: ClipNorm behind the rule needs the norm of the update, a second pass: not built"))
+                push!(stages, EhOptStage(2, Float32(o.omega), Float32(o.p), o.throw ? 1 : 0))
+            elseif n == :WeightDecay
+                lam = hasproperty(o, :lambda) ? o.lambda : o.gamma
+                lam >= 0 || throw(ArgumentError("WeightDecay: lambda must not be negative"))
+                push!(stages, EhOptStage(3, Float32(lam), 0.0f0, 0))
+            else
+                rule === nothing || throw(ArgumentError("OptimiserChain: a second rule $(typeof(o)) (a chain on the device holds exactly one)"))
+                rule = _opt_args(o)
+                push!(stages, EhOptStage(0, 0.0f0, 0.0f0, 0))
+            end
+        end
+    end
+    walk(chain)
+    rule === nothing && throw(ArgumentError("OptimiserChain without a rule: the device runs ClipGrad / ClipNorm / WeightDecay around one of Adam / AdamW / RMSProp / Descent"))
+    length(stages) <= 8 || throw(ArgumentError("OptimiserChain: $(length(stages)) stages, the device keeps at most 8"))
+    return stages, rule
+end
 # (duck-typed on the field names, so Optimisers.Adam(0.01) etc. work as well)
 function _opt_args(o)
     n = nameof(typeof(o))
@@ -833,7 +894,11 @@ function train(m::SingleNNHybridModel, data; nepochs = 200, batchsize = 64, opt 
     ((xt, ft), yt), ((xv, fv), yv) = tr, va
     set_data!(e, EH_SPLIT_TRAIN, xt, ft, yt); set_data!(e, EH_SPLIT_VAL, xv, fv, yv)
     if opt isa NamedTuple
+        any(_is_chain, values(opt)) && throw(ArgumentError("per-branch optimiser: an OptimiserChain per branch is not built (its norms would be per leaf array); one chain for the whole model is"))
         opt_init_per_branch!(e, m, opt)
+    elseif _is_chain(opt)
+        stages, o = _chain_args(opt)
+        opt_init_chain!(e, stages; rule = o.rule, eta = o.eta, beta = o.beta, epsilon = o.epsilon, lambda = o.lambda)
     else
         o = _opt_args(opt)
         opt_init!(e; rule = o.rule, eta = o.eta, beta = o.beta, epsilon = o.epsilon, lambda = o.lambda)

@@ -56,7 +56,84 @@ class Descent:
     eta: float = 0.1
 
 
+@dataclass(frozen=True)
+class ClipGrad:                       # dx <- clamp(dx, -delta, delta)
+    delta: float = 10.0
+
+
+@dataclass(frozen=True)
+class ClipNorm:                       # dx <- dx * min(omega / norm(dx, p), 1), the norm over all of flat theta; throw: a non-finite norm is an error
+    omega: float = 10.0
+    p: float = 2.0
+    throw: bool = True
+
+
+@dataclass(frozen=True)
+class WeightDecay:                    # dx <- dx + lambda * x (no learning rate in it)
+    lambda_: float = 5e-4
+
+
+@dataclass(frozen=True, init=False)
+class OptimiserChain:
+    """OptimiserChain(o1, ..., on): the gradient passes through the stages in order, each seeing the current parameter, then
+    x <- x - dx.  On the device: exactly one rule, ClipGrad / WeightDecay stages on either side of it, at most one ClipNorm
+    (p = 1, 2 or Inf) in front of it, at most 8 stages; nested chains flatten."""
+    opts: tuple = ()
+
+    def __init__(self, *opts):
+        object.__setattr__(self, "opts", tuple(opts))
+
+
+def _chain_args(chain):
+    """OptimiserChain -> opt_init_chain's keyword arguments (stages + the rule's), or the reason why the device does not run it"""
+    flat = []
+
+    def walk(c):
+        for o in c.opts:
+            if isinstance(o, OptimiserChain):
+                walk(o)
+            else:
+                flat.append(o)
+    walk(chain)
+    stages, rule, have_norm = [], None, False
+    for o in flat:
+        if isinstance(o, _RULES):
+            if rule is not None:
+                raise NotImplementedError(f"OptimiserChain: a second rule {o!r} -- a chain on the device holds exactly one of Adam/AdamW/RMSProp/Descent")
+            rule = _opt_args(o)
+            stages.append(("rule",))
+        elif isinstance(o, ClipGrad):
+            if not o.delta >= 0:
+                raise ValueError(f"{o!r}: delta must not be negative")
+            stages.append(("clipgrad", float(o.delta)))
+        elif isinstance(o, WeightDecay):
+            if not o.lambda_ >= 0:
+                raise ValueError(f"{o!r}: lambda must not be negative")
+            stages.append(("weightdecay", float(o.lambda_)))
+        elif isinstance(o, ClipNorm):
+            if not o.omega > 0:
+                raise ValueError(f"{o!r}: omega must be positive")
+            if float(o.p) not in (1.0, 2.0, float("inf")):
+                raise NotImplementedError(f"{o!r}: the device computes the 1-, 2- and Inf-norm")
+            if have_norm:
+                raise NotImplementedError("OptimiserChain: a second ClipNorm -- one norm pass per step is built")
+            if rule is not None:
+                raise NotImplementedError("OptimiserChain: ClipNorm behind the rule needs the norm of the update, a second pass over it: not built "
+                                          "(put it in front of the rule)")
+            have_norm = True
+            stages.append(("clipnorm", float(o.omega), float(o.p), bool(o.throw)))
+        else:
+            raise NotImplementedError(f"OptimiserChain stage {o!r}: ClipGrad, ClipNorm, WeightDecay and one Adam/AdamW/RMSProp/Descent rule run on the device")
+    if rule is None:
+        raise NotImplementedError("OptimiserChain without a rule: a chain on the device holds exactly one of Adam/AdamW/RMSProp/Descent")
+    if len(stages) > L.EH_MAX_OPT_STAGES:
+        raise NotImplementedError(f"OptimiserChain: {len(stages)} stages, the device keeps at most {L.EH_MAX_OPT_STAGES}")
+    return dict(rule, stages=stages)
+
+
 def _opt_args(opt):
+    if isinstance(opt, OptimiserChain):
+        return _chain_args(opt)
     if isinstance(opt, Adam):
         return dict(rule="Adam", lr=opt.eta, beta1=opt.beta[0], beta2=opt.beta[1], eps=opt.epsilon)
     if isinstance(opt, AdamW):
@@ -90,6 +167,9 @@ def _opt_groups(opt, model):
     if not isinstance(opt, dict):
         return None, [_opt_args(opt)]                                 # (raises NotImplementedError)
     for k, r in opt.items():
+        if isinstance(r, OptimiserChain):
+            raise NotImplementedError(f"per-branch optimiser {k!r}: an OptimiserChain per branch is not built (Optimisers applies it per leaf array "
+                                      "there, so ClipNorm's norm would be per layer matrix); one chain for the whole model is")
         if not isinstance(r, _RULES):
             raise NotImplementedError(f"per-branch optimiser {k!r}: {r!r} -- only Adam/AdamW/RMSProp/Descent rules run on the device "
                                       "(pre-built Optimisers.setup state trees are not supported)")
@@ -116,7 +196,9 @@ def _opt_groups(opt, model):
 
 def _opt_setup(eng, opt, model):
     group, rules = _opt_groups(opt, model)
-    if group is None:
+    if group is None and "stages" in rules[0]:
+        eng.opt_init_chain(**rules[0])
+    elif group is None:
         eng.opt_init(**rules[0])
     else:
         eng.opt_init_groups(group, rules)
@@ -313,6 +395,16 @@ def _apply_step_mode(eng, tc: "TrainConfig", seq: bool = False):
     """TrainConfig.specialize / fused_update -> engine options (single-GPU training)"""
     if tc.fused_update not in (True, False, "auto") or tc.specialize not in (True, False, "auto"):
         raise ValueError("specialize / fused_update must be True, False or 'auto'")
+    if getattr(eng, "has_chain", False):      # an optimiser chain: step kernel + reduction + chain kernels (the norm needs the whole gradient first)
+        if tc.fused_update is True:
+            raise NotImplementedError("fused_update=True: the one-kernel step is not built for an OptimiserChain (ClipNorm needs the norm of the whole "
+                                      "gradient before any element moves); 'auto' and False run the step + reduce + chain kernels")
+        if not seq:
+            eng.set_option("fused_update", 0)
+            eng.set_option("specialize", (1 if tc.random_seed is not None else 2) if tc.specialize == "auto" else int(bool(tc.specialize)))
+        elif tc.specialize is True:
+            eng.set_option("specialize", 1)
+        return
     if seq:      # sequence models always run the reproducible step + reduce pair on the one kernel family: "auto" is that; True is refused by the engine
         if tc.fused_update is True:
             eng.set_option("fused_update", 1)
@@ -653,12 +745,14 @@ class TrainResults:                                                # TrainingCon
     itself): they are computed, exactly as the eager form would have, when first read; `release()` drops them and the device memory."""
 
     def __init__(self, train_history, val_history, epoch_history, train_obs_pred, val_obs_pred, train_diffs, val_diffs, ps, st, best_epoch, best_loss,
-                 timing=None, pending: Optional[_PendingPredictions] = None):
+                 timing=None, pending: Optional[_PendingPredictions] = None, chain_status=None):
         self.train_history, self.val_history, self.epoch_history = train_history, val_history, epoch_history
         self._pred = (train_obs_pred, val_obs_pred, train_diffs, val_diffs)
         self._pending = pending
         self.ps, self.st, self.best_epoch, self.best_loss = ps, st, best_epoch, best_loss
         self.timing = timing           # TrainConfig.timing: seconds of the call by part
+        # opt = OptimiserChain(...): steps applied, of them with ClipNorm's factor below 1 (their fraction is how one tunes omega), steps with a non-finite norm
+        self.chain_applied, self.chain_clipped, self.chain_nonfinite = chain_status if chain_status is not None else (None, None, None)
 
     def _get(self, i):
         if self._pending is not None:
@@ -695,6 +789,19 @@ def _losses(engine, split, targets, loss_types, agg="sum"):
         per[agg] = tot / len(targets) if agg == "mean" else tot
         out[lt] = per
     return out
+
+
+def _chain_check(eng, epoch):
+    """opt = OptimiserChain(...): the engine's counters (applied, clipped, non-finite) where the epoch loop has synchronised anyway;
+    ClipNorm(throw = true) and a step whose norm was not finite: Optimisers.jl's error (that step was not applied).  None without a chain."""
+    if not getattr(eng, "has_chain", False):
+        return None
+    stat = eng.chain_status()
+    cn = [st for st in eng._chain if st[0] == "clipnorm"]
+    if cn and cn[0][3] and stat[2]:
+        raise FloatingPointError(f"gradient has {cn[0][2]:g}-norm that is not finite in {stat[2]} step(s) up to epoch {epoch} "
+                                 "(ClipNorm(throw = true)): those steps were not applied")
+    return stat
 
 
 def _want_distributed(tc: TrainConfig) -> bool:
@@ -771,6 +878,7 @@ def _train_distributed(model, tc: TrainConfig, rng, train_split, val_split) -> T
                 first = min(s_ * b, n_loc)
                 drv.step(first, min(b, n_loc - first))
             snap = snapshot()
+            _chain_check(eng, epoch)
             if tc.keep_history:
                 history.append(snap)
             cur = snap.l_val[first_lt][aggn]
@@ -804,7 +912,7 @@ def _train_distributed(model, tc: TrainConfig, rng, train_split, val_split) -> T
         if has_bn:
             st["st_nn"] = {"running_mean": bn_out[0], "running_var": bn_out[1]}
         return TrainResults([s.l_train for s in history], [s.l_val for s in history], history, tr_op, va_op, tr_diff, va_diff,
-                            ps, st, best_epoch, best_loss)
+                            ps, st, best_epoch, best_loss, chain_status=_chain_check(eng, best_epoch))
     finally:
         eng.close(); ev.close()
 
@@ -949,6 +1057,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
             # upload of both splits | parameters, optimiser, options (incl. a run-time compilation that is not in the disk cache) | the
             # evaluation of epoch 0
             tm.update(prepare_s=t_prep - t_call, engine_s=t_eng - t_prep, upload_s=t_up - t_eng, setup_s=t_setup - t_up, initial_eval_s=time.perf_counter() - t_setup)
+        chain_stat = _chain_check(eng, 0)
         t_loop = time.perf_counter()
         for epoch in range(1, tc.nepochs + 1):
             t0 = time.perf_counter()
@@ -957,6 +1066,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
                 eng.synchronize()
                 t1 = time.perf_counter()
             snap = snapshot()                                                                  # evaluate_epoch
+            chain_stat = _chain_check(eng, epoch)                                              # (the evaluation has synchronised)
             if tm is not None:
                 t2 = time.perf_counter()
                 tm["steps_s"] += t1 - t0; tm["eval_s"] += t2 - t1; tm["epochs"] += 1
@@ -1000,7 +1110,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
             tm["final_predictions_s"] = time.perf_counter() - t_final       # (eager: forward over both splits with the returned parameters + the copies to the host)
             tm["call_s_before_close"] = time.perf_counter() - t_call
         return TrainResults([s.l_train for s in history], [s.l_val for s in history], history, *preds,
-                            ps, st, best_epoch, best_loss, tm, pending)
+                            ps, st, best_epoch, best_loss, tm, pending, chain_stat)
     finally:
         if own and not keep_engine:
             eng.close()

@@ -44,6 +44,7 @@ extern "C" {
 #define EH_MAX_PROG_CONST 16   /* its literal constants */
 #define EH_MAX_PROG_OUT 3      /* its outputs */
 #define EH_MAX_OPT_GROUPS 16   /* optimiser rules of one handle: one per top-level branch of the parameter tree (eh_opt_init_groups) */
+#define EH_MAX_OPT_STAGES 8    /* stages of an optimiser chain, the rule among them (eh_opt_init_chain) */
 
 typedef enum eh_status {
     EH_OK = 0,
@@ -273,6 +274,26 @@ int32_t eh_set_opt_state(eh_handle* h, const float* m, const float* v, int64_t n
  * The tables are taken as given (no merging of equal rules).  n_groups <= EH_MAX_OPT_GROUPS, else EH_EUNSUPPORTED.  eh_opt_init
  * returns the handle to one rule.  In this mode eh_get_opt_state / eh_set_opt_state read and write group 0's products. */
 int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, int32_t n_groups, const int32_t* rule, const float* hyper);
+/* Optimisers.OptimiserChain(stages...) around ONE rule: the gradient dx passes through the stages in order, each seeing the current
+ * parameter x, then x <- x - dx.
+ *   EH_STAGE_CLIPGRAD     dx <- clamp(dx, -a, a)                                      (ClipGrad(delta = a))
+ *   EH_STAGE_CLIPNORM     dx <- dx * min(a / ||dx||_p, 1), the norm over ALL of flat theta, p = b in {1, 2, INFINITY}; a NaN norm
+ *                         makes a NaN factor.  flags & 1 (Optimisers' throw = true): a step whose norm is not finite is not applied
+ *                         -- theta, the moments and the running products stay, the loss is reported as computed -- and is counted
+ *   EH_STAGE_WEIGHTDECAY  dx <- dx + a * x                                            (WeightDecay(lambda = a); no learning rate in it)
+ *   EH_STAGE_RULE         the rule of the arguments behind n_stages (eh_opt_init's): dx <- its update
+ * Exactly one EH_STAGE_RULE; any number of CLIPGRAD / WEIGHTDECAY stages on either side of it; at most one CLIPNORM, in front of
+ * it; n_stages <= EH_MAX_OPT_STAGES.  Anything else: EH_EUNSUPPORTED; a < 0 (CLIPNORM: a <= 0): EH_EINVAL.  Zero moments, as
+ * eh_opt_init.  A handle with a chain runs every step as step kernel + reduction + chain kernels ("fused_update" 2 resolves to
+ * that; "fused_update" 1 and eh_dp_fused_step are EH_EUNSUPPORTED); the sums of the norm run in a fixed order, so the step stays
+ * bit-reproducible.  eh_opt_init / eh_opt_init_groups return the handle to the unchained paths.  (Added without a new
+ * EH_ABI_VERSION: nothing that existed changes, and eh_version() == 4 is what callers of this library check for.) */
+enum { EH_STAGE_RULE = 0, EH_STAGE_CLIPGRAD = 1, EH_STAGE_CLIPNORM = 2, EH_STAGE_WEIGHTDECAY = 3 };
+typedef struct eh_opt_stage { int32_t kind; float a; float b; int32_t flags; } eh_opt_stage;
+int32_t eh_opt_init_chain(eh_handle* h, const eh_opt_stage* stages, int32_t n_stages,
+                          int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay);
+/* since eh_opt_init_chain: steps applied, of them steps with a factor below 1, steps with a non-finite norm (drains the stream) */
+int32_t eh_opt_chain_status(eh_handle* h, int64_t* n_applied, int64_t* n_clipped, int64_t* n_nonfinite);
 /* every group's running products: bt[2 * k], bt[2 * k + 1] for group k < n_groups (n_groups == the handle's count; 1 in one-rule mode) */
 int32_t eh_get_opt_beta_t(eh_handle* h, float* bt, int32_t n_groups);
 int32_t eh_set_opt_beta_t(eh_handle* h, const float* bt, int32_t n_groups);
