@@ -135,6 +135,9 @@ SIGNATURES = {
     "eh_set_option": (C.c_int32, [_H, C.c_char_p, C.c_int64]),
     "eh_set_target_losses": (C.c_int32, [_H, C.POINTER(C.c_int32), C.c_int32]),
     "eh_set_target_roles": (C.c_int32, [_H, C.POINTER(C.c_int32), C.c_int32]),
+    "eh_set_dropout": (C.c_int32, [_H, _F, C.c_int32, C.c_uint64, C.c_uint64]),
+    "eh_get_dropout": (C.c_int32, [_H, _F, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "eh_dropout_mask": (C.c_int32, [_H, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
 }
 
 

@@ -290,19 +290,21 @@ static bool jit_wanted(const eh_handle* h, int mode) {
     const bool prog = h->net.mech == EH_MECH_PROGRAM, closs = h->net.loss == EH_LOSS_PROGRAM;
     if (mode == EH_MODE_TRAIN_P2P && h->act == EH_ACT_PER_NET) return false;
     if (mode == EH_MODE_TRAIN_P2P) return h->jit_on && !h->jit_failed && h->specialize && !prog && !closs && !h->arch->wide;
-    if (closs || h->act == EH_ACT_PER_NET) return mode != EH_MODE_TRAIN_P2P;          // a recorded loss / per-net activations exist in run-time compiled kernels only
+    if (closs || h->act == EH_ACT_PER_NET || h->drop_on) return mode != EH_MODE_TRAIN_P2P;          // a recorded loss / per-net activations / dropout exist in run-time compiled kernels only
     return h->jit_on && !h->jit_failed && (h->specialize || prog);
 }
 // the compiled kernels for the handle's current (family, variant, descriptor); builds them on first use; nullptr = not available
 static eh_handle_s::JitEntry* jit_entry(eh_handle* h) {
     const int kf = KFAST(h);
     const bool closs = h->net.loss == EH_LOSS_PROGRAM, prog = h->net.mech == EH_MECH_PROGRAM;
-    const bool spec = h->specialize || prog || closs || h->act == EH_ACT_PER_NET;        // a model that is compiled anyway gets its descriptor baked in as well
+    const bool spec = h->specialize || prog || closs || h->act == EH_ACT_PER_NET || h->drop_on;        // a model that is compiled anyway gets its descriptor baked in as well
+    float drop[EH_MAX_HIDDEN] = {0};
+    if (h->drop_on) memcpy(drop, h->drop, sizeof drop);
     const bool want_p2p = h->specialize && h->p2p_on && !closs && !prog;
     const int lgen = closs ? h->loss_prog.gen : 0;
     for (auto& up : h->jit) {
         eh_handle_s::JitEntry& e = *up;
-        if (e.arch == h->arch && e.variant == h->variant && e.fast == kf && e.spec == spec && (e.p2p || !want_p2p) && e.loss_gen == lgen &&
+        if (e.arch == h->arch && e.variant == h->variant && e.fast == kf && e.spec == spec && (e.p2p || !want_p2p) && e.loss_gen == lgen && !memcmp(e.drop, drop, sizeof drop) &&
             (!e.spec || !memcmp(&e.net, &h->net, sizeof(EhNet)))) {
             const int st = e.state.load(std::memory_order_acquire);
             if (st < 0 && !h->jit_failed) { h->jit_log = e.log; h->jit_failed = true; }       // (a background build that failed: reported like a synchronous one)
@@ -312,8 +314,9 @@ static eh_handle_s::JitEntry* jit_entry(eh_handle* h) {
     h->jit.emplace_back(new eh_handle_s::JitEntry());
     eh_handle_s::JitEntry* je = h->jit.back().get();
     je->arch = h->arch; je->variant = h->variant; je->fast = kf; je->spec = spec; je->p2p = want_p2p; je->net = h->net; je->loss_gen = lgen;
+    memcpy(je->drop, drop, sizeof drop);
     // Only a kernel that merely REPLACES one built ahead of time may arrive later; a recorded closure / loss / per-net activation has no other form
-    const bool async = h->specialize_async && !prog && !closs && h->act != EH_ACT_PER_NET && !want_p2p && !h->capturing;
+    const bool async = h->specialize_async && !prog && !closs && h->act != EH_ACT_PER_NET && !h->drop_on && !want_p2p && !h->capturing;
     if (async) {
         const eh_model_desc desc = h->desc;
         const int act = h->act, device = h->device;
@@ -324,7 +327,8 @@ static eh_handle_s::JitEntry* jit_entry(eh_handle* h) {
         });
         return nullptr;
     }
-    const bool ok = eh_jit_build(h->desc, h->arch, h->variant, h->act, kf, spec ? &h->net : nullptr, want_p2p, closs ? &h->loss_prog : nullptr, &je->k, &je->log);
+    const bool ok = eh_jit_build(h->desc, h->arch, h->variant, h->act, kf, spec ? &h->net : nullptr, want_p2p, closs ? &h->loss_prog : nullptr, &je->k, &je->log,
+                                 /*allow_slp*/ true, h->drop_on ? je->drop : nullptr);
     je->state.store(ok ? 1 : -1, std::memory_order_release);
     if (!ok) { h->jit_log = je->log; h->jit_failed = true; return nullptr; }
     return je;
@@ -406,7 +410,7 @@ static const EhSpecKernel* spec_lookup(const eh_handle* h) {
     // the first with a kernel that failed to launch on every step and fell back silently)
     static std::mutex mu;
     static uint64_t prepared[sizeof list / sizeof list[0]] = {};          // bit d: prepared on device d
-    if (!h->aot_spec || h->lform || h->act == EH_ACT_PER_NET) return nullptr;
+    if (!h->aot_spec || h->lform || h->act == EH_ACT_PER_NET || h->drop_on) return nullptr;
     const EhArchInfo* A = h->arch;
     const EhVariant& V = A->var[h->variant];
     const int kf = KFAST(h);
@@ -464,7 +468,7 @@ static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs
     if (jit_wanted(h, mode)) {
         eh_handle_s::JitEntry* je = jit_entry(h);
         if (je && !je->verified && mode != EH_MODE_EVAL && !h->capturing && je->spec && h->net.mech != EH_MECH_PROGRAM && h->net.loss != EH_LOSS_PROGRAM &&
-            h->act != EH_ACT_PER_NET && !getenv("EH_JIT_NO_VERIFY")) {
+            h->act != EH_ACT_PER_NET && !h->drop_on && !getenv("EH_JIT_NO_VERIFY")) {      // (dropout: nothing built ahead of time computes the same)
             bool has_lprog = false;
             for (int t = 0; t < h->net.T; ++t) has_lprog = has_lprog || ((h->net.loss_t >> (4 * t)) & 15u) == (unsigned)EH_LOSS_PROGRAM;
             if (has_lprog || jit_verify(h, je, a)) je->verified = true; else je = nullptr;
@@ -476,7 +480,7 @@ static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs
             je->state.store(-1); h->jit_failed = true;
             h->jit_log = std::string("launch of the run-time compiled kernel failed: ") + hipGetErrorString(e);
         }
-        if (h->net.loss == EH_LOSS_PROGRAM && mode != EH_MODE_EVAL) return hipErrorNotSupported;     // no other form of a recorded loss exists
+        if ((h->net.loss == EH_LOSS_PROGRAM || h->drop_on) && mode != EH_MODE_EVAL) return hipErrorNotSupported;     // no other form of a recorded loss / of dropout exists
     }
     if (h->act == EH_ACT_PER_NET) return hipErrorNotSupported;       // (the table below has no such kernel; eh_create made sure the compiled one exists)
     return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
@@ -1132,6 +1136,8 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
         if (!strcmp(name, "precision") && value) return fail(h, EH_EUNSUPPORTED, "precision: the layer-wise form computes in fp32");
         return EH_OK;                        // tile / kernel-family knobs of the fused kernels: nothing to choose in the layer-wise form
     }
+    if (h->drop_on && value && (!strcmp(name, "precision") || !strcmp(name, "row_split")))
+        return fail(h, EH_EUNSUPPORTED, "%s: dropout is built for the fp32 per-wave kernels only (eh_set_dropout with all rates zero removes it)", name);
     if (!strcmp(name, "max_blocks")) {
         if (value < 1 || value > 256) return fail(h, EH_EINVAL, "max_blocks must be 1..256 (one workgroup per CU)");
         h->max_blocks = (int)value;
@@ -2184,6 +2190,17 @@ static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long 
     return EH_OK;
 }
 
+// what a training launch returned -> status.  A handle with dropout has no kernel but the one compiled at run time: where that one
+// is missing (the build failed: step_launch answers hipErrorNotSupported) the step fails with the compiler's log; any other HIP error
+// keeps its own code
+static int train_launch_status(eh_handle* h, hipError_t e) {
+    if (e == hipErrorNotSupported && h->drop_on) {
+        (void)hipGetLastError();
+        return fail(h, EH_EUNSUPPORTED, "dropout: the step kernel is compiled at run time and there is no other: %s", h->jit_log.empty() ? "no log" : h->jit_log.c_str());
+    }
+    HIPCHK(h, e);
+    return EH_OK;
+}
 static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out, bool bn_update) {
     if (h->seq) return seq_train(h, sp, idx, first, count, grid_out);
     if (h->lform) return lform_train(h, sp, idx, first, count, grid_out, bn_update);
@@ -2228,11 +2245,14 @@ static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, 
     if (!no_direct && h->arch->wide && h->arch->var[h->variant].bf16 && h->n_nets == 1 && h->desc.n_nets == 0) a.rmap = nullptr;
     a.stamps = h->stamps;
     a.fz.gacc = nullptr;
+    if (h->drop_on) {
+        if (moment_loss) return fail(h, EH_EUNSUPPORTED, "dropout: the two-pass training losses (pearsonLoss / kgeLoss / pbkgeLoss, rmse on several targets) take their batch moments in passes without masks: not built");
+        eh_drop_set(a, h->drop_seed, h->drop_step);
+    }
     if (int rc = bn_prepare(h, sp, idx, first, count, bn_update, &a)) return rc;
     const int grid = grid_for(h, count);
     *grid_out = grid;
-    HIPCHK(h, step_launch(h, EH_MODE_TRAIN, grid, &a));
-    return EH_OK;
+    return train_launch_status(h, step_launch(h, EH_MODE_TRAIN, grid, &a));
 }
 
 // one fused kernel: prologue applies the previous step's update, epilogue accumulates this step's sums
@@ -2264,6 +2284,7 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
     a.p2p = h->p2p_on ? h->p2p_dev : nullptr;
     if (h->p2p_on) a.p2pv = h->p2p_host;
     a.p2p_seq = h->p2p_on ? ++h->p2p_seq : 0u;
+    if (h->drop_on) { eh_drop_set(a, h->drop_seed, h->drop_step); }
     if (int rc = bn_prepare(h, sp, idx, first, count, true, &a)) return rc;
     const int grid = grid_for(h, count);
     if (ord) {
@@ -2277,7 +2298,10 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
         HIPCHK(h, e);
         *launched = true;
         h->ord_grid = grid;
-    } else HIPCHK(h, step_launch(h, h->p2p_on ? EH_MODE_TRAIN_P2P : EH_MODE_TRAIN, grid, &a));
+    } else {
+        if (int rc = train_launch_status(h, step_launch(h, h->p2p_on ? EH_MODE_TRAIN_P2P : EH_MODE_TRAIN, grid, &a))) return rc;
+    }
+    if (h->drop_on) h->drop_step++;      // (a training step was launched: the next one draws new masks, applied or not)
     // (the ordered step leaves the accumulator rotation alone: gstep counts the steps that add into gacc)
     h->cur ^= 1; h->sc_sel ^= 1;
     if (!ord) h->gstep++;
@@ -2295,7 +2319,7 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
 // Several fused-update steps in one launch (EH_MODE_TRAIN_MULTI, eh_device.hpp): minibatches one workgroup covers -- the reference's
 // default batch of 64 among them -- with the step-to-step state in LDS.
 static bool multi_ok(const eh_handle* h, long long batch) {
-    if (!h->fused || !h->multi_step || h->lform || h->arch->wide || h->p2p_on || h->prof || h->capturing || h->chain.n) return false;
+    if (!h->fused || !h->multi_step || h->lform || h->arch->wide || h->p2p_on || h->prof || h->capturing || h->chain.n || h->drop_on) return false;
     if (h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->bn_on && (h->bn_ext || h->bn_no_self || batch > EH_BN_SELF_MAX)) return false;
     if (h->arch->var[h->variant].lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(h->net.n_theta, h->n_acc, h->opt.tab != nullptr) > EH_LDS_LIMIT) return false;
@@ -2359,7 +2383,7 @@ static int launch_chain(eh_handle* h, bool raw, float* sc_in, float* sc_out, flo
 // allowed and the pair's reduce would run eh_reduce_kernel<true, 16> on slab rows the per-wave kernels wrote -- its bits are that pair's
 static bool ord_ok(const eh_handle* h, int grid) {
     static const int cw_env = getenv("EH_REDUCE_CW") ? atoi(getenv("EH_REDUCE_CW")) : 0;      // (the A/B switch of do_step)
-    if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS || h->chain.n) return false;
+    if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS || h->chain.n || h->drop_on) return false;
     if (h->lform || h->arch->wide || h->p2p_on || h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->img.l2c != 0.0f || h->img.l2w || two_pass_mask(h->net) || h->dp_weights || h->dp_moments) return false;
     // (the step stages its row in LDS over the parameter image before it stores it)
@@ -2415,6 +2439,7 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     int rc = launch_train_kernel(h, sp, idx, first, count, &grid, apply);
     h->l_apply = nullptr;
     if (rc) return rc;
+    if (h->drop_on && apply) h->drop_step++;      // (eh_loss_and_grad leaves the count: its gradient is the one the next training step applies)
     if (prof && !burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
     if (h->l_applied) {                  // theta, the moments, the loss and the beta products are done (a chain: the gradient is; its kernels follow)
         h->l_applied = false;
@@ -3062,6 +3087,69 @@ int32_t eh_set_opt_state(eh_handle* h, const float* m, const float* v, int64_t n
     return EH_OK;
 }
 
+// ---- dropout (eh_device.hpp: EH_JIT_DROPOUT) -----------------------------------------------------------
+int32_t eh_set_dropout(eh_handle* h, const float* rate, int32_t n_hidden, uint64_t seed, uint64_t step) {
+    if (!h) return EH_EINVAL;
+    if (!rate || n_hidden != h->desc.n_hidden) return fail(h, EH_EINVAL, "eh_set_dropout: %d rates for %d hidden layers", (int)n_hidden, (int)h->desc.n_hidden);
+    bool any = false;
+    for (int l = 0; l < n_hidden; ++l) {
+        if (!(rate[l] >= 0.0f && rate[l] < 1.0f)) return fail(h, EH_EINVAL, "eh_set_dropout: rate[%d] = %g (0 <= p < 1)", l, (double)rate[l]);
+        any = any || rate[l] > 0.0f;
+    }
+    if (any) {
+        const char* why = nullptr;
+        if (h->seq) why = "sequence models";
+        else if (h->lform) why = "the layer-wise form (more than 3 hidden layers or widths above 128)";
+        else if (h->desc.n_nets != 0) why = "MultiNN models";
+        else if (h->arch->var[h->variant].bf16) why = "the bf16 kernels (precision option)";      // (a row-split family too: said first)
+        else if (h->arch->wide) why = "the row-split kernels (hidden widths above 64, or the row_split option)";
+        else if (h->p2p_on || h->p2p_alloc || h->comm || h->lgroup) why = "data parallelism (a communicator or a peer-to-peer exchange is set up on this handle)";
+        else if (h->capturing) why = "a handle that is recording a graph";
+        if (why) return fail(h, EH_EUNSUPPORTED, "eh_set_dropout: dropout is built for the fp32 per-wave fused kernels of single-network models, not for %s", why);
+        if (!h->jit_on) return fail(h, EH_EUNSUPPORTED, "eh_set_dropout: the dropout kernels are compiled at run time and the jit option is off (EH_JIT=0)");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    h->drop_on = any;
+    for (int l = 0; l < EH_MAX_HIDDEN; ++l) h->drop[l] = (any && l < n_hidden) ? rate[l] : 0.0f;
+    h->drop_seed = seed; h->drop_step = step;
+    if (any) { h->jit_failed = false; h->jit_log.clear(); }      // (a build that failed for other rates says nothing about these)
+    return EH_OK;
+}
+
+int32_t eh_get_dropout(eh_handle* h, float* rate, int32_t cap, uint64_t* seed, uint64_t* step) {
+    if (!h) return EH_EINVAL;
+    if (rate) {
+        if (cap < h->desc.n_hidden) return fail(h, EH_EINVAL, "eh_get_dropout: room for %d rates, the model has %d hidden layers", (int)cap, (int)h->desc.n_hidden);
+        for (int l = 0; l < h->desc.n_hidden; ++l) rate[l] = h->drop[l];
+    }
+    if (seed) *seed = h->drop_seed;
+    if (step) *step = h->drop_step;
+    return EH_OK;
+}
+
+int32_t eh_dropout_mask(eh_handle* h, int32_t layer, uint64_t step, int64_t count, uint8_t* keep) {
+    if (!h || !keep) return EH_EINVAL;
+    if (layer < 0 || layer >= h->desc.n_hidden || count < 0 || count > (1LL << 24)) return fail(h, EH_EINVAL, "eh_dropout_mask: layer %d, count %lld", (int)layer, (long long)count);
+    if (h->desc.n_nets != 0) return fail(h, EH_EUNSUPPORTED, "eh_dropout_mask: single-network models only");
+    const int width = h->desc.hidden[layer];
+    if (count == 0) return EH_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t n = (size_t)count * (size_t)width;
+    uint8_t* dev = nullptr;
+    HIPCHK(h, hipMalloc(&dev, n));
+    const int nq = (width + 3) / 4;
+    const long long work = (long long)count * nq;
+    hipLaunchKernelGGL(eh_dropout_mask_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, h->stream, (unsigned long long)h->drop_seed, (unsigned long long)step, (int)layer, width,
+                       (long long)count, eh_drop_threshold(h->drop[layer]), dev);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(keep, dev, n, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(dev);
+    HIPCHK(h, e);
+    return EH_OK;
+}
+
 int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, int64_t first, int64_t count, float* loss_out) {
     if (!h) return EH_EINVAL;
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_train_step: call eh_opt_init first");
@@ -3140,6 +3228,7 @@ static int make_permutation(eh_handle* h, long long N, uint64_t seed) {
 int32_t eh_graph_begin(eh_handle* h) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: graph capture is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: dropout: every step carries its own step count in its arguments, a recorded graph would replay one mask: not built");
     if (h->capturing) return fail(h, EH_ESTATE, "eh_graph_begin: already capturing");
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
@@ -3287,6 +3376,7 @@ int32_t eh_set_weight_l2_coef(eh_handle* h, const float* coef, int64_t n) {
 int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     HIPCHK(h, hipSetDevice(h->device));
     if (!on) { h->perm_valid = false; return EH_OK; }      // (stream order keeps earlier steps on the old permutation)
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
@@ -3299,6 +3389,7 @@ int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
 int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (h->net.T != 1 && !h->tcount_ready) return fail(h, EH_ESTATE, "eh_dp_grad: multi-target model: call eh_dp_counts for this window and all-reduce EH_BUF_TCOUNT first");
     const unsigned tpm_dp = two_pass_mask(h->net);
     if (tpm_dp && h->mom_stage != 2) return fail(h, EH_ESTATE, "eh_dp_grad: rmse (multi-target) / pearson / kge training losses need the moments of the GLOBAL batch's predictions first: eh_dp_moments stage 0, all-reduce EH_BUF_MOMENT, stage 1, all-reduce");
@@ -3331,6 +3422,7 @@ int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
 int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
     int rc = check_window(h, sp, first, count, "eh_dp_counts");
@@ -3357,6 +3449,7 @@ int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
 int32_t eh_dp_moments(eh_handle* h, int64_t first, int64_t count, int32_t stage) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     const EhNet& net = h->net;
     if (!two_pass_mask(net)) return fail(h, EH_ESTATE, "eh_dp_moments: the training loss needs no batch moments of the predictions");
     if (h->lform) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: the layer-wise form has no data-parallel seam for the two-pass training losses");
@@ -3407,6 +3500,7 @@ int32_t eh_set_target_shift(eh_handle* h, int32_t split, const float* shift, int
 int32_t eh_dp_fused_step(eh_handle* h, int64_t first, int64_t count, int32_t* buffer_index) {
     if (!h || !buffer_index) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->fused) return fail(h, EH_ESTATE, "eh_dp_fused_step: set the fused_update option first");
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: multi-target models need the global per-target counts before the pass: use eh_dp_counts + eh_dp_grad (fused_update off)");
     if (h->bn_on && !h->bn_ext) return fail(h, EH_ESTATE, "eh_dp_fused_step: input BatchNorm needs the global batch statistics: call eh_dp_bn_stats and all-reduce EH_BUF_BNSTAT first");
@@ -3433,6 +3527,7 @@ int32_t eh_set_bn_shift(eh_handle* h, const float* shift, int64_t n) {
 int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->bn_on) return fail(h, EH_ESTATE, "eh_dp_bn_stats: the model has no input BatchNorm");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
@@ -3451,6 +3546,7 @@ int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
 int32_t eh_dp_apply(eh_handle* h, float* loss_out) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: data parallelism is not built for sequence models");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_dp_apply: call eh_opt_init first");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_loss_hist(h, 1);

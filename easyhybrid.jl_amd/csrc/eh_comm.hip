@@ -172,6 +172,7 @@ static int p2p_wire(eh_handle* h) {
 
 int32_t eh_p2p_init(eh_handle* h, int32_t world, int32_t rank, void* handle_out, int64_t handle_bytes) {
     if (!h || !handle_out) return EH_EINVAL;
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_p2p_init: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (handle_bytes < (int64_t)sizeof(hipIpcMemHandle_t)) return fail(h, EH_EINVAL, "eh_p2p_init: handle buffer of %lld bytes, need %zu", (long long)handle_bytes, sizeof(hipIpcMemHandle_t));
     hipIpcMemHandle_t hd;
     if (int rc = p2p_alloc(h, world, rank, &hd, "eh_p2p_init")) return rc;
@@ -270,6 +271,7 @@ int32_t eh_p2p_init_local(eh_handle* const* handles, int32_t n, int32_t selftest
     *ok = 0;
     for (int i = 0; i < n; ++i) {
         if (!handles[i]) return fail(nullptr, EH_EINVAL, "eh_p2p_init_local: handle %d is NULL", i);
+        if (handles[i]->drop_on) return fail(handles[i], EH_EUNSUPPORTED, "eh_p2p_init_local: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
         for (int j = 0; j < i; ++j) if (handles[j] == handles[i]) return fail(handles[i], EH_EINVAL, "eh_p2p_init_local: handle %d is listed twice", i);
         if (handles[i]->net.n_theta != handles[0]->net.n_theta || handles[i]->n_acc != handles[0]->n_acc)
             return fail(handles[i], EH_EINVAL, "eh_p2p_init_local: handle %d is a different model (%d parameters, handle 0 has %d)", i, handles[i]->net.n_theta, handles[0]->net.n_theta);
@@ -547,6 +549,7 @@ int32_t eh_dp_allreduce(eh_handle* h, int32_t which, int32_t index) {
 
 int32_t eh_dp_train_step(eh_handle* h, int64_t first, int64_t count, float* loss_out) {
     if (!h) return EH_EINVAL;
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_train_step: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->comm && !h->lgroup) return fail(h, EH_ESTATE, "eh_dp_train_step: call eh_comm_init first");
     if (h->lgroup && h->lgroup->n > 1) return fail(h, EH_ESTATE, "eh_dp_train_step: the members of a local group step together: eh_dp_train_step_group");
     int rc;
@@ -582,6 +585,7 @@ int32_t eh_dp_train_step_group(eh_handle* const* hs, int32_t n, const int64_t* f
     if (!hs || !first || n < 1 || n > EH_GSHARDS) return fail(nullptr, EH_EINVAL, "eh_dp_train_step_group: %d handles (1..%d)", n, EH_GSHARDS);
     for (int i = 0; i < n; ++i) {
         if (!hs[i]) return fail(nullptr, EH_EINVAL, "eh_dp_train_step_group: handle %d is NULL", i);
+        if (hs[i]->drop_on) return fail(hs[i], EH_EUNSUPPORTED, "eh_dp_train_step_group: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
         if (!hs[i]->comm && !hs[i]->lgroup) return fail(hs[i], EH_ESTATE, "eh_dp_train_step_group: handle %d has no communicator (eh_comm_init / eh_comm_init_local)", i);
         if (hs[i]->fused != hs[0]->fused || hs[i]->net.T != hs[0]->net.T || hs[i]->bn_on != hs[0]->bn_on || hs[i]->p2p_on != hs[0]->p2p_on)
             return fail(hs[i], EH_EINVAL, "eh_dp_train_step_group: handle %d runs a different step mode than handle 0", i);

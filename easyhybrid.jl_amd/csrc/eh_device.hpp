@@ -464,10 +464,17 @@ struct EhStepArgs {
     int ms_direct;          // set by the multi-step kernel: ONE workgroup, so the step that produced the gradient applies the optimiser itself (see eh_ms_apply)
     long long ms_end;
     float* ms_loss;
-    long long pf_first, pf_count;     // set by the multi-step kernel: the NEXT step's window (pf_count == 0: none) -- its records are fetched behind this step's compute
+    long long pf_first, pf_count;     // read under `carry` only (EH_MODE_TRAIN_MULTI, eh_step_body); set by the multi-step kernel: the NEXT step's window (pf_count == 0: none) -- its records are fetched behind this step's compute
+    // (kernels compiled with EH_JIT_DROPOUT -- never multi-step launches -- read these two words as the key and the step count of the mask
+    //  generator, eh_drop_seed / eh_drop_step below: the argument block is twelve 64-byte lines to the byte (eh_kernarg_warm), and a
+    //  union here changed the code of kernels that never look at it)
     EhOrd ord;            // EH_MODE_TRAIN_ORD only
 };
 enum { EH_LPROG_WORDS = 24 + EH_MAX_PROG };
+static_assert(sizeof(long long) == sizeof(unsigned long long), "seed and step of the dropout kernels ride in pf_first / pf_count");
+__host__ __device__ inline unsigned long long eh_drop_seed(const EhStepArgs& a) { return (unsigned long long)a.pf_first; }
+__host__ __device__ inline unsigned long long eh_drop_step(const EhStepArgs& a) { return (unsigned long long)a.pf_count; }
+__host__ inline void eh_drop_set(EhStepArgs& a, unsigned long long seed, unsigned long long step) { a.pf_first = (long long)seed; a.pf_count = (long long)step; }
 
 #define EH_BN_EPS 1e-5f
 #define EH_BN_MOMENTUM 0.1f
@@ -593,6 +600,65 @@ template <int ACT>
 __device__ __forceinline__ float eh_dact_row(float s, int l, int row) {
     if constexpr (ACT == EH_ACT_PER_NET) return eh_dact_z_id(eh_row_act(l, row), s);
     else return eh_dact<ACT>(s);
+}
+
+// ------------------------------------------------------------------------------------------
+// Dropout (Lux `Dropout(p)`, dims = :) behind a hidden layer, in kernels compiled at run time with EH_JIT_DROPOUT only: the generated
+// header holds the per-layer thresholds and 1 / (1 - p) as constants.  The masks come from a counter-based generator, Philox4x32-10
+// (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants): no state, so a mask is a function of
+// (seed, step, sample position in the minibatch, layer, unit) alone -- the same bits whatever the grid, the tile size or the wave that
+// owns the sample.  One call yields the four words of one f32x4 C/D fragment: sample k, units 4 q .. 4 q + 3.
+//   key = (seed lo, seed hi); counter = (k, 32 l + q, step lo, step hi); unit u is kept iff word (u & 3) >= thr, unsigned.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void eh_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// bit r set: unit 4 q + r of sample k is kept (eh_dropout_mask_kernel calls this with logical coordinates, the step kernel with its lanes')
+__device__ __forceinline__ unsigned eh_drop_keep4(unsigned long long seed, unsigned long long step, unsigned k, int l, unsigned q, unsigned thr) {
+    unsigned w[4];
+    eh_philox4x32_10(k, 32u * (unsigned)l + q, (unsigned)step, (unsigned)(step >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+    return (w[0] >= thr ? 1u : 0u) | (w[1] >= thr ? 2u : 0u) | (w[2] >= thr ? 4u : 0u) | (w[3] >= thr ? 8u : 0u);
+}
+#ifdef EH_JIT_DROPOUT
+#include "eh_jit_dropout.inc"      // constexpr unsigned eh_drop_thr(int layer); constexpr float eh_drop_invp(int layer)
+#else
+__device__ __forceinline__ constexpr unsigned eh_drop_thr(int) { return 0u; }
+__device__ __forceinline__ constexpr float eh_drop_invp(int) { return 1.0f; }
+#endif
+// The backward pass needs, per unit, the undropped value (h or z, for act') AND whether it was kept.  Where it was dropped its delta
+// and its activation are both 0 whatever act' is, so the value kept for the backward pass -- register or LDS image -- carries the mask
+// itself: a dropped unit holds this NaN pattern instead (compared as bits; a real value never has it).  No second image, no second
+// Philox call.
+// EVERY reader of a kept value in a dropout build goes through eh_drop_sel, which SELECTS on the bit pattern and never multiplies the
+// marker: the `hs` registers / the HS image read in C/D layout for act' and the K == 1 output-weight gradient (`sv`), and the HS image read
+// in operand layout for the MFMA weight gradients (`b4` of the output layer, `bH` of layer l).  A new reader that skips it turns a dropped
+// unit into NaN.  The build must honour NaNs: no -ffast-math / -ffinite-math-only on these kernels (eh_jit.hip's options have none) -- a
+// compiler allowed to assume finite values may fold the select away.
+#define EH_DROP_SENT 0x7fc0d809u
+// forward: h (the activation, handed to the next layer) -> h * keep / (1 - p); s (what the backward pass keeps) -> s or the marker
+__device__ __forceinline__ void eh_drop_fwd(unsigned long long seed, unsigned long long step, int l, unsigned k, unsigned q, f32x4& h, f32x4& s) {
+    const unsigned thr = eh_drop_thr(l);
+    if (thr == 0u) return;
+    const unsigned kb = eh_drop_keep4(seed, step, k, l, q, thr);
+    const float ip = eh_drop_invp(l);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const bool keep = ((kb >> r) & 1u) != 0u;
+        h[r] = keep ? h[r] * ip : 0.0f;
+        s[r] = keep ? s[r] : __uint_as_float(EH_DROP_SENT);
+    }
+}
+// backward: v (an activation or a delta derived from the kept value `kept`) -> v * keep / (1 - p)
+__device__ __forceinline__ float eh_drop_sel(int l, float kept, float v) {
+    if (eh_drop_thr(l) == 0u) return v;
+    return __float_as_uint(kept) != EH_DROP_SENT ? v * eh_drop_invp(l) : 0.0f;
 }
 
 // cross-lane sums on the DPP network (no LDS round trips): rotate-and-add inside each row of 16
@@ -1113,6 +1179,14 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     static_assert(!PROG || FAST == 4, "the program kernels are generic kernels");
     constexpr bool KEEPH = TRAIN && !EhStoresZ<ACT>::value && NL * NBH * NT * 4 <= EH_KEEPH_MAX;   // activations stay in registers for act'
     constexpr int NHS = KEEPH ? NL : 1, NHM = KEEPH ? NBH : 1, NHT = KEEPH ? NT : 1;
+#ifdef EH_JIT_DROPOUT
+    constexpr bool DROP = TRAIN;                          // (evaluation and forward passes: test mode, dropout is the identity)
+    // (a.pf_first / a.pf_count hold seed and step here: the reads of pf_count below sit under `carry`, which only a multi-step launch
+    //  passes, and no multi-step or ordered kernel is ever instantiated with dropout -- eh_jit.hip builds train + eval only)
+    static_assert(MODE == EH_MODE_TRAIN || MODE == EH_MODE_EVAL, "dropout kernels are single-step train / eval kernels");
+#else
+    constexpr bool DROP = false;
+#endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const wl = smem;
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
@@ -1695,6 +1769,16 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const f32x4 z4 = h[m][t], hv4 = eh_act4_rows<ACT>(z4, 0, 16 * m + 4 * g);
+                if constexpr (DROP) {      // the next layer and the weight gradients see the dropped activation; act' the kept value (or the marker)
+                    f32x4 hd4 = hv4, sv4 = EhStoresZ<ACT>::value ? z4 : hv4;
+                    eh_drop_fwd(eh_drop_seed(a), eh_drop_step(a), 0, (unsigned)(tile * MT + 16 * t + c), (unsigned)(4 * m + g), hd4, sv4);
+                    h[m][t] = hd4;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (NL > 1 || !K1 || !KEEPH) HS[(16 * m + 4 * g + r) * SR + 16 * t + c] = EhStoresZ<ACT>::value ? eh_vgpr(sv4[r]) : sv4[r];
+                    if constexpr (KEEPH) hs[0][m][t] = sv4;
+                    continue;
+                }
                 h[m][t] = hv4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -1741,6 +1825,16 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     const f32x4 z4 = hn[m][t], hv4 = eh_act4_rows<ACT>(z4, l, 16 * m + 4 * g);
+                    if constexpr (DROP) {
+                        f32x4 hd4 = hv4, sv4 = EhStoresZ<ACT>::value ? z4 : hv4;
+                        eh_drop_fwd(eh_drop_seed(a), eh_drop_step(a), l, (unsigned)(tile * MT + 16 * t + c), (unsigned)(4 * m + g), hd4, sv4);
+                        h[m][t] = hd4;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (l < NL - 1 || !K1 || !KEEPH) Hl[(16 * m + 4 * g + r) * SR + 16 * t + c] = EhStoresZ<ACT>::value ? eh_vgpr(sv4[r]) : sv4[r];
+                        if constexpr (KEEPH) hs[l < NHS ? l : 0][m < NHM ? m : 0][t < NHT ? t : 0] = sv4;
+                        continue;
+                    }
                     h[m][t] = hv4;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)      // the last layer's image is only read back for act' / dWo when those do not have it in registers
@@ -1932,9 +2026,11 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                     for (int r = 0; r < 4; ++r) {
                         const int ad = (16 * m + 4 * g + r) * SR + 16 * t + c;
                         const float sv = KEEPH ? hs[NL - 1 < NHS ? NL - 1 : 0][m < NHM ? m : 0][t < NHT ? t : 0][r] : Hl[ad];
-                        const float hv = eh_hval<ACT>(sv, NL - 1, 16 * m + 4 * g + r);
+                        float hv = eh_hval<ACT>(sv, NL - 1, 16 * m + 4 * g + r);
+                        if constexpr (DROP) hv = eh_drop_sel(NL - 1, sv, hv);
                         aWoV[m][r] = fmaf(dOt[t], hv, aWoV[m][r]);
-                        const float d = w4[r] * dOt[t] * eh_dact_row<ACT>(sv, NL - 1, 16 * m + 4 * g + r);
+                        float d = w4[r] * dOt[t] * eh_dact_row<ACT>(sv, NL - 1, 16 * m + 4 * g + r);
+                        if constexpr (DROP) d = eh_drop_sel(NL - 1, sv, d);
                         dz[m][t][r] = d;
                         if constexpr (DZ_LAST) Hl[ad] = d;         // delta replaces the activation it was derived from (same lane, same word)
                     }
@@ -1957,7 +2053,11 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     f32x4 b4 = *(const f32x4*)&Hl[(16 * n + c) * SR + 16 * t + 4 * g];
-                    if (EhStoresZ<ACT>::value) {
+                    if constexpr (DROP) {
+                        const f32x4 b4k = b4;
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) b4[s] = eh_drop_sel(NL - 1, b4k[s], eh_hval<ACT>(b4k[s], NL - 1, 16 * n + c));
+                    } else if (EhStoresZ<ACT>::value) {
 #pragma unroll
                         for (int s = 0; s < 4; ++s) b4[s] = eh_hval<ACT>(b4[s], NL - 1, 16 * n + c);
                     }
@@ -1992,7 +2092,8 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                     for (int r = 0; r < 4; ++r) {
                         const int ad = (16 * m + 4 * g + r) * SR + 16 * t + c;
                         const float sv = KEEPH ? hs[NL - 1 < NHS ? NL - 1 : 0][m < NHM ? m : 0][t < NHT ? t : 0][r] : Hl[ad];
-                        const float d = dh[t][r] * eh_dact_row<ACT>(sv, NL - 1, 16 * m + 4 * g + r);
+                        float d = dh[t][r] * eh_dact_row<ACT>(sv, NL - 1, 16 * m + 4 * g + r);
+                        if constexpr (DROP) d = eh_drop_sel(NL - 1, sv, d);
                         dz[m][t][r] = d;
                         if constexpr (DZ_LAST) Hl[ad] = d;
                     }
@@ -2014,7 +2115,11 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     bH[n][t] = *(const f32x4*)&Hp[(16 * n + c) * SR + 16 * t + 4 * g];
-                    if (EhStoresZ<ACT>::value) {
+                    if constexpr (DROP) {      // the image holds the kept value or the marker: the operand is the dropped activation
+                        const f32x4 bHk = bH[n][t];
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) bH[n][t][s] = eh_drop_sel(l - 1, bHk[s], eh_hval<ACT>(bHk[s], l - 1, 16 * n + c));
+                    } else if (EhStoresZ<ACT>::value) {
 #pragma unroll
                         for (int s = 0; s < 4; ++s) bH[n][t][s] = eh_hval<ACT>(bH[n][t][s], l - 1, 16 * n + c);
                     }
@@ -2083,7 +2188,8 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                     for (int r = 0; r < 4; ++r) {
                         const int ad = (16 * m + 4 * g + r) * SR + 16 * t + c;
                         const float sv = KEEPH ? hs[l - 1 < NHS ? l - 1 : 0][m < NHM ? m : 0][t < NHT ? t : 0][r] : Hp[ad];
-                        const float d = dn[m][t][r] * eh_dact_row<ACT>(sv, l - 1, 16 * m + 4 * g + r);
+                        float d = dn[m][t][r] * eh_dact_row<ACT>(sv, l - 1, 16 * m + 4 * g + r);
+                        if constexpr (DROP) d = eh_drop_sel(l - 1, sv, d);
                         dz[m][t][r] = d;
                         if (need_dz) Hp[ad] = d;
                     }

@@ -189,7 +189,7 @@ struct eh_handle_s {
     // EH_MECH_PROGRAM: kernels compiled at run time around the program (eh_jit.hpp), one entry per (kernel family, variant) used
     // state: 0 = being compiled by `worker` ("specialize" = 2: the steps run the kernels built ahead of time meanwhile), 1 = ready, -1 = failed
     // verified: the kernel has been run next to the one built ahead of time on one window of the user's data and agreed (jit_verify, eh_api.hip)
-    struct JitEntry { const EhArchInfo* arch; int variant, fast; bool spec, p2p; EhNet net; int loss_gen; std::atomic<int> state{0}; EhJitKernel k; std::thread worker; std::string log; bool verified = false; };
+    struct JitEntry { const EhArchInfo* arch; int variant, fast; bool spec, p2p; EhNet net; int loss_gen; float drop[EH_MAX_HIDDEN] = {0}; std::atomic<int> state{0}; EhJitKernel k; std::thread worker; std::string log; bool verified = false; };
     std::vector<std::unique_ptr<JitEntry>> jit;
     bool check_idx = false;         // "check_idx" option: range-check device-side minibatch indices before the step (debug)
     bool empty_nan = false;         // "empty_target_nan" option: eh_loss_and_grad reports NaN when a target of a non-empty batch has no valid sample (the reference's value; gradient unchanged)
@@ -201,6 +201,11 @@ struct eh_handle_s {
     bool specialize = false;        // "specialize" option: every model gets kernels compiled around its descriptor
     EhLossProg loss_prog;           // eh_set_loss_program (EH_LOSS_PROGRAM)
     std::string jit_log;
+    // eh_set_dropout: Lux Dropout(drop[l]) behind hidden layer l in the training passes (per-wave kernels compiled at run time with the
+    // rates in them; eh_device.hpp EH_JIT_DROPOUT).  drop_step counts the training steps launched since, applied or not
+    bool drop_on = false;
+    float drop[EH_MAX_HIDDEN] = {0};
+    unsigned long long drop_seed = 0, drop_step = 0;
     float* l2val = nullptr;         // lambda * weight_l2 of the current parameters (device scalar)
     float* l2w = nullptr;           // eh_set_weight_l2_coef: one coefficient per canonical entry (device)
     int n_weights = 0;

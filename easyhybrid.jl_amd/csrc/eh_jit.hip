@@ -335,6 +335,21 @@ static std::string eh_jit_rowact_source(const eh_model_desc& d) {
     return s;
 }
 
+// eh_jit_dropout.inc: the per-layer constants of Dropout(p_l) behind hidden layer l -- thr = floor(p 2^32) (a word below it drops the
+// unit; 0 = no dropout behind this layer, whose code then folds away) and 1 / (1 - p) in fp32, written as an exact hexadecimal literal
+static std::string eh_jit_dropout_source(const float* drop, int n_hidden) {
+    std::string t = "__device__ __forceinline__ constexpr unsigned eh_drop_thr(int l) { return", v = "__device__ __forceinline__ constexpr float eh_drop_invp(int l) { return";
+    char b[96];
+    for (int l = 0; l < n_hidden; ++l) {
+        if (!(drop[l] > 0.0f)) continue;
+        snprintf(b, sizeof b, " l == %d ? %uu :", l, eh_drop_threshold(drop[l]));
+        t += b;
+        snprintf(b, sizeof b, " l == %d ? %af :", l, (double)eh_drop_scale(drop[l]));
+        v += b;
+    }
+    return t + " 0u; }\n" + v + " 1.0f; }\n";
+}
+
 // A build that does not get through the compiler is tried again more conservatively: level 1 without the SLP vectoriser (where the
 // first attempt had it), level 2 at -O1.  Seen with the hiprtc / comgr that PyTorch bundles (ROCm 7.0) on the per-net-activation
 // row-split kernels: "Illegal instruction detected: both data operands should be VGPR or AGPR" (a merged ds_write2_b32 with one
@@ -342,13 +357,14 @@ static std::string eh_jit_rowact_source(const eh_model_desc& d) {
 // none: these models have no kernel built ahead of time.
 static thread_local int g_jit_level = 0;
 bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int act, int fast, const EhNet* spec, bool with_p2p,
-                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp) {
+                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp, const float* drop) {
     const EhVariant& V = A->var[variant];
     const bool prog = d.mech == EH_MECH_PROGRAM;
     const std::string mech = prog ? eh_jit_mech_source(d) : std::string();
     const std::string lsrc = loss ? eh_jit_loss_source(*loss) : std::string();
     const bool rowact = act == EH_ACT_PER_NET;
     const std::string rsrc = rowact ? eh_jit_rowact_source(d) : std::string();
+    const std::string dsrc = drop ? eh_jit_dropout_source(drop, d.n_hidden) : std::string();
     // (hiprtc has the HIP device runtime built in but no C library headers)
     std::string src = "typedef signed char int8_t; typedef unsigned char uint8_t; typedef int int32_t; typedef unsigned int uint32_t;\n"
                       "typedef long long int64_t; typedef unsigned long long uint64_t;\n";
@@ -369,6 +385,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     if (prog) src += "#define EH_JIT_MECH 1\n";
     if (loss) src += "#define EH_JIT_LOSS 1\n";
     if (rowact) src += "#define EH_JIT_ROWACT 1\n";
+    if (drop) src += "#define EH_JIT_DROPOUT 1\n";
     if (spec) {
         char b[512];
         snprintf(b, sizeof b, "#define EH_SPEC_NET %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %uu, %uu, %uu, %uu, %uu\n", spec->P, spec->K, spec->G, spec->T, spec->F,
@@ -376,12 +393,13 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
         src += b;
     }
     src += V.so ? "#include \"eh_bf16_sample.hpp\"\n" : V.bf16 ? "#include \"eh_wide_bf16.hpp\"\n" : A->wide ? "#include \"eh_wide.hpp\"\n" : "#include \"eh_device.hpp\"\n";
-    const char* hnames[8] = {"eh_device.hpp", "eh_wide.hpp", "easyhybrid_hip.h", "eh_wide_bf16.hpp", "eh_bf16_sample.hpp", nullptr, nullptr, nullptr};
-    const char* hsrc[8] = {eh_src_device, eh_src_wide, eh_src_public, eh_src_widebf, eh_src_bfs, nullptr, nullptr, nullptr};
+    const char* hnames[9] = {"eh_device.hpp", "eh_wide.hpp", "easyhybrid_hip.h", "eh_wide_bf16.hpp", "eh_bf16_sample.hpp", nullptr, nullptr, nullptr, nullptr};
+    const char* hsrc[9] = {eh_src_device, eh_src_wide, eh_src_public, eh_src_widebf, eh_src_bfs, nullptr, nullptr, nullptr, nullptr};
     int nh = 5;
     if (prog) { hnames[nh] = "eh_jit_mech.inc"; hsrc[nh++] = mech.c_str(); }
     if (loss) { hnames[nh] = "eh_jit_loss.inc"; hsrc[nh++] = lsrc.c_str(); }
     if (rowact) { hnames[nh] = "eh_jit_rowact.inc"; hsrc[nh++] = rsrc.c_str(); }
+    if (drop) { hnames[nh] = "eh_jit_dropout.inc"; hsrc[nh++] = dsrc.c_str(); }
     hiprtcProgram hp = nullptr;
     if (hiprtcCreateProgram(&hp, src.c_str(), "eh_jit.hip", nh, hsrc, hnames) != HIPRTC_SUCCESS) { *log = "hiprtcCreateProgram failed"; return false; }
     // which kernels: train + eval, the cross-GPU train kernel when asked for, and -- per-wave family, registry model with its descriptor
@@ -390,7 +408,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     int modes[5], nmode = 0;
     modes[nmode++] = EH_MODE_TRAIN; modes[nmode++] = EH_MODE_EVAL;
     if (with_p2p && !A->wide && !prog) modes[nmode++] = EH_MODE_TRAIN_P2P;
-    if (!A->wide && !prog && !loss && !rowact && spec && spec->T == 1 && !(fast & 4)) { modes[nmode++] = EH_MODE_TRAIN_MULTI; modes[nmode++] = EH_MODE_TRAIN_ORD; }
+    if (!A->wide && !prog && !loss && !rowact && !drop && spec && spec->T == 1 && !(fast & 4)) { modes[nmode++] = EH_MODE_TRAIN_MULTI; modes[nmode++] = EH_MODE_TRAIN_ORD; }
     char name[5][160];
     for (int i = 0; i < nmode; ++i) {
         const int m = modes[i];
@@ -435,6 +453,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
             hiprtcVersion(&ver[0], &ver[1]);
             h = fnv(h, ver, sizeof ver);
             h = fnv(h, src.data(), src.size()); h = fnv(h, mech.data(), mech.size()); h = fnv(h, lsrc.data(), lsrc.size()); h = fnv(h, rsrc.data(), rsrc.size());
+            h = fnv(h, dsrc.data(), dsrc.size());
             h = fnv(h, eh_src_device, sizeof eh_src_device); h = fnv(h, eh_src_wide, sizeof eh_src_wide); h = fnv(h, eh_src_public, sizeof eh_src_public);
             h = fnv(h, eh_src_widebf, sizeof eh_src_widebf); h = fnv(h, eh_src_bfs, sizeof eh_src_bfs);
             for (int m = 0; m < nmode; ++m) h = fnv(h, name[m], strlen(name[m]));
@@ -462,7 +481,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
                 const std::string first = log->substr(0, 240);
                 const int saved = g_jit_level;
                 g_jit_level = next;
-                const bool ok2 = eh_jit_build(d, A, variant, act, fast, spec, with_p2p, loss, out, log, allow_slp);
+                const bool ok2 = eh_jit_build(d, A, variant, act, fast, spec, with_p2p, loss, out, log, allow_slp, drop);
                 g_jit_level = saved;
                 if (ok2 && log->empty()) *log = std::string(next == 1 ? "(compiled with -fno-slp-vectorize" : "(compiled at -O1") + " after the first build failed: " + first + ")";
                 return ok2;

@@ -40,7 +40,13 @@ std::string eh_jit_mech_source(const eh_model_desc& d);
 // allow_slp = false: never the SLP vectoriser (the flags of the kernels built ahead of time: a kernel that REPLACES one of those in the
 // middle of a run -- "specialize" = 2 -- must give the same bits)
 bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int act, int fast, const EhNet* spec, bool with_p2p,
-                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp = true);
+                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp = true, const float* drop = nullptr);
+// (drop: dropout rates per hidden layer, d.n_hidden of them, or nullptr -- compiled in under EH_JIT_DROPOUT with the generated
+//  eh_jit_dropout.inc; such kernels are single-step only)
+// threshold of the keep test (a word below it drops the unit) and the factor on a kept unit for rate p in [0, 1): one definition for the
+// generated header, eh_dropout_mask and the tests' twin
+inline unsigned eh_drop_threshold(float p) { const double t = (double)p * 4294967296.0; return t >= 4294967295.0 ? 4294967295u : (unsigned)t; }
+inline float eh_drop_scale(float p) { return 1.0f / (1.0f - p); }
 hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args);
 void eh_jit_release(EhJitKernel* k);
 // Sequence models around a recorded closure (eh_seq.hpp, EH_SEQ_HEAD_PROG): the (NBI, NBH) instantiation of the three modes compiled

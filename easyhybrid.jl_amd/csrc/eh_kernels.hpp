@@ -866,6 +866,19 @@ __global__ void eh_perm_kernel(int* idx, uint32_t n, int hb, uint64_t seed) {
     if (i < n) idx[i] = (int)eh_perm32(i, n, hb, seed);
 }
 
+// eh_dropout_mask: keep[k][u] of (seed, step, layer) for k < count, u < width -- one thread per (sample, unit quad), through the keep
+// function the step kernels call (eh_drop_keep4) with LOGICAL coordinates: what the tests hold the step kernel's lane mapping against
+__global__ __launch_bounds__(256) void eh_dropout_mask_kernel(unsigned long long seed, unsigned long long step, int layer, int width, long long count, unsigned thr, uint8_t* keep) {
+    const int nq = (width + 3) / 4;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= count * nq) return;
+    const long long k = e / nq;
+    const int q = (int)(e % nq);
+    const unsigned kb = eh_drop_keep4(seed, step, (unsigned)k, layer, (unsigned)q, thr);
+    for (int r = 0; r < 4; ++r)
+        if (4 * q + r < width) keep[k * width + 4 * q + r] = (uint8_t)((kb >> r) & 1u);
+}
+
 // (P x N col-major predictors, F forcing arrays, T target arrays) -> N records of C floats
 struct EhPackArgs {
     const float* x;

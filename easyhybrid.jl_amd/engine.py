@@ -236,6 +236,27 @@ class HybridEngine:
         self._chk(self._lib.eh_loss_and_grad(self._h, split, ip, first, count, C.byref(loss), _fptr(grad), C.byref(nv)))
         return float(loss.value), grad, int(nv.value)
 
+    # -- dropout ---------------------------------------------------------------------------------
+    def set_dropout(self, rates, seed: int = 0, step: int = 0):
+        """Lux Dropout(rates[l]) behind hidden layer l in the training passes (eh_set_dropout); all zeros removes it.  `seed` keys the
+        mask generator, `step` is the count of training steps the next one continues from (get_dropout gives both back)."""
+        r = np.ascontiguousarray(rates, np.float32)
+        self._chk(self._lib.eh_set_dropout(self._h, _fptr(r), r.size, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF))
+
+    def get_dropout(self):
+        """(rates per hidden layer, seed, step): what a checkpoint needs to continue the mask stream"""
+        r = np.zeros(int(self.desc.n_hidden), np.float32)
+        seed, step = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.eh_get_dropout(self._h, _fptr(r), r.size, C.byref(seed), C.byref(step)))
+        return r, int(seed.value), int(step.value)
+
+    def dropout_mask(self, layer: int, step: int, count: int) -> np.ndarray:
+        """the keep mask (count, hidden[layer]) of training step `step` as the step kernel draws it (eh_dropout_mask)"""
+        w = int(self.desc.hidden[layer]) if 0 <= layer < int(self.desc.n_hidden) else 0
+        keep = np.zeros((int(count), w), np.uint8)
+        self._chk(self._lib.eh_dropout_mask(self._h, int(layer), int(step) & 0xFFFFFFFFFFFFFFFF, int(count), C.c_void_p(keep.ctypes.data)))
+        return keep.astype(bool)
+
     # -- optimiser / training --------------------------------------------------------------------
     def opt_init(self, rule: str = "Adam", lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999,
                  eps: float = 1e-8, weight_decay: float = 0.0):

@@ -409,6 +409,49 @@ function chain_status(e::HybridEngine)
     check(e, @ccall LIB[].eh_opt_chain_status(e.h::Ptr{Cvoid}, a::Ref{Int64}, c::Ref{Int64}, n::Ref{Int64})::Int32)
     return (applied = a[], clipped = c[], nonfinite = n[])
 end
+"""
+Dropout behind the hidden layers (`hidden_layers = Chain(Dense(16, 16, tanh), Dropout(0.2), Dense(16, 16, tanh))`): `rates[l]` ∈ [0, 1) is
+the rate behind hidden layer `l` (a `Dropout` belongs to the Dense layer in front of it; as the chain's first element to the layer
+`prepare_hidden_chain` prepends; `Dropout(0)` is Lux's `NoOpLayer`), `seed` keys the engine's Philox4x32-10 mask generator (not Julia's
+RNG stream), `step` is the count of training steps the next one continues from.  Training passes only; `forward` / `evaluate` run in
+test mode.  (These bindings are written against include/easyhybrid_hip.h; no Julia runs where the library is built and tested.)
+"""
+function set_dropout!(e::HybridEngine, rates::Vector{Float32}; seed::Integer = 0, step::Integer = 0)
+    check(e, @ccall LIB[].eh_set_dropout(e.h::Ptr{Cvoid}, rates::Ptr{Float32}, length(rates)::Int32, UInt64(seed)::UInt64, UInt64(step)::UInt64)::Int32)
+end
+"(rates, seed, step): what a checkpoint needs to continue the mask stream"
+function get_dropout(e::HybridEngine, n_hidden::Integer)
+    r = zeros(Float32, n_hidden); seed = Ref{UInt64}(0); step = Ref{UInt64}(0)
+    check(e, @ccall LIB[].eh_get_dropout(e.h::Ptr{Cvoid}, r::Ptr{Float32}, n_hidden::Int32, seed::Ref{UInt64}, step::Ref{UInt64})::Int32)
+    return (rates = r, seed = seed[], step = step[])
+end
+"keep mask (width x count, 1 = kept) of hidden layer `layer` (0-based) at training step `step`, as the step kernel draws it"
+function dropout_mask(e::HybridEngine, layer::Integer, width::Integer, step::Integer, count::Integer)
+    keep = Matrix{UInt8}(undef, width, count)
+    check(e, @ccall LIB[].eh_dropout_mask(e.h::Ptr{Cvoid}, layer::Int32, UInt64(step)::UInt64, count::Int64, keep::Ptr{UInt8})::Int32)
+    return keep
+end
+"""
+Chain of Dense / Dropout layers -> (the Dense layers, rate per hidden layer) as `set_dropout!` takes them; refuses what the device
+kernels do not hold (two Dropout layers in a row, `dims`, p outside [0, 1)).  Works on anything with Lux's field names (`p`, `dims`).
+"""
+function split_dropout(layers)
+    dense = Any[]; rates = Dict{Int, Float32}(); prev = false
+    for l in layers
+        if nameof(typeof(l)) === :Dropout
+            prev && throw(ArgumentError("two Dropout layers in a row have no device kernel"))
+            hasproperty(l, :dims) && !(l.dims isa Colon) && throw(ArgumentError("Dropout(dims = $(l.dims)): only dims = : has a device kernel"))
+            0 <= l.p < 1 || throw(ArgumentError("Dropout(p = $(l.p)): the device kernels take 0 <= p < 1"))
+            l.p > 0 && (rates[length(dense)] = Float32(l.p))
+            prev = true
+        elseif nameof(typeof(l)) === :NoOpLayer
+            prev = false                      # Dropout(0)
+        else
+            push!(dense, l); prev = false
+        end
+    end
+    return dense, Float32[get(rates, k, 0f0) for k in 0:length(dense)]
+end
 "one rule per group of flat-θ elements: group[i] ∈ 0:n-1, rules[k] (0 Adam, 1 AdamW, 2 RMSProp, 3 Descent), hyper[:, k] = (eta, beta1, beta2, epsilon, lambda)"
 function opt_init_groups!(e::HybridEngine, group::Vector{UInt8}, rules::Vector{Int32}, hyper::Matrix{Float32})
     size(hyper) == (5, length(rules)) || throw(ArgumentError("hyper: 5 x $(length(rules))"))

@@ -222,6 +222,49 @@ class Recurrence:
         return f"Recurrence({self.cell!r})"
 
 
+class Dropout:
+    """Lux `Dropout(p)` with `dims = :` as a DESCRIPTION: in training every unit of the hidden layer in front of it is zeroed with
+    probability p and the others are multiplied by 1 / (1 - p); identity in evaluation.  The masks come from the engine's own
+    counter-based generator (Philox4x32-10, keyed by the training seed), not from Julia's RNG stream."""
+
+    def __init__(self, p, dims=None, **kwargs):
+        if dims is not None or kwargs:
+            raise NotImplementedError(f"Dropout(dims = {dims!r}{', ...' if kwargs else ''}): only the default dims = : (one draw per unit and sample) has a device kernel")
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"Dropout(p = {p!r}): the device kernels take 0 <= p < 1")
+        self.p = p
+
+    def __repr__(self):
+        return f"Dropout({self.p})"
+
+
+def _split_dropout(hidden_layers):
+    """Chain with Dropout layers -> (the Chain without them, [p_0 .. p_{L-1}] per hidden layer or None).  A Dropout belongs to the hidden
+    layer in front of it; as the first element that is the layer the reference prepends (Dense(in_dim, first_h, activation)).
+    Dropout(0) is Lux's NoOpLayer and disappears.  Chains around a Recurrence are left to _hidden_widths (and its refusals)."""
+    if not isinstance(hidden_layers, Chain) or not any(isinstance(l, Dropout) for l in hidden_layers.layers):
+        return hidden_layers, None
+    if any(isinstance(l, Recurrence) for l in hidden_layers.layers):
+        return hidden_layers, None
+    rest, rates, prev = [], {}, False
+    for i, l in enumerate(hidden_layers.layers):
+        if isinstance(l, Dropout):
+            if prev:
+                raise NotImplementedError(f"hidden_layers Chain: layers {i} and {i + 1} are both Dropout; two Dropout layers in a row have no device kernel (write one with the combined rate)")
+            prev = True
+            if l.p > 0.0:
+                rates[len(rest)] = l.p
+        else:
+            prev = False
+            rest.append(l)
+    n = len(rest) + 1
+    return Chain(*rest), ([rates.get(l, 0.0) for l in range(n)] if rates else None)
+
+
+DROPOUT_MAX_WIDTH, DROPOUT_MAX_LAYERS = 64, 3      # the per-wave fused kernel family (csrc/eh_device.hpp)
+
+
 LSTM_LAYER = "lstm"      # the "activation" of a hidden layer that is Recurrence(LSTMCell): EH_LAYER_LSTM in the descriptor
 
 
@@ -297,6 +340,7 @@ class SingleNNHybridModel:
     predictor_sets: Optional[Dict[str, List[str]]] = None
     net_activations: Optional[List[str]] = None      # MultiNN with activation::NamedTuple: the activation of net k (None = one for all)
     layer_activations: Optional[List[str]] = None    # single network from `hidden_layers::Chain` whose layers differ: the activation of hidden layer l (None = one for all)
+    dropout: Optional[List[float]] = None            # `hidden_layers::Chain` with Dropout layers: the rate behind hidden layer l (None = none anywhere)
 
     # -- sizes ---------------------------------------------------------------------------------
     @property
@@ -541,8 +585,14 @@ class SingleNNHybridModel:
         prec = self.config.get("precision", "f32")
         if prec not in ("f32", "bf16_fwd", "bf16"):
             raise ValueError(f"precision {prec!r}: 'f32', 'bf16_fwd' or 'bf16'")
-        if prec != "f32":
-            eng.set_option("precision", 1 if prec == "bf16_fwd" else 2)
+        try:
+            if prec != "f32":
+                eng.set_option("precision", 1 if prec == "bf16_fwd" else 2)
+            if self.dropout is not None:                  # (train() sets the seed of its run and the step it continues from)
+                eng.set_dropout(self.dropout, seed=0, step=0)
+        except Exception:
+            eng.close()
+            raise
         return eng
 
 
@@ -570,6 +620,9 @@ def _construct_multi(predictors: Dict[str, Sequence[str]], forcing, targets, mec
     else:
         act = _act_name(activation)
     acts_k = dict(zip(neural, net_acts)) if net_acts is not None else {k: act for k in neural}
+    for hl_k in (hidden_layers.values() if isinstance(hidden_layers, dict) else [hidden_layers]):
+        if isinstance(hl_k, Chain) and any(isinstance(l, Dropout) for l in hl_k.layers) and not any(isinstance(l, Recurrence) for l in hl_k.layers):
+            raise NotImplementedError("hidden_layers Chain: Dropout layers in a MultiNN model have no device kernel (dropout is built for single-network models)")
     hl = ({k: _hidden_widths(hidden_layers[k], acts_k[k]) for k in neural} if isinstance(hidden_layers, dict)
           else {k: _hidden_widths(hidden_layers, acts_k[k]) for k in neural})
     hidden_layers = hl if isinstance(hidden_layers, dict) else next(iter(hl.values()), [])
@@ -647,7 +700,11 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
         if t not in ms.outputs:
             raise ValueError(f"target {t!r} is not an output of {ms.name} {ms.outputs}")
     act = _act_name(activation)
+    hidden_layers, dropout = _split_dropout(hidden_layers)
     hidden_layers, layer_acts = _hidden_widths(hidden_layers, act, per_layer=True)
+    if dropout is not None and (len(hidden_layers) > DROPOUT_MAX_LAYERS or max(hidden_layers) > DROPOUT_MAX_WIDTH):
+        raise NotImplementedError(f"hidden_layers Chain: Dropout on hidden layers {hidden_layers}: the dropout kernels are the per-wave fused family, "
+                                  f"1..{DROPOUT_MAX_LAYERS} hidden layers of at most {DROPOUT_MAX_WIDTH} units")
     dims = [len(predictors)] + hidden_layers + [len(neural_param_names)]
     NN = [] if no_nn else [(dims[i + 1], dims[i]) for i in range(len(dims) - 1)]
     if no_nn:
@@ -659,4 +716,4 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
         config["layer_activations"] = list(layer_acts)
     return SingleNNHybridModel(NN, predictors, forcing, targets, ms, parameters, neural_param_names, global_param_names,
                                fixed, bool(scale_nn_outputs), bool(start_from_default), config,
-                               layer_activations=None if no_nn else layer_acts)
+                               layer_activations=None if no_nn else layer_acts, dropout=None if no_nn else dropout)

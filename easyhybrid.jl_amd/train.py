@@ -745,7 +745,7 @@ class TrainResults:                                                # TrainingCon
     itself): they are computed, exactly as the eager form would have, when first read; `release()` drops them and the device memory."""
 
     def __init__(self, train_history, val_history, epoch_history, train_obs_pred, val_obs_pred, train_diffs, val_diffs, ps, st, best_epoch, best_loss,
-                 timing=None, pending: Optional[_PendingPredictions] = None, chain_status=None):
+                 timing=None, pending: Optional[_PendingPredictions] = None, chain_status=None, dropout_state=None):
         self.train_history, self.val_history, self.epoch_history = train_history, val_history, epoch_history
         self._pred = (train_obs_pred, val_obs_pred, train_diffs, val_diffs)
         self._pending = pending
@@ -753,6 +753,8 @@ class TrainResults:                                                # TrainingCon
         self.timing = timing           # TrainConfig.timing: seconds of the call by part
         # opt = OptimiserChain(...): steps applied, of them with ClipNorm's factor below 1 (their fraction is how one tunes omega), steps with a non-finite norm
         self.chain_applied, self.chain_clipped, self.chain_nonfinite = chain_status if chain_status is not None else (None, None, None)
+        # a model with Dropout layers: the seed of the run's masks and the count of training steps behind it (train_from continues there)
+        self.dropout_seed, self.dropout_step = dropout_state if dropout_state is not None else (None, None)
 
     def _get(self, i):
         if self._pending is not None:
@@ -961,6 +963,9 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
     rng = np.random.default_rng(tc.random_seed)
     dist_run = _want_distributed(tc)
     own = engine is None
+    has_drop = getattr(model, "dropout", None) is not None
+    if has_drop and dist_run:
+        raise NotImplementedError("train(distributed=True): Dropout layers are not built for data parallelism (the masks are drawn per handle)")
     xfn = _extra_fn(tc.extra_loss)                    # extra_loss as a function of the predictions (compute_loss.jl:31-34): recorded, its entries ride on targets of their own
     if xfn is not None and engine is not None and not engine.n_pseudo:
         raise ValueError("train(engine = ...): an extra_loss of the predictions needs an engine created with it (model.engine(device, extra_fn = f))")
@@ -1034,6 +1039,19 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         aggn = _agg_name(tc.agg)
         _apply_extra_loss(eng, model, xterms, aggn, eng.n_pseudo)
         _apply_step_mode(eng, tc, is_seq)
+        drop_seed = None
+        if has_drop:
+            # masks keyed by the run's seed; without one the run continues the seed of the TrainResults it starts from, or draws one (reported
+            # as dropout_seed either way).  A run continued under the SAME seed continues the step count, so no mask of the first run comes
+            # back; under another seed the stream is a new one and starts at step 0.  (The engine runs a dropout handle one launch per step.)
+            prev = tc.train_from if isinstance(tc.train_from, TrainResults) and tc.train_from.dropout_seed is not None else None
+            if tc.random_seed is not None:
+                drop_seed = int(tc.random_seed)
+            elif prev is not None:
+                drop_seed = int(prev.dropout_seed)
+            else:
+                drop_seed = int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
+            eng.set_dropout(model.dropout, seed=drop_seed, step=int(prev.dropout_step) if (prev is not None and int(prev.dropout_seed) == drop_seed) else 0)
         first_lt = tc.loss_types[0]
 
         def snapshot():
@@ -1088,6 +1106,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
             tm["loop_s"] = time.perf_counter() - t_loop
             tm["host_s"] = tm["loop_s"] - tm["steps_s"] - tm["eval_s"]
         t_final = time.perf_counter()
+        drop_step = eng.get_dropout()[2] if has_drop else None
         ps = best_ps if tc.return_model == "best" else eng.get_params()                        # best_or_final
         bn_out = (best_bn if tc.return_model == "best" else eng.get_bn_state()) if has_bn else None
         eng.set_params(ps)
@@ -1110,7 +1129,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
             tm["final_predictions_s"] = time.perf_counter() - t_final       # (eager: forward over both splits with the returned parameters + the copies to the host)
             tm["call_s_before_close"] = time.perf_counter() - t_call
         return TrainResults([s.l_train for s in history], [s.l_val for s in history], history, *preds,
-                            ps, st, best_epoch, best_loss, tm, pending, chain_stat)
+                            ps, st, best_epoch, best_loss, tm, pending, chain_stat, (drop_seed, drop_step) if has_drop else None)
     finally:
         if own and not keep_engine:
             eng.close()

@@ -294,6 +294,27 @@ int32_t eh_opt_init_chain(eh_handle* h, const eh_opt_stage* stages, int32_t n_st
                           int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay);
 /* since eh_opt_init_chain: steps applied, of them steps with a factor below 1, steps with a non-finite norm (drains the stream) */
 int32_t eh_opt_chain_status(eh_handle* h, int64_t* n_applied, int64_t* n_clipped, int64_t* n_nonfinite);
+/* Dropout behind the hidden layers (Lux `Dropout(p)`, dims = :; a `hidden_layers::Chain` with Dropout layers, NNModels.jl:145-219):
+ * in the training passes -- eh_train_step, eh_train_epoch, eh_loss_and_grad -- the output of hidden layer l becomes
+ * h * (keep ? 1 / (1 - rate[l]) : 0), P(keep) = 1 - rate[l]; eh_forward and eh_eval run in test mode (identity).  The masks come from
+ * the engine's own counter-based generator, not from Julia's RNG stream: Philox4x32-10, key = (seed lo, seed hi), counter =
+ * (k, 32 l + (u >> 2), step lo, step hi) for unit u of hidden layer l of the k-th sample of the minibatch; unit u is kept iff word
+ * u & 3 >= min(2^32 - 1, floor(rate[l] * 2^32)), unsigned.  `step` counts the training steps launched on the handle since
+ * eh_set_dropout, applied or not: eh_train_step and every step of eh_train_epoch use the current value and advance it,
+ * eh_loss_and_grad uses it and leaves it -- its gradient is the one the next eh_train_step applies.  A seeded run is bit-reproducible.
+ *   eh_set_dropout   rate[l] in [0, 1) for the n_hidden hidden layers (else EH_EINVAL); all zero removes dropout.  Built for the fp32
+ *                    per-wave fused kernels of single-network models (1..3 hidden layers, widths <= 64), on kernels compiled at run
+ *                    time with the rates in them: row-split, layer-wise, sequence, bf16 and MultiNN handles, and handles set up for
+ *                    data parallelism, get EH_EUNSUPPORTED with the reason.  On a handle with dropout eh_graph_begin, eh_dp_*,
+ *                    eh_p2p_init* and the options precision != 0 / row_split are EH_EUNSUPPORTED; eh_train_epoch runs one launch per
+ *                    step; a failed run-time build makes the step fail (the log is in eh_jit_status): there is no other kernel.
+ *   eh_get_dropout   the state a checkpoint needs (rate: room for `cap` >= n_hidden values, or NULL)
+ *   eh_dropout_mask  keep[k * hidden[layer] + u] (1 = kept) for k < count of step `step` under the handle's seed and rate[layer], from
+ *                    a kernel of its own that calls the step kernels' keep function with logical coordinates
+ * (Added without a new EH_ABI_VERSION: nothing that existed changes.) */
+int32_t eh_set_dropout(eh_handle* h, const float* rate, int32_t n_hidden, uint64_t seed, uint64_t step);
+int32_t eh_get_dropout(eh_handle* h, float* rate, int32_t cap, uint64_t* seed, uint64_t* step);
+int32_t eh_dropout_mask(eh_handle* h, int32_t layer, uint64_t step, int64_t count, uint8_t* keep);
 /* every group's running products: bt[2 * k], bt[2 * k + 1] for group k < n_groups (n_groups == the handle's count; 1 in one-rule mode) */
 int32_t eh_get_opt_beta_t(eh_handle* h, float* bt, int32_t n_groups);
 int32_t eh_set_opt_beta_t(eh_handle* h, const float* bt, int32_t n_groups);
