@@ -53,6 +53,20 @@ class TargetMetrics(C.Structure):
                 ("n", "mse", "rmse", "mae", "r2", "nse", "pearson", "kge", "pbkge", "beta", "alpha", "sse")]
 
 
+class LbfgsOpts(C.Structure):
+    _fields_ = [("m", C.c_int32), ("max_linesearch", C.c_int32), ("c1", C.c_double), ("c2", C.c_double), ("g_tol", C.c_double),
+                ("f_reltol", C.c_double), ("initial_step", C.c_double)]
+
+
+class LbfgsStat(C.Structure):
+    _fields_ = [("iterations", C.c_int64), ("evaluations", C.c_int64), ("f0", C.c_double), ("g_inf", C.c_double), ("last_t", C.c_double),
+                ("pairs", C.c_int32), ("code", C.c_int32)]
+
+
+EH_LBFGS_MAX_M, EH_LBFGS_GRAM_DIM, EH_LBFGS_STATE_DOUBLES, EH_LBFGS_RECORD_DOUBLES = 16, 33, 24, 40
+LBFGS_STATUS = ("running", "converged on g", "converged on f", "maxiters", "line search failed", "empty batch")
+
+
 class OptStage(C.Structure):
     _fields_ = [("kind", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("flags", C.c_int32)]
 
@@ -90,6 +104,14 @@ SIGNATURES = {
     "eh_opt_init_groups": (C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F]),
     "eh_opt_init_chain": (C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "eh_opt_chain_status": (C.c_int32, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "eh_lbfgs_init": (C.c_int32, [_H, C.c_void_p]),
+    "eh_lbfgs_set_batch": (C.c_int32, [_H, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int64]),
+    "eh_lbfgs_set_maxiters": (C.c_int32, [_H, C.c_int64]),
+    "eh_lbfgs_run": (C.c_int32, [_H, C.c_int64]),
+    "eh_lbfgs_status": (C.c_int32, [_H, C.c_void_p]),
+    "eh_lbfgs_trace": (C.c_int32, [_H, _F, C.c_int64, C.POINTER(C.c_int64)]),
+    "eh_lbfgs_host_decide": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "eh_get_opt_beta_t": (C.c_int32, [_H, _F, C.c_int32]),
     "eh_set_opt_beta_t": (C.c_int32, [_H, _F, C.c_int32]),
     "eh_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_int64]),

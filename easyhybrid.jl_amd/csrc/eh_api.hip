@@ -22,6 +22,7 @@
 #include "eh_internal.hpp"
 #include "eh_kernels.hpp"
 #include "eh_chain.hpp"
+#include "eh_lbfgs.hpp"
 #include "eh_wide.hpp"
 #include "eh_lform.hpp"
 #include "eh_seq.hpp"
@@ -499,6 +500,7 @@ static std::mutex g_stage_mu;                 // eh_set_data's pinned staging pa
 static float* g_stage[2] = {nullptr, nullptr};
 static size_t g_stage_bytes = 0;
 static int copy_out(eh_handle* h, float* dst, const float* src_dev, size_t n);
+static void lbfgs_release(eh_handle* h);
 static int copy_in(eh_handle* h, float* dst_dev, const float* src, size_t n);
 static std::mutex g_stream_pool_mu;
 static std::vector<std::pair<int, hipStream_t>> g_stream_pool;
@@ -957,6 +959,7 @@ int32_t eh_destroy(eh_handle* h) {
     (void)hipFree(h->gacc); (void)hipFree(h->ord); if (h->ord_err) (void)hipHostFree(h->ord_err); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
     (void)hipFree(h->prog); (void)hipFree(h->l2val); (void)hipFree(h->l2w); (void)hipFree(h->loss_hist); (void)hipFree(h->perm); (void)hipFree(h->out_buf); (void)hipFree(h->idx_buf);
     eval_host_release(h);
+    lbfgs_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
     (void)hipFree(h->stamps); (void)hipFree(h->image); (void)hipFree(h->imap); (void)hipFree(h->rmap);
     (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs); (void)hipFree(h->split[0].starts); (void)hipFree(h->split[1].starts); (void)hipFree(h->seq_ws); (void)hipFree(h->chain_part);
@@ -1138,6 +1141,11 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
     }
     if (h->drop_on && value && (!strcmp(name, "precision") || !strcmp(name, "row_split")))
         return fail(h, EH_EUNSUPPORTED, "%s: dropout is built for the fp32 per-wave kernels only (eh_set_dropout with all rates zero removes it)", name);
+    if (!strcmp(name, "lbfgs_one_max")) {    // n_theta up to which an L-BFGS evaluation's dots + decision + update run as one launch (-1: the measured default; A/B, tests)
+        if (value < -1 || value > INT32_MAX) return fail(h, EH_EINVAL, "lbfgs_one_max must be -1 or a parameter count");
+        h->lb_one_max = (int)value;
+        return EH_OK;
+    }
     if (!strcmp(name, "max_blocks")) {
         if (value < 1 || value > 256) return fail(h, EH_EINVAL, "max_blocks must be 1..256 (one workgroup per CU)");
         h->max_blocks = (int)value;
@@ -2931,6 +2939,7 @@ int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float bet
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->lb) h->lb->active = false;
     h->opt = EhOpt{rule, lr, beta1, beta2, eps, weight_decay, nullptr};
     h->opt_groups = 1;
     h->chain = EhChain{}; h->chain_gen = 0;
@@ -2972,6 +2981,7 @@ int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, 
     // (the handle's own rule names Adam, so every site moves m and v; its hyper-parameters are group 0's -- the table is what is read)
     h->opt = EhOpt{EH_OPT_ADAM, t->r[0].lr, t->r[0].b1, t->r[0].b2, t->r[0].eps, t->r[0].wd, h->opt_tab};
     h->opt_groups = n_groups;
+    if (h->lb) h->lb->active = false;
     h->chain = EhChain{}; h->chain_gen = 0;
     HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
     HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
@@ -3035,6 +3045,177 @@ int32_t eh_opt_chain_status(eh_handle* h, int64_t* n_applied, int64_t* n_clipped
     if (n_applied) *n_applied = (int64_t)ctr[0];
     if (n_clipped) *n_clipped = (int64_t)ctr[1];
     if (n_nonfinite) *n_nonfinite = (int64_t)ctr[2];
+    return EH_OK;
+}
+
+// ---- L-BFGS on the device (eh_lbfgs.hpp) --------------------------------------------------------------
+static void lbfgs_release(eh_handle* h) {
+    if (!h->lb) return;
+    (void)hipFree(h->lb->vec); (void)hipFree(h->lb->dbl); (void)hipFree(h->lb->trace); (void)hipFree(h->lb->idx);
+    delete h->lb;
+    h->lb = nullptr;
+}
+
+static int lbfgs_ready(eh_handle* h, const char* who) {
+    if (!h->lb || !h->lb->active) return fail(h, EH_ESTATE, "%s: call eh_lbfgs_init first (eh_opt_init* leaves L-BFGS mode)", who);
+    if (h->capturing) return fail(h, EH_EUNSUPPORTED, "%s: graph capture is not built for L-BFGS", who);
+    return EH_OK;
+}
+
+int32_t eh_lbfgs_init(eh_handle* h, const eh_lbfgs_opts* o) {
+    if (!h || !o) return EH_EINVAL;
+    if (o->m < 1 || o->m > EH_LBFGS_MAX_M) return fail(h, EH_EINVAL, "eh_lbfgs_init: m = %d (1..%d)", o->m, (int)EH_LBFGS_MAX_M);
+    if (!(o->c1 > 0.0 && o->c1 < o->c2 && o->c2 < 1.0)) return fail(h, EH_EINVAL, "eh_lbfgs_init: need 0 < c1 < c2 < 1 (c1 = %g, c2 = %g)", o->c1, o->c2);
+    if (o->max_linesearch < 1 || o->max_linesearch > 48) return fail(h, EH_EINVAL, "eh_lbfgs_init: max_linesearch = %d (1..48)", o->max_linesearch);
+    if (!(o->g_tol >= 0.0) || !(o->f_reltol >= 0.0)) return fail(h, EH_EINVAL, "eh_lbfgs_init: g_tol = %g, f_reltol = %g (both >= 0)", o->g_tol, o->f_reltol);
+    if (!(o->initial_step >= 0.0) || !std::isfinite(o->initial_step)) return fail(h, EH_EINVAL, "eh_lbfgs_init: initial_step = %g (>= 0; 0 = min(1, 1 / ||g||))", o->initial_step);
+    if (h->capturing) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: graph capture is not built for L-BFGS");
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: dropout: the line search needs the same objective at every trial point, the masks change with every pass (eh_set_dropout with all rates zero removes it)");
+    if (h->bn_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: input BatchNorm: the reference's Optimization.jl driver never carries the layer state, and that path is not built");
+    if (h->comm || h->lgroup || h->p2p_on || h->p2p_alloc) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: data parallelism (a communicator or a peer-to-peer group on this handle) is not built for L-BFGS");
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t n = (size_t)h->net.n_theta;
+    if (!h->lb) h->lb = new EhLbfgs();
+    EhLbfgs* lb = h->lb;
+    lb->active = false;
+    if (lb->m_cap < o->m) {
+        (void)hipFree(lb->vec); lb->vec = nullptr; lb->m_cap = 0;
+        HIPCHK(h, hipMalloc(&lb->vec, (3 + 2 * (size_t)o->m) * n * sizeof(float)));
+        lb->m_cap = o->m;
+    }
+    if (!lb->dbl) HIPCHK(h, hipMalloc(&lb->dbl, (size_t)(EH_LB_DBL_HEAD + EH_LB_PARTS * EH_LB_NQ_MAX) * sizeof(double)));
+    if (!lb->trace) HIPCHK(h, hipMalloc(&lb->trace, (size_t)EH_LB_TRACE_ROWS * 8 * sizeof(float)));
+    HIPCHK(h, hipMemset(lb->vec, 0, (3 + 2 * (size_t)o->m) * n * sizeof(float)));
+    HIPCHK(h, hipMemset(lb->dbl, 0, (size_t)EH_LB_DBL_HEAD * sizeof(double)));
+    lb->o = *o; lb->nq = EH_LQ_HIST + 6 * o->m; lb->maxiters = 100;
+    lb->batch_set = false; lb->empty = false;
+    lb->active = true;
+    return EH_OK;
+}
+
+static EhLbfgsArgs lbfgs_args(const eh_handle* h) {
+    const EhLbfgs* lb = h->lb;
+    const int n = h->net.n_theta;
+    EhLbfgsArgs a{};
+    a.gradbuf = h->gradbuf; a.theta = TH(h);
+    a.x0 = lb->vec; a.g0 = lb->vec + (size_t)n; a.d = lb->vec + 2 * (size_t)n; a.S = lb->vec + 3 * (size_t)n; a.Y = a.S + (size_t)lb->o.m * n;
+    a.st = lb->dbl; a.rec = lb->dbl + EH_LBFGS_STATE_DOUBLES; a.gram = a.rec + EH_LBFGS_RECORD_DOUBLES; a.part = lb->dbl + EH_LB_DBL_HEAD;
+    a.trace = lb->trace;
+    a.n = n; a.T = h->net.T; a.nq = lb->nq; a.nparts = std::min<int>(EH_LB_PARTS, (n + 1023) / 1024); a.maxiters = lb->maxiters;
+    a.o = lb->o;
+    return a;
+}
+
+int32_t eh_lbfgs_set_maxiters(eh_handle* h, int64_t n) {
+    if (!h) return EH_EINVAL;
+    if (int rc = lbfgs_ready(h, "eh_lbfgs_set_maxiters")) return rc;
+    if (n < 0 || n > INT32_MAX) return fail(h, EH_EINVAL, "eh_lbfgs_set_maxiters: %lld", (long long)n);
+    h->lb->maxiters = (int)n;
+    if (h->lb->batch_set && !h->lb->empty) {      // a solve that stopped at a lower limit goes on (decided on the device: nothing is read back here)
+        HIPCHK(h, hipSetDevice(h->device));
+        FLUSH(h);
+        hipLaunchKernelGGL(eh_lbfgs_resume_kernel, dim3(1), dim3(256), 0, h->stream, lbfgs_args(h), h->img);
+        HIPCHK(h, hipGetLastError());
+    }
+    return EH_OK;
+}
+
+int32_t eh_lbfgs_set_batch(eh_handle* h, int32_t split, const int32_t* idx, int32_t idx_on_device, int64_t first, int64_t count) {
+    if (!h) return EH_EINVAL;
+    if (int rc = lbfgs_ready(h, "eh_lbfgs_set_batch")) return rc;
+    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_lbfgs_set_batch: split %d", split);
+    EhLbfgs* lb = h->lb;
+    EhSplit& sp = h->split[split];
+    if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "eh_lbfgs_set_batch: no data set for this split (call eh_set_data)");
+    if (first < 0 || count < 0) return fail(h, EH_EINVAL, "eh_lbfgs_set_batch: first %lld, count %lld", (long long)first, (long long)count);
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    lb->batch_set = false;
+    if (idx && !idx_on_device) {
+        for (int64_t i = 0; i < count; ++i)
+            if (idx[first + i] < 0 || idx[first + i] >= sp.samples()) return fail(h, EH_EINVAL, "eh_lbfgs_set_batch: idx[%lld] = %d outside 0..%lld", (long long)(first + i), idx[first + i], sp.samples());
+        if (count > lb->idx_cap) {
+            (void)hipFree(lb->idx); lb->idx = nullptr; lb->idx_cap = 0;
+            HIPCHK(h, hipMalloc(&lb->idx, (size_t)count * sizeof(int)));
+            lb->idx_cap = count;
+        }
+        if (count > 0) HIPCHK(h, hipMemcpy(lb->idx, idx + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+        lb->didx = lb->idx; first = 0;
+    } else if (idx) lb->didx = idx;
+    else {
+        if (int rc = check_window(h, sp, first, count, "eh_lbfgs_set_batch")) return rc;
+        lb->didx = nullptr;
+    }
+    lb->split = split; lb->first = first; lb->count = count;
+    HIPCHK(h, hipMemset(lb->dbl, 0, (size_t)EH_LB_DBL_HEAD * sizeof(double)));      // a fresh solve: no history, phase 0
+    lb->empty = count == 0;
+    lb->batch_set = true;
+    return EH_OK;
+}
+
+int32_t eh_lbfgs_run(eh_handle* h, int64_t n_evals) {
+    if (!h) return EH_EINVAL;
+    if (int rc = lbfgs_ready(h, "eh_lbfgs_run")) return rc;
+    EhLbfgs* lb = h->lb;
+    if (!lb->batch_set) return fail(h, EH_ESTATE, "eh_lbfgs_run: call eh_lbfgs_set_batch first");
+    if (n_evals < 0) return fail(h, EH_EINVAL, "eh_lbfgs_run: %lld evaluations", (long long)n_evals);
+    if (h->drop_on || h->bn_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_run: dropout / input BatchNorm were switched on after eh_lbfgs_init: not built for L-BFGS");
+    if (lb->empty) return EH_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    const int n = h->net.n_theta;
+    const EhLbfgsArgs a = lbfgs_args(h);
+    const bool one = n <= (h->lb_one_max >= 0 ? h->lb_one_max : (int)EH_LB_ONE_MAX);
+    const EhSplit& sp = h->split[lb->split];
+    for (int64_t e = 0; e < n_evals; ++e) {
+        if (int rc = do_step(h, sp, lb->didx, lb->first, lb->count, false, false, nullptr)) return rc;
+        if (one) hipLaunchKernelGGL(eh_lbfgs_one_kernel, dim3(1), dim3(256), 0, h->stream, a, h->img);
+        else {
+            hipLaunchKernelGGL(eh_lbfgs_dots_kernel, dim3(a.nparts), dim3(256), 0, h->stream, a);
+            hipLaunchKernelGGL(eh_lbfgs_decide_kernel, dim3(1), dim3(256), 0, h->stream, a);
+            hipLaunchKernelGGL(eh_lbfgs_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, a, h->img);
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    return EH_OK;
+}
+
+int32_t eh_lbfgs_status(eh_handle* h, eh_lbfgs_stat* out) {
+    if (!h || !out) return EH_EINVAL;
+    if (int rc = lbfgs_ready(h, "eh_lbfgs_status")) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double st[EH_LBFGS_STATE_DOUBLES];
+    HIPCHK(h, hipMemcpy(st, h->lb->dbl, sizeof st, hipMemcpyDeviceToHost));
+    out->iterations = (int64_t)st[EH_LS_ITERS]; out->evaluations = (int64_t)st[EH_LS_EVALS];
+    out->f0 = st[EH_LS_F0]; out->g_inf = st[EH_LS_GINF0]; out->last_t = st[EH_LS_LAST_T];
+    out->pairs = (int32_t)st[EH_LS_NPAIRS];
+    out->code = h->lb->empty ? (int32_t)EH_LBFGS_EMPTY_BATCH : (int32_t)st[EH_LS_DONE];
+    return EH_OK;
+}
+
+int32_t eh_lbfgs_trace(eh_handle* h, float* out, int64_t max_rows, int64_t* n_rows) {
+    if (!h || !n_rows || (max_rows > 0 && !out)) return EH_EINVAL;
+    if (int rc = lbfgs_ready(h, "eh_lbfgs_trace")) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double rows = 0.0;
+    HIPCHK(h, hipMemcpy(&rows, h->lb->dbl + EH_LS_ROWS, sizeof rows, hipMemcpyDeviceToHost));
+    *n_rows = (int64_t)rows;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>((int64_t)rows, max_rows), (int64_t)EH_LB_TRACE_ROWS);
+    if (k > 0) HIPCHK(h, hipMemcpy(out, h->lb->trace, (size_t)k * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    return EH_OK;
+}
+
+int32_t eh_lbfgs_host_decide(const eh_lbfgs_opts* o, int32_t maxiters, double* state, double* gram, const double* sums, double f, double n_valid,
+                             double* record, double* trace_row, int32_t* wrote_row) {
+    if (!o || !state || !gram || !sums || !record || !trace_row) return EH_EINVAL;
+    if (o->m < 1 || o->m > EH_LBFGS_MAX_M || o->max_linesearch < 1 || o->max_linesearch > 48) return EH_EINVAL;
+    const int w = eh_lb_decide(*o, maxiters, state, gram, sums, f, n_valid, record, trace_row);
+    if (wrote_row) *wrote_row = w;
     return EH_OK;
 }
 
@@ -3229,6 +3410,7 @@ int32_t eh_graph_begin(eh_handle* h) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: graph capture is not built for sequence models");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: dropout: every step carries its own step count in its arguments, a recorded graph would replay one mask: not built");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: the handle is in L-BFGS mode (capture is not built for it): eh_opt_init* leaves the mode");
     if (h->capturing) return fail(h, EH_ESTATE, "eh_graph_begin: already capturing");
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
@@ -3389,6 +3571,7 @@ int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
 int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: data parallelism is not built for sequence models");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (h->net.T != 1 && !h->tcount_ready) return fail(h, EH_ESTATE, "eh_dp_grad: multi-target model: call eh_dp_counts for this window and all-reduce EH_BUF_TCOUNT first");
     const unsigned tpm_dp = two_pass_mask(h->net);
@@ -3422,6 +3605,7 @@ int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
 int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: data parallelism is not built for sequence models");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
@@ -3449,6 +3633,7 @@ int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
 int32_t eh_dp_moments(eh_handle* h, int64_t first, int64_t count, int32_t stage) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: data parallelism is not built for sequence models");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     const EhNet& net = h->net;
     if (!two_pass_mask(net)) return fail(h, EH_ESTATE, "eh_dp_moments: the training loss needs no batch moments of the predictions");
@@ -3500,6 +3685,7 @@ int32_t eh_set_target_shift(eh_handle* h, int32_t split, const float* shift, int
 int32_t eh_dp_fused_step(eh_handle* h, int64_t first, int64_t count, int32_t* buffer_index) {
     if (!h || !buffer_index) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: data parallelism is not built for sequence models");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->fused) return fail(h, EH_ESTATE, "eh_dp_fused_step: set the fused_update option first");
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: multi-target models need the global per-target counts before the pass: use eh_dp_counts + eh_dp_grad (fused_update off)");
@@ -3527,6 +3713,7 @@ int32_t eh_set_bn_shift(eh_handle* h, const float* shift, int64_t n) {
 int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: data parallelism is not built for sequence models");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->bn_on) return fail(h, EH_ESTATE, "eh_dp_bn_stats: the model has no input BatchNorm");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3546,6 +3733,7 @@ int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
 int32_t eh_dp_apply(eh_handle* h, float* loss_out) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: data parallelism is not built for sequence models");
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_dp_apply: call eh_opt_init first");
     HIPCHK(h, hipSetDevice(h->device));

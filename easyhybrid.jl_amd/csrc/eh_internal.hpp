@@ -108,6 +108,8 @@ struct eh_handle_s {
     float* sc = nullptr;            // [EH_MAX_OPT_GROUPS][2][2] running beta products per optimiser group, ping-pong (group 0 = the one rule)
     EhOptTab* opt_tab = nullptr;    // per-branch optimiser rules (eh_opt_init_groups): allocated once, so a recorded graph's pointer stays valid
     int opt_groups = 1;             // groups of the current rule table; h->opt.tab != nullptr when it came from eh_opt_init_groups
+    struct EhLbfgs* lb = nullptr;   // eh_lbfgs_init: the L-BFGS state (eh_lbfgs.hpp; lb->active: the handle is in L-BFGS mode)
+    int lb_one_max = -1;            // "lbfgs_one_max" option: n_theta up to which one launch takes dots + decision + update (-1: EH_LB_ONE_MAX)
     EhChain chain{};                // eh_opt_init_chain: chain.n != 0 -> every step is step kernel + eh_reduce_kernel<false> + the chain kernels
     int chain_gen = 0;              // 0: no chain; else the number of the eh_opt_init_chain call that installed it (what a recorded graph carries by value)
     double* chain_part = nullptr;   // [EH_CHAIN_PARTS] partial sums of the norm pass, then the three counters of eh_opt_chain_status (allocated by eh_opt_init_chain)

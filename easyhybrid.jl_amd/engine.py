@@ -71,6 +71,14 @@ class _LazySums(dict):
         return key in self._src or dict.__contains__(self, key)
 
 
+def lbfgs_trace_row(r) -> dict:
+    """one row of eh_lbfgs_trace as a dict; the decision string from the mask of the rejected trials"""
+    trials = int(r[2])
+    mask = int(r[5]) | (int(r[6]) << 24)
+    return {"f": float(r[0]), "t": float(r[1]), "trials": trials, "g_inf": float(r[3]), "sy": float(r[4]),
+            "decisions": "".join("A" if (mask >> k) & 1 else "C" for k in range(trials - 1)), "evaluations": int(r[7])}
+
+
 class HybridEngine:
     """Device-resident hybrid model: parameters, optimiser state and datasets live in HBM."""
 
@@ -235,6 +243,79 @@ class HybridEngine:
             count = self.n_samples[split] - first if count is None else count
         self._chk(self._lib.eh_loss_and_grad(self._h, split, ip, first, count, C.byref(loss), _fptr(grad), C.byref(nv)))
         return float(loss.value), grad, int(nv.value)
+
+    # -- L-BFGS on the device (eh_lbfgs_*) -----------------------------------------------------------
+    def lbfgs_init(self, m: int = 10, c1: float = 1e-4, c2: float = 0.9, max_linesearch: int = 20, g_tol: float = 1e-5,
+                   f_reltol: float = 0.0, initial_step: float = 0.0):
+        """puts the handle into L-BFGS mode (opt_init* leaves it): history m, weak-Wolfe bisection line search"""
+        o = L.LbfgsOpts(int(m), int(max_linesearch), float(c1), float(c2), float(g_tol), float(f_reltol), float(initial_step))
+        self._chk(self._lib.eh_lbfgs_init(self._h, C.byref(o)))
+        self._lbfgs_max_ls = int(max_linesearch)
+
+    def lbfgs_set_batch(self, split: int = L.EH_SPLIT_TRAIN, first: int = 0, count: Optional[int] = None, idx=None, maxiters: Optional[int] = None):
+        """fixes the objective -- the window, or samples idx (host int32 array, or a device pointer that stays alive) -- and starts a
+        fresh solve from the current parameters"""
+        ip, on_dev = None, 0
+        if isinstance(idx, numbers.Integral):
+            ip, on_dev = C.cast(C.c_void_p(int(idx)), C.POINTER(C.c_int32)), 1
+            if count is None:
+                raise ValueError("lbfgs_set_batch: a device index pointer needs count")
+        elif idx is not None:
+            idx = np.ascontiguousarray(idx, np.int32)
+            ip = idx.ctypes.data_as(C.POINTER(C.c_int32))
+            count = idx.size - first if count is None else count
+        elif count is None:
+            count = self.n_samples[split] - first
+        self._chk(self._lib.eh_lbfgs_set_batch(self._h, split, ip, on_dev, first, count))
+        if maxiters is not None:
+            self.lbfgs_set_maxiters(maxiters)
+
+    def lbfgs_set_maxiters(self, n: int):
+        self._chk(self._lib.eh_lbfgs_set_maxiters(self._h, int(n)))
+
+    def lbfgs_run(self, n_evals: int):
+        """enqueues n_evals objective evaluations (asynchronous); those behind the end of the solve change nothing"""
+        self._chk(self._lib.eh_lbfgs_run(self._h, int(n_evals)))
+
+    def lbfgs_status(self) -> dict:
+        """synchronises; iterations, evaluations, f0, g_inf, last_t, pairs, code, and the code's name as status"""
+        st = L.LbfgsStat()
+        self._chk(self._lib.eh_lbfgs_status(self._h, C.byref(st)))
+        return {"iterations": int(st.iterations), "evaluations": int(st.evaluations), "f0": float(st.f0), "g_inf": float(st.g_inf),
+                "last_t": float(st.last_t), "pairs": int(st.pairs), "code": int(st.code), "status": L.LBFGS_STATUS[st.code]}
+
+    def lbfgs_trace(self):
+        """synchronises; one dict per accepted iteration: f, t, trials, g_inf, sy, decisions ("A" per trial that failed the
+        sufficient-decrease test, "C" per trial that failed the curvature test), evaluations"""
+        n = C.c_int64()
+        self._chk(self._lib.eh_lbfgs_trace(self._h, None, 0, C.byref(n)))
+        rows = np.zeros((min(int(n.value), 4096), 8), np.float32)
+        if rows.shape[0]:
+            self._chk(self._lib.eh_lbfgs_trace(self._h, _fptr(rows), rows.shape[0], C.byref(n)))
+        return [lbfgs_trace_row(r) for r in rows]
+
+    def lbfgs_solve(self, maxiters: int, chunk_iters: Optional[int] = None, on_chunk=None) -> dict:
+        """runs the solve lbfgs_set_batch started (or goes on with one that stopped at a lower limit) until the device reports an end or
+        `maxiters` iterations are accepted in all: evaluations are enqueued in chunks sized from the iterations still wanted (at most
+        chunk_iters of them per chunk), the status is read once per chunk, and never more than max_linesearch evaluations per iteration
+        still wanted (plus the one at the starting point) are enqueued.  on_chunk(status) may stop the solve by returning True."""
+        self.lbfgs_set_maxiters(maxiters)
+        st = self.lbfgs_status()
+        start = 1 if st["evaluations"] == 0 else 0
+        budget = (int(maxiters) - st["iterations"]) * self._lbfgs_max_ls + start
+        used = 0
+        while st["code"] == 0 and used < budget:
+            want = int(maxiters) - st["iterations"]
+            if chunk_iters is not None:
+                want = min(want, int(chunk_iters))
+            # about one and a quarter trials per iteration; what turns out not to be needed is skipped on the device
+            n = min(budget - used, max(2, want + (want + 3) // 4 + (start if used == 0 else 0)))
+            self.lbfgs_run(n)
+            used += n
+            st = self.lbfgs_status()
+            if on_chunk is not None and on_chunk(st):
+                break
+        return st
 
     # -- dropout ---------------------------------------------------------------------------------
     def set_dropout(self, rates, seed: int = 0, step: int = 0):

@@ -409,6 +409,65 @@ function chain_status(e::HybridEngine)
     check(e, @ccall LIB[].eh_opt_chain_status(e.h::Ptr{Cvoid}, a::Ref{Int64}, c::Ref{Int64}, n::Ref{Int64})::Int32)
     return (applied = a[], clipped = c[], nonfinite = n[])
 end
+"eh_lbfgs_opts of include/easyhybrid_hip.h"
+struct EhLbfgsOpts
+    m::Int32
+    max_linesearch::Int32
+    c1::Float64
+    c2::Float64
+    g_tol::Float64
+    f_reltol::Float64
+    initial_step::Float64
+end
+"eh_lbfgs_stat of include/easyhybrid_hip.h; code: 0 running, 1 converged on g, 2 converged on f, 3 maxiters, 4 line search failed, 5 empty batch"
+struct EhLbfgsStat
+    iterations::Int64
+    evaluations::Int64
+    f0::Float64
+    g_inf::Float64
+    last_t::Float64
+    pairs::Int32
+    code::Int32
+end
+"""
+L-BFGS on the device: what `_train_optimization` (src/training/train_optimization.jl:33-193) hands to Optimization.jl's `LBFGS()`.  History
+`m`, weak-Wolfe bisection line search; `lbfgs_set_batch!` fixes the objective and starts a fresh solve from the current parameters,
+`lbfgs_run!` enqueues evaluations (asynchronous), `lbfgs_status` synchronises.  `opt_init!` returns the engine to the Optimisers path.
+(Written against the header, not run: there is no Julia where the library is built.)
+"""
+function lbfgs_init!(e::HybridEngine; m = 10, c1 = 1e-4, c2 = 0.9, max_linesearch = 20, g_tol = 1e-5, f_reltol = 0.0, initial_step = 0.0)
+    o = Ref(EhLbfgsOpts(m, max_linesearch, c1, c2, g_tol, f_reltol, initial_step))
+    check(e, @ccall LIB[].eh_lbfgs_init(e.h::Ptr{Cvoid}, o::Ref{EhLbfgsOpts})::Int32)
+end
+"samples `idx` (0-based Int32, host) of `split`, or the window `first`, `count`"
+function lbfgs_set_batch!(e::HybridEngine, split::Integer, first::Integer, count::Integer; idx::Union{Nothing, Vector{Int32}} = nothing)
+    if idx === nothing
+        check(e, @ccall LIB[].eh_lbfgs_set_batch(e.h::Ptr{Cvoid}, split::Int32, C_NULL::Ptr{Int32}, 0::Int32, first::Int64, count::Int64)::Int32)
+    else
+        check(e, @ccall LIB[].eh_lbfgs_set_batch(e.h::Ptr{Cvoid}, split::Int32, idx::Ptr{Int32}, 0::Int32, first::Int64, count::Int64)::Int32)
+    end
+end
+lbfgs_set_maxiters!(e::HybridEngine, n::Integer) = check(e, @ccall LIB[].eh_lbfgs_set_maxiters(e.h::Ptr{Cvoid}, n::Int64)::Int32)
+lbfgs_run!(e::HybridEngine, n_evals::Integer) = check(e, @ccall LIB[].eh_lbfgs_run(e.h::Ptr{Cvoid}, n_evals::Int64)::Int32)
+function lbfgs_status(e::HybridEngine)
+    st = Ref(EhLbfgsStat(0, 0, 0.0, 0.0, 0.0, 0, 0))
+    check(e, @ccall LIB[].eh_lbfgs_status(e.h::Ptr{Cvoid}, st::Ref{EhLbfgsStat})::Int32)
+    return st[]
+end
+"rows of (f, t, trials, ||g||inf, s.y, Armijo mask bits 0-23, bits 24-47, evaluations), one per accepted iteration"
+function lbfgs_trace(e::HybridEngine; max_rows = 4096)
+    out = Matrix{Float32}(undef, 8, max_rows); n = Ref{Int64}(0)
+    check(e, @ccall LIB[].eh_lbfgs_trace(e.h::Ptr{Cvoid}, out::Ptr{Float32}, max_rows::Int64, n::Ref{Int64})::Int32)
+    return out[:, 1:min(n[], max_rows)]
+end
+"the device's decision and two-loop recursion on the host, on caller-supplied sums (pure host code; see the header for the layouts)"
+function lbfgs_host_decide!(o::EhLbfgsOpts, maxiters::Integer, state::Vector{Float64}, gram::Vector{Float64}, sums::Vector{Float64}, f::Real, n_valid::Real)
+    rec = zeros(Float64, 40); row = zeros(Float64, 8); wrote = Ref{Int32}(0); ro = Ref(o)
+    rc = @ccall LIB[].eh_lbfgs_host_decide(ro::Ref{EhLbfgsOpts}, maxiters::Int32, state::Ptr{Float64}, gram::Ptr{Float64}, sums::Ptr{Float64}, f::Float64,
+        n_valid::Float64, rec::Ptr{Float64}, row::Ptr{Float64}, wrote::Ref{Int32})::Int32
+    rc == 0 || throw(ArgumentError("eh_lbfgs_host_decide: status $rc"))
+    return rec, (wrote[] == 1 ? row : nothing)
+end
 """
 Dropout behind the hidden layers (`hidden_layers = Chain(Dense(16, 16, tanh), Dropout(0.2), Dense(16, 16, tanh))`): `rates[l]` ∈ [0, 1) is
 the rate behind hidden layer `l` (a `Dropout` belongs to the Dense layer in front of it; as the chain's first element to the layer

@@ -73,6 +73,18 @@ class WeightDecay:                    # dx <- dx + lambda * x (no learning rate 
     lambda_: float = 5e-4
 
 
+@dataclass(frozen=True)
+class LBFGS:
+    """L-BFGS through the reference's Optimization.jl driver (src/training/train_optimization.jl): history m, weak-Wolfe bisection line
+    search (sufficient decrease c1, curvature c2, at most max_linesearch trials per iteration); initial_step 0 = min(1, 1 / ||g||) on
+    the first iteration.  Runs on the device; see TrainConfig.full_batch / eval_every / inner_maxiters."""
+    m: int = 10
+    c1: float = 1e-4
+    c2: float = 0.9
+    max_linesearch: int = 20
+    initial_step: float = 0.0
+
+
 @dataclass(frozen=True, init=False)
 class OptimiserChain:
     """OptimiserChain(o1, ..., on): the gradient passes through the stages in order, each seeing the current parameter, then
@@ -122,6 +134,9 @@ def _chain_args(chain):
                                           "(put it in front of the rule)")
             have_norm = True
             stages.append(("clipnorm", float(o.omega), float(o.p), bool(o.throw)))
+        elif isinstance(o, LBFGS):
+            raise NotImplementedError("OptimiserChain: LBFGS is not an Optimisers.jl rule -- it takes the Optimization.jl driver and its own line search, "
+                                      "and cannot be a stage of a chain (pass opt = LBFGS() on its own)")
         else:
             raise NotImplementedError(f"OptimiserChain stage {o!r}: ClipGrad, ClipNorm, WeightDecay and one Adam/AdamW/RMSProp/Descent rule run on the device")
     if rule is None:
@@ -142,8 +157,11 @@ def _opt_args(opt):
         return dict(rule="RMSProp", lr=opt.eta, beta1=opt.rho, eps=opt.epsilon)
     if isinstance(opt, Descent):
         return dict(rule="Descent", lr=opt.eta)
-    raise NotImplementedError(f"optimiser {opt!r}: only Optimisers.jl-style Adam/AdamW/RMSProp/Descent run on the device "
-                              "(the Optimization.jl path, src/training/train_optimization.jl, is out of scope)")
+    if isinstance(opt, LBFGS):
+        raise NotImplementedError("LBFGS is not an Optimisers.jl rule: train(opt = LBFGS()) takes the Optimization.jl driver on the device; "
+                                  "it cannot be handed to opt_init")
+    raise NotImplementedError(f"optimiser {opt!r}: Optimisers.jl-style Adam/AdamW/RMSProp/Descent and, of the Optimization.jl path "
+                              "(src/training/train_optimization.jl), LBFGS run on the device")
 
 
 _RULES = (Adam, AdamW, RMSProp, Descent)
@@ -170,6 +188,9 @@ def _opt_groups(opt, model):
         if isinstance(r, OptimiserChain):
             raise NotImplementedError(f"per-branch optimiser {k!r}: an OptimiserChain per branch is not built (Optimisers applies it per leaf array "
                                       "there, so ClipNorm's norm would be per layer matrix); one chain for the whole model is")
+        if isinstance(r, LBFGS):
+            raise NotImplementedError(f"per-branch optimiser {k!r}: LBFGS works on the whole parameter vector (one line search, one history): "
+                                      "not built as a per-branch rule")
         if not isinstance(r, _RULES):
             raise NotImplementedError(f"per-branch optimiser {k!r}: {r!r} -- only Adam/AdamW/RMSProp/Descent rules run on the device "
                                       "(pre-built Optimisers.setup state trees are not supported)")
@@ -377,6 +398,18 @@ class TrainConfig:
     # not in the reference: True = TrainResults.timing splits the wall-clock of the epoch loop into training steps / evaluation passes /
     # host bookkeeping (one extra device synchronisation per epoch, after the steps, so that the split is clean: bench.py `train_e2e`)
     timing: bool = False
+    # the Optimization.jl driver only (opt = LBFGS(); TrainingConfig.jl:127-159):
+    #   full_batch      True: one solve over the whole training split (solve keywords maxiters, g_tol, f_reltol), a train / validation
+    #                   snapshot every `eval_every` accepted iterations; False: `nepochs` passes over the shuffled minibatches, a fresh solve
+    #                   of `inner_maxiters` iterations on each, warm-started from the current parameters, one snapshot per pass
+    #   promote_f64     accepted with a warning: the parameters stay fp32 on the device, the recurrences are in double already
+    full_batch: bool = False
+    promote_f64: bool = False
+    eval_every: int = 1
+    inner_maxiters: int = 4
+
+
+_SOLVE_KEYWORDS = ("maxiters", "epochs", "g_tol", "f_reltol")          # what train() hands on to the solve (the reference: solve(...; kwargs...))
 
 
 @dataclass
@@ -745,7 +778,7 @@ class TrainResults:                                                # TrainingCon
     itself): they are computed, exactly as the eager form would have, when first read; `release()` drops them and the device memory."""
 
     def __init__(self, train_history, val_history, epoch_history, train_obs_pred, val_obs_pred, train_diffs, val_diffs, ps, st, best_epoch, best_loss,
-                 timing=None, pending: Optional[_PendingPredictions] = None, chain_status=None, dropout_state=None):
+                 timing=None, pending: Optional[_PendingPredictions] = None, chain_status=None, dropout_state=None, lbfgs=None):
         self.train_history, self.val_history, self.epoch_history = train_history, val_history, epoch_history
         self._pred = (train_obs_pred, val_obs_pred, train_diffs, val_diffs)
         self._pending = pending
@@ -755,6 +788,9 @@ class TrainResults:                                                # TrainingCon
         self.chain_applied, self.chain_clipped, self.chain_nonfinite = chain_status if chain_status is not None else (None, None, None)
         # a model with Dropout layers: the seed of the run's masks and the count of training steps behind it (train_from continues there)
         self.dropout_seed, self.dropout_step = dropout_state if dropout_state is not None else (None, None)
+        # opt = LBFGS(): the status of the (last) solve -- iterations, evaluations, f0, g_inf, last_t, pairs, status -- and its trace, one
+        # dict per accepted iteration (f, t, trials, g_inf, sy, decisions, evaluations)
+        self.lbfgs_status, self.lbfgs_trace = lbfgs if lbfgs is not None else (None, None)
 
     def _get(self, i):
         if self._pending is not None:
@@ -804,6 +840,49 @@ def _chain_check(eng, epoch):
         raise FloatingPointError(f"gradient has {cn[0][2]:g}-norm that is not finite in {stat[2]} step(s) up to epoch {epoch} "
                                  "(ClipNorm(throw = true)): those steps were not applied")
     return stat
+
+
+def _lbfgs_misplaced(opt):
+    """LBFGS anywhere but as `opt` itself: the reason, before anything is uploaded"""
+    if isinstance(opt, OptimiserChain):
+        _chain_has_lbfgs = lambda c: any(isinstance(o, LBFGS) or (isinstance(o, OptimiserChain) and _chain_has_lbfgs(o)) for o in c.opts)
+        if _chain_has_lbfgs(opt):
+            _chain_args(OptimiserChain(LBFGS()))
+    if isinstance(opt, tuple) and hasattr(opt, "_asdict"):
+        opt = opt._asdict()
+    if isinstance(opt, dict):
+        for k, r in opt.items():
+            if isinstance(r, LBFGS):
+                raise NotImplementedError(f"per-branch optimiser {k!r}: LBFGS works on the whole parameter vector (one line search, one history): "
+                                          "not built as a per-branch rule")
+
+
+def _lbfgs_check(model, tc: TrainConfig, solve_kw):
+    """opt = LBFGS(): what the Optimization.jl driver on the device does not run, with the reason; the solve keywords it drops"""
+    o = tc.opt
+    if not (1 <= int(o.m) <= L.EH_LBFGS_MAX_M):
+        raise ValueError(f"LBFGS(m = {o.m}): the history holds 1..{L.EH_LBFGS_MAX_M} pairs")
+    if not (0 < o.c1 < o.c2 < 1):
+        raise ValueError(f"LBFGS(c1 = {o.c1}, c2 = {o.c2}): need 0 < c1 < c2 < 1")
+    if not (1 <= int(o.max_linesearch) <= 48):
+        raise ValueError(f"LBFGS(max_linesearch = {o.max_linesearch}): 1..48")
+    if not o.initial_step >= 0:
+        raise ValueError(f"LBFGS(initial_step = {o.initial_step}): must not be negative")
+    if tc.eval_every < 1 or tc.inner_maxiters < 1:
+        raise ValueError("eval_every and inner_maxiters must be >= 1")
+    if getattr(model, "dropout", None) is not None:
+        raise NotImplementedError("train(opt = LBFGS()): Dropout layers -- the line search needs the same objective at every trial point, the masks "
+                                  "change with every pass: not built")
+    if bool(model.config.get("input_batchnorm")):
+        raise NotImplementedError("train(opt = LBFGS()): input BatchNorm -- the reference's Optimization.jl driver never carries the layer state: not built")
+    if tc.distributed is True:
+        raise NotImplementedError("train(opt = LBFGS(), distributed=True): data parallelism is not built for the Optimization.jl driver")
+    if tc.promote_f64:
+        warnings.warn("promote_f64: the parameters stay float32 on the device; every scalar of the L-BFGS recurrences (dot products, step lengths, "
+                      "the two-loop coefficients) is kept in double already, and the field works around a Lux issue this path does not have")
+    if not tc.full_batch:                 # train_optimization.jl drops them for the minibatch solves: inner_maxiters and nepochs rule there
+        solve_kw.pop("maxiters", None)
+        solve_kw.pop("epochs", None)
 
 
 def _want_distributed(tc: TrainConfig) -> bool:
@@ -950,20 +1029,30 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
     Flat kwargs override config fields exactly like override_configs (train.jl:300-314)."""
     tc = copy.copy(train_cfg) if train_cfg else TrainConfig()
     dc = copy.copy(data_cfg) if data_cfg else DataConfig()
+    solve_kw = {}
     for k, v in kwargs.items():
         if hasattr(tc, k):
             setattr(tc, k, v)
         elif hasattr(dc, k):
             setattr(dc, k, v)
+        elif k in _SOLVE_KEYWORDS and isinstance(kwargs.get("opt", tc.opt), LBFGS):
+            solve_kw[k] = v
         else:
             raise TypeError(f"train: unknown keyword {k!r}")
     validate_config(tc)
+    lbfgs = tc.opt if isinstance(tc.opt, LBFGS) else None
+    if lbfgs is not None:
+        _lbfgs_check(model, tc, solve_kw)
+    else:
+        _lbfgs_misplaced(tc.opt)
     _freeze_gc_once()
     t_call = time.perf_counter()
     rng = np.random.default_rng(tc.random_seed)
     dist_run = _want_distributed(tc)
     own = engine is None
     has_drop = getattr(model, "dropout", None) is not None
+    if lbfgs is not None and dist_run:
+        raise NotImplementedError("train(opt = LBFGS(), distributed=True): data parallelism is not built for the Optimization.jl driver")
     if has_drop and dist_run:
         raise NotImplementedError("train(distributed=True): Dropout layers are not built for data parallelism (the masks are drawn per handle)")
     xfn = _extra_fn(tc.extra_loss)                    # extra_loss as a function of the predictions (compute_loss.jl:31-34): recorded, its entries ride on targets of their own
@@ -1033,12 +1122,16 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         else:
             theta = np.asarray(tc.train_from.ps if isinstance(tc.train_from, TrainResults) else tc.train_from[0], np.float32)
         eng.set_params(theta)
-        _opt_setup(eng, tc.opt, model)
+        if lbfgs is None:
+            _opt_setup(eng, tc.opt, model)
         eng.set_training_loss(tc.training_loss)
         xterms = _extra_terms(tc.extra_loss)
         aggn = _agg_name(tc.agg)
         _apply_extra_loss(eng, model, xterms, aggn, eng.n_pseudo)
-        _apply_step_mode(eng, tc, is_seq)
+        _apply_step_mode(eng, replace(tc, fused_update=False) if lbfgs is not None else tc, is_seq)
+        if lbfgs is not None:      # (after the losses and options: the mode refuses what changes the objective between trial points)
+            eng.lbfgs_init(m=lbfgs.m, c1=lbfgs.c1, c2=lbfgs.c2, max_linesearch=lbfgs.max_linesearch, initial_step=lbfgs.initial_step,
+                           g_tol=float(solve_kw.get("g_tol", 1e-5)), f_reltol=float(solve_kw.get("f_reltol", 0.0)))
         drop_seed = None
         if has_drop:
             # masks keyed by the run's seed; without one the run continues the seed of the TrainResults it starts from, or draws one (reported
@@ -1077,7 +1170,47 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
             tm.update(prepare_s=t_prep - t_call, engine_s=t_eng - t_prep, upload_s=t_up - t_eng, setup_s=t_setup - t_up, initial_eval_s=time.perf_counter() - t_setup)
         chain_stat = _chain_check(eng, 0)
         t_loop = time.perf_counter()
-        for epoch in range(1, tc.nepochs + 1):
+        lb_out = [None, None]
+
+        def lbfgs_snapshot(index):
+            """a snapshot at history index `index` (iteration or pass); True when the patience has run out"""
+            nonlocal best_loss, best_ps, best_epoch, counter
+            snap = snapshot()
+            if tc.keep_history:
+                history.append(snap)
+            cur = snap.l_val[first_lt][aggn]
+            if isbetter(cur, best_loss, first_lt):
+                best_loss, best_ps, best_epoch, counter = cur, eng.get_params(), index, 0
+                if not tc.keep_history:
+                    history[0] = snap
+            else:
+                counter += 1
+            return counter >= tc.patience
+        if lbfgs is not None and tc.full_batch:                  # one solve over the training split, paused every eval_every iterations (_optim_callback)
+            maxiters = int(solve_kw.get("maxiters", 1000))
+            eng.lbfgs_set_batch(L.EH_SPLIT_TRAIN)
+            at, st = 0, eng.lbfgs_status()
+            while at < maxiters and st["code"] in (0, 3):
+                st = eng.lbfgs_solve(min(maxiters, at + tc.eval_every))
+                if st["iterations"] == at:                       # (converged, failed or empty at the iterate the last snapshot saw)
+                    break
+                at = st["iterations"]
+                if lbfgs_snapshot(at):
+                    break
+            lb_out = [st, eng.lbfgs_trace()]
+        elif lbfgs is not None:                                  # _run_minibatch!: a fresh solve on every minibatch, warm-started
+            ntr = eng.n_samples[L.EH_SPLIT_TRAIN]
+            for epoch in range(1, tc.nepochs + 1):
+                perm = rng.permutation(ntr).astype(np.int32)
+                for lo in range(0, ntr, tc.batchsize):
+                    eng.lbfgs_set_batch(L.EH_SPLIT_TRAIN, idx=perm[lo:lo + tc.batchsize])
+                    st = eng.lbfgs_solve(tc.inner_maxiters)      # (an empty minibatch: "empty batch" after its first evaluation, theta untouched)
+                    lb_out = [st, None]
+                if lbfgs_snapshot(epoch):
+                    break
+            if lb_out[0] is not None:
+                lb_out[1] = eng.lbfgs_trace()
+        for epoch in range(1, (tc.nepochs if lbfgs is None else 0) + 1):
             t0 = time.perf_counter()
             eng.train_epoch(tc.batchsize, seed=seed0 + epoch, shuffle=True, want_loss=False)      # run_epoch!
             if tm is not None:
@@ -1129,7 +1262,8 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
             tm["final_predictions_s"] = time.perf_counter() - t_final       # (eager: forward over both splits with the returned parameters + the copies to the host)
             tm["call_s_before_close"] = time.perf_counter() - t_call
         return TrainResults([s.l_train for s in history], [s.l_val for s in history], history, *preds,
-                            ps, st, best_epoch, best_loss, tm, pending, chain_stat, (drop_seed, drop_step) if has_drop else None)
+                            ps, st, best_epoch, best_loss, tm, pending, chain_stat, (drop_seed, drop_step) if has_drop else None,
+                            lbfgs=lb_out if lbfgs is not None else None)
     finally:
         if own and not keep_engine:
             eng.close()

@@ -253,11 +253,54 @@ int32_t eh_mech_loss_vjp(eh_handle* h, int64_t count, int64_t ld, const float* o
                          float* loss, float* grad_global, int64_t* n_valid);
 
 /* compute_loss(train_mode) value and its gradient wrt flat theta on one minibatch, no update
- * (the objective Zygote differentiates, src/training/epoch.jl:40-51; also the seam
- * train_optimization.jl:121-133 would use).  idx: optional count sample indices (host, int32) into the
+ * (the objective Zygote differentiates, src/training/epoch.jl:40-51; the objective of
+ * train_optimization.jl:121-133 too -- eh_lbfgs_* below runs that driver's L-BFGS around the same
+ * passes without leaving the device).  idx: optional count sample indices (host, int32) into the
  * split, NULL = the contiguous window.  An all-masked batch gives loss = NaN, grad = 0, n_valid = 0. */
 int32_t eh_loss_and_grad(eh_handle* h, int32_t split, const int32_t* idx, int64_t first, int64_t count,
                          float* loss, float* grad, int64_t* n_valid);
+
+/* L-BFGS on the device (the reference's Optimization.jl driver, src/training/train_optimization.jl:33-193): history m, weak-Wolfe
+ * bisection line search (Lewis & Overton), every scalar in double, theta / gradients / history in fp32.  One objective evaluation is
+ * the passes of eh_loss_and_grad at the trial point plus the dot products, the decision and the element-wise update, enqueued
+ * without a synchronisation; all sums run in a fixed order, so a solve is bit-reproducible.
+ *   eh_lbfgs_init        allocates the state (never inside a graph capture) and puts the handle into L-BFGS mode.  1 <= m <=
+ *                        EH_LBFGS_MAX_M, 0 < c1 < c2 < 1, 1 <= max_linesearch <= 48, g_tol >= 0, f_reltol >= 0, initial_step >= 0
+ *                        (0: min(1, 1 / ||g||_2) on the first iteration), else EH_EINVAL.  EH_EUNSUPPORTED with the reason: Dropout (the
+ *                        objective must be one function), input BatchNorm, a handle in a communicator / peer-to-peer group.  While the
+ *                        mode is on, eh_dp_* and eh_graph_begin are EH_EUNSUPPORTED; eh_opt_init* return the handle to the other paths.
+ *   eh_lbfgs_set_batch   fixes the objective -- samples idx[first .. first + count) of the split (idx NULL: the window; host indices
+ *                        are copied) -- and starts a fresh solve from the current theta: empty history.
+ *   eh_lbfgs_set_maxiters  accepted iterations after which the device ends the solve (default 100).  Raised on a solve that ended on
+ *                        this limit, the solve goes on where it stopped, history and all (asynchronous, decided on the device).
+ *   eh_lbfgs_run         enqueues exactly n_evals evaluations; asynchronous.  Evaluations behind the end of a solve change nothing.
+ *   eh_lbfgs_status      drains the stream; one small copy
+ *   eh_lbfgs_trace       drains the stream; one row of 8 floats per accepted iteration (at most 4096 are kept): f, t, trials of its line
+ *                        search, ||g||inf, s.y, the trials that failed the sufficient-decrease test as a bit mask (bits 0-23, bits 24-47;
+ *                        every other rejected trial failed the curvature test), evaluations so far.  n_rows: rows the solve has written
+ *   eh_lbfgs_host_decide pure host code, needs no device: the very decision and two-loop recursion the device runs, on caller-supplied
+ *                        numbers.  state [EH_LBFGS_STATE_DOUBLES] (all zero = a fresh solve) and gram [EH_LBFGS_GRAM_DIM]^2 (the Gram
+ *                        matrix of the basis S_0 .. S_{m-1}, Y_0 .. Y_{m-1}, g, row stride EH_LBFGS_GRAM_DIM) are updated in place;
+ *                        sums [8 + 6 m]: g.d, s.y, y.y, ||g||inf, g.g, s.s, s.g, y.g, then for basis vector j < 2 m: g.B_j, s.B_j, y.B_j;
+ *                        record [EH_LBFGS_RECORD_DOUBLES]: action (0 nothing, 1 rejected, 2 accepted, 3 accepted and done, 4 restart
+ *                        from -g0, 5 failed: back to x0, 6 accepted and stopped at maxiters), the next t, the ring slot the pair went to or -1, pairs held, the 2 m + 1
+ *                        coefficients of the new direction; trace_row [8] as above, *wrote_row = 1 if it was written. */
+#define EH_LBFGS_MAX_M 16
+#define EH_LBFGS_GRAM_DIM (2 * EH_LBFGS_MAX_M + 1)
+#define EH_LBFGS_STATE_DOUBLES 24
+#define EH_LBFGS_RECORD_DOUBLES 40
+#define EH_LBFGS_SUMS_DOUBLES (8 + 6 * EH_LBFGS_MAX_M)
+enum { EH_LBFGS_RUNNING = 0, EH_LBFGS_CONVERGED_G = 1, EH_LBFGS_CONVERGED_F = 2, EH_LBFGS_MAXITERS = 3, EH_LBFGS_LINESEARCH_FAILED = 4, EH_LBFGS_EMPTY_BATCH = 5 };
+typedef struct eh_lbfgs_opts { int32_t m; int32_t max_linesearch; double c1, c2, g_tol, f_reltol, initial_step; } eh_lbfgs_opts;
+typedef struct eh_lbfgs_stat { int64_t iterations, evaluations; double f0, g_inf, last_t; int32_t pairs, code; } eh_lbfgs_stat;
+int32_t eh_lbfgs_init(eh_handle* h, const eh_lbfgs_opts* opts);
+int32_t eh_lbfgs_set_batch(eh_handle* h, int32_t split, const int32_t* idx, int32_t idx_on_device, int64_t first, int64_t count);
+int32_t eh_lbfgs_set_maxiters(eh_handle* h, int64_t n);
+int32_t eh_lbfgs_run(eh_handle* h, int64_t n_evals);
+int32_t eh_lbfgs_status(eh_handle* h, eh_lbfgs_stat* out);
+int32_t eh_lbfgs_trace(eh_handle* h, float* out, int64_t max_rows, int64_t* n_rows);
+int32_t eh_lbfgs_host_decide(const eh_lbfgs_opts* opts, int32_t maxiters, double* state, double* gram, const double* sums, double f,
+                             double n_valid, double* record, double* trace_row, int32_t* wrote_row);
 
 /* running statistics of the input BatchNorm layer (the model state `st.st_nn`; Lux starts them at mean 0, var 1).
  * Training steps use the statistics of their own minibatch and update these with momentum 0.1; forward / eval use them. */
