@@ -89,9 +89,10 @@ def fluxpart_model(target, I, H, act="tanh"):
 
 
 # ---- the twin ------------------------------------------------------------------------------------------------------------------------
-def forward(model, mech, out, theta, X, forcings, starts, W, ow, dtype=torch.float64, requires_grad=False):
+def forward(model, mech, out, theta, X, forcings, starts, W, ow, dtype=torch.float64, requires_grad=False, tanh=torch.tanh):
     """tests/seq_twin.py `forward` with the mechanistic stage `mech(**forcings, **parameters) -> dict`, of which output `out` is the
-    prediction -> (yhat (n, ow), {parameter: (n, ow)}, theta tensor)"""
+    prediction -> (yhat (n, ow), {parameter: (n, ow)}, theta tensor).  `tanh`: the spelling of the cell's two tanh (tests/seq_fuzz_cases.py
+    runs the fp32 twin with a second one)"""
     th = torch.tensor(np.asarray(theta), dtype=dtype, requires_grad=requires_grad)
     p = tw.unpack(model, th)
     act = tw.ACT[model.config["activation"]]
@@ -105,8 +106,8 @@ def forward(model, mech, out, theta, X, forcings, starts, W, ow, dtype=torch.flo
         x = act(Xt[:, starts + t].T @ p["w_in"].T + p["b_in"])
         z = x @ p["w_ih"].T + h @ p["w_hh"].T + p["b_ih"] + p["b_hh"]
         i, f, g, o = (z[:, k * H:(k + 1) * H] for k in range(4))
-        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-        h = torch.sigmoid(o) * torch.tanh(c)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * tanh(g)
+        h = torch.sigmoid(o) * tanh(c)
         if t >= W - ow:
             outs.append(act(h @ p["w_hd"].T + p["b_hd"]) @ p["w_out"].T + p["b_out"])
     O = torch.stack(outs, 1)                                             # (n, ow, K)
@@ -126,14 +127,16 @@ def forward(model, mech, out, theta, X, forcings, starts, W, ow, dtype=torch.flo
     return list(res.values())[out], par, th
 
 
-def loss_and_grad(model, mech, out, theta, X, forcings, y, starts, W, ow, lam, kind="mse", dtype=torch.float64):
+def loss_and_grad(model, mech, out, theta, X, forcings, y, starts, W, ow, lam, kind="mse", dtype=torch.float64, tanh=torch.tanh):
     """-> (loss, gradient (n_theta,), n_valid)"""
-    yhat, _, th = forward(model, mech, out, theta, X, forcings, starts, W, ow, dtype, requires_grad=True)
+    yhat, _, th = forward(model, mech, out, theta, X, forcings, starts, W, ow, dtype, requires_grad=True, tanh=tanh)
     yt = torch.tensor(tw.targets_of(y, starts, W, ow, lam), dtype=dtype)
     nv = int((~torch.isnan(yt)).sum())
     if nv == 0:
         return float("nan"), np.zeros(th.numel()), 0
     loss = tw.loss_of(yhat, yt, kind)
+    if not loss.requires_grad:                                           # (a target that no trained parameter reaches)
+        return float(loss), np.zeros(th.numel()), nv
     loss.backward()
     return float(loss.detach()), th.grad.numpy().astype(np.float64), nv
 
@@ -189,13 +192,13 @@ def all_starts(rows, W, lam, s=1):
 
 
 # ---- the parity cases ---------------------------------------------------------------------------------------------------------------
-SHAPES = [(6, 2, 5, 2, 1), (32, 32, 3, 3, 0), (20, 9, 7, 3, 0), (15, 15, 10, 1, 0)]      # (I, H, W, ow, lam)
-SHAPE_IDS = ["I6H2", "I32H32", "I20H9", "tutorial"]
+SHAPES = [(6, 2, 5, 2, 1), (32, 32, 3, 3, 0), (20, 9, 7, 3, 0), (15, 15, 10, 1, 0), (9, 24, 6, 2, 1)]      # (I, H, W, ow, lam)
+SHAPE_IDS = ["I6H2", "I32H32", "I20H9", "tutorial", "I9H24"]          # (appended to only: `variant` pairs by position)
 COUNTS = [5, 17, 70, 300]
 
 
 def variant(si, ci):
-    """-> (closure, activation, sigma-scaling, loss, shuffled idx) of a case: every value of the issue's list occurs over the 16 cases"""
+    """-> (closure, activation, sigma-scaling, loss, shuffled idx) of a case: every value of the issue's list occurs over the first 16 cases"""
     k = si * len(COUNTS) + ci
     cid = (1, 2, 3)[k % 3]
     scale = not (cid == 1 and (k // 3) % 2 == 0)          # raw NN outputs on closure 1 only (the flux closure divides and takes logs of its parameters)
