@@ -432,20 +432,69 @@ static const EhSpecKernel* spec_lookup(const eh_handle* h) {
     return nullptr;
 }
 
+// May the handle's single-step train launches (EH_MODE_TRAIN, EH_MODE_TRAIN_ORD) run the lean form of their kernel?  Decided here, from
+// the handle's configuration, wherever that changes (creation, optimiser set-up, options, dropout, recorded losses, diagnostics) --
+// not per step: one target trained on a one-pass loss, no input BatchNorm, no dropout, no recorded program or loss, one activation,
+// ONE optimiser rule and that rule Adam, no diagnostics buffer.  "lean" = 0 / EH_NO_LEAN=1: never (the A/B).
+// (EH_LEAN_DIAG=1, the measurement tools: a RUN-TIME COMPILED kernel built with EH_STAMPS through EH_JIT_DEFINES keeps the diagnostics
+//  pointer in its lean form too -- tools/stamps_*.py then stamp both forms with one library.  The kernels built ahead of time never
+//  take an armed diagnostics buffer in their lean form: lean_wanted is strict for them.)
+static bool lean_diag_env() { static const bool on = getenv("EH_LEAN_DIAG") != nullptr; return on; }
+static void lean_refresh(eh_handle* h) {
+    static const bool env_off = getenv("EH_NO_LEAN") != nullptr;
+#ifdef EH_STAMPS
+    const bool diag = false;                     // (diagnostic builds: the lean kernel keeps the stamps, tools/stamps_*.py measure both forms)
+#else
+    const bool diag = h->stamps != nullptr && !lean_diag_env();
+#endif
+    h->lean_cfg = h->lean && !env_off && h->arch && !h->arch->wide && !h->lform && !h->seq && h->net.T == 1 && !h->bn_on && !h->drop_on &&
+                  h->net.mech != EH_MECH_PROGRAM && h->net.loss != EH_LOSS_PROGRAM && h->act != EH_ACT_PER_NET && eh_two_pass_mask(h) == 0u &&
+                  h->opt.tab == nullptr && h->opt.rule == EH_OPT_ADAM && !diag;
+}
+// ... and do this launch's arguments keep the contract (a cheap cross-check of what lean_refresh concluded: anything else runs the general kernel)
+// (jit: the launch goes to a run-time compiled kernel -- the only place EH_LEAN_DIAG lets an armed diagnostics buffer through)
+static bool lean_wanted(const eh_handle* h, const EhStepArgs* a, bool jit = false) {
+    if (!h->lean_cfg) return false;
+    if (eh_lean_args_ok(*a)) return true;
+    if (!jit || !lean_diag_env() || !a->stamps) return false;
+    EhStepArgs b = *a;
+    b.stamps = nullptr;
+    return eh_lean_args_ok(b);
+}
+// which form the single-step train launch ran (eh_jit_status reports the last one; EH_JIT_TRACE=1 prints every change)
+static void lean_note(eh_handle* h, bool lean) {
+    const int v = lean ? 1 : 0;
+    if (h->lean_last != v && getenv("EH_JIT_TRACE")) fprintf(stderr, "eh_jit: train step kernel: %s\n", lean ? "lean" : "general");
+    h->lean_last = v;
+}
+
 static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs* a) {
     if (mode == EH_MODE_TRAIN_ORD) {
         // the ordered step gives the bits of the step + reduce pair only on the kernel the pair's step runs: the kernel family EH_MODE_TRAIN
         // picks below, or nothing (hipErrorNotSupported, nothing launched: the caller runs the pair).  A run-time compiled kernel is
         // taken once the pair's first step has checked it (jit_verify).
         if (const EhSpecKernel* sk = spec_lookup(h)) {
-            const hipError_t e = sk->launch(mode, grid, h->stream, &h->net, a);
-            if (e == hipSuccess) h->spec_used = sk; else (void)hipGetLastError();
+            bool ln = sk->launch_lean && lean_wanted(h, a);
+            hipError_t e = ln ? sk->launch_lean(mode, grid, h->stream, &h->net, a) : sk->launch(mode, grid, h->stream, &h->net, a);
+            if (ln && e != hipSuccess) {         // (the lean entry refused the arguments: nothing was launched, the general kernel takes the step)
+                (void)hipGetLastError();
+                ln = false;
+                e = sk->launch(mode, grid, h->stream, &h->net, a);
+            }
+            if (e == hipSuccess) { h->spec_used = sk; lean_note(h, ln); } else (void)hipGetLastError();
             return e;
         }
         if (jit_wanted(h, EH_MODE_TRAIN)) {
             eh_handle_s::JitEntry* je = jit_entry(h);
-            if (je) return (je->verified && je->k.fn[EH_MODE_TRAIN_ORD]) ? eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a) : hipErrorNotSupported;
+            if (je) {
+                if (!je->verified || !je->k.fn[EH_MODE_TRAIN_ORD]) return hipErrorNotSupported;
+                const bool ln = je->k.fn_lean[1] && lean_wanted(h, a, true);
+                const hipError_t e = eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a, ln);
+                if (e == hipSuccess) lean_note(h, ln);
+                return e;
+            }
         }
+        lean_note(h, false);
         return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
     }
     if (mode == EH_MODE_TRAIN_MULTI) {     // (built ahead of time only -- specialised for the canonical descriptors, generic otherwise; the caller checked: multi_ok)
@@ -461,9 +510,18 @@ static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs
         }
         return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
     }
+    // the lean form of the single-step train kernel (eh_lean_fold, eh_device.hpp): kernels with the descriptor baked in, a handle whose
+    // configuration is inside the contract (lean_refresh), arguments that say the same
+    const bool train = mode == EH_MODE_TRAIN;
     if (const EhSpecKernel* sk = spec_lookup(h)) {
-        const hipError_t e = sk->launch(mode, grid, h->stream, &h->net, a);
-        if (e == hipSuccess) { h->spec_used = sk; return e; }
+        bool ln = train && sk->launch_lean && lean_wanted(h, a);
+        hipError_t e = ln ? sk->launch_lean(mode, grid, h->stream, &h->net, a) : sk->launch(mode, grid, h->stream, &h->net, a);
+        if (ln && e != hipSuccess) {             // (the lean entry refused the arguments: nothing was launched, the general kernel takes the step)
+            (void)hipGetLastError();
+            ln = false;
+            e = sk->launch(mode, grid, h->stream, &h->net, a);
+        }
+        if (e == hipSuccess) { h->spec_used = sk; if (train) lean_note(h, ln); return e; }
         (void)hipGetLastError();                 // (a mode the specialised unit does not hold: the paths below)
     }
     if (jit_wanted(h, mode)) {
@@ -475,8 +533,12 @@ static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs
             if (has_lprog || jit_verify(h, je, a)) je->verified = true; else je = nullptr;
         }
         if (je) {
-            const hipError_t e = eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a);
-            if (e == hipSuccess) return e;
+            // (the lean entry of a module whose GENERAL train kernel jit_verify has checked against the one built ahead of time: the lean
+            //  entry itself is not run through that check -- it is the same source in the same module, and tests/test_gpu_lean_step.py
+            //  compares the two bit for bit)
+            const bool ln = train && je->verified && je->k.fn_lean[0] && lean_wanted(h, a, true);
+            const hipError_t e = eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a, ln);
+            if (e == hipSuccess) { if (train) lean_note(h, ln); return e; }
             (void)hipGetLastError();
             je->state.store(-1); h->jit_failed = true;
             h->jit_log = std::string("launch of the run-time compiled kernel failed: ") + hipGetErrorString(e);
@@ -484,6 +546,7 @@ static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs
         if ((h->net.loss == EH_LOSS_PROGRAM || h->drop_on) && mode != EH_MODE_EVAL) return hipErrorNotSupported;     // no other form of a recorded loss / of dropout exists
     }
     if (h->act == EH_ACT_PER_NET) return hipErrorNotSupported;       // (the table below has no such kernel; eh_create made sure the compiled one exists)
+    if (train) lean_note(h, false);
     return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
 }
 
@@ -942,6 +1005,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         eh_destroy(h);
         return fail(nullptr, EH_EUNSUPPORTED, "eh_create: per-net activations need the run-time compiled kernel, which failed to build: %.600s", log.c_str());
     }
+    lean_refresh(h);
     *out = h;
     return EH_OK;
 }
@@ -1022,6 +1086,7 @@ static int set_loss_program(eh_handle* h, int target, const uint32_t* code, int3
     lp.consts.assign(consts, consts + n_const);
     lp.out = out_slot;
     h->loss_prog.gen++;
+    lean_refresh(h);
     return EH_OK;
 }
 int32_t eh_set_loss_program(eh_handle* h, const uint32_t* code, int32_t n_instr, const float* consts, int32_t n_const, int32_t out_slot) {
@@ -1097,6 +1162,8 @@ int32_t eh_jit_status(eh_handle* h, int32_t* n_compiled, char* log, int64_t log_
     // a canonical descriptor runs the kernel specialised AHEAD of time (eh_spec.hip): counted like a compiled pair, the log says which it is
     std::string msg = h->jit_log;
     if (h->spec_used && h->aot_spec) { n += 1; msg = std::string("ahead-of-time: ") + h->spec_used->what + (msg.empty() ? "" : "; ") + msg; }
+    // which form of the single-step train kernel the last such launch ran (eh_lean_fold, eh_device.hpp)
+    if (h->lean_last >= 0) msg += std::string(msg.empty() ? "" : "; ") + (h->lean_last ? "train step kernel: lean" : "train step kernel: general");
     *n_compiled = n;
     if (log && log_bytes > 0) {
         const size_t m = std::min((size_t)log_bytes - 1, msg.size());
@@ -1113,8 +1180,14 @@ static bool so_allowed(const eh_handle* h) {
     return !no_so && h->n_nets == 1 && h->desc.n_nets == 0;
 }
 
+static int32_t set_option(eh_handle* h, const char* name, int64_t value);
 int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
     if (!h || !name) return EH_EINVAL;
+    const int32_t rc = set_option(h, name, value);
+    lean_refresh(h);                         // (an option may move the handle into or out of the lean kernels' contract)
+    return rc;
+}
+static int32_t set_option(eh_handle* h, const char* name, int64_t value) {
     if (h->seq) {                            // sequence models: always the reproducible step + reduce pair on the one fp32 kernel family
         if (!strcmp(name, "fused_update")) {
             if (value < 0 || value > 2) return fail(h, EH_EINVAL, "fused_update must be 0, 1 or 2");
@@ -1125,7 +1198,7 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
             if (value) return fail(h, EH_EUNSUPPORTED, "%s: not built for sequence models (one fp32 kernel family, one launch per step)", name);
             return EH_OK;
         }
-        if (!strcmp(name, "fast_paths") || !strcmp(name, "row_split") || !strcmp(name, "variant") || !strcmp(name, "aot_spec") || !strcmp(name, "bn_in_kernel")) return EH_OK;
+        if (!strcmp(name, "fast_paths") || !strcmp(name, "row_split") || !strcmp(name, "variant") || !strcmp(name, "aot_spec") || !strcmp(name, "bn_in_kernel") || !strcmp(name, "lean")) return EH_OK;
         if (!strcmp(name, "jit")) { h->jit_on = value != 0; return EH_OK; }      // a recorded closure: 1 = the kernels compiled around the program once built (seq_jit_entry), 0 = the interpreter
         if (!strcmp(name, "training_loss")) {
             if (value < EH_LOSS_MSE || value > EH_LOSS_PROGRAM) return fail(h, EH_EUNSUPPORTED, "training_loss %lld is not implemented on the device", (long long)value);
@@ -1253,6 +1326,10 @@ int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
     if (!strcmp(name, "empty_target_nan")) { // a target with no valid sample inside a batch that has some: the gradient is the reference's either way (that target adds
         h->empty_nan = value != 0;           // nothing); the VALUE is the sum of the other targets (0, default) or the reference's NaN = mean over an empty selection
         return EH_OK;                        // (1; src/losses/loss_fn.jl:61-63), reported by eh_loss_and_grad -- the seam where the reference's objective is called directly
+    }
+    if (!strcmp(name, "lean")) {             // 0 = never the lean form of the single-step train kernels (eh_lean_fold, eh_device.hpp): the general kernel, A/B
+        h->lean = value != 0;
+        return EH_OK;
     }
     if (!strcmp(name, "aot_spec")) {         // 0 = never the kernels specialised ahead of time for the canonical descriptors (eh_spec.hip): tests of the other paths, A/B
         h->aot_spec = value != 0;
@@ -2950,6 +3027,7 @@ int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float bet
     HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
     h->sc_sel = 0;
     h->opt_ready = true;
+    lean_refresh(h);
     return EH_OK;
 }
 
@@ -2993,6 +3071,7 @@ int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, 
     HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
     h->sc_sel = 0;
     h->opt_ready = true;
+    lean_refresh(h);
     return EH_OK;
 }
 
@@ -3295,6 +3374,7 @@ int32_t eh_set_dropout(eh_handle* h, const float* rate, int32_t n_hidden, uint64
     for (int l = 0; l < EH_MAX_HIDDEN; ++l) h->drop[l] = (any && l < n_hidden) ? rate[l] : 0.0f;
     h->drop_seed = seed; h->drop_step = step;
     if (any) { h->jit_failed = false; h->jit_log.clear(); }      // (a build that failed for other rates says nothing about these)
+    lean_refresh(h);
     return EH_OK;
 }
 
@@ -3787,6 +3867,7 @@ int32_t eh_debug_stamps(eh_handle* h, uint64_t* out, int32_t n) {
         HIPCHK(h, hipMalloc(&h->stamps, EH_STAMP_WORDS * sizeof(unsigned long long)));      // (words 32 on: the ordered step's hand-off, EH_ORD_ST_TAIL)
         HIPCHK(h, hipMemset(h->stamps, 0, EH_STAMP_WORDS * sizeof(unsigned long long)));
         memset(out, 0, (size_t)n * sizeof(uint64_t));
+        lean_refresh(h);                     // (diagnostics are outside the lean kernels' contract)
         return EH_OK;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));

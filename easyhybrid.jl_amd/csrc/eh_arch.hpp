@@ -45,6 +45,8 @@ struct EhSpecKernel {
     const char* what;
     hipError_t (*prepare)(void);
     hipError_t (*launch)(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args);
+    // the lean form of EH_MODE_TRAIN / EH_MODE_TRAIN_ORD (eh_lean_fold, eh_device.hpp), or nullptr: for arguments inside its contract only
+    hipError_t (*launch_lean)(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args);
 };
 #define EH_SPEC_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)
 #define EH_SPEC_DECL(k) extern "C" const EhSpecKernel* eh_spec_##k(void);

@@ -381,20 +381,34 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
 #pragma unroll
             for (int k = 0; k < NK; ++k) in = in && !empty(k);
             if (!in) {
+                // Cold, and kept out of the hot path's way: ONE loop over the group's rows that is not unrolled.  Row k is read again, on
+                // its own, until its words have arrived, and goes into the sum where fold() puts it: the same additions in the same
+                // order from + 0.  (Unrolled over the 16 rows x 4 words with the spin inside, this branch was a third of the ordered
+                // kernel's code and the reason its scalar registers spilled into vector lanes -- on every step, for a path that runs
+                // only when a store is late.  A row that has arrived reads the same again: nobody writes it before the next launch.)
                 const unsigned long long t0 = wall_clock64();
-                while (true) {
-                    __builtin_amdgcn_s_sleep(1);
-                    in = true;
+                bool late = false;
+                s = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+                for (int k = 0; k < NK; ++k) {
+                    f32x4 q = own;
+                    if (k != kown) {
+                        const int off = (unsigned)k < gsz ? rb + k * rk + 16 * v : (int)EH_ORD_OOB;
+                        auto empty_q = [&]() {
+                            bool e = false;
 #pragma unroll
-                    for (int k = 0; k < NK; ++k)
-                        if (empty(k)) {
-                            r[k] = eh_ord_ld16(rr, rb + k * rk + 16 * v);
-                            in = in && !empty(k);
+                            for (int j = 0; j < 4; ++j) e = e || (4 * v + j < nth && __float_as_uint(q[j]) == EH_ORD_EMPTY);
+                            return e;
+                        };
+                        q = eh_ord_ld16(rr, off);
+                        while (!late && empty_q()) {
+                            if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); late = true; break; }
+                            __builtin_amdgcn_s_sleep(1);
+                            q = eh_ord_ld16(rr, off);
                         }
-                    if (in) break;
-                    if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+                    }
+                    s += q;
                 }
-                s = fold();
             }
         }
         eh_ord_st16(gr, gb + 16 * v, s);
@@ -2567,6 +2581,38 @@ __device__ __forceinline__ void eh_kernarg_warm() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(d0), "s"(d1), "s"(d2), "s"(d3), "s"(d4), "s"(d5), "s"(d6), "s"(d7), "s"(d8), "s"(d9), "s"(d10), "s"(d11));
 #endif
 }
+// The "lean" form of the single-step train kernels (bit 3 of FAST; EH_MODE_TRAIN and EH_MODE_TRAIN_ORD of a kernel with its descriptor
+// baked in).  Most switches of EhStepArgs are properties of the HANDLE -- they do not change from one step of a training run to the next
+// -- yet every wave of every workgroup tested them on every step, on a kernel whose clock is the instructions its waves issue.  Here
+// the step body runs on a copy of the arguments in which those switches are constants: the same source with the branches decided, so
+// every sum is formed by the same additions in the same order.  THE CONTRACT (eh_lean_args_ok; the host launches the general kernel
+// for anything else): no batch statistics inside the step (bn_part == nullptr, bn_nblk != -1), one target with deferred normalisation
+// (inv_n == nullptr), no diagnostics (stamps == nullptr), not a step of a multi-step launch (ms_keep == ms_direct == 0, no carry), ONE
+// optimiser rule and that rule Adam (fz.opt.tab == nullptr, fz.opt.rule == EH_OPT_ADAM).  What changes within a run stays a run-time
+// value: idx, first, count, fz.pending / gslot / cur / sc_sel / loss_slot / agg_a, ord.slot / prev_grid, and whether fz.gacc is set.
+// (EH_AB_NO_LEAN_FOLD, through EH_JIT_DEFINES: the lean entry points with nothing folded -- the A/B of one source in one session;
+//  EH_STAMPS builds keep the diagnostics pointer, or there would be nothing to read.)
+enum { EH_FAST_LEAN = 8 };
+__host__ __device__ inline bool eh_lean_args_ok(const EhStepArgs& a) {
+#ifdef EH_STAMPS
+    const bool diag = false;
+#else
+    const bool diag = a.stamps != nullptr;
+#endif
+    return a.bn_part == nullptr && a.bn_nblk != -1 && a.inv_n == nullptr && !diag && a.ms_keep == 0 && a.ms_direct == 0 &&
+           a.fz.opt.tab == nullptr && a.fz.opt.rule == EH_OPT_ADAM;
+}
+__device__ __forceinline__ void eh_lean_fold(EhStepArgs& b) {
+#ifndef EH_AB_NO_LEAN_FOLD
+    b.bn_part = nullptr; b.bn_nblk = 0; b.bn_update = 0; b.bn_n = nullptr; b.bn_c = nullptr; b.bn_run = nullptr;
+    b.inv_n = nullptr;
+#ifndef EH_STAMPS
+    b.stamps = nullptr;
+#endif
+    b.ms_keep = 0; b.ms_direct = 0;
+    b.fz.opt.tab = nullptr; b.fz.opt.rule = EH_OPT_ADAM;
+#endif
+}
 #ifdef EH_SPEC_NS
 namespace EH_SPEC_NS {
 #endif
@@ -2636,6 +2682,11 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void eh_step_kernel(const Eh
                 const int q = i - (G::PHI_OFF + EH_IMG_BNM);
                 if (q < 0 || q >= 64) a.image_out[i] = eh_ms_smem[i];
             }
+    } else if constexpr ((FAST & EH_FAST_LEAN) != 0) {
+        static_assert(MODE == EH_MODE_TRAIN || MODE == EH_MODE_TRAIN_ORD, "the lean form exists for the single-step train kernels only");
+        EhStepArgs b = a;
+        eh_lean_fold(b);
+        eh_step_body<NBI, NBH, NL, NT, NW, ACT, MODE, (FAST & ~EH_FAST_LEAN)>(net, b);
     } else {
         eh_step_body<NBI, NBH, NL, NT, NW, ACT, MODE, FAST>(net, a);
     }

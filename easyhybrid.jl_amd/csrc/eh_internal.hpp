@@ -196,6 +196,9 @@ struct eh_handle_s {
     bool check_idx = false;         // "check_idx" option: range-check device-side minibatch indices before the step (debug)
     bool empty_nan = false;         // "empty_target_nan" option: eh_loss_and_grad reports NaN when a target of a non-empty batch has no valid sample (the reference's value; gradient unchanged)
     bool aot_spec = true;           // "aot_spec" option / EH_NO_AOT_SPEC: run the kernel specialised ahead of time when the descriptor is a canonical one (eh_spec.hip)
+    bool lean = true;               // "lean" option / EH_NO_LEAN: the lean form of the single-step train kernels where the handle's configuration allows it (eh_lean_fold, eh_device.hpp)
+    bool lean_cfg = false;          // ... and whether it does (lean_refresh, eh_api.hip: decided where the configuration changes, not per step)
+    int lean_last = -1;             // the last single-step train launch ran the lean (1) / the general (0) kernel; -1: none yet (eh_jit_status)
     const struct EhSpecKernel* spec_used = nullptr;      // ... the one the last launch ran (eh_jit_status reports it)
     bool specialize_async = false;  // "specialize" = 2
     bool jit_on = true;             // "jit" option / EH_JIT=0: 0 = the interpreting kernels built ahead of time

@@ -405,11 +405,18 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     // which kernels: train + eval, the cross-GPU train kernel when asked for, and -- per-wave family, registry model with its descriptor
     // baked in, one target -- the multi-step train kernel (several one-workgroup steps per launch, eh_device.hpp EH_MODE_TRAIN_MULTI) and
     // the ordered fused-update step (EH_MODE_TRAIN_ORD)
-    int modes[5], nmode = 0;
+    // ... and, with those two, the lean form of the single-step train kernels (bit 3 of FAST: eh_lean_fold, eh_device.hpp) -- the host
+    // launches it under the same test as the lean kernels built ahead of time (lean_refresh, eh_api.hip)
+    int modes[7], nmode = 0;
+    bool lean_k[7] = {false, false, false, false, false, false, false};
     modes[nmode++] = EH_MODE_TRAIN; modes[nmode++] = EH_MODE_EVAL;
     if (with_p2p && !A->wide && !prog) modes[nmode++] = EH_MODE_TRAIN_P2P;
-    if (!A->wide && !prog && !loss && !rowact && !drop && spec && spec->T == 1 && !(fast & 4)) { modes[nmode++] = EH_MODE_TRAIN_MULTI; modes[nmode++] = EH_MODE_TRAIN_ORD; }
-    char name[5][160];
+    if (!A->wide && !prog && !loss && !rowact && !drop && spec && spec->T == 1 && !(fast & 4)) {
+        modes[nmode++] = EH_MODE_TRAIN_MULTI; modes[nmode++] = EH_MODE_TRAIN_ORD;
+        lean_k[nmode] = true; modes[nmode++] = EH_MODE_TRAIN;
+        lean_k[nmode] = true; modes[nmode++] = EH_MODE_TRAIN_ORD;
+    }
+    char name[7][160];
     for (int i = 0; i < nmode; ++i) {
         const int m = modes[i];
         if (A->wide && V.so && m == EH_MODE_TRAIN) snprintf(name[i], sizeof name[i], "eh_bfs_kernel<%d, %d, %d, %d, %d, %s, %d>", A->nbi, A->nbh, A->nl, V.nw, act, prog ? "true" : "false", V.bf16 == 2 ? 1 : 3);
@@ -417,7 +424,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
         else if (A->wide && V.bf16) snprintf(name[i], sizeof name[i], "eh_widebf_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d>", A->nbi, A->nbh, A->nl, V.nt, V.nw, act, m, prog ? "true" : "false", V.bf16 == 2 ? 1 : 3);
         else if (A->wide) snprintf(name[i], sizeof name[i], "eh_wide_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", A->nbi, A->nbh, A->nl, V.nt, V.nw, act, m, prog ? "true" : "false");
         else snprintf(name[i], sizeof name[i], "eh_step_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", A->nbi, A->nbh, A->nl, V.nt, V.nw, act, m,
-                      (m == EH_MODE_EVAL) ? (fast & 5) : fast);       // (the eval kernels exist for FAST 0 / 1 / 4)
+                      (m == EH_MODE_EVAL) ? (fast & 5) : lean_k[i] ? (fast | EH_FAST_LEAN) : fast);       // (the eval kernels exist for FAST 0 / 1 / 4)
         hiprtcAddNameExpression(hp, name[i]);
     }
     // The flags of the Makefile, with one exception.  -fno-slp-vectorize is there because the SLP vectoriser miscompiled ONE group of
@@ -472,7 +479,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
         if (at != std::string::npos) fprintf(stderr, "eh_jit: %s\n", src.substr(at, src.find('\n', at) - at).c_str());
     }
     if (!from_cache) {
-        const char* names[5];
+        const char* names[7];
         for (int m = 0; m < nmode; ++m) names[m] = name[m];
         if (!compile_and_cache(hp, opts, names, nmode, cpath, &lowered, &code, log)) {
             hiprtcDestroyProgram(&hp);
@@ -492,9 +499,10 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     bool ok = hipModuleLoadData(&out->mod, code.data()) == hipSuccess;
     for (int i = 0; i < nmode && ok; ++i) {
         const int m = modes[i];
-        ok = !lowered[i].empty() && hipModuleGetFunction(&out->fn[m], out->mod, lowered[i].c_str()) == hipSuccess;
+        hipFunction_t& f = lean_k[i] ? out->fn_lean[m == EH_MODE_TRAIN_ORD ? 1 : 0] : out->fn[m];
+        ok = !lowered[i].empty() && hipModuleGetFunction(&f, out->mod, lowered[i].c_str()) == hipSuccess;
         // (raises the dynamic-LDS limit where the runtime wants to be told; a refusal shows up as a failed launch, which the caller handles)
-        if (ok) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(out->fn[m]), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (ok) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           m == EH_MODE_TRAIN_MULTI ? (int)EH_LDS_LIMIT : (int)V.lds_bytes);
     }
     if (!ok && from_cache) (void)unlink(cpath.c_str());       // a stale or damaged entry: gone, the next build compiles
@@ -507,9 +515,14 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     return true;
 }
 
-hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args) {
+hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args, bool lean) {
     void* params[] = {const_cast<EhNet*>(net), const_cast<EhStepArgs*>(args)};
     if (mode < 0 || mode > 4 || !k->fn[mode]) return hipErrorNotSupported;
+    if (lean) {       // the lean form of a single-step train kernel: for arguments inside its contract only (the caller has checked: lean_wanted, eh_api.hip)
+        const hipFunction_t f = mode == EH_MODE_TRAIN ? k->fn_lean[0] : mode == EH_MODE_TRAIN_ORD ? k->fn_lean[1] : nullptr;
+        if (!f) return hipErrorNotSupported;
+        return hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, 64u * (unsigned)k->nw, 1, 1, (unsigned)k->lds_bytes, stream, params, nullptr);
+    }
     if (mode == EH_MODE_TRAIN_MULTI) {      // one workgroup; its step-to-step state sits in LDS behind the work space
         const size_t lds_ms = k->lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, args->fz.opt.tab != nullptr);
         if (grid != 1 || lds_ms > EH_LDS_LIMIT) return hipErrorInvalidValue;
@@ -578,5 +591,5 @@ hipError_t eh_jit_launch_seq(const EhJitKernel* k, int mode, int grid, hipStream
 
 void eh_jit_release(EhJitKernel* k) {
     if (k->mod) (void)hipModuleUnload(k->mod);
-    k->mod = nullptr; k->fn[0] = k->fn[1] = k->fn[2] = k->fn[3] = k->fn[4] = nullptr;
+    k->mod = nullptr; k->fn[0] = k->fn[1] = k->fn[2] = k->fn[3] = k->fn[4] = nullptr; k->fn_lean[0] = k->fn_lean[1] = nullptr;
 }

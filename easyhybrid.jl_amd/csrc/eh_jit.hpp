@@ -14,6 +14,7 @@ struct EhJitKernel {
     hipModule_t mod = nullptr;
     hipFunction_t fn[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // EH_MODE_TRAIN, EH_MODE_EVAL, EH_MODE_TRAIN_P2P (when asked for), EH_MODE_TRAIN_MULTI and
                                                                            // EH_MODE_TRAIN_ORD (per-wave registry models with one target)
+    hipFunction_t fn_lean[2] = {nullptr, nullptr};   // the lean form of EH_MODE_TRAIN [0] and EH_MODE_TRAIN_ORD [1] (eh_lean_fold, eh_device.hpp), where those two are built
     int nw = 0;
     size_t lds_bytes = 0;
     size_t lds_eval_bytes = 0;      // forward / evaluation kernel (0: lds_bytes)
@@ -47,7 +48,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
 // generated header, eh_dropout_mask and the tests' twin
 inline unsigned eh_drop_threshold(float p) { const double t = (double)p * 4294967296.0; return t >= 4294967295.0 ? 4294967295u : (unsigned)t; }
 inline float eh_drop_scale(float p) { return 1.0f / (1.0f - p); }
-hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args);
+hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args, bool lean = false);
 void eh_jit_release(EhJitKernel* k);
 // Sequence models around a recorded closure (eh_seq.hpp, EH_SEQ_HEAD_PROG): the (NBI, NBH) instantiation of the three modes compiled
 // around the generated eh_jit_fwd / eh_jit_rev; fn[EH_SEQ_TRAIN], fn[EH_SEQ_EVAL], fn[EH_SEQ_FORWARD].  Same disk cache as above.

@@ -48,6 +48,11 @@ using Geom = EhGeom<NBI, NBH, NL, NT, NW>;
 constexpr bool HASP2P = (FAST & 4) == 0;
 constexpr bool HASMULTI = (FAST & 4) == 0 && EhNet{EH_SPEC_NET}.T == 1;
 constexpr bool HASORD = HASMULTI;      // (the ordered fused-update step: one target, no program)
+// -DEH_SPEC_LEAN (the headline descriptors): the lean form of the single-step train kernels as well (eh_lean_fold, eh_device.hpp)
+#ifdef EH_SPEC_LEAN
+#define EH_SPEC_KERNEL_LEAN(MODE) eh_step_kernel<NBI, NBH, NL, NT, NW, ACT, MODE, (FAST | EH_FAST_LEAN)>
+static_assert(HASORD, "the lean form is built for descriptors that have the ordered step");
+#endif
 #endif
 constexpr size_t LDS = sizeof(float) * Geom::TOTAL_FLOATS;
 #if EH_SPEC_FAMILY == 0
@@ -64,6 +69,10 @@ hipError_t prepare() {
     if constexpr (HASP2P) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL(EH_MODE_TRAIN_P2P)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); }
     if constexpr (HASORD) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL(EH_MODE_TRAIN_ORD)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); }
     if constexpr (HASMULTI) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL(EH_MODE_TRAIN_MULTI)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EH_LDS_LIMIT); }
+#ifdef EH_SPEC_LEAN
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN_ORD)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+#endif
 #endif
     return e;
 }
@@ -85,10 +94,23 @@ hipError_t launch(int mode, int grid, hipStream_t stream, const EhNet* net, cons
     else return hipErrorNotSupported;
     return hipGetLastError();
 }
+// the lean form (the caller has checked the contract: eh_lean_args_ok)
+#ifdef EH_SPEC_LEAN
+hipError_t launch_lean(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args) {
+    if (!eh_lean_args_ok(*args)) return hipErrorInvalidValue;
+    if (mode == EH_MODE_TRAIN) hipLaunchKernelGGL((EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
+    else if (mode == EH_MODE_TRAIN_ORD) hipLaunchKernelGGL((EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN_ORD)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
+    else return hipErrorNotSupported;
+    return hipGetLastError();
+}
+constexpr auto LAUNCH_LEAN = &launch_lean;
+#else
+constexpr hipError_t (*LAUNCH_LEAN)(int, int, hipStream_t, const EhNet*, const EhStepArgs*) = nullptr;
+#endif
 #define EH_STR_(x) #x
 #define EH_STR(x) EH_STR_(x)
 const EhSpecKernel spec = {EhNet{EH_SPEC_NET}, EH_SPEC_FAMILY != 0, EH_SPEC_FAMILY >= 2 ? (EH_SPEC_NSPLIT == 3 ? 1 : 2) : 0, NBI, NBH, NL, NT, NW, ACT, FAST, EH_SPEC_FAMILY == 3 ? 1 : 0, LDS,
-                           "descriptor " EH_STR(EH_SPEC_ID) " of csrc/Makefile, specialised ahead of time", &prepare, &launch};
+                           "descriptor " EH_STR(EH_SPEC_ID) " of csrc/Makefile, specialised ahead of time", &prepare, &launch, LAUNCH_LEAN};
 }   // namespace
 
 #define EH_CAT_(a) eh_spec_##a
