@@ -1,7 +1,7 @@
-// C ABI of libeasyhybrid_hip.so (declared in include/easyhybrid_hip.h): model, data, parameters, forward / eval, the training
-// step and epoch, the optimiser, graphs, the data-parallel seam eh_dp_*.  The small kernels live in eh_kernels.hpp, the handle in
-// eh_internal.hpp, the library's own collectives (eh_comm_*, eh_p2p_*) in eh_comm.hip.  Everything here runs on one HIP stream
-// per handle; there is no CPU compute path.
+// C ABI of libeasyhybrid_hip.so (declared in include/easyhybrid_hip.h): model, parameters, forward / eval, the training step and
+// epoch, the optimiser, graphs, the data-parallel seam eh_dp_*.  The small kernels live in eh_kernels.hpp, the handle and the map of
+// the other units (data upload, layer-wise form, L-BFGS, mechanistic stage, sequence kernels, collectives) in eh_internal.hpp.
+// Everything here runs on one HIP stream per handle; there is no CPU compute path.
 #include <hip/hip_runtime.h>
 #include <chrono>
 
@@ -24,7 +24,6 @@
 #include "eh_chain.hpp"
 #include "eh_lbfgs.hpp"
 #include "eh_wide.hpp"
-#include "eh_lform.hpp"
 #include "eh_seq.hpp"
 
 std::string g_create_err;
@@ -70,6 +69,13 @@ static EhOrd ord_args(const eh_handle* h, int slot, int prev_grid) {
     o.rs = h->ord_rs; o.soff = h->ord_soff; o.slot = slot; o.prev_grid = prev_grid;
     return o;
 }
+static int flush_done(eh_handle* h) {      // the update is applied: the beta products advance, nothing is pending
+    h->sc_sel ^= 1;
+    h->pending = false;
+    h->pend_ord = false;
+    h->pending_loss = nullptr;
+    return EH_OK;
+}
 static int flush_one(eh_handle* h) {
     const int nt = h->net.n_theta;
     if (h->pend_ord) {        // an ordered step's sums: its rows and group rows (the step wrote slot h->cur ^ 1, which is what slot h->cur reads)
@@ -77,11 +83,7 @@ static int flush_one(eh_handle* h) {
         hipLaunchKernelGGL(eh_ord_flush_kernel, dim3(std::max((nt + 255) / 256, h->ord_grid)), dim3(256), 0, h->stream, ord_args(h, h->cur, h->ord_grid), nt, TH(h), MM(h), VV(h),
                            h->sc + 2 * h->sc_sel, h->sc + 2 * (h->sc_sel ^ 1), h->opt, h->pending_loss, h->img, h->net.loss);
         HIPCHK(h, hipGetLastError());
-        h->sc_sel ^= 1;
-        h->pending = false;
-        h->pend_ord = false;
-        h->pending_loss = nullptr;
-        return EH_OK;
+        return flush_done(h);
     }
     const float* g_prev = h->gacc + (size_t)((h->gstep + 2) % 3) * EH_GSHARDS * h->n_acc;
     float* sc_in = h->sc + 2 * h->sc_sel;
@@ -93,10 +95,7 @@ static int flush_one(eh_handle* h) {
     // its prologue and nobody reads a slot before the step after its clearing has filled it).  Under EhP2P the workgroups add
     // into a staging copy that the publishing workgroup reads whole: cleared here.
     if (h->p2p_on) HIPCHK(h, hipMemsetAsync(h->p2p_stage, 0, (size_t)3 * EH_GSHARDS * h->n_acc * sizeof(float), h->stream));
-    h->sc_sel ^= 1;
-    h->pending = false;
-    h->pending_loss = nullptr;
-    return EH_OK;
+    return flush_done(h);
 }
 // Every trainable scalar of the model as (canonical flat index, layer, row, col) in the padded
 // block-diagonal MLP.  col < 0 marks a bias.  SingleNN = one net covering everything.
@@ -261,7 +260,6 @@ static hipError_t lform_prepare(void) { return hipSuccess; }
 static hipError_t lform_launch(int, int, int, int, hipStream_t, const EhNet*, const EhStepArgs*) { return hipErrorNotSupported; }
 static const EhArchInfo g_lform_arch = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, /*phi_off*/ 0, /*img_floats*/ EH_IMG_META, /*has_fast*/ 0, /*nvar*/ 1,
                                         {{4, 4, 0, 1 << 30, &lform_prepare, &lform_launch, 1, 0}, {}, {}, {}}, /*wide*/ 1};
-enum { EH_LFORM_ROWS = 64 };      // partial slabs of the weight gradients (split over the samples of a minibatch)
 
 static bool arch_fits(const EhArchInfo* A, int need) {
     for (int vi = 0; vi < A->nvar; ++vi)
@@ -468,61 +466,54 @@ static void lean_note(eh_handle* h, bool lean) {
     h->lean_last = v;
 }
 
+// One attempt on the kernel built ahead of time for the handle's descriptor (eh_spec.hip).  The single-step train modes take its lean form
+// (eh_lean_fold, eh_device.hpp) where the unit holds one, the handle's configuration is inside the contract (lean_refresh) and the
+// arguments say the same; a lean entry that refuses them has launched nothing, and the general kernel takes the step.
+static hipError_t spec_launch(eh_handle* h, const EhSpecKernel* sk, int mode, int grid, const EhStepArgs* a) {
+    const bool single = mode == EH_MODE_TRAIN || mode == EH_MODE_TRAIN_ORD;
+    bool ln = single && sk->has_lean && lean_wanted(h, a);
+    hipError_t e = sk->launch(mode, grid, h->stream, &h->net, a, ln);
+    if (ln && e != hipSuccess) {
+        (void)hipGetLastError();
+        ln = false;
+        e = sk->launch(mode, grid, h->stream, &h->net, a, false);
+    }
+    if (e == hipSuccess) { h->spec_used = sk; if (single) lean_note(h, ln); } else (void)hipGetLastError();
+    return e;
+}
+// The step kernel of `mode` for the handle: ahead-of-time specialised (spec_lookup), compiled at run time (jit_entry), or the table
+// entry of the handle's (family, variant) -- in that order, with fall-through rules that differ by mode and are the contract of the
+// ordered step (its bits are those of the step + reduce pair only on the kernel the pair's step runs):
+//   EH_MODE_TRAIN_ORD    when an ahead-of-time kernel matched, its result is final.  A run-time compiled kernel is used only once the
+//                        pair's first step has checked it (`verified`, jit_verify) and only if it has the mode; otherwise
+//                        hipErrorNotSupported, nothing launched: the caller runs the pair.
+//   EH_MODE_TRAIN_MULTI  (the caller checked multi_ok) a failed ahead-of-time launch goes straight to the table, not to the run-time
+//                        compiled kernel; that one is used only if `verified` (the single-step path does the check).
+//   every other mode     a failed ahead-of-time launch (a mode the unit does not hold) falls through to the run-time compiled kernel and
+//                        then the table.  Here jit_verify runs; a failed launch of the compiled kernel retires it; a recorded loss,
+//                        dropout and per-net activations have no other form: hipErrorNotSupported instead of the table.
 static hipError_t step_launch(eh_handle* h, int mode, int grid, const EhStepArgs* a) {
-    if (mode == EH_MODE_TRAIN_ORD) {
-        // the ordered step gives the bits of the step + reduce pair only on the kernel the pair's step runs: the kernel family EH_MODE_TRAIN
-        // picks below, or nothing (hipErrorNotSupported, nothing launched: the caller runs the pair).  A run-time compiled kernel is
-        // taken once the pair's first step has checked it (jit_verify).
-        if (const EhSpecKernel* sk = spec_lookup(h)) {
-            bool ln = sk->launch_lean && lean_wanted(h, a);
-            hipError_t e = ln ? sk->launch_lean(mode, grid, h->stream, &h->net, a) : sk->launch(mode, grid, h->stream, &h->net, a);
-            if (ln && e != hipSuccess) {         // (the lean entry refused the arguments: nothing was launched, the general kernel takes the step)
-                (void)hipGetLastError();
-                ln = false;
-                e = sk->launch(mode, grid, h->stream, &h->net, a);
-            }
-            if (e == hipSuccess) { h->spec_used = sk; lean_note(h, ln); } else (void)hipGetLastError();
+    const bool train = mode == EH_MODE_TRAIN, ord = mode == EH_MODE_TRAIN_ORD, multi = mode == EH_MODE_TRAIN_MULTI;
+    const EhSpecKernel* sk = spec_lookup(h);
+    if (sk) {
+        const hipError_t e = spec_launch(h, sk, mode, grid, a);
+        if (e == hipSuccess || ord) return e;
+    }
+    if (ord || multi) {      // the run-time compiled kernel of the single-step path, once that path has checked it against the generic one
+        eh_handle_s::JitEntry* je = ((multi && sk) || !jit_wanted(h, EH_MODE_TRAIN)) ? nullptr : jit_entry(h);
+        if (je && ord) {
+            if (!je->verified || !je->k.fn[EH_MODE_TRAIN_ORD]) return hipErrorNotSupported;
+            const bool ln = je->k.fn_lean[1] && lean_wanted(h, a, true);
+            const hipError_t e = eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a, ln);
+            if (e == hipSuccess) lean_note(h, ln);
             return e;
         }
-        if (jit_wanted(h, EH_MODE_TRAIN)) {
-            eh_handle_s::JitEntry* je = jit_entry(h);
-            if (je) {
-                if (!je->verified || !je->k.fn[EH_MODE_TRAIN_ORD]) return hipErrorNotSupported;
-                const bool ln = je->k.fn_lean[1] && lean_wanted(h, a, true);
-                const hipError_t e = eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a, ln);
-                if (e == hipSuccess) lean_note(h, ln);
-                return e;
-            }
-        }
-        lean_note(h, false);
-        return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
-    }
-    if (mode == EH_MODE_TRAIN_MULTI) {     // (built ahead of time only -- specialised for the canonical descriptors, generic otherwise; the caller checked: multi_ok)
-        if (const EhSpecKernel* sk = spec_lookup(h)) {
-            if (sk->launch(mode, grid, h->stream, &h->net, a) == hipSuccess) { h->spec_used = sk; return hipSuccess; }
+        if (je && je->verified && je->k.fn[EH_MODE_TRAIN_MULTI]) {
+            if (eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a) == hipSuccess) return hipSuccess;
             (void)hipGetLastError();
-        } else if (jit_wanted(h, EH_MODE_TRAIN)) {      // the kernel compiled at run time, once it has been checked against the generic one (the single-step path does that)
-            eh_handle_s::JitEntry* je = jit_entry(h);
-            if (je && je->verified && je->k.fn[EH_MODE_TRAIN_MULTI]) {
-                if (eh_jit_launch(&je->k, mode, grid, h->stream, &h->net, a) == hipSuccess) return hipSuccess;
-                (void)hipGetLastError();
-            }
         }
+        if (ord) lean_note(h, false);
         return h->arch->var[h->variant].launch(mode, h->act, KFAST(h), grid, h->stream, &h->net, a);
-    }
-    // the lean form of the single-step train kernel (eh_lean_fold, eh_device.hpp): kernels with the descriptor baked in, a handle whose
-    // configuration is inside the contract (lean_refresh), arguments that say the same
-    const bool train = mode == EH_MODE_TRAIN;
-    if (const EhSpecKernel* sk = spec_lookup(h)) {
-        bool ln = train && sk->launch_lean && lean_wanted(h, a);
-        hipError_t e = ln ? sk->launch_lean(mode, grid, h->stream, &h->net, a) : sk->launch(mode, grid, h->stream, &h->net, a);
-        if (ln && e != hipSuccess) {             // (the lean entry refused the arguments: nothing was launched, the general kernel takes the step)
-            (void)hipGetLastError();
-            ln = false;
-            e = sk->launch(mode, grid, h->stream, &h->net, a);
-        }
-        if (e == hipSuccess) { h->spec_used = sk; if (train) lean_note(h, ln); return e; }
-        (void)hipGetLastError();                 // (a mode the specialised unit does not hold: the paths below)
     }
     if (jit_wanted(h, mode)) {
         eh_handle_s::JitEntry* je = jit_entry(h);
@@ -559,12 +550,6 @@ const char* eh_last_error(const eh_handle* h) { return h ? h->err.c_str() : g_cr
 // Streams of destroyed handles are kept for the next handle on the same device: creating one takes 1.4-1.9 ms and destroying it as long
 // again -- a fifth of a whole train() call on the reference's tutorial data set, which creates and destroys one engine per call.  At most
 // eight per device are kept (more are destroyed); the kept ones live until the process ends.
-static std::mutex g_stage_mu;                 // eh_set_data's pinned staging pair (host memory: any device)
-static float* g_stage[2] = {nullptr, nullptr};
-static size_t g_stage_bytes = 0;
-static int copy_out(eh_handle* h, float* dst, const float* src_dev, size_t n);
-static void lbfgs_release(eh_handle* h);
-static int copy_in(eh_handle* h, float* dst_dev, const float* src, size_t n);
 static std::mutex g_stream_pool_mu;
 static std::vector<std::pair<int, hipStream_t>> g_stream_pool;
 static hipStream_t stream_pool_take(int device) {
@@ -1023,7 +1008,7 @@ int32_t eh_destroy(eh_handle* h) {
     (void)hipFree(h->gacc); (void)hipFree(h->ord); if (h->ord_err) (void)hipHostFree(h->ord_err); (void)hipFree(h->bn_part); (void)hipFree(h->bn_run); (void)hipFree(h->bn_shift); (void)hipFree(h->bn_stat); (void)hipFree(h->tcount); (void)hipFree(h->mombuf); (void)hipFree(h->slab); (void)hipFree(h->gradbuf); (void)hipFree(h->inv_n);
     (void)hipFree(h->prog); (void)hipFree(h->l2val); (void)hipFree(h->l2w); (void)hipFree(h->loss_hist); (void)hipFree(h->perm); (void)hipFree(h->out_buf); (void)hipFree(h->idx_buf);
     eval_host_release(h);
-    lbfgs_release(h);
+    eh_lbfgs_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
     (void)hipFree(h->stamps); (void)hipFree(h->image); (void)hipFree(h->imap); (void)hipFree(h->rmap);
     (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs); (void)hipFree(h->split[0].starts); (void)hipFree(h->split[1].starts); (void)hipFree(h->seq_ws); (void)hipFree(h->chain_part);
@@ -1394,195 +1379,13 @@ static int32_t set_option(eh_handle* h, const char* name, int64_t value) {
     return fail(h, EH_EINVAL, "unknown option %s", name);
 }
 
-int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, const float* const* forcings, const float* const* targets,
-                    int32_t on_device) {
-    if (!h) return EH_EINVAL;
-    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_set_data: split %d", split);
-    if (n < 0 || n > 0x7fffffffLL) return fail(h, EH_EINVAL, "eh_set_data: n = %lld", (long long)n);
-    if (on_device & ~(EH_DATA_ON_DEVICE | EH_DATA_X_PLANES | EH_DATA_X_ROWS)) return fail(h, EH_EINVAL, "eh_set_data: flags %d", on_device);
-    if ((on_device & EH_DATA_X_ROWS) && (on_device & (EH_DATA_ON_DEVICE | EH_DATA_X_PLANES))) return fail(h, EH_EINVAL, "eh_set_data: EH_DATA_X_ROWS goes with host arrays only, and not with EH_DATA_X_PLANES");
-    if (n > 0 && ((!x && h->net.P > 0) || !forcings || !targets)) return fail(h, EH_EINVAL, "eh_set_data: null array");
-    const EhNet& net = h->net;
-    HIPCHK(h, hipSetDevice(h->device));
-    EhSplit& sp = h->split[split];
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(sp.recs); (void)hipFree(sp.starts);
-    sp.recs = nullptr; sp.n = 0; sp.starts = nullptr; sp.nwin = 0;
-    if (split == EH_SPLIT_TRAIN) h->perm_valid = false;
-    if (n == 0) return EH_OK;
-    const int C = h->C;
-    static const bool dbg_t = getenv("EH_DEBUG_SET_DATA") != nullptr;      // (diagnostic: where an upload's wall clock goes)
-    const auto t_a = std::chrono::steady_clock::now();
-    HIPCHK(h, hipMalloc(&sp.recs, (size_t)n * C * sizeof(float)));
-    const auto t_b = std::chrono::steady_clock::now();
-    const bool planes = (on_device & EH_DATA_X_PLANES) != 0;       // x as P arrays of N (row-major P x N: what a NumPy host holds) instead of N records of P
-    const bool xrows = (on_device & EH_DATA_X_ROWS) != 0;          // x as P POINTERS to arrays of N: the caller's own columns, never stacked into a matrix
-    const float* const* const xr = reinterpret_cast<const float* const*>(x);
-    if (xrows) for (int j = 0; j < net.P; ++j) if (!xr[j]) return fail(h, EH_EINVAL, "eh_set_data: predictor row %d is null", j);
-    on_device &= EH_DATA_ON_DEVICE;
-    if (on_device) {
-        EhPackArgs pa{};
-        pa.x = x;
-        for (int f = 0; f < net.F; ++f) pa.forc[f] = forcings[f];
-        for (int t = 0; t < net.T; ++t) pa.targ[t] = targets[t];
-        const long long tot = (long long)n * C;
-        hipLaunchKernelGGL(eh_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, pa, sp.recs, (long long)n, net.P, net.F, net.T, planes ? 1 : 0);
-        HIPCHK(h, hipGetLastError());
-        // metric shift: mean of the first EH_SHIFT_VALID valid targets, from small host copies (a record that starts with a gap is read on
-        // until that many are found)
-        std::vector<float> tmp((size_t)std::min<int64_t>(n, 4096));
-        for (int t = 0; t < net.T; ++t) {
-            double s = 0; long long c = 0;
-            for (int64_t off = 0; off < n && c < EH_SHIFT_VALID; off += (int64_t)tmp.size()) {
-                const size_t m = (size_t)std::min<int64_t>((int64_t)tmp.size(), n - off);
-                HIPCHK(h, hipMemcpy(tmp.data(), targets[t] + off, m * sizeof(float), hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < m && c < EH_SHIFT_VALID; ++i) if (!std::isnan(tmp[i])) { s += tmp[i]; ++c; }
-            }
-            sp.shift[t] = c ? (float)(s / c) : 0.0f;
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-        // records interleaved on the host in chunks of <= 1 M samples, through two pinned staging buffers: chunk k is packed (two
-        // to eight threads, each on its own run of samples) while chunk k - 1 is on its way over PCIe.  (Rounds 1-3: one pageable 67 MB vector, one thread, one
-        // blocking copy: 56 ms for the headline data set; the one-time cost a user's train() call pays before its first step.)
-        for (int t = 0; t < net.T; ++t) {
-            double sum = 0; long long c = 0;
-            for (int64_t s = 0; s < n && c < EH_SHIFT_VALID; ++s) if (!std::isnan(targets[t][s])) { sum += targets[t][s]; ++c; }
-            sp.shift[t] = c ? (float)(sum / c) : 0.0f;
-        }
-        const int64_t CH = std::min<int64_t>(n, (int64_t)1 << 20);
-        // (the two pinned buffers are kept for the next call of the process -- pinning 2 x 16 MB costs as much as the upload they stage;
-        //  a second thread uploading at the same time gets buffers of its own)
-        float* stage[2] = {nullptr, nullptr};
-        hipEvent_t done[2] = {nullptr, nullptr};
-        const size_t stage_bytes = (size_t)CH * C * sizeof(float);
-        std::unique_lock<std::mutex> pool_lk(g_stage_mu, std::try_to_lock);
-        const bool pooled = pool_lk.owns_lock();
-        bool pinned;
-        if (pooled) {
-            if (g_stage_bytes < stage_bytes) {
-                for (int k = 0; k < 2; ++k) { if (g_stage[k]) (void)hipHostFree(g_stage[k]); g_stage[k] = nullptr; }
-                g_stage_bytes = 0;
-                if (hipHostMalloc((void**)&g_stage[0], stage_bytes, hipHostMallocPortable) == hipSuccess &&          // (portable: the next handle may sit on another device)
-                    hipHostMalloc((void**)&g_stage[1], stage_bytes, hipHostMallocPortable) == hipSuccess) g_stage_bytes = stage_bytes;
-                else { (void)hipGetLastError(); for (int k = 0; k < 2; ++k) { if (g_stage[k]) (void)hipHostFree(g_stage[k]); g_stage[k] = nullptr; } }
-            }
-            pinned = g_stage_bytes >= stage_bytes;
-            if (pinned) { stage[0] = g_stage[0]; stage[1] = g_stage[1]; }
-        } else {
-            pinned = hipHostMalloc((void**)&stage[0], stage_bytes, hipHostMallocDefault) == hipSuccess &&
-                     hipHostMalloc((void**)&stage[1], stage_bytes, hipHostMallocDefault) == hipSuccess;
-        }
-        std::vector<float> pageable;
-        if (!pinned) {                                   // (no pinned memory to be had: the plain path)
-            (void)hipGetLastError();
-            if (!pooled) { if (stage[0]) (void)hipHostFree(stage[0]); if (stage[1]) (void)hipHostFree(stage[1]); }
-            pageable.resize((size_t)CH * C);
-            stage[0] = stage[1] = pageable.data();
-        } else {
-            // (an event that cannot be made: the first one is not leaked and a one-off staging pair not kept; advisor, round 4)
-            hipError_t ee = hipEventCreateWithFlags(&done[0], hipEventDisableTiming);
-            if (ee == hipSuccess) { ee = hipEventCreateWithFlags(&done[1], hipEventDisableTiming); if (ee != hipSuccess) (void)hipEventDestroy(done[0]); }
-            if (ee != hipSuccess) { if (!pooled) { (void)hipHostFree(stage[0]); (void)hipHostFree(stage[1]); } HIPCHK(h, ee); }
-        }
-        const auto t_c = std::chrono::steady_clock::now();
-        const int P = net.P, F = net.F, T = net.T;
-        auto pack = [&](float* dst, int64_t s0, int64_t s1, int64_t base) {
-            for (int64_t s = s0; s < s1; ++s) {
-                float* r = dst + (size_t)(s - base) * C;
-                if (xrows) for (int j = 0; j < P; ++j) r[j] = xr[j][s];
-                else if (planes) for (int j = 0; j < P; ++j) r[j] = x[(size_t)j * (size_t)n + (size_t)s];
-                else for (int j = 0; j < P; ++j) r[j] = x[(size_t)s * P + j];
-                for (int f = 0; f < F; ++f) r[P + f] = forcings[f][s];
-                for (int t = 0; t < T; ++t) r[P + F + t] = targets[t][s];
-            }
-        };
-        hipError_t err = hipSuccess;
-        int k = 0;
-        for (int64_t s0 = 0; s0 < n && err == hipSuccess; s0 += CH, ++k) {
-            const int64_t cnt = std::min(CH, n - s0);
-            float* const buf = stage[k & 1];
-            const auto tq0 = std::chrono::steady_clock::now();
-            if (pinned && k >= 2) err = hipEventSynchronize(done[k & 1]);       // the copy that last read this buffer is through
-            if (err != hipSuccess) break;
-            const auto tq1 = std::chrono::steady_clock::now();
-            if (cnt >= 65536) {          // a chunk is interleaved by up to eight threads, each on its own run of samples
-                const unsigned hw = std::thread::hardware_concurrency();
-                static const int pack_max = getenv("EH_PACK_THREADS") ? std::max(1, atoi(getenv("EH_PACK_THREADS"))) : 8;
-                const int nthr = (int)std::max<int64_t>(2, std::min<int64_t>({(int64_t)pack_max, (int64_t)(hw ? hw / 2 : 2), cnt / 32768}));
-                const int64_t per = (cnt + nthr - 1) / nthr;
-                std::vector<std::thread> others;
-                int64_t mine_end = std::min(s0 + cnt, s0 + per);
-                try {                    // (no exception crosses the C ABI: a thread that cannot be started leaves its run of samples to this one)
-                    for (int w = 1; w < nthr; ++w) {
-                        const int64_t a0 = s0 + w * per, a1 = std::min(s0 + cnt, a0 + per);
-                        if (a0 < a1) others.emplace_back([&, a0, a1] { pack(buf, a0, a1, s0); });
-                    }
-                } catch (...) {
-                    for (auto& t : others) t.join();
-                    others.clear();
-                    mine_end = s0 + cnt;         // single-threaded: everything (the threads that did start packed the same values into the same places)
-                }
-                pack(buf, s0, mine_end, s0);
-                for (auto& t : others) t.join();
-            } else pack(buf, s0, s0 + cnt, s0);
-            const auto tq2 = std::chrono::steady_clock::now();
-            if (pinned) {
-                err = hipMemcpyAsync(sp.recs + (size_t)s0 * C, buf, (size_t)cnt * C * sizeof(float), hipMemcpyHostToDevice, h->stream);
-                if (err == hipSuccess) err = hipEventRecord(done[k & 1], h->stream);
-                if (dbg_t) {
-                    auto ms = [](std::chrono::steady_clock::time_point u, std::chrono::steady_clock::time_point v) { return std::chrono::duration<double, std::milli>(v - u).count(); };
-                    fprintf(stderr, "   chunk %d: wait %.2f pack %.2f enqueue %.2f ms\n", k, ms(tq0, tq1), ms(tq1, tq2), ms(tq2, std::chrono::steady_clock::now()));
-                }
-            } else err = hipMemcpy(sp.recs + (size_t)s0 * C, buf, (size_t)cnt * C * sizeof(float), hipMemcpyHostToDevice);
-        }
-        // always drained before the staging pair is released or handed to the next caller -- also after an error: copies of earlier chunks
-        // may still be reading it (advisor, round 4)
-        const auto t_d = std::chrono::steady_clock::now();
-        { const hipError_t es = hipStreamSynchronize(h->stream); if (err == hipSuccess) err = es; }
-        if (dbg_t) {
-            auto ms = [](std::chrono::steady_clock::time_point u, std::chrono::steady_clock::time_point v) { return std::chrono::duration<double, std::milli>(v - u).count(); };
-            fprintf(stderr, "eh_set_data n=%lld: hipMalloc %.2f ms, staging (pooled %d pinned %d) %.2f ms, pack + enqueue %.2f ms, drain %.2f ms\n", (long long)n, ms(t_a, t_b), (int)pooled, (int)pinned,
-                    ms(t_b, t_c), ms(t_c, t_d), ms(t_d, std::chrono::steady_clock::now()));
-        }
-        if (pinned) { (void)hipEventDestroy(done[0]); (void)hipEventDestroy(done[1]); if (!pooled) { (void)hipHostFree(stage[0]); (void)hipHostFree(stage[1]); } }
-        HIPCHK(h, err);
-    }
-    sp.n = n;
-    return EH_OK;
-}
-
-int32_t eh_set_sequences(eh_handle* h, int32_t split, int32_t input_window, int32_t output_window, int32_t lead_time, const int32_t* starts, int64_t n_windows) {
-    if (!h) return EH_EINVAL;
-    if (!h->seq) return fail(h, EH_EUNSUPPORTED, "eh_set_sequences: the model has no LSTM layer (EH_LAYER_LSTM): its samples are single records");
-    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_set_sequences: split %d", split);
-    if (input_window < 1 || input_window > EH_MAX_SEQ_WINDOW) return fail(h, EH_EINVAL, "eh_set_sequences: input_window %d (1..%d)", input_window, EH_MAX_SEQ_WINDOW);
-    if (output_window < 1 || output_window > input_window) return fail(h, EH_EINVAL, "eh_set_sequences: output_window %d (1..input_window = %d)", output_window, input_window);
-    if (lead_time < 0) return fail(h, EH_EINVAL, "eh_set_sequences: lead_time %d", lead_time);
-    if (n_windows < 0 || n_windows > 0x7fffffffLL || (n_windows > 0 && !starts)) return fail(h, EH_EINVAL, "eh_set_sequences: n_windows = %lld", (long long)n_windows);
-    EhSplit& sp = h->split[split];
-    if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "eh_set_sequences: no data set for this split (call eh_set_data first)");
-    const long long last = sp.n - input_window - lead_time;      // (every row a window reads -- inputs, forcings, targets -- lies inside the series)
-    for (int64_t i = 0; i < n_windows; ++i)
-        if (starts[i] < 0 || starts[i] > last) return fail(h, EH_EINVAL, "eh_set_sequences: starts[%lld] = %d outside 0..%lld (series of %lld rows, input_window %d, lead_time %d)", (long long)i, starts[i], last, sp.n, input_window, lead_time);
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(sp.starts);
-    sp.starts = nullptr; sp.nwin = 0;
-    if (split == EH_SPLIT_TRAIN) h->perm_valid = false;
-    HIPCHK(h, hipMalloc(&sp.starts, (size_t)std::max<int64_t>(n_windows, 1) * sizeof(int)));
-    if (n_windows > 0) HIPCHK(h, hipMemcpy(sp.starts, starts, (size_t)n_windows * sizeof(int), hipMemcpyHostToDevice));
-    sp.nwin = n_windows; sp.W = input_window; sp.ow = output_window; sp.lam = lead_time;
-    return EH_OK;
-}
-
 int32_t eh_set_params(eh_handle* h, const float* theta, int64_t n) {
     if (!h || !theta) return EH_EINVAL;
     if (n != h->net.n_theta) return fail(h, EH_EINVAL, "eh_set_params: n = %lld, model has %d", (long long)n, h->net.n_theta);
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (int rc = copy_in(h, TH(h), theta, (size_t)n)) return rc;
+    if (int rc = eh_copy_in(h, TH(h), theta, (size_t)n)) return rc;
     hipLaunchKernelGGL(eh_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, TH(h), (int)n, h->img);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1595,13 +1398,41 @@ int32_t eh_get_params(eh_handle* h, float* theta, int64_t n) {
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    return copy_out(h, theta, TH(h), (size_t)n);
+    return eh_copy_out(h, theta, TH(h), (size_t)n);
 }
 
 }   // extern "C"
 
 // ---- internal launch helpers ---------------------------------------------------------------------
-static int ensure_events(eh_handle* h, size_t need);
+static int ensure_events(eh_handle* h, size_t need) {
+    while (h->ev.size() < need) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    return EH_OK;
+}
+// eh_profile_enable: three events per bracket -- before the step kernel, between it and the reduction, after -- around every step, or
+// (stride S > 1) around every burst of S consecutive steps, the middle one then at the burst's end.  prof_begin in front of a step's
+// first launch, prof_end behind its last; mid_marked: the caller has recorded the middle event itself (eh_do_step, stride 1)
+struct EhProf { bool on, burst, last; };
+static int prof_begin(eh_handle* h, EhProf* p) {
+    p->on = h->prof && h->ev_used + 3 <= 3 * 8192;
+    p->burst = h->prof_stride > 1;
+    p->last = h->prof_k % h->prof_stride == h->prof_stride - 1;
+    if (!p->on) return EH_OK;
+    if (int rc = ensure_events(h, h->ev_used + 3)) return rc;
+    if (h->prof_k % h->prof_stride == 0) HIPCHK(h, hipEventRecord(h->ev[h->ev_used], h->stream));
+    h->prof_k++;
+    return EH_OK;
+}
+static int prof_end(eh_handle* h, const EhProf& p, bool mid_marked) {
+    if (!p.on || !p.last) return EH_OK;
+    if (!mid_marked) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 2], h->stream));
+    h->ev_used += 3;
+    return EH_OK;
+}
 static int grid_for(const eh_handle* h, long long count) {
     const EhVariant& v = h->arch->var[h->variant];
     const long long mt = 16LL * v.nt;
@@ -1628,9 +1459,29 @@ static int eval_grid_for(const eh_handle* h, long long count) {
     return (int)std::max<long long>(std::max<long long>(1, floor), std::min<long long>((ntiles + per - 1) / per, cap));
 }
 
+// per-target weights of the minibatch (1 / n_t, 1 / sum (y - ybar)^2) -> inv_n; tcount (eh_dp_counts): the shard's raw sums as well
+int eh_launch_count(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* tcount) {
+    const EhNet& net = h->net;
+    hipLaunchKernelGGL(eh_count_kernel, dim3(net.T), dim3(256), 0, h->stream, sp.recs, h->C, net.P + net.F, net.T, idx, first, count, h->inv_n, net.loss_t, sp.shift4(), h->img.agg_a, h->roles, h->img.l2s, tcount);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+// two-pass losses: `nrows` rows of moment sums about the shift (the slab of a forward-only pass, or the all-reduced EH_BUF_MOMENT) -> the
+// centre of yhat; the rows of the pass about that centre -> k0 k1 k2 and the loss value of every two-pass target, all in inv_n
+int eh_launch_moment_centre(eh_handle* h, const EhSplit& sp, const float* rows, int nrows) {
+    hipLaunchKernelGGL(eh_moment_centre_kernel, dim3(h->net.T), dim3(64), 0, h->stream, rows, nrows, h->net.T, h->net.loss_t, sp.shift4(), h->inv_n);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+int eh_launch_moment_coef(eh_handle* h, const EhSplit& sp, const float* rows, int nrows) {
+    hipLaunchKernelGGL(eh_moment_coef_kernel, dim3(h->net.T), dim3(64), 0, h->stream, rows, nrows, h->net.T, h->net.loss_t, sp.shift4(), h->inv_n, h->img.agg_a);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+
 // input BatchNorm: statistics of the minibatch [first, first+count) -> a.bn_* (train-mode kernels only)
 // consume = false: a forward-only pass in front of the step's training pass (eh_dp_moments) -- the global statistics stay for the passes behind it
-static int bn_prepare(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool update, EhStepArgs* a, bool consume = true) {
+int eh_bn_prepare(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool update, EhStepArgs* a, bool consume) {
     a->bn_part = nullptr; a->bn_nblk = 0; a->bn_update = 0; a->bn_run = h->bn_run; a->image_out = h->image;
     a->bn_c = nullptr; a->bn_n = nullptr;
     if (!h->bn_on) return EH_OK;
@@ -1652,222 +1503,6 @@ static int bn_prepare(eh_handle* h, const EhSplit& sp, const int* idx, long long
     return EH_OK;
 }
 
-// ---- layer-wise execution form (eh_lform.hpp) ---------------------------------------------------------------------------
-struct EhLWs { float *Xb, *H[EH_MAX_NETS][EH_MAX_HIDDEN], *Z[EH_MAX_NETS][EH_MAX_HIDDEN], *D[2], *O, *part; long long ldo; };
-static long long lform_floats_per_sample(const eh_handle* h) {
-    long long w = h->net.P + 16, maxw = 0;
-    for (int k = 0; k < h->l_nnets; ++k)
-        for (int l = 0; l + 1 < h->l_net[k].nl; ++l) {
-            w += h->l_net[k].out[l] * (h->l_net[k].lact[l] == EH_ACT_SWISH ? 2 : 1);      // swish keeps the pre-activation too
-            maxw = std::max<long long>(maxw, h->l_net[k].out[l]);
-        }
-    return w + 2 * maxw;
-}
-// an allocation would be needed while a graph is being recorded: drop the recording (the engine stays usable) and say what to do
-static int lform_alloc_in_capture(eh_handle* h, const char* what) {
-    hipGraph_t g = nullptr;
-    (void)hipStreamEndCapture(h->stream, &g);
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    h->capturing = false;
-    return fail(h, EH_ESTATE, "%s: the layer-wise form sizes this buffer at the first step that needs it -- run one step of this batch size (and training loss) "
-                              "before eh_graph_begin, then record; the recording was dropped", what);
-}
-static int lform_workspace(eh_handle* h, long long count, EhLWs* W) {
-    const long long cap_need = (count + 127) / 128 * 128;
-    if (cap_need > h->l_cap) {
-        if (h->capturing) return lform_alloc_in_capture(h, "workspace");
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->l_ws);
-        h->l_ws = nullptr; h->l_cap = 0;
-        HIPCHK(h, hipMalloc(&h->l_ws, ((size_t)cap_need * lform_floats_per_sample(h) + (size_t)4096 * EH_EVAL_STATS * EH_MAX_TARG) * sizeof(float)));
-        h->l_cap = cap_need;
-    }
-    const long long cap = h->l_cap;
-    float* p = h->l_ws;
-    long long maxw = 0;
-    W->Xb = p; p += cap * h->net.P;
-    for (int k = 0; k < h->l_nnets; ++k)
-        for (int l = 0; l + 1 < h->l_net[k].nl; ++l) {
-            const long long o = h->l_net[k].out[l];
-            maxw = std::max(maxw, o);
-            W->H[k][l] = p; p += cap * o;
-            W->Z[k][l] = nullptr;
-            if (h->l_net[k].lact[l] == EH_ACT_SWISH) { W->Z[k][l] = p; p += cap * o; }
-        }
-    W->D[0] = p; p += cap * maxw;
-    W->D[1] = p; p += cap * maxw;
-    W->O = p; p += cap * 16; W->ldo = cap;
-    W->part = p;
-    return EH_OK;
-}
-static const bool g_gemm_novec = getenv("EH_GEMM_NOVEC") != nullptr;      // (A/B switch of the measurement tools)
-// a weight gradient (A transposed, plain store) with a thin side runs as a streaming kernel (eh_thin_gemm_kernel): its arguments
-static bool lform_thin_args(const EhGemmArgs& g, bool btr, EhThinArgs* out) {
-    if (g_gemm_novec || !(g.M <= 8 || g.N <= 8) || (g.M <= 8 ? btr : !btr)) return false;
-    EhThinArgs t{};
-    t.K = g.K; t.kchunk = g.kchunk; t.C = g.C; t.c_z = g.c_zstride; t.cs_z = g.c_zstride;
-    if (g.M <= 8) {          // few inputs: wide = B (dZ [B x out]), thin = A (the layer's input [B x in])
-        t.wide = g.B; t.ldw = g.ldb; t.ncols = g.N; t.thin = g.A; t.tsb = g.lda; t.tsj = 1; t.J = g.M; t.c_col = 1; t.c_j = g.ldc; t.cs_wide = g.colsum;
-    } else {                 // few outputs, dO stored [K][ldo]: wide = A (the layer's input [B x in]), thin = B
-        t.wide = g.A; t.ldw = g.lda; t.ncols = g.M; t.thin = g.B; t.tsb = 1; t.tsj = g.ldb; t.J = g.N; t.c_col = g.ldc; t.c_j = 1; t.cs_thin = g.colsum;
-    }
-    *out = t;
-    return true;
-}
-template <bool ATR, bool BTR, int EPI>
-static void lform_gemm(eh_handle* h, const EhGemmArgs& g, int nz) {
-    const bool novec = g_gemm_novec;
-    if constexpr (EPI == EH_GEPI_STORE && ATR) {
-        EhThinArgs t;
-        if (lform_thin_args(g, BTR, &t)) {
-            hipLaunchKernelGGL(eh_thin_gemm_kernel, dim3((unsigned)((t.ncols + 63) / 64), (unsigned)nz), dim3(256), 0, h->stream, t);
-            return;
-        }
-    }
-    if (!novec && nz == 1 && g.kchunk >= g.K) {          // products with a degenerate dimension: streaming kernels (eh_lform.hpp)
-        const long long tot = (long long)g.M * g.N;
-        const unsigned sg = (unsigned)std::max<long long>(1, std::min<long long>(2048, (tot + 255) / 256));
-        if (EPI == EH_GEPI_BIAS_ACT && !ATR && !BTR && g.K <= 8) { hipLaunchKernelGGL(eh_thin_fwd_k_kernel, dim3(sg), dim3(256), 0, h->stream, g); return; }
-        if (EPI == EH_GEPI_BIAS_T && !ATR && !BTR && g.N <= 16 && g.M <= 16384) {
-            hipLaunchKernelGGL(eh_thin_fwd_n_kernel, dim3((unsigned)std::max(1, std::min(1024, (g.M + 3) / 4))), dim3(256), 0, h->stream, g);
-            return;
-        }
-        if (EPI == EH_GEPI_DACT && ATR && BTR && g.K <= 16) { hipLaunchKernelGGL(eh_thin_dact_kernel, dim3(sg), dim3(256), 0, h->stream, g); return; }
-    }
-    if constexpr (EPI == EH_GEPI_BIAS_ACT || EPI == EH_GEPI_DACT) {
-        // few rows, deep k: split-K into partial products + a combine pass (eh_splitk_combine_kernel)
-        static const bool nosplit = getenv("EH_GEMM_NOSPLIT") != nullptr;
-        static const bool nofew = getenv("EH_GEMM_NOFEWROWS") != nullptr;
-        static const int fewmax = getenv("EH_GEMM_FEWROWS_MAX") ? atoi(getenv("EH_GEMM_FEWROWS_MAX")) : 1024;
-        if constexpr (!ATR) {
-            // ... or, without the combine pass, one 16 x 16 tile per workgroup with the k range split over its waves (eh_fewrows_gemm_kernel)
-            if (!novec && !nofew && nz == 1 && g.M <= fewmax && g.K >= 64 && g.kchunk >= g.K && eh_gemm_vec_ok(g, ATR, BTR)) {
-                EhGemmArgs p = g;
-                p.kchunk = std::max(16, ((g.K + 15) / 16 + 15) / 16 * 16);         // <= 16 slices of whole 16-deep groups
-                const int nw = (g.K + p.kchunk - 1) / p.kchunk;
-                static const int few32 = getenv("EH_GEMM_FEW32_MIN") ? atoi(getenv("EH_GEMM_FEW32_MIN")) : 512;       // rows from which the 32 x 32 tile runs
-                if (g.M >= few32) hipLaunchKernelGGL((eh_fewrows32_gemm_kernel<BTR, EPI>), dim3((unsigned)((g.N + 31) / 32), (unsigned)((g.M + 31) / 32)), dim3(64u * (unsigned)nw), 0, h->stream, p);
-                else {
-                    hipLaunchKernelGGL((eh_fewrows_gemm_kernel<BTR, EPI>), dim3((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16)), dim3(64u * (unsigned)nw), 0, h->stream, p);
-                    if (p.job_part) h->l_job_done = true;      // (the one product kernel that takes the side job, EhGemmArgs::job_part)
-                }
-                return;
-            }
-        }
-        if (!novec && !nosplit && nz == 1 && g.M <= 256 && g.K >= 128 && g.kchunk >= g.K && eh_gemm_vec_ok(g, ATR, BTR)) {
-            int kc = std::max(32, ((g.K + 15) / 16 + 15) / 16 * 16);          // ~16 parts, whole 16-deep steps
-            const int ns = (g.K + kc - 1) / kc;
-            const size_t need = (size_t)ns * g.M * g.N;
-            if (ns > 1) {
-                if (need > h->l_split_cap && !h->capturing) {      // (while a graph is being recorded: no allocation -- the tiled kernel below runs instead)
-                    if (hipStreamSynchronize(h->stream) == hipSuccess) { (void)hipFree(h->l_split); h->l_split = nullptr; h->l_split_cap = 0; }
-                    if (hipMalloc(&h->l_split, need * sizeof(float)) == hipSuccess) h->l_split_cap = need; else (void)hipGetLastError();
-                }
-                if (need <= h->l_split_cap) {
-                    EhGemmArgs p = g;
-                    p.C = h->l_split; p.ldc = g.N; p.c_zstride = (long long)g.M * g.N; p.kchunk = kc; p.colsum = nullptr; p.bias = nullptr; p.H = nullptr; p.Z = nullptr;
-                    const dim3 g64((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64), (unsigned)ns);
-                    hipLaunchKernelGGL((eh_gemm_kernel<ATR, BTR, EH_GEPI_STORE, true, 64>), g64, dim3(256), 0, h->stream, p);
-                    const long long tot = (long long)g.M * g.N;
-                    hipLaunchKernelGGL(eh_splitk_combine_kernel, dim3((unsigned)std::max<long long>(1, std::min<long long>(1024, (tot + 255) / 256))), dim3(256), 0, h->stream,
-                                       h->l_split, ns, (int)EPI, g);
-                    return;
-                }
-            }
-        }
-    }
-    const dim3 grid((unsigned)((g.N + 127) / 128), (unsigned)((g.M + 127) / 128), (unsigned)nz);
-    const bool vec = !novec && eh_gemm_vec_ok(g, ATR, BTR);
-    static const long long t128_min = getenv("EH_GEMM_T128_MIN") ? atoll(getenv("EH_GEMM_T128_MIN")) : 2048;
-    if (vec && (long long)grid.x * grid.y * grid.z < t128_min) {      // fewer 128 x 128 tiles than CUs: 64 x 64 ones (four times the workgroups, a quarter of the work each)
-        const dim3 grid64((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64), (unsigned)nz);
-        hipLaunchKernelGGL((eh_gemm_kernel<ATR, BTR, EPI, true, 64>), grid64, dim3(256), 0, h->stream, g);
-        return;
-    }
-    if (vec) hipLaunchKernelGGL((eh_gemm_kernel<ATR, BTR, EPI, true>), grid, dim3(256), 0, h->stream, g);
-    else hipLaunchKernelGGL((eh_gemm_kernel<ATR, BTR, EPI, false>), grid, dim3(256), 0, h->stream, g);
-}
-// minibatch -> Xb (input BatchNorm applied), forward through every Dense layer; O^T [K][ldo] = the raw NN outputs
-// (lstop >= 0: a one-network model, only its layers below `lstop` run here -- the rest belongs to eh_lform_tailchain_kernel)
-static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool train_mode, bool bn_update, const EhLWs& W, int lstop = -1) {
-    const EhNet& net = h->net;
-    const int B = (int)count;
-    if (h->l_nnets == 0) return EH_OK;        // no network (no neural parameter): the mechanistic stage reads the records itself
-    EhStepArgs bn{};
-    // (small minibatches: the prep kernel takes the batch statistics itself -- one dependent launch fewer)
-    static const bool nofuse = getenv("EH_LFORM_NOFUSE") != nullptr;
-    const bool bn_self = train_mode && h->bn_on && !h->bn_ext && count > 0 && count <= 256 && !nofuse;
-    if (train_mode && !bn_self) { if (int rc = bn_prepare(h, sp, idx, first, count, bn_update, &bn)) return rc; }
-    EhLPrepArgs pa{};
-    pa.recs = sp.recs; pa.C = h->C; pa.P = net.P; pa.idx = idx; pa.first = first; pa.count = B; pa.Xb = W.Xb; pa.meta = h->image;
-    pa.bn_part = bn.bn_part; pa.bn_nblk = bn.bn_nblk; pa.bn_c = bn.bn_c; pa.bn_n = bn.bn_n; pa.bn_update = bn.bn_update; pa.bn_run = h->bn_run;
-    if (bn_self) { pa.bn_self = 1; pa.bn_update = bn_update ? 1 : 0; }
-    static const bool stamp_first = getenv("EH_STAMP_FIRST") != nullptr;      // (diagnostic builds: the stamps of the first launch instead of the chain kernel's)
-    pa.stamps = stamp_first ? h->stamps : nullptr;
-    const long long tot = (long long)B * net.P;
-    const float* theta = TH(h);
-    // Few rows: minibatch matrix + BatchNorm + first layer + the SECOND layer's few-rows product as one launch (eh_fewrows_first_kernel) where
-    // the second layer is a hidden layer that would run eh_fewrows_gemm_kernel anyway
-    bool fused01 = false;
-    {
-        static const bool nofirst = getenv("EH_LFORM_NOFIRST") != nullptr;
-        static const bool nofew = getenv("EH_GEMM_NOFEWROWS") != nullptr;
-        static const int first_maxb = getenv("EH_LFORM_FIRST_MAXB") ? atoi(getenv("EH_LFORM_FIRST_MAXB")) : 64;   // every workgroup takes the statistics itself: a loss from ~128 rows up
-        const eh_handle_s::LNet& L0 = h->l_net[0];
-        const int stop = lstop >= 0 ? lstop : L0.nl;
-        auto al16 = [](const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; };
-        if (!nofirst && !nofuse && !nofew && !g_gemm_novec && L0.nl >= 3 && stop >= 2 && L0.in[0] <= 4 && B >= 1 && B <= first_maxb &&
-            L0.out[0] >= 64 && (L0.out[0] % 16) == 0 && (L0.out[1] % 4) == 0 &&
-            al16(theta + L0.woff[0]) && al16(theta + L0.boff[0]) && al16(theta + L0.woff[1])) {
-            EhGemmArgs f{};
-            f.lda = net.P; f.B = theta + L0.woff[0]; f.ldb = L0.out[0]; f.M = B; f.N = L0.out[0]; f.K = L0.in[0]; f.kchunk = f.K;
-            f.bias = theta + L0.boff[0]; f.act = L0.lact[0]; f.C = W.H[0][0]; f.ldc = L0.out[0]; f.Z = W.Z[0][0];
-            EhGemmArgs g{};
-            g.A = nullptr; g.lda = L0.in[1]; g.B = theta + L0.woff[1]; g.ldb = L0.out[1];
-            g.M = B; g.N = L0.out[1]; g.K = L0.in[1]; g.c_zstride = 0;
-            g.bias = theta + L0.boff[1]; g.act = L0.lact[1]; g.C = W.H[0][1]; g.ldc = L0.out[1]; g.Z = W.Z[0][1];
-            g.kchunk = std::max(16, ((g.K + 15) / 16 + 15) / 16 * 16);         // <= 16 slices of whole 16-deep groups (lform_gemm's few-rows rule)
-            const int nwv = (g.K + g.kchunk - 1) / g.kchunk;
-            if (f.K <= 2) hipLaunchKernelGGL((eh_fewrows_first_kernel<EH_GEPI_BIAS_ACT, 2>), dim3((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16)), dim3(64u * (unsigned)nwv), 0, h->stream, pa, f, g, L0.c0);
-            else hipLaunchKernelGGL((eh_fewrows_first_kernel<EH_GEPI_BIAS_ACT, 4>), dim3((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16)), dim3(64u * (unsigned)nwv), 0, h->stream, pa, f, g, L0.c0);
-            HIPCHK(h, hipGetLastError());
-            fused01 = true;
-        }
-    }
-    // the first network's first layer rides along when it is one of the few-predictor products (K <= 8, hidden layer behind it)
-    bool fused0 = false;
-    if (!fused01) {
-        const eh_handle_s::LNet& L0 = h->l_net[0];
-        if (!nofuse && !g_gemm_novec && L0.nl >= 2 && L0.in[0] <= 8 && lstop != 0) {
-            EhGemmArgs g{};
-            g.A = nullptr; g.lda = net.P; g.B = theta + L0.woff[0]; g.ldb = L0.out[0];
-            g.M = B; g.N = L0.out[0]; g.K = L0.in[0]; g.kchunk = g.K; g.bias = theta + L0.boff[0]; g.act = L0.lact[0];
-            g.C = W.H[0][0]; g.ldc = L0.out[0]; g.Z = W.Z[0][0];
-            const long long totc = (long long)g.M * g.N;
-            hipLaunchKernelGGL((eh_lform_prep_kernel<true>), dim3((unsigned)std::max<long long>(1, std::min<long long>(2048, (std::max(tot, totc) + 255) / 256))), dim3(256), 0, h->stream, pa, g, L0.c0);
-            fused0 = true;
-        }
-    }
-    if (!fused0 && !fused01) hipLaunchKernelGGL((eh_lform_prep_kernel<false>), dim3((unsigned)std::max<long long>(1, std::min<long long>(1024, (tot + 255) / 256))), dim3(256), 0, h->stream, pa, EhGemmArgs{}, 0);
-    HIPCHK(h, hipGetLastError());
-    for (int k = 0; k < h->l_nnets; ++k) {
-        const eh_handle_s::LNet& L = h->l_net[k];
-        for (int l = 0; l < (lstop >= 0 ? lstop : L.nl); ++l) {
-            if ((fused0 || fused01) && k == 0 && l == 0) continue;
-            if (fused01 && k == 0 && l == 1) continue;
-            EhGemmArgs g{};
-            g.A = l == 0 ? W.Xb + L.c0 : W.H[k][l - 1]; g.lda = l == 0 ? net.P : L.in[l];      // (a network's predictors: its columns of the minibatch matrix)
-            g.B = theta + L.woff[l]; g.ldb = L.out[l];                   // canonical (out, in) column-major == [in][out] row-major
-            g.M = B; g.N = L.out[l]; g.K = L.in[l]; g.kchunk = g.K; g.c_zstride = 0;
-            g.bias = theta + L.boff[l]; g.act = L.lact[l];
-            if (l + 1 < L.nl) { g.C = W.H[k][l]; g.ldc = L.out[l]; g.Z = W.Z[k][l]; lform_gemm<false, false, EH_GEPI_BIAS_ACT>(h, g, 1); }
-            else { g.C = W.O + (long long)L.orow * W.ldo; g.ldc = W.ldo; lform_gemm<false, false, EH_GEPI_BIAS_T>(h, g, 1); }
-            HIPCHK(h, hipGetLastError());
-        }
-    }
-    return EH_OK;
-}
 // targets whose training loss takes two forward passes ahead of the training pass (batch statistics of yhat): bit t
 static unsigned two_pass_mask(const EhNet& net) {
     unsigned m = 0;
@@ -1878,303 +1513,6 @@ static unsigned two_pass_mask(const EhNet& net) {
     return m;
 }
 unsigned eh_two_pass_mask(const eh_handle* h) { return two_pass_mask(h->net); }
-// one training step's gradient sums into `rows` partial slab rows (the contract of the fused step kernels: eh_reduce_kernel follows)
-static int lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* rows_out, bool bn_update) {
-    const EhNet& net = h->net;
-    EhLWs W;
-    if (int rc = lform_workspace(h, std::max<long long>(count, 1), &W)) return rc;
-    const int B = (int)count;
-    // slab rows = sample chunks the weight-gradient products are split over (their only source of parallelism beyond the tiles of the
-    // weight matrix itself): >= EH_LFORM_CHUNK samples each, at most EH_LFORM_ROWS of them
-    static const long long lchunk = getenv("EH_LFORM_CHUNK") ? std::max(64, atoi(getenv("EH_LFORM_CHUNK"))) : 128;
-    const int rows = (int)std::max<long long>(1, std::min<long long>(EH_LFORM_ROWS, (count + lchunk - 1) / lchunk));
-    const int chunk = std::max(16, (int)(((count + rows - 1) / rows + 15) / 16 * 16));
-    *rows_out = rows;
-    if (net.T > 1 && !h->dp_weights) {        // (data-parallel step: eh_dp_grad has just filled inv_n with the weights of the GLOBAL batch)
-        EhShift4 sh4; for (int t = 0; t < EH_MAX_TARG; ++t) sh4.c[t] = sp.shift[t];
-        hipLaunchKernelGGL(eh_count_kernel, dim3(net.T), dim3(256), 0, h->stream, sp.recs, h->C, net.P + net.F, net.T, idx, first, count, h->inv_n, net.loss_t, sh4, h->img.agg_a, h->roles, h->img.l2s);
-        HIPCHK(h, hipGetLastError());
-    }
-    if (count <= 0) {                          // nothing to do: an all-zero partial (the reduce kernel then skips the update)
-        HIPCHK(h, hipMemsetAsync(h->slab, 0, (size_t)h->n_acc * sizeof(float), h->stream));
-        return EH_OK;
-    }
-    const unsigned tpm = two_pass_mask(net);
-    // Small minibatches: every layer's delta is kept (l_dk), the chain of delta products runs first and the weight gradients -- a
-    // handful of tiles each, 4-6 us per dependent launch -- follow as ONE grouped launch of the tiled ones and one of the thin ones.
-    static const long long lgroup_max = getenv("EH_LFORM_GROUP_MAX") ? atoll(getenv("EH_LFORM_GROUP_MAX")) : 4096;
-    bool grouped = count <= lgroup_max && h->l_nnets > 0;
-    long long dk_floats = 0;
-    // (sized by THIS minibatch, rounded up to a power of two -- not by the largest one the path serves: a B = 64 step of a deep, wide
-    //  MultiNN model used to ask for up to the 1 GiB cap; advisor, round 3.  A larger batch later re-grows it, outside a capture.)
-    long long dk_rows = 64;
-    while (dk_rows < count) dk_rows *= 2;
-    if (grouped) {
-        for (int k = 0; k < h->l_nnets; ++k)
-            for (int l = 0; l + 1 < h->l_net[k].nl; ++l) dk_floats += dk_rows * h->l_net[k].out[l];
-        if (dk_floats > (1ll << 28)) { grouped = false; h->jit_log = "layer-wise form: kept deltas of this minibatch exceed 1 GiB -- weight gradients run layer by layer (slower small-batch steps)"; }
-        else if ((size_t)dk_floats > h->l_dk_cap) {
-            if (h->capturing) return lform_alloc_in_capture(h, "kept deltas");
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(h->l_dk); h->l_dk = nullptr; h->l_dk_cap = 0;
-            if (hipMalloc(&h->l_dk, (size_t)dk_floats * sizeof(float)) == hipSuccess) h->l_dk_cap = (size_t)dk_floats;
-            else { (void)hipGetLastError(); grouped = false; h->jit_log = "layer-wise form: no memory for the kept deltas of the grouped small-batch path -- weight gradients run layer by layer (slower small-batch steps)"; }
-        }
-    }
-    // Few rows, one network: the narrow end of the network -- every layer from `tail_s` on, the mechanistic stage and the deltas back
-    // down to layer tail_s - 1 -- is ONE launch with a workgroup per row (eh_lform_tailchain_kernel, eh_lform.hpp)
-    static const bool notail = getenv("EH_LFORM_NOTAIL") != nullptr;
-    int tail_s = -1;
-    // (a workgroup per ROW up to 256 rows: every CU streams the suffix's weights once whatever the number of rows -- 57.5 / 61.3 / 70.1 / 77.5 us
-    //  per step at 96 / 128 / 192 / 256 rows against 70.9 / 74.2 / 80.1 / 86.6 with the products launched one by one.  With FOUR rows per
-    //  workgroup, the form of the round's first half for more than 64 rows, it was slower than either: 75.5 / 78.6 / 90.2 / 96.7; those
-    //  instantiations are gone.)
-    if (!notail && grouped && h->l_nnets == 1 && count <= 256 && !tpm && !g_gemm_novec) {
-        const eh_handle_s::LNet& L = h->l_net[0];
-        long long wsum = 0;
-        for (int l = L.nl - 1; l >= 0; --l) {
-            if (L.in[l] > (int)EH_LTAIL_MAXW || L.out[l] > (int)EH_LTAIL_MAXW || wsum + (long long)L.in[l] * L.out[l] > (96ll << 10)) break;
-            wsum += (long long)L.in[l] * L.out[l];
-            tail_s = l;
-        }
-    }
-    if (int rc = lform_forward(h, sp, idx, first, count, true, bn_update, W, tail_s)) return rc;
-    EhStepArgs a{};
-    a.prog = h->prog; a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = count; a.stamps = (getenv("EH_STAMP_DW") || getenv("EH_STAMP_FIRST")) ? nullptr : h->stamps;
-    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
-    if (tpm) {
-        // losses that need batch statistics of yhat (see launch_train_kernel): the NN outputs O stay where the forward left them, so
-        // the two statistics passes are two runs of the mechanistic stage alone (eval form), not two forwards
-        EhStepArgs e = a;
-        e.inv_n = nullptr; e.yld = count;
-        const int egrid = (int)std::min<long long>(256, (count + 255) / 256);
-        EhLMechArgs me{W.O, W.ldo, h->slab};                   // [egrid][EH_EVAL_STATS * T] (the slab is rewritten by the training pass afterwards)
-        EhShift4 s4; for (int t = 0; t < EH_MAX_TARG; ++t) s4.c[t] = sp.shift[t];
-        for (int pass = 0; pass < 2; ++pass) {
-            if (net.mech == EH_MECH_PROGRAM) hipLaunchKernelGGL((eh_lform_mech_kernel<false, true>), dim3(egrid), dim3(256), 0, h->stream, net, e, me, h->image);
-            else hipLaunchKernelGGL((eh_lform_mech_kernel<false, false>), dim3(egrid), dim3(256), 0, h->stream, net, e, me, h->image);
-            HIPCHK(h, hipGetLastError());
-            if (pass == 0) hipLaunchKernelGGL(eh_moment_centre_kernel, dim3(net.T), dim3(64), 0, h->stream, h->slab, egrid, net.T, net.loss_t, s4, h->inv_n);
-            else hipLaunchKernelGGL(eh_moment_coef_kernel, dim3(net.T), dim3(64), 0, h->stream, h->slab, egrid, net.T, net.loss_t, s4, h->inv_n, h->img.agg_a);
-            HIPCHK(h, hipGetLastError());
-            e.inv_n = h->inv_n;
-        }
-    }
-    a.inv_n = (net.T > 1 || tpm) ? h->inv_n : nullptr;
-    // recorded loss functions: no kernel is compiled at run time in this form -- the mechanistic kernel interprets their tapes
-    bool lprog = false;
-    for (int t = 0; t < net.T; ++t) lprog = lprog || ((net.loss_t >> (4 * t)) & 15u) == (unsigned)EH_LOSS_PROGRAM;
-    if (lprog) {
-        if (h->l_lprog_gen != h->loss_prog.gen) {
-            if (h->capturing) return lform_alloc_in_capture(h, "recorded loss programs");
-            std::vector<unsigned> img((size_t)EH_MAX_TARG * EH_LPROG_WORDS, 0u);
-            for (int t = 0; t < net.T; ++t) {
-                if (!h->loss_prog.has(t)) continue;
-                const EhLossProg1& lp = h->loss_prog.of(t);
-                unsigned* q = img.data() + (size_t)t * EH_LPROG_WORDS;
-                q[0] = (unsigned)lp.code.size(); q[1] = 1u; q[2] = (unsigned)lp.out;
-                for (size_t k = 0; k < lp.consts.size() && k < (size_t)EH_MAX_PROG_CONST; ++k) memcpy(&q[8 + k], &lp.consts[k], sizeof(float));
-                for (size_t i = 0; i < lp.code.size() && i < (size_t)EH_MAX_PROG; ++i) q[24 + i] = lp.code[i];
-            }
-            if (!h->l_lprog) HIPCHK(h, hipMalloc(&h->l_lprog, img.size() * sizeof(unsigned)));
-            HIPCHK(h, hipStreamSynchronize(h->stream));          // (steps in flight read the old programs)
-            HIPCHK(h, hipMemcpy(h->l_lprog, img.data(), img.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-            h->l_lprog_gen = h->loss_prog.gen;
-        }
-        a.lprog = h->l_lprog;
-    }
-    EhLMechArgs m{W.O, W.ldo, W.part, nullptr, 0, 0};
-    const int mgrid = (int)std::min<long long>(2048, (count + 255) / 256);
-    static const bool nofuse = getenv("EH_LFORM_NOFUSE") != nullptr;
-    if (mgrid == 1 && !nofuse) { m.slab = h->slab; m.nrows = rows; m.n_acc = (long long)h->n_acc; }      // one workgroup: it writes the slab's tail columns itself
-    EhLTailJob tjob{nullptr, 0, nullptr, 0, 0};
-    if (tail_s >= 0) {
-        const eh_handle_s::LNet& L = h->l_net[0];
-        const float* theta = TH(h);
-        EhLTailArgs t{};
-        t.nl = L.nl - tail_s;
-        // dZ_l of the hidden layers where the grouped weight gradients will look for them (the order of the backward loop below: from the top)
-        float* dptr[EH_MAX_HIDDEN + 1] = {nullptr};
-        { float* q = h->l_dk; for (int l = L.nl - 1; l >= 1; --l) { dptr[l - 1] = q; q += dk_rows * L.in[l]; } }
-        int wmax = 4;
-        for (int j = 0; j < t.nl; ++j) {
-            const int l = tail_s + j;
-            EhLTailLayer& T = t.L[j];
-            T.W = theta + L.woff[l]; T.b = theta + L.boff[l]; T.in = L.in[l]; T.out = L.out[l]; T.act = L.lact[l];
-            T.vec = ((reinterpret_cast<unsigned long long>(T.W) & 15ull) == 0 && (T.out & 3) == 0) ? 1 : 0;
-            const bool hidden = l + 1 < L.nl;
-            T.H = hidden ? W.H[0][l] : nullptr; T.Z = hidden ? W.Z[0][l] : nullptr; T.D = hidden ? dptr[l] : nullptr;
-            eh_ltail_geometry(T);
-            if (hidden && T.act == EH_ACT_SWISH) t.any_swish = 1;
-            wmax = std::max(wmax, std::max(T.in, T.out));
-        }
-        (void)wmax;
-        t.wmax = (int)EH_LTAIL_MAXW;        // (rows of EH_LTAIL_MAXW + EH_LTAIL_PAD floats whatever the widths: a product reads on past a row's width into zeros, up to the next power of two)
-        t.Hin = tail_s == 0 ? W.Xb + L.c0 : W.H[0][tail_s - 1]; t.ldin = tail_s == 0 ? net.P : L.in[tail_s];
-        t.act_below = tail_s > 0 ? L.lact[tail_s - 1] : EH_ACT_IDENTITY;
-        t.Zin = (tail_s > 0 && t.act_below == EH_ACT_SWISH) ? W.Z[0][tail_s - 1] : nullptr;
-        if (t.Zin) t.any_swish = 1;
-        t.Dbelow = tail_s > 0 ? dptr[tail_s - 1] : nullptr;
-        t.O = W.O + (long long)L.orow * W.ldo; t.ldo = W.ldo; t.part = W.part;
-        const int R = 1;
-        const int tgrid = (int)((count + R - 1) / R);
-        const size_t lds0 = eh_ltail_lds_bytes(R, t.nl, t.wmax, t.any_swish != 0);
-        const bool mp = net.mech == EH_MECH_PROGRAM;
-        const void* fn = lprog ? (mp ? (const void*)&eh_lform_tailchain_kernel<1, true, true> : (const void*)&eh_lform_tailchain_kernel<1, false, true>)
-                               : (mp ? (const void*)&eh_lform_tailchain_kernel<1, true, false> : (const void*)&eh_lform_tailchain_kernel<1, false, false>);
-        // one or two hidden layers + the output layer whose weights fit the threads' registers: they stay there for the delta products (eh_lform_tailkeep_kernel)
-        static const bool nokeep = getenv("EH_LFORM_NOKEEP") != nullptr;
-        int trf = 0;
-        const bool keep = !nokeep && R == 1 && eh_ltail_keep_ok(t, (int)count, &trf);
-        size_t lds = lds0;
-        if (keep) {
-            lds = lds0 + ((size_t)trf + 8) * sizeof(float);
-            fn = lprog ? (mp ? (const void*)&eh_lform_tailkeep_kernel<true, true> : (const void*)&eh_lform_tailkeep_kernel<false, true>)
-                       : (mp ? (const void*)&eh_lform_tailkeep_kernel<true, false> : (const void*)&eh_lform_tailkeep_kernel<false, false>);
-        }
-        if (lds > EH_LDS_LIMIT) return fail(h, EH_EUNSUPPORTED, "layer-wise form: %zu bytes of LDS for the tail chain", lds);
-        bool& prepared = h->l_tail_fn[(keep ? 8 : 0) + (lprog ? 2 : 0) + (mp ? 1 : 0)];      // (per handle = per device)
-        if (!prepared) { HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EH_LDS_LIMIT)); prepared = true; }
-        void* kargs[] = {(void*)&net, (void*)&a, (void*)&t, (void*)&h->image};
-        HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)tgrid), dim3(EH_LTAIL_THREADS), kargs, lds, h->stream));
-        tjob = EhLTailJob{W.part, tgrid, h->slab, rows, (long long)h->n_acc};
-    } else
-    if (lprog) {
-        if (net.mech == EH_MECH_PROGRAM) hipLaunchKernelGGL((eh_lform_mech_kernel<true, true, true>), dim3(mgrid), dim3(256), 0, h->stream, net, a, m, h->image);
-        else hipLaunchKernelGGL((eh_lform_mech_kernel<true, false, true>), dim3(mgrid), dim3(256), 0, h->stream, net, a, m, h->image);
-    }
-    else if (net.mech == EH_MECH_PROGRAM) hipLaunchKernelGGL((eh_lform_mech_kernel<true, true>), dim3(mgrid), dim3(256), 0, h->stream, net, a, m, h->image);
-    else hipLaunchKernelGGL((eh_lform_mech_kernel<true, false>), dim3(mgrid), dim3(256), 0, h->stream, net, a, m, h->image);
-    HIPCHK(h, hipGetLastError());
-    if (!m.slab && tail_s < 0) {
-        hipLaunchKernelGGL(eh_lform_tail_kernel, dim3(1), dim3(256), 0, h->stream, W.part, mgrid, net, h->slab, rows, (long long)h->n_acc);
-        HIPCHK(h, hipGetLastError());
-    }
-    // backward, every network from its output layer down; dZ of the output layer = its rows of d loss / d O^T, still [K][ldo]
-    const float* theta = TH(h);
-    EhGemmGroup GG{}; EhThinGroup TG{};
-    float* tot_job = nullptr;              // where a delta product's side job leaves the sums of the chain's partial rows (only the few-rows product kernel takes the job: l_job_done)
-    h->l_job_done = false;
-    bool all_grouped = true;               // every weight-gradient product of the step sits in GG / TG (none launched on its own, no group flushed early)
-    auto flush_tiled = [&]() {
-        if (GG.n > 0) hipLaunchKernelGGL((eh_gemm_group_kernel<true, false, EH_GEPI_STORE, true, 64>), dim3((unsigned)GG.t0[GG.n]), dim3(256), 0, h->stream, GG);
-        GG.n = 0;
-    };
-    auto flush_thin = [&]() {
-        if (TG.n > 0) hipLaunchKernelGGL(eh_thin_gemm_group_kernel, dim3((unsigned)TG.t0[TG.n]), dim3(256), 0, h->stream, TG);
-        TG.n = 0;
-    };
-    float* dkp = h->l_dk;
-    for (int k = 0; k < h->l_nnets; ++k) {
-        const eh_handle_s::LNet& L = h->l_net[k];
-        const float* dZ = W.O + (long long)L.orow * W.ldo;
-        bool dz_t = true;                      // dZ stored transposed ([out][B])
-        int which = 0;
-        for (int l = L.nl - 1; l >= 0; --l) {
-            const int in = L.in[l], out = L.out[l];
-            const float* Hprev = l == 0 ? W.Xb + L.c0 : W.H[k][l - 1];
-            const long long ldp = l == 0 ? net.P : in;
-            EhGemmArgs g{};                    // dW_l^T [in x out] = Hprev^T [in x B] * dZ_l [B x out], split over the samples
-            g.A = Hprev; g.lda = ldp; g.B = dZ; g.ldb = dz_t ? W.ldo : out;
-            g.C = h->slab + L.woff[l]; g.ldc = out; g.M = in; g.N = out; g.K = B; g.kchunk = chunk; g.c_zstride = h->n_acc;
-            g.colsum = h->slab + L.boff[l];      // db_l = column sums of dZ_l, from the same tiles
-            EhThinArgs ta;
-            if (grouped && lform_thin_args(g, dz_t, &ta)) {
-                if (TG.n == EH_GEMM_GROUP) { flush_thin(); all_grouped = false; HIPCHK(h, hipGetLastError()); }
-                const int gx = (ta.ncols + 63) / 64;
-                TG.a[TG.n] = ta; TG.gx[TG.n] = gx; TG.t0[TG.n + 1] = TG.t0[TG.n] + gx * rows; ++TG.n;
-            } else if (grouped && !dz_t && eh_gemm_vec_ok(g, true, false)) {
-                if (GG.n == EH_GEMM_GROUP) { flush_tiled(); all_grouped = false; HIPCHK(h, hipGetLastError()); }
-                const int gx = (g.N + 63) / 64, gy = (g.M + 63) / 64;
-                GG.g[GG.n] = g; GG.gx[GG.n] = gx; GG.gy[GG.n] = gy; GG.t0[GG.n + 1] = GG.t0[GG.n] + gx * gy * rows; ++GG.n;
-            } else {
-                // (in grouped mode too: dZ_l stays where it is until the step ends)
-                all_grouped = false;
-                if (dz_t) lform_gemm<true, true, EH_GEPI_STORE>(h, g, rows); else lform_gemm<true, false, EH_GEPI_STORE>(h, g, rows);
-                HIPCHK(h, hipGetLastError());
-            }
-            if (l > 0) {                       // dZ_{l-1} [B x in] = (dZ_l [B x out] * W_l [out x in]) .* act'(H_{l-1})  (swish: act' from the stored Z_{l-1})
-                EhGemmArgs b{};
-                b.A = dZ; b.lda = dz_t ? W.ldo : out; b.B = theta + L.woff[l]; b.ldb = out;        // W_l element (k = out, n = in) at n * out + k
-                float* const dnext = grouped ? dkp : W.D[which];
-                if (grouped) dkp += dk_rows * in;
-                if (!(tail_s >= 0 && l >= tail_s)) {      // (the tail chain has left this delta where the weight gradients look for it)
-                    if (tjob.part && !h->l_job_done && h->l_apply && rows == 1) {      // (its first workgroup also adds up the chain's rows of partial sums: eh_dw_apply_kernel finds them ready)
-                        b.job_part = tjob.part; b.job_nblk = tjob.nblk; b.job_out = W.part + (size_t)2048 * EH_LMECH_PART;
-                        tot_job = b.job_out;
-                    }
-                    b.C = dnext; b.ldc = in; b.M = B; b.N = in; b.K = out; b.kchunk = out; b.c_zstride = 0;
-                    b.H = L.lact[l - 1] == EH_ACT_SWISH ? W.Z[k][l - 1] : W.H[k][l - 1]; b.ldh = in; b.act = L.lact[l - 1];
-                    if (dz_t) lform_gemm<true, true, EH_GEPI_DACT>(h, b, 1); else lform_gemm<false, true, EH_GEPI_DACT>(h, b, 1);
-                    HIPCHK(h, hipGetLastError());
-                }
-                dZ = dnext; dz_t = false; which ^= 1;
-            }
-        }
-    }
-    static const bool nodwmerge = getenv("EH_LFORM_NODWMERGE") != nullptr;
-    static const bool noapply = getenv("EH_LFORM_NOAPPLY") != nullptr;
-    if (h->l_apply && !noapply && tjob.part && all_grouped && rows == 1) {
-        // one slab row: the products ARE the gradient -- the optimiser runs in their epilogues (eh_dw_apply_kernel), no reduce launch behind them
-        EhLApply ap = *h->l_apply;
-        ap.slab = h->slab; ap.part = tjob.part; ap.nblk = tjob.nblk; ap.tot = h->l_job_done ? tot_job : nullptr;
-        static const bool stamp_dw = getenv("EH_STAMP_DW") != nullptr;      // (diagnostic builds: the stamps of this launch instead of the chain kernel's)
-        ap.stamps = stamp_dw ? h->stamps : nullptr;
-        ap.stamp_wg = stamp_dw ? atoi(getenv("EH_STAMP_DW")) : 0;
-        if (ap.stamp_wg < 0) ap.stamp_wg += TG.t0[TG.n] + GG.t0[GG.n] + 1;
-        static const bool noapply64 = getenv("EH_LFORM_NOAPPLY64") != nullptr;
-        if (B <= 64 && ap.tot && !noapply64) {       // everything requested at once, 32 x 32 tiles with the samples split over the waves (eh_dw_apply64_kernel)
-            for (int i = 0; i < GG.n; ++i) {
-                GG.gx[i] = (GG.g[i].N + 31) / 32; GG.gy[i] = (GG.g[i].M + 31) / 32;
-                GG.t0[i + 1] = GG.t0[i] + GG.gx[i] * GG.gy[i];
-            }
-            if (ap.stamp_wg < 0) ap.stamp_wg = TG.t0[TG.n] + GG.t0[GG.n];
-#ifdef EH_STAMPS
-            if (ap.stamps) { hipMemsetAsync(ap.stamps + 28, 0xff, 8, h->stream); hipMemsetAsync(ap.stamps + 30, 0, 8, h->stream); }
-#endif
-            hipLaunchKernelGGL(eh_dw_apply64_kernel, dim3((unsigned)(TG.t0[TG.n] + 8 * ((GG.t0[GG.n] + 7) / 8) + 1)), dim3(256), 0, h->stream, GG, TG, net, ap);
-        } else
-        hipLaunchKernelGGL(eh_dw_apply_kernel, dim3((unsigned)(TG.t0[TG.n] + GG.t0[GG.n] + 1)), dim3(256), 0, h->stream, GG, TG, net, ap);
-        HIPCHK(h, hipGetLastError());
-        h->l_applied = true;
-        return EH_OK;
-    }
-    if (tjob.part || (TG.n > 0 && GG.n > 0 && !nodwmerge)) {       // what is left of both groups: one launch (+ the workgroup that sums the tail chain's partial rows)
-        hipLaunchKernelGGL(eh_dw_group_kernel, dim3((unsigned)(TG.t0[TG.n] + GG.t0[GG.n] + (tjob.part ? 1 : 0))), dim3(256), 0, h->stream, GG, TG, tjob, net);
-        TG.n = 0; GG.n = 0;
-        HIPCHK(h, hipGetLastError());
-    }
-    flush_thin(); HIPCHK(h, hipGetLastError());
-    flush_tiled(); HIPCHK(h, hipGetLastError());
-    return EH_OK;
-}
-// forward + metric sums of samples [first, first+count) in chunks; per-workgroup rows of EH_EVAL_STATS * T sums land in the slab
-static int lform_eval(eh_handle* h, const EhSplit& sp, long long first, long long count, float* yhat, float* pout, int* rows_out) {
-    const EhNet& net = h->net;
-    const long long CH = 65536;
-    int rows = 0;
-    const int ncol = EH_EVAL_STATS * net.T;
-    for (long long c0 = 0; c0 < count; c0 += CH) {
-        const long long n = std::min(CH, count - c0);
-        EhLWs W;
-        if (int rc = lform_workspace(h, n, &W)) return rc;
-        if (int rc = lform_forward(h, sp, nullptr, first + c0, n, false, false, W)) return rc;
-        EhStepArgs a{};
-        a.prog = h->prog; a.recs = sp.recs; a.C = h->C; a.idx = nullptr; a.first = first + c0; a.count = n;
-        a.yhat = yhat ? yhat + c0 : nullptr; a.pout = pout ? pout + c0 : nullptr; a.yld = count;
-        for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
-        const int mgrid = (int)std::min<long long>(256, (n + 255) / 256);
-        if ((size_t)(rows + mgrid) * ncol > std::max((size_t)h->slab_rows * std::max(h->n_acc, ncol), (size_t)1 << 20)) return fail(h, EH_ENOMEM, "eh_eval: window too large for the metric rows");
-        EhLMechArgs m{W.O, W.ldo, h->slab + (size_t)rows * ncol};
-        if (net.mech == EH_MECH_PROGRAM) hipLaunchKernelGGL((eh_lform_mech_kernel<false, true>), dim3(mgrid), dim3(256), 0, h->stream, net, a, m, h->image);
-        else hipLaunchKernelGGL((eh_lform_mech_kernel<false, false>), dim3(mgrid), dim3(256), 0, h->stream, net, a, m, h->image);
-        HIPCHK(h, hipGetLastError());
-        rows += mgrid;
-    }
-    *rows_out = std::max(rows, 0);
-    return EH_OK;
-}
-
 // ---- sequence models (eh_seq.hpp) --------------------------------------------------------------------------------------------
 constexpr long long EH_SEQ_WS_CAP = 256ll << 20;      // bytes of backward workspace at most: fewer workgroups are launched when it binds
 static int seq_grid_for(const eh_handle* h, const EhSplit& sp, long long count, bool train) {
@@ -2262,13 +1600,7 @@ static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long 
     EhSeqArgs a = seq_args(h, sp, idx, first, count);
     a.ws_wave = eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow);
     const long long need = (long long)grid * EH_SEQ_NW * a.ws_wave;      // sized by the grid actually launched
-    if (need > h->seq_ws_floats) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->seq_ws);
-        h->seq_ws = nullptr; h->seq_ws_floats = 0;
-        HIPCHK(h, hipMalloc(&h->seq_ws, (size_t)need * sizeof(float)));
-        h->seq_ws_floats = need;
-    }
+    if (need > h->seq_ws_floats) { if (int rc = eh_grow(h, &h->seq_ws, &h->seq_ws_floats, need)) return rc; }
     a.ws = h->seq_ws;
     *grid_out = grid;
     HIPCHK(h, seq_launch(h, EH_SEQ_TRAIN, grid, a));
@@ -2288,41 +1620,30 @@ static int train_launch_status(eh_handle* h, hipError_t e) {
 }
 static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out, bool bn_update) {
     if (h->seq) return seq_train(h, sp, idx, first, count, grid_out);
-    if (h->lform) return lform_train(h, sp, idx, first, count, grid_out, bn_update);
+    if (h->lform) return eh_lform_train(h, sp, idx, first, count, grid_out, bn_update);
     const EhNet& net = h->net;
     if (net.T > 1 && !h->dp_weights) {
-        EhShift4 sh4; for (int t = 0; t < EH_MAX_TARG; ++t) sh4.c[t] = sp.shift[t];
-        hipLaunchKernelGGL(eh_count_kernel, dim3(net.T), dim3(256), 0, h->stream, sp.recs, h->C, net.P + net.F, net.T, idx, first, count, h->inv_n, net.loss_t, sh4, h->img.agg_a, h->roles, h->img.l2s);
-        HIPCHK(h, hipGetLastError());
+        if (int rc = eh_launch_count(h, sp, idx, first, count)) return rc;
     }
     const bool moment_loss = two_pass_mask(net) != 0;
     if (moment_loss && !h->dp_moments) {      // (data-parallel step: eh_dp_grad has just made the coefficients from the moments of the GLOBAL batch)
         // forward-only passes (train-mode BatchNorm statistics included): the batch mean of yhat, then the moments of
         // (yhat, y) about the means -> the coefficients of the per-sample d loss / d yhat that the training pass multiplies
         // into the VJP
-        EhStepArgs e{};
-        e.prog = h->prog;
-        e.recs = sp.recs; e.C = h->C; e.idx = idx; e.first = first; e.count = count;
+        EhStepArgs e = eh_step_args(h, sp, idx, first, count);
         e.image = h->image; e.slab = h->slab; e.n_acc = EH_EVAL_STATS * net.T; e.rmap = h->rmap; e.stamps = nullptr;
         e.yld = count;
-        for (int t = 0; t < EH_MAX_TARG; ++t) e.shift[t] = sp.shift[t];
-        if (int rc = bn_prepare(h, sp, idx, first, count, false, &e)) return rc;
+        if (int rc = eh_bn_prepare(h, sp, idx, first, count, false, &e)) return rc;
         const int egrid = count > 0 ? grid_for(h, count) : 1;
         HIPCHK(h, step_launch(h, EH_MODE_EVAL, egrid, &e));       // -> mean of yhat
-        EhShift4 s4; for (int t = 0; t < EH_MAX_TARG; ++t) s4.c[t] = sp.shift[t];
-        hipLaunchKernelGGL(eh_moment_centre_kernel, dim3(net.T), dim3(64), 0, h->stream, h->slab, egrid, net.T, net.loss_t, s4, h->inv_n);
-        HIPCHK(h, hipGetLastError());
+        if (int rc = eh_launch_moment_centre(h, sp, h->slab, egrid)) return rc;
         e.inv_n = h->inv_n;                                                                                               // -> moments about it
         HIPCHK(h, step_launch(h, EH_MODE_EVAL, egrid, &e));
-        hipLaunchKernelGGL(eh_moment_coef_kernel, dim3(net.T), dim3(64), 0, h->stream, h->slab, egrid, net.T, net.loss_t, s4, h->inv_n, h->img.agg_a);
-        HIPCHK(h, hipGetLastError());
+        if (int rc = eh_launch_moment_coef(h, sp, h->slab, egrid)) return rc;
     }
-    EhStepArgs a{};
-    a.prog = h->prog;
-    a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = count;
+    EhStepArgs a = eh_step_args(h, sp, idx, first, count);
     a.image = h->image; a.slab = h->slab; a.n_acc = h->n_acc;
     a.inv_n = (net.T > 1 || moment_loss) ? h->inv_n : nullptr;
-    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
     a.rmap = h->rmap;
     // one network on a row-split bf16 kernel: the accumulators go to the slab row straight from the registers (canonical order is plain
     // column-major per layer; eh_wide_bf16.hpp) -- signalled by a null map
@@ -2334,7 +1655,7 @@ static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, 
         if (moment_loss) return fail(h, EH_EUNSUPPORTED, "dropout: the two-pass training losses (pearsonLoss / kgeLoss / pbkgeLoss, rmse on several targets) take their batch moments in passes without masks: not built");
         eh_drop_set(a, h->drop_seed, h->drop_step);
     }
-    if (int rc = bn_prepare(h, sp, idx, first, count, bn_update, &a)) return rc;
+    if (int rc = eh_bn_prepare(h, sp, idx, first, count, bn_update, &a)) return rc;
     const int grid = grid_for(h, count);
     *grid_out = grid;
     return train_launch_status(h, step_launch(h, EH_MODE_TRAIN, grid, &a));
@@ -2344,23 +1665,12 @@ static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, 
 static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* loss_slot_for_this_step,
                          bool ord = false, bool* launched = nullptr) {
     if (h->pending && h->pend_ord != ord) FLUSH(h);      // (a pending update is applied by a step of its own kind only)
-    const bool prof = h->prof && h->ev_used + 3 <= 3 * 8192;
-    const bool burst_first = h->prof_k % h->prof_stride == 0, burst_last = h->prof_k % h->prof_stride == h->prof_stride - 1;
-    if (prof) {
-        int rc = ensure_events(h, h->ev_used + 3);
-        if (rc) return rc;
-        if (burst_first) HIPCHK(h, hipEventRecord(h->ev[h->ev_used], h->stream));
-        h->prof_k++;
-    }
-    EhStepArgs a{};
-    a.prog = h->prog;
-    a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = count;
+    EhProf prof;
+    if (int rc = prof_begin(h, &prof)) return rc;
+    EhStepArgs a = eh_step_args(h, sp, idx, first, count);
     a.image = h->image; a.slab = h->slab; a.n_acc = h->n_acc; a.inv_n = nullptr; a.rmap = h->rmap; a.stamps = h->stamps;
-    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
     if (h->net.T > 1) {      // multi-target: the per-target weights (1 / n_t, 1 / sum (y - ybar)^2) have to be known inside the streaming pass
-        EhShift4 sh4; for (int t = 0; t < EH_MAX_TARG; ++t) sh4.c[t] = sp.shift[t];
-        hipLaunchKernelGGL(eh_count_kernel, dim3(h->net.T), dim3(256), 0, h->stream, sp.recs, h->C, h->net.P + h->net.F, h->net.T, idx, first, count, h->inv_n, h->net.loss_t, sh4, h->img.agg_a, h->roles, h->img.l2s);
-        HIPCHK(h, hipGetLastError());
+        if (int rc = eh_launch_count(h, sp, idx, first, count)) return rc;
         a.inv_n = h->inv_n;
     }
     EhFused& z = a.fz;
@@ -2370,13 +1680,13 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
     if (h->p2p_on) a.p2pv = h->p2p_host;
     a.p2p_seq = h->p2p_on ? ++h->p2p_seq : 0u;
     if (h->drop_on) { eh_drop_set(a, h->drop_seed, h->drop_step); }
-    if (int rc = bn_prepare(h, sp, idx, first, count, true, &a)) return rc;
+    if (int rc = eh_bn_prepare(h, sp, idx, first, count, true, &a)) return rc;
     const int grid = grid_for(h, count);
     if (ord) {
         a.ord = ord_args(h, h->cur, h->pending ? h->ord_grid : 0);
         const hipError_t e = step_launch(h, EH_MODE_TRAIN_ORD, grid, &a);
         if (e == hipErrorNotSupported) {          // (no such kernel for this handle: the caller runs the pair)
-            if (prof) h->prof_k--;
+            if (prof.on) h->prof_k--;
             *launched = false;
             return EH_OK;
         }
@@ -2393,12 +1703,7 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
     h->pending = true;
     h->pend_ord = ord;
     h->pending_loss = loss_slot_for_this_step;
-    if (prof && burst_last) {
-        HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 2], h->stream));
-        h->ev_used += 3;
-    }
-    return EH_OK;
+    return prof_end(h, prof, false);
 }
 
 // Several fused-update steps in one launch (EH_MODE_TRAIN_MULTI, eh_device.hpp): minibatches one workgroup covers -- the reference's
@@ -2417,16 +1722,13 @@ static bool multi_ok(const eh_handle* h, long long batch) {
 }
 static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long batch, long long end, int nsteps, float* loss_slots) {
     if (h->pending && h->pend_ord) FLUSH(h);
-    EhStepArgs a{};
-    a.prog = h->prog;
-    a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = std::min(batch, end - first);
+    EhStepArgs a = eh_step_args(h, sp, idx, first, std::min(batch, end - first));
     a.image = h->image; a.slab = h->slab; a.n_acc = h->n_acc; a.inv_n = nullptr; a.rmap = h->rmap; a.stamps = h->stamps;      // (diagnostic builds: the stamps of the launch's LAST step remain)
-    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
     EhFused& z = a.fz;
     z.gacc = h->gacc; z.pset = h->pset; z.imap = h->imap; z.loss_slot = h->pending_loss;
     z.gslot = (int)(h->gstep % 3); z.cur = h->cur; z.sc_sel = h->sc_sel; z.pending = h->pending ? 1 : 0; z.opt = h->opt; z.agg_a = h->img.agg_a;
     a.p2p = nullptr; a.p2p_seq = 0u;
-    if (int rc = bn_prepare(h, sp, idx, first, a.count, true, &a)) return rc;       // (input BatchNorm: statistics inside the kernel, multi_ok made sure)
+    if (int rc = eh_bn_prepare(h, sp, idx, first, a.count, true, &a)) return rc;       // (input BatchNorm: statistics inside the kernel, multi_ok made sure)
     a.ms_nsteps = nsteps; a.ms_batch = (int)batch; a.ms_end = end; a.ms_loss = loss_slots;
     HIPCHK(h, step_launch(h, EH_MODE_TRAIN_MULTI, 1, &a));
     // every step of the launch has applied its own update and written its own loss (eh_ms_apply): nothing is pending behind it; the first
@@ -2467,7 +1769,7 @@ static int launch_chain(eh_handle* h, bool raw, float* sc_in, float* sc_out, flo
 // "fused_update" 2 on a minibatch of several workgroups: the ordered one-kernel step (EH_MODE_TRAIN_ORD) wherever "fused_update" 1 would be
 // allowed and the pair's reduce would run eh_reduce_kernel<true, 16> on slab rows the per-wave kernels wrote -- its bits are that pair's
 static bool ord_ok(const eh_handle* h, int grid) {
-    static const int cw_env = getenv("EH_REDUCE_CW") ? atoi(getenv("EH_REDUCE_CW")) : 0;      // (the A/B switch of do_step)
+    static const int cw_env = getenv("EH_REDUCE_CW") ? atoi(getenv("EH_REDUCE_CW")) : 0;      // (the A/B switch of eh_do_step)
     if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS || h->chain.n || h->drop_on) return false;
     if (h->lform || h->arch->wide || h->p2p_on || h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->img.l2c != 0.0f || h->img.l2w || two_pass_mask(h->net) || h->dp_weights || h->dp_moments) return false;
@@ -2475,26 +1777,11 @@ static bool ord_ok(const eh_handle* h, int grid) {
     return h->n_acc < 8192 && h->ord_rs <= h->arch->img_floats && (cw_env == 0 || cw_env == 16);
 }
 
-static int ensure_events(eh_handle* h, size_t need) {
-    while (h->ev.size() < need) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreate(&e));
-        h->ev.push_back(e);
-    }
-    return EH_OK;
-}
-
 // fused step on the train split.  apply = update theta; loss_slot = device float for the loss.
-static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool apply, bool raw, float* loss_slot) {
+int eh_do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool apply, bool raw, float* loss_slot) {
     const EhNet& net = h->net;
-    const bool prof = h->prof && h->ev_used + 3 <= 3 * 8192;
-    const bool burst = h->prof_stride > 1, burst_first = h->prof_k % h->prof_stride == 0, burst_last = h->prof_k % h->prof_stride == h->prof_stride - 1;
-    if (prof) {
-        int rc = ensure_events(h, h->ev_used + 3);
-        if (rc) return rc;
-        if (burst_first) HIPCHK(h, hipEventRecord(h->ev[h->ev_used], h->stream));
-        h->prof_k++;
-    }
+    EhProf prof;
+    if (int rc = prof_begin(h, &prof)) return rc;
     int grid = 1;
     const int deferred = (net.T == 1 && !raw) ? 1 : 0;
     const unsigned tp_mask = two_pass_mask(net);
@@ -2502,7 +1789,7 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     const bool l2 = (h->img.l2c != 0.0f || h->img.l2w) && !raw;      // (data-parallel seam: raw sums only -- the extra loss is added once, in eh_dp_apply)
     float* sc_in = h->sc + 2 * h->sc_sel;
     float* sc_out = h->sc + 2 * (h->sc_sel ^ 1);
-    // layer-wise form, few rows: the optimiser may run in the epilogue of the grouped weight-gradient launch (lform_train decides; eh_lform.hpp EhLApply)
+    // layer-wise form, few rows: the optimiser may run in the epilogue of the grouped weight-gradient launch (eh_lform_train decides, eh_lform.hip; EhLApply)
     EhLApply lap{};
     h->l_apply = nullptr; h->l_applied = false;
     const bool chained = apply && h->chain.n != 0;      // an optimiser chain: the reduction leaves the gradient, the chain kernels apply it
@@ -2525,19 +1812,15 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     h->l_apply = nullptr;
     if (rc) return rc;
     if (h->drop_on && apply) h->drop_step++;      // (eh_loss_and_grad leaves the count: its gradient is the one the next training step applies)
-    if (prof && !burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
+    const bool mid = prof.on && !prof.burst;      // (every step bracketed on its own: the mark between the step kernel and the reduction)
+    if (mid) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
     if (h->l_applied) {                  // theta, the moments, the loss and the beta products are done (a chain: the gradient is; its kernels follow)
         h->l_applied = false;
         if (chained) {
             if (int rcc = launch_chain(h, false, sc_in, sc_out, nullptr)) return rcc;
         }
         h->sc_sel ^= 1;
-        if (prof && burst_last) {
-            if (burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
-            HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 2], h->stream));
-            h->ev_used += 3;
-        }
-        return EH_OK;
+        return prof_end(h, prof, mid);
     }
     if (l2) {
         hipLaunchKernelGGL(eh_weight_l2_kernel, dim3(1), dim3(256), 0, h->stream, TH(h), h->img, h->l2val);
@@ -2567,26 +1850,16 @@ static int do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
         if (int rcc = launch_chain(h, false, sc_in, sc_out, nullptr)) return rcc;
         h->sc_sel ^= 1;
     }
-    if (prof && burst_last) {
-        if (burst) HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 2], h->stream));
-        h->ev_used += 3;
-    }
-    return EH_OK;
+    return prof_end(h, prof, mid);
 }
 
 static int ensure_loss_hist(eh_handle* h, long long need) {
     if (h->loss_cap >= need) return EH_OK;
     FLUSH(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->loss_hist);
-    h->loss_hist = nullptr; h->loss_cap = 0;
-    HIPCHK(h, hipMalloc(&h->loss_hist, (size_t)need * sizeof(float)));
-    h->loss_cap = need;
-    return EH_OK;
+    return eh_grow(h, &h->loss_hist, &h->loss_cap, need);
 }
 
-static int check_window(eh_handle* h, const EhSplit& sp, long long first, long long count, const char* who) {
+int eh_check_window(eh_handle* h, const EhSplit& sp, long long first, long long count, const char* who) {
     if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "%s: no data set for this split (call eh_set_data)", who);
     if (first < 0 || count < 0 || first + count > sp.samples()) return fail(h, EH_EINVAL, "%s: window [%lld, %lld) outside 0..%lld", who, first, first + count, sp.samples());
     return EH_OK;
@@ -2630,85 +1903,12 @@ static int eval_host_acquire(eh_handle* h, size_t need) {
     h->eval_host_cap = cap;
     return EH_OK;
 }
-// A large result array to the caller's (pageable) memory: through the pinned staging pair of eh_set_data, chunk k + 1 on its way over
-// PCIe while chunk k is copied out by the CPU.  (hipMemcpy straight into pageable memory pins the destination pages behind the
-// scenes; with 50 MB of predictions per train() call on the headline data set that cost 1-27 ms per call depending on where the
-// allocator had put the arrays -- and whatever the runtime queued to undo it made the NEXT call's first upload chunk wait 15-28 ms
-// (tools/e2e_breakdown2.py).)  Small arrays, or a staging pair that is busy or cannot be had: the plain copy.
-static int copy_out(eh_handle* h, float* dst, const float* src_dev, size_t n) {
-    const size_t bytes = n * sizeof(float);
-    std::unique_lock<std::mutex> lk(g_stage_mu, std::try_to_lock);
-    if (bytes < ((size_t)256 << 10) || !lk.owns_lock()) { HIPCHK(h, hipMemcpy(dst, src_dev, bytes, hipMemcpyDeviceToHost)); return EH_OK; }
-    const size_t want = (size_t)8 << 20;                     // 8 MB chunks
-    if (g_stage_bytes < want) {
-        for (int k = 0; k < 2; ++k) { if (g_stage[k]) (void)hipHostFree(g_stage[k]); g_stage[k] = nullptr; }
-        g_stage_bytes = 0;
-        if (hipHostMalloc((void**)&g_stage[0], want, hipHostMallocPortable) == hipSuccess && hipHostMalloc((void**)&g_stage[1], want, hipHostMallocPortable) == hipSuccess) g_stage_bytes = want;
-        else { (void)hipGetLastError(); for (int k = 0; k < 2; ++k) { if (g_stage[k]) (void)hipHostFree(g_stage[k]); g_stage[k] = nullptr; } }
-    }
-    if (g_stage_bytes < want) { HIPCHK(h, hipMemcpy(dst, src_dev, bytes, hipMemcpyDeviceToHost)); return EH_OK; }
-    const size_t CH = std::min(g_stage_bytes, want) / sizeof(float);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIPCHK(h, hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-    { const hipError_t e = hipEventCreateWithFlags(&ev[1], hipEventDisableTiming); if (e != hipSuccess) { (void)hipEventDestroy(ev[0]); HIPCHK(h, e); } }
-    hipError_t err = hipSuccess;
-    const size_t nch = (n + CH - 1) / CH;
-    for (size_t k = 0; k <= nch && err == hipSuccess; ++k) {
-        if (k < nch) {                                       // chunk k: device -> stage[k & 1]
-            const size_t off = k * CH, cnt = std::min(CH, n - off);
-            err = hipMemcpyAsync(g_stage[k & 1], src_dev + off, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-            if (err == hipSuccess) err = hipEventRecord(ev[k & 1], h->stream);
-        }
-        if (k >= 1 && err == hipSuccess) {                   // chunk k - 1: stage -> caller
-            const size_t off = (k - 1) * CH, cnt = std::min(CH, n - off);
-            err = hipEventSynchronize(ev[(k - 1) & 1]);
-            if (err == hipSuccess) memcpy(dst + off, g_stage[(k - 1) & 1], cnt * sizeof(float));
-        }
-    }
-    { const hipError_t es = hipStreamSynchronize(h->stream); if (err == hipSuccess) err = es; }      // (the pair is not handed on with a copy in flight)
-    (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-    HIPCHK(h, err);
-    return EH_OK;
-}
-// ... and the other way (the parameter vector of a wide model, eh_set_params: 2.8 MB for the tutorial's large net -- a plain hipMemcpy from
-// pageable memory was 3 ms of every train() call and 33 ms of one call in eight, tools/e2e_spikes.py)
-static int copy_in(eh_handle* h, float* dst_dev, const float* src, size_t n) {
-    const size_t bytes = n * sizeof(float);
-    std::unique_lock<std::mutex> lk(g_stage_mu, std::try_to_lock);
-    const size_t want = (size_t)8 << 20;
-    if (bytes < ((size_t)256 << 10) || !lk.owns_lock()) { HIPCHK(h, hipMemcpy(dst_dev, src, bytes, hipMemcpyHostToDevice)); return EH_OK; }
-    if (g_stage_bytes < want) {
-        for (int k = 0; k < 2; ++k) { if (g_stage[k]) (void)hipHostFree(g_stage[k]); g_stage[k] = nullptr; }
-        g_stage_bytes = 0;
-        if (hipHostMalloc((void**)&g_stage[0], want, hipHostMallocPortable) == hipSuccess && hipHostMalloc((void**)&g_stage[1], want, hipHostMallocPortable) == hipSuccess) g_stage_bytes = want;
-        else { (void)hipGetLastError(); for (int k = 0; k < 2; ++k) { if (g_stage[k]) (void)hipHostFree(g_stage[k]); g_stage[k] = nullptr; } }
-    }
-    if (g_stage_bytes < want) { HIPCHK(h, hipMemcpy(dst_dev, src, bytes, hipMemcpyHostToDevice)); return EH_OK; }
-    const size_t CH = want / sizeof(float);
-    hipError_t err = hipSuccess;
-    for (size_t off = 0, k = 0; off < n && err == hipSuccess; off += CH, ++k) {
-        const size_t cnt = std::min(CH, n - off);
-        if (k >= 2) err = hipStreamSynchronize(h->stream);          // (the buffer about to be refilled has been read)
-        if (err != hipSuccess) break;
-        memcpy(g_stage[k & 1], src + off, cnt * sizeof(float));
-        err = hipMemcpyAsync(dst_dev + off, g_stage[k & 1], cnt * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    }
-    { const hipError_t es = hipStreamSynchronize(h->stream); if (err == hipSuccess) err = es; }
-    HIPCHK(h, err);
-    return EH_OK;
-}
 
 // sequence models: `count` windows, count * ow predictions [window][j]; EVAL leaves one row of shifted sums per workgroup in the slab
 static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count, double* stats, float* const* yhat, float* const* params) {
     if (!sp.starts) return fail(h, EH_ESTATE, "eh_eval: sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
     const long long nout = count * sp.ow, need = (long long)((yhat ? 1 : 0) + (params ? h->n_par : 0)) * nout;
-    if (need > h->out_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->out_buf);
-        h->out_buf = nullptr; h->out_cap = 0;
-        HIPCHK(h, hipMalloc(&h->out_buf, (size_t)need * sizeof(float)));
-        h->out_cap = need;
-    }
+    if (need > h->out_cap) { if (int rc2 = eh_grow(h, &h->out_buf, &h->out_cap, need)) return rc2; }
     EhSeqArgs a = seq_args(h, sp, nullptr, first, count);
     a.n_acc = EH_EVAL_STATS;
     a.yhat = yhat ? h->out_buf : nullptr;
@@ -2728,10 +1928,10 @@ static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count,
             for (int b = 0; b < grid; ++b) s += part[(size_t)b * EH_EVAL_STATS + k];
             stats[k] = s;
         }
-    if (yhat && yhat[0]) { if (int rc = copy_out(h, yhat[0], a.yhat, (size_t)nout)) return rc; }
+    if (yhat && yhat[0]) { if (int rc = eh_copy_out(h, yhat[0], a.yhat, (size_t)nout)) return rc; }
     if (params)
         for (int j = 0; j < h->n_par; ++j)
-            if (params[j]) { if (int rc = copy_out(h, params[j], a.pout + (long long)j * nout, (size_t)nout)) return rc; }
+            if (params[j]) { if (int rc = eh_copy_out(h, params[j], a.pout + (long long)j * nout, (size_t)nout)) return rc; }
     return EH_OK;
 }
 
@@ -2739,26 +1939,17 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
     const EhNet& net = h->net;
     EhSplit& sp = h->split[split];
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = check_window(h, sp, first, count, "eh_eval");
+    int rc = eh_check_window(h, sp, first, count, "eh_eval");
     if (rc) return rc;
     FLUSH(h);
     if (h->seq) return seq_eval(h, sp, first, count, stats, yhat, params);
     const long long need = (long long)(yhat ? net.T : 0) * count + (long long)(params ? h->n_par : 0) * count;
-    if (need > h->out_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->out_buf);
-        h->out_buf = nullptr; h->out_cap = 0;
-        HIPCHK(h, hipMalloc(&h->out_buf, (size_t)need * sizeof(float)));
-        h->out_cap = need;
-    }
-    EhStepArgs a{};
-    a.prog = h->prog;
-    a.recs = sp.recs; a.C = h->C; a.idx = nullptr; a.first = first; a.count = count;
+    if (need > h->out_cap) { if (int rc2 = eh_grow(h, &h->out_buf, &h->out_cap, need)) return rc2; }
+    EhStepArgs a = eh_step_args(h, sp, nullptr, first, count);
     a.image = h->image; a.slab = h->slab; a.n_acc = EH_EVAL_STATS * net.T;
     a.yhat = yhat ? h->out_buf : nullptr;
     a.pout = params ? h->out_buf + (yhat ? (long long)net.T * count : 0) : nullptr;
     a.yld = count;
-    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
     int grid = count > 0 ? (h->lform ? grid_for(h, count) : eval_grid_for(h, count)) : 1;
     // The per-workgroup sums (grid x 8 T floats) go to the host for the final fold in double.  The step kernels store them straight into
     // pinned, device-visible host memory -- the call is the kernel and one synchronisation; as a copy out of the slab into pageable
@@ -2780,7 +1971,7 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
     //  which also holds the launch, the synchronisation and the reading of the sums; bench.py eh_eval_roofline)
     const bool prof_ev = h->prof && h->ev_used + 3 <= 3 * 8192 && ensure_events(h, h->ev_used + 3) == EH_OK;
     if (prof_ev) HIPCHK(h, hipEventRecord(h->ev[h->ev_used], h->stream));
-    if (h->lform) { if ((rc = lform_eval(h, sp, first, count, a.yhat, a.pout, &grid))) return rc; }
+    if (h->lform) { if ((rc = eh_lform_eval(h, sp, first, count, a.yhat, a.pout, &grid))) return rc; }
     else HIPCHK(h, step_launch(h, EH_MODE_EVAL, grid, &a));
     if (prof_ev) {
         HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
@@ -2802,10 +1993,10 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
     }
     if (yhat)
         for (int t = 0; t < net.T; ++t)
-            if (yhat[t]) { if (int rc2 = copy_out(h, yhat[t], a.yhat + (long long)t * count, (size_t)count)) return rc2; }
+            if (yhat[t]) { if (int rc2 = eh_copy_out(h, yhat[t], a.yhat + (long long)t * count, (size_t)count)) return rc2; }
     if (params)
         for (int j = 0; j < h->n_par; ++j)
-            if (params[j]) { if (int rc2 = copy_out(h, params[j], a.pout + (long long)j * count, (size_t)count)) return rc2; }
+            if (params[j]) { if (int rc2 = eh_copy_out(h, params[j], a.pout + (long long)j * count, (size_t)count)) return rc2; }
     return EH_OK;
 }
 
@@ -2849,100 +2040,6 @@ int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_ta
     return EH_OK;
 }
 
-int32_t eh_mech_loss_vjp(eh_handle* h, int64_t count, int64_t ld, const float* o_dev, const float* const* forcings_dev, const float* const* targets_dev,
-                         const int64_t* n_valid_in, float* d_o_dev, float* yhat_dev, float* loss, float* grad_global, int64_t* n_valid) {
-    if (!h || !o_dev || !forcings_dev || !targets_dev || !d_o_dev) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: not built for sequence models");
-    const EhNet& net = h->net;
-    if (net.K == 0) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: the model has no neural parameter (no NN outputs to differentiate by): eh_loss_and_grad / eh_train_step run it whole");
-    if (net.loss != EH_LOSS_MSE && net.loss != EH_LOSS_MAE) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: training loss %d (built: mse, mae)", net.loss);
-    if (count < 1 || ld < count) return fail(h, EH_EINVAL, "eh_mech_loss_vjp: count %lld, ld %lld", (long long)count, (long long)ld);
-    for (int f = 0; f < net.F; ++f) if (!forcings_dev[f]) return fail(h, EH_EINVAL, "eh_mech_loss_vjp: forcing %d is null", f);
-    for (int t = 0; t < net.T; ++t) if (!targets_dev[t]) return fail(h, EH_EINVAL, "eh_mech_loss_vjp: target %d is null", t);
-    HIPCHK(h, hipSetDevice(h->device));
-    FLUSH(h);
-    EhMechArgs a{};
-    a.o = o_dev; a.d_o = d_o_dev; a.yhat = yhat_dev; a.n = count; a.ld = ld; a.meta = h->image + h->arch->phi_off;
-    bool vec = count % 4 == 0 && ld % 4 == 0 && ((uintptr_t)o_dev | (uintptr_t)d_o_dev | (uintptr_t)yhat_dev) % 16 == 0;
-    for (int f = 0; f < net.F; ++f) { a.frc[f] = forcings_dev[f]; vec = vec && (uintptr_t)forcings_dev[f] % 16 == 0; }
-    for (int t = 0; t < net.T; ++t) { a.y[t] = targets_dev[t]; vec = vec && (uintptr_t)targets_dev[t] % 16 == 0; }
-    if (net.mech == EH_MECH_PROGRAM) { vec = false; a.prog = h->prog; }        // the interpreter keeps its tape in scratch: one sample per lane
-    const int per = vec ? 1024 : 256;                                      // samples per workgroup and tile
-    if (net.n_out == 1 && net.T > 1) return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: %d targets on a single-output model", net.T);
-    // Many short workgroups, each on its own consecutive tiles: the accesses then move through the arrays as one front, in dispatch
-    // order, which is what the memory system serves best (tools/ubench/stream31.hip: 5.8 TB/s for this 3 : 1 mix, against 4.8-5.3 for
-    // a persistent grid of 1-4 k workgroups striding through it).  Rows of partials: one per workgroup, <= EH_MECH_MAXROWS.
-    const long long ntile = (count + per - 1) / per;
-    // (default: two tiles per workgroup; models with several outputs -- twice the streams, more registers per lane, fewer resident waves --
-    //  eight: FluxPart 0.59 -> 0.63 of the roof per call, RbQ10 best at two, Expo2Pool indifferent; tools/bench_mech.py --tiles)
-    int tiles = h->mech_tiles > 0 ? h->mech_tiles : (net.n_out > 1 ? 8 : 2);
-    while ((ntile + tiles - 1) / tiles > EH_MECH_MAXROWS) tiles *= 2;
-    int nblk = (int)((ntile + tiles - 1) / tiles);
-    if (h->mech_blocks > 0 && nblk > h->mech_blocks) { nblk = h->mech_blocks; tiles = 0; }      // "mech_blocks" option: a capped, grid-striding launch
-    a.tiles = tiles;
-    a.agg_a = h->img.agg_a;
-    const int nfold = nblk <= 2048 ? 0 : std::min(64, (nblk + 511) / 512);      // workgroups of the fold kernel (512 rows and more each)
-    const int rows_per = nfold ? (nblk + nfold - 1) / nfold : 0;
-    const size_t ws_bytes = EH_MAX_TARG * sizeof(unsigned long long) + 64 + 64 + (size_t)(64 + EH_MECH_MAXROWS) * EH_MECH_PART * sizeof(float);
-    if (ws_bytes > h->mech_ws_bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->mech_ws);
-        h->mech_ws = nullptr; h->mech_ws_bytes = 0;
-        HIPCHK(h, hipMalloc(&h->mech_ws, ws_bytes));
-        h->mech_ws_bytes = ws_bytes;
-    }
-    // [counts (4 x u64) | out: loss + 8 gradients, padded to 32 floats | part2 [64][16] | part [rows][16]]
-    unsigned long long* counts = reinterpret_cast<unsigned long long*>(h->mech_ws);
-    float* out = reinterpret_cast<float*>(h->mech_ws + EH_MAX_TARG * sizeof(unsigned long long));
-    float* part2 = out + 32;
-    a.part = part2 + 64 * EH_MECH_PART;
-    a.counts = counts;
-    unsigned long long hc[EH_MAX_TARG] = {0, 0, 0, 0};
-    if (n_valid_in) {                        // masks are a property of the data set (src/training/train.jl:221-232): the caller may know the counts
-        for (int t = 0; t < net.T; ++t) { if (n_valid_in[t] < 0 || n_valid_in[t] > count) return fail(h, EH_EINVAL, "eh_mech_loss_vjp: n_valid_in[%d] = %lld", t, (long long)n_valid_in[t]); hc[t] = (unsigned long long)n_valid_in[t]; }
-        for (int t = 0; t < EH_MAX_TARG; ++t) a.counts_v[t] = hc[t];
-        a.use_v = 1;                                             // travels in the kernarg segment: no copy, no counting pass
-    } else {
-        HIPCHK(h, hipMemsetAsync(counts, 0, sizeof hc, h->stream));
-        const unsigned ncb = (unsigned)std::min(nblk, 512);      // (one atomic per workgroup and target on ONE address: they serialise, ~13 ns each)
-        if (vec) hipLaunchKernelGGL(eh_count_valid_kernel<4>, dim3(ncb), dim3(256), 0, h->stream, a, net.T, counts);
-        else hipLaunchKernelGGL(eh_count_valid_kernel<1>, dim3(ncb), dim3(256), 0, h->stream, a, net.T, counts);
-        HIPCHK(h, hipGetLastError());
-    }
-#define EH_MECH_GO(M)                                                                                                              \
-    case M:                                                                                                                      \
-        if (vec) hipLaunchKernelGGL((eh_mech_vjp_kernel<4, M>), dim3((unsigned)nblk), dim3(256), 0, h->stream, net, a);           \
-        else hipLaunchKernelGGL((eh_mech_vjp_kernel<1, M>), dim3((unsigned)nblk), dim3(256), 0, h->stream, net, a);               \
-        break;
-    switch (net.mech) {
-        EH_MECH_GO(EH_MECH_RBQ10) EH_MECH_GO(EH_MECH_EXPO) EH_MECH_GO(EH_MECH_LINEAR) EH_MECH_GO(EH_MECH_EXPO2POOL)
-        EH_MECH_GO(EH_MECH_RS_COMPONENTS) EH_MECH_GO(EH_MECH_RS_COMPONENTS3F) EH_MECH_GO(EH_MECH_FLUXPART)
-        case EH_MECH_PROGRAM: hipLaunchKernelGGL((eh_mech_vjp_kernel<1, EH_MECH_PROGRAM>), dim3((unsigned)nblk), dim3(256), 0, h->stream, net, a); break;
-        default: return fail(h, EH_EUNSUPPORTED, "eh_mech_loss_vjp: mechanistic model %d", net.mech);
-    }
-#undef EH_MECH_GO
-    HIPCHK(h, hipGetLastError());
-    if (nfold) {
-        hipLaunchKernelGGL(eh_mech_fold_kernel, dim3((unsigned)nfold), dim3(1024), 0, h->stream, a.part, nblk, rows_per, part2);
-        HIPCHK(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(eh_mech_finish_kernel, dim3(1), dim3(1024), 0, h->stream, nfold ? part2 : a.part, nfold ? nfold : nblk, net, a.meta, a, out);
-    HIPCHK(h, hipGetLastError());
-    if (!loss && !grad_global && !n_valid) return EH_OK;         // asynchronous use: results stay on the device, ordered on the handle's stream
-    float ho[9];
-    HIPCHK(h, hipMemcpyAsync(ho, out, sizeof ho, hipMemcpyDeviceToHost, h->stream));
-    if (!a.use_v) HIPCHK(h, hipMemcpyAsync(hc, counts, sizeof hc, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    long long nv = 0;
-    for (int t = 0; t < net.T; ++t) nv += (long long)hc[t];
-    if (n_valid) *n_valid = nv;
-    if (loss) *loss = nv > 0 ? ho[0] : __builtin_nanf("");      // all-masked batch: skipped (epoch.jl:17-19)
-    if (grad_global)
-        for (int j = 0; j < h->desc.n_params; ++j)
-            if (h->desc.param_kind[j] == EH_PAR_GLOBAL) grad_global[h->desc.param_index[j]] = ho[1 + j];
-    return EH_OK;
-}
-
 int32_t eh_loss_and_grad(eh_handle* h, int32_t split, const int32_t* idx, int64_t first, int64_t count, float* loss, float* grad, int64_t* n_valid) {
     if (!h) return EH_EINVAL;
     if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_loss_and_grad: split %d", split);
@@ -2956,10 +2053,10 @@ int32_t eh_loss_and_grad(eh_handle* h, int32_t split, const int32_t* idx, int64_
         didx = h->idx_buf;
         first = 0;
     } else {
-        rc = check_window(h, sp, first, count, "eh_loss_and_grad");
+        rc = eh_check_window(h, sp, first, count, "eh_loss_and_grad");
         if (rc) return rc;
     }
-    rc = do_step(h, sp, didx, first, count, false, false, nullptr);
+    rc = eh_do_step(h, sp, didx, first, count, false, false, nullptr);
     if (rc) return rc;
     std::vector<float> host((size_t)h->n_acc);
     HIPCHK(h, hipMemcpyAsync(host.data(), h->gradbuf, host.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -3010,25 +2107,28 @@ int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* ru
     return EH_OK;
 }
 
+// a new rule (eh_opt_init, eh_opt_init_groups): out of L-BFGS mode, no chain, zero moments, the running beta products at their start
+static int opt_restart(eh_handle* h, const float* sc, size_t sc_bytes) {
+    if (h->lb) h->lb->active = false;
+    h->chain = EhChain{}; h->chain_gen = 0;
+    HIPCHK(h, hipMemset(MM(h), 0, (size_t)h->net.n_theta * sizeof(float)));
+    HIPCHK(h, hipMemset(VV(h), 0, (size_t)h->net.n_theta * sizeof(float)));
+    HIPCHK(h, hipMemcpy(h->sc, sc, sc_bytes, hipMemcpyHostToDevice));
+    h->sc_sel = 0;
+    h->opt_ready = true;
+    lean_refresh(h);
+    return EH_OK;
+}
 int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay) {
     if (!h) return EH_EINVAL;
     if (rule < EH_OPT_ADAM || rule > EH_OPT_DESCENT) return fail(h, EH_EUNSUPPORTED, "eh_opt_init: unknown rule %d", rule);
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->lb) h->lb->active = false;
     h->opt = EhOpt{rule, lr, beta1, beta2, eps, weight_decay, nullptr};
     h->opt_groups = 1;
-    h->chain = EhChain{}; h->chain_gen = 0;
-    const size_t nt = (size_t)h->net.n_theta;
-    HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
-    HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
     const float sc[4] = {beta1, beta2, beta1, beta2};   // Optimisers.jl starts the running product at beta (t = 1)
-    HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
-    h->sc_sel = 0;
-    h->opt_ready = true;
-    lean_refresh(h);
-    return EH_OK;
+    return opt_restart(h, sc, sizeof sc);
 }
 
 int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, int32_t n_groups, const int32_t* rule, const float* hyper) {
@@ -3059,20 +2159,12 @@ int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, 
     // (the handle's own rule names Adam, so every site moves m and v; its hyper-parameters are group 0's -- the table is what is read)
     h->opt = EhOpt{EH_OPT_ADAM, t->r[0].lr, t->r[0].b1, t->r[0].b2, t->r[0].eps, t->r[0].wd, h->opt_tab};
     h->opt_groups = n_groups;
-    if (h->lb) h->lb->active = false;
-    h->chain = EhChain{}; h->chain_gen = 0;
-    HIPCHK(h, hipMemset(MM(h), 0, nt * sizeof(float)));
-    HIPCHK(h, hipMemset(VV(h), 0, nt * sizeof(float)));
     float sc[4 * EH_MAX_OPT_GROUPS] = {};
     for (int k = 0; k < n_groups; ++k) {       // group k, set s at [4 k + 2 s]; Optimisers.jl starts each product at beta (t = 1)
         sc[4 * k] = sc[4 * k + 2] = hyper[5 * k + 1];
         sc[4 * k + 1] = sc[4 * k + 3] = hyper[5 * k + 2];
     }
-    HIPCHK(h, hipMemcpy(h->sc, sc, sizeof sc, hipMemcpyHostToDevice));
-    h->sc_sel = 0;
-    h->opt_ready = true;
-    lean_refresh(h);
-    return EH_OK;
+    return opt_restart(h, sc, sizeof sc);
 }
 
 int32_t eh_opt_init_chain(eh_handle* h, const eh_opt_stage* stages, int32_t n_stages, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay) {
@@ -3127,177 +2219,6 @@ int32_t eh_opt_chain_status(eh_handle* h, int64_t* n_applied, int64_t* n_clipped
     return EH_OK;
 }
 
-// ---- L-BFGS on the device (eh_lbfgs.hpp) --------------------------------------------------------------
-static void lbfgs_release(eh_handle* h) {
-    if (!h->lb) return;
-    (void)hipFree(h->lb->vec); (void)hipFree(h->lb->dbl); (void)hipFree(h->lb->trace); (void)hipFree(h->lb->idx);
-    delete h->lb;
-    h->lb = nullptr;
-}
-
-static int lbfgs_ready(eh_handle* h, const char* who) {
-    if (!h->lb || !h->lb->active) return fail(h, EH_ESTATE, "%s: call eh_lbfgs_init first (eh_opt_init* leaves L-BFGS mode)", who);
-    if (h->capturing) return fail(h, EH_EUNSUPPORTED, "%s: graph capture is not built for L-BFGS", who);
-    return EH_OK;
-}
-
-int32_t eh_lbfgs_init(eh_handle* h, const eh_lbfgs_opts* o) {
-    if (!h || !o) return EH_EINVAL;
-    if (o->m < 1 || o->m > EH_LBFGS_MAX_M) return fail(h, EH_EINVAL, "eh_lbfgs_init: m = %d (1..%d)", o->m, (int)EH_LBFGS_MAX_M);
-    if (!(o->c1 > 0.0 && o->c1 < o->c2 && o->c2 < 1.0)) return fail(h, EH_EINVAL, "eh_lbfgs_init: need 0 < c1 < c2 < 1 (c1 = %g, c2 = %g)", o->c1, o->c2);
-    if (o->max_linesearch < 1 || o->max_linesearch > 48) return fail(h, EH_EINVAL, "eh_lbfgs_init: max_linesearch = %d (1..48)", o->max_linesearch);
-    if (!(o->g_tol >= 0.0) || !(o->f_reltol >= 0.0)) return fail(h, EH_EINVAL, "eh_lbfgs_init: g_tol = %g, f_reltol = %g (both >= 0)", o->g_tol, o->f_reltol);
-    if (!(o->initial_step >= 0.0) || !std::isfinite(o->initial_step)) return fail(h, EH_EINVAL, "eh_lbfgs_init: initial_step = %g (>= 0; 0 = min(1, 1 / ||g||))", o->initial_step);
-    if (h->capturing) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: graph capture is not built for L-BFGS");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: dropout: the line search needs the same objective at every trial point, the masks change with every pass (eh_set_dropout with all rates zero removes it)");
-    if (h->bn_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: input BatchNorm: the reference's Optimization.jl driver never carries the layer state, and that path is not built");
-    if (h->comm || h->lgroup || h->p2p_on || h->p2p_alloc) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: data parallelism (a communicator or a peer-to-peer group on this handle) is not built for L-BFGS");
-    HIPCHK(h, hipSetDevice(h->device));
-    FLUSH(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t n = (size_t)h->net.n_theta;
-    if (!h->lb) h->lb = new EhLbfgs();
-    EhLbfgs* lb = h->lb;
-    lb->active = false;
-    if (lb->m_cap < o->m) {
-        (void)hipFree(lb->vec); lb->vec = nullptr; lb->m_cap = 0;
-        HIPCHK(h, hipMalloc(&lb->vec, (3 + 2 * (size_t)o->m) * n * sizeof(float)));
-        lb->m_cap = o->m;
-    }
-    if (!lb->dbl) HIPCHK(h, hipMalloc(&lb->dbl, (size_t)(EH_LB_DBL_HEAD + EH_LB_PARTS * EH_LB_NQ_MAX) * sizeof(double)));
-    if (!lb->trace) HIPCHK(h, hipMalloc(&lb->trace, (size_t)EH_LB_TRACE_ROWS * 8 * sizeof(float)));
-    HIPCHK(h, hipMemset(lb->vec, 0, (3 + 2 * (size_t)o->m) * n * sizeof(float)));
-    HIPCHK(h, hipMemset(lb->dbl, 0, (size_t)EH_LB_DBL_HEAD * sizeof(double)));
-    lb->o = *o; lb->nq = EH_LQ_HIST + 6 * o->m; lb->maxiters = 100;
-    lb->batch_set = false; lb->empty = false;
-    lb->active = true;
-    return EH_OK;
-}
-
-static EhLbfgsArgs lbfgs_args(const eh_handle* h) {
-    const EhLbfgs* lb = h->lb;
-    const int n = h->net.n_theta;
-    EhLbfgsArgs a{};
-    a.gradbuf = h->gradbuf; a.theta = TH(h);
-    a.x0 = lb->vec; a.g0 = lb->vec + (size_t)n; a.d = lb->vec + 2 * (size_t)n; a.S = lb->vec + 3 * (size_t)n; a.Y = a.S + (size_t)lb->o.m * n;
-    a.st = lb->dbl; a.rec = lb->dbl + EH_LBFGS_STATE_DOUBLES; a.gram = a.rec + EH_LBFGS_RECORD_DOUBLES; a.part = lb->dbl + EH_LB_DBL_HEAD;
-    a.trace = lb->trace;
-    a.n = n; a.T = h->net.T; a.nq = lb->nq; a.nparts = std::min<int>(EH_LB_PARTS, (n + 1023) / 1024); a.maxiters = lb->maxiters;
-    a.o = lb->o;
-    return a;
-}
-
-int32_t eh_lbfgs_set_maxiters(eh_handle* h, int64_t n) {
-    if (!h) return EH_EINVAL;
-    if (int rc = lbfgs_ready(h, "eh_lbfgs_set_maxiters")) return rc;
-    if (n < 0 || n > INT32_MAX) return fail(h, EH_EINVAL, "eh_lbfgs_set_maxiters: %lld", (long long)n);
-    h->lb->maxiters = (int)n;
-    if (h->lb->batch_set && !h->lb->empty) {      // a solve that stopped at a lower limit goes on (decided on the device: nothing is read back here)
-        HIPCHK(h, hipSetDevice(h->device));
-        FLUSH(h);
-        hipLaunchKernelGGL(eh_lbfgs_resume_kernel, dim3(1), dim3(256), 0, h->stream, lbfgs_args(h), h->img);
-        HIPCHK(h, hipGetLastError());
-    }
-    return EH_OK;
-}
-
-int32_t eh_lbfgs_set_batch(eh_handle* h, int32_t split, const int32_t* idx, int32_t idx_on_device, int64_t first, int64_t count) {
-    if (!h) return EH_EINVAL;
-    if (int rc = lbfgs_ready(h, "eh_lbfgs_set_batch")) return rc;
-    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_lbfgs_set_batch: split %d", split);
-    EhLbfgs* lb = h->lb;
-    EhSplit& sp = h->split[split];
-    if (!sp.recs || sp.n == 0) return fail(h, EH_ESTATE, "eh_lbfgs_set_batch: no data set for this split (call eh_set_data)");
-    if (first < 0 || count < 0) return fail(h, EH_EINVAL, "eh_lbfgs_set_batch: first %lld, count %lld", (long long)first, (long long)count);
-    HIPCHK(h, hipSetDevice(h->device));
-    FLUSH(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    lb->batch_set = false;
-    if (idx && !idx_on_device) {
-        for (int64_t i = 0; i < count; ++i)
-            if (idx[first + i] < 0 || idx[first + i] >= sp.samples()) return fail(h, EH_EINVAL, "eh_lbfgs_set_batch: idx[%lld] = %d outside 0..%lld", (long long)(first + i), idx[first + i], sp.samples());
-        if (count > lb->idx_cap) {
-            (void)hipFree(lb->idx); lb->idx = nullptr; lb->idx_cap = 0;
-            HIPCHK(h, hipMalloc(&lb->idx, (size_t)count * sizeof(int)));
-            lb->idx_cap = count;
-        }
-        if (count > 0) HIPCHK(h, hipMemcpy(lb->idx, idx + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
-        lb->didx = lb->idx; first = 0;
-    } else if (idx) lb->didx = idx;
-    else {
-        if (int rc = check_window(h, sp, first, count, "eh_lbfgs_set_batch")) return rc;
-        lb->didx = nullptr;
-    }
-    lb->split = split; lb->first = first; lb->count = count;
-    HIPCHK(h, hipMemset(lb->dbl, 0, (size_t)EH_LB_DBL_HEAD * sizeof(double)));      // a fresh solve: no history, phase 0
-    lb->empty = count == 0;
-    lb->batch_set = true;
-    return EH_OK;
-}
-
-int32_t eh_lbfgs_run(eh_handle* h, int64_t n_evals) {
-    if (!h) return EH_EINVAL;
-    if (int rc = lbfgs_ready(h, "eh_lbfgs_run")) return rc;
-    EhLbfgs* lb = h->lb;
-    if (!lb->batch_set) return fail(h, EH_ESTATE, "eh_lbfgs_run: call eh_lbfgs_set_batch first");
-    if (n_evals < 0) return fail(h, EH_EINVAL, "eh_lbfgs_run: %lld evaluations", (long long)n_evals);
-    if (h->drop_on || h->bn_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_run: dropout / input BatchNorm were switched on after eh_lbfgs_init: not built for L-BFGS");
-    if (lb->empty) return EH_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    FLUSH(h);
-    const int n = h->net.n_theta;
-    const EhLbfgsArgs a = lbfgs_args(h);
-    const bool one = n <= (h->lb_one_max >= 0 ? h->lb_one_max : (int)EH_LB_ONE_MAX);
-    const EhSplit& sp = h->split[lb->split];
-    for (int64_t e = 0; e < n_evals; ++e) {
-        if (int rc = do_step(h, sp, lb->didx, lb->first, lb->count, false, false, nullptr)) return rc;
-        if (one) hipLaunchKernelGGL(eh_lbfgs_one_kernel, dim3(1), dim3(256), 0, h->stream, a, h->img);
-        else {
-            hipLaunchKernelGGL(eh_lbfgs_dots_kernel, dim3(a.nparts), dim3(256), 0, h->stream, a);
-            hipLaunchKernelGGL(eh_lbfgs_decide_kernel, dim3(1), dim3(256), 0, h->stream, a);
-            hipLaunchKernelGGL(eh_lbfgs_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, a, h->img);
-        }
-        HIPCHK(h, hipGetLastError());
-    }
-    return EH_OK;
-}
-
-int32_t eh_lbfgs_status(eh_handle* h, eh_lbfgs_stat* out) {
-    if (!h || !out) return EH_EINVAL;
-    if (int rc = lbfgs_ready(h, "eh_lbfgs_status")) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    double st[EH_LBFGS_STATE_DOUBLES];
-    HIPCHK(h, hipMemcpy(st, h->lb->dbl, sizeof st, hipMemcpyDeviceToHost));
-    out->iterations = (int64_t)st[EH_LS_ITERS]; out->evaluations = (int64_t)st[EH_LS_EVALS];
-    out->f0 = st[EH_LS_F0]; out->g_inf = st[EH_LS_GINF0]; out->last_t = st[EH_LS_LAST_T];
-    out->pairs = (int32_t)st[EH_LS_NPAIRS];
-    out->code = h->lb->empty ? (int32_t)EH_LBFGS_EMPTY_BATCH : (int32_t)st[EH_LS_DONE];
-    return EH_OK;
-}
-
-int32_t eh_lbfgs_trace(eh_handle* h, float* out, int64_t max_rows, int64_t* n_rows) {
-    if (!h || !n_rows || (max_rows > 0 && !out)) return EH_EINVAL;
-    if (int rc = lbfgs_ready(h, "eh_lbfgs_trace")) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    double rows = 0.0;
-    HIPCHK(h, hipMemcpy(&rows, h->lb->dbl + EH_LS_ROWS, sizeof rows, hipMemcpyDeviceToHost));
-    *n_rows = (int64_t)rows;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>((int64_t)rows, max_rows), (int64_t)EH_LB_TRACE_ROWS);
-    if (k > 0) HIPCHK(h, hipMemcpy(out, h->lb->trace, (size_t)k * 8 * sizeof(float), hipMemcpyDeviceToHost));
-    return EH_OK;
-}
-
-int32_t eh_lbfgs_host_decide(const eh_lbfgs_opts* o, int32_t maxiters, double* state, double* gram, const double* sums, double f, double n_valid,
-                             double* record, double* trace_row, int32_t* wrote_row) {
-    if (!o || !state || !gram || !sums || !record || !trace_row) return EH_EINVAL;
-    if (o->m < 1 || o->m > EH_LBFGS_MAX_M || o->max_linesearch < 1 || o->max_linesearch > 48) return EH_EINVAL;
-    const int w = eh_lb_decide(*o, maxiters, state, gram, sums, f, n_valid, record, trace_row);
-    if (wrote_row) *wrote_row = w;
-    return EH_OK;
-}
-
 int32_t eh_get_opt_beta_t(eh_handle* h, float* bt, int32_t n_groups) {
     if (!h || !bt) return EH_EINVAL;
     if (n_groups != h->opt_groups) return fail(h, EH_EINVAL, "eh_get_opt_beta_t: %d groups, the handle has %d", n_groups, h->opt_groups);
@@ -3328,8 +2249,8 @@ int32_t eh_get_opt_state(eh_handle* h, float* m, float* v, int64_t n, float* bet
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (m) { if (int rc = copy_out(h, m, MM(h), (size_t)n)) return rc; }
-    if (v) { if (int rc = copy_out(h, v, VV(h), (size_t)n)) return rc; }
+    if (m) { if (int rc = eh_copy_out(h, m, MM(h), (size_t)n)) return rc; }
+    if (v) { if (int rc = eh_copy_out(h, v, VV(h), (size_t)n)) return rc; }
     if (beta_t) HIPCHK(h, hipMemcpy(beta_t, h->sc + 2 * h->sc_sel, 2 * sizeof(float), hipMemcpyDeviceToHost));
     return EH_OK;
 }
@@ -3341,8 +2262,8 @@ int32_t eh_set_opt_state(eh_handle* h, const float* m, const float* v, int64_t n
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (m) { if (int rc = copy_in(h, MM(h), m, (size_t)n)) return rc; }
-    if (v) { if (int rc = copy_in(h, VV(h), v, (size_t)n)) return rc; }
+    if (m) { if (int rc = eh_copy_in(h, MM(h), m, (size_t)n)) return rc; }
+    if (v) { if (int rc = eh_copy_in(h, VV(h), v, (size_t)n)) return rc; }
     if (beta_t) HIPCHK(h, hipMemcpy(h->sc + 2 * h->sc_sel, beta_t, 2 * sizeof(float), hipMemcpyHostToDevice));
     return EH_OK;
 }
@@ -3411,6 +2332,22 @@ int32_t eh_dropout_mask(eh_handle* h, int32_t layer, uint64_t step, int64_t coun
     return EH_OK;
 }
 
+// One training step on the path the handle's mode takes; *one_kernel: a fused-update step (its update is pending), else the step + reduce pair.
+// "fused_update" 2: the float-atomic one-kernel step only where one workgroup covers the minibatch, the ordered one elsewhere (ord_ok), the
+// pair where that is not built; an optimiser chain: always the step + reduce + chain kernels
+static int train_one(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* loss_slot, bool* one_kernel) {
+    const int grid = h->seq ? 0 : grid_for(h, count);
+    *one_kernel = false;
+    if (h->fused && !(h->fused_det && grid != 1) && !h->chain.n) {
+        if (int rc = do_fused_step(h, sp, idx, first, count, loss_slot)) return rc;
+        *one_kernel = true;
+    } else if (ord_ok(h, grid)) {
+        if (int rc = do_fused_step(h, sp, idx, first, count, loss_slot, true, one_kernel)) return rc;
+    }
+    if (*one_kernel) return EH_OK;
+    FLUSH(h);                                  // ("fused_update" 2: a one-workgroup step may be pending in front of this larger one)
+    return eh_do_step(h, sp, idx, first, count, true, false, loss_slot);
+}
 int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, int64_t first, int64_t count, float* loss_out) {
     if (!h) return EH_EINVAL;
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_train_step: call eh_opt_init first");
@@ -3441,26 +2378,12 @@ int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, i
             HIPCHK(h, e);
             if (res[0]) return fail(h, EH_EINVAL, "eh_train_step: %u of the %lld device-side indices are outside 0..%lld (first offender: idx[%lld])", res[0], (long long)count, (long long)sp.samples() - 1, (long long)first + (long long)res[1]);
         }
-    } else if ((rc = check_window(h, sp, first, count, "eh_train_step"))) return rc;
+    } else if ((rc = eh_check_window(h, sp, first, count, "eh_train_step"))) return rc;
     rc = ensure_loss_hist(h, 1);
     if (rc) return rc;
-    const int grid = h->seq ? 0 : grid_for(h, count);
-    bool done = false;
-    if (h->fused && !(h->fused_det && grid != 1) && !h->chain.n) {      // (an optimiser chain: always the step + reduce + chain kernels)
-        rc = do_fused_step(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr);
-        if (rc) return rc;
-        done = true;
-    } else if (ord_ok(h, grid)) {
-        rc = do_fused_step(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr, true, &done);
-        if (rc) return rc;
-    }
-    if (done) {
-        if (loss_out) FLUSH(h);
-    } else {
-        FLUSH(h);                              // ("fused_update" 2: a one-workgroup step may be pending in front of this larger one)
-        rc = do_step(h, sp, didx, first, count, true, false, loss_out ? h->loss_hist : nullptr);
-        if (rc) return rc;
-    }
+    bool one_kernel = false;
+    if ((rc = train_one(h, sp, didx, first, count, loss_out ? h->loss_hist : nullptr, &one_kernel))) return rc;
+    if (one_kernel && loss_out) FLUSH(h);
     if (loss_out) {
         HIPCHK(h, hipMemcpyAsync(loss_out, h->loss_hist, sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3470,13 +2393,7 @@ int32_t eh_train_step(eh_handle* h, const int32_t* idx, int32_t idx_on_device, i
 
 // device-side keyed permutation of the train split's sample indices into h->perm
 static int make_permutation(eh_handle* h, long long N, uint64_t seed) {
-    if (h->perm_cap < N) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->perm);
-        h->perm = nullptr; h->perm_cap = 0;
-        HIPCHK(h, hipMalloc(&h->perm, (size_t)N * sizeof(int)));
-        h->perm_cap = N;
-    }
+    if (h->perm_cap < N) { if (int rc = eh_grow(h, &h->perm, &h->perm_cap, N)) return rc; }
     int bits = 1;
     while ((1LL << bits) < N) ++bits;
     const int hb = std::max(1, (bits + 1) / 2);
@@ -3575,21 +2492,9 @@ int32_t eh_train_epoch(eh_handle* h, int64_t batchsize, uint64_t seed, int32_t s
         }
     } else
     for (long long s = 0; s < steps; ++s) {
-        const long long first = s * batchsize, count = std::min<long long>(batchsize, N - first);
-        const int grid = h->seq ? 0 : grid_for(h, count);
-        // ("fused_update" 2: the float-atomic one-kernel step only where one workgroup covers the minibatch, the ordered one elsewhere)
-        const bool one_kernel = h->fused && !(h->fused_det && grid != 1) && !h->chain.n;
-        bool done = false;
-        if (one_kernel) {
-            if ((rc = do_fused_step(h, sp, shuffle ? h->perm : nullptr, first, count, h->loss_hist + s))) return rc;
-            done = true;
-        } else if (ord_ok(h, grid)) {
-            if ((rc = do_fused_step(h, sp, shuffle ? h->perm : nullptr, first, count, h->loss_hist + s, true, &done))) return rc;
-        }
-        if (!done) {
-            FLUSH(h);
-            if ((rc = do_step(h, sp, shuffle ? h->perm : nullptr, first, count, true, false, h->loss_hist + s))) return rc;
-        }
+        const long long first = s * batchsize;
+        bool one_kernel;
+        if ((rc = train_one(h, sp, shuffle ? h->perm : nullptr, first, std::min<long long>(batchsize, N - first), h->loss_hist + s, &one_kernel))) return rc;
     }
     if (mean_loss) FLUSH(h);
     if (n_steps) *n_steps = steps;
@@ -3635,6 +2540,13 @@ int32_t eh_set_weight_l2_coef(eh_handle* h, const float* coef, int64_t n) {
     return EH_OK;
 }
 
+// what no entry point of the data-parallel seam is built for
+static int dp_refused(eh_handle* h, const char* who) {
+    if (h->seq) return fail(h, EH_EUNSUPPORTED, "%s: data parallelism is not built for sequence models", who);
+    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "%s: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)", who);
+    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "%s: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)", who);
+    return EH_OK;
+}
 int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: data parallelism is not built for sequence models");
@@ -3650,9 +2562,7 @@ int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
 
 int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: data parallelism is not built for sequence models");
-    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_grad: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
+    if (int rc = dp_refused(h, "eh_dp_grad")) return rc;
     if (h->net.T != 1 && !h->tcount_ready) return fail(h, EH_ESTATE, "eh_dp_grad: multi-target model: call eh_dp_counts for this window and all-reduce EH_BUF_TCOUNT first");
     const unsigned tpm_dp = two_pass_mask(h->net);
     if (tpm_dp && h->mom_stage != 2) return fail(h, EH_ESTATE, "eh_dp_grad: rmse (multi-target) / pearson / kge training losses need the moments of the GLOBAL batch's predictions first: eh_dp_moments stage 0, all-reduce EH_BUF_MOMENT, stage 1, all-reduce");
@@ -3661,7 +2571,7 @@ int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
-    int rc = check_window(h, sp, first, count, "eh_dp_grad");
+    int rc = eh_check_window(h, sp, first, count, "eh_dp_grad");
     if (rc) return rc;
     if (h->net.T != 1) {      // the weights of the GLOBAL batch from the all-reduced sums; the step kernel then normalises exactly
         hipLaunchKernelGGL(eh_weights_from_counts_kernel, dim3(1), dim3(64), 0, h->stream, h->tcount, h->net.T, h->net.loss_t, h->inv_n, h->img.agg_a, h->roles, h->img.l2s);
@@ -3669,12 +2579,10 @@ int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
         h->dp_weights = true;
     }
     if (tpm_dp) {             // the all-reduced moments about the global centre -> k0 k1 k2 and the loss value of every two-pass target
-        EhShift4 s4; for (int t = 0; t < EH_MAX_TARG; ++t) s4.c[t] = sp.shift[t];
-        hipLaunchKernelGGL(eh_moment_coef_kernel, dim3(h->net.T), dim3(64), 0, h->stream, h->mombuf, 1, h->net.T, h->net.loss_t, s4, h->inv_n, h->img.agg_a);
-        HIPCHK(h, hipGetLastError());
+        if ((rc = eh_launch_moment_coef(h, sp, h->mombuf, 1))) return rc;
         h->dp_moments = true;
     }
-    rc = do_step(h, sp, h->perm_valid ? h->perm : nullptr, first, count, false, true, nullptr);
+    rc = eh_do_step(h, sp, h->perm_valid ? h->perm : nullptr, first, count, false, true, nullptr);
     h->dp_weights = false; h->tcount_ready = false; h->dp_moments = false; h->mom_stage = 0;
     return rc;
 }
@@ -3684,19 +2592,13 @@ int32_t eh_dp_grad(eh_handle* h, int64_t first, int64_t count) {
 // The caller all-reduces the 12 floats; eh_dp_grad turns them into the weights 1 / n_t (mse, mae) or 1 / sum (y - ybar)^2 (nseLoss).
 int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: data parallelism is not built for sequence models");
-    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_counts: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
+    if (int rc = dp_refused(h, "eh_dp_counts")) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
-    int rc = check_window(h, sp, first, count, "eh_dp_counts");
+    int rc = eh_check_window(h, sp, first, count, "eh_dp_counts");
     if (rc) return rc;
-    const EhNet& net = h->net;
-    EhShift4 sh4; for (int t = 0; t < EH_MAX_TARG; ++t) sh4.c[t] = sp.shift[t];
     HIPCHK(h, hipMemsetAsync(h->tcount, 0, 3 * EH_MAX_TARG * sizeof(float), h->stream));
-    hipLaunchKernelGGL(eh_count_kernel, dim3(net.T), dim3(256), 0, h->stream, sp.recs, h->C, net.P + net.F, net.T, h->perm_valid ? h->perm : nullptr, first, count,
-                       h->inv_n, net.loss_t, sh4, h->img.agg_a, h->roles, h->img.l2s, h->tcount);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = eh_launch_count(h, sp, h->perm_valid ? h->perm : nullptr, first, count, h->tcount))) return rc;
     h->tcount_ready = true;
     return EH_OK;
 }
@@ -3712,9 +2614,7 @@ int32_t eh_dp_counts(eh_handle* h, int64_t first, int64_t count) {
 // keeps its statistics passes inside its own forward).
 int32_t eh_dp_moments(eh_handle* h, int64_t first, int64_t count, int32_t stage) {
     if (!h) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: data parallelism is not built for sequence models");
-    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
+    if (int rc = dp_refused(h, "eh_dp_moments")) return rc;
     const EhNet& net = h->net;
     if (!two_pass_mask(net)) return fail(h, EH_ESTATE, "eh_dp_moments: the training loss needs no batch moments of the predictions");
     if (h->lform) return fail(h, EH_EUNSUPPORTED, "eh_dp_moments: the layer-wise form has no data-parallel seam for the two-pass training losses");
@@ -3724,21 +2624,16 @@ int32_t eh_dp_moments(eh_handle* h, int64_t first, int64_t count, int32_t stage)
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
-    if (int rc = check_window(h, sp, first, count, "eh_dp_moments")) return rc;
+    if (int rc = eh_check_window(h, sp, first, count, "eh_dp_moments")) return rc;
     const int* idx = h->perm_valid ? h->perm : nullptr;
-    EhStepArgs e{};
-    e.prog = h->prog;
-    e.recs = sp.recs; e.C = h->C; e.idx = idx; e.first = first; e.count = count;
+    EhStepArgs e = eh_step_args(h, sp, idx, first, count);
     e.image = h->image; e.slab = h->slab; e.n_acc = EH_EVAL_STATS * net.T; e.rmap = h->rmap; e.stamps = nullptr;
     e.yld = count;
-    for (int t = 0; t < EH_MAX_TARG; ++t) e.shift[t] = sp.shift[t];
     // (the global BatchNorm statistics of eh_dp_bn_stats serve both moment passes AND the training pass behind them: eh_dp_grad /
     //  eh_dp_fused_step consume them; advisor, round 4: stage 0 used to clear them and every later pass of the step failed)
-    if (int rc = bn_prepare(h, sp, idx, first, count, false, &e, /*consume*/ false)) return rc;
-    EhShift4 s4; for (int t = 0; t < EH_MAX_TARG; ++t) s4.c[t] = sp.shift[t];
+    if (int rc = eh_bn_prepare(h, sp, idx, first, count, false, &e, /*consume*/ false)) return rc;
     if (stage == 1) {        // the all-reduced sums about the shift -> the centre of yhat of the global batch
-        hipLaunchKernelGGL(eh_moment_centre_kernel, dim3(net.T), dim3(64), 0, h->stream, h->mombuf, 1, net.T, net.loss_t, s4, h->inv_n);
-        HIPCHK(h, hipGetLastError());
+        if (int rc = eh_launch_moment_centre(h, sp, h->mombuf, 1)) return rc;
         e.inv_n = h->inv_n;
     }
     const int egrid = count > 0 ? grid_for(h, count) : 1;
@@ -3764,9 +2659,7 @@ int32_t eh_set_target_shift(eh_handle* h, int32_t split, const float* shift, int
 
 int32_t eh_dp_fused_step(eh_handle* h, int64_t first, int64_t count, int32_t* buffer_index) {
     if (!h || !buffer_index) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: data parallelism is not built for sequence models");
-    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
+    if (int rc = dp_refused(h, "eh_dp_fused_step")) return rc;
     if (!h->fused) return fail(h, EH_ESTATE, "eh_dp_fused_step: set the fused_update option first");
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: multi-target models need the global per-target counts before the pass: use eh_dp_counts + eh_dp_grad (fused_update off)");
     if (h->bn_on && !h->bn_ext) return fail(h, EH_ESTATE, "eh_dp_fused_step: input BatchNorm needs the global batch statistics: call eh_dp_bn_stats and all-reduce EH_BUF_BNSTAT first");
@@ -3774,7 +2667,7 @@ int32_t eh_dp_fused_step(eh_handle* h, int64_t first, int64_t count, int32_t* bu
     if (h->chain.n) return fail(h, EH_EUNSUPPORTED, "eh_dp_fused_step: not built for an optimiser chain (the norm needs the all-reduced gradient before the update): use eh_dp_grad + eh_dp_apply");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
-    int rc = check_window(h, sp, first, count, "eh_dp_fused_step");
+    int rc = eh_check_window(h, sp, first, count, "eh_dp_fused_step");
     if (rc) return rc;
     *buffer_index = h->p2p_on ? -1 : (int32_t)(h->gstep % 3);        // -1: the kernels exchange the sums themselves (eh_p2p_attach)
     return do_fused_step(h, sp, h->perm_valid ? h->perm : nullptr, first, count, nullptr);
@@ -3792,13 +2685,11 @@ int32_t eh_set_bn_shift(eh_handle* h, const float* shift, int64_t n) {
 
 int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
     if (!h) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: data parallelism is not built for sequence models");
-    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_bn_stats: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
+    if (int rc = dp_refused(h, "eh_dp_bn_stats")) return rc;
     if (!h->bn_on) return fail(h, EH_ESTATE, "eh_dp_bn_stats: the model has no input BatchNorm");
     HIPCHK(h, hipSetDevice(h->device));
     EhSplit& sp = h->split[EH_SPLIT_TRAIN];
-    int rc = check_window(h, sp, first, count, "eh_dp_bn_stats");
+    int rc = eh_check_window(h, sp, first, count, "eh_dp_bn_stats");
     if (rc) return rc;
     const int* idx = h->perm_valid ? h->perm : nullptr;      // the same samples eh_dp_grad / eh_dp_fused_step will read
     const int nblk = (int)std::max<long long>(1, std::min<long long>(32, (count + 1023) / 1024));
@@ -3812,9 +2703,7 @@ int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
 
 int32_t eh_dp_apply(eh_handle* h, float* loss_out) {
     if (!h) return EH_EINVAL;
-    if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: data parallelism is not built for sequence models");
-    if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)");
-    if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_apply: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
+    if (int rc = dp_refused(h, "eh_dp_apply")) return rc;
     if (!h->opt_ready) return fail(h, EH_ESTATE, "eh_dp_apply: call eh_opt_init first");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_loss_hist(h, 1);

@@ -44,9 +44,10 @@ struct EhSpecKernel {
     size_t lds_bytes;
     const char* what;
     hipError_t (*prepare)(void);
-    hipError_t (*launch)(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args);
-    // the lean form of EH_MODE_TRAIN / EH_MODE_TRAIN_ORD (eh_lean_fold, eh_device.hpp), or nullptr: for arguments inside its contract only
-    hipError_t (*launch_lean)(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args);
+    // lean: the lean form of EH_MODE_TRAIN / EH_MODE_TRAIN_ORD (eh_lean_fold, eh_device.hpp), where the unit holds it (has_lean): for arguments
+    // inside its contract only
+    hipError_t (*launch)(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args, bool lean);
+    bool has_lean;
 };
 #define EH_SPEC_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)
 #define EH_SPEC_DECL(k) extern "C" const EhSpecKernel* eh_spec_##k(void);

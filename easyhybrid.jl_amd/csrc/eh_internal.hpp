@@ -1,6 +1,14 @@
-// Shared by the translation units of libeasyhybrid_hip.so (eh_api.hip: entry points and their kernels; eh_comm.hip: the library's
-// own collectives -- RCCL binding, local groups, the peer-to-peer exchange): the handle behind the opaque eh_handle pointer, the
-// error convention and the few helpers both sides call.  Not installed; the public ABI is include/easyhybrid_hip.h.
+// Shared by the translation units of libeasyhybrid_hip.so: the handle behind the opaque eh_handle pointer, the error convention and the
+// functions that cross units.  The units, each the only instantiation of its kernels:
+//   eh_api.hip    handle lifecycle, options, the training step and epoch, evaluation, the optimiser, graphs, the eh_dp_* seam
+//                 (kernels: eh_kernels.hpp, eh_chain.hpp)
+//   eh_data.hip   eh_set_data / eh_set_sequences, the pinned staging pair, the staged copies (eh_pack_kernel)
+//   eh_lform.hip  the layer-wise execution form (eh_lform.hpp)
+//   eh_lbfgs.hip  L-BFGS (eh_lbfgs.hpp)
+//   eh_mech.hip   the stand-alone mechanistic stage, eh_mech_loss_vjp
+//   eh_seq.hip    the sequence-model kernels (eh_seq.hpp)
+//   eh_comm.hip   the library's own collectives -- RCCL binding, local groups, the peer-to-peer exchange
+// Not installed; the public ABI is include/easyhybrid_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>      // types only: the library is bound at run time, by the first eh_comm_* call (see EhRccl in eh_comm.hip)
@@ -40,6 +48,19 @@ struct EhImg {
     // agg = sum: both 1
     float agg_a, l2s;
 };
+__device__ __forceinline__ bool eh_is_weight(const EhImg& im, int idx) { return idx < im.g_off && (im.imap ? im.imap[idx] < im.b_off : im.wflag[idx] != 0); }
+// d(extra loss) / d theta_idx = 2 * this * theta_idx
+__device__ __forceinline__ float eh_l2_coef(const EhImg& im, int idx) { return im.l2s * (im.l2w ? im.l2w[idx] : (eh_is_weight(im, idx) ? im.l2c : 0.0f)); }
+__device__ __forceinline__ void eh_image_store(const EhImg& im, int idx, float th) {
+    if (idx < im.g_off) {
+        if (im.imap) im.image[im.imap[idx]] = th;      // (layer-wise form: the kernels read the canonical theta itself)
+    } else {   // raw global -> physical value and sigmoid slope (GenericHybridModel.jl:348-352)
+        const int g = idx - im.g_off, j = im.glob_par[g];
+        const float s = 1.0f / (1.0f + expf(-th));
+        im.image[im.phi_off + EH_IMG_PHI + j] = im.glo[g] + (im.ghi[g] - im.glo[g]) * s;
+        im.image[im.phi_off + EH_IMG_DPHI + j] = (im.ghi[g] - im.glo[g]) * s * (1.0f - s);
+    }
+}
 
 // an optimiser chain (eh_opt_init_chain; the kernels are in eh_chain.hpp): handed to them by value
 struct EhChain {
@@ -52,6 +73,20 @@ struct EhChain {
     int thr;                           // ClipNorm(throw = true): a step with a non-finite norm is not applied
 };
 
+// The optimiser in the epilogue of the weight-gradient products (few rows, ONE slab row: the product IS the gradient, un-normalised):
+// the element that would have gone to the slab goes through the update rule into theta / m / v instead -- no slab row written and read
+// back, no reduce + optimiser launch behind the products (8.6 us of the tutorial net's 59 us step at batch 64).  EhLApply: what the
+// host hands over (eh_do_step fills it, eh_lform_train decides; the kernels are in eh_lform.hpp).
+struct EhLApply {
+    float* slab; float* theta; float* m; float* v;
+    const float* sc_in; float* sc_out;
+    EhOpt o; float* loss_slot; float* gradbuf; EhImg im;
+    int loss_kind, n_theta, g_off;
+    const float* part; int nblk;         // the mechanistic stage's rows of partial sums ...
+    const float* tot;                    // ... or, non-null, their sums [16] (a side job of an earlier launch of the step, EhGemmArgs::job_out)
+    unsigned long long* stamps; int stamp_wg;      // diagnostic builds (-DEH_STAMPS): workgroup stamp_wg stamps its phases
+};
+
 // --------------------------------------------------------------------------------------------
 // handle
 // --------------------------------------------------------------------------------------------
@@ -61,11 +96,15 @@ constexpr int EH_EVAL_TILES = 64;        // most tiles one wave of an evaluation
 // the metric shift c_t of a split (eh_set_data): the mean of its first EH_SHIFT_VALID valid values of target t, so that the centred sums of
 // the metrics (sum (y - c)^2 - (sum (y - c))^2 / n) do not cancel in fp32; a target whose record starts with a gap is scanned further
 constexpr long long EH_SHIFT_VALID = 4096;
+enum { EH_MECH_MAXROWS = 65536 };            // eh_mech_loss_vjp: rows of partials (workgroups of the streaming kernel) at most: 4 MiB
+enum { EH_LFORM_ROWS = 64 };                 // layer-wise form: partial slabs of the weight gradients (split over the samples of a minibatch)
 
+struct EhShift4 { float c[EH_MAX_TARG]; };   // the shifts as a kernel argument (eh_count_kernel, eh_moment_*_kernel)
 struct EhSplit {
     float* recs = nullptr;
     long long n = 0;
     float shift[EH_MAX_TARG] = {0, 0, 0, 0};
+    EhShift4 shift4() const { EhShift4 s; for (int t = 0; t < EH_MAX_TARG; ++t) s.c[t] = shift[t]; return s; }
     // sequence models (eh_set_sequences): sample i of the split is the window of W records from starts[i]
     int* starts = nullptr;
     long long nwin = 0;
@@ -167,8 +206,8 @@ struct eh_handle_s {
     float* l_split = nullptr; size_t l_split_cap = 0;    // split-K partial products of the small-batch GEMMs
     unsigned* l_lprog = nullptr; int l_lprog_gen = -1;  // the recorded loss programs as the layer-wise form interprets them (device copy, generation it was made from)
     float* l_dk = nullptr; size_t l_dk_cap = 0;          // every layer's delta of a small-batch step (the weight gradients then run as one grouped launch)
-    bool l_job_done = false;                              // lform_gemm -> lform_train: a few-rows product took the side job of summing the chain's partial rows
-    struct EhLApply* l_apply = nullptr; bool l_applied = false;   // do_step -> lform_train: the optimiser may run in the epilogue of the grouped weight gradients / it did
+    bool l_job_done = false;                              // lform_gemm -> eh_lform_train (eh_lform.hip): a few-rows product took the side job of summing the chain's partial rows
+    EhLApply* l_apply = nullptr; bool l_applied = false;   // eh_do_step -> eh_lform_train: the optimiser may run in the epilogue of the grouped weight gradients / it did
     bool l_tail_fn[12] = {false};
     float* l_ws = nullptr;                               // [Xb | H_0 .. H_{NL-1} | D0 | D1 | O | mech partial rows]
     long long l_cap = 0;                                 // samples the workspace holds
@@ -260,8 +299,47 @@ int flush_pending(eh_handle* h);
         if (rc_) return rc_;              \
     } while (0)
 
+// a device buffer the stream may still be reading grows: drain, free, allocate (cap and need in elements)
+template <class T, class N>
+int eh_grow(eh_handle* h, T** buf, N* cap, N need) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    (void)hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    HIPCHK(h, hipMalloc(buf, (size_t)need * sizeof(T)));
+    *cap = need;
+    return EH_OK;
+}
+
 // bit t set: target t's training loss needs batch moments of the predictions ahead of the pass (two forward-only passes; eh_api.hip)
 unsigned eh_two_pass_mask(const eh_handle* h);
+
+// what every pass over a window of a split hands its kernels: the fields all of them set alike, the rest zero
+inline EhStepArgs eh_step_args(const eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
+    EhStepArgs a{};
+    a.prog = h->prog; a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = count;
+    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
+    return a;
+}
+
+// eh_api.hip, for the units that run steps of their own (eh_lbfgs.hip) or sit inside one (eh_lform.hip).  The three launchers are the only
+// callers of their kernels (eh_kernels.hpp): a unit that needs one of them calls these
+int eh_do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool apply, bool raw, float* loss_slot);
+int eh_check_window(eh_handle* h, const EhSplit& sp, long long first, long long count, const char* who);
+int eh_bn_prepare(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool update, EhStepArgs* a, bool consume = true);
+int eh_launch_count(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* tcount = nullptr);      // per-target weights -> inv_n (tcount: the raw sums too)
+int eh_launch_moment_centre(eh_handle* h, const EhSplit& sp, const float* rows, int nrows);      // rows of moment sums -> the centre of yhat in inv_n
+int eh_launch_moment_coef(eh_handle* h, const EhSplit& sp, const float* rows, int nrows);        // ... about it -> k0 k1 k2 and the loss value in inv_n
+
+// eh_lform.hip: one training step's gradient sums into *rows partial slab rows | forward + metric sums of a window, *rows rows of them in the slab
+int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* rows, bool bn_update);
+int eh_lform_eval(eh_handle* h, const EhSplit& sp, long long first, long long count, float* yhat, float* pout, int* rows);
+
+// eh_lbfgs.hip: eh_destroy's share
+void eh_lbfgs_release(eh_handle* h);
+
+// eh_data.hip: large arrays between the caller's pageable memory and the device, through the pinned staging pair of eh_set_data
+int eh_copy_out(eh_handle* h, float* dst, const float* src_dev, size_t n);
+int eh_copy_in(eh_handle* h, float* dst_dev, const float* src, size_t n);
 
 // eh_destroy's share of eh_comm.hip: leave the communicator / local group, unmap the peers, free the exchange buffers
 void eh_comm_release(eh_handle* h);

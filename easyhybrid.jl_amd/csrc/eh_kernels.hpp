@@ -1,16 +1,12 @@
-// The small kernels around the fused step kernel: partial-slab reduction + optimiser update, the stand-alone mechanistic stage,
-// valid counts, moment coefficients, input BatchNorm statistics, epoch permutation, record packing.  Included by eh_api.hip only
-// (the kernels have external linkage: one translation unit).
+// The small kernels around the fused step kernel: partial-slab reduction + optimiser update, valid counts, moment coefficients, input
+// BatchNorm statistics, epoch permutation.  Included by eh_api.hip only (the kernels have external linkage: one translation unit;
+// the other units reach them through the launchers declared in eh_internal.hpp).
 #pragma once
 #include "eh_internal.hpp"
 
 // --------------------------------------------------------------------------------------------
 // small kernels
 // --------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool eh_is_weight(const EhImg& im, int idx) { return idx < im.g_off && (im.imap ? im.imap[idx] < im.b_off : im.wflag[idx] != 0); }
-// d(extra loss) / d theta_idx = 2 * this * theta_idx
-__device__ __forceinline__ float eh_l2_coef(const EhImg& im, int idx) { return im.l2s * (im.l2w ? im.l2w[idx] : (eh_is_weight(im, idx) ? im.l2c : 0.0f)); }
-
 // the extra loss of the CURRENT parameters (before the optimiser kernel touches them): l2c * sum of squared Dense weights, or sum_i l2w[i] theta_i^2
 __global__ __launch_bounds__(256) void eh_weight_l2_kernel(const float* theta, EhImg im, float* out) {
     __shared__ float red[4];
@@ -28,263 +24,11 @@ __global__ __launch_bounds__(256) void eh_weight_l2_kernel(const float* theta, E
     if (threadIdx.x == 0) *out = im.l2s * (im.l2w ? 1.0f : im.l2c) * ((red[0] + red[1]) + (red[2] + red[3]));
 }
 
-__device__ __forceinline__ void eh_image_store(const EhImg& im, int idx, float th) {
-    if (idx < im.g_off) {
-        if (im.imap) im.image[im.imap[idx]] = th;      // (layer-wise form: the kernels read the canonical theta itself)
-    } else {   // raw global -> physical value and sigmoid slope (GenericHybridModel.jl:348-352)
-        const int g = idx - im.g_off, j = im.glob_par[g];
-        const float s = 1.0f / (1.0f + expf(-th));
-        im.image[im.phi_off + EH_IMG_PHI + j] = im.glo[g] + (im.ghi[g] - im.glo[g]) * s;
-        im.image[im.phi_off + EH_IMG_DPHI + j] = (im.ghi[g] - im.glo[g]) * s * (1.0f - s);
-    }
-}
-
 __global__ void eh_image_kernel(const float* theta, int n_theta, EhImg im) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < n_theta) eh_image_store(im, idx, theta[idx]);
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Mechanistic stage on its own (eh_mech_loss_vjp): o = NN outputs of an MLP that lives OUTSIDE this library -> physical
-// parameters (sigma-scaling) -> M(par, forcings) -> masked MSE summed over the targets -> d loss / d o and the gradient of
-// the raw global parameters.  Pure streaming: 4 (K + F + T) bytes read and 4 K written per sample, ~20-60 flop -- the one
-// stage of the path that the HBM roof bounds.  Every lane owns V consecutive samples (V = 4: 16-byte
-// loads and stores, a wave covers 1 KiB runs of every array); sums leave a workgroup once, as one row of partials.
-// ---------------------------------------------------------------------------------------------------------------------
-struct EhMechArgs {
-    const float* o;                          // [K][ld] NN outputs (raw)
-    const float* frc[EH_MAX_FORC];           // the F forcing arrays in eh_set_data order
-    const float* y[EH_MAX_TARG];             // the T target arrays (NaN = missing)
-    float* d_o;                              // [K][ld] d loss / d o
-    float* yhat;                             // [T][ld] or nullptr
-    long long n, ld;
-    const float* meta;                       // parameter image, PHI block (values / d value d raw of the global and fixed parameters, lo, hi - lo)
-    const unsigned long long* counts;        // valid samples per target (whole call), counted on the device ...
-    unsigned long long counts_v[EH_MAX_TARG];   // ... or handed in by the caller (use_v)
-    int use_v;
-    float* part;                             // [gridDim.x][EH_MECH_PART] partial sums
-    const unsigned* prog;                    // EH_MECH_PROGRAM: the recorded closure (EhStepArgs::prog layout)
-    float agg_a;                             // factor of `agg` on the data loss (EhImg::agg_a)
-    int tiles;                               // > 0: workgroup b owns the `tiles` consecutive 256 V-sample tiles from b * tiles (a front that moves through memory
-                                             // with the dispatch order); 0: grid-stride trips (a capped grid)
-};
-enum { EH_MECH_PART = 16 };                  // [dL/dpar_j (8) | S_t (4) | pad]
-enum { EH_MECH_MAXROWS = 65536 };            // rows of partials (workgroups of the streaming kernel) at most: 4 MiB
-
-template <int V>
-__global__ __launch_bounds__(256) void eh_count_valid_kernel(EhMechArgs a, int T, unsigned long long* counts) {
-    unsigned c[EH_MAX_TARG] = {0, 0, 0, 0};
-    const long long stride = (long long)gridDim.x * 256 * V;
-    for (long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * V; i0 < a.n; i0 += 4 * stride)
-#pragma unroll
-        for (int t = 0; t < EH_MAX_TARG; ++t)
-            if (t < T) {
-                if constexpr (V == 4) {
-                    f32x4 v[4];                                  // four trips requested before the first is examined
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = i0 + u * stride < a.n ? *(const f32x4*)(a.y[t] + i0 + u * stride) : f32x4{0, 0, 0, 0};
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (i0 + u * stride < a.n) c[t] += !__builtin_isnan(v[u][0]) + !__builtin_isnan(v[u][1]) + !__builtin_isnan(v[u][2]) + !__builtin_isnan(v[u][3]);
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (i0 + u * stride < a.n) c[t] += !__builtin_isnan(a.y[t][i0 + u * stride]);
-                }
-            }
-    __shared__ unsigned sh[4][EH_MAX_TARG];
-#pragma unroll
-    for (int t = 0; t < EH_MAX_TARG; ++t) {
-        unsigned v = c[t];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][t] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < T) atomicAdd(&counts[threadIdx.x], (unsigned long long)(sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]));
-}
-
-// (parameters, forcings, outputs) of a registry model: compile-time array sizes, so that a two-parameter model keeps a dozen
-// values per sample in registers, not the 8 + 4 + 4 of the largest one (occupancy is what a streaming kernel lives on)
-// (EH_MECH_PROGRAM, a recorded closure run by the interpreter of eh_device.hpp: the limits of the program format)
-constexpr int eh_mech_np(int m) { return m == EH_MECH_PROGRAM ? EH_MAX_PARAMS : m == EH_MECH_EXPO2POOL ? 4 : (m == EH_MECH_RS_COMPONENTS || m == EH_MECH_RS_COMPONENTS3F) ? 6 : m == EH_MECH_FLUXPART ? 3 : 2; }
-constexpr int eh_mech_nf(int m) { return m == EH_MECH_PROGRAM ? EH_MAX_FORC : m == EH_MECH_FLUXPART ? 2 : m == EH_MECH_RS_COMPONENTS3F ? 3 : 1; }
-constexpr int eh_mech_no(int m) { return (m == EH_MECH_PROGRAM || m == EH_MECH_FLUXPART) ? 3 : 1; }
-
-// (RbQ10: 68 VGPRs, seven waves per SIMD.  Forcing eight -- amdgpu_waves_per_eu(8): 64 VGPRs -- spills two registers, and a kernel
-// with ANY scratch pays for the allocation at every wave launch, which a launch of tens of thousands of short workgroups cannot afford.)
-template <int V, int MECH>
-__global__ __launch_bounds__(256) void eh_mech_vjp_kernel(const EhNet net, EhMechArgs a) {
-    constexpr int NP = eh_mech_np(MECH), NF = eh_mech_nf(MECH), NO = eh_mech_no(MECH), NTG = NO > 1 ? EH_MAX_TARG : 1;
-    float cpar[NP], lo[NP], sc[NP], w[NTG];
-    int row[NP];                                                 // NN output row of a neural parameter, -1 otherwise
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        cpar[j] = a.meta[EH_IMG_PHI + j]; lo[j] = a.meta[EH_IMG_LO + j]; sc[j] = a.meta[EH_IMG_SC + j];
-        row[j] = (((net.par_kind >> (2 * j)) & 3u) == EH_PAR_NEURAL) ? (int)((net.par_idx >> (4 * j)) & 15u) : -1;
-    }
-#pragma unroll
-    for (int t = 0; t < NTG; ++t) {
-        const unsigned long long c = a.use_v ? a.counts_v[t] : a.counts[t];
-        w[t] = (t < net.T && c > 0) ? a.agg_a / (float)c : 0.0f;
-    }
-    float gp[NP], S[NTG];
-    const bool mae = net.loss == EH_LOSS_MAE;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) gp[j] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < NTG; ++t) S[t] = 0.0f;
-    const long long i_first = a.tiles > 0 ? ((long long)blockIdx.x * a.tiles * 256 + threadIdx.x) * V : ((long long)blockIdx.x * 256 + threadIdx.x) * V;
-    const long long i_step = a.tiles > 0 ? 256ll * V : (long long)gridDim.x * 256 * V;
-    // (no std::min here: it takes references, and a reference to a member of the by-value kernarg struct makes the compiler copy the
-    // whole struct to scratch -- 200 bytes per lane and 24 VGPRs more, measured)
-    const long long n_all = a.n, tile_end = (long long)(blockIdx.x + 1) * a.tiles * 256 * V;
-    const long long i_end = (a.tiles > 0 && tile_end < n_all) ? tile_end : n_all;
-    for (long long i = i_first; i < i_end; i += i_step) {
-        float ov[NP][V], fv[NF][V], yv[NTG][V], dov[NP][V], yh[NTG][V];
-        auto ld = [&](const float* p, float (&dst)[V]) {
-            if constexpr (V == 4) { const f32x4 v = *(const f32x4*)(p + i); dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3]; }
-            else dst[0] = p[i];
-        };
-        auto st = [&](float* p, const float (&src)[V]) {
-            if constexpr (V == 4) *(f32x4*)(p + i) = f32x4{src[0], src[1], src[2], src[3]};
-            else p[i] = src[0];
-        };
-        // every load of the tile is requested before the first use
-#pragma unroll
-        for (int j = 0; j < NP; ++j)
-            if (row[j] >= 0) ld(a.o + (long long)row[j] * a.ld, ov[j]);
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            const unsigned col = (net.forc_col >> (8 * f)) & 255u;
-            if (col != 255u) ld(a.frc[col], fv[f]);
-            else
-#pragma unroll
-                for (int e = 0; e < V; ++e) fv[f][e] = 0.0f;
-        }
-#pragma unroll
-        for (int t = 0; t < NTG; ++t)
-            if (t < net.T) ld(a.y[t], yv[t]);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            float par[EH_MAX_PARAMS], sg[NP], dydp[EH_MAX_PARAMS], frc[EH_MAX_FORC];
-#pragma unroll
-            for (int j = NP; j < EH_MAX_PARAMS; ++j) { par[j] = 0.0f; dydp[j] = 0.0f; }
-#pragma unroll
-            for (int f = NF; f < EH_MAX_FORC; ++f) frc[f] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                par[j] = cpar[j]; sg[j] = 0.0f; dydp[j] = 0.0f;
-                if (row[j] >= 0) {
-                    if (net.scale_nn) { const float s = eh_sigmoid(ov[j][e]); par[j] = fmaf(sc[j], s, lo[j]); sg[j] = sc[j] * s * (1.0f - s); }
-                    else { par[j] = ov[j][e]; sg[j] = 1.0f; }
-                }
-            }
-#pragma unroll
-            for (int f = 0; f < NF; ++f) frc[f] = fv[f][e];
-            float yx[2] = {0.0f, 0.0f}, Jx[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-            constexpr bool PROG = MECH == EH_MECH_PROGRAM;
-            float pval[PROG ? EH_PROG_SLOTS : 1], y0;
-            if constexpr (PROG) {
-                eh_prog_forward(a.prog, par, frc, pval);
-                y0 = pval[a.prog[2]];
-                if (net.n_out > 1) yx[0] = pval[a.prog[3]];
-                if (net.n_out > 2) yx[1] = pval[a.prog[4]];
-            } else {
-                y0 = eh_mech_eval(MECH, par, frc, dydp);
-                if constexpr (NO > 1) eh_mech_extra(MECH, par, frc, yx, Jx);
-            }
-            float dy = 0.0f, dyx[2] = {0.0f, 0.0f};
-#pragma unroll
-            for (int t = 0; t < NTG; ++t)
-                if (t < net.T) {
-                    const int oi = NO > 1 ? (int)((net.targ_out >> (2 * t)) & 3u) : 0;
-                    const float y = oi == 0 ? y0 : (oi == 1 ? yx[0] : yx[1]);
-                    yh[t][e] = y;
-                    const float r = __builtin_isnan(yv[t][e]) ? 0.0f : y - yv[t][e];
-                    float d;
-                    if (mae) { S[t] += fabsf(r); d = r > 0.0f ? w[t] : (r < 0.0f ? -w[t] : 0.0f); }      // mean |r| (loss_fn.jl:64-66)
-                    else { S[t] = fmaf(r, r, S[t]); d = 2.0f * w[t] * r; }                              // mean r^2 (loss_fn.jl:61-63)
-                    dy += oi == 0 ? d : 0.0f; dyx[0] += oi == 1 ? d : 0.0f; dyx[1] += oi == 2 ? d : 0.0f;
-                }
-            float padj[PROG ? EH_PROG_SLOTS : 1];
-            if constexpr (PROG) {                                // reverse sweep over the tape (what Zygote derives from the closure)
-                const int nslot = EH_PROG_SLOT_INSTR + (int)a.prog[0];
-                for (int q = 0; q < nslot; ++q) padj[q] = 0.0f;
-                padj[a.prog[2]] += dy;
-                if (net.n_out > 1) padj[a.prog[3]] += dyx[0];
-                if (net.n_out > 2) padj[a.prog[4]] += dyx[1];
-                eh_prog_reverse(a.prog, pval, padj);
-            }
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                float dp = PROG ? padj[PROG ? j : 0] : dy * dydp[j];
-                if (!PROG && NO > 1 && j < 3) dp += dyx[0] * Jx[0][j] + dyx[1] * Jx[1][j];
-                gp[j] += row[j] >= 0 ? 0.0f : dp;
-                dov[j][e] = dp * sg[j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NP; ++j)
-            if (row[j] >= 0) st(a.d_o + (long long)row[j] * a.ld, dov[j]);
-        if (a.yhat)
-#pragma unroll
-            for (int t = 0; t < NTG; ++t)
-                if (t < net.T) st(a.yhat + (long long)t * a.ld, yh[t]);
-    }
-    __shared__ float sh[4][EH_MECH_PART];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        const float v = eh_wave_sum(k < 8 ? (k < NP ? gp[k < NP ? k : 0] : 0.0f) : (k - 8 < NTG ? S[k - 8 < NTG ? k - 8 : 0] : 0.0f));
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) a.part[(long long)blockIdx.x * EH_MECH_PART + threadIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
-
-// rows of partials -> out[0] = loss, out[1 + j] = d loss / d raw global parameter j (canonical parameter order), fixed order:
-// deterministic.  Up to 2 048 rows: eh_mech_finish_kernel alone (one workgroup, 64 row groups x 16 columns, all of a thread's loads
-// -- rows written on other XCDs, each a trip to memory -- requested before the first add).  More rows: eh_mech_fold_kernel first,
-// whose workgroup g folds rows [g rows_per, (g + 1) rows_per) into row g of a second, <= 64-row table for the finish kernel.  (One
-// launch with a ticket for the last workgroup was measured and lost: 13.6 us at 4 096 rows, 37 us at 65 536 -- the release in front
-// of the ticket writes back an L2 -- against 5.1-5.7 us for the plain one-workgroup kernel; profiles/r03/mech_stage_ab.txt.)
-__device__ __forceinline__ float eh_mech_fold_rows(const float* part, int r0, int r1, float (*red)[EH_MECH_PART]) {
-    const int k = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    for (int rb = r0 + grp; rb < r1; rb += 64 * 32) {
-        float v[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) v[u] = rb + 64 * u < r1 ? part[(long long)(rb + 64 * u) * EH_MECH_PART + k] : 0.0f;
-#pragma unroll
-        for (int u = 0; u < 32; u += 4) { s0 += v[u]; s1 += v[u + 1]; s2 += v[u + 2]; s3 += v[u + 3]; }
-    }
-    red[grp][k] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    float s = 0.0f;
-    if (grp == 0)
-        for (int g2 = 0; g2 < 64; ++g2) s += red[g2][k];
-    return s;                                                    // (threads 0..15 hold column k's sum)
-}
-__global__ __launch_bounds__(1024) void eh_mech_fold_kernel(const float* part, int nblk, int rows_per, float* part2) {
-    __shared__ float red[64][EH_MECH_PART];
-    const int r0 = blockIdx.x * rows_per;
-    const float s = eh_mech_fold_rows(part, r0, min(nblk, r0 + rows_per), red);
-    if (threadIdx.x < EH_MECH_PART) part2[blockIdx.x * EH_MECH_PART + threadIdx.x] = s;
-}
-__global__ __launch_bounds__(1024) void eh_mech_finish_kernel(const float* part, int nblk, const EhNet net, const float* meta, const EhMechArgs a, float* out) {
-    __shared__ float red[64][EH_MECH_PART];
-    const int k = threadIdx.x & 15;
-    const float s = eh_mech_fold_rows(part, 0, nblk, red);
-    if (threadIdx.x >= EH_MECH_PART) return;
-    __shared__ float St[EH_MAX_TARG];
-    if (k >= 8 && k < 12) {
-        const unsigned long long c = a.use_v ? a.counts_v[k - 8] : a.counts[k - 8];
-        St[k - 8] = (k - 8 < net.T && c > 0) ? a.agg_a * s / (float)c : 0.0f;
-    }
-    else if (k < 8) out[1 + k] = (k < net.n_par && ((net.par_kind >> (2 * k)) & 3u) == EH_PAR_GLOBAL) ? s * meta[EH_IMG_DPHI + k] : 0.0f;
-    EH_WAVE_SYNC();                                              // (the 16 threads left are lanes of one wave)
-    if (k == 0) out[0] = (St[0] + St[1]) + (St[2] + St[3]);
-}
 
 // Sum the per-workgroup partials of the step kernel (fixed order: deterministic), normalise by the
 // valid count when the step ran with deferred normalisation, and (APPLY) update theta and its
@@ -638,7 +382,6 @@ __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_
 // beta = mean(yhat) / mean(y);  dr/du_i = (w_i - mw) / sqrt(Suu_c Sww_c) - r (u_i - mu) / Suu_c,
 // dalpha/du_i = (u_i - mu) / (alpha Sww_c),  dbeta/du_i = 1 / (n mean(y)).
 // stage 0: the centre of yhat for the moment pass proper = its batch mean (sum (yhat - c) is accurate; the squares are not)
-struct EhShift4 { float c[EH_MAX_TARG]; };
 // (one workgroup per target; targets whose loss needs no batch statistics of yhat are left alone)
 __device__ __forceinline__ bool eh_kind_two_pass(unsigned kind, int T) {
     return (kind >= (unsigned)EH_LOSS_PEARSONLOSS && kind <= (unsigned)EH_LOSS_PBKGELOSS) || (kind == (unsigned)EH_LOSS_RMSE && T > 1);
@@ -878,23 +621,3 @@ __global__ __launch_bounds__(256) void eh_dropout_mask_kernel(unsigned long long
     for (int r = 0; r < 4; ++r)
         if (4 * q + r < width) keep[k * width + 4 * q + r] = (uint8_t)((kb >> r) & 1u);
 }
-
-// (P x N col-major predictors, F forcing arrays, T target arrays) -> N records of C floats
-struct EhPackArgs {
-    const float* x;
-    const float* forc[EH_MAX_FORC];
-    const float* targ[EH_MAX_TARG];
-};
-__global__ void eh_pack_kernel(EhPackArgs a, float* recs, long long n, int P, int F, int T, int planes) {
-    const int C = P + F + T;
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * C) return;
-    const long long s = e / C;
-    const int j = (int)(e % C);
-    float v;
-    if (j < P) v = planes ? a.x[(long long)j * n + s] : a.x[s * P + j];
-    else if (j < P + F) v = a.forc[j - P][s];
-    else v = a.targ[j - P - F][s];
-    recs[e] = v;
-}
-

@@ -1,9 +1,9 @@
-// L-BFGS on the device (the reference's Optimization.jl driver, src/training/train_optimization.jl).  Included by eh_api.hip only,
-// behind eh_kernels.hpp.
+// L-BFGS on the device (the reference's Optimization.jl driver, src/training/train_optimization.jl).  eh_lbfgs.hip is its unit: it defines
+// EH_LBFGS_KERNELS and holds the only instantiation of the decision code and the kernels; everybody else sees the constants and EhLbfgs.
 //
 // One objective evaluation is always the same launches, enqueued without a synchronisation:
 //
-//   do_step(apply = false)     the step kernel and eh_reduce_kernel<false, ...> the handle runs anyway: gradient, loss and valid counts
+//   eh_do_step(apply = false)    the step kernel and eh_reduce_kernel<false, ...> the handle runs anyway: gradient, loss and valid counts
 //                              in gradbuf, at the trial point theta
 //   eh_lbfgs_dots_kernel       every dot product the decision may need, one row of partial sums per workgroup (at most EH_LB_PARTS)
 //   eh_lbfgs_decide_kernel     ONE workgroup: folds the rows in row order, then one thread runs eh_lb_decide -- the weak-Wolfe bisection
@@ -23,10 +23,6 @@
 #pragma once
 #include "eh_internal.hpp"
 
-#ifndef EH_HD
-#define EH_HD __host__ __device__ inline
-#endif
-
 enum { EH_LB_MAX_M = EH_LBFGS_MAX_M, EH_LB_NB = 2 * EH_LBFGS_MAX_M + 1, EH_LB_PARTS = 256, EH_LB_TRACE_ROWS = 4096 };
 // the sums of one evaluation: q[0 .. 8) and, for basis vector j (S_j: j < m, Y_{j-m}: m <= j < 2m), q[8 + 3 j ..] = g.H_j, s.H_j, y.H_j
 enum { EH_LQ_GD = 0, EH_LQ_SY, EH_LQ_YY, EH_LQ_GINF, EH_LQ_GG, EH_LQ_SS, EH_LQ_SG, EH_LQ_YG, EH_LQ_HIST = 8 };
@@ -42,6 +38,31 @@ enum { EH_LA_NOOP = 0, EH_LA_REJECT = 1, EH_LA_ACCEPT = 2, EH_LA_ACCEPT_DONE = 3
 static_assert(EH_LS_ROWS < EH_LBFGS_STATE_DOUBLES, "state");
 static_assert(EH_LR_COEF + EH_LB_NB <= EH_LBFGS_RECORD_DOUBLES, "record");
 static_assert(EH_LB_NQ_MAX <= EH_LBFGS_SUMS_DOUBLES, "sums");
+
+// the handle's side (eh_lbfgs_init)
+enum { EH_LB_DBL_HEAD = EH_LBFGS_STATE_DOUBLES + EH_LBFGS_RECORD_DOUBLES + EH_LB_NB * EH_LB_NB };      // state | record | Gram matrix, then the partial rows
+// n_theta up to which one workgroup takes dots, decision and update in one launch.  Measured (tools/bench_lbfgs.py --threshold,
+// profiles/r15/lbfgs.txt): at 338 parameters one launch is 2.2 us per evaluation cheaper than three (55.8 against 58.0), at 1 186 it is
+// 15.9 us dearer (86.8 against 70.9) -- 0.037 us per parameter against 0.015, so the two meet near 440.
+enum { EH_LB_ONE_MAX = 384 };
+struct EhLbfgs {
+    bool active = false, batch_set = false, empty = false;
+    eh_lbfgs_opts o{};
+    int maxiters = 100, nq = 0, m_cap = 0;
+    float* vec = nullptr;          // x0 | g0 | d | S[m] | Y[m]
+    double* dbl = nullptr;         // EH_LB_DBL_HEAD doubles, then [EH_LB_PARTS][nq]
+    float* trace = nullptr;
+    int* idx = nullptr;            // the batch's indices where the caller's were on the host
+    long long idx_cap = 0;
+    int split = 0;
+    const int* didx = nullptr;
+    long long first = 0, count = 0;
+};
+
+#ifdef EH_LBFGS_KERNELS
+#ifndef EH_HD
+#define EH_HD __host__ __device__ inline
+#endif
 
 EH_HD bool eh_lb_finite(double x) { return x - x == 0.0; }
 
@@ -221,26 +242,6 @@ EH_HD int eh_lb_decide(const eh_lbfgs_opts& o, int maxiters, double* st, double*
     if (done) { st[EH_LS_DONE] = done; rec[EH_LR_ACTION] = EH_LA_ACCEPT_PAUSE; }      // maxiters: the next search is set up, theta stays at the accepted point
     return 1;
 }
-
-// the handle's side (eh_lbfgs_init)
-enum { EH_LB_DBL_HEAD = EH_LBFGS_STATE_DOUBLES + EH_LBFGS_RECORD_DOUBLES + EH_LB_NB * EH_LB_NB };      // state | record | Gram matrix, then the partial rows
-// n_theta up to which one workgroup takes dots, decision and update in one launch.  Measured (tools/bench_lbfgs.py --threshold,
-// profiles/r15/lbfgs.txt): at 338 parameters one launch is 2.2 us per evaluation cheaper than three (55.8 against 58.0), at 1 186 it is
-// 15.9 us dearer (86.8 against 70.9) -- 0.037 us per parameter against 0.015, so the two meet near 440.
-enum { EH_LB_ONE_MAX = 384 };
-struct EhLbfgs {
-    bool active = false, batch_set = false, empty = false;
-    eh_lbfgs_opts o{};
-    int maxiters = 100, nq = 0, m_cap = 0;
-    float* vec = nullptr;          // x0 | g0 | d | S[m] | Y[m]
-    double* dbl = nullptr;         // EH_LB_DBL_HEAD doubles, then [EH_LB_PARTS][nq]
-    float* trace = nullptr;
-    int* idx = nullptr;            // the batch's indices where the caller's were on the host
-    long long idx_cap = 0;
-    int split = 0;
-    const int* didx = nullptr;
-    long long first = 0, count = 0;
-};
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // kernels
@@ -445,3 +446,4 @@ __global__ __launch_bounds__(256) void eh_lbfgs_resume_kernel(EhLbfgsArgs a, EhI
     }
     if (threadIdx.x == 0) a.st[EH_LS_DONE] = 0.0;
 }
+#endif      // EH_LBFGS_KERNELS

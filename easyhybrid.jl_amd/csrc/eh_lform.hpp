@@ -14,7 +14,16 @@
 // GenericHybridModel.jl:236-256) IS the [in][out] row-major operand these GEMMs want, and dW^T comes out in the same order: no
 // parameter image, no index maps.  Same arithmetic as the fused kernels (fp32 products, fp32 sums; only the summation order
 // differs), same slab / gradbuf contract, so reduce + optimiser, the data-parallel seam and the epoch driver are shared.
+//
+// eh_lform.hip is the unit of this form: it defines EH_LFORM_KERNELS and holds the only instantiation of the kernels below.  Everybody else
+// sees the constants here and, in eh_internal.hpp, EhLApply and EH_LFORM_ROWS.
 #pragma once
+#include "eh_internal.hpp"
+// the few-rows tail chain (eh_lform_tailchain_kernel below): its limits and launch shape
+enum { EH_LTAIL_MAXL = EH_MAX_HIDDEN + 1, EH_LTAIL_MAXW = 256, EH_LTAIL_THREADS = 512, EH_LTAIL_RED = 4 * EH_LTAIL_THREADS, EH_LTAIL_RED2 = 1024, EH_LTAIL_PAD = 64,
+       EH_LTAIL_FD = 8, EH_LTAIL_BU = 4 };      // weight fragments a thread keeps in flight: rows of its k slice (forward), passes over the k rows (delta)
+
+#ifdef EH_LFORM_KERNELS
 #include "eh_wide_bf16.hpp"      // EhMechAcc, eh_mech_stage_lane
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -40,19 +49,8 @@ struct EhGemmArgs {
     const float* job_part; float* job_out; int job_nblk;
 };
 
-// The optimiser in the epilogue of the weight-gradient products (few rows, ONE slab row: the product IS the gradient, un-normalised):
-// the element that would have gone to the slab goes through the update rule into theta / m / v instead -- no slab row written and read
-// back, no reduce + optimiser launch behind the products (8.6 us of the tutorial net's 59 us step at batch 64).  EhLApply: what the
-// host hands over; EhLApplyS: what a workgroup keeps in LDS once it has the step's normalisation (the sums of the mechanistic stage).
-struct EhLApply {
-    float* slab; float* theta; float* m; float* v;
-    const float* sc_in; float* sc_out;
-    EhOpt o; float* loss_slot; float* gradbuf; EhImg im;
-    int loss_kind, n_theta, g_off;
-    const float* part; int nblk;         // the mechanistic stage's rows of partial sums ...
-    const float* tot;                    // ... or, non-null, their sums [16] (a side job of an earlier launch of the step, EhGemmArgs::job_out)
-    unsigned long long* stamps; int stamp_wg;      // diagnostic builds (-DEH_STAMPS): workgroup stamp_wg stamps its phases
-};
+// (EhLApply, what the host hands over: eh_internal.hpp -- eh_api.hip fills it; EhLApplyS: what a workgroup keeps in LDS once it has the step's
+//  normalisation, the sums of the mechanistic stage)
 struct EhLApplyS { float* slab; float* theta; float* m; float* v; EhOpt o; float scale, bt1, bt2; int go, use_m, use_v; unsigned long long* stamps; const float* bt; };
 #ifdef EH_STAMPS
 #define EH_LSTAMP(S, i) do { __builtin_amdgcn_sched_barrier(0); if ((S)->stamps && threadIdx.x == 0) { (S)->stamps[2 * (i)] = __builtin_readcyclecounter(); (S)->stamps[2 * (i) + 1] = wall_clock64(); } __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -1170,8 +1168,7 @@ __global__ __launch_bounds__(256) void eh_lform_tail_kernel(const float* part, i
 // (lane = 4 adjacent columns, a lane group per k row, butterfly sum).  Every sum in a fixed order: deterministic.  What the weight-
 // gradient products (grouped launch, eh_dw_group_kernel) need -- H_l, dZ_l -- goes to global memory on the way.
 // Suffix: every layer from `first` on has in, out <= 256 (EH_LTAIL_MAXW); each workgroup streams its weights from L2 twice.
-enum { EH_LTAIL_MAXL = EH_MAX_HIDDEN + 1, EH_LTAIL_MAXW = 256, EH_LTAIL_THREADS = 512, EH_LTAIL_RED = 4 * EH_LTAIL_THREADS, EH_LTAIL_RED2 = 1024, EH_LTAIL_PAD = 64,
-       EH_LTAIL_FD = 8, EH_LTAIL_BU = 4 };      // weight fragments a thread keeps in flight: rows of its k slice (forward), passes over the k rows (delta)
+// (the EH_LTAIL_* constants: at the head of this file)
 struct EhLTailLayer {
     const float* W; const float* b;      // canonical [in][out] row-major weights, bias [out]
     float* H; float* Z;                  // (hidden layers) activations [B][out] out; pre-activations out when the layer's activation is swish, else null
@@ -2280,3 +2277,4 @@ __global__ __launch_bounds__(EH_LTAIL_THREADS, 1) void eh_lform_tailkeep_kernel(
     if (t.Dbelow) backward(0, L0, w0, F0, g0, n00, k00, on0, t.Dbelow);
     EH_STAMP(15);
 }
+#endif      // EH_LFORM_KERNELS

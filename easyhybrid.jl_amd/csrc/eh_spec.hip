@@ -76,7 +76,18 @@ hipError_t prepare() {
 #endif
     return e;
 }
-hipError_t launch(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args) {
+hipError_t launch(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args, bool lean) {
+    if (lean) {      // the lean form (the caller has checked the contract: eh_lean_args_ok)
+#ifdef EH_SPEC_LEAN
+        if (!eh_lean_args_ok(*args)) return hipErrorInvalidValue;
+        if (mode == EH_MODE_TRAIN) hipLaunchKernelGGL((EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
+        else if (mode == EH_MODE_TRAIN_ORD) hipLaunchKernelGGL((EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN_ORD)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
+        else return hipErrorNotSupported;
+        return hipGetLastError();
+#else
+        return hipErrorNotSupported;
+#endif
+    }
 #if EH_SPEC_FAMILY == 3
     if (mode == EH_MODE_TRAIN && args->rmap) return hipErrorNotSupported;      // (the sample-owned kernel writes plain canonical slab rows)
 #endif
@@ -94,23 +105,15 @@ hipError_t launch(int mode, int grid, hipStream_t stream, const EhNet* net, cons
     else return hipErrorNotSupported;
     return hipGetLastError();
 }
-// the lean form (the caller has checked the contract: eh_lean_args_ok)
 #ifdef EH_SPEC_LEAN
-hipError_t launch_lean(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args) {
-    if (!eh_lean_args_ok(*args)) return hipErrorInvalidValue;
-    if (mode == EH_MODE_TRAIN) hipLaunchKernelGGL((EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
-    else if (mode == EH_MODE_TRAIN_ORD) hipLaunchKernelGGL((EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN_ORD)), dim3(grid), dim3(64 * NW), LDS, stream, *net, *args);
-    else return hipErrorNotSupported;
-    return hipGetLastError();
-}
-constexpr auto LAUNCH_LEAN = &launch_lean;
+constexpr bool HAS_LEAN = true;
 #else
-constexpr hipError_t (*LAUNCH_LEAN)(int, int, hipStream_t, const EhNet*, const EhStepArgs*) = nullptr;
+constexpr bool HAS_LEAN = false;
 #endif
 #define EH_STR_(x) #x
 #define EH_STR(x) EH_STR_(x)
 const EhSpecKernel spec = {EhNet{EH_SPEC_NET}, EH_SPEC_FAMILY != 0, EH_SPEC_FAMILY >= 2 ? (EH_SPEC_NSPLIT == 3 ? 1 : 2) : 0, NBI, NBH, NL, NT, NW, ACT, FAST, EH_SPEC_FAMILY == 3 ? 1 : 0, LDS,
-                           "descriptor " EH_STR(EH_SPEC_ID) " of csrc/Makefile, specialised ahead of time", &prepare, &launch, LAUNCH_LEAN};
+                           "descriptor " EH_STR(EH_SPEC_ID) " of csrc/Makefile, specialised ahead of time", &prepare, &launch, HAS_LEAN};
 }   // namespace
 
 #define EH_CAT_(a) eh_spec_##a
