@@ -24,6 +24,8 @@ EH_BUF_GRAD, EH_BUF_THETA, EH_BUF_OPT_M, EH_BUF_OPT_V, EH_BUF_GACC, EH_BUF_BNSTA
 ACTIVATIONS = {"tanh": 0, "sigmoid": 1, "relu": 2, "swish": 3, "identity": 4}
 EH_ACT_PER_NET = 5        # MultiNN: net k uses net_activation[k]
 EH_LAYER_LSTM = 16        # net_activation[l] of a hidden layer that is Recurrence(LSTMCell) (sequence models)
+EH_LAYER_GRU = 24         # ... Recurrence(GRUCell)
+EH_LAYER_RNN = 32         # ... Recurrence(RNNCell(.., act)): EH_LAYER_RNN + ACTIVATIONS[act]
 EH_MAX_SEQ_WINDOW = 64
 OPT_RULES = {"Adam": 0, "AdamW": 1, "RMSProp": 2, "Descent": 3}
 TRAINING_LOSSES = {"mse": 0, "rmse": 1, "mae": 2, "nseLoss": 3, "pearsonLoss": 4, "kgeLoss": 5, "pbkgeLoss": 6}

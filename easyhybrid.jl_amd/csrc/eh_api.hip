@@ -568,14 +568,16 @@ static void stream_pool_give(int device, hipStream_t s) {
     (void)hipStreamDestroy(s);
 }
 
-// Sequence models (EH_LAYER_LSTM in the per-layer activation slots): 0 = the descriptor has no LSTM layer, 1 = the one shape that is
-// built -- Dense(P -> I) -> LSTM(I -> H) -> Dense(H -> H) -> Dense(H -> K), eh_seq.hpp --, otherwise the status of the refusal.
+// Sequence models (EH_LAYER_LSTM, EH_LAYER_GRU or EH_LAYER_RNN + activation in the per-layer activation slots; the messages say "LSTM"
+// for every cell): 0 = the descriptor has no recurrent layer, 1 = the one shape that is built -- Dense(P -> I) -> cell(I -> H) ->
+// Dense(H -> H) -> Dense(H -> K), eh_seq.hpp --, otherwise the status of the refusal.
+static bool seq_layer_code(int a) { return a == EH_LAYER_LSTM || a == EH_LAYER_GRU || (a >= EH_LAYER_RNN && a <= EH_LAYER_RNN + EH_ACT_IDENTITY); }
 static int seq_desc_check(const eh_model_desc* d) {
     if (d->activation != EH_ACT_PER_NET) return 0;
     const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
     int n_lstm = 0, at = -1;
     for (int l = 0; l < na; ++l)
-        if (d->net_activation[l] == EH_LAYER_LSTM) { if (at < 0) at = l; ++n_lstm; }
+        if (seq_layer_code(d->net_activation[l])) { if (at < 0) at = l; ++n_lstm; }
     if (!n_lstm) return 0;
     if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a MultiNN sequence model (EH_LAYER_LSTM with n_nets = %d)", d->n_nets);
     if (at == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_LSTM at hidden layer 0: the LSTM layer takes the Dense layer in front of it");
@@ -637,7 +639,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         if (na < 1 || na > EH_MAX_HIDDEN) return fail(nullptr, EH_EINVAL, "eh_create: per-layer activations need 1..%d hidden layers (n_hidden = %d)", EH_MAX_HIDDEN, d->n_hidden);
         bool same = true;
         for (int k = 0; k < na; ++k) {
-            if (seq && d->net_activation[k] == EH_LAYER_LSTM) { same = false; continue; }
+            if (seq && seq_layer_code(d->net_activation[k])) { same = false; continue; }
             if (d->net_activation[k] < 0 || d->net_activation[k] > EH_ACT_IDENTITY)
                 return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown activation id %d for %s %d", d->net_activation[k], d->n_nets > 0 ? "net" : "hidden layer", k);
             same = same && d->net_activation[k] == d->net_activation[0];
@@ -782,11 +784,14 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
             in = o;
         }
     }
-    if (seq) {      // Dense-in | weight_ih, weight_hh, bias_ih, bias_hh | head Dense | output Dense
-        const int P = d->n_predictors, I = d->hidden[0], H = d->hidden[1];
+    if (seq) {      // Dense-in | weight_ih, weight_hh, bias_ih, bias_hh (NG gate blocks of H rows each) | head Dense | output Dense
+        const int P = d->n_predictors, I = d->hidden[0], H = d->hidden[1], code = d->net_activation[1];
+        h->seq_cell = code == EH_LAYER_LSTM ? EH_SEQ_CELL_LSTM : (code == EH_LAYER_GRU ? EH_SEQ_CELL_GRU : EH_SEQ_CELL_RNN);
+        h->seq_act_cell = h->seq_cell == EH_SEQ_CELL_RNN ? code - EH_LAYER_RNN : 0;
+        const int NG = eh_seq_gates(h->seq_cell);
         int* o = h->seq_off;
-        o[EH_SEQ_WIN] = 0; o[EH_SEQ_BIN] = I * P; o[EH_SEQ_WIH] = o[EH_SEQ_BIN] + I; o[EH_SEQ_WHH] = o[EH_SEQ_WIH] + 4 * H * I;
-        o[EH_SEQ_BIH] = o[EH_SEQ_WHH] + 4 * H * H; o[EH_SEQ_BHH] = o[EH_SEQ_BIH] + 4 * H; o[EH_SEQ_WHD] = o[EH_SEQ_BHH] + 4 * H;
+        o[EH_SEQ_WIN] = 0; o[EH_SEQ_BIN] = I * P; o[EH_SEQ_WIH] = o[EH_SEQ_BIN] + I; o[EH_SEQ_WHH] = o[EH_SEQ_WIH] + NG * H * I;
+        o[EH_SEQ_BIH] = o[EH_SEQ_WHH] + NG * H * H; o[EH_SEQ_BHH] = o[EH_SEQ_BIH] + NG * H; o[EH_SEQ_WHD] = o[EH_SEQ_BHH] + NG * H;
         o[EH_SEQ_BHD] = o[EH_SEQ_WHD] + H * H; o[EH_SEQ_WOUT] = o[EH_SEQ_BHD] + H; o[EH_SEQ_BOUT] = o[EH_SEQ_WOUT] + K * H;
         off = o[EH_SEQ_BOUT] + K;
         h->seq = true; h->seq_I = I; h->seq_H = H; h->seq_nbi = (I + 15) / 16; h->seq_nbh = (H + 15) / 16;
@@ -827,7 +832,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     h->C = n.P + n.F + n.T;
     h->n_par = d->n_params;
     h->n_acc = n.n_theta + 1 + n.T + 2;      // [grad | S | n_valid per target | Sy | Syy]
-    if (seq && h->n_acc > eh_seq_row_cap(h->seq_nbi, h->seq_nbh)) {
+    if (seq && h->n_acc > eh_seq_row_cap(h->seq_nbi, h->seq_nbh, h->seq_cell)) {
         delete h;
         return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model of %d parameters (the slab row is staged in LDS)", n.n_theta);
     }
@@ -1518,7 +1523,7 @@ constexpr long long EH_SEQ_WS_CAP = 256ll << 20;      // bytes of backward works
 static int seq_grid_for(const eh_handle* h, const EhSplit& sp, long long count, bool train) {
     const long long ntiles = (count + 15) / 16;
     long long grid = std::max<long long>(1, std::min<long long>((ntiles + EH_SEQ_NW - 1) / EH_SEQ_NW, std::min(h->max_blocks, h->slab_rows)));
-    if (train) grid = std::max<long long>(1, std::min<long long>(grid, EH_SEQ_WS_CAP / (4 * EH_SEQ_NW * eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow))));
+    if (train) grid = std::max<long long>(1, std::min<long long>(grid, EH_SEQ_WS_CAP / (4 * EH_SEQ_NW * eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow, h->seq_cell))));
     return (int)grid;
 }
 static EhSeqArgs seq_args(const eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
@@ -1527,7 +1532,7 @@ static EhSeqArgs seq_args(const eh_handle* h, const EhSplit& sp, const int* idx,
     a.W = sp.W; a.ow = sp.ow; a.lam = sp.lam;
     a.theta = TH(h); a.meta = h->image + h->arch->phi_off; a.slab = h->slab; a.n_acc = h->n_acc;
     a.shift = sp.shift[0];
-    a.I = h->seq_I; a.H = h->seq_H; a.act_in = h->seq_act_in; a.act_hd = h->seq_act_hd;
+    a.I = h->seq_I; a.H = h->seq_H; a.act_in = h->seq_act_in; a.act_hd = h->seq_act_hd; a.act_cell = h->seq_act_cell;
     for (int k = 0; k < EH_SEQ_NOFF; ++k) a.off[k] = h->seq_off[k];
     a.prog = h->prog;
     return a;
@@ -1541,7 +1546,7 @@ static eh_handle_s::JitEntry* seq_jit_entry(eh_handle* h) {
     h->jit.emplace_back(new eh_handle_s::JitEntry());
     eh_handle_s::JitEntry* je = h->jit.back().get();
     je->arch = h->arch; je->variant = 0; je->fast = 0; je->spec = false; je->p2p = false; je->net = h->net; je->loss_gen = 0;
-    const bool ok = eh_jit_build_seq(h->desc, h->seq_nbi, h->seq_nbh, &je->k, &je->log);
+    const bool ok = eh_jit_build_seq(h->desc, h->seq_nbi, h->seq_nbh, h->seq_cell, &je->k, &je->log);
     je->state.store(ok ? 1 : -1, std::memory_order_release);
     if (!ok) { h->jit_log = je->log; h->jit_failed = true; return nullptr; }
     return je;
@@ -1558,7 +1563,7 @@ static void seq_jit_verify(eh_handle* h, eh_handle_s::JitEntry* je, int grid, co
     std::vector<float> part[2] = {std::vector<float>(n), std::vector<float>(n)};
     bool ran = true;
     for (int k = 0; k < 2 && ran; ++k) {
-        ran = (k == 0 ? eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a)
+        ran = (k == 0 ? eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a, h->seq_cell)
                       : eh_jit_launch_seq(&je->k, EH_SEQ_TRAIN, grid, h->stream, &net, &a)) == hipSuccess &&
               hipMemcpyAsync(part[k].data(), a.slab, n * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
     }
@@ -1592,13 +1597,13 @@ static hipError_t seq_launch(eh_handle* h, int mode, int grid, const EhSeqArgs& 
         h->jit_log = std::string("launch of the run-time compiled sequence kernel failed: ") + hipGetErrorString(e);
     }
     const int head = h->net.mech == EH_MECH_PROGRAM ? EH_SEQ_HEAD_PROG : (h->net.n_out > 1 ? EH_SEQ_HEAD_MULTI : EH_SEQ_HEAD_MECH);
-    return eh_seq_launch(h->seq_nbi, h->seq_nbh, mode, head, grid, h->stream, h->net, a);
+    return eh_seq_launch(h->seq_nbi, h->seq_nbh, mode, head, grid, h->stream, h->net, a, h->seq_cell);
 }
 static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out) {
     if (!sp.starts) return fail(h, EH_ESTATE, "sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
     const int grid = seq_grid_for(h, sp, count, true);
     EhSeqArgs a = seq_args(h, sp, idx, first, count);
-    a.ws_wave = eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow);
+    a.ws_wave = eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow, h->seq_cell);
     const long long need = (long long)grid * EH_SEQ_NW * a.ws_wave;      // sized by the grid actually launched
     if (need > h->seq_ws_floats) { if (int rc = eh_grow(h, &h->seq_ws, &h->seq_ws_floats, need)) return rc; }
     a.ws = h->seq_ws;

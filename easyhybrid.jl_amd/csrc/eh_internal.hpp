@@ -193,7 +193,7 @@ struct eh_handle_s {
     bool opt_ready = false;
     // sequence models (eh_seq.hpp): Dense-in -> LSTM -> head Dense -> output Dense over windows (EH_LAYER_LSTM); always the step + reduce pair
     bool seq = false;
-    int seq_I = 0, seq_H = 0, seq_nbi = 0, seq_nbh = 0, seq_act_in = 0, seq_act_hd = 0;
+    int seq_I = 0, seq_H = 0, seq_nbi = 0, seq_nbh = 0, seq_act_in = 0, seq_act_hd = 0, seq_cell = 0, seq_act_cell = 0;      // (seq_cell: EH_SEQ_CELL_*)
     int seq_off[10] = {0};           // canonical offsets of the ten leaves (EH_SEQ_WIN .. EH_SEQ_BOUT)
     float* seq_ws = nullptr;         // what the backward needs of every step, per wave of the grid (allocated outside graph capture)
     long long seq_ws_floats = 0;

@@ -1,19 +1,28 @@
-// The sequence-model kernels (eh_seq.hpp) as a translation unit of their own: one instantiation per padded block count of the
-// LSTM's input and hidden widths, per mode and per form of the head's mechanistic stage (EH_SEQ_HEAD_*).
+// The sequence-model kernels (eh_seq.hpp): one instantiation per padded block count of the cell's input and hidden widths, per mode and
+// per form of the head's mechanistic stage (EH_SEQ_HEAD_*).  Compiled once per recurrent cell (-DEH_SEQ_UNIT_CELL=<EH_SEQ_CELL_*>, the
+// Makefile's eh_seq.o / eh_seq_gru.o / eh_seq_rnn.o) so that the cells build side by side; the LSTM's unit also holds the dispatch.
 #define EH_SEQ_KERNELS
 #include "eh_seq.hpp"
 
-int eh_seq_row_cap(int nbi, int nbh) {
-    return nbi == 1 ? (nbh == 1 ? EhSeqGeom<1, 1>::L_TILE : EhSeqGeom<1, 2>::L_TILE) : (nbh == 1 ? EhSeqGeom<2, 1>::L_TILE : EhSeqGeom<2, 2>::L_TILE);
-}
+#ifndef EH_SEQ_UNIT_CELL
+#define EH_SEQ_UNIT_CELL EH_SEQ_CELL_LSTM
+#endif
+#if EH_SEQ_UNIT_CELL == 0
+#define EH_SEQ_UNIT_LAUNCH eh_seq_launch_lstm
+#elif EH_SEQ_UNIT_CELL == 1
+#define EH_SEQ_UNIT_LAUNCH eh_seq_launch_gru
+#else
+#define EH_SEQ_UNIT_LAUNCH eh_seq_launch_rnn
+#endif
+constexpr int CELL = EH_SEQ_UNIT_CELL;
 
 template <int NBI, int NBH, int HEAD>
 static hipError_t seq_go_head(int mode, int grid, hipStream_t s, const EhNet& net, const EhSeqArgs& a) {
     const dim3 g((unsigned)grid), b(64 * EH_SEQ_NW);
     switch (mode) {
-        case EH_SEQ_TRAIN: hipLaunchKernelGGL((eh_seq_kernel<NBI, NBH, EH_SEQ_TRAIN, HEAD>), g, b, 0, s, net, a); break;
-        case EH_SEQ_EVAL: hipLaunchKernelGGL((eh_seq_kernel<NBI, NBH, EH_SEQ_EVAL, HEAD>), g, b, 0, s, net, a); break;
-        case EH_SEQ_FORWARD: hipLaunchKernelGGL((eh_seq_kernel<NBI, NBH, EH_SEQ_FORWARD, HEAD>), g, b, 0, s, net, a); break;
+        case EH_SEQ_TRAIN: hipLaunchKernelGGL((eh_seq_kernel<NBI, NBH, EH_SEQ_TRAIN, HEAD, CELL>), g, b, 0, s, net, a); break;
+        case EH_SEQ_EVAL: hipLaunchKernelGGL((eh_seq_kernel<NBI, NBH, EH_SEQ_EVAL, HEAD, CELL>), g, b, 0, s, net, a); break;
+        case EH_SEQ_FORWARD: hipLaunchKernelGGL((eh_seq_kernel<NBI, NBH, EH_SEQ_FORWARD, HEAD, CELL>), g, b, 0, s, net, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -28,10 +37,32 @@ static hipError_t seq_go(int mode, int head, int grid, hipStream_t s, const EhNe
     }
 }
 
-hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a) {
+hipError_t EH_SEQ_UNIT_LAUNCH(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a) {
     if (nbi == 1 && nbh == 1) return seq_go<1, 1>(mode, head, grid, stream, net, a);
     if (nbi == 1 && nbh == 2) return seq_go<1, 2>(mode, head, grid, stream, net, a);
     if (nbi == 2 && nbh == 1) return seq_go<2, 1>(mode, head, grid, stream, net, a);
     if (nbi == 2 && nbh == 2) return seq_go<2, 2>(mode, head, grid, stream, net, a);
     return hipErrorInvalidValue;                                // (no kernel: an error, never another path)
 }
+
+#if EH_SEQ_UNIT_CELL == 0
+hipError_t eh_seq_launch_gru(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a);
+hipError_t eh_seq_launch_rnn(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a);
+
+template <int C>
+static int seq_row_cap(int nbi, int nbh) {
+    return nbi == 1 ? (nbh == 1 ? EhSeqGeom<1, 1, C>::L_TILE : EhSeqGeom<1, 2, C>::L_TILE) : (nbh == 1 ? EhSeqGeom<2, 1, C>::L_TILE : EhSeqGeom<2, 2, C>::L_TILE);
+}
+int eh_seq_row_cap(int nbi, int nbh, int cell) {
+    return cell == EH_SEQ_CELL_GRU ? seq_row_cap<EH_SEQ_CELL_GRU>(nbi, nbh) : (cell == EH_SEQ_CELL_RNN ? seq_row_cap<EH_SEQ_CELL_RNN>(nbi, nbh) : seq_row_cap<EH_SEQ_CELL_LSTM>(nbi, nbh));
+}
+
+hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a, int cell) {
+    switch (cell) {
+        case EH_SEQ_CELL_LSTM: return eh_seq_launch_lstm(nbi, nbh, mode, head, grid, stream, net, a);
+        case EH_SEQ_CELL_GRU: return eh_seq_launch_gru(nbi, nbh, mode, head, grid, stream, net, a);
+        case EH_SEQ_CELL_RNN: return eh_seq_launch_rnn(nbi, nbh, mode, head, grid, stream, net, a);
+        default: return hipErrorInvalidValue;
+    }
+}
+#endif

@@ -1,5 +1,6 @@
-// Sequence models: Dense(P -> I, act) -> Recurrence(LSTMCell(I -> H)) -> Dense(H -> H, act) -> Dense(H -> K) over windows of W consecutive
-// records, with back-propagation through time.  eh_step_body's idiom stretched over time:
+// Sequence models: Dense(P -> I, act) -> Recurrence(cell(I -> H)) -> Dense(H -> H, act) -> Dense(H -> K) over windows of W consecutive
+// records, with back-propagation through time; the cell is an LSTMCell, a GRUCell or an RNNCell (template
+// parameter CELL; what follows is told for the LSTM).  eh_step_body's idiom stretched over time:
 //
 //   * one wave owns a tile of 16 windows for the whole forward and backward chain; the window sits on the MFMA N dimension and every
 //     product runs on v_mfma_f32_16x16x4_f32.  A C/D block (lane (n = lane & 15, g = lane >> 4), register r <-> row 4g + r, window n)
@@ -20,12 +21,21 @@
 //     compiled at run time around the generated eh_jit_fwd / eh_jit_rev (eh_jit.hip, EH_JIT_MECH) the tape is registers.
 //   * epilogue: the workgroup's waves are gathered in wave order into one slab row [n_theta gradient | S | n | Sy | Syy]
 //     (eh_reduce_kernel's contract), so the step is bit-reproducible.
+//   * the other cells change the recurrent step alone -- geometry, head, Dense-in and epilogue are shared.  GRUCell, gate blocks
+//     [r | z | n]: h' = (1 - z) n + z h with n = tanh(W_in x + b_in + r (W_hn h + b_hn)); the reset gate multiplies the hidden product, so
+//     that product is a fourth accumulator chain q of its own and b_hn a bias row of its own (r and z fold b_ih + b_hh as the LSTM does).
+//     Parked per step: r, z, n, q, h_t.  RNNCell: h' = act(W_ih x + W_hh h + b_ih + b_hh), act one of the Dense activations
+//     (EhSeqArgs::act_cell); parked: the pre-activation and h_t.  h_{t-1} is the h_t of the record before for both.
 #pragma once
 #include "eh_device.hpp"
 
 enum { EH_SEQ_TRAIN = 0, EH_SEQ_EVAL = 1, EH_SEQ_FORWARD = 2 };
 enum { EH_SEQ_HEAD_MECH = 0, EH_SEQ_HEAD_MULTI = 1, EH_SEQ_HEAD_PROG = 2 };      // the mechanistic stage of the head: see above
 constexpr int EH_SEQ_NW = 4;                 // waves per workgroup: one per SIMD (the accumulators take most of a wave's 512 registers)
+enum { EH_SEQ_CELL_LSTM = 0, EH_SEQ_CELL_GRU = 1, EH_SEQ_CELL_RNN = 2 };         // the recurrent cell
+constexpr int eh_seq_gates(int cell) { return cell == EH_SEQ_CELL_LSTM ? 4 : (cell == EH_SEQ_CELL_GRU ? 3 : 1); }        // gate blocks of weight_ih / weight_hh
+constexpr int eh_seq_bias_rows(int cell) { return cell == EH_SEQ_CELL_RNN ? 1 : 4; }                                      // bias blocks in LDS (GRU: r | z | n_ih | n_hh)
+constexpr int eh_seq_parked(int cell) { return cell == EH_SEQ_CELL_LSTM ? 6 : (cell == EH_SEQ_CELL_GRU ? 5 : 2); }       // C/D blocks parked per step and hidden block
 constexpr int EH_SEQ_TS = 20;                // row stride of the transposition tile (16 windows + 4: 16-byte rows, no two rows in one bank group)
 
 // canonical offsets into flat theta (ComponentArray order) and the LDS layout of the zero-padded parameters
@@ -51,22 +61,24 @@ struct EhSeqArgs {
     int I, H, act_in, act_hd;
     int off[EH_SEQ_NOFF];
     const unsigned* prog;    // EH_SEQ_HEAD_PROG: the recorded closure (EhStepArgs::prog layout)
+    int act_cell;            // EH_SEQ_CELL_RNN: the cell's activation
 };
 
-template <int NBI, int NBH>
+template <int NBI, int NBH, int CELL = EH_SEQ_CELL_LSTM>
 struct EhSeqGeom {
+    static constexpr int NG = eh_seq_gates(CELL), NB = eh_seq_bias_rows(CELL);
     static constexpr int RI = 16 * NBI, RH = 16 * NBH, SP = 36, SI = RI + 4, SH = RH + 4;
-    static constexpr int L_WIN = 0, L_WIH = L_WIN + RI * SP, L_WHH = L_WIH + 4 * RH * SI, L_WHD = L_WHH + 4 * RH * SH, L_WOUT = L_WHD + RH * SH,
-                         L_BIN = L_WOUT + 16 * SH, L_BG = L_BIN + RI, L_BHD = L_BG + 4 * RH, L_BOUT = L_BHD + RH, L_TILE = L_BOUT + 16,
-                         L_GB = L_TILE + EH_SEQ_NW * 16 * EH_SEQ_TS, L_END = L_GB + EH_SEQ_NW * 4 * RH;
+    static constexpr int L_WIN = 0, L_WIH = L_WIN + RI * SP, L_WHH = L_WIH + NG * RH * SI, L_WHD = L_WHH + NG * RH * SH, L_WOUT = L_WHD + RH * SH,
+                         L_BIN = L_WOUT + 16 * SH, L_BG = L_BIN + RI, L_BHD = L_BG + NB * RH, L_BOUT = L_BHD + RH, L_TILE = L_BOUT + 16,
+                         L_GB = L_TILE + EH_SEQ_NW * 16 * EH_SEQ_TS, L_END = L_GB + EH_SEQ_NW * NB * RH;
 };
 
 #ifndef __HIPCC_RTC__      // (host side; this header is also compiled at run time, by hiprtc, around a recorded closure: eh_jit.hip)
-// floats of workspace one wave needs: 6 NBH blocks per step, NBH + 1 per head step, 256 floats a block
-inline long long eh_seq_ws_floats(int nbh, int W, int ow) { return ((long long)W * 6 * nbh + (long long)ow * (nbh + 1)) * 256; }
-int eh_seq_row_cap(int nbi, int nbh);        // accumulators a slab row may hold (the row is staged in LDS over the parameters)
-// head: EH_SEQ_HEAD_* of the model (a missing instantiation is an error, never another path)
-hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a);
+// floats of workspace one wave needs: eh_seq_parked(cell) NBH blocks per step, NBH + 1 per head step, 256 floats a block
+inline long long eh_seq_ws_floats(int nbh, int W, int ow, int cell = EH_SEQ_CELL_LSTM) { return ((long long)W * eh_seq_parked(cell) * nbh + (long long)ow * (nbh + 1)) * 256; }
+int eh_seq_row_cap(int nbi, int nbh, int cell = EH_SEQ_CELL_LSTM);        // accumulators a slab row may hold (the row is staged in LDS over the parameters)
+// head: EH_SEQ_HEAD_* of the model, cell: EH_SEQ_CELL_* (a missing instantiation is an error, never another path)
+hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a, int cell = EH_SEQ_CELL_LSTM);
 #endif
 
 #ifdef EH_SEQ_KERNELS
@@ -81,10 +93,11 @@ __device__ __forceinline__ f32x4 eh_seq_dact4(int id, const f32x4 z) { return f3
 __device__ __forceinline__ f32x4 eh_seq_sig4(const f32x4 z) { return f32x4{eh_sigmoid(z[0]), eh_sigmoid(z[1]), eh_sigmoid(z[2]), eh_sigmoid(z[3])}; }
 __device__ __forceinline__ f32x4 eh_seq_tanh4(const f32x4 z) { return f32x4{eh_tanh(z[0]), eh_tanh(z[1]), eh_tanh(z[2]), eh_tanh(z[3])}; }
 
-template <int NBI, int NBH, int MODE, int HEAD = EH_SEQ_HEAD_MECH>
+template <int NBI, int NBH, int MODE, int HEAD = EH_SEQ_HEAD_MECH, int CELL = EH_SEQ_CELL_LSTM>
 __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net, const EhSeqArgs a) {
-    using G = EhSeqGeom<NBI, NBH>;
-    constexpr bool TRAIN = MODE == EH_SEQ_TRAIN, PROG = HEAD == EH_SEQ_HEAD_PROG;
+    using G = EhSeqGeom<NBI, NBH, CELL>;
+    constexpr bool TRAIN = MODE == EH_SEQ_TRAIN, PROG = HEAD == EH_SEQ_HEAD_PROG, LSTM = CELL == EH_SEQ_CELL_LSTM, GRU = CELL == EH_SEQ_CELL_GRU;
+    constexpr int NG = G::NG, NB = G::NB, PER = eh_seq_parked(CELL);
     constexpr int RH = G::RH, SP = G::SP, SI = G::SI, SH = G::SH;
     // (a closure's tape takes registers at the head step that the registry models leave free: with PROG the gradient of the two head biases
     //  is summed over the windows at every head step and kept in a wave-private LDS row behind the layout, as the gate biases' is)
@@ -98,12 +111,19 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     {
         const float* th = a.theta;
         for (int e = tid; e < I * P; e += 64 * EH_SEQ_NW) lds[G::L_WIN + (e % I) * SP + e / I] = th[a.off[EH_SEQ_WIN] + e];
-        for (int e = tid; e < 4 * H * I; e += 64 * EH_SEQ_NW) { const int rf = e % (4 * H); lds[G::L_WIH + ((rf / H) * RH + rf % H) * SI + e / (4 * H)] = th[a.off[EH_SEQ_WIH] + e]; }
-        for (int e = tid; e < 4 * H * H; e += 64 * EH_SEQ_NW) { const int rf = e % (4 * H); lds[G::L_WHH + ((rf / H) * RH + rf % H) * SH + e / (4 * H)] = th[a.off[EH_SEQ_WHH] + e]; }
+        for (int e = tid; e < NG * H * I; e += 64 * EH_SEQ_NW) { const int rf = e % (NG * H); lds[G::L_WIH + ((rf / H) * RH + rf % H) * SI + e / (NG * H)] = th[a.off[EH_SEQ_WIH] + e]; }
+        for (int e = tid; e < NG * H * H; e += 64 * EH_SEQ_NW) { const int rf = e % (NG * H); lds[G::L_WHH + ((rf / H) * RH + rf % H) * SH + e / (NG * H)] = th[a.off[EH_SEQ_WHH] + e]; }
         for (int e = tid; e < H * H; e += 64 * EH_SEQ_NW) lds[G::L_WHD + (e % H) * SH + e / H] = th[a.off[EH_SEQ_WHD] + e];
         for (int e = tid; e < K * H; e += 64 * EH_SEQ_NW) lds[G::L_WOUT + (e % K) * SH + e / K] = th[a.off[EH_SEQ_WOUT] + e];
         for (int e = tid; e < I; e += 64 * EH_SEQ_NW) lds[G::L_BIN + e] = th[a.off[EH_SEQ_BIN] + e];
-        for (int e = tid; e < 4 * H; e += 64 * EH_SEQ_NW) lds[G::L_BG + (e / H) * RH + e % H] = th[a.off[EH_SEQ_BIH] + e] + th[a.off[EH_SEQ_BHH] + e];
+        if constexpr (GRU) {      // r and z fold their two biases; b_in and b_hn stay apart (rows 2 and 3)
+            for (int e = tid; e < 3 * H; e += 64 * EH_SEQ_NW) {
+                const float bi = th[a.off[EH_SEQ_BIH] + e], bh = th[a.off[EH_SEQ_BHH] + e];
+                if (e < 2 * H) lds[G::L_BG + (e / H) * RH + e % H] = bi + bh;
+                else { lds[G::L_BG + 2 * RH + e - 2 * H] = bi; lds[G::L_BG + 3 * RH + e - 2 * H] = bh; }
+            }
+        } else
+        for (int e = tid; e < NG * H; e += 64 * EH_SEQ_NW) lds[G::L_BG + (e / H) * RH + e % H] = th[a.off[EH_SEQ_BIH] + e] + th[a.off[EH_SEQ_BHH] + e];
         for (int e = tid; e < H; e += 64 * EH_SEQ_NW) lds[G::L_BHD + e] = th[a.off[EH_SEQ_BHD] + e];
         for (int e = tid; e < K; e += 64 * EH_SEQ_NW) lds[G::L_BOUT + e] = th[a.off[EH_SEQ_BOUT] + e];
     }
@@ -112,8 +132,8 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     float* const TT = lds + G::L_TILE + wave * 16 * EH_SEQ_TS;
     // the gate biases' gradient: summed over the 16 windows every step and kept in a wave-private LDS row (as per-lane registers they
     // are 32 more at H = 32, which the W_ih / W_hh accumulators leave no room for)
-    float* const GB = lds + G::L_GB + wave * 4 * RH;
-    for (int e = lane; e < 4 * RH; e += 64) GB[e] = 0.0f;
+    float* const GB = lds + G::L_GB + wave * NB * RH;
+    for (int e = lane; e < NB * RH; e += 64) GB[e] = 0.0f;
     float* const HB = lds + G::L_END + (PROG ? wave * (RH + 16) : 0);      // PROG: [RH] head Dense bias | [16] output Dense bias
     if constexpr (PROG) { for (int e = lane; e < RH + 16; e += 64) HB[e] = 0.0f; }
     // C/D block -> its transpose as an MFMA operand with the window on K: element r of the result = M[row n][window 4g + r]
@@ -135,6 +155,11 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     };
     auto ldB = [&](int base, int row0) -> f32x4 { return *reinterpret_cast<const f32x4*>(lds + base + row0 + 4 * g); };      // a bias in C/D layout
 
+    // h_t of a step, block hb, from the step's parked record (w4: this lane's word of the record's first block)
+    auto h_of = [&](const f32x4* w4, int hb) -> f32x4 {
+        if constexpr (LSTM) return w4[(hb * 6 + 3) * 64] * w4[(hb * 6 + 5) * 64];      // o tanh(c)
+        else return w4[(hb * PER + PER - 1) * 64];
+    };
     // Dense-in of one record per window: pre-activation blocks zx
     auto dense_in = [&](const float* rec, f32x4 (&zx)[NBI]) {
         f32x4 p[2];
@@ -152,10 +177,10 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
 
     // ---- accumulators (TRAIN): they live across all steps and tiles of the wave ------------------------------------------------
     const f32x4 Z4 = {0.0f, 0.0f, 0.0f, 0.0f};
-    f32x4 gWih[4][NBH][NBI], gWhh[4][NBH][NBH], gWin[NBI][2], gBin[NBI], gWhd[NBH][NBH], gBhd[NBH], gWout[NBH], gBout = Z4;
+    f32x4 gWih[NG][NBH][NBI], gWhh[NG][NBH][NBH], gWin[NBI][2], gBin[NBI], gWhd[NBH][NBH], gBhd[NBH], gWout[NBH], gBout = Z4;
     float gp[EH_MAX_PARAMS], est[EH_EVAL_STATS];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < NG; ++q)
 #pragma unroll
         for (int hb = 0; hb < NBH; ++hb) {
 #pragma unroll
@@ -180,7 +205,7 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     const int W = a.W, t_head = a.W - a.ow;
     const long long ntiles = (a.count + 15) / 16;
     float* const ws = TRAIN ? a.ws + (long long)(blockIdx.x * EH_SEQ_NW + wave) * a.ws_wave : nullptr;
-    float* const wsh = TRAIN ? ws + (long long)W * 6 * NBH * 256 : nullptr;
+    float* const wsh = TRAIN ? ws + (long long)W * PER * NBH * 256 : nullptr;
 
     for (long long tile = (long long)blockIdx.x * EH_SEQ_NW + wave; tile < ntiles; tile += (long long)gridDim.x * EH_SEQ_NW) {
         const long long kwin = tile * 16 + n;
@@ -204,39 +229,84 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
             f32x4 hn[NBH];
 #pragma unroll
             for (int hb = 0; hb < NBH; ++hb) {
-                // the four gate blocks of these 16 rows are independent chains: issued interleaved, each one's dependent MFMA latency
-                // hides behind the issue of the other three
-                f32x4 z[4];
+                if constexpr (LSTM) {
+                    // the four gate blocks of these 16 rows are independent chains: issued interleaved, each one's dependent MFMA latency
+                    // hides behind the issue of the other three
+                    f32x4 z[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) z[q] = ldB(G::L_BG, q * RH + hb * 16);
+                    for (int q = 0; q < 4; ++q) z[q] = ldB(G::L_BG, q * RH + hb * 16);
 #pragma unroll
-                for (int ib = 0; ib < NBI; ++ib) {
-                    f32x4 A[4];
+                    for (int ib = 0; ib < NBI; ++ib) {
+                        f32x4 A[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) A[q] = ldA(G::L_WIH, SI, q * RH + hb * 16, ib * 16);
+                        for (int q = 0; q < 4; ++q) A[q] = ldA(G::L_WIH, SI, q * RH + hb * 16, ib * 16);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
+                        for (int r = 0; r < 4; ++r)
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], x[ib][r], z[q], 0, 0, 0);
-                }
+                            for (int q = 0; q < 4; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], x[ib][r], z[q], 0, 0, 0);
+                    }
 #pragma unroll
-                for (int kb = 0; kb < NBH; ++kb) {
-                    f32x4 A[4];
+                    for (int kb = 0; kb < NBH; ++kb) {
+                        f32x4 A[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) A[q] = ldA(G::L_WHH, SH, q * RH + hb * 16, kb * 16);
+                        for (int q = 0; q < 4; ++q) A[q] = ldA(G::L_WHH, SH, q * RH + hb * 16, kb * 16);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
+                        for (int r = 0; r < 4; ++r)
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], h[kb][r], z[q], 0, 0, 0);
-                }
-                const f32x4 gi = eh_seq_sig4(z[0]), gf = eh_seq_sig4(z[1]), gg = eh_seq_tanh4(z[2]), go = eh_seq_sig4(z[3]);
-                const f32x4 cp = c[hb];
-                c[hb] = gf * cp + gi * gg;
-                const f32x4 tc = eh_seq_tanh4(c[hb]);
-                hn[hb] = go * tc;
-                if constexpr (TRAIN) {
-                    f32x4* const w4 = reinterpret_cast<f32x4*>(ws) + ((long long)(t * NBH + hb) * 6) * 64 + lane;
-                    w4[0] = gi; w4[64] = gf; w4[128] = gg; w4[192] = go; w4[256] = cp; w4[320] = tc;
+                            for (int q = 0; q < 4; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], h[kb][r], z[q], 0, 0, 0);
+                    }
+                    const f32x4 gi = eh_seq_sig4(z[0]), gf = eh_seq_sig4(z[1]), gg = eh_seq_tanh4(z[2]), go = eh_seq_sig4(z[3]);
+                    const f32x4 cp = c[hb];
+                    c[hb] = gf * cp + gi * gg;
+                    const f32x4 tc = eh_seq_tanh4(c[hb]);
+                    hn[hb] = go * tc;
+                    if constexpr (TRAIN) {
+                        f32x4* const w4 = reinterpret_cast<f32x4*>(ws) + ((long long)(t * NBH + hb) * 6) * 64 + lane;
+                        w4[0] = gi; w4[64] = gf; w4[128] = gg; w4[192] = go; w4[256] = cp; w4[320] = tc;
+                    }
+                } else if constexpr (GRU) {
+                    // four chains again: r, z, the input half of n, and q = W_hn h + b_hn (the reset gate multiplies q: it is not summed into n's chain)
+                    f32x4 z[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) z[q] = ldB(G::L_BG, q * RH + hb * 16);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib) {
+                        f32x4 A[3];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) A[q] = ldA(G::L_WIH, SI, q * RH + hb * 16, ib * 16);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) z[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], x[ib][r], z[q], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) {
+                        f32x4 A[3];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) A[q] = ldA(G::L_WHH, SH, q * RH + hb * 16, kb * 16);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) z[q == 2 ? 3 : q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q][r], h[kb][r], z[q == 2 ? 3 : q], 0, 0, 0);
+                    }
+                    const f32x4 gr = eh_seq_sig4(z[0]), gz = eh_seq_sig4(z[1]), gq = z[3];
+                    const f32x4 gn = eh_seq_tanh4(z[2] + gr * gq);
+                    hn[hb] = (1.0f - gz) * gn + gz * h[hb];
+                    if constexpr (TRAIN) {
+                        f32x4* const w4 = reinterpret_cast<f32x4*>(ws) + ((long long)(t * NBH + hb) * PER) * 64 + lane;
+                        w4[0] = gr; w4[64] = gz; w4[128] = gn; w4[192] = gq; w4[256] = hn[hb];
+                    }
+                } else {
+                    f32x4 z = ldB(G::L_BG, hb * 16);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib) z = eh_seq_mfma4(ldA(G::L_WIH, SI, hb * 16, ib * 16), x[ib], z);
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) z = eh_seq_mfma4(ldA(G::L_WHH, SH, hb * 16, kb * 16), h[kb], z);
+                    hn[hb] = eh_seq_act4(a.act_cell, z);
+                    if constexpr (TRAIN) {
+                        f32x4* const w4 = reinterpret_cast<f32x4*>(ws) + ((long long)(t * NBH + hb) * PER) * 64 + lane;
+                        w4[0] = z; w4[64] = hn[hb];
+                    }
                 }
             }
 #pragma unroll
@@ -379,14 +449,14 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
         for (int hb = 0; hb < NBH; ++hb) { dh[hb] = Z4; dc[hb] = Z4; }
         for (int t = W - 1; t >= 0; --t) {
             const float* const rec = a.recs + (long long)(st + t) * C;
-            const f32x4* const w4 = reinterpret_cast<const f32x4*>(ws) + (long long)t * NBH * 6 * 64 + lane;
+            const f32x4* const w4 = reinterpret_cast<const f32x4*>(ws) + (long long)t * NBH * PER * 64 + lane;
             if (t >= t_head) {
                 // ---- head backward: its delta joins dh of this step ----
                 const f32x4* const wh = reinterpret_cast<const f32x4*>(wsh) + (long long)(t - t_head) * (NBH + 1) * 64 + lane;
                 const f32x4 dob = wh[NBH * 64];
                 f32x4 z1[NBH], hT[NBH];
 #pragma unroll
-                for (int hb = 0; hb < NBH; ++hb) { z1[hb] = wh[hb * 64]; hT[hb] = tr(w4[(hb * 6 + 3) * 64] * w4[(hb * 6 + 5) * 64]); }
+                for (int hb = 0; hb < NBH; ++hb) { z1[hb] = wh[hb * 64]; hT[hb] = tr(h_of(w4, hb)); }
                 const f32x4 dobT = tr(dob);
                 if constexpr (PROG) {
 #pragma unroll
@@ -409,47 +479,94 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                 }
             }
             // ---- the operands of this step's weight gradients, window on K ----
-            f32x4 zx[NBI], xT[NBI], hpT[NBH], dhn[NBH], dx[NBI];
+            f32x4 zx[NBI], xT[NBI], hpT[NBH], hpv[NBH], dhn[NBH], dx[NBI];
             dense_in(rec, zx);
 #pragma unroll
             for (int ib = 0; ib < NBI; ++ib) { xT[ib] = tr(eh_seq_act4(a.act_in, zx[ib])); dx[ib] = Z4; }
 #pragma unroll
             for (int kb = 0; kb < NBH; ++kb) {
                 f32x4 hp = Z4;
-                if (t > 0) hp = w4[(kb * 6 + 3 - NBH * 6) * 64] * w4[(kb * 6 + 5 - NBH * 6) * 64];      // h_{t-1} = o_{t-1} tanh(c_{t-1})
+                if (t > 0) hp = h_of(w4 - NBH * PER * 64, kb);      // h_{t-1}: the record before (LSTM: o_{t-1} tanh(c_{t-1}))
                 hpT[kb] = tr(hp);
+                hpv[kb] = hp;                                       // (the GRU's own update reads it untransposed)
                 dhn[kb] = Z4;
             }
 #pragma unroll
             for (int hb = 0; hb < NBH; ++hb) {
-                const f32x4 gi = w4[(hb * 6 + 0) * 64], gf = w4[(hb * 6 + 1) * 64], gg = w4[(hb * 6 + 2) * 64], go = w4[(hb * 6 + 3) * 64],
-                            cp = w4[(hb * 6 + 4) * 64], tc = w4[(hb * 6 + 5) * 64];
-                const f32x4 dcn = dc[hb] + dh[hb] * go * (1.0f - tc * tc);
-                f32x4 dz[4];
-                dz[0] = dcn * gg * gi * (1.0f - gi);
-                dz[1] = dcn * cp * gf * (1.0f - gf);
-                dz[2] = dcn * gi * (1.0f - gg * gg);
-                dz[3] = dh[hb] * tc * go * (1.0f - go);
-                dc[hb] = dcn * gf;
+                if constexpr (LSTM) {
+                    const f32x4 gi = w4[(hb * 6 + 0) * 64], gf = w4[(hb * 6 + 1) * 64], gg = w4[(hb * 6 + 2) * 64], go = w4[(hb * 6 + 3) * 64],
+                                cp = w4[(hb * 6 + 4) * 64], tc = w4[(hb * 6 + 5) * 64];
+                    const f32x4 dcn = dc[hb] + dh[hb] * go * (1.0f - tc * tc);
+                    f32x4 dz[4];
+                    dz[0] = dcn * gg * gi * (1.0f - gi);
+                    dz[1] = dcn * cp * gf * (1.0f - gf);
+                    dz[2] = dcn * gi * (1.0f - gg * gg);
+                    dz[3] = dh[hb] * tc * go * (1.0f - go);
+                    dc[hb] = dcn * gf;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
+                    for (int q = 0; q < 4; ++q) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dz[q][r]); if (n == 0) GB[q * RH + hb * 16 + 4 * g + r] += v; }
-                    const f32x4 dzT = tr(dz[q]);
+                        for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dz[q][r]); if (n == 0) GB[q * RH + hb * 16 + 4 * g + r] += v; }
+                        const f32x4 dzT = tr(dz[q]);
 #pragma unroll
-                    for (int ib = 0; ib < NBI; ++ib) gWih[q][hb][ib] = eh_seq_mfma4(dzT, xT[ib], gWih[q][hb][ib]);
+                        for (int ib = 0; ib < NBI; ++ib) gWih[q][hb][ib] = eh_seq_mfma4(dzT, xT[ib], gWih[q][hb][ib]);
 #pragma unroll
-                    for (int kb = 0; kb < NBH; ++kb) gWhh[q][hb][kb] = eh_seq_mfma4(dzT, hpT[kb], gWhh[q][hb][kb]);
+                        for (int kb = 0; kb < NBH; ++kb) gWhh[q][hb][kb] = eh_seq_mfma4(dzT, hpT[kb], gWhh[q][hb][kb]);
+                    }
+                    // dh_{t-1} += W_hh^T dz, dx_t += W_ih^T dz: the four gates as interleaved chains again
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) dhn[kb] = eh_seq_mfma4(ldAT(G::L_WHH, SH, q * RH + hb * 16, kb * 16), dz[q], dhn[kb]);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) dx[ib] = eh_seq_mfma4(ldAT(G::L_WIH, SI, q * RH + hb * 16, ib * 16), dz[q], dx[ib]);
+                } else if constexpr (GRU) {
+                    const f32x4 gr = w4[(hb * 5 + 0) * 64], gz = w4[(hb * 5 + 1) * 64], gn = w4[(hb * 5 + 2) * 64], gq = w4[(hb * 5 + 3) * 64];
+                    f32x4 dz[4];                                    // [r | z | n_ih | n_hh]: the GB row's order
+                    dz[2] = dh[hb] * (1.0f - gz) * (1.0f - gn * gn);
+                    dz[1] = dh[hb] * (hpv[hb] - gn) * gz * (1.0f - gz);
+                    dz[0] = dz[2] * gq * gr * (1.0f - gr);
+                    dz[3] = dz[2] * gr;
+                    dhn[hb] += dh[hb] * gz;
+                    f32x4 dzT[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dz[q][r]); if (n == 0) GB[q * RH + hb * 16 + 4 * g + r] += v; }
+                        dzT[q] = tr(dz[q]);
+                    }
+                    // W_ih sees [r | z | n_ih], W_hh [r | z | n_hh]
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+                        for (int ib = 0; ib < NBI; ++ib) gWih[q][hb][ib] = eh_seq_mfma4(dzT[q], xT[ib], gWih[q][hb][ib]);
+#pragma unroll
+                        for (int kb = 0; kb < NBH; ++kb) gWhh[q][hb][kb] = eh_seq_mfma4(dzT[q == 2 ? 3 : q], hpT[kb], gWhh[q][hb][kb]);
+                    }
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb)
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) dhn[kb] = eh_seq_mfma4(ldAT(G::L_WHH, SH, q * RH + hb * 16, kb * 16), dz[q == 2 ? 3 : q], dhn[kb]);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib)
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) dx[ib] = eh_seq_mfma4(ldAT(G::L_WIH, SI, q * RH + hb * 16, ib * 16), dz[q], dx[ib]);
+                } else {
+                    const f32x4 dz = dh[hb] * eh_seq_dact4(a.act_cell, w4[(hb * 2) * 64]);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { const float v = eh_row16_sum(dz[r]); if (n == 0) GB[hb * 16 + 4 * g + r] += v; }
+                    const f32x4 dzT = tr(dz);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib) gWih[0][hb][ib] = eh_seq_mfma4(dzT, xT[ib], gWih[0][hb][ib]);
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) gWhh[0][hb][kb] = eh_seq_mfma4(dzT, hpT[kb], gWhh[0][hb][kb]);
+#pragma unroll
+                    for (int kb = 0; kb < NBH; ++kb) dhn[kb] = eh_seq_mfma4(ldAT(G::L_WHH, SH, hb * 16, kb * 16), dz, dhn[kb]);
+#pragma unroll
+                    for (int ib = 0; ib < NBI; ++ib) dx[ib] = eh_seq_mfma4(ldAT(G::L_WIH, SI, hb * 16, ib * 16), dz, dx[ib]);
                 }
-                // dh_{t-1} += W_hh^T dz, dx_t += W_ih^T dz: the four gates as interleaved chains again
-#pragma unroll
-                for (int kb = 0; kb < NBH; ++kb)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dhn[kb] = eh_seq_mfma4(ldAT(G::L_WHH, SH, q * RH + hb * 16, kb * 16), dz[q], dhn[kb]);
-#pragma unroll
-                for (int ib = 0; ib < NBI; ++ib)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dx[ib] = eh_seq_mfma4(ldAT(G::L_WIH, SI, q * RH + hb * 16, ib * 16), dz[q], dx[ib]);
             }
 #pragma unroll
             for (int kb = 0; kb < NBH; ++kb) dh[kb] = dhn[kb];
@@ -512,13 +629,13 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
         for (int w = 0; w < EH_SEQ_NW; ++w) {                  // wave order: the sums meet in one fixed order
             if (wave == w) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
+                for (int q = 0; q < NG; ++q)
 #pragma unroll
                     for (int hb = 0; hb < NBH; ++hb) {
 #pragma unroll
-                        for (int ib = 0; ib < NBI; ++ib) putW(gWih[q][hb][ib], a.off[EH_SEQ_WIH], 4 * H, q * H, H, hb * 16, ib * 16, I);
+                        for (int ib = 0; ib < NBI; ++ib) putW(gWih[q][hb][ib], a.off[EH_SEQ_WIH], NG * H, q * H, H, hb * 16, ib * 16, I);
 #pragma unroll
-                        for (int kb = 0; kb < NBH; ++kb) putW(gWhh[q][hb][kb], a.off[EH_SEQ_WHH], 4 * H, q * H, H, hb * 16, kb * 16, H);
+                        for (int kb = 0; kb < NBH; ++kb) putW(gWhh[q][hb][kb], a.off[EH_SEQ_WHH], NG * H, q * H, H, hb * 16, kb * 16, H);
                     }
 #pragma unroll
                 for (int ib = 0; ib < NBI; ++ib) {
@@ -539,7 +656,15 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                         else if (e >= RH && e - RH < K) row[a.off[EH_SEQ_BOUT] + e - RH] += HB[e];
                     }
                 } else putB(gBout, a.off[EH_SEQ_BOUT], K, 0);
-                for (int e = lane; e < 4 * RH; e += 64)        // b_ih and b_hh: the same gradient, written to both
+                if constexpr (GRU) {                           // r and z as below; the n block of b_ih is row 2, that of b_hh row 3
+                    for (int e = lane; e < 4 * RH; e += 64)
+                        if (e % RH < H) {
+                            const int blk = e / RH, o = (blk < 2 ? blk : 2) * H + e % RH;
+                            if (blk != 3) row[a.off[EH_SEQ_BIH] + o] += GB[e];
+                            if (blk != 2) row[a.off[EH_SEQ_BHH] + o] += GB[e];
+                        }
+                } else
+                for (int e = lane; e < NG * RH; e += 64)       // b_ih and b_hh: the same gradient, written to both
                     if (e % RH < H) { const int o = (e / RH) * H + e % RH; row[a.off[EH_SEQ_BIH] + o] += GB[e]; row[a.off[EH_SEQ_BHH] + o] += GB[e]; }
                 if (lane == 0) {
                     row[net.n_theta] += sums[0]; row[net.n_theta + 1] += sums[3]; row[net.n_theta + 2] += sums[1]; row[net.n_theta + 3] += sums[2];

@@ -22,6 +22,7 @@ const LIB = Ref{String}(get(ENV, "EASYHYBRID_HIP_LIB", joinpath(@__DIR__, "..", 
 
 const EH_MAX_HIDDEN, EH_MAX_PARAMS, EH_MAX_FORC, EH_MAX_TARG = 8, 8, 4, 4
 const EH_SPLIT_TRAIN, EH_SPLIT_VAL = Int32(0), Int32(1)
+const EH_LAYER_LSTM, EH_LAYER_GRU, EH_LAYER_RNN = Int32(16), Int32(24), Int32(32)      # net_activation[l] of a recurrent hidden layer (EH_LAYER_RNN + the RNNCell's activation id)
 
 # mirror of `eh_model_desc` (field order and widths exactly as in the header)
 struct EhModelDesc
@@ -599,7 +600,7 @@ dp_counts!(e::HybridEngine, first::Integer, count::Integer) = check(e, @ccall LI
 """
     set_sequences!(e, starts; split, input_window = 10, output_window = 1, lead_time = 1)
 
-Sequence models (`hidden_layers = Chain(Recurrence(LSTMCell(I => H)))`, descriptor layer id `EH_LAYER_LSTM = 16`): sample `i` of `split`
+Sequence models (`hidden_layers = Chain(Recurrence(LSTMCell(I => H)))`, descriptor layer id `EH_LAYER_LSTM`; likewise `GRUCell`, `EH_LAYER_GRU`, and `RNNCell`, `EH_LAYER_RNN` + its activation id): sample `i` of `split`
 becomes the window of `input_window` rows that starts at row `starts[i]` (0-based) of the series `set_data!` loaded into that split
 (`src/data/sequences.jl:203-229`).  From then on `first`, `count` and the minibatch indices of the step, epoch, loss-and-gradient, eval and
 forward calls count windows, and the prediction arrays hold `count * output_window` values as `[window][j]`.

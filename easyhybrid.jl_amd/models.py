@@ -212,6 +212,28 @@ class LSTMCell:
         return f"LSTMCell({self.in_dims} => {self.out_dims})"
 
 
+class GRUCell:
+    """Lux `GRUCell(in => out)` as a DESCRIPTION (defaults only: use_bias = true, train_state = false, zero initial h).  Gate blocks
+    [r | z | n]: h' = (1 - z) n + z h, n = tanh(W_in x + b_in + r (W_hn h + b_hn)) -- torch.nn.GRUCell's algebra and order."""
+
+    def __init__(self, in_dims: int, out_dims: int):
+        self.in_dims, self.out_dims = int(in_dims), int(out_dims)
+
+    def __repr__(self):
+        return f"GRUCell({self.in_dims} => {self.out_dims})"
+
+
+class RNNCell:
+    """Lux `RNNCell(in => out, activation)` as a DESCRIPTION (defaults only: use_bias = true, train_state = false, zero initial h):
+    h' = activation(W_ih x + b_ih + W_hh h + b_hh), the activation one of the Dense layers' five (default tanh)."""
+
+    def __init__(self, in_dims: int, out_dims: int, activation="tanh"):
+        self.in_dims, self.out_dims, self.activation = int(in_dims), int(out_dims), _act_name(activation)
+
+    def __repr__(self):
+        return f"RNNCell({self.in_dims} => {self.out_dims}, {self.activation})"
+
+
 class Recurrence:
     """Lux `Recurrence(cell; return_sequence)`.  The reference always runs it with return_sequence = true (NNModels.jl:172-176)."""
 
@@ -266,6 +288,24 @@ DROPOUT_MAX_WIDTH, DROPOUT_MAX_LAYERS = 64, 3      # the per-wave fused kernel f
 
 
 LSTM_LAYER = "lstm"      # the "activation" of a hidden layer that is Recurrence(LSTMCell): EH_LAYER_LSTM in the descriptor
+GRU_LAYER = "gru"        # ... Recurrence(GRUCell): EH_LAYER_GRU
+RNN_LAYER = "rnn:"       # ... Recurrence(RNNCell(.., act)): "rnn:<act>", EH_LAYER_RNN + the activation's id
+CELL_GATES = {"lstm": 4, "gru": 3, "rnn": 1}      # gate blocks of H rows in weight_ih / weight_hh / bias_ih / bias_hh
+
+
+def _cell_kind(a) -> Optional[str]:
+    """a hidden layer's "activation" -> "lstm" | "gru" | "rnn" when the layer is a Recurrence, None when it is a Dense layer"""
+    if a == LSTM_LAYER or a == GRU_LAYER:
+        return a
+    return "rnn" if isinstance(a, str) and a.startswith(RNN_LAYER) else None
+
+
+def _layer_code(a: str) -> int:
+    """net_activation[l] of the descriptor"""
+    kind = _cell_kind(a)
+    if kind == "rnn":
+        return L.EH_LAYER_RNN + L.ACTIVATIONS[a[len(RNN_LAYER):]]
+    return {"lstm": L.EH_LAYER_LSTM, "gru": L.EH_LAYER_GRU}[kind] if kind else L.ACTIVATIONS[a]
 
 
 class Chain:
@@ -295,11 +335,12 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
                 raise NotImplementedError(f"hidden_layers Chain: {len(ls)} layers around a Recurrence; the device kernel holds Chain(Recurrence(LSTMCell(I => H))) "
                                           "alone (stacked or non-final Recurrence layers are not built)")
             r = ls[0]
-            if not isinstance(r.cell, LSTMCell):
-                raise NotImplementedError(f"hidden_layers Chain: Recurrence({type(r.cell).__name__}); only LSTMCell has a device kernel")
+            if not isinstance(r.cell, (LSTMCell, GRUCell, RNNCell)):
+                raise NotImplementedError(f"hidden_layers Chain: Recurrence({type(r.cell).__name__}); only LSTMCell, GRUCell and RNNCell have a device kernel")
             if not r.return_sequence:
                 raise NotImplementedError("hidden_layers Chain: Recurrence(return_sequence = false) is not built (the reference always sets it true)")
-            return [r.cell.in_dims, r.cell.out_dims, r.cell.out_dims], [act, LSTM_LAYER, act]
+            cell = LSTM_LAYER if isinstance(r.cell, LSTMCell) else (GRU_LAYER if isinstance(r.cell, GRUCell) else RNN_LAYER + r.cell.activation)
+            return [r.cell.in_dims, r.cell.out_dims, r.cell.out_dims], [act, cell, act]
         acts = [act]
         for i, l in enumerate(ls):
             if not isinstance(l, Dense):
@@ -355,18 +396,33 @@ class SingleNNHybridModel:
 
     @property
     def lstm_layer(self) -> Optional[int]:
-        """index into NN of the layer that is Recurrence(LSTMCell) (sequence models), or None"""
-        la = self.layer_activations
-        return la.index(LSTM_LAYER) if la is not None and LSTM_LAYER in la else None
+        """index into NN of the layer that is a Recurrence (sequence models; the name is from when LSTMCell was the one cell), or None"""
+        for l, a in enumerate(self.layer_activations or ()):
+            if _cell_kind(a) is not None:
+                return l
+        return None
+
+    @property
+    def cell(self) -> Optional[str]:
+        """"lstm" | "gru" | "rnn" of a sequence model, None otherwise"""
+        ll = self.lstm_layer
+        return None if ll is None else _cell_kind(self.layer_activations[ll])
+
+    @property
+    def cell_activation(self) -> Optional[str]:
+        """the activation of a sequence model's RNNCell, None otherwise"""
+        return self.layer_activations[self.lstm_layer][len(RNN_LAYER):] if self.cell == "rnn" else None
 
     def leaves(self):
         """[(network index, layer index, leaf name, shape)] of the networks in ComponentArray order: Dense layers have `weight` (out, in) and
-        `bias`; the LSTM layer `weight_ih` (4H, I), `weight_hh` (4H, H), `bias_ih`, `bias_hh` (4H), gate blocks [i | f | g | o]"""
+        `bias`; the recurrent layer `weight_ih` (nH, I), `weight_hh` (nH, H), `bias_ih`, `bias_hh` (nH): n = 4 gate blocks [i | f | g | o] of
+        an LSTMCell, 3 [r | z | n] of a GRUCell, 1 of an RNNCell"""
         out, ll = [], self.lstm_layer
+        ng = CELL_GATES.get(self.cell, 0)
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
                 if ll is not None and li == ll:
-                    out += [(k, li, "weight_ih", (4 * o, i)), (k, li, "weight_hh", (4 * o, o)), (k, li, "bias_ih", (4 * o,)), (k, li, "bias_hh", (4 * o,))]
+                    out += [(k, li, "weight_ih", (ng * o, i)), (k, li, "weight_hh", (ng * o, o)), (k, li, "bias_ih", (ng * o,)), (k, li, "bias_hh", (ng * o,))]
                 else:
                     out += [(k, li, "weight", (o, i)), (k, li, "bias", (o,))]
         return out
@@ -398,7 +454,7 @@ class SingleNNHybridModel:
         parts = []
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
-                if li == self.lstm_layer:      # LSTMCell: every leaf U(+-1/sqrt(H))
+                if li == self.lstm_layer:      # LSTMCell, GRUCell, RNNCell: every leaf U(+-1/sqrt(H))
                     bh = 1 / math.sqrt(o)
                     parts += [rng.uniform(-bh, bh, shape).astype(np.float32).flatten(order="F") for _, l2, _, shape in self.leaves() if l2 == li]
                     continue
@@ -417,7 +473,7 @@ class SingleNNHybridModel:
         """True at the flat-theta positions of the Dense weight matrices (the leaves weight_l2 sums, src/utils/extract_weights.jl:69-91)"""
         m = np.zeros(self.n_theta, bool)
         off = 0
-        for _, _, name, shape in self.leaves():      # (the LSTM's leaves are weight_ih / weight_hh: not matched)
+        for _, _, name, shape in self.leaves():      # (a cell's leaves are weight_ih / weight_hh: not matched)
             n = int(np.prod(shape))
             m[off:off + n] = name == "weight"
             off += n
@@ -452,7 +508,7 @@ class SingleNNHybridModel:
     def unpack(self, theta: np.ndarray):
         """flat theta -> (ps = [(weight (out,in), bias)...], {global: raw})"""
         off, nets = 0, []
-        if self.lstm_layer is not None:      # sequence model: the LSTM layer unpacks to a dict of its four leaves
+        if self.lstm_layer is not None:      # sequence model: the recurrent layer unpacks to a dict of its four leaves
             layers, cur = [], {}
             for _, li, name, shape in self.leaves():
                 n = int(np.prod(shape))
@@ -518,7 +574,7 @@ class SingleNNHybridModel:
         elif self.layer_activations is not None:   # an activation per hidden layer (n_nets = 0): net_activation[l] is layer l's
             d.activation = L.EH_ACT_PER_NET
             for l, a in enumerate(self.layer_activations):
-                d.net_activation[l] = L.EH_LAYER_LSTM if a == LSTM_LAYER else L.ACTIVATIONS[a]
+                d.net_activation[l] = _layer_code(a)
         else:
             d.activation = L.ACTIVATIONS[self.activation]
         d.scale_nn_outputs = int(self.scale_nn_outputs)

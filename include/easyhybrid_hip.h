@@ -67,8 +67,14 @@ typedef enum eh_activation { EH_ACT_TANH = 0, EH_ACT_SIGMOID = 1, EH_ACT_RELU = 
  * at l = 1 of n_hidden = 3 with hidden[2] == hidden[1] -- the chain Dense(P -> I, act) -> LSTM(I -> H) -> Dense(H -> H, act) -> Dense(H -> K)
  * the reference makes of `Chain(Recurrence(LSTMCell(I => H)))`, I and H up to 32, one target, fp32.  Flat theta: Dense-in weight (I x P,
  * column-major), bias; LSTM weight_ih (4H x I), weight_hh (4H x H), bias_ih (4H), bias_hh (4H), gate blocks [i | f | g | o]; head Dense;
- * output Dense; globals.  Such a handle works on windows of its records: eh_set_sequences. */
+ * output Dense; globals.  Such a handle works on windows of its records: eh_set_sequences.
+ * The cell may also be a GRUCell (EH_LAYER_GRU: weight_ih (3H x I), weight_hh (3H x H), bias_ih (3H), bias_hh (3H), gate blocks
+ * [r | z | n], h' = (1 - z) n + z h with n = tanh(W_in x + b_in + r (W_hn h + b_hn))) or an RNNCell (EH_LAYER_RNN + its eh_activation
+ * TANH..IDENTITY: weight_ih (H x I), weight_hh (H x H), bias_ih, bias_hh, h' = act(W_ih x + b_ih + W_hh h + b_hh)); same chain, same
+ * limits, one recurrent layer of whichever kind. */
 #define EH_LAYER_LSTM 16
+#define EH_LAYER_GRU 24
+#define EH_LAYER_RNN 32       /* .. EH_LAYER_RNN + EH_ACT_IDENTITY */
 #define EH_MAX_SEQ_WINDOW 64  /* longest input window of a sequence model */
 
 /* registry of mechanistic models (the reference takes an arbitrary Julia closure,

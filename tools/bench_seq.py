@@ -10,7 +10,10 @@ One JSON line per window count.
 --closure: the mechanistic model three ways -- RbQ10 of the registry, the same formula as a recorded closure on the interpreter
 ("jit" = 0) and on the kernels compiled at run time ("jit" = 1) -- ALTERNATED in one process: `rounds` times round the three engines,
 `steps` timed steps each.  One JSON line per (windows, output_window): per variant the median us / step of the rounds and their
-minimum and maximum (the spread the comparison has to be read against).  profiles/r11/seq_closure_step.txt."""
+minimum and maximum (the spread the comparison has to be read against).  profiles/r11/seq_closure_step.txt.
+--cell lstm|gru|rnn: the recurrent cell of every mode above (RNNCell with tanh); default lstm.
+  python tools/bench_seq.py --cells lstm,gru,rnn [--steps 300] [--warmup 20] [--rounds 5] [--windows 128,16384] [--output-windows 1,10]
+--cells: the listed cells around the registry's RbQ10, ALTERNATED in one process as --closure alternates its three; same output."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -29,12 +32,17 @@ ap.add_argument("--cpu-twin", action="store_true")
 ap.add_argument("--closure", action="store_true")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--output-windows", default="1,10")
+ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"])
+ap.add_argument("--cells", default=None, help="comma-separated cells to alternate")
 a = ap.parse_args()
 
 
 def rbq10_closure(*, ta, rb, Q10):
     """RbQ10 as a user writes it (the reference's LSTM tutorial returns the parameters next to the prediction)"""
     return dict(reco=rb * Q10 ** (0.1 * (ta - 15.0)), Q10=Q10, rb=rb)
+
+
+CELL = {"lstm": lambda: eh.LSTMCell(a.width, a.width), "gru": lambda: eh.GRUCell(a.width, a.width), "rnn": lambda: eh.RNNCell(a.width, a.width, "tanh")}
 
 
 def closure_bench():
@@ -45,15 +53,17 @@ def closure_bench():
     cols = make_synth_rbq10(rows, 1, 0.05)
     X = np.stack([cols["sw_pot"], cols["dsw_pot"]]) / np.float32(50)
     starts = np.arange(rows - W - lam + 1, dtype=np.int32)
-    chain = lambda: eh.Chain(eh.Recurrence(eh.LSTMCell(a.width, a.width)))
-    mk = lambda mech: eh.constructHybridModel(["sw_pot", "dsw_pot"], ["ta"], ["reco"], mech, dict(RBQ10_PARAMS), ["rb"], ["Q10"], hidden_layers=chain(),
-                                              activation="tanh", scale_nn_outputs=True)
-    variants = [("registry", eh.RbQ10, None), ("closure_interpreted", rbq10_closure, 0), ("closure_compiled", rbq10_closure, 1)]
+    mk = lambda mech, cell: eh.constructHybridModel(["sw_pot", "dsw_pot"], ["ta"], ["reco"], mech, dict(RBQ10_PARAMS), ["rb"], ["Q10"],
+                                                    hidden_layers=eh.Chain(eh.Recurrence(CELL[cell]())), activation="tanh", scale_nn_outputs=True)
+    if a.cells:
+        variants = [(c, eh.RbQ10, None, c) for c in a.cells.split(",")]
+    else:
+        variants = [("registry", eh.RbQ10, None, a.cell), ("closure_interpreted", rbq10_closure, 0, a.cell), ("closure_compiled", rbq10_closure, 1, a.cell)]
     for B in counts:
         for ow in [int(o) for o in a.output_windows.split(",")]:
             engs = []
-            for name, mech, jit in variants:
-                model = mk(mech)
+            for name, mech, jit, cell in variants:
+                model = mk(mech, cell)
                 eng = model.engine(0)
                 if jit is not None:
                     eng.set_option("jit", jit)
@@ -67,30 +77,30 @@ def closure_bench():
                 if eng.jit_status()[0] != (jit or 0):
                     raise SystemExit(f"{name}: eh_jit_status reports {eng.jit_status()[0]} compiled kernels: {eng.jit_status()[1][:400]}")
                 engs.append(eng)
-            times = {name: [] for name, _, _ in variants}
+            times = {v[0]: [] for v in variants}
             for r in range(a.rounds):
-                for (name, _, _), eng in zip(variants, engs):
+                for (name, *_), eng in zip(variants, engs):
                     t0 = time.perf_counter()
                     for s in range(a.steps):
                         eng.train_step(((r * a.steps + s) % nb) * B, B, want_loss=False)
                     eng.synchronize()
                     times[name].append(1e6 * (time.perf_counter() - t0) / a.steps)
             out = {"windows": B, "input_window": W, "output_window": ow, "I": a.width, "H": a.width, "rounds": a.rounds, "steps": a.steps}
-            for name, _, _ in variants:
+            for name, *_ in variants:
                 t = sorted(times[name])
                 out[name] = {"us_per_step_median": t[len(t) // 2], "min": t[0], "max": t[-1]}
-            out["final_loss"] = {name: eng.train_step(0, B) for (name, _, _), eng in zip(variants, engs)}
+            out["final_loss"] = {name: eng.train_step(0, B) for (name, *_), eng in zip(variants, engs)}
             print(json.dumps(out), flush=True)
             for eng in engs:
                 eng.close()
 
 
-if a.closure:
+if a.closure or a.cells:
     closure_bench()
     sys.exit(0)
 W, ow, lam = a.input_window, a.output_window, 1
 model = eh.constructHybridModel(["sw_pot", "dsw_pot"], ["ta"], ["reco"], eh.RbQ10, dict(RBQ10_PARAMS), ["rb"], ["Q10"],
-                                hidden_layers=eh.Chain(eh.Recurrence(eh.LSTMCell(a.width, a.width))), activation="tanh", scale_nn_outputs=True)
+                                hidden_layers=eh.Chain(eh.Recurrence(CELL[a.cell]())), activation="tanh", scale_nn_outputs=True)
 counts = [int(c) for c in a.windows.split(",")]
 nb = 4                                            # minibatches the steps rotate through
 rows = nb * max(counts) + W + lam
@@ -117,9 +127,9 @@ for B in counts:
     eng.profile_enable(False)
     tiles = (B + 15) // 16
     grid = max(1, min((tiles + 3) // 4, 256))
-    out = {"windows": B, "input_window": W, "output_window": ow, "I": a.width, "H": a.width, "n_theta": model.n_theta, "us_per_step": 1e6 * dt / a.steps,
+    out = {"windows": B, "input_window": W, "output_window": ow, "I": a.width, "H": a.width, "cell": a.cell, "n_theta": model.n_theta, "us_per_step": 1e6 * dt / a.steps,
            "windows_per_s": B * a.steps / dt, "step_kernel_us": 1e3 * k_step, "reduce_kernel_us": 1e3 * k_reduce, "workgroups": grid,
-           "tiles_per_wave": -(-tiles // (4 * grid)), "workspace_bytes": grid * 4 * (W * 6 * nbh + ow * (nbh + 1)) * 1024, "final_loss": eng.train_step(0, B)}
+           "tiles_per_wave": -(-tiles // (4 * grid)), "workspace_bytes": grid * 4 * (W * {"lstm": 6, "gru": 5, "rnn": 2}[a.cell] * nbh + ow * (nbh + 1)) * 1024, "final_loss": eng.train_step(0, B)}
     if a.cpu_twin:
         import torch
         from tests import seq_twin as tw
