@@ -26,6 +26,8 @@ EH_ACT_PER_NET = 5        # MultiNN: net k uses net_activation[k]
 EH_LAYER_LSTM = 16        # net_activation[l] of a hidden layer that is Recurrence(LSTMCell) (sequence models)
 EH_LAYER_GRU = 24         # ... Recurrence(GRUCell)
 EH_LAYER_RNN = 32         # ... Recurrence(RNNCell(.., act)): EH_LAYER_RNN + ACTIVATIONS[act]
+EH_LAYER_BATCHNORM = 40   # ... BatchNorm(n, act) behind the layer in front of it: EH_LAYER_BATCHNORM + ACTIVATIONS[act]
+EH_LAYER_BN_NOAFFINE = 8  # ... added to it: affine = false (no scale / bias in theta)
 EH_MAX_SEQ_WINDOW = 64
 OPT_RULES = {"Adam": 0, "AdamW": 1, "RMSProp": 2, "Descent": 3}
 TRAINING_LOSSES = {"mse": 0, "rmse": 1, "mae": 2, "nseLoss": 3, "pearsonLoss": 4, "kgeLoss": 5, "pbkgeLoss": 6}
@@ -100,6 +102,9 @@ SIGNATURES = {
     "eh_loss_and_grad": (C.c_int32, [_H, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64, _F, _F, C.POINTER(C.c_int64)]),
     "eh_get_bn_state": (C.c_int32, [_H, _F, _F, C.c_int64]),
     "eh_set_bn_state": (C.c_int32, [_H, _F, _F, C.c_int64]),
+    "eh_get_layer_state": (C.c_int32, [_H, C.c_int32, _F, _F, C.c_int64]),
+    "eh_set_layer_state": (C.c_int32, [_H, C.c_int32, _F, _F, C.c_int64]),
+    "eh_set_layer_norm": (C.c_int32, [_H, C.c_int32, C.c_float, C.c_float]),
     "eh_opt_init": (C.c_int32, [_H, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "eh_get_opt_state": (C.c_int32, [_H, _F, _F, C.c_int64, _F]),
     "eh_set_opt_state": (C.c_int32, [_H, _F, _F, C.c_int64, _F]),

@@ -592,13 +592,40 @@ static int seq_desc_check(const eh_model_desc* d) {
     return 1;                                // (around every mechanistic model: registry, several outputs -- the one target names its output --, recorded closure)
 }
 
+// BatchNorm layers inside the chain (EH_LAYER_BATCHNORM [+ EH_LAYER_BN_NOAFFINE] + activation in the per-layer activation slots): 0 = the
+// descriptor has none, 1 = well formed (one network, every such layer as wide as the layer in front of it), otherwise the status of the refusal
+static bool bnl_layer_code(int a) {
+    const int b = a - EH_LAYER_BATCHNORM;
+    return (b >= 0 && b <= EH_ACT_IDENTITY) || (b >= EH_LAYER_BN_NOAFFINE && b <= EH_LAYER_BN_NOAFFINE + EH_ACT_IDENTITY);
+}
+static int bnl_desc_check(const eh_model_desc* d) {
+    if (d->activation != EH_ACT_PER_NET) return 0;
+    const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
+    int n_bn = 0;
+    bool cell = false;
+    for (int l = 0; l < na; ++l) { n_bn += bnl_layer_code(d->net_activation[l]) ? 1 : 0; cell = cell || seq_layer_code(d->net_activation[l]); }
+    if (!n_bn) return 0;
+    if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for BatchNorm layers in a MultiNN model (EH_LAYER_BATCHNORM with n_nets = %d)", d->n_nets);
+    if (cell) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a chain that holds both a BatchNorm layer and a recurrent layer");
+    for (int l = 0; l < na; ++l) {
+        if (!bnl_layer_code(d->net_activation[l])) continue;
+        if (l == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_BATCHNORM at hidden layer 0: a BatchNorm layer normalises the layer in front of it (hidden layer 0 is a Dense layer)");
+        if (d->hidden[l] != d->hidden[l - 1]) return fail(nullptr, EH_EINVAL, "eh_create: BatchNorm layer %d has width %d, the layer in front of it %d", l, d->hidden[l], d->hidden[l - 1]);
+    }
+    return 1;
+}
+
 int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     if (!d || !out) return fail(nullptr, EH_EINVAL, "eh_create: null argument");
     *out = nullptr;
     if (d->struct_size != (int32_t)sizeof(eh_model_desc)) return fail(nullptr, EH_EINVAL, "eh_create: struct_size %d != %zu", d->struct_size, sizeof(eh_model_desc));
     MechInfo mi;
     if (!mech_info(d->mech, &mi, d)) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown mechanistic model id %d (no silent fallback)", d->mech);
-    const int seqk = (d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS) ? seq_desc_check(d) : 0;
+    const bool desc_layers = d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS;
+    const int bnk = desc_layers ? bnl_desc_check(d) : 0;
+    if (bnk < 0) return bnk;
+    const bool bnl = bnk == 1;
+    const int seqk = (desc_layers && !bnl) ? seq_desc_check(d) : 0;
     if (seqk < 0) return seqk;
     const bool seq = seqk == 1;
     if (d->mech == EH_MECH_PROGRAM) {
@@ -640,6 +667,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         bool same = true;
         for (int k = 0; k < na; ++k) {
             if (seq && seq_layer_code(d->net_activation[k])) { same = false; continue; }
+            if (bnl && bnl_layer_code(d->net_activation[k])) { same = false; continue; }
             if (d->net_activation[k] < 0 || d->net_activation[k] > EH_ACT_IDENTITY)
                 return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown activation id %d for %s %d", d->net_activation[k], d->n_nets > 0 ? "net" : "hidden layer", k);
             same = same && d->net_activation[k] == d->net_activation[0];
@@ -725,6 +753,9 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     const EhArchInfo* const wide_arch = (nbh && K <= 16 && !no_nn) ? find_wide(nbi, nbh, d->n_hidden) : nullptr;
     if (!arch) arch = wide_arch;
     bool lform = false;
+    // (EH_FORCE_LFORM: A/B switch of the measurement tools -- every feed-forward model layer by layer, the baseline tools/bench_bn_chain.py compares with)
+    static const bool force_lform = getenv("EH_FORCE_LFORM") != nullptr;
+    if (bnl || (force_lform && !seq)) arch = nullptr;      // (a BatchNorm layer couples the samples of a minibatch: always layer by layer, eh_bnl.hpp)
     if (no_nn) { arch = &g_lform_arch; lform = true; }
     else if (seq) arch = &g_lform_arch;      // (its own kernel family, eh_seq.hpp; of the "architecture" only the PHI block of the image is used)
     else if (!arch) {
@@ -777,6 +808,11 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         for (int l = 0; l <= nl; ++l) {
             const int o = l < nl ? net_w[k][l] : net_K[k];
             if (k == 0) lw_off[l] = off;
+            if (bnl && l < nl && bnl_layer_code(d->net_activation[l])) {      // a BatchNorm layer: scale and bias, or nothing (affine = false)
+                if (k == 0) lb_off[l] = off;
+                if (d->net_activation[l] - EH_LAYER_BATCHNORM < EH_LAYER_BN_NOAFFINE) off += 2 * o;
+                continue;
+            }
             if (l < nl && l >= net_d[k]) { if (k == 0) lb_off[l] = off; continue; }       // identity block: nothing of it in theta
             off += o * in;
             if (k == 0) lb_off[l] = off;
@@ -811,6 +847,16 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
             int in = net_P[k];
             for (int l = 0; l < L.nl; ++l) {
                 const int o = l + 1 < L.nl ? net_w[k][l] : net_K[k];
+                if (bnl && l + 1 < L.nl && bnl_layer_code(d->net_activation[l])) {
+                    const int b = d->net_activation[l] - EH_LAYER_BATCHNORM;
+                    const bool affine = b < EH_LAYER_BN_NOAFFINE;
+                    L.lbn[l] = affine ? 1 : 2; L.lact[l] = affine ? b : b - EH_LAYER_BN_NOAFFINE;
+                    L.in[l] = in; L.out[l] = in; L.woff[l] = o2; L.boff[l] = affine ? o2 + in : o2;
+                    if (affine) o2 += 2 * in;
+                    h->bnl = true; h->bnl_off[l] = h->bnl_maxn; h->bnl_maxn += 2 * in;      // (bnl_maxn: the running total here, the widest layer below)
+                    h->bnl_mom[l] = EH_BN_MOMENTUM; h->bnl_eps[l] = EH_BN_EPS;
+                    continue;
+                }
                 L.in[l] = in; L.out[l] = o; L.woff[l] = o2; L.boff[l] = o2 + o * in;
                 o2 += o * in + o; in = o;
             }
@@ -846,7 +892,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         h->variant = 0;
         h->fast = 0;
     }
-    h->arch_alt = (arch == wide_arch || seq) ? nullptr : wide_arch;
+    h->arch_alt = (arch == wide_arch || seq || lform) ? nullptr : wide_arch;
 #define HIPCHK_C(expr)                                                            \
     do {                                                                          \
         hipError_t e_ = (expr);                                                   \
@@ -901,6 +947,20 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         for (int p = 0; p < 32; ++p) { run0[p] = 0.0f; run0[32 + p] = 1.0f; }     // LuxCore.initialstates(BatchNorm)
         HIPCHK_C(hipMemcpy(h->bn_run, run0, sizeof run0, hipMemcpyHostToDevice));
     }
+    if (h->bnl) {             // BatchNorm layers: running statistics (LuxCore.initialstates: mean 0, var 1), the step's own, the partial column sums
+        const int tot = h->bnl_maxn;
+        int widest = 0;
+        for (int l = 0; l < h->l_net[0].nl; ++l) if (h->l_net[0].lbn[l]) widest = std::max(widest, h->l_net[0].out[l]);
+        h->bnl_maxn = widest;
+        std::vector<float> run0((size_t)tot, 0.0f);
+        for (int l = 0; l < h->l_net[0].nl; ++l)
+            if (h->l_net[0].lbn[l]) std::fill(run0.begin() + h->bnl_off[l] + h->l_net[0].out[l], run0.begin() + h->bnl_off[l] + 2 * h->l_net[0].out[l], 1.0f);
+        HIPCHK_C(hipMalloc(&h->bnl_run, (size_t)tot * sizeof(float)));
+        HIPCHK_C(hipMemcpy(h->bnl_run, run0.data(), (size_t)tot * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK_C(hipMalloc(&h->bnl_stat, (size_t)2 * tot * sizeof(float)));
+        HIPCHK_C(hipMemset(h->bnl_stat, 0, (size_t)2 * tot * sizeof(float)));
+        HIPCHK_C(hipMalloc(&h->bnl_part, (size_t)(EH_BNL_CHUNKS + 1) * 2 * widest * sizeof(float)));
+    }
     if (!lform && !seq) {     // (the fused-update accumulators: that mode exists for the per-wave kernels only)
         HIPCHK_C(hipMalloc(&h->gacc, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));      // (+4: the fused prologue reads five tail floats of every shard whatever T is)
         HIPCHK_C(hipMemset(h->gacc, 0, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));
@@ -938,7 +998,8 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     else {
         std::vector<unsigned char> wf((size_t)n.n_theta, 0);
         for (int k = 0; k < h->l_nnets; ++k)
-            for (int l = 0; l < h->l_net[k].nl; ++l) std::fill(wf.begin() + h->l_net[k].woff[l], wf.begin() + h->l_net[k].boff[l], (unsigned char)1);
+            for (int l = 0; l < h->l_net[k].nl; ++l)
+                if (!h->l_net[k].lbn[l]) std::fill(wf.begin() + h->l_net[k].woff[l], wf.begin() + h->l_net[k].boff[l], (unsigned char)1);      // (a BatchNorm's scale is no weight)
         HIPCHK_C(hipMalloc(&h->wflag, wf.size()));
         HIPCHK_C(hipMemcpy(h->wflag, wf.data(), wf.size(), hipMemcpyHostToDevice));
     }
@@ -973,7 +1034,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         {
             int nw = 0;
             if (seq) nw = (h->seq_off[EH_SEQ_BIN] - h->seq_off[EH_SEQ_WIN]) + (h->seq_off[EH_SEQ_BHD] - h->seq_off[EH_SEQ_WHD]) + (h->seq_off[EH_SEQ_BOUT] - h->seq_off[EH_SEQ_WOUT]);
-            else if (lform) { for (int k = 0; k < h->l_nnets; ++k) for (int l = 0; l < h->l_net[k].nl; ++l) nw += h->l_net[k].in[l] * h->l_net[k].out[l]; }
+            else if (lform) { for (int k = 0; k < h->l_nnets; ++k) for (int l = 0; l < h->l_net[k].nl; ++l) nw += h->l_net[k].lbn[l] ? 0 : h->l_net[k].in[l] * h->l_net[k].out[l]; }
             else for (const EhEntry& e : enumerate_entries(h)) nw += e.col >= 0 ? 1 : 0;
             h->n_weights = nw;
         }
@@ -1015,6 +1076,7 @@ int32_t eh_destroy(eh_handle* h) {
     eval_host_release(h);
     eh_lbfgs_release(h);
     (void)hipFree(h->mech_ws); (void)hipFree(h->l_ws); (void)hipFree(h->l_split); (void)hipFree(h->l_dk); (void)hipFree(h->l_lprog); (void)hipFree(h->wflag);
+    (void)hipFree(h->bnl_run); (void)hipFree(h->bnl_stat); (void)hipFree(h->bnl_part);
     (void)hipFree(h->stamps); (void)hipFree(h->image); (void)hipFree(h->imap); (void)hipFree(h->rmap);
     (void)hipFree(h->split[0].recs); (void)hipFree(h->split[1].recs); (void)hipFree(h->split[0].starts); (void)hipFree(h->split[1].starts); (void)hipFree(h->seq_ws); (void)hipFree(h->chain_part);
     if (h->own_stream) stream_pool_give(h->device, h->own_stream);      // (drained above; the next handle on this device takes it over)
@@ -1195,6 +1257,17 @@ static int32_t set_option(eh_handle* h, const char* name, int64_t value) {
             if (value > EH_LOSS_NSELOSS) return fail(h, EH_EUNSUPPORTED, "training_loss %lld: sequence models train on mse, rmse, mae and nseLoss (the two-pass losses and recorded losses are not built for them)", (long long)value);
             h->net.loss = (int)value;
             h->net.loss_t = (unsigned)value;
+            return EH_OK;
+        }
+    }
+    if (h->bnl) {                            // BatchNorm layers in the chain: always the layer-wise step + reduce pair, fp32
+        if (!strcmp(name, "fused_update")) {
+            if (value < 0 || value > 2) return fail(h, EH_EINVAL, "fused_update must be 0, 1 or 2");
+            if (value == 1) return fail(h, EH_EUNSUPPORTED, "fused_update: the one-kernel step is not built for BatchNorm layers in the chain (they run the layer-wise step + reduce pair)");
+            return EH_OK;                    // (2 = "where it is reproducible": the pair is)
+        }
+        if (!strcmp(name, "multi_step") || !strcmp(name, "specialize") || !strcmp(name, "precision")) {
+            if (value) return fail(h, EH_EUNSUPPORTED, "%s: not built for BatchNorm layers in the chain (fp32 layer-wise form, one step per launch sequence)", name);
             return EH_OK;
         }
     }
@@ -2112,6 +2185,40 @@ int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* ru
     return EH_OK;
 }
 
+// running statistics of a BatchNorm layer inside the chain (eh_bnl.hpp)
+static int layer_state_check(eh_handle* h, const char* who, int32_t layer, int64_t n) {
+    if (!h->bnl || layer < 0 || layer >= h->l_net[0].nl || !h->l_net[0].lbn[layer]) return fail(h, EH_ESTATE, "%s: hidden layer %d is no BatchNorm layer", who, layer);
+    if (n != h->l_net[0].out[layer]) return fail(h, EH_EINVAL, "%s: n = %lld, the layer has %d units", who, (long long)n, h->l_net[0].out[layer]);
+    return EH_OK;
+}
+int32_t eh_get_layer_state(eh_handle* h, int32_t layer, float* running_mean, float* running_var, int64_t n) {
+    if (!h || !running_mean || !running_var) return EH_EINVAL;
+    if (int rc = layer_state_check(h, "eh_get_layer_state", layer, n)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(running_mean, h->bnl_run + h->bnl_off[layer], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(running_var, h->bnl_run + h->bnl_off[layer] + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return EH_OK;
+}
+int32_t eh_set_layer_state(eh_handle* h, int32_t layer, const float* running_mean, const float* running_var, int64_t n) {
+    if (!h || !running_mean || !running_var) return EH_EINVAL;
+    if (int rc = layer_state_check(h, "eh_set_layer_state", layer, n)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    FLUSH(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->bnl_run + h->bnl_off[layer], running_mean, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->bnl_run + h->bnl_off[layer] + n, running_var, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    return EH_OK;
+}
+int32_t eh_set_layer_norm(eh_handle* h, int32_t layer, float momentum, float epsilon) {
+    if (!h) return EH_EINVAL;
+    if (int rc = layer_state_check(h, "eh_set_layer_norm", layer, h->bnl && layer >= 0 && layer < h->l_net[0].nl ? h->l_net[0].out[layer] : 0)) return rc;
+    if (!(momentum >= 0.0f && momentum <= 1.0f) || !(epsilon > 0.0f)) return fail(h, EH_EINVAL, "eh_set_layer_norm: momentum %g (0..1), epsilon %g (> 0)", (double)momentum, (double)epsilon);
+    h->bnl_mom[layer] = momentum; h->bnl_eps[layer] = epsilon;      // (kernel arguments of the steps launched from now on)
+    return EH_OK;
+}
+
 // a new rule (eh_opt_init, eh_opt_init_groups): out of L-BFGS mode, no chain, zero moments, the running beta products at their start
 static int opt_restart(eh_handle* h, const float* sc, size_t sc_bytes) {
     if (h->lb) h->lb->active = false;
@@ -2411,6 +2518,7 @@ static int make_permutation(eh_handle* h, long long N, uint64_t seed) {
 int32_t eh_graph_begin(eh_handle* h) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: graph capture is not built for sequence models");
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: graph capture is not built for BatchNorm layers in the chain");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: dropout: every step carries its own step count in its arguments, a recorded graph would replay one mask: not built");
     if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: the handle is in L-BFGS mode (capture is not built for it): eh_opt_init* leaves the mode");
     if (h->capturing) return fail(h, EH_ESTATE, "eh_graph_begin: already capturing");
@@ -2550,11 +2658,13 @@ static int dp_refused(eh_handle* h, const char* who) {
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "%s: data parallelism is not built for sequence models", who);
     if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "%s: the handle is in L-BFGS mode, which is not built for data parallelism (eh_opt_init* leaves the mode)", who);
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "%s: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)", who);
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "%s: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)", who);
     return EH_OK;
 }
 int32_t eh_dp_shuffle(eh_handle* h, uint64_t seed, int32_t on) {
     if (!h) return EH_EINVAL;
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: data parallelism is not built for sequence models");
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_shuffle: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     HIPCHK(h, hipSetDevice(h->device));
     if (!on) { h->perm_valid = false; return EH_OK; }      // (stream order keeps earlier steps on the old permutation)

@@ -126,6 +126,7 @@ static int p2p_alloc(eh_handle* h, int32_t world, int32_t rank, hipIpcMemHandle_
     // (world == 1 is a loopback: the rank publishes to and reads from itself -- measures the cost of the machinery)
     if (world < 1 || world > EH_GSHARDS || rank < 0 || rank >= world) return fail(h, EH_EINVAL, "%s: world %d (1..%d), rank %d", who, world, EH_GSHARDS, rank);
     if (h->seq) return fail(h, EH_EUNSUPPORTED, "%s: data parallelism is not built for sequence models", who);
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "%s: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)", who);
     if (!h->fused) return fail(h, EH_ESTATE, "%s: set the fused_update option first", who);
     if (h->net.T != 1) return fail(h, EH_EUNSUPPORTED, "%s: the peer-to-peer exchange is built for single-target models (use the all-reduce seam)", who);
     if (h->net.mech == EH_MECH_PROGRAM) return fail(h, EH_EUNSUPPORTED, "%s: the program kernels have no cross-GPU variant (use the all-reduce seam)", who);
@@ -172,6 +173,7 @@ static int p2p_wire(eh_handle* h) {
 
 int32_t eh_p2p_init(eh_handle* h, int32_t world, int32_t rank, void* handle_out, int64_t handle_bytes) {
     if (!h || !handle_out) return EH_EINVAL;
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "eh_p2p_init: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_p2p_init: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (handle_bytes < (int64_t)sizeof(hipIpcMemHandle_t)) return fail(h, EH_EINVAL, "eh_p2p_init: handle buffer of %lld bytes, need %zu", (long long)handle_bytes, sizeof(hipIpcMemHandle_t));
     hipIpcMemHandle_t hd;
@@ -271,6 +273,7 @@ int32_t eh_p2p_init_local(eh_handle* const* handles, int32_t n, int32_t selftest
     *ok = 0;
     for (int i = 0; i < n; ++i) {
         if (!handles[i]) return fail(nullptr, EH_EINVAL, "eh_p2p_init_local: handle %d is NULL", i);
+        if (handles[i]->bnl) return fail(handles[i], EH_EUNSUPPORTED, "eh_p2p_init_local: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
         if (handles[i]->drop_on) return fail(handles[i], EH_EUNSUPPORTED, "eh_p2p_init_local: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
         for (int j = 0; j < i; ++j) if (handles[j] == handles[i]) return fail(handles[i], EH_EINVAL, "eh_p2p_init_local: handle %d is listed twice", i);
         if (handles[i]->net.n_theta != handles[0]->net.n_theta || handles[i]->n_acc != handles[0]->n_acc)
@@ -367,6 +370,7 @@ int32_t eh_comm_init(eh_handle* h, const void* unique_id, int64_t id_bytes, int3
     if (id_bytes < (int64_t)sizeof(ncclUniqueId)) return fail(h, EH_EINVAL, "eh_comm_init: id of %lld bytes, need %zu", (long long)id_bytes, sizeof(ncclUniqueId));
     if (world < 1 || rank < 0 || rank >= world) return fail(h, EH_EINVAL, "eh_comm_init: world %d, rank %d", world, rank);
     if (h->comm || h->lgroup) return fail(h, EH_ESTATE, "eh_comm_init: the handle already has a communicator (eh_comm_destroy first)");
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "eh_comm_init: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
     HIPCHK(h, hipSetDevice(h->device));
     ncclUniqueId id;
     memcpy(&id, unique_id, sizeof id);
@@ -390,6 +394,7 @@ int32_t eh_comm_init_local(eh_handle* const* handles, int32_t n) {
         if (!handles[i]) return fail(nullptr, EH_EINVAL, "eh_comm_init_local: handle %d is NULL", i);
         for (int j = 0; j < i; ++j) if (handles[j] == handles[i]) return fail(handles[i], EH_EINVAL, "eh_comm_init_local: handle %d is listed twice", i);
         if (handles[i]->comm || handles[i]->lgroup) return fail(handles[i], EH_ESTATE, "eh_comm_init_local: handle %d already has a communicator (eh_comm_destroy first)", i);
+        if (handles[i]->bnl) return fail(handles[i], EH_EUNSUPPORTED, "eh_comm_init_local: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
         if (handles[i]->net.n_theta != handles[0]->net.n_theta || handles[i]->n_acc != handles[0]->n_acc)
             return fail(handles[i], EH_EINVAL, "eh_comm_init_local: handle %d is a different model (%d parameters, handle 0 has %d)", i, handles[i]->net.n_theta, handles[0]->net.n_theta);
     }
@@ -549,6 +554,7 @@ int32_t eh_dp_allreduce(eh_handle* h, int32_t which, int32_t index) {
 
 int32_t eh_dp_train_step(eh_handle* h, int64_t first, int64_t count, float* loss_out) {
     if (!h) return EH_EINVAL;
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "eh_dp_train_step: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_dp_train_step: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
     if (!h->comm && !h->lgroup) return fail(h, EH_ESTATE, "eh_dp_train_step: call eh_comm_init first");
     if (h->lgroup && h->lgroup->n > 1) return fail(h, EH_ESTATE, "eh_dp_train_step: the members of a local group step together: eh_dp_train_step_group");
@@ -585,6 +591,7 @@ int32_t eh_dp_train_step_group(eh_handle* const* hs, int32_t n, const int64_t* f
     if (!hs || !first || n < 1 || n > EH_GSHARDS) return fail(nullptr, EH_EINVAL, "eh_dp_train_step_group: %d handles (1..%d)", n, EH_GSHARDS);
     for (int i = 0; i < n; ++i) {
         if (!hs[i]) return fail(nullptr, EH_EINVAL, "eh_dp_train_step_group: handle %d is NULL", i);
+        if (hs[i]->bnl) return fail(hs[i], EH_EUNSUPPORTED, "eh_dp_train_step_group: BatchNorm layers in the chain are not built for data parallelism (their statistics would have to be those of the global batch)");
         if (hs[i]->drop_on) return fail(hs[i], EH_EUNSUPPORTED, "eh_dp_train_step_group: dropout is not built for data parallelism (the masks are drawn per handle, from its own step count)");
         if (!hs[i]->comm && !hs[i]->lgroup) return fail(hs[i], EH_ESTATE, "eh_dp_train_step_group: handle %d has no communicator (eh_comm_init / eh_comm_init_local)", i);
         if (hs[i]->fused != hs[0]->fused || hs[i]->net.T != hs[0]->net.T || hs[i]->bn_on != hs[0]->bn_on || hs[i]->p2p_on != hs[0]->p2p_on)

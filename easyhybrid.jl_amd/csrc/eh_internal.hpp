@@ -98,6 +98,7 @@ constexpr int EH_EVAL_TILES = 64;        // most tiles one wave of an evaluation
 constexpr long long EH_SHIFT_VALID = 4096;
 enum { EH_MECH_MAXROWS = 65536 };            // eh_mech_loss_vjp: rows of partials (workgroups of the streaming kernel) at most: 4 MiB
 enum { EH_LFORM_ROWS = 64 };                 // layer-wise form: partial slabs of the weight gradients (split over the samples of a minibatch)
+enum { EH_BNL_CHUNKS = 256, EH_BNL_CHUNK_ROWS = 128 };      // BatchNorm layers (eh_bnl.hpp): partial rows of the column sums at most; rows a chunk holds at least
 
 struct EhShift4 { float c[EH_MAX_TARG]; };   // the shifts as a kernel argument (eh_count_kernel, eh_moment_*_kernel)
 struct EhSplit {
@@ -200,7 +201,8 @@ struct eh_handle_s {
     // layer-wise execution form (eh_lform.hpp): networks no fused kernel holds
     bool lform = false;
     // one entry per network (SingleNN: one; MultiNN: one single-output network per neural parameter, each on its own predictor rows)
-    struct LNet { int nl = 0, c0 = 0, orow = 0, act = 0; int lact[EH_MAX_HIDDEN + 1] = {0}; int in[EH_MAX_HIDDEN + 1] = {0}, out[EH_MAX_HIDDEN + 1] = {0}, woff[EH_MAX_HIDDEN + 1] = {0}, boff[EH_MAX_HIDDEN + 1] = {0}; };
+    // (lbn[l] != 0: entry l is a BatchNorm layer, EH_LAYER_BATCHNORM -- 1 affine, 2 not; in = out = its width, woff / boff = its scale / bias, lact its activation)
+    struct LNet { int nl = 0, c0 = 0, orow = 0, act = 0; int lact[EH_MAX_HIDDEN + 1] = {0}; int in[EH_MAX_HIDDEN + 1] = {0}, out[EH_MAX_HIDDEN + 1] = {0}, woff[EH_MAX_HIDDEN + 1] = {0}, boff[EH_MAX_HIDDEN + 1] = {0}; int lbn[EH_MAX_HIDDEN + 1] = {0}; };
     int l_nnets = 0;                                     // 0: no network at all (no neural parameter)
     LNet l_net[EH_MAX_NETS];
     float* l_split = nullptr; size_t l_split_cap = 0;    // split-K partial products of the small-batch GEMMs
@@ -209,6 +211,15 @@ struct eh_handle_s {
     bool l_job_done = false;                              // lform_gemm -> eh_lform_train (eh_lform.hip): a few-rows product took the side job of summing the chain's partial rows
     EhLApply* l_apply = nullptr; bool l_applied = false;   // eh_do_step -> eh_lform_train: the optimiser may run in the epilogue of the grouped weight gradients / it did
     bool l_tail_fn[12] = {false};
+    // BatchNorm layers inside the chain (eh_bnl.hpp; one network, always this form, its few-rows fusions off): per layer l of l_net[0]
+    // with lbn[l] != 0, at bnl_off[l] floats into bnl_run: [running mean | running var]; at twice that into bnl_stat: [first row | mean about it | rstd]
+    // of the step, n each
+    bool bnl = false;
+    int bnl_off[EH_MAX_HIDDEN + 1] = {0};
+    float bnl_mom[EH_MAX_HIDDEN + 1] = {0}, bnl_eps[EH_MAX_HIDDEN + 1] = {0};      // eh_set_layer_norm (defaults: EH_BN_MOMENTUM, EH_BN_EPS)
+    float *bnl_run = nullptr, *bnl_stat = nullptr;
+    float* bnl_part = nullptr;                           // [EH_BNL_CHUNKS][2][widest] partial column sums, then [2][widest] their totals of the backward
+    int bnl_maxn = 0;
     float* l_ws = nullptr;                               // [Xb | H_0 .. H_{NL-1} | D0 | D1 | O | mech partial rows]
     long long l_cap = 0;                                 // samples the workspace holds
     unsigned char* wflag = nullptr;

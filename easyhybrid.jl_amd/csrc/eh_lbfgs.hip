@@ -41,6 +41,7 @@ int32_t eh_lbfgs_init(eh_handle* h, const eh_lbfgs_opts* o) {
     if (!(o->g_tol >= 0.0) || !(o->f_reltol >= 0.0)) return fail(h, EH_EINVAL, "eh_lbfgs_init: g_tol = %g, f_reltol = %g (both >= 0)", o->g_tol, o->f_reltol);
     if (!(o->initial_step >= 0.0) || !std::isfinite(o->initial_step)) return fail(h, EH_EINVAL, "eh_lbfgs_init: initial_step = %g (>= 0; 0 = min(1, 1 / ||g||))", o->initial_step);
     if (h->capturing) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: graph capture is not built for L-BFGS");
+    if (h->bnl) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: BatchNorm layers in the chain: the L-BFGS driver carries no layer state (the running statistics would stay at their start)");
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: dropout: the line search needs the same objective at every trial point, the masks change with every pass (eh_set_dropout with all rates zero removes it)");
     if (h->bn_on) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: input BatchNorm: the reference's Optimization.jl driver never carries the layer state, and that path is not built");
     if (h->comm || h->lgroup || h->p2p_on || h->p2p_alloc) return fail(h, EH_EUNSUPPORTED, "eh_lbfgs_init: data parallelism (a communicator or a peer-to-peer group on this handle) is not built for L-BFGS");

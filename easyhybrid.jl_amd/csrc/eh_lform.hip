@@ -8,13 +8,14 @@
 
 #define EH_LFORM_KERNELS
 #include "eh_lform.hpp"
+#include "eh_bnl.hpp"
 
 struct EhLWs { float *Xb, *H[EH_MAX_NETS][EH_MAX_HIDDEN], *Z[EH_MAX_NETS][EH_MAX_HIDDEN], *D[2], *O, *part; long long ldo; };
 static long long lform_floats_per_sample(const eh_handle* h) {
     long long w = h->net.P + 16, maxw = 0;
     for (int k = 0; k < h->l_nnets; ++k)
         for (int l = 0; l + 1 < h->l_net[k].nl; ++l) {
-            w += h->l_net[k].out[l] * (h->l_net[k].lact[l] == EH_ACT_SWISH ? 2 : 1);      // swish keeps the pre-activation too
+            w += h->l_net[k].out[l] * ((h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) ? 2 : 1);      // swish keeps the pre-activation too, a BatchNorm layer its normalised input
             maxw = std::max<long long>(maxw, h->l_net[k].out[l]);
         }
     return w + 2 * maxw;
@@ -49,7 +50,7 @@ static int lform_workspace(eh_handle* h, long long count, EhLWs* W) {
             maxw = std::max(maxw, o);
             W->H[k][l] = p; p += cap * o;
             W->Z[k][l] = nullptr;
-            if (h->l_net[k].lact[l] == EH_ACT_SWISH) { W->Z[k][l] = p; p += cap * o; }
+            if (h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) { W->Z[k][l] = p; p += cap * o; }
         }
     W->D[0] = p; p += cap * maxw;
     W->D[1] = p; p += cap * maxw;
@@ -144,6 +145,69 @@ static void lform_gemm(eh_handle* h, const EhGemmArgs& g, int nz) {
     if (vec) hipLaunchKernelGGL((eh_gemm_kernel<ATR, BTR, EPI, true>), grid, dim3(256), 0, h->stream, g);
     else hipLaunchKernelGGL((eh_gemm_kernel<ATR, BTR, EPI, false>), grid, dim3(256), 0, h->stream, g);
 }
+// BatchNorm layer l of the one network (eh_bnl.hpp): H_l = act(scale xh + bias), xh from the statistics of this minibatch (train mode; kept in
+// Z_l for the backward; `update`: the running statistics move on) or from the running ones (test mode, nothing kept)
+static bool bnl_vec_ok(int n, std::initializer_list<const void*> ps) {
+    if (n % 4) return false;
+    for (const void* p : ps) if (reinterpret_cast<unsigned long long>(p) & 15ull) return false;
+    return true;
+}
+static int bnl_chunks(int B, int* chunk) {
+    const int nchunk = std::max(1, std::min<int>(EH_BNL_CHUNKS, (B + EH_BNL_CHUNK_ROWS - 1) / EH_BNL_CHUNK_ROWS));
+    *chunk = (B + nchunk - 1) / nchunk;
+    return (B + *chunk - 1) / *chunk;
+}
+static unsigned bnl_ew_grid(long long tot, bool vec) { return (unsigned)std::max<long long>(1, std::min<long long>(4096, ((vec ? tot / 4 : tot) + 255) / 256)); }
+static int bnl_forward_layer(eh_handle* h, int l, int B, bool train_mode, bool update, const EhLWs& W) {
+    const eh_handle_s::LNet& L = h->l_net[0];
+    const int n = L.out[l];
+    const float* theta = TH(h);
+    const float* gamma = L.lbn[l] == 1 ? theta + L.woff[l] : nullptr;
+    const float* beta = L.lbn[l] == 1 ? theta + L.boff[l] : nullptr;
+    const float* X = W.H[0][l - 1];
+    float* stat = h->bnl_stat + 2 * h->bnl_off[l];      // [c | d | rstd]
+    float* run = h->bnl_run + h->bnl_off[l];
+    if (train_mode) {
+        EhBnlArgs a{};
+        a.X = X; a.part = h->bnl_part; a.B = B; a.n = n; a.act = L.lact[l];
+        const int nchunk = bnl_chunks(B, &a.chunk);
+        hipLaunchKernelGGL((eh_bnl_colsum_kernel<false>), dim3((unsigned)((n + 63) / 64), (unsigned)nchunk), dim3(256), 0, h->stream, a);
+        hipLaunchKernelGGL(eh_bnl_fold_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->bnl_part, nchunk, X, B, n, h->bnl_eps[l], h->bnl_mom[l], stat, run, update ? 1 : 0);
+    }
+    EhBnlNormArgs na{};
+    na.X = X; na.Y = W.H[0][l]; na.Xh = train_mode ? W.Z[0][l] : nullptr;
+    na.mean = train_mode ? stat : run; na.d = train_mode ? stat + n : nullptr; na.second = train_mode ? stat + 2 * n : run + n; na.from_var = train_mode ? 0 : 1;
+    na.gamma = gamma; na.beta = beta; na.tot = (long long)B * n; na.n = n; na.act = L.lact[l]; na.eps = h->bnl_eps[l];
+    na.vec = bnl_vec_ok(n, {na.X, na.Y, na.Xh}) ? 1 : 0;
+    hipLaunchKernelGGL(eh_bnl_norm_kernel, dim3(bnl_ew_grid(na.tot, na.vec != 0)), dim3(256), 0, h->stream, na);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+// ... its backward: dY [B x n] -> d scale / d bias into the slab (row 0; zeros in the other rows), dZ of the layer below into dX
+static int bnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float* dX, int rows, const EhLWs& W) {
+    const eh_handle_s::LNet& L = h->l_net[0];
+    const int n = L.out[l];
+    const float* theta = TH(h);
+    const bool affine = L.lbn[l] == 1;
+    EhBnlArgs a{};
+    a.X = dY; a.Xh = W.Z[0][l]; a.Y = W.H[0][l]; a.gamma = affine ? theta + L.woff[l] : nullptr; a.beta = affine ? theta + L.boff[l] : nullptr;
+    a.part = h->bnl_part; a.B = B; a.n = n; a.act = L.lact[l];
+    const int nchunk = bnl_chunks(B, &a.chunk);
+    float* sums = h->bnl_part + (size_t)EH_BNL_CHUNKS * 2 * h->bnl_maxn;
+    hipLaunchKernelGGL((eh_bnl_colsum_kernel<true>), dim3((unsigned)((n + 63) / 64), (unsigned)nchunk), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(eh_bnl_fold_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->bnl_part, nchunk, n, sums,
+                       affine ? h->slab + L.woff[l] : nullptr, affine ? h->slab + L.boff[l] : nullptr, rows, (long long)h->n_acc);
+    EhBnlDxArgs d{};
+    d.dY = dY; d.Xh = a.Xh; d.Y = a.Y; d.gamma = a.gamma; d.beta = a.beta; d.rstd = h->bnl_stat + 2 * h->bnl_off[l] + 2 * n; d.sums = sums;
+    // (the layer below: a Dense layer's act' from its output -- swish: its pre-activation --; a BatchNorm layer takes its own in its own backward)
+    d.act_below = L.lbn[l - 1] ? (int)EH_ACT_IDENTITY : L.lact[l - 1];
+    d.Hb = (d.act_below == EH_ACT_SWISH) ? W.Z[0][l - 1] : W.H[0][l - 1];
+    d.dX = dX; d.tot = (long long)B * n; d.n = n; d.act = L.lact[l]; d.inv_b = 1.0f / (float)B;
+    d.vec = bnl_vec_ok(n, {d.dY, d.Xh, d.Y, d.Hb, d.dX}) ? 1 : 0;
+    hipLaunchKernelGGL(eh_bnl_dx_kernel, dim3(bnl_ew_grid(d.tot, d.vec != 0)), dim3(256), 0, h->stream, d);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
 // minibatch -> Xb (input BatchNorm applied), forward through every Dense layer; O^T [K][ldo] = the raw NN outputs
 // (lstop >= 0: a one-network model, only its layers below `lstop` run here -- the rest belongs to eh_lform_tailchain_kernel)
 static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool train_mode, bool bn_update, const EhLWs& W, int lstop = -1) {
@@ -152,7 +216,8 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
     if (h->l_nnets == 0) return EH_OK;        // no network (no neural parameter): the mechanistic stage reads the records itself
     EhStepArgs bn{};
     // (small minibatches: the prep kernel takes the batch statistics itself -- one dependent launch fewer)
-    static const bool nofuse = getenv("EH_LFORM_NOFUSE") != nullptr;
+    static const bool nofuse_env = getenv("EH_LFORM_NOFUSE") != nullptr;
+    const bool nofuse = nofuse_env || h->bnl;      // (BatchNorm layers in the chain: the plain loop below, one launch per layer and pass)
     const bool bn_self = train_mode && h->bn_on && !h->bn_ext && count > 0 && count <= 256 && !nofuse;
     if (train_mode && !bn_self) { if (int rc = eh_bn_prepare(h, sp, idx, first, count, bn_update, &bn)) return rc; }
     EhLPrepArgs pa{};
@@ -212,6 +277,7 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
         for (int l = 0; l < (lstop >= 0 ? lstop : L.nl); ++l) {
             if ((fused0 || fused01) && k == 0 && l == 0) continue;
             if (fused01 && k == 0 && l == 1) continue;
+            if (L.lbn[l]) { if (int rc = bnl_forward_layer(h, l, B, train_mode, bn_update, W)) return rc; continue; }
             EhGemmArgs g{};
             g.A = l == 0 ? W.Xb + L.c0 : W.H[k][l - 1]; g.lda = l == 0 ? net.P : L.in[l];      // (a network's predictors: its columns of the minibatch matrix)
             g.B = theta + L.woff[l]; g.ldb = L.out[l];                   // canonical (out, in) column-major == [in][out] row-major
@@ -247,7 +313,7 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     // Small minibatches: every layer's delta is kept (l_dk), the chain of delta products runs first and the weight gradients -- a
     // handful of tiles each, 4-6 us per dependent launch -- follow as ONE grouped launch of the tiled ones and one of the thin ones.
     static const long long lgroup_max = getenv("EH_LFORM_GROUP_MAX") ? atoll(getenv("EH_LFORM_GROUP_MAX")) : 4096;
-    bool grouped = count <= lgroup_max && h->l_nnets > 0;
+    bool grouped = count <= lgroup_max && h->l_nnets > 0 && !h->bnl;      // (the kept-deltas groups and the tail chain behind them hold Dense layers only)
     long long dk_floats = 0;
     // (sized by THIS minibatch, rounded up to a power of two -- not by the largest one the path serves: a B = 64 step of a deep, wide
     //  MultiNN model used to ask for up to the 1 GiB cap; advisor, round 3.  A larger batch later re-grows it, outside a capture.)
@@ -414,6 +480,12 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
         int which = 0;
         for (int l = L.nl - 1; l >= 0; --l) {
             const int in = L.in[l], out = L.out[l];
+            if (L.lbn[l]) {                    // a BatchNorm layer: dZ is d loss / d its output; its leaves' sums to the slab, the delta of the layer below to the other buffer
+                float* const dnext = W.D[which];
+                if (int rc = bnl_backward_layer(h, l, B, dZ, dnext, rows, W)) return rc;
+                dZ = dnext; dz_t = false; which ^= 1;
+                continue;
+            }
             const float* Hprev = l == 0 ? W.Xb + L.c0 : W.H[k][l - 1];
             const long long ldp = l == 0 ? net.P : in;
             EhGemmArgs g{};                    // dW_l^T [in x out] = Hprev^T [in x B] * dZ_l [B x out], split over the samples
@@ -447,6 +519,7 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
                     }
                     b.C = dnext; b.ldc = in; b.M = B; b.N = in; b.K = out; b.kchunk = out; b.c_zstride = 0;
                     b.H = L.lact[l - 1] == EH_ACT_SWISH ? W.Z[k][l - 1] : W.H[k][l - 1]; b.ldh = in; b.act = L.lact[l - 1];
+                    if (L.lbn[l - 1]) { b.H = W.H[k][l - 1]; b.act = EH_ACT_IDENTITY; }      // (the layer below is a BatchNorm layer: its backward applies its own act')
                     if (dz_t) lform_gemm<true, true, EH_GEPI_DACT>(h, b, 1); else lform_gemm<false, true, EH_GEPI_DACT>(h, b, 1);
                     HIPCHK(h, hipGetLastError());
                 }

@@ -417,6 +417,23 @@ class HybridEngine:
         m = np.ascontiguousarray(mean, np.float32); v = np.ascontiguousarray(var, np.float32)
         self._chk(self._lib.eh_set_bn_state(self._h, _fptr(m), _fptr(v), m.size))
 
+    def get_layer_state(self, l: int):
+        """running (mean, var) of the BatchNorm layer that is hidden layer `l` of the chain (model.bn_layers lists them)"""
+        n = int(self.desc.hidden[l]) if 0 <= int(l) < int(self.desc.n_hidden) else 0
+        m = np.empty(n, np.float32); v = np.empty(n, np.float32)
+        self._chk(self._lib.eh_get_layer_state(self._h, int(l), _fptr(m), _fptr(v), n))
+        return m, v
+
+    def set_layer_state(self, l: int, mean, var):
+        m = np.ascontiguousarray(mean, np.float32); v = np.ascontiguousarray(var, np.float32)
+        if m.shape != v.shape or m.ndim != 1:
+            raise ValueError(f"set_layer_state: mean {m.shape} and var {v.shape} must be vectors of the layer's width")
+        self._chk(self._lib.eh_set_layer_state(self._h, int(l), _fptr(m), _fptr(v), m.size))
+
+    def set_layer_norm(self, l: int, momentum: float = 0.1, epsilon: float = 1e-5):
+        """momentum and epsilon of the BatchNorm layer that is hidden layer `l` (eh_set_layer_norm)"""
+        self._chk(self._lib.eh_set_layer_norm(self._h, int(l), float(momentum), float(epsilon)))
+
     def set_training_loss(self, name):
         """TrainConfig.training_loss (src/config/TrainingConfig.jl:64): mse | rmse | mae | nseLoss (one pass) |
         pearsonLoss | kgeLoss | pbkgeLoss (forward passes for the batch moments first; not in fused_update mode, not data parallel;

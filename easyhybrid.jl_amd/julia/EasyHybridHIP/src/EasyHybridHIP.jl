@@ -22,6 +22,7 @@ const LIB = Ref{String}(get(ENV, "EASYHYBRID_HIP_LIB", joinpath(@__DIR__, "..", 
 
 const EH_MAX_HIDDEN, EH_MAX_PARAMS, EH_MAX_FORC, EH_MAX_TARG = 8, 8, 4, 4
 const EH_SPLIT_TRAIN, EH_SPLIT_VAL = Int32(0), Int32(1)
+const EH_LAYER_BATCHNORM, EH_LAYER_BN_NOAFFINE = Int32(40), Int32(8)      # net_activation[l] of a BatchNorm layer inside the chain: EH_LAYER_BATCHNORM [+ EH_LAYER_BN_NOAFFINE] + its activation id
 const EH_LAYER_LSTM, EH_LAYER_GRU, EH_LAYER_RNN = Int32(16), Int32(24), Int32(32)      # net_activation[l] of a recurrent hidden layer (EH_LAYER_RNN + the RNNCell's activation id)
 
 # mirror of `eh_model_desc` (field order and widths exactly as in the header)
@@ -694,6 +695,17 @@ function get_bn_state(e::HybridEngine, P::Integer)
 end
 set_bn_state!(e::HybridEngine, m::Vector{Float32}, v::Vector{Float32}) =
     check(e, @ccall LIB[].eh_set_bn_state(e.h::Ptr{Cvoid}, m::Ptr{Float32}, v::Ptr{Float32}, length(m)::Int64)::Int32)
+
+# running statistics of a BatchNorm layer inside the chain (hidden layer `layer` of the descriptor, 0-based, `n` units), its momentum and epsilon
+function get_layer_state(e::HybridEngine, layer::Integer, n::Integer)
+    m = Vector{Float32}(undef, n); v = Vector{Float32}(undef, n)
+    check(e, @ccall LIB[].eh_get_layer_state(e.h::Ptr{Cvoid}, layer::Int32, m::Ptr{Float32}, v::Ptr{Float32}, n::Int64)::Int32)
+    return m, v
+end
+set_layer_state!(e::HybridEngine, layer::Integer, m::Vector{Float32}, v::Vector{Float32}) =
+    check(e, @ccall LIB[].eh_set_layer_state(e.h::Ptr{Cvoid}, layer::Int32, m::Ptr{Float32}, v::Ptr{Float32}, length(m)::Int64)::Int32)
+set_layer_norm!(e::HybridEngine, layer::Integer, momentum::Real, epsilon::Real) =
+    check(e, @ccall LIB[].eh_set_layer_norm(e.h::Ptr{Cvoid}, layer::Int32, Float32(momentum)::Float32, Float32(epsilon)::Float32)::Int32)
 
 """
 two-pass training losses (pearsonLoss / kgeLoss / pbkgeLoss; rmse on a multi-target model) under DP: the shard's moment sums of the

@@ -261,13 +261,44 @@ class Dropout:
         return f"Dropout({self.p})"
 
 
+class BatchNorm:
+    """Lux `BatchNorm(n, activation; affine, track_stats, momentum, epsilon)` as a DESCRIPTION of a layer inside `hidden_layers = Chain(...)`:
+    in training y = activation(scale (x - mean_B) / sqrt(var_B + epsilon) + bias) over all rows of the minibatch, the gradient through both
+    statistics; evaluation and predictions use the running statistics (start 0 / 1, moved by `momentum`, the variance by the unbiased
+    estimate).  affine = True adds the leaves `scale` (ones) and `bias` (zeros); no weight_l2 term reads them."""
+
+    def __init__(self, dims: int, activation="identity", affine: bool = True, track_stats: bool = True, momentum: float = 0.1, epsilon: float = 1e-5):
+        if not track_stats:
+            raise NotImplementedError("BatchNorm(track_stats = false): evaluation on the statistics of its own batch has no device kernel (the layer keeps running statistics)")
+        self.dims, self.activation, self.affine, self.track_stats = int(dims), _act_name(activation), bool(affine), True
+        self.momentum, self.epsilon = float(momentum), float(epsilon)
+        if self.dims < 1:
+            raise ValueError(f"BatchNorm({dims!r}): the layer needs at least one unit")
+        if not 0.0 <= self.momentum <= 1.0 or not self.epsilon > 0.0:
+            raise ValueError(f"BatchNorm(momentum = {momentum!r}, epsilon = {epsilon!r}): 0 <= momentum <= 1, epsilon > 0")
+
+    def __repr__(self):
+        return f"BatchNorm({self.dims}{'' if self.activation == 'identity' else ', ' + self.activation}{'' if self.affine else ', affine=false'})"
+
+
+BN_LAYER = "bn:"          # the "activation" of a hidden layer that is BatchNorm(n, act): "bn:<act>", EH_LAYER_BATCHNORM + the activation's id
+BN_LAYER_NOAFFINE = "bn0:"    # ... with affine = false: EH_LAYER_BATCHNORM + EH_LAYER_BN_NOAFFINE + the activation's id
+
+
+def _bn_kind(a) -> int:
+    """a hidden layer's "activation" -> 1 when the layer is a BatchNorm with scale / bias, 2 without, 0 otherwise"""
+    if not isinstance(a, str):
+        return 0
+    return 1 if a.startswith(BN_LAYER) else (2 if a.startswith(BN_LAYER_NOAFFINE) else 0)
+
+
 def _split_dropout(hidden_layers):
     """Chain with Dropout layers -> (the Chain without them, [p_0 .. p_{L-1}] per hidden layer or None).  A Dropout belongs to the hidden
     layer in front of it; as the first element that is the layer the reference prepends (Dense(in_dim, first_h, activation)).
     Dropout(0) is Lux's NoOpLayer and disappears.  Chains around a Recurrence are left to _hidden_widths (and its refusals)."""
     if not isinstance(hidden_layers, Chain) or not any(isinstance(l, Dropout) for l in hidden_layers.layers):
         return hidden_layers, None
-    if any(isinstance(l, Recurrence) for l in hidden_layers.layers):
+    if any(isinstance(l, (Recurrence, BatchNorm)) for l in hidden_layers.layers):
         return hidden_layers, None
     rest, rates, prev = [], {}, False
     for i, l in enumerate(hidden_layers.layers):
@@ -303,6 +334,10 @@ def _cell_kind(a) -> Optional[str]:
 def _layer_code(a: str) -> int:
     """net_activation[l] of the descriptor"""
     kind = _cell_kind(a)
+    if _bn_kind(a) == 1:
+        return L.EH_LAYER_BATCHNORM + L.ACTIVATIONS[a[len(BN_LAYER):]]
+    if _bn_kind(a) == 2:
+        return L.EH_LAYER_BATCHNORM + L.EH_LAYER_BN_NOAFFINE + L.ACTIVATIONS[a[len(BN_LAYER_NOAFFINE):]]
     if kind == "rnn":
         return L.EH_LAYER_RNN + L.ACTIVATIONS[a[len(RNN_LAYER):]]
     return {"lstm": L.EH_LAYER_LSTM, "gru": L.EH_LAYER_GRU}[kind] if kind else L.ACTIVATIONS[a]
@@ -326,6 +361,8 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
         ls = hidden_layers.layers
         if not ls:
             raise ValueError("hidden_layers: an empty Chain has no dimensions (NNModels.jl: 'Could not determine input dimension of hidden_layers Chain.')")
+        if any(isinstance(l, BatchNorm) for l in ls):
+            return _bn_chain_widths(ls, act, per_layer)
         if any(isinstance(l, Recurrence) for l in ls):
             # a chain that ends in Recurrence(LSTMCell) gets its sequence head (NNModels.jl:171-211):
             # Dense(in_dim, I, act) -> Recurrence(LSTMCell(I => H)) -> RecurrenceOutputDense(H => H, act) -> Dense(H, out_dim), per time step
@@ -360,6 +397,34 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
     return (widths, None) if per_layer else widths
 
 
+def _bn_chain_widths(ls, act: str, per_layer: bool):
+    """a Chain that holds BatchNorm layers next to Dense layers -> (widths, activations) with one entry per hidden layer of the descriptor:
+    the Dense layer the reference puts in front (first_h read off the chain's first layer -- a BatchNorm's dims, NNModels.jl:156-169), then
+    every layer of the chain, a BatchNorm as an entry as wide as the layer in front of it"""
+    if not per_layer:
+        raise NotImplementedError("hidden_layers Chain: BatchNorm layers in a MultiNN model have no device kernel (they are built for single-network models)")
+    if any(isinstance(l, Recurrence) for l in ls):
+        raise NotImplementedError("hidden_layers Chain: a BatchNorm layer next to a Recurrence has no device kernel (sequence models take no BatchNorm)")
+    if any(isinstance(l, Dropout) for l in ls):
+        raise NotImplementedError("hidden_layers Chain: a BatchNorm layer next to a Dropout has no device kernel (dropout runs on the fused per-wave kernels, BatchNorm layer by layer)")
+    first = ls[0].dims if isinstance(ls[0], BatchNorm) else getattr(ls[0], "in_dims", None)
+    widths, acts, w = [first], [act], first
+    for i, l in enumerate(ls):
+        if isinstance(l, BatchNorm):
+            if l.dims != w:
+                raise ValueError(f"hidden_layers Chain: layer {i + 1} is BatchNorm({l.dims}), the layer in front of it gives {w}")
+            acts.append((BN_LAYER if l.affine else BN_LAYER_NOAFFINE) + l.activation)
+        elif isinstance(l, Dense):
+            if l.in_dims != w:
+                raise ValueError(f"hidden_layers Chain: layer {i + 1} takes {l.in_dims} inputs, the layer in front of it gives {w}")
+            w = l.out_dims
+            acts.append(_act_name(l.activation))
+        else:
+            raise NotImplementedError(f"hidden_layers Chain: layer {i + 1} is {type(l).__name__}; only Dense and BatchNorm layers have a device kernel here")
+        widths.append(w)
+    return widths, acts
+
+
 @dataclass
 class SingleNNHybridModel:
     """Field-for-field mirror of the reference struct (GenericHybridModel.jl:44-63); `NN` is the
@@ -382,6 +447,7 @@ class SingleNNHybridModel:
     net_activations: Optional[List[str]] = None      # MultiNN with activation::NamedTuple: the activation of net k (None = one for all)
     layer_activations: Optional[List[str]] = None    # single network from `hidden_layers::Chain` whose layers differ: the activation of hidden layer l (None = one for all)
     dropout: Optional[List[float]] = None            # `hidden_layers::Chain` with Dropout layers: the rate behind hidden layer l (None = none anywhere)
+    batchnorm: Optional[Dict[int, Tuple[float, float]]] = None      # `hidden_layers::Chain` with BatchNorm layers: hidden layer l -> (momentum, epsilon) (None = none anywhere)
 
     # -- sizes ---------------------------------------------------------------------------------
     @property
@@ -413,6 +479,11 @@ class SingleNNHybridModel:
         """the activation of a sequence model's RNNCell, None otherwise"""
         return self.layer_activations[self.lstm_layer][len(RNN_LAYER):] if self.cell == "rnn" else None
 
+    @property
+    def bn_layers(self) -> List[int]:
+        """the hidden layers (indices into NN, = the descriptor's) that are BatchNorm layers, in chain order"""
+        return [l for l, a in enumerate(self.layer_activations or ()) if _bn_kind(a)]
+
     def leaves(self):
         """[(network index, layer index, leaf name, shape)] of the networks in ComponentArray order: Dense layers have `weight` (out, in) and
         `bias`; the recurrent layer `weight_ih` (nH, I), `weight_hh` (nH, H), `bias_ih`, `bias_hh` (nH): n = 4 gate blocks [i | f | g | o] of
@@ -421,7 +492,10 @@ class SingleNNHybridModel:
         ng = CELL_GATES.get(self.cell, 0)
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
-                if ll is not None and li == ll:
+                bn = _bn_kind(self.layer_activations[li]) if (self.layer_activations is not None and li < len(self.layer_activations)) else 0
+                if bn:       # BatchNorm: `scale` and `bias` (affine), or nothing
+                    out += [(k, li, "scale", (o,)), (k, li, "bias", (o,))] if bn == 1 else []
+                elif ll is not None and li == ll:
                     out += [(k, li, "weight_ih", (ng * o, i)), (k, li, "weight_hh", (ng * o, o)), (k, li, "bias_ih", (ng * o,)), (k, li, "bias_hh", (ng * o,))]
                 else:
                     out += [(k, li, "weight", (o, i)), (k, li, "bias", (o,))]
@@ -454,11 +528,15 @@ class SingleNNHybridModel:
         parts = []
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
+                if li in self.bn_layers:       # BatchNorm: scale = ones, bias = zeros (affine), or no leaf at all
+                    if _bn_kind(self.layer_activations[li]) == 1:
+                        parts += [np.ones(o, np.float32), np.zeros(o, np.float32)]
+                    continue
                 if li == self.lstm_layer:      # LSTMCell, GRUCell, RNNCell: every leaf U(+-1/sqrt(H))
                     bh = 1 / math.sqrt(o)
                     parts += [rng.uniform(-bh, bh, shape).astype(np.float32).flatten(order="F") for _, l2, _, shape in self.leaves() if l2 == li]
                     continue
-                gain = _ACT_GAIN[self.activation_of(k, li)] if li < len(net) - 1 else 1.0
+                gain = _ACT_GAIN[self.activation_of(k, li)] if li < len(net) - 1 else 1.0      # (a Dense layer in front of a BatchNorm keeps the gain of its own activation)
                 bw = gain * math.sqrt(3.0 / i)
                 parts.append(rng.uniform(-bw, bw, (o, i)).astype(np.float32).flatten(order="F"))
                 parts.append(rng.uniform(-1 / math.sqrt(i), 1 / math.sqrt(i), o).astype(np.float32))
@@ -488,10 +566,10 @@ class SingleNNHybridModel:
         if net is not None and net not in names:
             raise KeyError(f"weight_l2: no network named {net!r} (networks: {[n for n in names if n is not None]})")
         m = np.zeros(self.n_theta, bool)
-        off = 0
-        for k, _, leaf, shape in self.leaves():
+        off, bn = 0, set(self.bn_layers)
+        for k, li, leaf, shape in self.leaves():
             n = int(np.prod(shape))
-            if (net is None or net == names[k]) and leaf == key:
+            if (net is None or net == names[k]) and leaf == key and li not in bn:      # (extract_weights.jl:24: a BatchNorm's scale / bias are skipped)
                 m[off:off + n] = True
             off += n
         return m
@@ -508,6 +586,17 @@ class SingleNNHybridModel:
     def unpack(self, theta: np.ndarray):
         """flat theta -> (ps = [(weight (out,in), bias)...], {global: raw})"""
         off, nets = 0, []
+        if self.bn_layers:                   # a BatchNorm layer unpacks to a dict of its leaves ({} with affine = false)
+            layers = [{} if li in self.bn_layers else [None, None] for li in range(len(self.NN))]
+            for _, li, name, shape in self.leaves():
+                n = int(np.prod(shape))
+                v = theta[off:off + n].reshape(shape, order="F") if len(shape) == 2 else theta[off:off + n]
+                off += n
+                if li in self.bn_layers:
+                    layers[li][name] = v
+                else:
+                    layers[li][0 if name == "weight" else 1] = v
+            return [l if isinstance(l, dict) else tuple(l) for l in layers], {g: theta[off + j:off + j + 1] for j, g in enumerate(self.global_param_names)}
         if self.lstm_layer is not None:      # sequence model: the recurrent layer unpacks to a dict of its four leaves
             layers, cur = [], {}
             for _, li, name, shape in self.leaves():
@@ -536,7 +625,7 @@ class SingleNNHybridModel:
         names = ["ps"] if self.NNs is None else list(self.neural_param_names)
         nets = self.nets if self.nets else [[]]
         for name, net in zip(names, nets):
-            n = self.n_nn if self.lstm_layer is not None else sum(o * i + o for o, i in net)
+            n = self.n_nn if (self.lstm_layer is not None or self.bn_layers) else sum(o * i + o for o, i in net)
             out[name] = (off, off + n)
             off += n
         for g in self.global_param_names:
@@ -646,6 +735,9 @@ class SingleNNHybridModel:
                 eng.set_option("precision", 1 if prec == "bf16_fwd" else 2)
             if self.dropout is not None:                  # (train() sets the seed of its run and the step it continues from)
                 eng.set_dropout(self.dropout, seed=0, step=0)
+            for l, (mom, eps) in (self.batchnorm or {}).items():
+                if (mom, eps) != (0.1, 1e-5):
+                    eng.set_layer_norm(l, mom, eps)
         except Exception:
             eng.close()
             raise
@@ -756,8 +848,15 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
         if t not in ms.outputs:
             raise ValueError(f"target {t!r} is not an output of {ms.name} {ms.outputs}")
     act = _act_name(activation)
+    chain = hidden_layers
     hidden_layers, dropout = _split_dropout(hidden_layers)
     hidden_layers, layer_acts = _hidden_widths(hidden_layers, act, per_layer=True)
+    batchnorm = None
+    if any(_bn_kind(a) for a in (layer_acts or ())):
+        if kwargs.get("precision", "f32") != "f32":
+            raise NotImplementedError(f"precision = {kwargs['precision']!r} with BatchNorm layers in hidden_layers: they run on the fp32 layer-wise kernels only")
+        bns = [l for l in chain.layers if isinstance(l, BatchNorm)]
+        batchnorm = {i: (b.momentum, b.epsilon) for i, b in zip([i for i, a in enumerate(layer_acts) if _bn_kind(a)], bns)}
     if dropout is not None and (len(hidden_layers) > DROPOUT_MAX_LAYERS or max(hidden_layers) > DROPOUT_MAX_WIDTH):
         raise NotImplementedError(f"hidden_layers Chain: Dropout on hidden layers {hidden_layers}: the dropout kernels are the per-wave fused family, "
                                   f"1..{DROPOUT_MAX_LAYERS} hidden layers of at most {DROPOUT_MAX_WIDTH} units")
@@ -772,4 +871,5 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
         config["layer_activations"] = list(layer_acts)
     return SingleNNHybridModel(NN, predictors, forcing, targets, ms, parameters, neural_param_names, global_param_names,
                                fixed, bool(scale_nn_outputs), bool(start_from_default), config,
-                               layer_activations=None if no_nn else layer_acts, dropout=None if no_nn else dropout)
+                               layer_activations=None if no_nn else layer_acts, dropout=None if no_nn else dropout,
+                               batchnorm=None if no_nn else batchnorm)

@@ -873,6 +873,9 @@ def _lbfgs_check(model, tc: TrainConfig, solve_kw):
     if getattr(model, "dropout", None) is not None:
         raise NotImplementedError("train(opt = LBFGS()): Dropout layers -- the line search needs the same objective at every trial point, the masks "
                                   "change with every pass: not built")
+    if getattr(model, "bn_layers", None):
+        raise NotImplementedError("train(opt = LBFGS()): BatchNorm layers in hidden_layers -- the Optimization.jl driver carries no layer state "
+                                  "(their running statistics would stay at their start): not built")
     if bool(model.config.get("input_batchnorm")):
         raise NotImplementedError("train(opt = LBFGS()): input BatchNorm -- the reference's Optimization.jl driver never carries the layer state: not built")
     if tc.distributed is True:
@@ -1055,6 +1058,10 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         raise NotImplementedError("train(opt = LBFGS(), distributed=True): data parallelism is not built for the Optimization.jl driver")
     if has_drop and dist_run:
         raise NotImplementedError("train(distributed=True): Dropout layers are not built for data parallelism (the masks are drawn per handle)")
+    bn_layers = list(getattr(model, "bn_layers", None) or [])
+    if bn_layers and dist_run:
+        raise NotImplementedError("train(distributed=True): BatchNorm layers in hidden_layers are not built for data parallelism (their statistics would "
+                                  "have to be those of the global batch)")
     xfn = _extra_fn(tc.extra_loss)                    # extra_loss as a function of the predictions (compute_loss.jl:31-34): recorded, its entries ride on targets of their own
     if xfn is not None and engine is not None and not engine.n_pseudo:
         raise ValueError("train(engine = ...): an extra_loss of the predictions needs an engine created with it (model.engine(device, extra_fn = f))")
@@ -1122,13 +1129,17 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         else:
             theta = np.asarray(tc.train_from.ps if isinstance(tc.train_from, TrainResults) else tc.train_from[0], np.float32)
         eng.set_params(theta)
+        if bn_layers and tc.train_from is not None:      # the layer state of the model the run continues from (its st.st_layers)
+            st_from = tc.train_from.st if isinstance(tc.train_from, TrainResults) else (tc.train_from[1] if len(tc.train_from) > 1 else None)
+            for l, s_l in ((st_from or {}).get("st_layers") or {}).items():
+                eng.set_layer_state(int(l), s_l["running_mean"], s_l["running_var"])
         if lbfgs is None:
             _opt_setup(eng, tc.opt, model)
         eng.set_training_loss(tc.training_loss)
         xterms = _extra_terms(tc.extra_loss)
         aggn = _agg_name(tc.agg)
         _apply_extra_loss(eng, model, xterms, aggn, eng.n_pseudo)
-        _apply_step_mode(eng, replace(tc, fused_update=False) if lbfgs is not None else tc, is_seq)
+        _apply_step_mode(eng, replace(tc, fused_update=False) if lbfgs is not None else tc, is_seq or bool(bn_layers))      # (BatchNorm layers: the engine runs the pair, as for sequence models)
         if lbfgs is not None:      # (after the losses and options: the mode refuses what changes the objective between trial points)
             eng.lbfgs_init(m=lbfgs.m, c1=lbfgs.c1, c2=lbfgs.c2, max_linesearch=lbfgs.max_linesearch, initial_step=lbfgs.initial_step,
                            g_tol=float(solve_kw.get("g_tol", 1e-5)), f_reltol=float(solve_kw.get("f_reltol", 0.0)))
@@ -1161,6 +1172,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         best_loss, best_ps, best_epoch, counter = init.l_val[first_lt][aggn], theta.copy(), 0, 0
         has_bn = bool(model.config.get("input_batchnorm"))
         best_bn = eng.get_bn_state() if has_bn else None            # early_stopping.jl update!: best_ps AND best_st
+        best_ls = {l: eng.get_layer_state(l) for l in bn_layers}      # ... the BatchNorm layers of the chain belong to best_st too
         seed0 = tc.random_seed if tc.random_seed is not None else int(rng.integers(2**31))
         tm = {"steps_s": 0.0, "eval_s": 0.0, "host_s": 0.0, "epochs": 0} if tc.timing else None
         if tm is not None:
@@ -1228,6 +1240,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
                 best_loss, best_ps, best_epoch, counter = cur, eng.get_params(), epoch, 0
                 if has_bn:
                     best_bn = eng.get_bn_state()
+                best_ls = {l: eng.get_layer_state(l) for l in bn_layers}
                 if not tc.keep_history:
                     history[0] = snap
             else:
@@ -1245,11 +1258,16 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         eng.set_params(ps)
         if has_bn:
             eng.set_bn_state(*bn_out)                                # the predictions below use the state that belongs to `ps`
+        ls_out = best_ls if tc.return_model == "best" else {l: eng.get_layer_state(l) for l in bn_layers}
+        for l, (m_l, v_l) in ls_out.items():
+            eng.set_layer_state(l, m_l, v_l)
 
         fixed = {f: np.float32(model.parameters.default(f)) for f in model.fixed_param_names}
         st = {"fixed": fixed}
         if has_bn:
             st["st_nn"] = {"running_mean": bn_out[0], "running_var": bn_out[1]}      # Lux BatchNorm state of the returned model (best_or_final)
+        if bn_layers:      # ... and of the chain's BatchNorm layers, by hidden layer
+            st["st_layers"] = {l: {"running_mean": m_l, "running_var": v_l} for l, (m_l, v_l) in ls_out.items()}
         if tc.predictions not in ("lazy", "eager"):
             raise ValueError("predictions must be 'lazy' or 'eager'")
         if own and tc.predictions == "lazy":

@@ -76,6 +76,16 @@ typedef enum eh_activation { EH_ACT_TANH = 0, EH_ACT_SIGMOID = 1, EH_ACT_RELU = 
 #define EH_LAYER_GRU 24
 #define EH_LAYER_RNN 32       /* .. EH_LAYER_RNN + EH_ACT_IDENTITY */
 #define EH_MAX_SEQ_WINDOW 64  /* longest input window of a sequence model */
+/* ... or Lux's BatchNorm(hidden[l], act) behind the layer in front of it (EH_LAYER_BATCHNORM + its eh_activation TANH..IDENTITY;
+ * EH_LAYER_BN_NOAFFINE added: affine = false).  hidden[l] must equal hidden[l-1] (l >= 1: hidden layer 0 is the Dense layer the reference
+ * puts in front of every chain); such a layer counts towards EH_MAX_HIDDEN.  Training: y = act(scale (x - mu_B) / sqrt(var_B + eps) + bias)
+ * with the mean and the biased variance over all rows of the minibatch (rows whose targets are NaN included), the gradient through both;
+ * forward / eval: the running statistics (eh_get_layer_state).  Flat theta: the layer's `scale` (ones) and `bias` (zeros), hidden[l] each,
+ * at its place in chain order; none with affine = false.  No weight_l2 term reads them.  One network (n_nets == 0), fp32, always the
+ * layer-wise form whatever the widths; refused with the reason: Dropout, a recurrent layer in the same chain, data parallelism, L-BFGS, graph
+ * capture, "fused_update" 1, "multi_step", "specialize", "precision". */
+#define EH_LAYER_BATCHNORM 40 /* .. EH_LAYER_BATCHNORM + EH_ACT_IDENTITY */
+#define EH_LAYER_BN_NOAFFINE 8 /* EH_LAYER_BATCHNORM + EH_LAYER_BN_NOAFFINE + activation: 48 .. 52 */
 
 /* registry of mechanistic models (the reference takes an arbitrary Julia closure,
  * src/models/GenericHybridModel.jl:425; a closure cannot run in a kernel, so the engine ships
@@ -312,6 +322,14 @@ int32_t eh_lbfgs_host_decide(const eh_lbfgs_opts* opts, int32_t maxiters, double
  * Training steps use the statistics of their own minibatch and update these with momentum 0.1; forward / eval use them. */
 int32_t eh_get_bn_state(eh_handle* h, float* running_mean, float* running_var, int64_t n_predictors);
 int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* running_var, int64_t n_predictors);
+/* The same of a BatchNorm layer inside the chain (EH_LAYER_BATCHNORM at hidden layer `layer`; n = hidden[layer]): running mean (starts at
+ * 0) and variance (1).  eh_train_step / eh_train_epoch move them with the layer's momentum (the variance by the unbiased m / (m - 1)
+ * estimate, m = rows of the minibatch; m = 1: factor 1); eh_loss_and_grad uses the batch statistics and leaves them alone.
+ * eh_set_layer_norm: the layer's momentum (0..1) and epsilon (> 0); defaults 0.1 and 1e-5.
+ * EH_ESTATE: hidden layer `layer` is no BatchNorm layer. */
+int32_t eh_get_layer_state(eh_handle* h, int32_t layer, float* running_mean, float* running_var, int64_t n);
+int32_t eh_set_layer_state(eh_handle* h, int32_t layer, const float* running_mean, const float* running_var, int64_t n);
+int32_t eh_set_layer_norm(eh_handle* h, int32_t layer, float momentum, float epsilon);
 
 /* Optimisers.setup(rule, ps): zero moments, t = 0 (src/training/initialization.jl:42-44) */
 int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay);
