@@ -966,7 +966,8 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         HIPCHK_C(hipMemset(h->gacc, 0, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));
         h->ord_soff = (n.n_theta + 3) & ~3;
         h->ord_rs = h->ord_soff + ((h->n_acc - n.n_theta + 3) & ~3);
-        const size_t ob = sizeof(unsigned) * 32 * EH_ORD_GROUPS + sizeof(float) * (size_t)2 * (EH_ORD_ROWS + EH_ORD_GROUPS) * h->ord_rs;
+        // (counters | rows | group rows | the scalars' block partials [2][4][16][4], addressed from the group rows: no pointer of their own)
+        const size_t ob = sizeof(unsigned) * 32 * EH_ORD_GROUPS + sizeof(float) * ((size_t)2 * (EH_ORD_ROWS + EH_ORD_GROUPS) * h->ord_rs + 2 * EH_ORD_PART);
         HIPCHK_C(hipMalloc(&h->ord, ob));
         HIPCHK_C(hipMemset(h->ord, 0, ob));      // (the counters start at 0; every launch leaves them there)
         HIPCHK_C(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(h->ord + 32 * EH_ORD_GROUPS), (int)EH_ORD_EMPTY, (size_t)2 * EH_ORD_ROWS * h->ord_rs));      // (the rows: "not written")
@@ -1851,6 +1852,8 @@ static bool ord_ok(const eh_handle* h, int grid) {
     if (!h->fused || !h->fused_det || !h->ord || grid <= 1 || grid > (int)EH_ORD_ROWS || h->chain.n || h->drop_on) return false;
     if (h->lform || h->arch->wide || h->p2p_on || h->net.T != 1 || h->net.mech == EH_MECH_PROGRAM || h->net.loss == EH_LOSS_PROGRAM || h->act == EH_ACT_PER_NET) return false;
     if (h->img.l2c != 0.0f || h->img.l2w || two_pass_mask(h->net) || h->dp_weights || h->dp_moments) return false;
+    // (one target: the row's scalars are ONE 16-byte vector, all four words written by the gather -- the marker regime of the hand-off counts on it)
+    if (h->n_acc != h->net.n_theta + 4 || h->ord_rs != h->ord_soff + 4) return false;
     // (the step stages its row in LDS over the parameter image before it stores it)
     return h->n_acc < 8192 && h->ord_rs <= h->arch->img_floats && (cw_env == 0 || cw_env == 16);
 }

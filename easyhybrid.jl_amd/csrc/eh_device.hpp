@@ -178,21 +178,28 @@ struct EhP2P {
 // workgroup b stores its row write-through (16-byte sc1 stores) into a row slot and takes a ticket on the counter of its group g = b % 16
 // (a 128-byte line of its own); the workgroup whose add comes last in its group folds the group's rows in that same order into group row g.  The
 // next step's prologue sums the 16 group rows in order (absent groups: + 0, as the pair's idle row groups) and folds the rows' scalars
-// [S | n | Sy | Syy] with the reduce kernel's butterfly, then applies the update as the mode-1 prologue does.  Nobody waits for
+// [S | n | Sy | Syy] with the reduce kernel's butterfly (its first two levels done per group by the last arrivers, below), then applies the update as the mode-1 prologue does.  Nobody waits for
 // anybody: no spin, no fence.  Two slots of each (parity `slot`): a fast workgroup of step s + 1 rewrites its row while a slow one
 // still reads step s's rows in its prologue; step s + 2 starts only once step s + 1 (every reader of step s's slot) has ended.
 template <int CTRL> __device__ __forceinline__ float eh_dpp(float v);      // (below: one DPP move)
 enum { EH_ORD_GROUPS = 16, EH_ORD_ROWS = 256 };
+// The rows' scalars [S | n | Sy | Syy] take the butterfly's first two levels (xor 32, xor 16) in the tail as well: those never leave a
+// group, so the group's last arriver forms the four block partials of its group next to the group row, and the next prologue reads one
+// coalesced KB of them (one 16-byte vector per lane of one wave) where it read 256 rows' scalar vectors, a cache line each.
+enum { EH_ORD_PART = 4 * EH_ORD_GROUPS * 4 };      // floats of one slot of the block partials: [4 blocks q][16 groups i][4]
+#if defined(EH_AB_ORD_PARENT) && !defined(EH_AB_ORD_ROW_SCALARS)
+#define EH_AB_ORD_ROW_SCALARS      // (the older A/B keeps meaning what it meant: the whole butterfly in the prologue)
+#endif
 struct EhOrd {
     float* rows;           // [2][EH_ORD_ROWS][rs]: one row per workgroup -- gradient at [0, n_theta), [S | n | Sy | Syy] at soff
-    float* grows;          // [2][EH_ORD_GROUPS][rs]: the group rows (gradient only)
+    float* grows;          // [2][EH_ORD_GROUPS][rs]: the group rows (gradient only); behind them [2][EH_ORD_PART]: the scalars' block partials
     unsigned* cnt;         // group g's ticket counter at cnt[32 g]; every group's last arriver sets it back to 0
     unsigned* err;         // host-visible word, set when a group's rows did not arrive before the deadline (eh_synchronize reports it)
     int rs, soff;          // row stride and offset of the scalar block: multiples of 4 floats (16-byte loads of the scalars)
     int slot;              // this step writes slot `slot`, its prologue reads slot `slot ^ 1`
     int prev_grid;         // workgroups of the step whose sums are pending (the rows and groups to read)
 };
-// The gradient words of the rows hold EH_ORD_EMPTY whenever no step in flight has written them: the buffer starts so, and the consumer
+// The words of the rows (gradient and scalar vector) hold EH_ORD_EMPTY whenever no step in flight has written them: the buffer starts so, and the consumer
 // of a pending step's sums (the next ordered step, or eh_ord_flush_kernel) writes it back into that step's rows (eh_ord_reset): off the
 // tail of the step that folds them.  It is a signalling NaN, a pattern no VALU result has (IEEE mode quiets
 // every NaN result), so a stored sum is never mistaken for it, and a word that still holds it has not arrived yet.  (No step number in
@@ -202,7 +209,7 @@ struct EhOrd {
 // Diagnostic builds (-DEH_STAMPS, tools/stamps_ord.py): the hand-off, which workgroup 0's stamps do not see.  Thread 0 of every group's
 // last arriver records (shader clock, wall clock) pairs at stamps[EH_ORD_ST_TAIL + 10 g ...]: [0] its row stored, [1] about to take the
 // ticket, [2] the ticket's answer known to the workgroup, [3] the group's rows read and folded, [4] the group row stored (a wait only
-// this build has); workgroup 0 at stamps[EH_ORD_ST_PRO ...]: [0] image staged, [1] the rows' scalars folded (wave 0).
+// this build has); workgroup 0 at stamps[EH_ORD_ST_PRO ...]: [0] image staged, [1] the scalars folded (both by the wave that folds).
 enum { EH_ORD_ST_TAIL = 32, EH_ORD_ST_PRO = EH_ORD_ST_TAIL + 10 * EH_ORD_GROUPS, EH_STAMP_WORDS = 256 };
 #ifdef EH_STAMPS
 #define EH_ORD_TICK(ts, p)                                                                            \
@@ -220,7 +227,35 @@ __device__ __forceinline__ int eh_ord_pos(int e, int nth, int soff) { return e <
 // with the same additions: lane 16 q + i holds rows 64 q + i + {0, 16, 32, 48}, so the butterfly's xor 32 and xor 16 are adds in
 // registers, xor 8 ... xor 1 are DPP adds within the lane's row of 16, and four readlanes take the blocks' sums.  (After each butterfly
 // level a lane's value equals its partner's bit for bit -- addition commutes -- which is what lets row_ror:4 stand in for xor 4.)
+// The register adds are the tail's (eh_ord_publish: part[q][i] = (c0 + c2) + (c1 + c3) over the rows of group i in block q, stored at
+// [q][i], which is lane 16 q + i's vector); a lane whose group the pending step did not have takes 0, as its four absent rows gave --
+// a step of a smaller grid leaves stale partials of absent groups behind.
 // eh_ord_scalar_loads issues the loads, eh_ord_scalar_fold folds; every lane of the wave must be active.
+// (EH_AB_ORD_ROW_SCALARS, through EH_JIT_DEFINES: the consumer as it was -- four scattered row loads per lane and all six levels here.)
+#ifndef EH_AB_ORD_ROW_SCALARS
+enum { EH_ORD_NSV = 1 };
+__device__ __forceinline__ f32x4 eh_ord_scalar_fold(const EhOrd& o, int lane, const f32x4 (&v)[EH_ORD_NSV]) {
+    f32x4 t;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float s = v[0][k];                           // xor 32 and xor 16: done by the group's last arriver
+        s += eh_dpp<0x128>(s);                       // row_ror:8 = xor 8
+        s += eh_dpp<0x124>(s);                       // row_ror:4 (= xor 4 modulo 8, and s repeats every 8 lanes by now)
+        s += eh_dpp<0x4E>(s);                        // quad_perm:[2,3,0,1] = xor 2
+        s += eh_dpp<0xB1>(s);                        // quad_perm:[1,0,3,2] = xor 1
+        const int si = __builtin_bit_cast(int, s);
+        const float w0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 0)), w1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 16)),
+                    w2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 32)), w3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 48));
+        t[k] = (w0 + w1) + (w2 + w3);
+    }
+    return t;                                        // {S, n, Sy, Syy}
+}
+__device__ __forceinline__ void eh_ord_scalar_loads(const EhOrd& o, int lane, f32x4 (&v)[EH_ORD_NSV]) {
+    const float* const P = o.grows + (long long)2 * EH_ORD_GROUPS * o.rs + (o.slot ^ 1) * EH_ORD_PART + 4 * lane;
+    v[0] = (lane & (EH_ORD_GROUPS - 1)) < o.prev_grid ? *(const f32x4*)P : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+#else
+enum { EH_ORD_NSV = 4 };
 #ifdef EH_AB_ORD_PARENT
 // (diagnostic A/B: the butterfly written as it reads, lane l holding rows l + 64 j -- 96 ds_bpermute in six dependent levels)
 __device__ __forceinline__ int eh_ord_scalar_row(int lane) { return lane; }
@@ -276,6 +311,7 @@ __device__ __forceinline__ void eh_ord_scalar_loads(const EhOrd& o, int lane, f3
         v[j] = r < o.prev_grid ? *(const f32x4*)(R + (long long)r * o.rs) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
 }
+#endif      // EH_AB_ORD_ROW_SCALARS
 // the pending step's gradient element idx: the 16 group rows in order from 0 (groups the step did not have: + 0)
 __device__ __forceinline__ void eh_ord_group_loads(const EhOrd& o, int idx, float (&g)[EH_ORD_GROUPS]) {
     const float* const G = o.grows + (long long)(o.slot ^ 1) * EH_ORD_GROUPS * o.rs + idx;
@@ -299,14 +335,22 @@ __device__ __forceinline__ f32x4 eh_ord_ld16(__amdgpu_buffer_rsrc_t r, int off) 
 __device__ __forceinline__ void eh_ord_st16(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_ord, v), r, off, 0, 16); }
 enum { EH_ORD_OOB = 0x7FFFFFF0 };       // (a byte offset past any row buffer: the load returns 0)
 // The consumer of a pending ordered step -- the next ordered step's prologue or eh_ord_flush_kernel -- writes EH_ORD_EMPTY back into the
-// gradient words of that step's rows (slot `slot ^ 1`, rows [0, prev_grid)): workgroup b takes rows b, b + nblk, ...; 16-byte stores over
-// [0, soff), the padding included, never the scalar block.  Nobody reads those words before the step two launches on writes them again,
-// and the kernel boundary in between publishes the marker.  (Done whether or not the pending step had a valid target.)
+// words of that step's rows (slot `slot ^ 1`, rows [0, prev_grid)): workgroup b takes rows b, b + nblk, ...; 16-byte stores over
+// [0, soff + 4): the gradient, its padding and the scalar vector, which the group's last arriver reads in-kernel like a gradient vector.
+// Nobody reads those words before the step two launches on writes them again, and the kernel boundary in between publishes the marker.
+// (Done whether or not the pending step had a valid target.)
+// (EH_AB_ORD_ROW_SCALARS: [0, soff) only, as before -- there every workgroup of this very kernel reads every row's scalars in its
+//  prologue, while another workgroup's reset of them may already have landed.  The tail of that build then meets the scalars of the step
+//  two launches back where it would meet the marker, and never waits for them; the partials it forms are read by nobody.)
 __device__ __forceinline__ void eh_ord_reset(const EhOrd& o, int b, int nblk, int tid, int nthr) {
     const __amdgpu_buffer_rsrc_t rr = eh_ord_rsrc(o.rows, 2 * EH_ORD_ROWS * o.rs);
     const float e = __uint_as_float(EH_ORD_EMPTY);
     const f32x4 ev = {e, e, e, e};
+#ifdef EH_AB_ORD_ROW_SCALARS
     const int nv = o.soff >> 2;
+#else
+    const int nv = (o.soff >> 2) + 1;
+#endif
     for (int r = b; r < o.prev_grid; r += nblk)
         for (int v = tid; v < nv; v += nthr) eh_ord_st16(rr, 4 * (((o.slot ^ 1) * EH_ORD_ROWS + r) * o.rs) + 16 * v, ev);
 }
@@ -317,8 +361,10 @@ __device__ __forceinline__ void eh_ord_reset(const EhOrd& o, int b, int nblk, in
 // joins; its own row it takes from LDS.  Every row store of the group has been issued by then, but some may still be on their way: a
 // gradient word that still holds EH_ORD_EMPTY is read again, its whole vector (a torn read included), until it holds the sum (a deadline
 // turns a store that never lands into the error word).  The padding words past n_theta take no part in the check.  No fence, no drain.
-// The fold is the one of eh_reduce_kernel's row groups, four elements per thread.  The group row goes to the next kernel on the stream,
-// whose start makes it visible; the rows stay as they are until that kernel's workgroups reset them (eh_ord_reset).
+// The fold is the one of eh_reduce_kernel's row groups, four elements per thread.  The rows' scalar vector is read the same way, under
+// the same marker with all four words checked: the last wave folds the group's rows into the four block partials of the reduce kernel's
+// butterfly (below) and stores them at part[slot][q][group].  Group row and partials go to the next kernel on the stream,
+// whose start makes them visible; the rows stay as they are until that kernel's workgroups reset them (eh_ord_reset).
 __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, const float* row, float* flag, unsigned long long* st) {
 #ifdef EH_STAMPS
     unsigned long long ts[10];
@@ -351,8 +397,56 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
     constexpr int NK = EH_ORD_ROWS / EH_ORD_GROUPS;
     const int kown = blockIdx.x / EH_ORD_GROUPS;
     const int rb = 4 * ((o.slot * EH_ORD_ROWS + (int)gi) * o.rs), rk = 4 * EH_ORD_GROUPS * o.rs;     // bytes: row k of the group at rb + k rk
-    const __amdgpu_buffer_rsrc_t gr = eh_ord_rsrc(o.grows, 2 * EH_ORD_GROUPS * o.rs);
+    const __amdgpu_buffer_rsrc_t gr = eh_ord_rsrc(o.grows, 2 * EH_ORD_GROUPS * o.rs + 2 * EH_ORD_PART);
     const int gb = 4 * ((o.slot * EH_ORD_GROUPS + (int)gi) * o.rs);
+    const int pb = 4 * (2 * EH_ORD_GROUPS * o.rs + o.slot * EH_ORD_PART + 4 * (int)gi), pq = 4 * 4 * EH_ORD_GROUPS;      // bytes: block q's partial of this group at pb + q pq
+    // The scalar vector, by the workgroup's last wave (on the headline it owns no gradient vector: nothing waits for this): lane k takes
+    // row k of the group -- the same sc1 load as a gradient vector's, its own row from LDS, 0 past the group's end -- as eh_reduce_kernel's
+    // thread holds it (0 + row).  The butterfly's first two levels over rows 64 q + gi + {0, 16, 32, 48} = rows 4 q ... 4 q + 3 of this
+    // group stay inside the quad 4 q ... 4 q + 3: xor 32 pairs c0 with c2 and c1 with c3 (quad_perm xor 2), xor 16 adds the pairs
+    // (quad_perm xor 1), so every lane of the quad holds (c0 + c2) + (c1 + c3) -- addition commutes -- and its first lane stores it at
+    // part[slot][q][gi].  eh_ord_scalar_fold goes on from there.  The vector is under the marker like a gradient vector, all four words of
+    // it (the gather writes all four): a NaN in a partial makes every lane look at its own row's words, a lane whose row has not arrived
+    // reads it again until it has (same sleep, deadline and error word as below), and the quads fold again.  A genuine NaN finds no
+    // marker and passes after that one look.  (As one more vector of the loop below, with the block sums in one thread's registers
+    // next to the 16 rows, the ordered kernels went from 110 to 156 VGPRs and from 4 waves per SIMD to 3.)
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == (nthr >> 6) - 1) {
+        const int k = tid & 63;
+        const int off = ((unsigned)k < gsz && k != kown) ? rb + k * rk + 4 * o.soff : (int)EH_ORD_OOB;
+        f32x4 q = eh_ord_ld16(rr, off);
+        if (k == kown) q = *(const f32x4*)&row[o.soff];
+        auto blocks = [&]() {
+            f32x4 c = f32x4{0.0f, 0.0f, 0.0f, 0.0f} + q;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float s = c[j];
+                s += eh_dpp<0x4E>(s);                    // quad_perm:[2,3,0,1]
+                s += eh_dpp<0xB1>(s);                    // quad_perm:[1,0,3,2]
+                c[j] = s;
+            }
+            return c;
+        };
+        f32x4 p = blocks();
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nan = nan || p[j] != p[j];
+        if (__builtin_amdgcn_ballot_w64(nan) != 0ull) {       // (wave-uniform: the quads fold again with every lane active)
+            auto empty_q = [&]() {
+                bool e = false;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) e = e || __float_as_uint(q[j]) == EH_ORD_EMPTY;
+                return e;
+            };
+            const unsigned long long t0 = wall_clock64();
+            while (empty_q()) {
+                if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+                __builtin_amdgcn_s_sleep(1);
+                q = eh_ord_ld16(rr, off);
+            }
+            p = blocks();
+        }
+        if (k < EH_ORD_GROUPS && (k & 3) == 0) eh_ord_st16(gr, pb + (k >> 2) * pq, p);
+    }
     for (int v = tid; v < nv; v += nthr) {
         f32x4 r[NK];
 #pragma unroll
@@ -1336,12 +1430,20 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     float f_sv = 0.0f;      // lane 8 k + sh of every wave: scalar k of shard sh
     float f_gs[EH_GSHARDS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // this thread's element in the eight shards
     float o_g[ORDM ? EH_ORD_GROUPS : 1];                  // EH_MODE_TRAIN_ORD: this thread's element in the 16 group rows ...
-    f32x4 o_sv[ORDM ? 4 : 1];                              // ... and (wave 0) the scalars of rows eh_ord_scalar_row(lane) + 16 j
+    f32x4 o_sv[ORDM ? EH_ORD_NSV : 1];                     // ... and (the wave that folds) lane 16 q + i's block partial of the scalars, part[q][i]
+    // Who folds the scalars: on a network that leaves the last wave without a parameter element (the headline: 338 of 512 threads) that
+    // wave -- it issues no state and no group-row loads, wave 0 has sixteen of them and the state -- else wave 0.  Wave-uniform; the result
+    // reaches the others through px_T behind the barrier in front of the update.
+#if defined(EH_AB_ORD_ROW_SCALARS) || defined(EH_AB_ORD_FOLD_WAVE0)
+    const int o_wave = 0;
+#else
+    const int o_wave = (ORDM && net.n_theta <= NTHR - 64) ? NTHR / 64 - 1 : 0;
+#endif
     if constexpr (ORDM) {
 #pragma unroll
         for (int k = 0; k < EH_ORD_GROUPS; ++k) o_g[k] = 0.0f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o_sv[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j = 0; j < EH_ORD_NSV; ++j) o_sv[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     if (deferred_upd) {
         const EhFused& z = a.fz;
@@ -1352,7 +1454,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         // loads are back (below, behind the image).  No branch on the target count: a uniform branch here split the prologue's single
         // memory round trip in two (+1.7 us per headline step on the kernels built ahead of time).  (Every thread used to load all forty
         // itself: 40 loads + their addresses in each of the workgroup's waves, ~0.6 us of a prologue that is bound by the instructions it issues.)
-        if constexpr (ORDM) { if (own_direct && wave == 0) eh_ord_scalar_loads(a.ord, lane, o_sv); }
+        if constexpr (ORDM) { if (own_direct && wave == o_wave) eh_ord_scalar_loads(a.ord, lane, o_sv); }
         else { if (own_direct && lane < 40) f_sv = g_prev[(lane & 7) * a.n_acc + net.n_theta + (lane >> 3)]; }
         const float* const sc_in = z.pset + 6 * net.n_theta + 2 * z.sc_sel;
         f_bt1 = sc_in[0]; f_bt2 = sc_in[1];
@@ -1427,14 +1529,14 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
     if (ORDM && own_direct) {
         if constexpr (ORDM) {
 #ifdef EH_STAMPS
-            if (a.stamps && blockIdx.x == 0 && tid == 0) { unsigned long long ts[4]; EH_ORD_TICK(ts, 0); a.stamps[EH_ORD_ST_PRO] = ts[0]; a.stamps[EH_ORD_ST_PRO + 1] = ts[1]; }
+            if (a.stamps && blockIdx.x == 0 && wave == o_wave && lane == 0) { unsigned long long ts[4]; EH_ORD_TICK(ts, 0); a.stamps[EH_ORD_ST_PRO] = ts[0]; a.stamps[EH_ORD_ST_PRO + 1] = ts[1]; }
 #endif
             f_g = eh_ord_group_fold(o_g);
-            if (wave == 0) {           // (read by every thread behind the workgroup barrier in front of the update below)
+            if (wave == o_wave) {      // (read by every thread behind the workgroup barrier in front of the update below)
                 const f32x4 t = eh_ord_scalar_fold(a.ord, lane, o_sv);
                 if (lane == 0) *(f32x4*)px_T = t;
 #ifdef EH_STAMPS
-                if (a.stamps && blockIdx.x == 0 && tid == 0) { unsigned long long ts[4]; EH_ORD_TICK(ts, 1); a.stamps[EH_ORD_ST_PRO + 2] = ts[2]; a.stamps[EH_ORD_ST_PRO + 3] = ts[3]; }
+                if (a.stamps && blockIdx.x == 0 && lane == 0) { unsigned long long ts[4]; EH_ORD_TICK(ts, 1); a.stamps[EH_ORD_ST_PRO + 2] = ts[2]; a.stamps[EH_ORD_ST_PRO + 3] = ts[3]; }
 #endif
             }
         }

@@ -158,7 +158,8 @@ struct eh_handle_s {
     bool fused = false, pending = false, fused_det = false;   // fused_det ("fused_update" 2): one kernel per step only where one workgroup covers the minibatch
     float* gacc = nullptr;          // [3][EH_GSHARDS][n_acc] rotating gradient accumulators
     // ordered fused-update step (EH_MODE_TRAIN_ORD: "fused_update" 2 on minibatches of several workgroups; EhOrd, eh_device.hpp)
-    unsigned* ord = nullptr;        // one allocation: the 16 group counters (2 KB), then rows [2][256][ord_rs], then group rows [2][16][ord_rs]
+    unsigned* ord = nullptr;        // one allocation: the 16 group counters (2 KB), then rows [2][256][ord_rs], then group rows [2][16][ord_rs],
+                                    // then the scalars' block partials [2 slots][4 blocks][16 groups][4 floats] (2 KB), addressed from the group rows
     unsigned* ord_err = nullptr;    // host memory: set by a group's last arriver whose rows did not arrive in time (EhOrd::err)
     int ord_rs = 0, ord_soff = 0;
     bool pend_ord = false;          // the pending update is an ordered step's (its sums in the row slots, not in gacc)

@@ -336,8 +336,8 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
     }
 }
 
-// ordered fused-update mode (EhOrd, eh_device.hpp): apply the still-pending step in place -- the 16 group rows in order, the rows'
-// scalars by the reduce kernel's butterfly (every wave folds them itself), then the update as eh_reduce_kernel<true, 16> makes it.
+// ordered fused-update mode (EhOrd, eh_device.hpp): apply the still-pending step in place -- the 16 group rows in order, the scalars'
+// block partials by the rest of the reduce kernel's butterfly (every wave folds them itself), then the update as eh_reduce_kernel<true, 16> makes it.
 // The grid is at least the pending step's: every workgroup resets the rows it takes (eh_ord_reset); those past ceil(n_theta / 256) only that.
 __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_theta, float* theta, float* m, float* v, const float* sc_in, float* sc_out,
                                                            EhOpt op, float* loss_slot, EhImg im, int loss_kind) {
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_
     const int idx = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
     const bool own = idx < n_theta;
     float gv[EH_ORD_GROUPS];
-    f32x4 sv[4];
+    f32x4 sv[EH_ORD_NSV];
     eh_ord_group_loads(o, own ? idx : 0, gv);
     eh_ord_scalar_loads(o, lane, sv);
     float th = 0.0f, mm = 0.0f, vv = 0.0f;

@@ -3,7 +3,12 @@ arriver (the stamps of workgroup 0 do not see it) and the ordered part of the pr
 The kernel is compiled at run time with the stamps in:
     EH_NO_AOT_SPEC=1 EH_JIT_CACHE=0 EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE" python tools/stamps_ord.py
     EH_NO_AOT_SPEC=1 EH_JIT_CACHE=0 EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_PARENT" python tools/stamps_ord.py   (the drain and
-        the shuffle butterfly put back)
+        the shuffle butterfly put back; implies EH_AB_ORD_ROW_SCALARS)
+    EH_NO_AOT_SPEC=1 EH_JIT_CACHE=0 EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_ROW_SCALARS" python tools/stamps_ord.py   (the
+        prologue reads the 256 rows' scalar vectors and folds all six butterfly levels, as before the tail formed the block partials)
+    EH_NO_AOT_SPEC=1 EH_JIT_CACHE=0 EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_FOLD_WAVE0" python tools/stamps_ord.py   (wave 0
+        folds the block partials, not the last wave)
+The scalar fold's slot is stamped by the wave that folds (its image staged -> its fold done).
 Every number is the median over the last `--reps` steps, each read back on its own (a synchronize per step: the steps run apart)."""
 import argparse
 import ctypes as C
@@ -65,7 +70,7 @@ for k, nm in enumerate(lab):
     print(f"    {nm:26s} {tc[k]:8.0f} cycles {tn[k]:8.0f} ns   {tm[k]:8.0f} ns")
 print(f"    {'sum':26s} {tc.sum():8.0f} cycles {tn.sum():8.0f} ns")
 print(f"  workgroup 0 start -> last group row stored  {med('end_ns'):8.0f} ns   (workgroup 0 start -> its end {med('wg0_ns'):.0f} ns)")
-print(f"  prologue, ordered scalar fold (wave 0)      {med('fold_cyc'):8.0f} cycles {med('fold_ns'):8.0f} ns")
+print(f"  prologue, ordered scalar fold (its wave)    {med('fold_cyc'):8.0f} cycles {med('fold_ns'):8.0f} ns")
 pc = np.diff(np.array([r["pro_cyc"] for r in rows]), axis=1)
 plab = ["state loads issued", "exchange words requested", "image staged + ordered fold", "(p2p wait)", "statistics + X images cleared",
         "update applied", "scalars, barrier"]
