@@ -18,7 +18,7 @@
 // elements with an 8-element skew on odd row octets (both the 8-byte row fragments of the forward and the transposed reads of
 // the backward are then conflict-free); staged images 144 / 48 / 16 (eight consecutive sample rows 8 dwords apart mod 64).
 // Same slab-row contract as eh_widebf_kernel's direct-store form (one network: a.rmap == nullptr), same parameter image, same
-// mechanistic stage (eh_mech_stage_lane); evaluation passes and MultiNN models stay on eh_widebf_kernel.
+// mechanistic stage (eh_mech_stage_lane, eh_wide.hpp); evaluation passes and MultiNN models stay on eh_widebf_kernel.
 #pragma once
 #include "eh_wide_bf16.hpp"
 

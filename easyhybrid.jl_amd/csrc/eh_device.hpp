@@ -988,6 +988,66 @@ __device__ __forceinline__ void eh_mech_extra(int mech, const float* par, const 
     }
 }
 
+// The model of ONE sample, forward and pullback, in whichever of its three forms the build runs: a registry model (value and
+// Jacobian rows together), a recorded closure interpreted (the value slots are the tape, in scratch memory), or the same closure
+// as generated code (EH_JIT_MECH).  Called by eh_mech_stage_lane (eh_wide.hpp) and eh_mech_vjp_kernel; the sites that keep a copy: DESIGN.md section 3.1.
+template <bool PROG> struct EhMechTape { float dydp[EH_MAX_PARAMS], Jx[2][3]; };
+#ifdef EH_JIT_MECH
+template <> struct EhMechTape<true> { EhJitTape jit; };
+#else
+template <> struct EhMechTape<true> { float pval[EH_PROG_SLOTS]; };
+#endif
+// par, frc -> output 0 in y0, outputs 1..2 in yx (0 where the model has none).  `extra`: the registry model has outputs beyond the first.
+template <bool PROG>
+__device__ __forceinline__ void eh_mech_fwd(int mech, int n_out, bool extra, const unsigned* __restrict__ prog, const float* par, const float* frc,
+                                            EhMechTape<PROG>& T, float& y0, float (&yx)[2]) {
+    yx[0] = 0.0f; yx[1] = 0.0f;
+    if constexpr (PROG) {
+#ifdef EH_JIT_MECH
+        eh_jit_fwd(par, frc, T.jit, y0, yx[0], yx[1]);
+#else
+        eh_prog_forward(prog, par, frc, T.pval);
+        y0 = T.pval[prog[2]];
+        if (n_out > 1) yx[0] = T.pval[prog[3]];
+        if (n_out > 2) yx[1] = T.pval[prog[4]];
+#endif
+    } else {
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) T.dydp[j] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { T.Jx[0][j] = 0.0f; T.Jx[1][j] = 0.0f; }
+        y0 = eh_mech_eval(mech, par, frc, T.dydp);
+        if (extra) eh_mech_extra(mech, par, frc, yx, T.Jx);
+    }
+}
+// d loss / d outputs (dy, dyx) -> dp[j] = d loss / d parameter j, unmasked.  `extra`: add the rows of outputs 1..2 (a kernel that
+// knows at build time that there are none leaves the term out; adding zeros is not the same thing, -0 + 0 = +0).
+template <bool PROG>
+__device__ __forceinline__ void eh_mech_rev(int n_out, bool extra, const unsigned* __restrict__ prog, const float* par, const float* frc,
+                                            const EhMechTape<PROG>& T, float dy, const float (&dyx)[2], float (&dp)[EH_MAX_PARAMS]) {
+    if constexpr (PROG) {
+#ifdef EH_JIT_MECH
+        eh_jit_rev(par, frc, T.jit, dy, dyx[0], dyx[1], dp);
+#else
+        float padj[EH_PROG_SLOTS];
+        const int nslot = EH_PROG_SLOT_INSTR + (int)prog[0];
+        for (int i = 0; i < nslot; ++i) padj[i] = 0.0f;
+        padj[prog[2]] += dy;
+        if (n_out > 1) padj[prog[3]] += dyx[0];
+        if (n_out > 2) padj[prog[4]] += dyx[1];
+        eh_prog_reverse(prog, T.pval, padj);
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) dp[j] = padj[j];
+#endif
+    } else {
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+            dp[j] = dy * T.dydp[j];
+            if (extra && j < 3) dp[j] += dyx[0] * T.Jx[0][j] + dyx[1] * T.Jx[1][j];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // cross-GPU exchange helpers (EhP2P).  Every wait has a deadline on the 100 MHz wall clock, so a
 // missing peer turns into an error flag, never into a kernel that does not finish; once a wait has
@@ -2025,6 +2085,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             // registers are consumed: measured 2 % faster at 16 tiles per wave (the wait is almost always
             // free at this point and the next prefetch then issues without a stall).
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // (this kernel's own copy of eh_mech_fwd / eh_mech_rev, on purpose: DESIGN.md section 3.1, "The model stage")
             float y0, yx[2] = {0.0f, 0.0f}, Jx[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
 #ifdef EH_JIT_MECH
             EhJitTape jtape;

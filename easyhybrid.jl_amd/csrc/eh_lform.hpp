@@ -5,7 +5,7 @@
 // (v_mfma_f32_32x32x2_f32) with its elementwise tail fused into the epilogue:
 //
 //   forward    H_l  [B x out]  = act(H_{l-1} [B x in] * W_l^T + b_l)         (last layer: O^T [K][B] = ... + b, no activation)
-//   mechanistic stage + masked loss + its pullback, one sample per lane (eh_mech_stage_lane, the code of the fused kernels)
+//   mechanistic stage + masked loss + its pullback, one sample per lane (eh_mech_stage_lane of eh_wide.hpp, the code of the fused kernels)
 //   backward   dW_l^T [in x out] = H_{l-1}^T * dZ_l      split over the samples into S partial slabs (-> eh_reduce_kernel + optimiser)
 //              db_l   [out]      = column sums of dZ_l   (same split)
 //              dZ_{l-1} [B x in] = (dZ_l * W_l) .* act'(H_{l-1})
@@ -24,7 +24,7 @@ enum { EH_LTAIL_MAXL = EH_MAX_HIDDEN + 1, EH_LTAIL_MAXW = 256, EH_LTAIL_THREADS 
        EH_LTAIL_FD = 8, EH_LTAIL_BU = 4 };      // weight fragments a thread keeps in flight: rows of its k slice (forward), passes over the k rows (delta)
 
 #ifdef EH_LFORM_KERNELS
-#include "eh_wide_bf16.hpp"      // EhMechAcc, eh_mech_stage_lane
+#include "eh_wide.hpp"           // EhMechAcc, eh_mech_stage_lane; eh_lds_barrier
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -122,14 +122,14 @@ __global__ __launch_bounds__(256) void eh_mech_vjp_kernel(const EhNet net, EhMec
             if (t < net.T) ld(a.y[t], yv[t]);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            float par[EH_MAX_PARAMS], sg[NP], dydp[EH_MAX_PARAMS], frc[EH_MAX_FORC];
+            float par[EH_MAX_PARAMS], sg[NP], frc[EH_MAX_FORC];
 #pragma unroll
-            for (int j = NP; j < EH_MAX_PARAMS; ++j) { par[j] = 0.0f; dydp[j] = 0.0f; }
+            for (int j = NP; j < EH_MAX_PARAMS; ++j) par[j] = 0.0f;
 #pragma unroll
             for (int f = NF; f < EH_MAX_FORC; ++f) frc[f] = 0.0f;
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
-                par[j] = cpar[j]; sg[j] = 0.0f; dydp[j] = 0.0f;
+                par[j] = cpar[j]; sg[j] = 0.0f;
                 if (row[j] >= 0) {
                     if (net.scale_nn) { const float s = eh_sigmoid(ov[j][e]); par[j] = fmaf(sc[j], s, lo[j]); sg[j] = sc[j] * s * (1.0f - s); }
                     else { par[j] = ov[j][e]; sg[j] = 1.0f; }
@@ -137,18 +137,10 @@ __global__ __launch_bounds__(256) void eh_mech_vjp_kernel(const EhNet net, EhMec
             }
 #pragma unroll
             for (int f = 0; f < NF; ++f) frc[f] = fv[f][e];
-            float yx[2] = {0.0f, 0.0f}, Jx[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
             constexpr bool PROG = MECH == EH_MECH_PROGRAM;
-            float pval[PROG ? EH_PROG_SLOTS : 1], y0;
-            if constexpr (PROG) {
-                eh_prog_forward(a.prog, par, frc, pval);
-                y0 = pval[a.prog[2]];
-                if (net.n_out > 1) yx[0] = pval[a.prog[3]];
-                if (net.n_out > 2) yx[1] = pval[a.prog[4]];
-            } else {
-                y0 = eh_mech_eval(MECH, par, frc, dydp);
-                if constexpr (NO > 1) eh_mech_extra(MECH, par, frc, yx, Jx);
-            }
+            EhMechTape<PROG> tape;
+            float y0, yx[2];
+            eh_mech_fwd<PROG>(MECH, net.n_out, NO > 1, a.prog, par, frc, tape, y0, yx);
             float dy = 0.0f, dyx[2] = {0.0f, 0.0f};
 #pragma unroll
             for (int t = 0; t < NTG; ++t)
@@ -162,21 +154,12 @@ __global__ __launch_bounds__(256) void eh_mech_vjp_kernel(const EhNet net, EhMec
                     else { S[t] = fmaf(r, r, S[t]); d = 2.0f * w[t] * r; }                              // mean r^2 (loss_fn.jl:61-63)
                     dy += oi == 0 ? d : 0.0f; dyx[0] += oi == 1 ? d : 0.0f; dyx[1] += oi == 2 ? d : 0.0f;
                 }
-            float padj[PROG ? EH_PROG_SLOTS : 1];
-            if constexpr (PROG) {                                // reverse sweep over the tape (what Zygote derives from the closure)
-                const int nslot = EH_PROG_SLOT_INSTR + (int)a.prog[0];
-                for (int q = 0; q < nslot; ++q) padj[q] = 0.0f;
-                padj[a.prog[2]] += dy;
-                if (net.n_out > 1) padj[a.prog[3]] += dyx[0];
-                if (net.n_out > 2) padj[a.prog[4]] += dyx[1];
-                eh_prog_reverse(a.prog, pval, padj);
-            }
+            float dp[EH_MAX_PARAMS];                             // (a closure: the reverse sweep over the tape, what Zygote derives from it)
+            eh_mech_rev<PROG>(net.n_out, NO > 1, a.prog, par, frc, tape, dy, dyx, dp);
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
-                float dp = PROG ? padj[PROG ? j : 0] : dy * dydp[j];
-                if (!PROG && NO > 1 && j < 3) dp += dyx[0] * Jx[0][j] + dyx[1] * Jx[1][j];
-                gp[j] += row[j] >= 0 ? 0.0f : dp;
-                dov[j][e] = dp * sg[j];
+                gp[j] += row[j] >= 0 ? 0.0f : dp[j];
+                dov[j][e] = dp[j] * sg[j];
             }
         }
 #pragma unroll

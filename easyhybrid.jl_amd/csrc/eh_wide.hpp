@@ -51,6 +51,135 @@ __device__ __forceinline__ void eh_store_upto4(float* p, const f32x4& v, int n) 
 // make every barrier wait for the next tile's records (global loads issued a tile ahead on purpose).
 __device__ __forceinline__ void eh_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// sums of one wave's mechanistic stage (train: gradient of the global parameters, loss terms; eval: metric sums)
+struct EhMechAcc {
+    float gacc[EH_MAX_PARAMS], lacc, syacc, syyacc, cacc[EH_MAX_TARG], est[EH_MAX_TARG][EH_EVAL_STATS];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) gacc[j] = 0.0f;
+        lacc = syacc = syyacc = 0.0f;
+#pragma unroll
+        for (int t = 0; t < EH_MAX_TARG; ++t) {
+            cacc[t] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < EH_EVAL_STATS; ++k) est[t][k] = 0.0f;
+        }
+    }
+};
+
+// Mechanistic model + masked loss + its pullback for ONE sample per lane (the caller's wave 0, lane = sample of the tile):
+// physical parameters in OS[row k][lane] with d parameter / d NN output in SG, forcings / targets in RS -> (train) d loss / d NN
+// output back into OS, sums into `acc`; (eval) predictions / parameters written out.  Stage 5 of eh_widebf_kernel,
+// of the sample-owned bf16 kernel (eh_bf16_sample.hpp) and of the layer-wise form (eh_lform.hpp); eh_wide_kernel below keeps the same
+// stage inline, on its own accumulators: as a call it measured 2.4 % slower ("The model stage").
+template <bool TRAIN, bool PROG, bool LPROG = false, class NET>
+__device__ __forceinline__ void eh_mech_stage_lane(const NET& net, const EhStepArgs& a, int lane, bool live, int n_loc, int SR, const float* RS,
+                                                   float* OS, const float* SG, const float* meta, EhMechAcc& A) {
+    auto pkind = [&](int j) { return (int)((net.par_kind >> (2 * j)) & 3u); };
+    auto pidx = [&](int j) { return (int)((net.par_idx >> (4 * j)) & 15u); };
+    float par[EH_MAX_PARAMS], sg[EH_MAX_PARAMS], frc[EH_MAX_FORC], yobs[EH_MAX_TARG];
+#pragma unroll
+    for (int f = 0; f < EH_MAX_FORC; ++f) {
+        const unsigned col = (net.forc_col >> (8 * f)) & 0xFFu;
+        frc[f] = col != 0xFFu ? RS[col * SR + lane] : 0.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < EH_MAX_TARG; ++t) yobs[t] = t < net.T ? RS[(EH_MAX_FORC + t) * SR + lane] : __builtin_nanf("");
+#pragma unroll
+    for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+        par[j] = meta[EH_IMG_PHI + j]; sg[j] = 1.0f;
+        if (j < net.n_par && pkind(j) == EH_PAR_NEURAL) {
+            par[j] = OS[pidx(j) * SR + lane];
+            sg[j] = SG[pidx(j) * SR + lane];
+        }
+    }
+    EhMechTape<PROG> tape;
+    float y0, yx[2];
+    eh_mech_fwd<PROG>(net.mech, net.n_out, net.n_out > 1, a.prog, par, frc, tape, y0, yx);
+    float dy = 0.0f, dyx[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int t = 0; t < EH_MAX_TARG; ++t) {
+        if (t < net.T) {
+            const int ot = (int)((net.targ_out >> (2 * t)) & 3u);
+            const float y = ot == 0 ? y0 : (ot == 1 ? yx[0] : yx[1]);
+            const bool valid = live && !__builtin_isnan(yobs[t]);
+            const float r = valid ? y - yobs[t] : 0.0f;
+            if constexpr (TRAIN) {
+                const float* const tt = a.inv_n + EH_TT * t;
+                const float w = a.inv_n ? tt[0] : 1.0f;
+                const float cy = valid ? yobs[t] - a.shift[t] : 0.0f;
+                float d;
+                if (eh_target_mae(net.loss_t, t)) { A.lacc += w * fabsf(r); d = r > 0.0f ? w : (r < 0.0f ? -w : 0.0f); }
+#ifdef EH_JIT_LOSS
+                else if (eh_target_prog(net.loss_t, t)) {
+                    float dl;
+                    const float lv = eh_jit_loss(t, y, valid ? yobs[t] : y, dl);
+                    A.lacc += valid ? w * lv : 0.0f;
+                    d = valid ? w * dl : 0.0f;
+                }
+#else
+                else if (LPROG && eh_target_prog(net.loss_t, t)) {
+                    // a recorded loss function where no kernel is compiled around it (the layer-wise form): its tape interpreted, forward
+                    // then the reverse sweep from d l / d l = 1 -- the arithmetic eh_jit_loss would have been generated from
+                    if constexpr (LPROG) {
+                        const unsigned* const lp = a.lprog + t * EH_LPROG_WORDS;
+                        float lpar[EH_MAX_PARAMS], lfrc[EH_MAX_FORC], lval[EH_PROG_SLOTS], ladj[EH_PROG_SLOTS];
+#pragma unroll
+                        for (int j = 0; j < EH_MAX_PARAMS; ++j) lpar[j] = 0.0f;
+#pragma unroll
+                        for (int f = 0; f < EH_MAX_FORC; ++f) lfrc[f] = 0.0f;
+                        lpar[0] = y; lpar[1] = valid ? yobs[t] : y;
+                        eh_prog_forward(lp, lpar, lfrc, lval);
+                        const int nslot = EH_PROG_SLOT_INSTR + (int)lp[0];
+                        for (int i = 0; i < nslot; ++i) ladj[i] = 0.0f;
+                        ladj[lp[2]] = 1.0f;
+                        eh_prog_reverse(lp, lval, ladj);
+                        A.lacc += valid ? w * lval[lp[2]] : 0.0f;
+                        d = valid ? w * ladj[0] : 0.0f;
+                    } else d = 0.0f;
+                }
+#endif
+                else if (eh_target_two_pass(net.loss_t, t, net.T)) {      // two-pass losses: d loss / d yhat = k0 + k1 (yhat - centre) + k2 (y - c), k from the batch moments (eh_moment_coef_kernel)
+                    d = valid ? fmaf(tt[6], cy, fmaf(tt[5], y - tt[1], tt[4])) : 0.0f;
+                }
+                else { A.lacc += w * r * r; d = 2.0f * w * r; }
+                dy += ot == 0 ? d : 0.0f; dyx[0] += ot == 1 ? d : 0.0f; dyx[1] += ot == 2 ? d : 0.0f;
+                A.cacc[t] += valid ? 1.0f : 0.0f;
+                A.syacc += cy; A.syyacc += cy * cy;
+            } else if (valid) {
+                const float cy = yobs[t] - a.shift[t], ch = y - (a.inv_n ? a.inv_n[EH_TT * t + 1] : a.shift[t]);      // (moment pass of the pearson / kge losses: yhat is centred on its own mean, found by a first pass)
+                A.est[t][0] += r * r; A.est[t][1] += cy; A.est[t][2] += cy * cy; A.est[t][3] += 1.0f;
+                A.est[t][4] += ch; A.est[t][5] += ch * ch; A.est[t][6] += ch * cy; A.est[t][7] += fabsf(r);
+            }
+        }
+    }
+    if constexpr (!TRAIN) {
+        if (live) {
+            if (a.yhat)
+                for (int t = 0; t < net.T; ++t) {
+                    const int o = (int)((net.targ_out >> (2 * t)) & 3u);
+                    a.yhat[(long long)t * a.yld + n_loc] = o == 0 ? y0 : (o == 1 ? yx[0] : yx[1]);
+                }
+            if (a.pout)
+                for (int j = 0; j < net.n_par; ++j) a.pout[(long long)j * a.yld + n_loc] = par[j];
+        }
+    } else {
+        float dpar[EH_MAX_PARAMS];
+        // (`extra` = true here although the forward passed n_out > 1: this stage has always added the rows of outputs 1..2, zeros for a
+        //  single-output model, and dp + 0 turns a -0 into +0 -- not to be "aligned" with the forward call)
+        eh_mech_rev<PROG>(net.n_out, true, a.prog, par, frc, tape, dy, dyx, dpar);
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+            if (j < net.n_par) {
+                const float dp = live ? dpar[j] : 0.0f;
+                const int kd = pkind(j);
+                if (kd == EH_PAR_NEURAL) OS[pidx(j) * SR + lane] = dp * sg[j];
+                else if (kd == EH_PAR_GLOBAL) A.gacc[j] += dp;
+            }
+        }
+    }
+}
+
 // (EH_SPEC_NS: a translation unit that bakes ONE model descriptor into its kernels ahead of time -- eh_spec.hip -- puts them in a
 //  namespace of its own: the same template arguments name a different kernel there than in the generic translation units)
 #ifdef EH_SPEC_NS
@@ -429,7 +558,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void eh_wide_kernel(const EhNet net_rt
                             d = valid ? w * dl : 0.0f;
                         }
 #endif
-                        else if (eh_target_two_pass(net.loss_t, t, net.T)) {      // two-pass losses (see eh_step_kernel)
+                        else if (eh_target_two_pass(net.loss_t, t, net.T)) {      // two-pass losses: as in eh_mech_stage_lane above
                             d = valid ? fmaf(tt[6], cy, fmaf(tt[5], y - tt[1], tt[4])) : 0.0f;
                         }
                         else { lacc += w * r * r; d = 2.0f * w * r; }
@@ -437,7 +566,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void eh_wide_kernel(const EhNet net_rt
                         cacc[t] += valid ? 1.0f : 0.0f;
                         syacc += cy; syyacc += cy * cy;
                     } else if (valid) {
-                        const float cy = yobs[t] - a.shift[t], ch = y - (a.inv_n ? a.inv_n[EH_TT * t + 1] : a.shift[t]);      // see eh_step_kernel
+                        const float cy = yobs[t] - a.shift[t], ch = y - (a.inv_n ? a.inv_n[EH_TT * t + 1] : a.shift[t]);      // (as in eh_mech_stage_lane above)
                         est[t][0] += r * r; est[t][1] += cy; est[t][2] += cy * cy; est[t][3] += 1.0f;
                         est[t][4] += ch; est[t][5] += ch * ch; est[t][6] += ch * cy; est[t][7] += fabsf(r);
                     }

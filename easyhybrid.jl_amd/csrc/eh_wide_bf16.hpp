@@ -90,163 +90,6 @@ struct EhBfGeom {
     static constexpr int TOTAL_FLOATS = MAP_FLOATS > STAGE_FLOATS ? MAP_FLOATS : STAGE_FLOATS;
 };
 
-// sums of one wave's mechanistic stage (train: gradient of the global parameters, loss terms; eval: metric sums)
-struct EhMechAcc {
-    float gacc[EH_MAX_PARAMS], lacc, syacc, syyacc, cacc[EH_MAX_TARG], est[EH_MAX_TARG][EH_EVAL_STATS];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int j = 0; j < EH_MAX_PARAMS; ++j) gacc[j] = 0.0f;
-        lacc = syacc = syyacc = 0.0f;
-#pragma unroll
-        for (int t = 0; t < EH_MAX_TARG; ++t) {
-            cacc[t] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < EH_EVAL_STATS; ++k) est[t][k] = 0.0f;
-        }
-    }
-};
-
-// Mechanistic model + masked loss + its pullback for ONE sample per lane (the caller's wave 0, lane = sample of the tile):
-// physical parameters in OS[row k][lane] with d parameter / d NN output in SG, forcings / targets in RS -> (train) d loss / d NN
-// output back into OS, sums into `acc`; (eval) predictions / parameters written out.  Same arithmetic as stage 5 of eh_wide_kernel.
-template <bool TRAIN, bool PROG, bool LPROG = false, class NET>
-__device__ __forceinline__ void eh_mech_stage_lane(const NET& net, const EhStepArgs& a, int lane, bool live, int n_loc, int SR, const float* RS,
-                                                   float* OS, const float* SG, const float* meta, EhMechAcc& A) {
-    auto pkind = [&](int j) { return (int)((net.par_kind >> (2 * j)) & 3u); };
-    auto pidx = [&](int j) { return (int)((net.par_idx >> (4 * j)) & 15u); };
-    float par[EH_MAX_PARAMS], sg[EH_MAX_PARAMS], dydp[EH_MAX_PARAMS], frc[EH_MAX_FORC], yobs[EH_MAX_TARG];
-#pragma unroll
-    for (int f = 0; f < EH_MAX_FORC; ++f) {
-        const unsigned col = (net.forc_col >> (8 * f)) & 0xFFu;
-        frc[f] = col != 0xFFu ? RS[col * SR + lane] : 0.0f;
-    }
-#pragma unroll
-    for (int t = 0; t < EH_MAX_TARG; ++t) yobs[t] = t < net.T ? RS[(EH_MAX_FORC + t) * SR + lane] : __builtin_nanf("");
-#pragma unroll
-    for (int j = 0; j < EH_MAX_PARAMS; ++j) {
-        par[j] = meta[EH_IMG_PHI + j]; sg[j] = 1.0f; dydp[j] = 0.0f;
-        if (j < net.n_par && pkind(j) == EH_PAR_NEURAL) {
-            par[j] = OS[pidx(j) * SR + lane];
-            sg[j] = SG[pidx(j) * SR + lane];
-        }
-    }
-    float y0, yx[2] = {0.0f, 0.0f}, Jx[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-#ifdef EH_JIT_MECH
-    EhJitTape jtape;
-    if constexpr (PROG) eh_jit_fwd(par, frc, jtape, y0, yx[0], yx[1]);
-    else {
-#else
-    float pval[PROG ? EH_PROG_SLOTS : 1];
-    if constexpr (PROG) {
-        eh_prog_forward(a.prog, par, frc, pval);
-        y0 = pval[a.prog[2]];
-        if (net.n_out > 1) yx[0] = pval[a.prog[3]];
-        if (net.n_out > 2) yx[1] = pval[a.prog[4]];
-    } else {
-#endif
-        y0 = eh_mech_eval(net.mech, par, frc, dydp);
-        if (net.n_out > 1) eh_mech_extra(net.mech, par, frc, yx, Jx);
-    }
-    float dy = 0.0f, dyx[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int t = 0; t < EH_MAX_TARG; ++t) {
-        if (t < net.T) {
-            const int ot = (int)((net.targ_out >> (2 * t)) & 3u);
-            const float y = ot == 0 ? y0 : (ot == 1 ? yx[0] : yx[1]);
-            const bool valid = live && !__builtin_isnan(yobs[t]);
-            const float r = valid ? y - yobs[t] : 0.0f;
-            if constexpr (TRAIN) {
-                const float* const tt = a.inv_n + EH_TT * t;
-                const float w = a.inv_n ? tt[0] : 1.0f;
-                const float cy = valid ? yobs[t] - a.shift[t] : 0.0f;
-                float d;
-                if (eh_target_mae(net.loss_t, t)) { A.lacc += w * fabsf(r); d = r > 0.0f ? w : (r < 0.0f ? -w : 0.0f); }
-#ifdef EH_JIT_LOSS
-                else if (eh_target_prog(net.loss_t, t)) {
-                    float dl;
-                    const float lv = eh_jit_loss(t, y, valid ? yobs[t] : y, dl);
-                    A.lacc += valid ? w * lv : 0.0f;
-                    d = valid ? w * dl : 0.0f;
-                }
-#else
-                else if (LPROG && eh_target_prog(net.loss_t, t)) {
-                    // a recorded loss function where no kernel is compiled around it (the layer-wise form): its tape interpreted, forward
-                    // then the reverse sweep from d l / d l = 1 -- the arithmetic eh_jit_loss would have been generated from
-                    if constexpr (LPROG) {
-                        const unsigned* const lp = a.lprog + t * EH_LPROG_WORDS;
-                        float lpar[EH_MAX_PARAMS], lfrc[EH_MAX_FORC], lval[EH_PROG_SLOTS], ladj[EH_PROG_SLOTS];
-#pragma unroll
-                        for (int j = 0; j < EH_MAX_PARAMS; ++j) lpar[j] = 0.0f;
-#pragma unroll
-                        for (int f = 0; f < EH_MAX_FORC; ++f) lfrc[f] = 0.0f;
-                        lpar[0] = y; lpar[1] = valid ? yobs[t] : y;
-                        eh_prog_forward(lp, lpar, lfrc, lval);
-                        const int nslot = EH_PROG_SLOT_INSTR + (int)lp[0];
-                        for (int i = 0; i < nslot; ++i) ladj[i] = 0.0f;
-                        ladj[lp[2]] = 1.0f;
-                        eh_prog_reverse(lp, lval, ladj);
-                        A.lacc += valid ? w * lval[lp[2]] : 0.0f;
-                        d = valid ? w * ladj[0] : 0.0f;
-                    } else d = 0.0f;
-                }
-#endif
-                else if (eh_target_two_pass(net.loss_t, t, net.T)) {      // two-pass losses (see eh_step_kernel)
-                    d = valid ? fmaf(tt[6], cy, fmaf(tt[5], y - tt[1], tt[4])) : 0.0f;
-                }
-                else { A.lacc += w * r * r; d = 2.0f * w * r; }
-                dy += ot == 0 ? d : 0.0f; dyx[0] += ot == 1 ? d : 0.0f; dyx[1] += ot == 2 ? d : 0.0f;
-                A.cacc[t] += valid ? 1.0f : 0.0f;
-                A.syacc += cy; A.syyacc += cy * cy;
-            } else if (valid) {
-                const float cy = yobs[t] - a.shift[t], ch = y - (a.inv_n ? a.inv_n[EH_TT * t + 1] : a.shift[t]);      // see eh_step_kernel
-                A.est[t][0] += r * r; A.est[t][1] += cy; A.est[t][2] += cy * cy; A.est[t][3] += 1.0f;
-                A.est[t][4] += ch; A.est[t][5] += ch * ch; A.est[t][6] += ch * cy; A.est[t][7] += fabsf(r);
-            }
-        }
-    }
-    if constexpr (!TRAIN) {
-        if (live) {
-            if (a.yhat)
-                for (int t = 0; t < net.T; ++t) {
-                    const int o = (int)((net.targ_out >> (2 * t)) & 3u);
-                    a.yhat[(long long)t * a.yld + n_loc] = o == 0 ? y0 : (o == 1 ? yx[0] : yx[1]);
-                }
-            if (a.pout)
-                for (int j = 0; j < net.n_par; ++j) a.pout[(long long)j * a.yld + n_loc] = par[j];
-        }
-    } else {
-#ifdef EH_JIT_MECH
-        float padj[EH_MAX_PARAMS];
-        if constexpr (PROG) eh_jit_rev(par, frc, jtape, dy, dyx[0], dyx[1], padj);
-#else
-        float padj[PROG ? EH_PROG_SLOTS : 1];
-        if constexpr (PROG) {
-            const int nslot = EH_PROG_SLOT_INSTR + (int)a.prog[0];
-            for (int i = 0; i < nslot; ++i) padj[i] = 0.0f;
-            padj[a.prog[2]] += dy;
-            if (net.n_out > 1) padj[a.prog[3]] += dyx[0];
-            if (net.n_out > 2) padj[a.prog[4]] += dyx[1];
-            eh_prog_reverse(a.prog, pval, padj);
-        }
-#endif
-#pragma unroll
-        for (int j = 0; j < EH_MAX_PARAMS; ++j) {
-            if (j < net.n_par) {
-                float dp;
-                if constexpr (PROG) dp = padj[j];
-                else {
-                    dp = dy * dydp[j];
-                    if (j < 3) dp += dyx[0] * Jx[0][j] + dyx[1] * Jx[1][j];
-                }
-                dp = live ? dp : 0.0f;
-                const int kd = pkind(j);
-                if (kd == EH_PAR_NEURAL) OS[pidx(j) * SR + lane] = dp * sg[j];
-                else if (kd == EH_PAR_GLOBAL) A.gacc[j] += dp;
-            }
-        }
-    }
-}
-
 // (EH_SPEC_NS: a translation unit that bakes ONE model descriptor into its kernels ahead of time -- eh_spec.hip -- puts them in a
 //  namespace of its own: the same template arguments name a different kernel there than in the generic translation units)
 #ifdef EH_SPEC_NS
