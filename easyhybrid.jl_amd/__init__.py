@@ -6,7 +6,7 @@ the root-level shim module `easyhybrid_jl_amd` (import easyhybrid_jl_amd as eh).
 """
 from . import _lib
 from .engine import EngineError, HybridEngine, PerTarget
-from .models import (BatchNorm, Chain, Dense, Dropout, LSTMCell, GRUCell, RNNCell, Recurrence, Expo2Pool, Expo_resp_model, FluxPartModelQ10, HybridModel, LinearHM, MECH_REGISTRY, MultiNNHybridModel, ParameterContainer, RbQ10,
+from .models import (BatchNorm, LayerNorm, Chain, Dense, Dropout, LSTMCell, GRUCell, RNNCell, Recurrence, Expo2Pool, Expo_resp_model, FluxPartModelQ10, HybridModel, LinearHM, MECH_REGISTRY, MultiNNHybridModel, ParameterContainer, RbQ10,
                      Rs_components, Rs_components3F, SingleNNHybridModel, build_parameters, constructHybridModel, hard_sigmoid,
                      inv_hard_sigmoid, inv_sigmoid, scale_single_param, scale_single_param_minmax, sigmoid)
 from .train import (Adam, AdamW, ClipGrad, ClipNorm, DataConfig, Descent, EpochSnapshot, LBFGS, OptimiserChain, RMSProp, TrainConfig, TrainResults, WeightDecay, WeightL2,

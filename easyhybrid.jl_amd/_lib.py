@@ -28,6 +28,8 @@ EH_LAYER_GRU = 24         # ... Recurrence(GRUCell)
 EH_LAYER_RNN = 32         # ... Recurrence(RNNCell(.., act)): EH_LAYER_RNN + ACTIVATIONS[act]
 EH_LAYER_BATCHNORM = 40   # ... BatchNorm(n, act) behind the layer in front of it: EH_LAYER_BATCHNORM + ACTIVATIONS[act]
 EH_LAYER_BN_NOAFFINE = 8  # ... added to it: affine = false (no scale / bias in theta)
+EH_LAYER_LAYERNORM = 56   # ... LayerNorm(n, act) behind the layer in front of it: EH_LAYER_LAYERNORM + ACTIVATIONS[act]
+EH_LAYER_LN_NOAFFINE = 8  # ... added to it: affine = false
 EH_MAX_SEQ_WINDOW = 64
 OPT_RULES = {"Adam": 0, "AdamW": 1, "RMSProp": 2, "Descent": 3}
 TRAINING_LOSSES = {"mse": 0, "rmse": 1, "mae": 2, "nseLoss": 3, "pearsonLoss": 4, "kgeLoss": 5, "pbkgeLoss": 6}

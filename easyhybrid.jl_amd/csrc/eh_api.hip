@@ -614,6 +614,28 @@ static int bnl_desc_check(const eh_model_desc* d) {
     }
     return 1;
 }
+// LayerNorm layers inside the chain (EH_LAYER_LAYERNORM [+ EH_LAYER_LN_NOAFFINE] + activation): the same three answers
+static bool lnl_layer_code(int a) {
+    const int b = a - EH_LAYER_LAYERNORM;
+    return (b >= 0 && b <= EH_ACT_IDENTITY) || (b >= EH_LAYER_LN_NOAFFINE && b <= EH_LAYER_LN_NOAFFINE + EH_ACT_IDENTITY);
+}
+static int lnl_desc_check(const eh_model_desc* d) {
+    if (d->activation != EH_ACT_PER_NET) return 0;
+    const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
+    int n_ln = 0;
+    bool cell = false;
+    for (int l = 0; l < na; ++l) { n_ln += lnl_layer_code(d->net_activation[l]) ? 1 : 0; cell = cell || seq_layer_code(d->net_activation[l]); }
+    if (!n_ln) return 0;
+    if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for LayerNorm layers in a MultiNN model (EH_LAYER_LAYERNORM with n_nets = %d)", d->n_nets);
+    if (cell) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a chain that holds both a LayerNorm layer and a recurrent layer");
+    for (int l = 0; l < na; ++l) {
+        if (!lnl_layer_code(d->net_activation[l])) continue;
+        if (l == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_LAYERNORM at hidden layer 0: a LayerNorm layer normalises the layer in front of it (hidden layer 0 is a Dense layer)");
+        if (d->hidden[l] != d->hidden[l - 1]) return fail(nullptr, EH_EINVAL, "eh_create: LayerNorm layer %d has width %d, the layer in front of it %d", l, d->hidden[l], d->hidden[l - 1]);
+        if (d->hidden[l] > EH_MAX_LAYERNORM_WIDTH) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a LayerNorm layer of width %d (built: up to %d, a row in one wave's registers)", d->hidden[l], EH_MAX_LAYERNORM_WIDTH);
+    }
+    return 1;
+}
 
 int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     if (!d || !out) return fail(nullptr, EH_EINVAL, "eh_create: null argument");
@@ -625,7 +647,12 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     const int bnk = desc_layers ? bnl_desc_check(d) : 0;
     if (bnk < 0) return bnk;
     const bool bnl = bnk == 1;
-    const int seqk = (desc_layers && !bnl) ? seq_desc_check(d) : 0;
+    const int lnk = desc_layers ? lnl_desc_check(d) : 0;
+    if (lnk < 0) return lnk;
+    const bool lnl = lnk == 1;
+    // (a normalisation layer of either kind: an entry of the chain that is no Dense layer)
+    auto norm_layer_code = [&](int a) { return (bnl && bnl_layer_code(a)) || (lnl && lnl_layer_code(a)); };
+    const int seqk = (desc_layers && !bnl && !lnl) ? seq_desc_check(d) : 0;
     if (seqk < 0) return seqk;
     const bool seq = seqk == 1;
     if (d->mech == EH_MECH_PROGRAM) {
@@ -667,7 +694,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         bool same = true;
         for (int k = 0; k < na; ++k) {
             if (seq && seq_layer_code(d->net_activation[k])) { same = false; continue; }
-            if (bnl && bnl_layer_code(d->net_activation[k])) { same = false; continue; }
+            if (norm_layer_code(d->net_activation[k])) { same = false; continue; }
             if (d->net_activation[k] < 0 || d->net_activation[k] > EH_ACT_IDENTITY)
                 return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown activation id %d for %s %d", d->net_activation[k], d->n_nets > 0 ? "net" : "hidden layer", k);
             same = same && d->net_activation[k] == d->net_activation[0];
@@ -755,7 +782,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     bool lform = false;
     // (EH_FORCE_LFORM: A/B switch of the measurement tools -- every feed-forward model layer by layer, the baseline tools/bench_bn_chain.py compares with)
     static const bool force_lform = getenv("EH_FORCE_LFORM") != nullptr;
-    if (bnl || (force_lform && !seq)) arch = nullptr;      // (a BatchNorm layer couples the samples of a minibatch: always layer by layer, eh_bnl.hpp)
+    if (bnl || lnl || (force_lform && !seq)) arch = nullptr;      // (a BatchNorm layer couples the samples of a minibatch: always layer by layer, eh_bnl.hpp; a LayerNorm layer runs as a pass of its own too, eh_lnl.hpp)
     if (no_nn) { arch = &g_lform_arch; lform = true; }
     else if (seq) arch = &g_lform_arch;      // (its own kernel family, eh_seq.hpp; of the "architecture" only the PHI block of the image is used)
     else if (!arch) {
@@ -813,6 +840,11 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
                 if (d->net_activation[l] - EH_LAYER_BATCHNORM < EH_LAYER_BN_NOAFFINE) off += 2 * o;
                 continue;
             }
+            if (lnl && l < nl && lnl_layer_code(d->net_activation[l])) {      // a LayerNorm layer: bias and scale, or nothing
+                if (k == 0) lb_off[l] = off;
+                if (d->net_activation[l] - EH_LAYER_LAYERNORM < EH_LAYER_LN_NOAFFINE) off += 2 * o;
+                continue;
+            }
             if (l < nl && l >= net_d[k]) { if (k == 0) lb_off[l] = off; continue; }       // identity block: nothing of it in theta
             off += o * in;
             if (k == 0) lb_off[l] = off;
@@ -855,6 +887,15 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
                     if (affine) o2 += 2 * in;
                     h->bnl = true; h->bnl_off[l] = h->bnl_maxn; h->bnl_maxn += 2 * in;      // (bnl_maxn: the running total here, the widest layer below)
                     h->bnl_mom[l] = EH_BN_MOMENTUM; h->bnl_eps[l] = EH_BN_EPS;
+                    continue;
+                }
+                if (lnl && l + 1 < L.nl && lnl_layer_code(d->net_activation[l])) {      // (Lux orders a LayerNorm's leaves bias, scale)
+                    const int b = d->net_activation[l] - EH_LAYER_LAYERNORM;
+                    const bool affine = b < EH_LAYER_LN_NOAFFINE;
+                    L.lbn[l] = affine ? 3 : 4; L.lact[l] = affine ? b : b - EH_LAYER_LN_NOAFFINE;
+                    L.in[l] = in; L.out[l] = in; L.boff[l] = o2; L.woff[l] = affine ? o2 + in : o2;
+                    if (affine) o2 += 2 * in;
+                    h->lnl = true; h->bnl_eps[l] = EH_BN_EPS;
                     continue;
                 }
                 L.in[l] = in; L.out[l] = o; L.woff[l] = o2; L.boff[l] = o2 + o * in;
@@ -947,18 +988,20 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
         for (int p = 0; p < 32; ++p) { run0[p] = 0.0f; run0[32 + p] = 1.0f; }     // LuxCore.initialstates(BatchNorm)
         HIPCHK_C(hipMemcpy(h->bn_run, run0, sizeof run0, hipMemcpyHostToDevice));
     }
-    if (h->bnl) {             // BatchNorm layers: running statistics (LuxCore.initialstates: mean 0, var 1), the step's own, the partial column sums
-        const int tot = h->bnl_maxn;
+    if (h->bnl || h->lnl) {   // BatchNorm layers: running statistics (LuxCore.initialstates: mean 0, var 1), the step's own; both kinds: the partial column sums
+        const int tot = h->bnl_maxn;          // (of the BatchNorm layers alone: a LayerNorm layer has no state)
         int widest = 0;
         for (int l = 0; l < h->l_net[0].nl; ++l) if (h->l_net[0].lbn[l]) widest = std::max(widest, h->l_net[0].out[l]);
         h->bnl_maxn = widest;
-        std::vector<float> run0((size_t)tot, 0.0f);
-        for (int l = 0; l < h->l_net[0].nl; ++l)
-            if (h->l_net[0].lbn[l]) std::fill(run0.begin() + h->bnl_off[l] + h->l_net[0].out[l], run0.begin() + h->bnl_off[l] + 2 * h->l_net[0].out[l], 1.0f);
-        HIPCHK_C(hipMalloc(&h->bnl_run, (size_t)tot * sizeof(float)));
-        HIPCHK_C(hipMemcpy(h->bnl_run, run0.data(), (size_t)tot * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK_C(hipMalloc(&h->bnl_stat, (size_t)2 * tot * sizeof(float)));
-        HIPCHK_C(hipMemset(h->bnl_stat, 0, (size_t)2 * tot * sizeof(float)));
+        if (h->bnl) {
+            std::vector<float> run0((size_t)tot, 0.0f);
+            for (int l = 0; l < h->l_net[0].nl; ++l)
+                if (h->l_net[0].lbn[l] == 1 || h->l_net[0].lbn[l] == 2) std::fill(run0.begin() + h->bnl_off[l] + h->l_net[0].out[l], run0.begin() + h->bnl_off[l] + 2 * h->l_net[0].out[l], 1.0f);
+            HIPCHK_C(hipMalloc(&h->bnl_run, (size_t)tot * sizeof(float)));
+            HIPCHK_C(hipMemcpy(h->bnl_run, run0.data(), (size_t)tot * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK_C(hipMalloc(&h->bnl_stat, (size_t)2 * tot * sizeof(float)));
+            HIPCHK_C(hipMemset(h->bnl_stat, 0, (size_t)2 * tot * sizeof(float)));
+        }
         HIPCHK_C(hipMalloc(&h->bnl_part, (size_t)(EH_BNL_CHUNKS + 1) * 2 * widest * sizeof(float)));
     }
     if (!lform && !seq) {     // (the fused-update accumulators: that mode exists for the per-wave kernels only)
@@ -1269,6 +1312,16 @@ static int32_t set_option(eh_handle* h, const char* name, int64_t value) {
         }
         if (!strcmp(name, "multi_step") || !strcmp(name, "specialize") || !strcmp(name, "precision")) {
             if (value) return fail(h, EH_EUNSUPPORTED, "%s: not built for BatchNorm layers in the chain (fp32 layer-wise form, one step per launch sequence)", name);
+            return EH_OK;
+        }
+    } else if (h->lnl) {                     // LayerNorm layers (and no BatchNorm layer): the same pair, the same refusals
+        if (!strcmp(name, "fused_update")) {
+            if (value < 0 || value > 2) return fail(h, EH_EINVAL, "fused_update must be 0, 1 or 2");
+            if (value == 1) return fail(h, EH_EUNSUPPORTED, "fused_update: the one-kernel step is not built for LayerNorm layers in the chain (they run the layer-wise step + reduce pair)");
+            return EH_OK;
+        }
+        if (!strcmp(name, "multi_step") || !strcmp(name, "specialize") || !strcmp(name, "precision")) {
+            if (value) return fail(h, EH_EUNSUPPORTED, "%s: not built for LayerNorm layers in the chain (fp32 layer-wise form, one step per launch sequence)", name);
             return EH_OK;
         }
     }
@@ -2190,7 +2243,7 @@ int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* ru
 
 // running statistics of a BatchNorm layer inside the chain (eh_bnl.hpp)
 static int layer_state_check(eh_handle* h, const char* who, int32_t layer, int64_t n) {
-    if (!h->bnl || layer < 0 || layer >= h->l_net[0].nl || !h->l_net[0].lbn[layer]) return fail(h, EH_ESTATE, "%s: hidden layer %d is no BatchNorm layer", who, layer);
+    if (!h->bnl || layer < 0 || layer >= h->l_net[0].nl || (h->l_net[0].lbn[layer] != 1 && h->l_net[0].lbn[layer] != 2)) return fail(h, EH_ESTATE, "%s: hidden layer %d is no BatchNorm layer", who, layer);
     if (n != h->l_net[0].out[layer]) return fail(h, EH_EINVAL, "%s: n = %lld, the layer has %d units", who, (long long)n, h->l_net[0].out[layer]);
     return EH_OK;
 }
@@ -2216,7 +2269,8 @@ int32_t eh_set_layer_state(eh_handle* h, int32_t layer, const float* running_mea
 }
 int32_t eh_set_layer_norm(eh_handle* h, int32_t layer, float momentum, float epsilon) {
     if (!h) return EH_EINVAL;
-    if (int rc = layer_state_check(h, "eh_set_layer_norm", layer, h->bnl && layer >= 0 && layer < h->l_net[0].nl ? h->l_net[0].out[layer] : 0)) return rc;
+    const bool ln = h->lnl && layer >= 0 && layer < h->l_net[0].nl && h->l_net[0].lbn[layer] >= 3;      // (a LayerNorm layer: its epsilon; it has no momentum to set)
+    if (!ln) { if (int rc = layer_state_check(h, "eh_set_layer_norm", layer, h->bnl && layer >= 0 && layer < h->l_net[0].nl ? h->l_net[0].out[layer] : 0)) return rc; }
     if (!(momentum >= 0.0f && momentum <= 1.0f) || !(epsilon > 0.0f)) return fail(h, EH_EINVAL, "eh_set_layer_norm: momentum %g (0..1), epsilon %g (> 0)", (double)momentum, (double)epsilon);
     h->bnl_mom[layer] = momentum; h->bnl_eps[layer] = epsilon;      // (kernel arguments of the steps launched from now on)
     return EH_OK;

@@ -202,7 +202,8 @@ struct eh_handle_s {
     // layer-wise execution form (eh_lform.hpp): networks no fused kernel holds
     bool lform = false;
     // one entry per network (SingleNN: one; MultiNN: one single-output network per neural parameter, each on its own predictor rows)
-    // (lbn[l] != 0: entry l is a BatchNorm layer, EH_LAYER_BATCHNORM -- 1 affine, 2 not; in = out = its width, woff / boff = its scale / bias, lact its activation)
+    // (lbn[l] != 0: entry l is a BatchNorm layer, EH_LAYER_BATCHNORM -- 1 affine, 2 not --, or a LayerNorm layer, EH_LAYER_LAYERNORM -- 3 affine, 4 not;
+    //  in = out = its width, woff / boff = its scale / bias -- a LayerNorm's bias comes first in theta --, lact its activation)
     struct LNet { int nl = 0, c0 = 0, orow = 0, act = 0; int lact[EH_MAX_HIDDEN + 1] = {0}; int in[EH_MAX_HIDDEN + 1] = {0}, out[EH_MAX_HIDDEN + 1] = {0}, woff[EH_MAX_HIDDEN + 1] = {0}, boff[EH_MAX_HIDDEN + 1] = {0}; int lbn[EH_MAX_HIDDEN + 1] = {0}; };
     int l_nnets = 0;                                     // 0: no network at all (no neural parameter)
     LNet l_net[EH_MAX_NETS];
@@ -215,7 +216,9 @@ struct eh_handle_s {
     // BatchNorm layers inside the chain (eh_bnl.hpp; one network, always this form, its few-rows fusions off): per layer l of l_net[0]
     // with lbn[l] != 0, at bnl_off[l] floats into bnl_run: [running mean | running var]; at twice that into bnl_stat: [first row | mean about it | rstd]
     // of the step, n each
-    bool bnl = false;
+    // LayerNorm layers (eh_lnl.hpp) set `lnl` instead: the same form with the same fusions off, no state; they share bnl_eps and -- for the
+    // column sums of their leaves' gradients -- bnl_part / bnl_maxn, nothing else of this block
+    bool bnl = false, lnl = false;
     int bnl_off[EH_MAX_HIDDEN + 1] = {0};
     float bnl_mom[EH_MAX_HIDDEN + 1] = {0}, bnl_eps[EH_MAX_HIDDEN + 1] = {0};      // eh_set_layer_norm (defaults: EH_BN_MOMENTUM, EH_BN_EPS)
     float *bnl_run = nullptr, *bnl_stat = nullptr;

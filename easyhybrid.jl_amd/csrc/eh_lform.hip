@@ -9,13 +9,15 @@
 #define EH_LFORM_KERNELS
 #include "eh_lform.hpp"
 #include "eh_bnl.hpp"
+#include "eh_lnl.hpp"
 
-struct EhLWs { float *Xb, *H[EH_MAX_NETS][EH_MAX_HIDDEN], *Z[EH_MAX_NETS][EH_MAX_HIDDEN], *D[2], *O, *part; long long ldo; };
+struct EhLWs { float *Xb, *H[EH_MAX_NETS][EH_MAX_HIDDEN], *Z[EH_MAX_NETS][EH_MAX_HIDDEN], *R[EH_MAX_HIDDEN], *D[2], *O, *part; long long ldo; };      // (R[l]: a LayerNorm layer's rstd, one per sample)
 static long long lform_floats_per_sample(const eh_handle* h) {
     long long w = h->net.P + 16, maxw = 0;
     for (int k = 0; k < h->l_nnets; ++k)
         for (int l = 0; l + 1 < h->l_net[k].nl; ++l) {
-            w += h->l_net[k].out[l] * ((h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) ? 2 : 1);      // swish keeps the pre-activation too, a BatchNorm layer its normalised input
+            w += h->l_net[k].out[l] * ((h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) ? 2 : 1);      // swish keeps the pre-activation too, a BatchNorm / LayerNorm layer its normalised input
+            w += h->l_net[k].lbn[l] >= 3 ? 1 : 0;      // ... a LayerNorm layer its rows' rstd
             maxw = std::max<long long>(maxw, h->l_net[k].out[l]);
         }
     return w + 2 * maxw;
@@ -51,6 +53,7 @@ static int lform_workspace(eh_handle* h, long long count, EhLWs* W) {
             W->H[k][l] = p; p += cap * o;
             W->Z[k][l] = nullptr;
             if (h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) { W->Z[k][l] = p; p += cap * o; }
+            if (k == 0) { W->R[l] = nullptr; if (h->l_net[k].lbn[l] >= 3) { W->R[l] = p; p += cap; } }      // (cap is a multiple of 128: what follows stays 16-byte aligned)
         }
     W->D[0] = p; p += cap * maxw;
     W->D[1] = p; p += cap * maxw;
@@ -208,6 +211,72 @@ static int bnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float
     HIPCHK(h, hipGetLastError());
     return EH_OK;
 }
+// LayerNorm layer l of the one network (eh_lnl.hpp): H_l = act(scale xh + bias), every row normalised over its own features; `keep`: xh into Z_l
+// and rstd into R_l for the backward (training), otherwise the same pass with nothing kept
+static void lnl_geometry(int n, int B, int* seg, int* per, unsigned* grid) {
+    int s = 1;
+    while (s < n && s < 64) s *= 2;
+    int p = 1;
+    while ((long long)s * p < n) p *= 2;      // (n <= EH_MAX_LAYERNORM_WIDTH, eh_create: p <= 16)
+    *seg = s; *per = p;
+    const long long rows_wg = 4ll * (64 / s);
+    *grid = (unsigned)((B + rows_wg - 1) / rows_wg);
+}
+static int lnl_forward_layer(eh_handle* h, int l, int B, bool keep, const EhLWs& W) {
+    const eh_handle_s::LNet& L = h->l_net[0];
+    const float* theta = TH(h);
+    EhLnlFwdArgs a{};
+    a.X = W.H[0][l - 1]; a.Y = W.H[0][l]; a.Xh = keep ? W.Z[0][l] : nullptr; a.rstd = keep ? W.R[l] : nullptr;
+    a.scale = L.lbn[l] == 3 ? theta + L.woff[l] : nullptr; a.bias = L.lbn[l] == 3 ? theta + L.boff[l] : nullptr;
+    a.B = B; a.n = L.out[l]; a.act = L.lact[l]; a.eps = h->bnl_eps[l];
+    int per; unsigned grid;
+    lnl_geometry(a.n, B, &a.seg, &per, &grid);
+    switch (per) {
+        case 1: hipLaunchKernelGGL((eh_lnl_fwd_kernel<1>), dim3(grid), dim3(256), 0, h->stream, a); break;
+        case 2: hipLaunchKernelGGL((eh_lnl_fwd_kernel<2>), dim3(grid), dim3(256), 0, h->stream, a); break;
+        case 4: hipLaunchKernelGGL((eh_lnl_fwd_kernel<4>), dim3(grid), dim3(256), 0, h->stream, a); break;
+        case 8: hipLaunchKernelGGL((eh_lnl_fwd_kernel<8>), dim3(grid), dim3(256), 0, h->stream, a); break;
+        case 16: hipLaunchKernelGGL((eh_lnl_fwd_kernel<16>), dim3(grid), dim3(256), 0, h->stream, a); break;
+        default: return fail(h, EH_EUNSUPPORTED, "layer-wise form: no kernel for a LayerNorm layer of width %d", a.n);
+    }
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+// ... its backward: dY [B x n] -> dZ of the layer below into dX (one launch); affine: d scale / d bias as column sums over the rows, by the
+// BatchNorm layers' two kernels, into the slab (row 0; zeros in the other rows)
+static int lnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float* dX, int rows, const EhLWs& W) {
+    const eh_handle_s::LNet& L = h->l_net[0];
+    const int n = L.out[l];
+    const float* theta = TH(h);
+    const bool affine = L.lbn[l] == 3;
+    EhLnlBwdArgs d{};
+    d.dY = dY; d.Xh = W.Z[0][l]; d.Y = W.H[0][l]; d.rstd = W.R[l];
+    d.scale = affine ? theta + L.woff[l] : nullptr; d.bias = affine ? theta + L.boff[l] : nullptr;
+    d.act_below = L.lbn[l - 1] ? (int)EH_ACT_IDENTITY : L.lact[l - 1];
+    d.Hb = (d.act_below == EH_ACT_SWISH) ? W.Z[0][l - 1] : W.H[0][l - 1];
+    d.dX = dX; d.B = B; d.n = n; d.act = L.lact[l];
+    int per; unsigned grid;
+    lnl_geometry(n, B, &d.seg, &per, &grid);
+    switch (per) {
+        case 1: hipLaunchKernelGGL((eh_lnl_bwd_kernel<1>), dim3(grid), dim3(256), 0, h->stream, d); break;
+        case 2: hipLaunchKernelGGL((eh_lnl_bwd_kernel<2>), dim3(grid), dim3(256), 0, h->stream, d); break;
+        case 4: hipLaunchKernelGGL((eh_lnl_bwd_kernel<4>), dim3(grid), dim3(256), 0, h->stream, d); break;
+        case 8: hipLaunchKernelGGL((eh_lnl_bwd_kernel<8>), dim3(grid), dim3(256), 0, h->stream, d); break;
+        case 16: hipLaunchKernelGGL((eh_lnl_bwd_kernel<16>), dim3(grid), dim3(256), 0, h->stream, d); break;
+        default: return fail(h, EH_EUNSUPPORTED, "layer-wise form: no kernel for a LayerNorm layer of width %d", n);
+    }
+    if (affine) {
+        EhBnlArgs a{};
+        a.X = dY; a.Xh = d.Xh; a.Y = d.Y; a.gamma = d.scale; a.beta = d.bias; a.part = h->bnl_part; a.B = B; a.n = n; a.act = L.lact[l];
+        const int nchunk = bnl_chunks(B, &a.chunk);
+        float* sums = h->bnl_part + (size_t)EH_BNL_CHUNKS * 2 * h->bnl_maxn;      // (the totals: nothing reads them here, the leaves' gradients are all of them)
+        hipLaunchKernelGGL((eh_bnl_colsum_kernel<true>), dim3((unsigned)((n + 63) / 64), (unsigned)nchunk), dim3(256), 0, h->stream, a);
+        hipLaunchKernelGGL(eh_bnl_fold_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->bnl_part, nchunk, n, sums,
+                           h->slab + L.woff[l], h->slab + L.boff[l], rows, (long long)h->n_acc);
+    }
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
 // minibatch -> Xb (input BatchNorm applied), forward through every Dense layer; O^T [K][ldo] = the raw NN outputs
 // (lstop >= 0: a one-network model, only its layers below `lstop` run here -- the rest belongs to eh_lform_tailchain_kernel)
 static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool train_mode, bool bn_update, const EhLWs& W, int lstop = -1) {
@@ -217,7 +286,7 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
     EhStepArgs bn{};
     // (small minibatches: the prep kernel takes the batch statistics itself -- one dependent launch fewer)
     static const bool nofuse_env = getenv("EH_LFORM_NOFUSE") != nullptr;
-    const bool nofuse = nofuse_env || h->bnl;      // (BatchNorm layers in the chain: the plain loop below, one launch per layer and pass)
+    const bool nofuse = nofuse_env || h->bnl || h->lnl;      // (BatchNorm / LayerNorm layers in the chain: the plain loop below, one launch per layer and pass)
     const bool bn_self = train_mode && h->bn_on && !h->bn_ext && count > 0 && count <= 256 && !nofuse;
     if (train_mode && !bn_self) { if (int rc = eh_bn_prepare(h, sp, idx, first, count, bn_update, &bn)) return rc; }
     EhLPrepArgs pa{};
@@ -277,6 +346,7 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
         for (int l = 0; l < (lstop >= 0 ? lstop : L.nl); ++l) {
             if ((fused0 || fused01) && k == 0 && l == 0) continue;
             if (fused01 && k == 0 && l == 1) continue;
+            if (L.lbn[l] >= 3) { if (int rc = lnl_forward_layer(h, l, B, train_mode, W)) return rc; continue; }
             if (L.lbn[l]) { if (int rc = bnl_forward_layer(h, l, B, train_mode, bn_update, W)) return rc; continue; }
             EhGemmArgs g{};
             g.A = l == 0 ? W.Xb + L.c0 : W.H[k][l - 1]; g.lda = l == 0 ? net.P : L.in[l];      // (a network's predictors: its columns of the minibatch matrix)
@@ -313,7 +383,7 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     // Small minibatches: every layer's delta is kept (l_dk), the chain of delta products runs first and the weight gradients -- a
     // handful of tiles each, 4-6 us per dependent launch -- follow as ONE grouped launch of the tiled ones and one of the thin ones.
     static const long long lgroup_max = getenv("EH_LFORM_GROUP_MAX") ? atoll(getenv("EH_LFORM_GROUP_MAX")) : 4096;
-    bool grouped = count <= lgroup_max && h->l_nnets > 0 && !h->bnl;      // (the kept-deltas groups and the tail chain behind them hold Dense layers only)
+    bool grouped = count <= lgroup_max && h->l_nnets > 0 && !h->bnl && !h->lnl;      // (the kept-deltas groups and the tail chain behind them hold Dense layers only)
     long long dk_floats = 0;
     // (sized by THIS minibatch, rounded up to a power of two -- not by the largest one the path serves: a B = 64 step of a deep, wide
     //  MultiNN model used to ask for up to the 1 GiB cap; advisor, round 3.  A larger batch later re-grows it, outside a capture.)
@@ -480,9 +550,9 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
         int which = 0;
         for (int l = L.nl - 1; l >= 0; --l) {
             const int in = L.in[l], out = L.out[l];
-            if (L.lbn[l]) {                    // a BatchNorm layer: dZ is d loss / d its output; its leaves' sums to the slab, the delta of the layer below to the other buffer
+            if (L.lbn[l]) {                    // a BatchNorm / LayerNorm layer: dZ is d loss / d its output; its leaves' sums to the slab, the delta of the layer below to the other buffer
                 float* const dnext = W.D[which];
-                if (int rc = bnl_backward_layer(h, l, B, dZ, dnext, rows, W)) return rc;
+                if (int rc = L.lbn[l] >= 3 ? lnl_backward_layer(h, l, B, dZ, dnext, rows, W) : bnl_backward_layer(h, l, B, dZ, dnext, rows, W)) return rc;
                 dZ = dnext; dz_t = false; which ^= 1;
                 continue;
             }

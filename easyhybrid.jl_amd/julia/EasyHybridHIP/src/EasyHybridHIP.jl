@@ -23,6 +23,9 @@ const LIB = Ref{String}(get(ENV, "EASYHYBRID_HIP_LIB", joinpath(@__DIR__, "..", 
 const EH_MAX_HIDDEN, EH_MAX_PARAMS, EH_MAX_FORC, EH_MAX_TARG = 8, 8, 4, 4
 const EH_SPLIT_TRAIN, EH_SPLIT_VAL = Int32(0), Int32(1)
 const EH_LAYER_BATCHNORM, EH_LAYER_BN_NOAFFINE = Int32(40), Int32(8)      # net_activation[l] of a BatchNorm layer inside the chain: EH_LAYER_BATCHNORM [+ EH_LAYER_BN_NOAFFINE] + its activation id
+const EH_LAYER_LAYERNORM, EH_LAYER_LN_NOAFFINE = Int32(56), Int32(8)      # ... of a LayerNorm layer: EH_LAYER_LAYERNORM [+ EH_LAYER_LN_NOAFFINE] + its activation id (theta: bias, then scale)
+"net_activation[l] of `LayerNorm((n,), act; affine)` behind hidden layer l - 1 (`act_id` = the eh_activation of `act`, 0..4); its epsilon: `set_layer_norm!`"
+layernorm_code(act_id::Integer; affine::Bool = true) = EH_LAYER_LAYERNORM + (affine ? Int32(0) : EH_LAYER_LN_NOAFFINE) + Int32(act_id)
 const EH_LAYER_LSTM, EH_LAYER_GRU, EH_LAYER_RNN = Int32(16), Int32(24), Int32(32)      # net_activation[l] of a recurrent hidden layer (EH_LAYER_RNN + the RNNCell's activation id)
 
 # mirror of `eh_model_desc` (field order and widths exactly as in the header)

@@ -292,13 +292,62 @@ def _bn_kind(a) -> int:
     return 1 if a.startswith(BN_LAYER) else (2 if a.startswith(BN_LAYER_NOAFFINE) else 0)
 
 
+LAYERNORM_MAX_WIDTH = 1024      # a row of the layer lives in one wave's registers (csrc/eh_lnl.hpp, EH_MAX_LAYERNORM_WIDTH)
+
+
+class LayerNorm:
+    """Lux `LayerNorm(shape, activation; epsilon, dims, affine)` for a 1-D shape `(n,)` as a DESCRIPTION of a layer inside
+    `hidden_layers = Chain(...)`: every sample over its own n features, y = activation(scale (x - mean(x)) / sqrt(var(x) + epsilon) + bias)
+    with the biased variance, the gradient through both.  No state: training, evaluation and predictions run the same pass.  affine = True
+    adds the leaves `bias` (zeros) and `scale` (ones), in that order; no weight_l2 term reads them."""
+
+    def __init__(self, shape, activation="identity", affine: bool = True, epsilon: float = 1e-5, dims=None):
+        if isinstance(shape, (tuple, list)):
+            if len(shape) != 1:
+                raise NotImplementedError(f"LayerNorm({tuple(shape)!r}): only a 1-D shape (n,) behind a layer of width n has a device kernel")
+            shape = shape[0]
+        if dims is not None:
+            raise NotImplementedError(f"LayerNorm(dims = {dims!r}): only the default dims = : (all features of a sample) has a device kernel")
+        self.dims, self.activation, self.affine, self.epsilon = int(shape), _act_name(activation), bool(affine), float(epsilon)
+        if self.dims < 1:
+            raise ValueError(f"LayerNorm({shape!r}): the layer needs at least one unit")
+        if not self.epsilon > 0.0:
+            raise ValueError(f"LayerNorm(epsilon = {epsilon!r}): epsilon > 0")
+        if self.dims > LAYERNORM_MAX_WIDTH:
+            raise NotImplementedError(f"LayerNorm({self.dims}): the device kernels take rows of up to {LAYERNORM_MAX_WIDTH} features")
+
+    def __repr__(self):
+        return f"LayerNorm({self.dims}, {self.activation})"
+
+
+LN_LAYER = "ln:"          # the "activation" of a hidden layer that is LayerNorm(n, act): "ln:<act>", EH_LAYER_LAYERNORM + the activation's id
+LN_LAYER_NOAFFINE = "ln0:"    # ... with affine = false: EH_LAYER_LAYERNORM + EH_LAYER_LN_NOAFFINE + the activation's id
+
+
+def _ln_kind(a) -> int:
+    """a hidden layer's "activation" -> 1 when the layer is a LayerNorm with bias / scale, 2 without, 0 otherwise"""
+    if not isinstance(a, str):
+        return 0
+    return 1 if a.startswith(LN_LAYER) else (2 if a.startswith(LN_LAYER_NOAFFINE) else 0)
+
+
+def _norm_leaves(a):
+    """a hidden layer's "activation" -> None for a Dense or recurrent layer, otherwise the names of the normalisation layer's leaves in theta
+    order: BatchNorm (scale, bias), LayerNorm (bias, scale), () with affine = false"""
+    if _bn_kind(a):
+        return ("scale", "bias") if _bn_kind(a) == 1 else ()
+    if _ln_kind(a):
+        return ("bias", "scale") if _ln_kind(a) == 1 else ()
+    return None
+
+
 def _split_dropout(hidden_layers):
     """Chain with Dropout layers -> (the Chain without them, [p_0 .. p_{L-1}] per hidden layer or None).  A Dropout belongs to the hidden
     layer in front of it; as the first element that is the layer the reference prepends (Dense(in_dim, first_h, activation)).
     Dropout(0) is Lux's NoOpLayer and disappears.  Chains around a Recurrence are left to _hidden_widths (and its refusals)."""
     if not isinstance(hidden_layers, Chain) or not any(isinstance(l, Dropout) for l in hidden_layers.layers):
         return hidden_layers, None
-    if any(isinstance(l, (Recurrence, BatchNorm)) for l in hidden_layers.layers):
+    if any(isinstance(l, (Recurrence, BatchNorm, LayerNorm)) for l in hidden_layers.layers):
         return hidden_layers, None
     rest, rates, prev = [], {}, False
     for i, l in enumerate(hidden_layers.layers):
@@ -338,6 +387,10 @@ def _layer_code(a: str) -> int:
         return L.EH_LAYER_BATCHNORM + L.ACTIVATIONS[a[len(BN_LAYER):]]
     if _bn_kind(a) == 2:
         return L.EH_LAYER_BATCHNORM + L.EH_LAYER_BN_NOAFFINE + L.ACTIVATIONS[a[len(BN_LAYER_NOAFFINE):]]
+    if _ln_kind(a) == 1:
+        return L.EH_LAYER_LAYERNORM + L.ACTIVATIONS[a[len(LN_LAYER):]]
+    if _ln_kind(a) == 2:
+        return L.EH_LAYER_LAYERNORM + L.EH_LAYER_LN_NOAFFINE + L.ACTIVATIONS[a[len(LN_LAYER_NOAFFINE):]]
     if kind == "rnn":
         return L.EH_LAYER_RNN + L.ACTIVATIONS[a[len(RNN_LAYER):]]
     return {"lstm": L.EH_LAYER_LSTM, "gru": L.EH_LAYER_GRU}[kind] if kind else L.ACTIVATIONS[a]
@@ -361,7 +414,7 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
         ls = hidden_layers.layers
         if not ls:
             raise ValueError("hidden_layers: an empty Chain has no dimensions (NNModels.jl: 'Could not determine input dimension of hidden_layers Chain.')")
-        if any(isinstance(l, BatchNorm) for l in ls):
+        if any(isinstance(l, (BatchNorm, LayerNorm)) for l in ls):
             return _bn_chain_widths(ls, act, per_layer)
         if any(isinstance(l, Recurrence) for l in ls):
             # a chain that ends in Recurrence(LSTMCell) gets its sequence head (NNModels.jl:171-211):
@@ -398,29 +451,34 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
 
 
 def _bn_chain_widths(ls, act: str, per_layer: bool):
-    """a Chain that holds BatchNorm layers next to Dense layers -> (widths, activations) with one entry per hidden layer of the descriptor:
-    the Dense layer the reference puts in front (first_h read off the chain's first layer -- a BatchNorm's dims, NNModels.jl:156-169), then
-    every layer of the chain, a BatchNorm as an entry as wide as the layer in front of it"""
+    """a Chain that holds BatchNorm / LayerNorm layers next to Dense layers -> (widths, activations) with one entry per hidden layer of the
+    descriptor: the Dense layer the reference puts in front (first_h read off the chain's first layer -- a normalisation layer's dims,
+    NNModels.jl:156-169), then every layer of the chain, a BatchNorm / LayerNorm as an entry as wide as the layer in front of it"""
+    what = "BatchNorm" if any(isinstance(l, BatchNorm) for l in ls) else "LayerNorm"      # (the messages name the kind the chain holds; both: BatchNorm's)
     if not per_layer:
-        raise NotImplementedError("hidden_layers Chain: BatchNorm layers in a MultiNN model have no device kernel (they are built for single-network models)")
+        raise NotImplementedError(f"hidden_layers Chain: {what} layers in a MultiNN model have no device kernel (they are built for single-network models)")
     if any(isinstance(l, Recurrence) for l in ls):
-        raise NotImplementedError("hidden_layers Chain: a BatchNorm layer next to a Recurrence has no device kernel (sequence models take no BatchNorm)")
+        raise NotImplementedError(f"hidden_layers Chain: a {what} layer next to a Recurrence has no device kernel (sequence models take no {what})")
     if any(isinstance(l, Dropout) for l in ls):
-        raise NotImplementedError("hidden_layers Chain: a BatchNorm layer next to a Dropout has no device kernel (dropout runs on the fused per-wave kernels, BatchNorm layer by layer)")
-    first = ls[0].dims if isinstance(ls[0], BatchNorm) else getattr(ls[0], "in_dims", None)
+        raise NotImplementedError(f"hidden_layers Chain: a {what} layer next to a Dropout has no device kernel (dropout runs on the fused per-wave kernels, {what} layer by layer)")
+    first = ls[0].dims if isinstance(ls[0], (BatchNorm, LayerNorm)) else getattr(ls[0], "in_dims", None)
     widths, acts, w = [first], [act], first
     for i, l in enumerate(ls):
         if isinstance(l, BatchNorm):
             if l.dims != w:
                 raise ValueError(f"hidden_layers Chain: layer {i + 1} is BatchNorm({l.dims}), the layer in front of it gives {w}")
             acts.append((BN_LAYER if l.affine else BN_LAYER_NOAFFINE) + l.activation)
+        elif isinstance(l, LayerNorm):
+            if l.dims != w:
+                raise ValueError(f"hidden_layers Chain: layer {i + 1} is LayerNorm({l.dims}), the layer in front of it gives {w}")
+            acts.append((LN_LAYER if l.affine else LN_LAYER_NOAFFINE) + l.activation)
         elif isinstance(l, Dense):
             if l.in_dims != w:
                 raise ValueError(f"hidden_layers Chain: layer {i + 1} takes {l.in_dims} inputs, the layer in front of it gives {w}")
             w = l.out_dims
             acts.append(_act_name(l.activation))
         else:
-            raise NotImplementedError(f"hidden_layers Chain: layer {i + 1} is {type(l).__name__}; only Dense and BatchNorm layers have a device kernel here")
+            raise NotImplementedError(f"hidden_layers Chain: layer {i + 1} is {type(l).__name__}; only Dense, BatchNorm and LayerNorm layers have a device kernel here")
         widths.append(w)
     return widths, acts
 
@@ -448,6 +506,7 @@ class SingleNNHybridModel:
     layer_activations: Optional[List[str]] = None    # single network from `hidden_layers::Chain` whose layers differ: the activation of hidden layer l (None = one for all)
     dropout: Optional[List[float]] = None            # `hidden_layers::Chain` with Dropout layers: the rate behind hidden layer l (None = none anywhere)
     batchnorm: Optional[Dict[int, Tuple[float, float]]] = None      # `hidden_layers::Chain` with BatchNorm layers: hidden layer l -> (momentum, epsilon) (None = none anywhere)
+    layernorm: Optional[Dict[int, float]] = None     # ... with LayerNorm layers: hidden layer l -> epsilon (None = none anywhere)
 
     # -- sizes ---------------------------------------------------------------------------------
     @property
@@ -484,6 +543,16 @@ class SingleNNHybridModel:
         """the hidden layers (indices into NN, = the descriptor's) that are BatchNorm layers, in chain order"""
         return [l for l, a in enumerate(self.layer_activations or ()) if _bn_kind(a)]
 
+    @property
+    def ln_layers(self) -> List[int]:
+        """the hidden layers that are LayerNorm layers, in chain order"""
+        return [l for l, a in enumerate(self.layer_activations or ()) if _ln_kind(a)]
+
+    @property
+    def norm_layers(self) -> List[int]:
+        """bn_layers and ln_layers together: the hidden layers that are no Dense layers but normalise the one in front of them"""
+        return [l for l, a in enumerate(self.layer_activations or ()) if _norm_leaves(a) is not None]
+
     def leaves(self):
         """[(network index, layer index, leaf name, shape)] of the networks in ComponentArray order: Dense layers have `weight` (out, in) and
         `bias`; the recurrent layer `weight_ih` (nH, I), `weight_hh` (nH, H), `bias_ih`, `bias_hh` (nH): n = 4 gate blocks [i | f | g | o] of
@@ -492,9 +561,9 @@ class SingleNNHybridModel:
         ng = CELL_GATES.get(self.cell, 0)
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
-                bn = _bn_kind(self.layer_activations[li]) if (self.layer_activations is not None and li < len(self.layer_activations)) else 0
-                if bn:       # BatchNorm: `scale` and `bias` (affine), or nothing
-                    out += [(k, li, "scale", (o,)), (k, li, "bias", (o,))] if bn == 1 else []
+                norm = _norm_leaves(self.layer_activations[li]) if (self.layer_activations is not None and li < len(self.layer_activations)) else None
+                if norm is not None:       # BatchNorm: `scale` and `bias`; LayerNorm: `bias` and `scale` (affine), or nothing
+                    out += [(k, li, name, (o,)) for name in norm]
                 elif ll is not None and li == ll:
                     out += [(k, li, "weight_ih", (ng * o, i)), (k, li, "weight_hh", (ng * o, o)), (k, li, "bias_ih", (ng * o,)), (k, li, "bias_hh", (ng * o,))]
                 else:
@@ -528,9 +597,8 @@ class SingleNNHybridModel:
         parts = []
         for k, net in enumerate(self.nets):
             for li, (o, i) in enumerate(net):
-                if li in self.bn_layers:       # BatchNorm: scale = ones, bias = zeros (affine), or no leaf at all
-                    if _bn_kind(self.layer_activations[li]) == 1:
-                        parts += [np.ones(o, np.float32), np.zeros(o, np.float32)]
+                if li in self.norm_layers:     # BatchNorm, LayerNorm: scale = ones, bias = zeros (affine), or no leaf at all
+                    parts += [np.ones(o, np.float32) if name == "scale" else np.zeros(o, np.float32) for name in _norm_leaves(self.layer_activations[li])]
                     continue
                 if li == self.lstm_layer:      # LSTMCell, GRUCell, RNNCell: every leaf U(+-1/sqrt(H))
                     bh = 1 / math.sqrt(o)
@@ -566,10 +634,10 @@ class SingleNNHybridModel:
         if net is not None and net not in names:
             raise KeyError(f"weight_l2: no network named {net!r} (networks: {[n for n in names if n is not None]})")
         m = np.zeros(self.n_theta, bool)
-        off, bn = 0, set(self.bn_layers)
+        off, bn = 0, set(self.norm_layers)
         for k, li, leaf, shape in self.leaves():
             n = int(np.prod(shape))
-            if (net is None or net == names[k]) and leaf == key and li not in bn:      # (extract_weights.jl:24: a BatchNorm's scale / bias are skipped)
+            if (net is None or net == names[k]) and leaf == key and li not in bn:      # (extract_weights.jl:24: a BatchNorm's / LayerNorm's scale / bias are skipped)
                 m[off:off + n] = True
             off += n
         return m
@@ -586,13 +654,13 @@ class SingleNNHybridModel:
     def unpack(self, theta: np.ndarray):
         """flat theta -> (ps = [(weight (out,in), bias)...], {global: raw})"""
         off, nets = 0, []
-        if self.bn_layers:                   # a BatchNorm layer unpacks to a dict of its leaves ({} with affine = false)
-            layers = [{} if li in self.bn_layers else [None, None] for li in range(len(self.NN))]
+        if self.norm_layers:                 # a BatchNorm / LayerNorm layer unpacks to a dict of its leaves ({} with affine = false)
+            layers = [{} if li in self.norm_layers else [None, None] for li in range(len(self.NN))]
             for _, li, name, shape in self.leaves():
                 n = int(np.prod(shape))
                 v = theta[off:off + n].reshape(shape, order="F") if len(shape) == 2 else theta[off:off + n]
                 off += n
-                if li in self.bn_layers:
+                if li in self.norm_layers:
                     layers[li][name] = v
                 else:
                     layers[li][0 if name == "weight" else 1] = v
@@ -625,7 +693,7 @@ class SingleNNHybridModel:
         names = ["ps"] if self.NNs is None else list(self.neural_param_names)
         nets = self.nets if self.nets else [[]]
         for name, net in zip(names, nets):
-            n = self.n_nn if (self.lstm_layer is not None or self.bn_layers) else sum(o * i + o for o, i in net)
+            n = self.n_nn if (self.lstm_layer is not None or self.norm_layers) else sum(o * i + o for o, i in net)
             out[name] = (off, off + n)
             off += n
         for g in self.global_param_names:
@@ -738,6 +806,9 @@ class SingleNNHybridModel:
             for l, (mom, eps) in (self.batchnorm or {}).items():
                 if (mom, eps) != (0.1, 1e-5):
                     eng.set_layer_norm(l, mom, eps)
+            for l, eps in (self.layernorm or {}).items():
+                if eps != 1e-5:
+                    eng.set_layer_norm(l, epsilon=eps)
         except Exception:
             eng.close()
             raise
@@ -857,6 +928,12 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
             raise NotImplementedError(f"precision = {kwargs['precision']!r} with BatchNorm layers in hidden_layers: they run on the fp32 layer-wise kernels only")
         bns = [l for l in chain.layers if isinstance(l, BatchNorm)]
         batchnorm = {i: (b.momentum, b.epsilon) for i, b in zip([i for i, a in enumerate(layer_acts) if _bn_kind(a)], bns)}
+    layernorm = None
+    if any(_ln_kind(a) for a in (layer_acts or ())):
+        if kwargs.get("precision", "f32") != "f32":
+            raise NotImplementedError(f"precision = {kwargs['precision']!r} with LayerNorm layers in hidden_layers: they run on the fp32 layer-wise kernels only")
+        lns = [l for l in chain.layers if isinstance(l, LayerNorm)]
+        layernorm = {i: b.epsilon for i, b in zip([i for i, a in enumerate(layer_acts) if _ln_kind(a)], lns)}
     if dropout is not None and (len(hidden_layers) > DROPOUT_MAX_LAYERS or max(hidden_layers) > DROPOUT_MAX_WIDTH):
         raise NotImplementedError(f"hidden_layers Chain: Dropout on hidden layers {hidden_layers}: the dropout kernels are the per-wave fused family, "
                                   f"1..{DROPOUT_MAX_LAYERS} hidden layers of at most {DROPOUT_MAX_WIDTH} units")
@@ -872,4 +949,4 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
     return SingleNNHybridModel(NN, predictors, forcing, targets, ms, parameters, neural_param_names, global_param_names,
                                fixed, bool(scale_nn_outputs), bool(start_from_default), config,
                                layer_activations=None if no_nn else layer_acts, dropout=None if no_nn else dropout,
-                               batchnorm=None if no_nn else batchnorm)
+                               batchnorm=None if no_nn else batchnorm, layernorm=None if no_nn else layernorm)

@@ -1139,7 +1139,7 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         xterms = _extra_terms(tc.extra_loss)
         aggn = _agg_name(tc.agg)
         _apply_extra_loss(eng, model, xterms, aggn, eng.n_pseudo)
-        _apply_step_mode(eng, replace(tc, fused_update=False) if lbfgs is not None else tc, is_seq or bool(bn_layers))      # (BatchNorm layers: the engine runs the pair, as for sequence models)
+        _apply_step_mode(eng, replace(tc, fused_update=False) if lbfgs is not None else tc, is_seq or bool(bn_layers) or bool(getattr(model, "ln_layers", None)))      # (BatchNorm / LayerNorm layers: the engine runs the pair, as for sequence models)
         if lbfgs is not None:      # (after the losses and options: the mode refuses what changes the objective between trial points)
             eng.lbfgs_init(m=lbfgs.m, c1=lbfgs.c1, c2=lbfgs.c2, max_linesearch=lbfgs.max_linesearch, initial_step=lbfgs.initial_step,
                            g_tol=float(solve_kw.get("g_tol", 1e-5)), f_reltol=float(solve_kw.get("f_reltol", 0.0)))

@@ -86,6 +86,19 @@ typedef enum eh_activation { EH_ACT_TANH = 0, EH_ACT_SIGMOID = 1, EH_ACT_RELU = 
  * capture, "fused_update" 1, "multi_step", "specialize", "precision". */
 #define EH_LAYER_BATCHNORM 40 /* .. EH_LAYER_BATCHNORM + EH_ACT_IDENTITY */
 #define EH_LAYER_BN_NOAFFINE 8 /* EH_LAYER_BATCHNORM + EH_LAYER_BN_NOAFFINE + activation: 48 .. 52 */
+/* ... or Lux's LayerNorm((hidden[l],), act) behind the layer in front of it (EH_LAYER_LAYERNORM + its eh_activation TANH..IDENTITY: 56 .. 60;
+ * EH_LAYER_LN_NOAFFINE added: affine = false, 64 .. 68).  hidden[l] must equal hidden[l-1] (l >= 1) and be at most EH_MAX_LAYERNORM_WIDTH;
+ * the layer counts towards EH_MAX_HIDDEN.  Every sample over its own hidden[l] features: y = act(scale (x - mu) / sqrt(var + eps) + bias),
+ * mu the mean and var the biased variance of the row, the gradient through both.  No state: training, eh_eval and eh_forward run the same
+ * pass.  Flat theta: the layer's `bias` (zeros) and then `scale` (ones) -- the order of Lux's LayerNorm leaves, the reverse of BatchNorm's
+ * --, hidden[l] each, at its place in chain order; none with affine = false.  No weight_l2 term reads them.  One network (n_nets == 0),
+ * fp32, always the layer-wise form and its step + reduce pair; refused with the reason: a recurrent layer in the same chain,
+ * "fused_update" 1, "multi_step", "specialize", "precision".  Nothing couples the samples, so -- unlike BatchNorm layers -- data
+ * parallelism (eh_dp_grad / eh_dp_apply), L-BFGS and graph capture work as for a chain of Dense layers; a chain that also holds a
+ * BatchNorm layer takes that layer's refusals.  Epsilon: eh_set_layer_norm (default 1e-5). */
+#define EH_LAYER_LAYERNORM 56 /* .. EH_LAYER_LAYERNORM + EH_ACT_IDENTITY */
+#define EH_LAYER_LN_NOAFFINE 8 /* EH_LAYER_LAYERNORM + EH_LAYER_LN_NOAFFINE + activation: 64 .. 68 */
+#define EH_MAX_LAYERNORM_WIDTH 1024 /* a row of the layer lives in one wave's registers (16 floats per lane) */
 
 /* registry of mechanistic models (the reference takes an arbitrary Julia closure,
  * src/models/GenericHybridModel.jl:425; a closure cannot run in a kernel, so the engine ships
@@ -326,7 +339,9 @@ int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* ru
  * 0) and variance (1).  eh_train_step / eh_train_epoch move them with the layer's momentum (the variance by the unbiased m / (m - 1)
  * estimate, m = rows of the minibatch; m = 1: factor 1); eh_loss_and_grad uses the batch statistics and leaves them alone.
  * eh_set_layer_norm: the layer's momentum (0..1) and epsilon (> 0); defaults 0.1 and 1e-5.
- * EH_ESTATE: hidden layer `layer` is no BatchNorm layer. */
+ * eh_set_layer_norm also takes a LayerNorm layer (EH_LAYER_LAYERNORM): its epsilon is set, the momentum is checked and otherwise ignored
+ * (the layer has no state; eh_get_layer_state / eh_set_layer_state refuse it).
+ * EH_ESTATE: hidden layer `layer` is no BatchNorm layer (eh_set_layer_norm: neither a BatchNorm nor a LayerNorm layer). */
 int32_t eh_get_layer_state(eh_handle* h, int32_t layer, float* running_mean, float* running_var, int64_t n);
 int32_t eh_set_layer_state(eh_handle* h, int32_t layer, const float* running_mean, const float* running_var, int64_t n);
 int32_t eh_set_layer_norm(eh_handle* h, int32_t layer, float momentum, float epsilon);
