@@ -90,6 +90,7 @@ SIGNATURES = {
     "eh_version": (C.c_int32, []),
     "eh_last_error": (C.c_char_p, [_H]),
     "eh_create": (C.c_int32, [C.POINTER(ModelDesc), C.POINTER(_H)]),
+    "eh_create_seq_targets": (C.c_int32, [C.POINTER(ModelDesc), C.POINTER(_H)]),
     "eh_destroy": (C.c_int32, [_H]),
     "eh_n_theta": (C.c_int32, [_H, C.POINTER(C.c_int64)]),
     "eh_set_stream": (C.c_int32, [_H, C.c_void_p]),

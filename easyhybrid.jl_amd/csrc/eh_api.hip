@@ -572,7 +572,7 @@ static void stream_pool_give(int device, hipStream_t s) {
 // for every cell): 0 = the descriptor has no recurrent layer, 1 = the one shape that is built -- Dense(P -> I) -> cell(I -> H) ->
 // Dense(H -> H) -> Dense(H -> K), eh_seq.hpp --, otherwise the status of the refusal.
 static bool seq_layer_code(int a) { return a == EH_LAYER_LSTM || a == EH_LAYER_GRU || (a >= EH_LAYER_RNN && a <= EH_LAYER_RNN + EH_ACT_IDENTITY); }
-static int seq_desc_check(const eh_model_desc* d) {
+static int seq_desc_check(const eh_model_desc* d, int n_out, bool several_targets) {
     if (d->activation != EH_ACT_PER_NET) return 0;
     const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
     int n_lstm = 0, at = -1;
@@ -588,8 +588,19 @@ static int seq_desc_check(const eh_model_desc* d) {
     if (d->hidden[0] > 32 || d->hidden[1] > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for LSTM widths I = %d, H = %d (built: up to 32 each)", d->hidden[0], d->hidden[1]);
     if (d->n_predictors > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with P = %d predictors (built: up to 32)", d->n_predictors);
     if (d->input_batchnorm) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for input BatchNorm on a sequence model (3-D input)");
-    if (d->n_targets > 1) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets (built: one)", d->n_targets);
-    return 1;                                // (around every mechanistic model: registry, several outputs -- the one target names its output --, recorded closure)
+    if (d->n_targets < 1 || d->n_targets > EH_MAX_TARG) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets (built: 1..%d)", d->n_targets, (int)EH_MAX_TARG);
+    for (int t = 0; t < d->n_targets; ++t)
+        if (d->target_output[t] < 0 || d->target_output[t] >= n_out)
+            return fail(nullptr, EH_EINVAL, "eh_create: sequence model: target_output[%d] = %d names an output the model does not have (it has %d)", t, d->target_output[t], n_out);
+    if (d->n_targets > 1 && n_out < 2)
+        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets around a model with one output (every target would observe the same value)", d->n_targets);
+    // eh_create keeps what it has always answered to such a descriptor, for the one reason that the tests of the one-target kernels pin that
+    // answer (include/easyhybrid_hip.h, eh_create_seq_targets): several targets are asked for by name
+    if (d->n_targets > 1 && !several_targets)
+        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets behind this entry point (one target per sequence handle; several: eh_create_seq_targets)", d->n_targets);
+    // (around every mechanistic model: registry, several outputs, recorded closure; every target names its output, in any order -- two
+    //  targets on one output are taken as the feed-forward families take them)
+    return 1;
 }
 
 // BatchNorm layers inside the chain (EH_LAYER_BATCHNORM [+ EH_LAYER_BN_NOAFFINE] + activation in the per-layer activation slots): 0 = the
@@ -637,7 +648,10 @@ static int lnl_desc_check(const eh_model_desc* d) {
     return 1;
 }
 
-int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
+static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets);
+int32_t eh_create(const eh_model_desc* d, eh_handle** out) { return create_handle(d, out, false); }
+int32_t eh_create_seq_targets(const eh_model_desc* d, eh_handle** out) { return create_handle(d, out, true); }
+static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets) {
     if (!d || !out) return fail(nullptr, EH_EINVAL, "eh_create: null argument");
     *out = nullptr;
     if (d->struct_size != (int32_t)sizeof(eh_model_desc)) return fail(nullptr, EH_EINVAL, "eh_create: struct_size %d != %zu", d->struct_size, sizeof(eh_model_desc));
@@ -652,7 +666,7 @@ int32_t eh_create(const eh_model_desc* d, eh_handle** out) {
     const bool lnl = lnk == 1;
     // (a normalisation layer of either kind: an entry of the chain that is no Dense layer)
     auto norm_layer_code = [&](int a) { return (bnl && bnl_layer_code(a)) || (lnl && lnl_layer_code(a)); };
-    const int seqk = (desc_layers && !bnl && !lnl) ? seq_desc_check(d) : 0;
+    const int seqk = (desc_layers && !bnl && !lnl) ? seq_desc_check(d, mi.n_out, seq_several_targets) : 0;
     if (seqk < 0) return seqk;
     const bool seq = seqk == 1;
     if (d->mech == EH_MECH_PROGRAM) {
@@ -1210,6 +1224,15 @@ int32_t eh_set_target_losses(eh_handle* h, const int32_t* kinds, int32_t n) {
         any_two = any_two || (kinds[t] >= EH_LOSS_PEARSONLOSS && kinds[t] <= EH_LOSS_PBKGELOSS) || (kinds[t] == EH_LOSS_RMSE && n > 1);
     }
     if (same) return eh_set_option(h, "training_loss", kinds[0]);
+    if (h->seq) {                            // sequence models: mse, mae and nseLoss per target -- one pass, no recorded losses
+        if (any_prog) return fail(h, EH_EUNSUPPORTED, "eh_set_target_losses: recorded losses (EH_LOSS_PROGRAM) are not built for sequence models");
+        if (any_two) return fail(h, EH_EUNSUPPORTED, "eh_set_target_losses: rmse on several targets / pearson / kge losses need passes ahead of the step, which are not built for sequence models (per target: mse, mae, nseLoss)");
+        HIPCHK(h, hipSetDevice(h->device));
+        FLUSH(h);
+        h->net.loss = EH_LOSS_MSE;
+        h->net.loss_t = lt;
+        return EH_OK;
+    }
     if (any_two && h->fused) return fail(h, EH_EUNSUPPORTED, "rmse (on a multi-target model) / pearson / kge training losses take forward passes ahead of the step: switch fused_update off first");
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
@@ -1235,6 +1258,9 @@ int32_t eh_set_target_losses(eh_handle* h, const int32_t* kinds, int32_t n) {
 int32_t eh_set_target_roles(eh_handle* h, const int32_t* roles, int32_t n) {
     if (!h || !roles) return EH_EINVAL;
     if (n != h->net.T) return fail(h, EH_EINVAL, "eh_set_target_roles: %d roles for %d targets", n, h->net.T);
+    if (h->seq)
+        for (int t = 0; t < n; ++t)
+            if (roles[t] != 0) return fail(h, EH_EUNSUPPORTED, "eh_set_target_roles: an extra_loss of the predictions (target %d as an entry of it) needs a recorded loss, which sequence models do not have", t);
     unsigned r = 0;
     int ndata = 0;
     for (int t = 0; t < n; ++t) {
@@ -1299,8 +1325,12 @@ static int32_t set_option(eh_handle* h, const char* name, int64_t value) {
         if (!strcmp(name, "training_loss")) {
             if (value < EH_LOSS_MSE || value > EH_LOSS_PROGRAM) return fail(h, EH_EUNSUPPORTED, "training_loss %lld is not implemented on the device", (long long)value);
             if (value > EH_LOSS_NSELOSS) return fail(h, EH_EUNSUPPORTED, "training_loss %lld: sequence models train on mse, rmse, mae and nseLoss (the two-pass losses and recorded losses are not built for them)", (long long)value);
+            if (value == EH_LOSS_RMSE && h->net.T > 1) return fail(h, EH_EUNSUPPORTED, "training_loss rmse: on a sequence model with %d targets it needs a pass ahead of the step (its scale cannot be applied after it), which is not built for sequence models: mse, mae and nseLoss are", h->net.T);
+            HIPCHK(h, hipSetDevice(h->device));
+            FLUSH(h);
             h->net.loss = (int)value;
-            h->net.loss_t = (unsigned)value;
+            h->net.loss_t = 0;
+            for (int t = 0; t < h->net.T; ++t) h->net.loss_t |= (unsigned)value << (4 * t);
             return EH_OK;
         }
     }
@@ -1659,6 +1689,8 @@ static EhSeqArgs seq_args(const eh_handle* h, const EhSplit& sp, const int* idx,
     a.W = sp.W; a.ow = sp.ow; a.lam = sp.lam;
     a.theta = TH(h); a.meta = h->image + h->arch->phi_off; a.slab = h->slab; a.n_acc = h->n_acc;
     a.shift = sp.shift[0];
+    for (int t = 0; t < EH_MAX_TARG; ++t) a.shift_t[t] = sp.shift[t];
+    a.inv_n = h->net.T > 1 ? h->inv_n : nullptr;
     a.I = h->seq_I; a.H = h->seq_H; a.act_in = h->seq_act_in; a.act_hd = h->seq_act_hd; a.act_cell = h->seq_act_cell;
     for (int k = 0; k < EH_SEQ_NOFF; ++k) a.off[k] = h->seq_off[k];
     a.prog = h->prog;
@@ -1673,7 +1705,7 @@ static eh_handle_s::JitEntry* seq_jit_entry(eh_handle* h) {
     h->jit.emplace_back(new eh_handle_s::JitEntry());
     eh_handle_s::JitEntry* je = h->jit.back().get();
     je->arch = h->arch; je->variant = 0; je->fast = 0; je->spec = false; je->p2p = false; je->net = h->net; je->loss_gen = 0;
-    const bool ok = eh_jit_build_seq(h->desc, h->seq_nbi, h->seq_nbh, h->seq_cell, &je->k, &je->log);
+    const bool ok = eh_jit_build_seq(h->desc, h->seq_nbi, h->seq_nbh, h->seq_cell, h->net.T > 1, &je->k, &je->log);
     je->state.store(ok ? 1 : -1, std::memory_order_release);
     if (!ok) { h->jit_log = je->log; h->jit_failed = true; return nullptr; }
     return je;
@@ -1684,13 +1716,15 @@ static eh_handle_s::JitEntry* seq_jit_entry(eh_handle* h) {
 // is another binary from another compiler run, at the register pressure of these kernels (the run-time compiler that ships with PyTorch
 // spills in TRAIN at NBI = NBH = 2, where the one of the build does not); the build's own errors only catch refusals.  On disagreement the
 // handle stays on the interpreter and says so in eh_jit_status.  A minibatch without a valid target decides nothing: the next one does.
+// Several targets: the row is [gradient | loss | n_1 .. n_T] under the weights of the count pre-pass (which has run: both passes read the
+// same table); the loss column and all T count columns are compared, and a minibatch in which no target has a valid entry is the one skipped.
 static void seq_jit_verify(eh_handle* h, eh_handle_s::JitEntry* je, int grid, const EhSeqArgs& a) {
     const EhNet& net = h->net;
     const size_t n = (size_t)grid * a.n_acc;
     std::vector<float> part[2] = {std::vector<float>(n), std::vector<float>(n)};
     bool ran = true;
     for (int k = 0; k < 2 && ran; ++k) {
-        ran = (k == 0 ? eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a, h->seq_cell)
+        ran = (k == 0 ? eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a, h->seq_cell, net.T > 1)
                       : eh_jit_launch_seq(&je->k, EH_SEQ_TRAIN, grid, h->stream, &net, &a)) == hipSuccess &&
               hipMemcpyAsync(part[k].data(), a.slab, n * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
     }
@@ -1702,8 +1736,10 @@ static void seq_jit_verify(eh_handle* h, eh_handle_s::JitEntry* je, int grid, co
         double gmax = 0.0, dmax = 0.0;
         for (int i = 0; i < net.n_theta; ++i) { const double x = col(0, i), y = col(1, i); gmax = std::max(gmax, fabs(x)); dmax = std::max(dmax, fabs(x - y)); }
         const double sa = col(0, net.n_theta), sb = col(1, net.n_theta) * (getenv("EH_DEBUG_JIT_SKEW") ? 1.01 : 1.0);      // (tests: the fall-back path)
-        const bool counts = col(0, net.n_theta + 1) == col(1, net.n_theta + 1);
-        if (counts && col(0, net.n_theta + 1) == 0.0) return;
+        bool counts = true;
+        double ntot = 0.0;
+        for (int t = 0; t < net.T; ++t) { counts = counts && col(0, net.n_theta + 1 + t) == col(1, net.n_theta + 1 + t); ntot += col(0, net.n_theta + 1 + t); }
+        if (counts && ntot == 0.0) return;
         if (dmax <= 1e-5 * gmax + 1e-30 && fabs(sa - sb) <= 1e-5 * fabs(sa) + 1e-30 && counts && std::isfinite(gmax)) { je->verified = true; return; }
         char b[320];
         snprintf(b, sizeof b, "the sequence kernel compiled at run time disagrees with the interpreter on %lld windows of this model's data (gradient: max |difference| %.3g "
@@ -1724,7 +1760,15 @@ static hipError_t seq_launch(eh_handle* h, int mode, int grid, const EhSeqArgs& 
         h->jit_log = std::string("launch of the run-time compiled sequence kernel failed: ") + hipGetErrorString(e);
     }
     const int head = h->net.mech == EH_MECH_PROGRAM ? EH_SEQ_HEAD_PROG : (h->net.n_out > 1 ? EH_SEQ_HEAD_MULTI : EH_SEQ_HEAD_MECH);
-    return eh_seq_launch(h->seq_nbi, h->seq_nbh, mode, head, grid, h->stream, h->net, a, h->seq_cell);
+    return eh_seq_launch(h->seq_nbi, h->seq_nbh, mode, head, grid, h->stream, h->net, a, h->seq_cell, h->net.T > 1);
+}
+// several targets: the per-target weights of this minibatch of windows -> inv_n (eh_seq_count_kernel), ahead of the training pass
+static int seq_launch_count(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
+    const EhNet& net = h->net;
+    hipLaunchKernelGGL(eh_seq_count_kernel, dim3(net.T), dim3(EH_SEQ_COUNT_NT), 0, h->stream, sp.recs, h->C, net.P + net.F, sp.starts, idx, first, count, sp.W, sp.ow, sp.lam,
+                       h->inv_n, net.loss_t, sp.shift4(), h->img.agg_a);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
 }
 static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* grid_out) {
     if (!sp.starts) return fail(h, EH_ESTATE, "sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
@@ -1735,6 +1779,7 @@ static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long 
     if (need > h->seq_ws_floats) { if (int rc = eh_grow(h, &h->seq_ws, &h->seq_ws_floats, need)) return rc; }
     a.ws = h->seq_ws;
     *grid_out = grid;
+    if (h->net.T > 1) { if (int rc = seq_launch_count(h, sp, idx, first, count)) return rc; }
     HIPCHK(h, seq_launch(h, EH_SEQ_TRAIN, grid, a));
     return EH_OK;
 }
@@ -2038,31 +2083,35 @@ static int eval_host_acquire(eh_handle* h, size_t need) {
     return EH_OK;
 }
 
-// sequence models: `count` windows, count * ow predictions [window][j]; EVAL leaves one row of shifted sums per workgroup in the slab
+// sequence models: `count` windows, count * ow predictions [window][j] per target; EVAL leaves one row of shifted sums per workgroup in the
+// slab, EH_EVAL_STATS per target
 static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count, double* stats, float* const* yhat, float* const* params) {
     if (!sp.starts) return fail(h, EH_ESTATE, "eh_eval: sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
-    const long long nout = count * sp.ow, need = (long long)((yhat ? 1 : 0) + (params ? h->n_par : 0)) * nout;
+    const int T = h->net.T, nst = EH_EVAL_STATS * T;
+    const long long nout = count * sp.ow, need = (long long)((yhat ? T : 0) + (params ? h->n_par : 0)) * nout;
     if (need > h->out_cap) { if (int rc2 = eh_grow(h, &h->out_buf, &h->out_cap, need)) return rc2; }
     EhSeqArgs a = seq_args(h, sp, nullptr, first, count);
-    a.n_acc = EH_EVAL_STATS;
+    a.n_acc = nst;
     a.yhat = yhat ? h->out_buf : nullptr;
-    a.pout = params ? h->out_buf + (yhat ? nout : 0) : nullptr;
+    a.pout = params ? h->out_buf + (yhat ? T * nout : 0) : nullptr;
     a.yld = nout;
     const int grid = seq_grid_for(h, sp, count, false);
     HIPCHK(h, seq_launch(h, stats ? EH_SEQ_EVAL : EH_SEQ_FORWARD, grid, a));
     std::vector<float> part;
     if (stats) {
-        part.resize((size_t)grid * EH_EVAL_STATS);
+        part.resize((size_t)grid * nst);
         HIPCHK(h, hipMemcpyAsync(part.data(), h->slab, part.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (stats)
-        for (int k = 0; k < EH_EVAL_STATS; ++k) {
+        for (int k = 0; k < nst; ++k) {
             double s = 0;
-            for (int b = 0; b < grid; ++b) s += part[(size_t)b * EH_EVAL_STATS + k];
+            for (int b = 0; b < grid; ++b) s += part[(size_t)b * nst + k];
             stats[k] = s;
         }
-    if (yhat && yhat[0]) { if (int rc = eh_copy_out(h, yhat[0], a.yhat, (size_t)nout)) return rc; }
+    if (yhat)
+        for (int t = 0; t < T; ++t)
+            if (yhat[t]) { if (int rc = eh_copy_out(h, yhat[t], a.yhat + (long long)t * nout, (size_t)nout)) return rc; }
     if (params)
         for (int j = 0; j < h->n_par; ++j)
             if (params[j]) { if (int rc = eh_copy_out(h, params[j], a.pout + (long long)j * nout, (size_t)nout)) return rc; }

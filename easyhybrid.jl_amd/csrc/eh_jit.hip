@@ -532,7 +532,7 @@ hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t s
     return hipModuleLaunchKernel(k->fn[mode], (unsigned)grid, 1, 1, 64u * (unsigned)k->nw, 1, 1, (unsigned)lds, stream, params, nullptr);
 }
 
-bool eh_jit_build_seq(const eh_model_desc& d, int nbi, int nbh, int cell, EhJitKernel* out, std::string* log) {
+bool eh_jit_build_seq(const eh_model_desc& d, int nbi, int nbh, int cell, bool mt, EhJitKernel* out, std::string* log) {
     if (d.mech != EH_MECH_PROGRAM) { *log = "eh_jit_build_seq: not a recorded closure"; return false; }
     const std::string mech = eh_jit_mech_source(d);
     const std::string src = "typedef signed char int8_t; typedef unsigned char uint8_t; typedef int int32_t; typedef unsigned int uint32_t;\n"
@@ -545,7 +545,8 @@ bool eh_jit_build_seq(const eh_model_desc& d, int nbi, int nbh, int cell, EhJitK
     const int modes[3] = {EH_SEQ_TRAIN, EH_SEQ_EVAL, EH_SEQ_FORWARD};
     char name[3][96];
     for (int i = 0; i < 3; ++i) {
-        if (cell == EH_SEQ_CELL_LSTM) snprintf(name[i], sizeof name[i], "eh_seq_kernel<%d, %d, %d, %d>", nbi, nbh, modes[i], (int)EH_SEQ_HEAD_PROG);
+        if (mt) snprintf(name[i], sizeof name[i], "eh_seq_kernel<%d, %d, %d, %d, %d, true>", nbi, nbh, modes[i], (int)EH_SEQ_HEAD_PROG, cell);
+        else if (cell == EH_SEQ_CELL_LSTM) snprintf(name[i], sizeof name[i], "eh_seq_kernel<%d, %d, %d, %d>", nbi, nbh, modes[i], (int)EH_SEQ_HEAD_PROG);
         else snprintf(name[i], sizeof name[i], "eh_seq_kernel<%d, %d, %d, %d, %d>", nbi, nbh, modes[i], (int)EH_SEQ_HEAD_PROG, cell);
         hiprtcAddNameExpression(hp, name[i]);
     }

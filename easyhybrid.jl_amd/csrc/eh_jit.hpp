@@ -52,5 +52,6 @@ hipError_t eh_jit_launch(const EhJitKernel* k, int mode, int grid, hipStream_t s
 void eh_jit_release(EhJitKernel* k);
 // Sequence models around a recorded closure (eh_seq.hpp, EH_SEQ_HEAD_PROG): the (NBI, NBH) instantiation of the three modes compiled
 // around the generated eh_jit_fwd / eh_jit_rev; fn[EH_SEQ_TRAIN], fn[EH_SEQ_EVAL], fn[EH_SEQ_FORWARD].  Same disk cache as above.
-bool eh_jit_build_seq(const eh_model_desc& d, int nbi, int nbh, int cell, EhJitKernel* out, std::string* log);      // cell: EH_SEQ_CELL_*
+// cell: EH_SEQ_CELL_*; mt: the kernels of several targets (the launch is the same: EhSeqArgs carries what they read)
+bool eh_jit_build_seq(const eh_model_desc& d, int nbi, int nbh, int cell, bool mt, EhJitKernel* out, std::string* log);
 hipError_t eh_jit_launch_seq(const EhJitKernel* k, int mode, int grid, hipStream_t stream, const EhNet* net, const EhSeqArgs* args);

@@ -520,6 +520,49 @@ __global__ __launch_bounds__(256) void eh_count_kernel(const float* recs, int C,
         inv_n[EH_TT * t] = role == 0u ? w * agg_a : (role == 2u ? (n > 0.0f ? l2s : 0.0f) : w * l2s);
     }
 }
+// The same weights for one minibatch of WINDOWS (sequence models with several targets, eh_seq.hpp): the entries of target t are its
+// observations at the `ow` head steps of every window, record starts[window] + W - ow + j + lam -- the address the step kernel reads.  A
+// record that several windows read counts once per window (the reference materialises the windows).  One workgroup per target; a thread
+// owns whole windows -- index, start and the `ow` observations are a chain of dependent loads, so it has EH_SEQ_COUNT_U windows in flight
+// at a time (one entry at a time on 256 threads the pass cost 38 us per head step at 16 384 windows, profiles/r22) -- and sums them in
+// window order, then the tree below: a fixed order, no atomics.
+constexpr int EH_SEQ_COUNT_NT = 1024, EH_SEQ_COUNT_U = 4;
+__global__ __launch_bounds__(EH_SEQ_COUNT_NT) void eh_seq_count_kernel(const float* recs, int C, int toff, const int* starts, const int* idx, long long first, long long count,
+                                                                       int W, int ow, int lam, float* inv_n, unsigned loss_t, EhShift4 shift, float agg_a) {
+    __shared__ float red[3][EH_SEQ_COUNT_NT];
+    const int t = blockIdx.x;
+    const float sh = shift.c[t];
+    float c = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (long long k0 = threadIdx.x; k0 < count; k0 += (long long)EH_SEQ_COUNT_NT * EH_SEQ_COUNT_U) {
+        long long row[EH_SEQ_COUNT_U];
+#pragma unroll
+        for (int u = 0; u < EH_SEQ_COUNT_U; ++u) {
+            const long long k = k0 + (long long)u * EH_SEQ_COUNT_NT;
+            row[u] = k < count ? (long long)starts[idx ? (long long)idx[first + k] : first + k] + W - ow + lam : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < EH_SEQ_COUNT_U; ++u) {
+            if (row[u] < 0) continue;
+            const float* const y0 = recs + row[u] * C + toff + t;
+            for (int j = 0; j < ow; ++j) {
+                const float y = y0[(long long)j * C];
+                if (!__builtin_isnan(y)) { const float d = y - sh; c += 1.0f; s1 += d; s2 += d * d; }
+            }
+        }
+    }
+    red[0][threadIdx.x] = c; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = EH_SEQ_COUNT_NT / 2; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) { red[0][threadIdx.x] += red[0][threadIdx.x + w]; red[1][threadIdx.x] += red[1][threadIdx.x + w]; red[2][threadIdx.x] += red[2][threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float n = red[0][0];
+        float w = n > 0.0f ? 1.0f / n : 0.0f;
+        if (((loss_t >> (4 * t)) & 15u) == (unsigned)EH_LOSS_NSELOSS && n > 0.0f) w = 1.0f / (red[2][0] - red[1][0] * red[1][0] / n);
+        inv_n[EH_TT * t] = w * agg_a;      // (a target without a valid entry in the batch: weight 0 -- it adds nothing to loss or gradient)
+    }
+}
 // (data parallel) the all-reduced sums [n_t | sum (y - c) | sum (y - c)^2] of the GLOBAL batch -> the per-target weights; c is common to the ranks (eh_set_target_shift)
 __global__ void eh_weights_from_counts_kernel(const float* raw, int T, unsigned loss_t, float* inv_n, float agg_a, unsigned roles, float l2s) {
     const int t = threadIdx.x;

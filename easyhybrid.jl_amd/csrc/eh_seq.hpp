@@ -21,6 +21,9 @@
 //     compiled at run time around the generated eh_jit_fwd / eh_jit_rev (eh_jit.hip, EH_JIT_MECH) the tape is registers.
 //   * epilogue: the workgroup's waves are gathered in wave order into one slab row [n_theta gradient | S | n | Sy | Syy]
 //     (eh_reduce_kernel's contract), so the step is bit-reproducible.
+//   * several targets (template parameter MT, kernels of their own): the head evaluates every output once and loops over the targets
+//     (eh_seq_head_targets).  Their normalisers differ, so the weights come from a count pre-pass over the minibatch's windows
+//     (eh_seq_count_kernel) and the row is the one of the multi-target feed-forward steps, [n_theta gradient | loss | n_1 .. n_T].
 //   * the other cells change the recurrent step alone -- geometry, head, Dense-in and epilogue are shared.  GRUCell, gate blocks
 //     [r | z | n]: h' = (1 - z) n + z h with n = tanh(W_in x + b_in + r (W_hn h + b_hn)); the reset gate multiplies the hidden product, so
 //     that product is a fourth accumulator chain q of its own and b_hn a bias row of its own (r and z fold b_ih + b_hh as the LSTM does).
@@ -36,6 +39,8 @@ enum { EH_SEQ_CELL_LSTM = 0, EH_SEQ_CELL_GRU = 1, EH_SEQ_CELL_RNN = 2 };        
 constexpr int eh_seq_gates(int cell) { return cell == EH_SEQ_CELL_LSTM ? 4 : (cell == EH_SEQ_CELL_GRU ? 3 : 1); }        // gate blocks of weight_ih / weight_hh
 constexpr int eh_seq_bias_rows(int cell) { return cell == EH_SEQ_CELL_RNN ? 1 : 4; }                                      // bias blocks in LDS (GRU: r | z | n_ih | n_hh)
 constexpr int eh_seq_parked(int cell) { return cell == EH_SEQ_CELL_LSTM ? 6 : (cell == EH_SEQ_CELL_GRU ? 5 : 2); }       // C/D blocks parked per step and hidden block
+constexpr int EH_SEQ_MTW = 16 * (1 + EH_MAX_TARG) + EH_MAX_TARG;      // several targets, TRAIN: floats of a wave's row of per-target scalars (eh_seq_head_targets)
+constexpr int EH_SEQ_MTE = 16 * EH_EVAL_STATS * EH_MAX_TARG;          // ... EVAL: of its row of shifted sums, a column per window for each
 constexpr int EH_SEQ_TS = 20;                // row stride of the transposition tile (16 windows + 4: 16-byte rows, no two rows in one bank group)
 
 // canonical offsets into flat theta (ComponentArray order) and the LDS layout of the zero-padded parameters
@@ -54,14 +59,17 @@ struct EhSeqArgs {
     int n_acc;
     float* ws;               // TRAIN: ws_wave floats per wave of the grid
     long long ws_wave;
-    float* yhat;             // FORWARD: [count][ow] predictions ...
+    float* yhat;             // FORWARD: [count][ow] predictions per target, `yld` apart ...
     float* pout;             // ... and [n_par][count * ow] parameters
     long long yld;
-    float shift;
+    float shift;             // metric shift (one target)
     int I, H, act_in, act_hd;
     int off[EH_SEQ_NOFF];
     const unsigned* prog;    // EH_SEQ_HEAD_PROG: the recorded closure (EhStepArgs::prog layout)
     int act_cell;            // EH_SEQ_CELL_RNN: the cell's activation
+    // several targets (behind what the kernels of one target read, so that those stay what they are):
+    const float* inv_n;      // TRAIN: the per-target table of the window count pre-pass (EH_TT floats per target, [0] the weight)
+    float shift_t[EH_MAX_TARG];      // metric shift per target
 };
 
 template <int NBI, int NBH, int CELL = EH_SEQ_CELL_LSTM>
@@ -77,8 +85,8 @@ struct EhSeqGeom {
 // floats of workspace one wave needs: eh_seq_parked(cell) NBH blocks per step, NBH + 1 per head step, 256 floats a block
 inline long long eh_seq_ws_floats(int nbh, int W, int ow, int cell = EH_SEQ_CELL_LSTM) { return ((long long)W * eh_seq_parked(cell) * nbh + (long long)ow * (nbh + 1)) * 256; }
 int eh_seq_row_cap(int nbi, int nbh, int cell = EH_SEQ_CELL_LSTM);        // accumulators a slab row may hold (the row is staged in LDS over the parameters)
-// head: EH_SEQ_HEAD_* of the model, cell: EH_SEQ_CELL_* (a missing instantiation is an error, never another path)
-hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a, int cell = EH_SEQ_CELL_LSTM);
+// head: EH_SEQ_HEAD_* of the model, cell: EH_SEQ_CELL_*, mt: the kernels of several targets (a missing instantiation is an error, never another path)
+hipError_t eh_seq_launch(int nbi, int nbh, int mode, int head, int grid, hipStream_t stream, const EhNet& net, const EhSeqArgs& a, int cell = EH_SEQ_CELL_LSTM, bool mt = false);
 #endif
 
 #ifdef EH_SEQ_KERNELS
@@ -93,7 +101,96 @@ __device__ __forceinline__ f32x4 eh_seq_dact4(int id, const f32x4 z) { return f3
 __device__ __forceinline__ f32x4 eh_seq_sig4(const f32x4 z) { return f32x4{eh_sigmoid(z[0]), eh_sigmoid(z[1]), eh_sigmoid(z[2]), eh_sigmoid(z[3])}; }
 __device__ __forceinline__ f32x4 eh_seq_tanh4(const f32x4 z) { return f32x4{eh_tanh(z[0]), eh_tanh(z[1]), eh_tanh(z[2]), eh_tanh(z[3])}; }
 
-template <int NBI, int NBH, int MODE, int HEAD = EH_SEQ_HEAD_MECH, int CELL = EH_SEQ_CELL_LSTM>
+// The head's mechanistic stage and loss of a model with several targets, one window per lane (eh_step_body's loop over the targets):
+// every output of the model is evaluated once; target t takes its own output (net.targ_out), its own column of the record `yrow` and
+// so its own mask, its own loss kind (net.loss_t) and its weight wt[t] from the count pre-pass, and seeds the adjoint of its output.
+// One reverse pass takes all seeds: the Jacobian rows of the registry model, one sweep over the closure's tape.
+//   TRAIN: the per-target scalars live in a wave-private LDS row (EH_SEQ_MTW floats; at I = H = 32 the accumulators leave no registers for
+//          them): acc = the lane's column of [1 + EH_MAX_TARG][16] sums over the head steps -- [0] the weighted loss terms, [1 + t] the valid
+//          entries of target t, touched by the lanes with `sums` --, wts = the targets' weights behind them; dp[j] = d loss / d parameter j
+//   EVAL: acc = the lane's column of the wave's [EH_MAX_TARG][EH_EVAL_STATS][16] shifted sums, in LDS as well (in registers the 32 sums
+//         took the kernels to 256 VGPRs and one wave per SIMD);  yt[t]: the prediction for target t (every mode)
+template <int MODE, int HEAD>
+__device__ __forceinline__ void eh_seq_head_targets(const EhNet& net, const EhSeqArgs& a, const float (&par)[EH_MAX_PARAMS], const float (&frc)[EH_MAX_FORC],
+                                                    const float* yrow, bool live, bool sums, const float* wts, float* acc,
+                                                    float (&yt)[EH_MAX_TARG], float (&dp)[EH_MAX_PARAMS]) {
+    constexpr bool TRAIN = MODE == EH_SEQ_TRAIN, PROG = HEAD == EH_SEQ_HEAD_PROG;
+    static_assert(HEAD != EH_SEQ_HEAD_MECH, "several targets need a model with several outputs");
+    float yo[3] = {0.0f, 0.0f, 0.0f}, dydp[EH_MAX_PARAMS], Jx[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+#ifdef EH_JIT_MECH
+    EhJitTape jtape;
+    if constexpr (PROG) eh_jit_fwd(par, frc, jtape, yo[0], yo[1], yo[2]);
+    else {
+#else
+    float pval[PROG ? EH_PROG_SLOTS : 1];
+    if constexpr (PROG) {
+        eh_prog_forward(a.prog, par, frc, pval);
+        yo[0] = pval[a.prog[2]];
+        if (net.n_out > 1) yo[1] = pval[a.prog[3]];
+        if (net.n_out > 2) yo[2] = pval[a.prog[4]];
+    } else {
+#endif
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) dydp[j] = 0.0f;
+        yo[0] = eh_mech_eval(net.mech, par, frc, dydp);
+        eh_mech_extra(net.mech, par, frc, yo + 1, Jx);
+    }
+    float dyo[3] = {0.0f, 0.0f, 0.0f};                        // d loss / d output
+    bool any = false;
+#pragma unroll
+    for (int t = 0; t < EH_MAX_TARG; ++t) {
+        yt[t] = 0.0f;
+        if (t < net.T) {
+            const int to = (int)((net.targ_out >> (2 * t)) & 3u);
+            const float y = to == 0 ? yo[0] : (to == 1 ? yo[1] : yo[2]), yobs = yrow[t];
+            const bool valid = live && !__builtin_isnan(yobs);
+            const float r = valid ? y - yobs : 0.0f;
+            yt[t] = y;
+            if constexpr (TRAIN) {
+                const float w = wts[t];
+                float d, lt;
+                if (eh_target_mae(net.loss_t, t)) { lt = w * fabsf(r); d = r > 0.0f ? w : (r < 0.0f ? -w : 0.0f); }
+                else { lt = w * r * r; d = 2.0f * w * r; }
+                if (sums) { acc[0] += lt; acc[16 * (1 + t)] += valid ? 1.0f : 0.0f; }
+                dyo[0] += to == 0 ? d : 0.0f; dyo[1] += to == 1 ? d : 0.0f; dyo[2] += to == 2 ? d : 0.0f;
+                any = any || valid;
+            } else if constexpr (MODE == EH_SEQ_EVAL) {
+                if (valid && sums) {
+                    const float cy = yobs - a.shift_t[t], ch = y - a.shift_t[t];
+                    float* const e = acc + 16 * EH_EVAL_STATS * t;
+                    e[0] = fmaf(r, r, e[0]); e[16] += cy; e[32] = fmaf(cy, cy, e[32]); e[48] += 1.0f;
+                    e[64] += ch; e[80] = fmaf(ch, ch, e[80]); e[96] = fmaf(ch, cy, e[96]); e[112] += fabsf(r);
+                }
+            }
+        }
+    }
+    if constexpr (TRAIN) {
+#ifdef EH_JIT_MECH
+        float padj[EH_MAX_PARAMS];
+        if constexpr (PROG) eh_jit_rev(par, frc, jtape, dyo[0], dyo[1], dyo[2], padj);
+#else
+        float padj[PROG ? EH_PROG_SLOTS : 1];
+        if constexpr (PROG) {
+            const int nslot = EH_PROG_SLOT_INSTR + (int)a.prog[0];
+            for (int i = 0; i < nslot; ++i) padj[i] = 0.0f;
+            padj[a.prog[2]] += dyo[0];
+            if (net.n_out > 1) padj[a.prog[3]] += dyo[1];
+            if (net.n_out > 2) padj[a.prog[4]] += dyo[2];
+            eh_prog_reverse(a.prog, pval, padj);
+        }
+#endif
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+            float v;
+            if constexpr (PROG) v = padj[j];
+            else v = dyo[0] * dydp[j] + (j < 3 ? dyo[1] * Jx[0][j] + dyo[2] * Jx[1][j] : 0.0f);
+            dp[j] = any ? v : 0.0f;                           // (a window without a valid target adds nothing, whatever the model made of its record)
+        }
+    }
+}
+
+// MT: the head of a model with several targets (eh_seq_head_targets; the kernels of one target are the default and stay what they are)
+template <int NBI, int NBH, int MODE, int HEAD = EH_SEQ_HEAD_MECH, int CELL = EH_SEQ_CELL_LSTM, bool MT = false>
 __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net, const EhSeqArgs a) {
     using G = EhSeqGeom<NBI, NBH, CELL>;
     constexpr bool TRAIN = MODE == EH_SEQ_TRAIN, PROG = HEAD == EH_SEQ_HEAD_PROG, LSTM = CELL == EH_SEQ_CELL_LSTM, GRU = CELL == EH_SEQ_CELL_GRU;
@@ -101,7 +198,7 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     constexpr int RH = G::RH, SP = G::SP, SI = G::SI, SH = G::SH;
     // (a closure's tape takes registers at the head step that the registry models leave free: with PROG the gradient of the two head biases
     //  is summed over the windows at every head step and kept in a wave-private LDS row behind the layout, as the gate biases' is)
-    __shared__ __attribute__((aligned(16))) float lds[G::L_END + (PROG ? EH_SEQ_NW * (RH + 16) : 0)];
+    __shared__ __attribute__((aligned(16))) float lds[G::L_END + (PROG ? EH_SEQ_NW * (RH + 16) : 0) + (MT && TRAIN ? EH_SEQ_NW * EH_SEQ_MTW : 0) + (MT && MODE == EH_SEQ_EVAL ? EH_SEQ_NW * EH_SEQ_MTE : 0)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
     const int P = net.P, I = a.I, H = a.H, K = net.K, C = a.C;
 
@@ -136,6 +233,16 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
     for (int e = lane; e < NB * RH; e += 64) GB[e] = 0.0f;
     float* const HB = lds + G::L_END + (PROG ? wave * (RH + 16) : 0);      // PROG: [RH] head Dense bias | [16] output Dense bias
     if constexpr (PROG) { for (int e = lane; e < RH + 16; e += 64) HB[e] = 0.0f; }
+    // MT, TRAIN: the sums over the head steps per target, zeroed, and the targets' weights -- read here, once for all tiles and head steps
+    float* const MTA = lds + G::L_END + (PROG ? EH_SEQ_NW * (RH + 16) : 0) + (MT && TRAIN ? wave * EH_SEQ_MTW : 0) + (MT && MODE == EH_SEQ_EVAL ? wave * EH_SEQ_MTE : 0);
+    if constexpr (MT && TRAIN) {
+        for (int e = lane; e < EH_SEQ_MTW; e += 64) { const int t = e - 16 * (1 + EH_MAX_TARG); MTA[e] = (t >= 0 && t < net.T) ? a.inv_n[EH_TT * t] : 0.0f; }
+        EH_WAVE_SYNC();
+    }
+    if constexpr (MT && MODE == EH_SEQ_EVAL) {                 // MT, EVAL: the shifted sums per target
+        for (int e = lane; e < EH_SEQ_MTE; e += 64) MTA[e] = 0.0f;
+        EH_WAVE_SYNC();
+    }
     // C/D block -> its transpose as an MFMA operand with the window on K: element r of the result = M[row n][window 4g + r]
     auto tr = [&](const f32x4 v) -> f32x4 {
 #pragma unroll
@@ -351,6 +458,40 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
             for (int f = 0; f < EH_MAX_FORC; ++f) {
                 const unsigned col = (net.forc_col >> (8 * f)) & 255u;
                 frc[f] = col != 255u ? rec[P + col] : 0.0f;
+            }
+            if constexpr (MT) {                               // several targets: all of the mechanistic stage and the loss (eh_seq_head_targets)
+                float yt[EH_MAX_TARG], dp[EH_MAX_PARAMS];
+                eh_seq_head_targets<MODE, HEAD>(net, a, par, frc, a.recs + (long long)(st + t + a.lam) * C + P + net.F, live, g == 0, MTA + 16 * (1 + EH_MAX_TARG), MTA + n, yt, dp);
+                if constexpr (TRAIN) {                        // (from here on as for one target, below)
+                    float dps[EH_MAX_PARAMS];
+#pragma unroll
+                    for (int j = 0; j < EH_MAX_PARAMS; ++j) {
+                        dps[j] = dp[j] * sg[j];
+                        if (g == 0 && j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL) gp[j] += dp[j];
+                    }
+                    f32x4 dob = Z4;
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+                        for (int j = 0; j < EH_MAX_PARAMS; ++j)
+                            if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_NEURAL && (int)((net.par_idx >> (4 * j)) & 15u) == 4 * g + rr) dob[rr] = dps[j];
+                    f32x4* const w4 = reinterpret_cast<f32x4*>(wsh) + (long long)j_out * (NBH + 1) * 64 + lane;
+                    if constexpr (!PROG) {
+#pragma unroll
+                        for (int hb = 0; hb < NBH; ++hb) w4[hb * 64] = z1[hb];
+                    }
+                    w4[NBH * 64] = dob;
+                } else if (live && g == 0) {
+                    const long long o = kwin * a.ow + j_out;
+                    if (a.yhat) {
+#pragma unroll
+                        for (int tt = 0; tt < EH_MAX_TARG; ++tt)
+                            if (tt < net.T) a.yhat[(long long)tt * a.yld + o] = yt[tt];
+                    }
+                    if (a.pout)
+                        for (int j = 0; j < net.n_par; ++j) a.pout[(long long)j * a.yld + o] = par[j];
+                }
+                continue;
             }
             float y;
 #ifdef EH_JIT_MECH
@@ -590,7 +731,19 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
 
     // ================= epilogue ===========================================================================================
     __syncthreads();                                           // every wave is through with the parameters: the row takes their place
-    if constexpr (MODE == EH_SEQ_EVAL) {
+    if constexpr (MODE == EH_SEQ_EVAL && MT) {                 // EH_EVAL_STATS sums per target, the targets one after the other (a.n_acc = EH_EVAL_STATS * T)
+        constexpr int NS = EH_EVAL_STATS * EH_MAX_TARG;
+#pragma unroll
+        for (int t = 0; t < EH_MAX_TARG; ++t)
+#pragma unroll
+            for (int k = 0; k < EH_EVAL_STATS; ++k) { const float v = eh_wave_sum(g == 0 ? MTA[16 * (t * EH_EVAL_STATS + k) + n] : 0.0f); if (lane == 0) lds[wave * NS + t * EH_EVAL_STATS + k] = v; }
+        __syncthreads();
+        if (tid < EH_EVAL_STATS * net.T) {
+            float s = 0.0f;
+            for (int w = 0; w < EH_SEQ_NW; ++w) s += lds[w * NS + tid];
+            a.slab[(long long)blockIdx.x * a.n_acc + tid] = s;
+        }
+    } else if constexpr (MODE == EH_SEQ_EVAL) {
 #pragma unroll
         for (int k = 0; k < EH_EVAL_STATS; ++k) { const float v = eh_wave_sum(est[k]); if (lane == 0) lds[wave * EH_EVAL_STATS + k] = v; }
         __syncthreads();
@@ -604,9 +757,10 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
         float* const row = lds;
         for (int e = tid; e < a.n_acc; e += 64 * EH_SEQ_NW) row[e] = 0.0f;
         __syncthreads();
-        float sums[4], gps[EH_MAX_PARAMS];
+        constexpr int NSUM = MT ? 1 + EH_MAX_TARG : 4;
+        float sums[NSUM], gps[EH_MAX_PARAMS];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) sums[k] = eh_wave_sum(est[k]);
+        for (int k = 0; k < NSUM; ++k) sums[k] = eh_wave_sum(MT ? (g == 0 ? MTA[16 * k + n] : 0.0f) : est[k]);
 #pragma unroll
         for (int j = 0; j < EH_MAX_PARAMS; ++j) gps[j] = eh_wave_sum(gp[j]) * a.meta[EH_IMG_DPHI + j];
         // a weight block: register r of lane (n, g) is row r0 + 4g + r (below `lim`), column c0 + n (below `ncol`) of a column-major matrix of `ld` rows
@@ -667,7 +821,12 @@ __global__ __launch_bounds__(64 * EH_SEQ_NW) void eh_seq_kernel(const EhNet net,
                 for (int e = lane; e < NG * RH; e += 64)       // b_ih and b_hh: the same gradient, written to both
                     if (e % RH < H) { const int o = (e / RH) * H + e % RH; row[a.off[EH_SEQ_BIH] + o] += GB[e]; row[a.off[EH_SEQ_BHH] + o] += GB[e]; }
                 if (lane == 0) {
-                    row[net.n_theta] += sums[0]; row[net.n_theta + 1] += sums[3]; row[net.n_theta + 2] += sums[1]; row[net.n_theta + 3] += sums[2];
+                    if constexpr (MT) {                        // [loss | n_1 .. n_T]: the weights were exact, the sums are final (Sy, Syy behind them stay 0, nobody reads them)
+                        row[net.n_theta] += sums[0];
+#pragma unroll
+                        for (int t = 0; t < EH_MAX_TARG; ++t)
+                            if (t < net.T) row[net.n_theta + 1 + t] += sums[1 + t];
+                    } else { row[net.n_theta] += sums[0]; row[net.n_theta + 1] += sums[3]; row[net.n_theta + 2] += sums[1]; row[net.n_theta + 3] += sums[2]; }
 #pragma unroll
                     for (int j = 0; j < EH_MAX_PARAMS; ++j)
                         if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL) row[net.g_off + (int)((net.par_idx >> (4 * j)) & 15u)] += gps[j];

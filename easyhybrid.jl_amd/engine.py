@@ -86,7 +86,11 @@ class HybridEngine:
         self._lib = L.lib()
         self._h = C.c_void_p()
         self.desc = desc
-        st = self._lib.eh_create(C.byref(desc), C.byref(self._h))
+        # (a sequence model with several targets is asked for by name: eh_create keeps refusing that descriptor)
+        seq = desc.activation == L.EH_ACT_PER_NET and desc.n_nets == 0 and any(
+            desc.net_activation[l] in (L.EH_LAYER_LSTM, L.EH_LAYER_GRU) or L.EH_LAYER_RNN <= desc.net_activation[l] <= L.EH_LAYER_RNN + 4 for l in range(min(desc.n_hidden, L.EH_MAX_HIDDEN)))
+        create = self._lib.eh_create_seq_targets if seq and desc.n_targets > 1 else self._lib.eh_create
+        st = create(C.byref(desc), C.byref(self._h))
         if st != L.EH_OK:
             self._h = C.c_void_p()
             _raise(st, self._lib.eh_last_error(None).decode())

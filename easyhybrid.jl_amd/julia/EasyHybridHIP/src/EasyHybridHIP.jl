@@ -372,7 +372,11 @@ end
 function HybridEngine(m::SingleNNHybridModel; device::Integer = 0)
     d = Ref(descriptor(m; device))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    st = @ccall LIB[].eh_create(d::Ref{EhModelDesc}, h::Ref{Ptr{Cvoid}})::Int32
+    # (a sequence model with several targets is asked for by name: eh_create keeps refusing that descriptor)
+    recurrent(a) = a == EH_LAYER_LSTM || a == EH_LAYER_GRU || EH_LAYER_RNN <= a <= EH_LAYER_RNN + 4
+    seq = d[].activation == 5 && d[].n_nets == 0 && any(recurrent, d[].net_activation[1:min(d[].n_hidden, 8)])
+    st = (seq && d[].n_targets > 1) ? (@ccall LIB[].eh_create_seq_targets(d::Ref{EhModelDesc}, h::Ref{Ptr{Cvoid}})::Int32) :
+                                      (@ccall LIB[].eh_create(d::Ref{EhModelDesc}, h::Ref{Ptr{Cvoid}})::Int32)
     st == 0 || error(unsafe_string(@ccall LIB[].eh_last_error(C_NULL::Ptr{Cvoid})::Cstring))
     e = HybridEngine(h[], m, n_theta(m))
     finalizer(x -> (@ccall LIB[].eh_destroy(x.h::Ptr{Cvoid})::Int32), e)
@@ -608,6 +612,9 @@ Sequence models (`hidden_layers = Chain(Recurrence(LSTMCell(I => H)))`, descript
 becomes the window of `input_window` rows that starts at row `starts[i]` (0-based) of the series `set_data!` loaded into that split
 (`src/data/sequences.jl:203-229`).  From then on `first`, `count` and the minibatch indices of the step, epoch, loss-and-gradient, eval and
 forward calls count windows, and the prediction arrays hold `count * output_window` values as `[window][j]`.
+Several targets (around a model with several outputs, up to four, in any order over the outputs): every target has its own prediction
+array, metrics and NaN mask, and `set_training_loss!` takes `PerTarget` of `:mse`, `:mae`, `:nseLoss`; the library refuses `:rmse` on
+several targets, the two-pass and recorded losses, an `extra_loss` of the predictions, `dp_*` and graph capture with the reason.
 """
 set_sequences!(e::HybridEngine, starts::Vector{Int32}; split = EH_SPLIT_TRAIN, input_window::Integer = 10, output_window::Integer = 1, lead_time::Integer = 1) =
     check(e, @ccall LIB[].eh_set_sequences(e.h::Ptr{Cvoid}, split::Int32, input_window::Int32, output_window::Int32, lead_time::Int32,

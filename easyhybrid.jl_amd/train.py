@@ -644,6 +644,27 @@ class _EarlyUpload:
 SEQUENCE_DEFAULTS = dict(input_window=10, output_window=1, output_shift=1, lead_time=1)      # split_data.jl:28
 
 
+SEQUENCE_LOSSES = ("mse", "mae", "nseLoss")      # what a sequence model trains on, per target (one target: rmse as well)
+
+
+def _sequence_loss_check(tl, n_targets: int):
+    """training_loss of a sequence model -- one kind, or PerTarget((l_1, ..., l_T)) -- against the losses its step kernel has: the others
+    are refused here, with the reason, before an engine is made"""
+    from .engine import PerTarget
+    kinds = list(tl.losses) if isinstance(tl, PerTarget) else (list(tl) if isinstance(tl, (list, tuple)) and tl and not callable(tl[0]) else [tl])
+    for k in kinds:
+        if callable(k) or (isinstance(k, (list, tuple)) and k and callable(k[0])):
+            raise NotImplementedError(f"sequence models: a function as training loss is a recorded loss, which is not built for them (have {list(SEQUENCE_LOSSES)})")
+        if k == "rmse" and n_targets == 1 and len(kinds) == 1:
+            continue
+        if k == "rmse":
+            raise NotImplementedError(f"sequence models: training loss 'rmse' on {n_targets} targets needs a pass ahead of the step (its scale cannot be applied "
+                                      f"after it), which is not built for them (have {list(SEQUENCE_LOSSES)})")
+        if k not in SEQUENCE_LOSSES:
+            raise NotImplementedError(f"sequence models: training loss {k!r} needs the batch moments of the predictions (two passes), which is not built for them "
+                                      f"(have {list(SEQUENCE_LOSSES)})")
+
+
 def _sequence_splits(model, data, cfg: DataConfig, rng: Optional[np.random.Generator] = None):
     """sequence models (split_data.jl:26-78): the whole series (no row is dropped), its windows filtered, and the surviving WINDOWS split
     by split_data_at / shuffleobs -> ((X, forcings), targets), train windows, validation windows.  Both splits index the same series."""
@@ -1073,6 +1094,8 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         raise ValueError("sequence_kwargs: the model has no Recurrence layer (hidden_layers = Chain(Recurrence(LSTMCell(I, H))))")
     if is_seq and (dist_run or xfn is not None):
         raise NotImplementedError("sequence models: data parallelism and an extra_loss of the predictions are not built")
+    if is_seq:
+        _sequence_loss_check(tc.training_loss, len(model.targets))
     wtr = wva = None
     if is_seq:
         ((xs, fs), ys), wtr, wva = _sequence_splits(model, data, dc, rng)

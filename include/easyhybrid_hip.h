@@ -65,7 +65,9 @@ typedef enum eh_activation { EH_ACT_TANH = 0, EH_ACT_SIGMOID = 1, EH_ACT_RELU = 
 /* A value of net_activation[l] beside the eh_activation ids (activation == EH_ACT_PER_NET, n_nets == 0): hidden layer l is not a Dense
  * layer but Recurrence(LSTMCell(hidden[l-1] -> hidden[l])), return_sequence = true (NNModels.jl:171-211).  Built: exactly one such layer,
  * at l = 1 of n_hidden = 3 with hidden[2] == hidden[1] -- the chain Dense(P -> I, act) -> LSTM(I -> H) -> Dense(H -> H, act) -> Dense(H -> K)
- * the reference makes of `Chain(Recurrence(LSTMCell(I => H)))`, I and H up to 32, one target, fp32.  Flat theta: Dense-in weight (I x P,
+ * the reference makes of `Chain(Recurrence(LSTMCell(I => H)))`, I and H up to 32, up to EH_MAX_TARG targets (several: through
+ * eh_create_seq_targets, around a model with several outputs -- FluxPartModelQ10 or a recorded closure --, every target_output naming one
+ * of them, in any order), fp32.  Flat theta: Dense-in weight (I x P,
  * column-major), bias; LSTM weight_ih (4H x I), weight_hh (4H x H), bias_ih (4H), bias_hh (4H), gate blocks [i | f | g | o]; head Dense;
  * output Dense; globals.  Such a handle works on windows of its records: eh_set_sequences.
  * The cell may also be a GRUCell (EH_LAYER_GRU: weight_ih (3H x I), weight_hh (3H x H), bias_ih (3H), bias_hh (3H), gate blocks
@@ -225,6 +227,15 @@ const char* eh_last_error(const eh_handle* h);
 
 /* constructHybridModel(...) -> device-side model + workspace (src/models/GenericHybridModel.jl:89-140) */
 int32_t eh_create(const eh_model_desc* desc, eh_handle** out);
+/* eh_create for every descriptor, and the one entry point that takes a SEQUENCE model (EH_LAYER_LSTM / GRU / RNN) with 2..EH_MAX_TARG targets
+ * around a model with several outputs.  The split has no technical reason: eh_create could take such a descriptor.  It exists because the
+ * tests of the one-target sequence kernels pin eh_create's EH_EUNSUPPORTED for exactly that descriptor (FluxPartModelQ10 or a closure with
+ * n_targets = 2) and the change that built several targets was to leave every existing test as it was; once those tests may be updated the
+ * two entry points fold into eh_create.  Refused here too, with the reason: several targets around a model with one output, a
+ * target_output the model does not have.
+ * (Added without a new EH_ABI_VERSION, like the entry points before it: nothing that existed changes, and eh_version() == 4 is what
+ * callers -- and the suite -- check for.) */
+int32_t eh_create_seq_targets(const eh_model_desc* desc, eh_handle** out);
 int32_t eh_destroy(eh_handle* h);
 int32_t eh_n_theta(const eh_handle* h, int64_t* n);
 
@@ -253,7 +264,9 @@ int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, cons
  * 0 .. n - input_window - lead_time.  From then on `first`, `count` and `idx` of eh_train_step, eh_train_epoch (which shuffles windows),
  * eh_loss_and_grad, eh_eval and eh_forward count windows of that split, n_valid counts valid (window, j) pairs, and the prediction /
  * parameter arrays of eh_forward / eh_eval hold count * output_window values as [window][j]: the head runs only at the steps the loss
- * reads.) */
+ * reads.  Several targets: target t is read at column t of the same row, with its own NaN mask; yhat[t] and the metrics of target t are
+ * its own, and n_valid sums the valid (window, j) pairs of all targets.  Not built for sequence handles: eh_graph_*, eh_dp_*, recorded
+ * losses, eh_set_target_roles with an extra-loss entry, the two-pass losses.) */
 int32_t eh_set_sequences(eh_handle* h, int32_t split, int32_t input_window, int32_t output_window, int32_t lead_time,
                          const int32_t* starts, int64_t n_windows);
 
@@ -620,7 +633,9 @@ int32_t eh_set_target_loss_program(eh_handle* h, int32_t target, const uint32_t*
 /* loss_spec = PerTarget((l_1, ..., l_T)) (src/losses/compute_loss.jl:128-145): target t is trained on its own loss, the total is
  * their sum (agg = sum).  Built per target: EH_LOSS_MSE, EH_LOSS_MAE, EH_LOSS_NSELOSS -- the losses whose per-sample weight is a
  * function of the targets alone (1 / n_t, 1 / n_t, 1 / sum (y - mean y)^2), found by a pre-pass; n must equal n_targets.  The same
- * three are what eh_set_option("training_loss") accepts on a multi-target model. */
+ * three are what eh_set_option("training_loss") accepts on a multi-target model.  Sequence handles (EH_LAYER_LSTM / GRU / RNN) take
+ * exactly these three per target -- the pre-pass counts over the minibatch's windows, a row that several windows read once per window;
+ * rmse on several targets, pearson / kge / pbkge and EH_LOSS_PROGRAM are EH_EUNSUPPORTED there, with the reason. */
 int32_t eh_set_target_losses(eh_handle* h, const int32_t* kinds, int32_t n);
 
 /* extra_loss as a function of the PREDICTIONS (src/losses/compute_loss.jl:31-34; the reference's own test:

@@ -13,7 +13,12 @@ One JSON line per window count.
 minimum and maximum (the spread the comparison has to be read against).  profiles/r11/seq_closure_step.txt.
 --cell lstm|gru|rnn: the recurrent cell of every mode above (RNNCell with tanh); default lstm.
   python tools/bench_seq.py --cells lstm,gru,rnn [--steps 300] [--warmup 20] [--rounds 5] [--windows 128,16384] [--output-windows 1,10]
---cells: the listed cells around the registry's RbQ10, ALTERNATED in one process as --closure alternates its three; same output."""
+--cells: the listed cells around the registry's RbQ10, ALTERNATED in one process as --closure alternates its three; same output.
+  python tools/bench_seq.py --targets 3 [--steps 300] [--warmup 20] [--rounds 5] [--windows 128,16384] [--output-windows 1,10]
+--targets N: 1 .. N targets (mse each) around the registry's FluxPartModelQ10 -- "fluxpart_T1" is the one-target kernel, the others the
+kernels of several targets behind their count pre-pass -- and N targets around the three-output closure of the tests (flux3) compiled at
+run time, ALTERNATED in one process as above; per line also the cost of a further target per launch and per head step, against the same
+build's fluxpart_T1.  profiles/r22/seq_multitarget_step.txt."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -34,6 +39,7 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--output-windows", default="1,10")
 ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"])
 ap.add_argument("--cells", default=None, help="comma-separated cells to alternate")
+ap.add_argument("--targets", type=int, default=0, help="1 .. N targets around FluxPartModelQ10, N around the compiled closure flux3")
 a = ap.parse_args()
 
 
@@ -95,6 +101,73 @@ def closure_bench():
                 eng.close()
 
 
+def targets_bench():
+    from tests import seq_closure_twin as ct
+    W, lam, N = a.input_window, 1, a.targets
+    if not 1 <= N <= 3:
+        raise SystemExit("--targets: 1..3 (FluxPartModelQ10 and flux3 have three outputs)")
+    counts = [int(c) for c in (a.windows if a.windows != "128,1024,16384" else "128,16384").split(",")]
+    nb = 4
+    rows = nb * max(counts) + W + lam
+    rng = np.random.default_rng(1)
+    X = (0.6 * rng.standard_normal((2, rows))).astype(np.float32)
+    frc = {"SW_IN": rng.uniform(0.0, 800.0, rows).astype(np.float32), "TA": (10 + 8 * rng.standard_normal(rows)).astype(np.float32), "vpd": rng.uniform(0.0, 30.0, rows).astype(np.float32)}
+    frc.update(sw=frc["SW_IN"], ta=frc["TA"])
+    ys = []
+    for _ in range(3):                                # noise with 5 % gaps of its own per target: the step's time does not depend on the values
+        v = (3.0 + rng.standard_normal(rows)).astype(np.float32)
+        v[rng.random(rows) < 0.05] = np.nan
+        ys.append(v)
+    starts = np.arange(rows - W - lam + 1, dtype=np.int32)
+    chain = lambda: eh.Chain(eh.Recurrence(CELL[a.cell]()))
+    flux3 = eh.models.resolve_mech(ct.flux3_np, list(ct.FLUX3_TABLE), list(ct.FLUX3_FORCINGS), list(ct.FLUX3_OUTPUTS))
+    variants = [(f"fluxpart_T{T}", eh.constructHybridModel(["x0", "x1"], ["SW_IN", "TA"], ["NEE", "GPP", "RECO"][:T], eh.FluxPartModelQ10, dict(ct.FLUXPART_TABLE), ["RUE", "Rb"],
+                                                           ["Q10"], hidden_layers=chain(), activation="tanh", scale_nn_outputs=True), None, T) for T in range(1, N + 1)]
+    variants.append((f"flux3_compiled_T{N}", eh.constructHybridModel(["x0", "x1"], list(ct.FLUX3_FORCINGS), list(ct.FLUX3_OUTPUTS)[:N], flux3, dict(ct.FLUX3_TABLE), ["rue", "rb"],
+                                                                     ["q10"], hidden_layers=chain(), activation="tanh", scale_nn_outputs=True), 1, N))
+    for B in counts:
+        for ow in [int(o) for o in a.output_windows.split(",")]:
+            engs = []
+            for name, model, jit, T in variants:
+                eng = model.engine(0)
+                if jit is not None:
+                    eng.set_option("jit", jit)
+                eng.set_data(0, X, [frc[f] for f in model.forcing], ys[:T])
+                eng.set_sequences(0, W, ow, lam, starts)
+                eng.set_params(model.initialparameters(1))
+                eng.opt_init("RMSProp", 0.01)
+                for s in range(a.warmup):
+                    eng.train_step((s % nb) * B, B, want_loss=False)
+                eng.synchronize()
+                if eng.jit_status()[0] != (jit or 0):
+                    raise SystemExit(f"{name}: eh_jit_status reports {eng.jit_status()[0]} compiled kernels: {eng.jit_status()[1][:400]}")
+                engs.append(eng)
+            times = {v[0]: [] for v in variants}
+            for r in range(a.rounds):
+                for (name, *_), eng in zip(variants, engs):
+                    t0 = time.perf_counter()
+                    for s in range(a.steps):
+                        eng.train_step(((r * a.steps + s) % nb) * B, B, want_loss=False)
+                    eng.synchronize()
+                    times[name].append(1e6 * (time.perf_counter() - t0) / a.steps)
+            out = {"windows": B, "input_window": W, "output_window": ow, "I": a.width, "H": a.width, "cell": a.cell, "rounds": a.rounds, "steps": a.steps}
+            med = {}
+            for name, *_ in variants:
+                t = sorted(times[name])
+                med[name] = t[len(t) // 2]
+                out[name] = {"us_per_step_median": med[name], "min": t[0], "max": t[-1]}
+            for T in range(2, N + 1):                 # against the same build's one-target step: per launch, and per head step and further target
+                d = med[f"fluxpart_T{T}"] - med["fluxpart_T1"]
+                out[f"further_targets_T{T}"] = {"us_per_launch": d, "us_per_head_step_and_target": d / (ow * (T - 1))}
+            out["final_loss"] = {name: eng.train_step(0, B) for (name, *_), eng in zip(variants, engs)}
+            print(json.dumps(out), flush=True)
+            for eng in engs:
+                eng.close()
+
+
+if a.targets:
+    targets_bench()
+    sys.exit(0)
 if a.closure or a.cells:
     closure_bench()
     sys.exit(0)
