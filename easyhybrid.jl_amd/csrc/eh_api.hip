@@ -2974,7 +2974,7 @@ int32_t eh_debug_stamps(eh_handle* h, uint64_t* out, int32_t n) {
     if (!h || !out || n < 0 || n > EH_STAMP_WORDS) return EH_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->stamps) {   // first call arms the buffer; later calls read it
-        HIPCHK(h, hipMalloc(&h->stamps, EH_STAMP_WORDS * sizeof(unsigned long long)));      // (words 32 on: the ordered step's hand-off, EH_ORD_ST_TAIL)
+        HIPCHK(h, hipMalloc(&h->stamps, EH_STAMP_WORDS * sizeof(unsigned long long)));      // (behind the step's own stamps: the ordered step's hand-off, EH_ORD_ST_PRO / EH_ORD_ST_TAIL)
         HIPCHK(h, hipMemset(h->stamps, 0, EH_STAMP_WORDS * sizeof(unsigned long long)));
         memset(out, 0, (size_t)n * sizeof(uint64_t));
         lean_refresh(h);                     // (diagnostics are outside the lean kernels' contract)

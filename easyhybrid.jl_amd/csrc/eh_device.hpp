@@ -175,8 +175,9 @@ struct EhP2P {
 // "Ordered" fused-update step (EH_MODE_TRAIN_ORD, "fused_update" 2 on minibatches of several workgroups): ONE kernel per step, and the
 // same bits as the deterministic step + eh_reduce_kernel<APPLY, 16> pair.  That reduce has 16 row groups: thread q of a column sums the
 // slab rows q, q + 16, q + 32, ... in ascending order from 0, and the column's total is the 16 partials summed in q order from 0.  Here
-// workgroup b stores its row write-through (16-byte sc1 stores) into a row slot and takes a ticket on the counter of its group g = b % 16
-// (a 128-byte line of its own); the workgroup whose add comes last in its group folds the group's rows in that same order into group row g.  The
+// workgroup b takes a ticket on the counter of its group g = b % 16 (a 128-byte line of its own) behind the first barrier of its workgroup
+// reduction and, once its row is staged, stores it write-through (16-byte sc1 stores) into a row slot; the workgroup whose add came last
+// in its group (the folder: it stores no row) folds the group's rows in that same order into group row g (eh_ord_publish).  The
 // next step's prologue sums the 16 group rows in order (absent groups: + 0, as the pair's idle row groups) and folds the rows' scalars
 // [S | n | Sy | Syy] with the reduce kernel's butterfly (its first two levels done per group by the last arrivers, below), then applies the update as the mode-1 prologue does.  Nobody waits for
 // anybody: no spin, no fence.  Two slots of each (parity `slot`): a fast workgroup of step s + 1 rewrites its row while a slow one
@@ -207,10 +208,14 @@ struct EhOrd {
 #define EH_ORD_EMPTY 0x7FA5A5A5u
 #define EH_ORD_DEADLINE_TICKS 200000000ull      // 2 s of the 100 MHz wall clock for a row store that has been issued to land
 // Diagnostic builds (-DEH_STAMPS, tools/stamps_ord.py): the hand-off, which workgroup 0's stamps do not see.  Thread 0 of every group's
-// last arriver records (shader clock, wall clock) pairs at stamps[EH_ORD_ST_TAIL + 10 g ...]: [0] its row stored, [1] about to take the
-// ticket, [2] the ticket's answer known to the workgroup, [3] the group's rows read and folded, [4] the group row stored (a wait only
-// this build has); workgroup 0 at stamps[EH_ORD_ST_PRO ...]: [0] image staged, [1] the scalars folded (both by the wave that folds).
-enum { EH_ORD_ST_TAIL = 32, EH_ORD_ST_PRO = EH_ORD_ST_TAIL + 10 * EH_ORD_GROUPS, EH_STAMP_WORDS = 256 };
+// folder records (shader clock, wall clock) pairs at stamps[EH_ORD_ST_TAIL + 32 g ...]: [0] its row staged, [1] behind the staged
+// barrier, the election known to the workgroup (EH_AB_ORD_TICKET_LATE: behind the ticket's barrier), [2] the loads of the group's rows
+// issued, [3] the first pass folded, [4] the wait rounds over (= [3] without one), [5] the group row stored (a wait only this build
+// has), [6] EH_AB_ORD_TICKET_LATE only: the row's stores issued, about to take the ticket.  Words 16 ... 23: per wave of the folder that
+// folds gradient vectors, (largest number of wait rounds of a lane) | (rows met under the marker, bit k = row k of the group) << 16;
+// word 24: the same of the wave that folds the scalar vector.  Workgroup 0 at stamps[EH_ORD_ST_PRO ...]: [0] image staged, [1] the
+// scalars folded (both by the wave that folds).
+enum { EH_ORD_ST_PRO = 32 + 10 * EH_ORD_GROUPS, EH_ORD_ST_TAIL = 256, EH_ORD_ST_TAILW = 32, EH_STAMP_WORDS = EH_ORD_ST_TAIL + EH_ORD_ST_TAILW * EH_ORD_GROUPS };
 #ifdef EH_STAMPS
 #define EH_ORD_TICK(ts, p)                                                                            \
     do {                                                                                               \
@@ -334,6 +339,29 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t eh_ord_rsrc(const float* base,
 __device__ __forceinline__ f32x4 eh_ord_ld16(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16)); }
 __device__ __forceinline__ void eh_ord_st16(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_ord, v), r, off, 0, 16); }
 enum { EH_ORD_OOB = 0x7FFFFFF0 };       // (a byte offset past any row buffer: the load returns 0)
+// The wait rounds of the group's folder (eh_ord_publish): the same 16-byte sc1 load, INTO the registers that hold the vector already and
+// only under the lanes that execute it.  Written as a builtin under a branch, sixteen of them made the compiler keep a second copy of
+// the sixteen rows across the loop (176 VGPRs where the kernel has 110, 2 waves per SIMD where it has 4); the tied operand keeps them in
+// place.  The compiler tracks no wait for a load inside asm: eh_ord_reld_wait behind the batch, through which every row passes.
+// (The address is formed inside, base + off + K stride bytes with off + K stride < 2^32: sixteen addresses formed outside were hoisted
+//  out of the loop and held sixteen registers more through the whole tail.)
+template <int K> __device__ __forceinline__ void eh_ord_reld16(f32x4& q, const float* base, unsigned off, unsigned stride) {
+    unsigned t;
+    asm volatile("v_mul_lo_u32 %1, %4, %5\n\tv_add_u32 %1, %1, %3\n\tglobal_load_dwordx4 %0, %1, %2 sc1"
+                 : "+v"(q), "=&v"(t) : "s"(base), "v"(off), "s"(stride), "n"(K) : "memory");
+}
+// rows K ... NK - 1 of the group, those whose bit in `pend` is set
+template <int K, int NK> __device__ __forceinline__ void eh_ord_reld_rows(f32x4 (&r)[NK], unsigned pend, const float* base, unsigned off, unsigned stride) {
+    if constexpr (K < NK) {
+        if ((pend >> K) & 1u) eh_ord_reld16<K>(r[K], base, off, stride);
+        eh_ord_reld_rows<K + 1>(r, pend, base, off, stride);
+    }
+}
+__device__ __forceinline__ void eh_ord_reld_wait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& a4, f32x4& a5, f32x4& a6, f32x4& a7,
+                                                 f32x4& a8, f32x4& a9, f32x4& a10, f32x4& a11, f32x4& a12, f32x4& a13, f32x4& a14, f32x4& a15) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7),
+                                        "+v"(a8), "+v"(a9), "+v"(a10), "+v"(a11), "+v"(a12), "+v"(a13), "+v"(a14), "+v"(a15) :: "memory");
+}
 // The consumer of a pending ordered step -- the next ordered step's prologue or eh_ord_flush_kernel -- writes EH_ORD_EMPTY back into the
 // words of that step's rows (slot `slot ^ 1`, rows [0, prev_grid)): workgroup b takes rows b, b + nblk, ...; 16-byte stores over
 // [0, soff + 4): the gradient, its padding and the scalar vector, which the group's last arriver reads in-kernel like a gradient vector.
@@ -354,36 +382,132 @@ __device__ __forceinline__ void eh_ord_reset(const EhOrd& o, int b, int nblk, in
     for (int r = b; r < o.prev_grid; r += nblk)
         for (int v = tid; v < nv; v += nthr) eh_ord_st16(rr, 4 * (((o.slot ^ 1) * EH_ORD_ROWS + r) * o.rs) + 16 * v, ev);
 }
+// Where the group's ticket is taken (through EH_JIT_DEFINES on run-time compiled kernels, for the A/B of one source): 14 = behind the
+// first barrier of the workgroup reduction (the default), 13 = behind the wave sums in front of that barrier, 8 = at the end of the
+// tile; EH_AB_ORD_TICKET_LATE (0) = behind the row stores with a barrier of its own behind it, as it was.
+#if defined(EH_AB_ORD_TICKET_LATE)
+#define EH_ORD_TICKET_AT 0
+#elif defined(EH_AB_ORD_TICKET_AT)
+#define EH_ORD_TICKET_AT EH_AB_ORD_TICKET_AT
+#else
+#define EH_ORD_TICKET_AT 14
+#endif
+#if EH_ORD_TICKET_AT != 0 && EH_ORD_TICKET_AT != 8 && EH_ORD_TICKET_AT != 13 && EH_ORD_TICKET_AT != 14
+#error "EH_AB_ORD_TICKET_AT is 8, 13 or 14"
+#endif
+// EH_AB_ORD_FOLDER_SLEEP = n (likewise): the folder's pause in front of its row loads, n x 64 cycles (eh_ord_publish); 0 = none
+#ifdef EH_AB_ORD_FOLDER_SLEEP
+#define EH_ORD_FOLDER_SLEEP EH_AB_ORD_FOLDER_SLEEP
+#else
+#define EH_ORD_FOLDER_SLEEP 5
+#endif
+#if defined(EH_TEST_ORD_LATE_ROW) && !defined(__HIPCC_RTC__)
+#error "EH_TEST_ORD_LATE_ROW is for kernels compiled at run time (tests/test_gpu_ordered_ticket.py)"
+#endif
+// The election, held early: ONE lane of wave 0 adds to its group's counter (relaxed, agent scope) at place AT of the step -- the place
+// the build has chosen, nothing elsewhere -- and keeps the answer in a register; nobody waits for it here.  eh_ord_publish reads it.
+template <int AT> __device__ __forceinline__ void eh_ord_ticket(const EhOrd& o, int tid, unsigned& tk) {
+    if constexpr (AT == EH_ORD_TICKET_AT) {
+        if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+            if (tid == 0) {
+                // (the index through a vector register the compiler cannot see through: an add at a uniform address it rewrites into
+                //  one add per wave and a readfirstlane of the answer -- a wait for the round trip right here)
+                unsigned gc = 32 * (blockIdx.x % EH_ORD_GROUPS);
+                asm("" : "+v"(gc));
+                tk = __hip_atomic_fetch_add(o.cnt + gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
 // Called by every thread of every workgroup once its row is staged in LDS at `row`, in its global layout (gradient at [0, n_theta), the
-// scalars at soff).  The hand-off: a workgroup barrier, then wave 0 stores the row write-through as 16-byte vectors -- the gradient's
-// ceil(n_theta / 4) and the scalar vector -- and, with no wait for them, ONE lane adds to the group's counter (agent scope).  The
-// workgroup whose add returns gsz - 1 reads the other rows of its group with 16-byte sc1 loads, behind a barrier that the adding wave
-// joins; its own row it takes from LDS.  Every row store of the group has been issued by then, but some may still be on their way: a
-// gradient word that still holds EH_ORD_EMPTY is read again, its whole vector (a torn read included), until it holds the sum (a deadline
-// turns a store that never lands into the error word).  The padding words past n_theta take no part in the check.  No fence, no drain.
-// The fold is the one of eh_reduce_kernel's row groups, four elements per thread.  The rows' scalar vector is read the same way, under
-// the same marker with all four words checked: the last wave folds the group's rows into the four block partials of the reduce kernel's
-// butterfly (below) and stores them at part[slot][q][group].  Group row and partials go to the next kernel on the stream,
-// whose start makes them visible; the rows stay as they are until that kernel's workgroups reset them (eh_ord_reset).
-__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, const float* row, float* flag, unsigned long long* st) {
+// scalars at soff); tk is thread 0's ticket (eh_ord_ticket).  The workgroup whose add came last in its group (it returned gsz - 1) is the
+// group's folder.  Thread 0 puts that into the LDS word `flag` -- the one wait for the add's answer, 3-5 k cycles behind the add -- and
+// sets the counter back; then ONE workgroup barrier: the row is staged and the election known.  Behind it a workgroup that is not the
+// folder has wave 0 store its row write-through as 16-byte vectors -- the gradient's ceil(n_theta / 4) and the scalar vector -- and is
+// finished.  The folder, behind a short pause for the others' stores (EH_ORD_FOLDER_SLEEP, below), issues the 16-byte sc1 loads of
+// the other rows of its group; its own row it takes from LDS and does NOT
+// store: nothing but the group's folder reads a row (the next prologue and eh_ord_flush_kernel read group rows and block partials
+// only) before eh_ord_reset overwrites it.  (EH_AB_ORD_ROW_SCALARS, whose prologue reads every row's scalars: stored behind the loads.)
+// The election says who took the ticket last, not whose row has landed: the folder regularly meets a row that is still on its way, by
+// less than a store's flight time.  Every word of a row is under EH_ORD_EMPTY, so the first pass folds what it has loaded and looks at
+// the words only if a sum among the words < n_theta is a NaN; then rounds: the vectors of this thread that still hold the marker (a torn
+// read included) are loaded again, all of them together, behind an s_sleep, and the fold is made again in the same k order from + 0 (a
+// deadline turns a store that never lands into the error word).  A genuine NaN finds no marker and passes after that one look.  The
+// padding words past n_theta take no part in the check.  No fence, no drain.  The fold is the one of eh_reduce_kernel's row groups, four
+// elements per thread.  The rows' scalar vector is read the same way, under the same marker with all four words checked: the last wave
+// folds the group's rows into the four block partials of the reduce kernel's butterfly (below) and stores them at
+// part[slot][q][group].  Group row and partials go to the next kernel on the stream, whose start makes them visible; the rows stay as
+// they are until that kernel's workgroups reset them (eh_ord_reset).
+// Why the folder's wait cannot deadlock: a workgroup takes its ticket AFTER its tile (places 8, 13, 14 all lie behind it).  So every
+// workgroup the folder waits for -- the others that have added to the group's counter -- has been dispatched, is resident, and has
+// nothing left between its add and its row stores that waits for another workgroup: the workgroup reduction (its own barriers) and this
+// function up to the stores.  The folder never waits for a workgroup that has not been dispatched, whatever the grid and however few
+// workgroups fit the device at once.  A ticket in front of the tile, or a fixed folder (say the group's first member), would lose this:
+// the folder could then sit on a compute unit waiting for a member that needs that unit to start.  The deadline and the host-mapped
+// error word remain as the backstop.
+// (EH_TEST_ORD_LATE_ROW = k, tests only: member k of every group waits some 20 us of the wall clock behind the staged barrier, in front
+//  of its row stores, so that its group's folder certainly meets the marker.)
+__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, const float* row, float* flag, unsigned long long* st, unsigned tk) {
 #ifdef EH_STAMPS
-    unsigned long long ts[10];
+    unsigned long long ts[16];
+    unsigned w_rounds = 0, w_late = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) ts[k] = 0;
 #endif
     EH_ORD_TICK(ts, 0);
     const unsigned gi = blockIdx.x % EH_ORD_GROUPS, gsz = (gridDim.x - gi + EH_ORD_GROUPS - 1) / EH_ORD_GROUPS;      // (ahead of the barrier)
     const __amdgpu_buffer_rsrc_t rr = eh_ord_rsrc(o.rows, 2 * EH_ORD_ROWS * o.rs);
     const int nv = (nth + 3) >> 2;         // the gradient's vectors; the scalar vector follows at soff
-#ifdef EH_AB_ORD_PARENT
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (diagnostic A/B: the drain of the hand-off before the sentinel words)
-#endif
-    __syncthreads();        // the row is staged
-    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+    const int kown = blockIdx.x / EH_ORD_GROUPS;
+    auto store_row = [&]() {               // (wave 0)
         const int rb = 4 * ((o.slot * EH_ORD_ROWS + (int)blockIdx.x) * o.rs);
         for (int v = tid; v <= nv; v += 64) {
             const int w = v < nv ? 4 * v : o.soff;
             eh_ord_st16(rr, rb + 4 * w, *(const f32x4*)&row[w]);
         }
-        EH_ORD_TICK(ts, 1);
+    };
+    auto late_row = [&]() {                // (wave 0)
+#ifdef EH_TEST_ORD_LATE_ROW
+        if (kown == (EH_TEST_ORD_LATE_ROW)) {
+            const unsigned long long t0 = wall_clock64();
+            while (wall_clock64() - t0 < 2000ull) __builtin_amdgcn_s_sleep(8);       // (20 us of the 100 MHz clock: 1e-5 of the deadline)
+        }
+#endif
+    };
+#ifdef EH_AB_ORD_PARENT
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (diagnostic A/B: the drain of the hand-off before the sentinel words)
+#endif
+#if EH_ORD_TICKET_AT != 0
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+        if (tid == 0) {
+            const bool last = tk == gsz - 1;
+            if (last) __hip_atomic_store(o.cnt + 32 * gi, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            flag[0] = last ? 1.0f : 0.0f;
+        }
+    }
+    __syncthreads();        // the row is staged, the election known
+    EH_ORD_TICK(ts, 1);
+    const bool folder = flag[0] != 0.0f;
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+        late_row();
+        if (!folder) store_row();
+    }
+    if (!folder) return;
+    // The folder is through the staged barrier when the slowest member of its group has only just issued its row stores (the
+    // workgroups of a step run in lockstep, and the election follows the order at the first reduction barrier): asking for the rows
+    // at once it met the marker in 47 % of all folders, and one wait round -- a sleep, a second load round trip, a second fold -- is
+    // 1.6 us of a 9.6 us step.  So it lets the stores fly first, EH_ORD_FOLDER_SLEEP x 64 cycles: what the late ticket's round trip
+    // (1.1 k cycles) gave for free, cut to what the stores need.  Measured on the headline step: 0 -> 11.2 us, 2 -> 10.9, 3 -> 10.0,
+    // 4 -> 9.33, 5 -> 9.29, 6 -> 9.35, 8 -> 9.39, 12 -> 9.48, 16 -> 9.59; the late ticket 9.63 (profiles/r22/ord_ticket_ab.txt).
+    // A row that is later still costs a wait round, never a wrong sum.
+    if (EH_ORD_FOLDER_SLEEP > 0) __builtin_amdgcn_s_sleep(EH_ORD_FOLDER_SLEEP);
+#else
+    (void)tk;
+    __syncthreads();        // the row is staged
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+        late_row();
+        store_row();
+        EH_ORD_TICK(ts, 6);
         if (tid == 0) {
             unsigned* const gc = o.cnt + 32 * gi;
             const bool last = __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsz - 1;
@@ -392,10 +516,10 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
         }
     }
     __syncthreads();
-    EH_ORD_TICK(ts, 2);
+    EH_ORD_TICK(ts, 1);
     if (flag[0] == 0.0f) return;
+#endif
     constexpr int NK = EH_ORD_ROWS / EH_ORD_GROUPS;
-    const int kown = blockIdx.x / EH_ORD_GROUPS;
     const int rb = 4 * ((o.slot * EH_ORD_ROWS + (int)gi) * o.rs), rk = 4 * EH_ORD_GROUPS * o.rs;     // bytes: row k of the group at rb + k rk
     const __amdgpu_buffer_rsrc_t gr = eh_ord_rsrc(o.grows, 2 * EH_ORD_GROUPS * o.rs + 2 * EH_ORD_PART);
     const int gb = 4 * ((o.slot * EH_ORD_GROUPS + (int)gi) * o.rs);
@@ -438,10 +562,16 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
                 return e;
             };
             const unsigned long long t0 = wall_clock64();
+#ifdef EH_STAMPS
+            w_late = (unsigned)__builtin_amdgcn_ballot_w64(empty_q()) & 0xFFFFu;
+#endif
             while (empty_q()) {
                 if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
                 __builtin_amdgcn_s_sleep(1);
                 q = eh_ord_ld16(rr, off);
+#ifdef EH_STAMPS
+                ++w_rounds;
+#endif
             }
             p = blocks();
         }
@@ -451,6 +581,7 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
         f32x4 r[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) r[k] = eh_ord_ld16(rr, ((unsigned)k < gsz && k != kown) ? rb + k * rk + 16 * v : (int)EH_ORD_OOB);    // (0 for the rest)
+        EH_ORD_TICK(ts, 2);
         const f32x4 own = *(const f32x4*)&row[4 * v];
         // (+ 0 for the rows past the group's end: the sum started at + 0 is never - 0, so x + 0 == x)
         auto fold = [&]() {
@@ -464,56 +595,72 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
         bool nan = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) nan = nan || (4 * v + j < nth && s[j] != s[j]);
-        if (nan) {            // (rare: a store of the group still on its way -- or a NaN gradient)
-            auto empty = [&](int k) {
-                bool e = false;
+        EH_ORD_TICK(ts, 3);
+        if (nan) {            // (a store of the group still on its way -- or a NaN gradient)
+            // bit k: row k's vector still holds the marker (own row and the rows past the group's end: 0 or a sum, never the marker)
+            auto pending = [&]() {
+                unsigned p = 0;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) e = e || (4 * v + j < nth && __float_as_uint(r[k][j]) == EH_ORD_EMPTY);
-                return e;
-            };
-            bool in = true;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) in = in && !empty(k);
-            if (!in) {
-                // Cold, and kept out of the hot path's way: ONE loop over the group's rows that is not unrolled.  Row k is read again, on
-                // its own, until its words have arrived, and goes into the sum where fold() puts it: the same additions in the same
-                // order from + 0.  (Unrolled over the 16 rows x 4 words with the spin inside, this branch was a third of the ordered
-                // kernel's code and the reason its scalar registers spilled into vector lanes -- on every step, for a path that runs
-                // only when a store is late.  A row that has arrived reads the same again: nobody writes it before the next launch.)
-                const unsigned long long t0 = wall_clock64();
-                bool late = false;
-                s = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
                 for (int k = 0; k < NK; ++k) {
-                    f32x4 q = own;
-                    if (k != kown) {
-                        const int off = (unsigned)k < gsz ? rb + k * rk + 16 * v : (int)EH_ORD_OOB;
-                        auto empty_q = [&]() {
-                            bool e = false;
+                    bool e = false;
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) e = e || (4 * v + j < nth && __float_as_uint(q[j]) == EH_ORD_EMPTY);
-                            return e;
-                        };
-                        q = eh_ord_ld16(rr, off);
-                        while (!late && empty_q()) {
-                            if (wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); late = true; break; }
-                            __builtin_amdgcn_s_sleep(1);
-                            q = eh_ord_ld16(rr, off);
-                        }
-                    }
-                    s += q;
+                    for (int j = 0; j < 4; ++j) e = e || (4 * v + j < nth && __float_as_uint(r[k][j]) == EH_ORD_EMPTY);
+                    p |= (e ? 1u : 0u) << k;
                 }
+                return p;
+            };
+            unsigned pend = pending();
+#ifdef EH_STAMPS
+            w_late |= pend;
+#endif
+            if (pend) {
+                // Warm: the folder is ahead of a neighbour's stores by less than their flight time on many steps.  A round loads again,
+                // all together, the vectors that still hold the marker -- each INTO the registers that hold it, under the lanes that miss
+                // it (eh_ord_reld16) -- waits once and looks again.  A row that has arrived is not read again: nobody writes it before
+                // the next launch.  Then the same additions in the same order from + 0.
+                const unsigned long long t0 = wall_clock64();
+                const float* const rp = o.rows + (rb >> 2);      // (row 0 of the group: uniform)
+                do {      // (ONE way out, at the bottom: a break in the middle made the compiler carry a second copy of the rows)
+                    __builtin_amdgcn_s_sleep(1);
+                    eh_ord_reld_rows<0>(r, pend, rp, 16u * (unsigned)v, (unsigned)rk);
+                    static_assert(NK == 16, "eh_ord_reld_wait names the sixteen rows");
+                    eh_ord_reld_wait(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11], r[12], r[13], r[14], r[15]);
+                    pend = pending();
+#ifdef EH_STAMPS
+                    ++w_rounds;
+#endif
+                    if (pend && wall_clock64() - t0 > EH_ORD_DEADLINE_TICKS) { __hip_atomic_store(o.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); pend = 0; }
+                } while (pend);
+                s = fold();
             }
         }
+        EH_ORD_TICK(ts, 4);
         eh_ord_st16(gr, gb + 16 * v, s);
     }
+#if EH_ORD_TICKET_AT != 0 && defined(EH_AB_ORD_ROW_SCALARS)
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) store_row();      // (that build's prologue reads every row's scalars)
+#endif
 #ifdef EH_STAMPS
-    EH_ORD_TICK(ts, 3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    EH_ORD_TICK(ts, 4);
-    if (st && tid == 0) {
+    EH_ORD_TICK(ts, 5);
+    if (st) {
+        // (per wave: the largest number of rounds of a lane, the rows any lane met under the marker)
 #pragma unroll
-        for (int k = 0; k < 10; ++k) st[EH_ORD_ST_TAIL + 10 * gi + k] = ts[k];
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned a = (unsigned)__shfl_xor((int)w_rounds, off, 64), b = (unsigned)__shfl_xor((int)w_late, off, 64);
+            w_rounds = a > w_rounds ? a : w_rounds;
+            w_late |= b;
+        }
+        unsigned long long* const sg = st + EH_ORD_ST_TAIL + EH_ORD_ST_TAILW * gi;
+        const int wv = tid >> 6;
+        if ((tid & 63) == 0) {
+            if (wv == (nthr >> 6) - 1) sg[24] = w_rounds | (w_late << 16);
+            if (wv < 8 && (wv < (nthr >> 6) - 1 || 64 * wv < nv)) sg[16 + wv] = 64 * wv < nv ? w_rounds | (w_late << 16) : 0u;
+        }
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) sg[k] = ts[k];
+        }
     }
 #else
     (void)st;
@@ -2426,6 +2573,8 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         carry->live = nx_live;
     }
     EH_STAMP(8);
+    unsigned ord_tk = 0;                           // (EH_MODE_TRAIN_ORD: thread 0's ticket of its row group, eh_ord_ticket)
+    if constexpr (ORDM) eh_ord_ticket<8>(a.ord, tid, ord_tk);
 #ifdef EH_DBG_LACC
     if (a.stamps && blockIdx.x == 0 && lane < 2) reinterpret_cast<float*>(a.stamps)[wave * 2 + lane] = lacc;      // diagnostics: lanes 0 / 1 of every wave, before the wave sums
 #endif
@@ -2445,8 +2594,10 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         tailv[13] = K1 ? eh_wave_sum(aBoS) : 0.0f;
         tailv[14] = eh_wave_sum(syacc); tailv[15] = eh_wave_sum(syyacc);
         EH_STAMP(13);
+        if constexpr (ORDM) eh_ord_ticket<13>(a.ord, tid, ord_tk);
         __syncthreads();                           // the wave workspaces are dead from here on
         EH_STAMP(14);
+        if constexpr (ORDM) eh_ord_ticket<14>(a.ord, tid, ord_tk);      // (the answer is first asked for in eh_ord_publish, behind the parking and the gather)
         // waves that had no tile (a minibatch smaller than the workgroup's NW tiles: the reference's batch of 64 fills two of eight) hold zeros
         // everywhere: they park nothing and the gather leaves them out -- the same sums bit for bit (x + 0), a quarter of the LDS traffic
 #ifdef EH_AB_FULL_GATHER       // (diagnostic A/B: the form of rounds 1-4 -- every wave parks, the gather sums all NW)
@@ -2563,7 +2714,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         EH_STAMP_RED(0, 0);
         EH_STAMP_RED(2, 64);
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps);
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);
@@ -2621,6 +2772,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
         }
         EH_STAMP(13);
+        if constexpr (ORDM) eh_ord_ticket<13>(a.ord, tid, ord_tk);
         float* const R = smem + G::IMG_FLOATS + wave * G::WAVE_WS;
         const float* const R0 = smem + G::IMG_FLOATS;
         float* const out = a.slab + (long long)blockIdx.x * a.n_acc;      // (EH_MODE_TRAIN_ORD: the row is staged in LDS, over the parameter image -- dead by now)
@@ -2640,6 +2792,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                 dst[u] = (wd < KH * 256 && rd * KH + wd / 256 < AL.na) ? a.rmap[rd * KH * 256 + wd] : -1;
             }
             if (rd == NR - 1 && tid < 16) dtail = a.rmap[AL.na * 256 + tid];
+            if constexpr (ORDM) { if (rd == 0) eh_ord_ticket<14>(a.ord, tid, ord_tk); }      // (behind the first round's barrier and its map loads, which then do not wait for it)
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk)
                 if (rd * KH + kk < AL.na) *(f32x4*)&R[kk * 256 + c * 16 + g * 4] = vals[rd * KH + kk];
@@ -2679,7 +2832,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps);
+        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);
