@@ -1286,6 +1286,8 @@ int32_t eh_jit_status(eh_handle* h, int32_t* n_compiled, char* log, int64_t log_
     if (h->spec_used && h->aot_spec) { n += 1; msg = std::string("ahead-of-time: ") + h->spec_used->what + (msg.empty() ? "" : "; ") + msg; }
     // which form of the single-step train kernel the last such launch ran (eh_lean_fold, eh_device.hpp)
     if (h->lean_last >= 0) msg += std::string(msg.empty() ? "" : "; ") + (h->lean_last ? "train step kernel: lean" : "train step kernel: general");
+    // how many training steps ran as the ordered one-kernel step (a step that fell back to the step + reduce pair is not counted)
+    if (h->ord_steps > 0) msg += std::string(msg.empty() ? "" : "; ") + "ordered steps: " + std::to_string(h->ord_steps);
     *n_compiled = n;
     if (log && log_bytes > 0) {
         const size_t m = std::min((size_t)log_bytes - 1, msg.size());
@@ -2561,6 +2563,7 @@ static int train_one(eh_handle* h, const EhSplit& sp, const int* idx, long long 
         *one_kernel = true;
     } else if (ord_ok(h, grid)) {
         if (int rc = do_fused_step(h, sp, idx, first, count, loss_slot, true, one_kernel)) return rc;
+        if (*one_kernel) ++h->ord_steps;
     }
     if (*one_kernel) return EH_OK;
     FLUSH(h);                                  // ("fused_update" 2: a one-workgroup step may be pending in front of this larger one)

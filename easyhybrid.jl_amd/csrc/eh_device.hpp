@@ -211,7 +211,8 @@ struct EhOrd {
 // folder records (shader clock, wall clock) pairs at stamps[EH_ORD_ST_TAIL + 32 g ...]: [0] its row staged, [1] behind the staged
 // barrier, the election known to the workgroup (EH_AB_ORD_TICKET_LATE: behind the ticket's barrier), [2] the loads of the group's rows
 // issued, [3] the first pass folded, [4] the wait rounds over (= [3] without one), [5] the group row stored (a wait only this build
-// has), [6] EH_AB_ORD_TICKET_LATE only: the row's stores issued, about to take the ticket.  Words 16 ... 23: per wave of the folder that
+// has), [6] EH_AB_ORD_TICKET_LATE: the row's stores issued, about to take the ticket; EH_AB_ORD_ROWS_EARLY: in front of the gather,
+// whose rounds issue the row's stores (ahead of [0]); 0 in every other build.  Words 16 ... 23: per wave of the folder that
 // folds gradient vectors, (largest number of wait rounds of a lane) | (rows met under the marker, bit k = row k of the group) << 16;
 // word 24: the same of the wave that folds the scalar vector.  Workgroup 0 at stamps[EH_ORD_ST_PRO ...]: [0] image staged, [1] the
 // scalars folded (both by the wave that folds).
@@ -338,6 +339,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t eh_ord_rsrc(const float* base,
 }
 __device__ __forceinline__ f32x4 eh_ord_ld16(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16)); }
 __device__ __forceinline__ void eh_ord_st16(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_ord, v), r, off, 0, 16); }
+// (AUX 16 = sc1 as above, 0 = a plain store, which stays in the XCD's L2 until the end of the kernel writes it back)
+template <int AUX> __device__ __forceinline__ void eh_ord_st16_aux(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_ord, v), r, off, 0, AUX); }
 enum { EH_ORD_OOB = 0x7FFFFFF0 };       // (a byte offset past any row buffer: the load returns 0)
 // The wait rounds of the group's folder (eh_ord_publish): the same 16-byte sc1 load, INTO the registers that hold the vector already and
 // only under the lanes that execute it.  Written as a builtin under a branch, sixteen of them made the compiler keep a second copy of
@@ -395,15 +398,75 @@ __device__ __forceinline__ void eh_ord_reset(const EhOrd& o, int b, int nblk, in
 #if EH_ORD_TICKET_AT != 0 && EH_ORD_TICKET_AT != 8 && EH_ORD_TICKET_AT != 13 && EH_ORD_TICKET_AT != 14
 #error "EH_AB_ORD_TICKET_AT is 8, 13 or 14"
 #endif
-// EH_AB_ORD_FOLDER_SLEEP = n (likewise): the folder's pause in front of its row loads, n x 64 cycles (eh_ord_publish); 0 = none
-#ifdef EH_AB_ORD_FOLDER_SLEEP
-#define EH_ORD_FOLDER_SLEEP EH_AB_ORD_FOLDER_SLEEP
-#else
-#define EH_ORD_FOLDER_SLEEP 5
-#endif
 #if defined(EH_TEST_ORD_LATE_ROW) && !defined(__HIPCC_RTC__)
 #error "EH_TEST_ORD_LATE_ROW is for kernels compiled at run time (tests/test_gpu_ordered_ticket.py)"
 #endif
+// EH_AB_ORD_ROWS_EARLY (likewise through EH_JIT_DEFINES; NOT the default): early row stores.  The v2 gather of eh_step_body stores
+// every 16-byte vector of the row from the registers of the threads that have just summed its elements, the later folder included --
+// one barrier wait and one LDS read ahead of wave 0's store out of the LDS staging behind the staged barrier (eh_ord_row_early).  No
+// folder then meets a marker even without the pause, but on the headline step that is 0.02 - 0.09 us of 9.0, inside three times the
+// run-to-run spread: measured and left off (DESIGN.md sections 3.2 and 8, profiles/r23/).  The older A/B builds whose prologue or
+// election needs the staged order (EH_AB_ORD_TICKET_LATE, EH_AB_ORD_ROW_SCALARS) and the shapes of the v3 gather are staged always.
+#if defined(EH_AB_ORD_ROWS_EARLY) && !defined(EH_AB_ORD_ROW_SCALARS) && EH_ORD_TICKET_AT != 0
+#define EH_ORD_EARLY_ROWS 1
+#else
+#define EH_ORD_EARLY_ROWS 0
+#endif
+// EH_AB_ORD_FOLDER_SLEEP = n (likewise): the folder's pause in front of its row loads, n x 64 cycles (eh_ord_publish); 0 = none.
+// Without the define: 5 where a row store waits for the staged barrier -- the staged path, and in an EH_AB_ORD_ROWS_EARLY build the
+// kernels of the v3 gather and the shapes whose scalar vector is still stored behind the barrier (eh_ord_scalars_split) --, and none
+// where the gather has stored the whole row, which is where the early row stores are fastest.
+#ifdef EH_AB_ORD_FOLDER_SLEEP
+#define EH_ORD_FOLDER_SLEEP EH_AB_ORD_FOLDER_SLEEP
+#define EH_ORD_FOLDER_SLEEP_EARLY EH_AB_ORD_FOLDER_SLEEP
+#else
+#define EH_ORD_FOLDER_SLEEP 5
+#define EH_ORD_FOLDER_SLEEP_EARLY 0
+#endif
+// The folder's group row and block partials are plain stores: nobody inside the kernel reads them -- the next kernel on the stream
+// does, and the kernel boundary publishes plain stores -- and a plain store is acknowledged by the XCD's L2, where the write-through one
+// (sc1) is a fabric write that the end of the kernel waited for ("group row stored": 1 060 -> 312 cycles of the last folder's tail).
+// EH_AB_ORD_GROW_WT (likewise): write-through, as they were.  The member rows, their loads and eh_ord_reset stay write-through: rows
+// are read inside the kernel that writes them, and a reset line must not survive as a clean copy in an L2 a later folder reads through.
+#ifdef EH_AB_ORD_GROW_WT
+#define EH_ORD_GROW_AUX 16
+#else
+#define EH_ORD_GROW_AUX 0
+#endif
+// (tests only, EH_TEST_ORD_LATE_ROW = k: member k of every group waits some 20 us of the wall clock in front of its row stores)
+__device__ __forceinline__ void eh_ord_late_row() {
+#ifdef EH_TEST_ORD_LATE_ROW
+    if ((int)(blockIdx.x / EH_ORD_GROUPS) == (EH_TEST_ORD_LATE_ROW)) {
+        const unsigned long long t0 = wall_clock64();
+        while (wall_clock64() - t0 < 2000ull) __builtin_amdgcn_s_sleep(8);       // (20 us of the 100 MHz clock: 1e-5 of the deadline)
+    }
+#endif
+}
+// The row's scalar vector [S | n | Sy | Syy] is elements nth ... nth + 3 of the gather: four consecutive lanes of one wave unless they
+// begin in its last three lanes.  Then (kernel-uniform) wave 0 stores that one vector from the LDS staging behind the barrier.
+__device__ __forceinline__ bool eh_ord_scalars_split(int nth) { return (nth & 63) > 60; }
+// Element e of the row, summed by this thread of the v2 gather (every thread of a wave whose e < nth + 4 is here, lane by lane in
+// ascending e; ebase = e - lane, wave-uniform).  The four elements of a gradient vector sit in the four lanes of a quad (the workgroup's
+// thread count is a multiple of 4): each lane takes the quad's four words by DPP and the lane of word 0 stores them, the words past nth
+// as + 0.0f (never the marker; nobody checks them).  All four lanes of such a quad are active: 4 ceil(nth / 4) <= nth + 3.  The scalar
+// vector is taken by readlane out of the wave that holds all of it and stored by the lane of its first word.  The stores are 16-byte
+// sc1 stores at the offsets the staged store used; an offset past the buffer drops the store of a lane that has none (no branch, so
+// that the compiler keeps counting the stores that are in flight ahead of the ticket's answer).
+// (rr, rb: the rows' descriptor and this row's byte offset, formed by the caller in front of its loop -- formed in here, under the
+//  loop's lane mask, the descriptor that eh_ord_publish shares with it went through vector registers and came back by sixty-four
+//  v_readfirstlane in front of the folder's row loads)
+__device__ __forceinline__ void eh_ord_row_early(const EhOrd& o, __amdgpu_buffer_rsrc_t rr, int rb, int nth, int e, int ebase, int lane, float sum) {
+    const float gv = e < nth ? sum : 0.0f;
+    const f32x4 q = {eh_dpp<0x00>(gv), eh_dpp<0x55>(gv), eh_dpp<0xAA>(gv), eh_dpp<0xFF>(gv)};      // quad_perm:[j,j,j,j]
+    eh_ord_st16(rr, ((e & 3) == 0 && e < nth) ? rb + 4 * e : (int)EH_ORD_OOB, q);
+    if (ebase == (nth & ~63) && !eh_ord_scalars_split(nth)) {      // (wave-uniform)
+        const int l0 = nth & 63, si = __builtin_bit_cast(int, sum);
+        f32x4 sv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sv[j] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, l0 + j));
+        eh_ord_st16(rr, lane == l0 ? rb + 4 * o.soff : (int)EH_ORD_OOB, sv);
+    }
+}
 // The election, held early: ONE lane of wave 0 adds to its group's counter (relaxed, agent scope) at place AT of the step -- the place
 // the build has chosen, nothing elsewhere -- and keeps the answer in a register; nobody waits for it here.  eh_ord_publish reads it.
 template <int AT> __device__ __forceinline__ void eh_ord_ticket(const EhOrd& o, int tid, unsigned& tk) {
@@ -445,14 +508,19 @@ template <int AT> __device__ __forceinline__ void eh_ord_ticket(const EhOrd& o, 
 // workgroups fit the device at once.  A ticket in front of the tile, or a fixed folder (say the group's first member), would lose this:
 // the folder could then sit on a compute unit waiting for a member that needs that unit to start.  The deadline and the host-mapped
 // error word remain as the backstop.
-// (EH_TEST_ORD_LATE_ROW = k, tests only: member k of every group waits some 20 us of the wall clock behind the staged barrier, in front
-//  of its row stores, so that its group's folder certainly meets the marker.)
-__device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, const float* row, float* flag, unsigned long long* st, unsigned tk) {
+// (EH_TEST_ORD_LATE_ROW = k, tests only: member k of every group waits some 20 us of the wall clock in front of its row stores, so that
+//  its group's folder certainly meets the marker: wave 0 behind the staged barrier, or with EH_AB_ORD_ROWS_EARLY every wave in front of
+//  the gather that stores the row -- eh_ord_late_row.)
+// EARLY (EH_AB_ORD_ROWS_EARLY on the v2 gather): the gather has stored the row already, the later folder's included (eh_ord_row_early);
+// behind the barrier thread 0 stores only a scalar vector that straddles two waves, and the folder does not pause unless it did.
+template <bool EARLY> __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid, int nthr, const float* row, float* flag, unsigned long long* st, unsigned tk,
+                                                                        unsigned long long g_cyc = 0, unsigned long long g_wall = 0) {
 #ifdef EH_STAMPS
     unsigned long long ts[16];
     unsigned w_rounds = 0, w_late = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) ts[k] = 0;
+    if constexpr (EARLY) { ts[12] = g_cyc; ts[13] = g_wall; }      // [6]: in front of the gather, whose rounds issue the row's stores
 #endif
     EH_ORD_TICK(ts, 0);
     const unsigned gi = blockIdx.x % EH_ORD_GROUPS, gsz = (gridDim.x - gi + EH_ORD_GROUPS - 1) / EH_ORD_GROUPS;      // (ahead of the barrier)
@@ -466,14 +534,7 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
             eh_ord_st16(rr, rb + 4 * w, *(const f32x4*)&row[w]);
         }
     };
-    auto late_row = [&]() {                // (wave 0)
-#ifdef EH_TEST_ORD_LATE_ROW
-        if (kown == (EH_TEST_ORD_LATE_ROW)) {
-            const unsigned long long t0 = wall_clock64();
-            while (wall_clock64() - t0 < 2000ull) __builtin_amdgcn_s_sleep(8);       // (20 us of the 100 MHz clock: 1e-5 of the deadline)
-        }
-#endif
-    };
+    auto late_row = [&]() { eh_ord_late_row(); };      // (wave 0)
 #ifdef EH_AB_ORD_PARENT
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (diagnostic A/B: the drain of the hand-off before the sentinel words)
 #endif
@@ -488,7 +549,11 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
     __syncthreads();        // the row is staged, the election known
     EH_ORD_TICK(ts, 1);
     const bool folder = flag[0] != 0.0f;
-    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+    if constexpr (EARLY) {
+        // (the gather has stored the row, the folder's own included; what is left is a scalar vector that begins in the last three
+        //  lanes of a wave: from the staging, by every workgroup -- nobody reads the folder's)
+        if (eh_ord_scalars_split(nth) && tid == 0) eh_ord_st16(rr, 4 * ((o.slot * EH_ORD_ROWS + (int)blockIdx.x) * o.rs + o.soff), *(const f32x4*)&row[o.soff]);
+    } else if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
         late_row();
         if (!folder) store_row();
     }
@@ -500,7 +565,10 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
     // (1.1 k cycles) gave for free, cut to what the stores need.  Measured on the headline step: 0 -> 11.2 us, 2 -> 10.9, 3 -> 10.0,
     // 4 -> 9.33, 5 -> 9.29, 6 -> 9.35, 8 -> 9.39, 12 -> 9.48, 16 -> 9.59; the late ticket 9.63 (profiles/r22/ord_ticket_ab.txt).
     // A row that is later still costs a wait round, never a wrong sum.
-    if (EH_ORD_FOLDER_SLEEP > 0) __builtin_amdgcn_s_sleep(EH_ORD_FOLDER_SLEEP);
+    // (EARLY: the gather issued the whole row's stores a barrier ago, and no folder meets a marker without any pause -- unless the
+    //  scalar vector was stored just now, behind the barrier; then the staged path's pause.)
+    if (EARLY && !eh_ord_scalars_split(nth)) { if (EH_ORD_FOLDER_SLEEP_EARLY > 0) __builtin_amdgcn_s_sleep(EH_ORD_FOLDER_SLEEP_EARLY); }
+    else if (EH_ORD_FOLDER_SLEEP > 0) __builtin_amdgcn_s_sleep(EH_ORD_FOLDER_SLEEP);
 #else
     (void)tk;
     __syncthreads();        // the row is staged
@@ -575,7 +643,7 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
             }
             p = blocks();
         }
-        if (k < EH_ORD_GROUPS && (k & 3) == 0) eh_ord_st16(gr, pb + (k >> 2) * pq, p);
+        if (k < EH_ORD_GROUPS && (k & 3) == 0) eh_ord_st16_aux<EH_ORD_GROW_AUX>(gr, pb + (k >> 2) * pq, p);
     }
     for (int v = tid; v < nv; v += nthr) {
         f32x4 r[NK];
@@ -635,7 +703,7 @@ __device__ __forceinline__ void eh_ord_publish(const EhOrd& o, int nth, int tid,
             }
         }
         EH_ORD_TICK(ts, 4);
-        eh_ord_st16(gr, gb + 16 * v, s);
+        eh_ord_st16_aux<EH_ORD_GROW_AUX>(gr, gb + 16 * v, s);
     }
 #if EH_ORD_TICKET_AT != 0 && defined(EH_AB_ORD_ROW_SCALARS)
     if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) store_row();      // (that build's prologue reads every row's scalars)
@@ -2661,6 +2729,23 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         const float* const R0 = smem + G::IMG_FLOATS;
         float* const out = a.slab + (long long)blockIdx.x * a.n_acc;      // (EH_MODE_TRAIN_ORD: the row is staged in LDS, over the parameter image -- dead by now)
         float* const gsh = (!ORDM && a.fz.gacc) ? (P2PM ? const_cast<float*>(px_stage) : a.fz.gacc) + (a.fz.gslot * EH_GSHARDS + (blockIdx.x & (EH_GSHARDS - 1))) * a.n_acc : nullptr;
+#if EH_ORD_EARLY_ROWS
+        unsigned long long ord_gc = 0, ord_gw = 0;      // (diagnostic builds: the gather begins -- the place of the early row stores)
+        // (The ticket's answer is taken into its register here, in front of the row's stores.  The gather's head joins the load of
+        //  rmap[e] with a wait for everything in flight anyway, 1.8 k cycles behind the add, so this costs nothing; behind the stores
+        //  the compiler can no longer tell the answer from them, and thread 0 would wait for its wave's row stores to be acknowledged
+        //  before it could write the election and reach the staged barrier.)
+        if constexpr (ORDM) { asm volatile("" : "+v"(ord_tk)); eh_ord_late_row(); }
+        const __amdgpu_buffer_rsrc_t ord_rr = eh_ord_rsrc(ORDM ? a.ord.rows : nullptr, ORDM ? 2 * EH_ORD_ROWS * a.ord.rs : 0);
+        const int ord_rb = ORDM ? 4 * ((a.ord.slot * EH_ORD_ROWS + (int)blockIdx.x) * a.ord.rs) : 0;
+#ifdef EH_STAMPS
+        if constexpr (ORDM) {
+            __builtin_amdgcn_sched_barrier(0);
+            ord_gc = __builtin_readcyclecounter(); ord_gw = wall_clock64();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
+#endif
         for (int e = tid; e < a.n_acc; e += NTHR) {
             const int code = e == tid ? f_rcode : a.rmap[e], pos = code & 0xFFFFFF, nlan = code >> 24;
             float sum = 0.0f;
@@ -2707,14 +2792,23 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
                 for (int w = 0; w < nlive; ++w) sum += R0[w * AL.rw + pos];
             }
 #endif
-            if constexpr (ORDM) wl[eh_ord_pos(e, net.n_theta, a.ord.soff)] = sum;      // (eh_ord_publish stores it write-through)
+            if constexpr (ORDM) {
+                wl[eh_ord_pos(e, net.n_theta, a.ord.soff)] = sum;      // (eh_ord_publish stores it write-through; EH_AB_ORD_ROWS_EARLY: only the folder takes its own row from here)
+#if EH_ORD_EARLY_ROWS
+                eh_ord_row_early(a.ord, ord_rr, ord_rb, net.n_theta, e, __builtin_amdgcn_readfirstlane(e - lane), lane, sum);
+#endif
+            }
             else if (gsh) { if (a.ms_direct) ((eh_lds_f*)gsh)[e] = sum; else atomicAdd(&gsh[e], sum); }      // (ms_direct: one workgroup, one writer per element)
             else out[e] = sum;
         }
         EH_STAMP_RED(0, 0);
         EH_STAMP_RED(2, 64);
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk);
+#if EH_ORD_EARLY_ROWS
+        if constexpr (ORDM) eh_ord_publish<true>(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk, ord_gc, ord_gw);
+#else
+        if constexpr (ORDM) eh_ord_publish<false>(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk);
+#endif
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);
@@ -2832,7 +2926,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
         }
         if constexpr (P2PM) { if (px_mode == 0) eh_p2p_publish(&a.p2pv, a.fz.gslot, a.p2p_seq, a.n_acc, tid, NTHR); }      // (mode 1: the next kernel's workgroup 0 publishes)
-        if constexpr (ORDM) eh_ord_publish(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk);
+        if constexpr (ORDM) eh_ord_publish<false>(a.ord, net.n_theta, tid, NTHR, wl, px_T + 4, a.stamps, ord_tk);
         EH_STAMP_FINE(15);
         if constexpr (!P2PM) { if (a.ms_direct) eh_ms_apply<G>(net, a, gsh, wl, tid, NTHR); }
         EH_STAMP(10);

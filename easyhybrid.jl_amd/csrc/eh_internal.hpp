@@ -254,6 +254,7 @@ struct eh_handle_s {
     bool lean_cfg = false;          // ... and whether it does (lean_refresh, eh_api.hip: decided where the configuration changes, not per step)
     int lean_last = -1;             // the last single-step train launch ran the lean (1) / the general (0) kernel; -1: none yet (eh_jit_status)
     const struct EhSpecKernel* spec_used = nullptr;      // ... the one the last launch ran (eh_jit_status reports it)
+    long long ord_steps = 0;        // training steps that ran as the ordered one-kernel step (EH_MODE_TRAIN_ORD; eh_jit_status reports the count)
     bool specialize_async = false;  // "specialize" = 2
     bool jit_on = true;             // "jit" option / EH_JIT=0: 0 = the interpreting kernels built ahead of time
     bool jit_failed = false;

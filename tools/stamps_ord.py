@@ -10,6 +10,10 @@ The kernel is compiled at run time with the stamps in:
     ... EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_ROW_SCALARS" ...   (the prologue reads the 256 rows' scalar vectors and
         folds all six butterfly levels, as before the tail formed the block partials)
     ... EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_FOLD_WAVE0" ...   (wave 0 folds the block partials, not the last wave)
+    ... EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_ROWS_EARLY" ...   (the gather stores the row in front of the staged barrier,
+        not wave 0 behind it; the folder's pause is then 0 unless EH_AB_ORD_FOLDER_SLEEP says otherwise)
+    ... EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_GROW_WT" ...   (group rows and block partials stored write-through)
+    ... EH_JIT_DEFINES="EH_STAMPS EH_STAMPS_PROLOGUE EH_AB_ORD_FOLDER_SLEEP=n" ...   (the folder's pause, n x 64 cycles)
 The scalar fold's slot is stamped by the wave that folds (its image staged -> its fold done).
 The tail's slots are the median over the last `--reps` steps, each read back on its own (a synchronize per step: the steps run apart);
 the wait rounds are counted over the same steps: a folder "waited" when any of its lanes met a row under the marker and loaded it again."""
@@ -43,8 +47,11 @@ buf = (C.c_uint64 * WORDS)()
 eng._lib.eh_debug_stamps(eng._h, buf, WORDS)          # arms the buffer
 # the folder's path: [0] row staged, ([6] LATE: row stores issued,) [1] election known, [2] loads issued, [3] first pass folded,
 # [4] wait rounds over, [5] group row stored
-path = [0, 6, 1, 2, 3, 4, 5] if late else [0, 1, 2, 3, 4, 5]
-lab = (["barrier, row stores issued", "ticket"] if late else ["staged barrier, election read"]) + \
+# the early row stores: [6] the gather begins -- its rounds issue the row's stores -- then [0] as above
+early = "EH_AB_ORD_ROWS_EARLY" in defs and not late and not any(d in defs for d in ("EH_AB_ORD_ROW_SCALARS", "EH_AB_ORD_PARENT"))
+path = [0, 6, 1, 2, 3, 4, 5] if late else [6, 0, 1, 2, 3, 4, 5] if early else [0, 1, 2, 3, 4, 5]
+lab = (["barrier, row stores issued", "ticket"] if late else
+       ["gather, row stores issued", "staged barrier, election read"] if early else ["staged barrier, election read"]) + \
       ["loads issued", "first pass folded", "wait rounds", "group row stored"]
 rows = []
 for i in range(args.warmup + args.reps):
