@@ -83,6 +83,7 @@ static int flush_one(eh_handle* h) {
         hipLaunchKernelGGL(eh_ord_flush_kernel, dim3(std::max((nt + 255) / 256, h->ord_grid)), dim3(256), 0, h->stream, ord_args(h, h->cur, h->ord_grid), nt, TH(h), MM(h), VV(h),
                            h->sc + 2 * h->sc_sel, h->sc + 2 * (h->sc_sel ^ 1), h->opt, h->pending_loss, h->img, h->net.loss);
         HIPCHK(h, hipGetLastError());
+        ++h->upd_site[EH_UPD_ORD_FLUSH];
         return flush_done(h);
     }
     const float* g_prev = h->gacc + (size_t)((h->gstep + 2) % 3) * EH_GSHARDS * h->n_acc;
@@ -91,6 +92,7 @@ static int flush_one(eh_handle* h) {
     hipLaunchKernelGGL(eh_fused_flush_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, g_prev, h->n_acc, nt, TH(h), MM(h), VV(h), sc_in, sc_out,
                        h->opt, h->pending_loss, h->img, h->net.loss, h->p2p_on ? h->p2p_dev : nullptr, (int)((h->gstep + 2) % 3), h->p2p_seq, h->net.T);
     HIPCHK(h, hipGetLastError());
+    ++h->upd_site[EH_UPD_FUSED_FLUSH];
     // Single GPU: nothing to clear -- the rotation keeps itself clean (the step that accumulates into slot g clears slot g + 1 in
     // its prologue and nobody reads a slot before the step after its clearing has filled it).  Under EhP2P the workgroups add
     // into a staging copy that the publishing workgroup reads whole: cleared here.
@@ -1288,6 +1290,13 @@ int32_t eh_jit_status(eh_handle* h, int32_t* n_compiled, char* log, int64_t log_
     if (h->lean_last >= 0) msg += std::string(msg.empty() ? "" : "; ") + (h->lean_last ? "train step kernel: lean" : "train step kernel: general");
     // how many training steps ran as the ordered one-kernel step (a step that fell back to the step + reduce pair is not counted)
     if (h->ord_steps > 0) msg += std::string(msg.empty() ? "" : "; ") + "ordered steps: " + std::to_string(h->ord_steps);
+    // which update sites applied how many optimiser updates (host-side counts of the launches; the non-zero ones)
+    {
+        std::string sites;
+        for (int s = 0; s < EH_UPD_SITES; ++s)
+            if (h->upd_site[s] > 0) sites += std::string(" ") + eh_upd_site_name(s) + " " + std::to_string(h->upd_site[s]);
+        if (!sites.empty()) msg += std::string(msg.empty() ? "" : "; ") + "update sites:" + sites;
+    }
     *n_compiled = n;
     if (log && log_bytes > 0) {
         const size_t m = std::min((size_t)log_bytes - 1, msg.size());
@@ -1861,6 +1870,7 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
     if (h->drop_on) { eh_drop_set(a, h->drop_seed, h->drop_step); }
     if (int rc = eh_bn_prepare(h, sp, idx, first, count, true, &a)) return rc;
     const int grid = grid_for(h, count);
+    const bool was_pending = h->pending;      // (this step's prologue applies that update)
     if (ord) {
         a.ord = ord_args(h, h->cur, h->pending ? h->ord_grid : 0);
         const hipError_t e = step_launch(h, EH_MODE_TRAIN_ORD, grid, &a);
@@ -1879,6 +1889,7 @@ static int do_fused_step(eh_handle* h, const EhSplit& sp, const int* idx, long l
     // (the ordered step leaves the accumulator rotation alone: gstep counts the steps that add into gacc)
     h->cur ^= 1; h->sc_sel ^= 1;
     if (!ord) h->gstep++;
+    if (was_pending) ++h->upd_site[ord ? EH_UPD_ORD_PROLOGUE : EH_UPD_PROLOGUE];
     h->pending = true;
     h->pend_ord = ord;
     h->pending_loss = loss_slot_for_this_step;
@@ -1910,6 +1921,8 @@ static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long 
     if (int rc = eh_bn_prepare(h, sp, idx, first, a.count, true, &a)) return rc;       // (input BatchNorm: statistics inside the kernel, multi_ok made sure)
     a.ms_nsteps = nsteps; a.ms_batch = (int)batch; a.ms_end = end; a.ms_loss = loss_slots;
     HIPCHK(h, step_launch(h, EH_MODE_TRAIN_MULTI, 1, &a));
+    if (h->pending) ++h->upd_site[EH_UPD_PROLOGUE];      // (the first step's prologue applied it)
+    h->upd_site[EH_UPD_MULTI] += nsteps;
     // every step of the launch has applied its own update and written its own loss (eh_ms_apply): nothing is pending behind it; the first
     // step's prologue flipped the parameter set and rotated the accumulator slots once
     h->cur ^= 1; h->sc_sel ^= 1;
@@ -1922,6 +1935,7 @@ static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long 
 // The chain kernels (eh_chain.hpp) on the gradient in h->gradbuf.  raw: the data-parallel seam's all-reduced sums (eh_dp_apply), whose
 // loss the apply pass writes to loss_slot; otherwise eh_reduce_kernel<false, ...> has written gradient and loss.
 static int launch_chain(eh_handle* h, bool raw, float* sc_in, float* sc_out, float* loss_slot) {
+    ++h->upd_site[EH_UPD_CHAIN];
     static const int one_env = getenv("EH_CHAIN_ONE") ? atoi(getenv("EH_CHAIN_ONE")) : -1;      // (A/B switch of tools/bench_chain.py: the largest n_theta one workgroup takes)
     const int nt = h->net.n_theta;
     const bool l2 = raw && (h->img.l2c != 0.0f || h->img.l2w);
@@ -2021,6 +2035,7 @@ int eh_do_step(eh_handle* h, const EhSplit& sp, const int* idx, long long first,
                        TH(h), MM(h), VV(h), sc_in, sc_out, h->opt, loss_slot, h->img, h->net.loss, (moment_loss && !raw) ? h->inv_n : nullptr, l2 ? h->l2val : nullptr, tp_mask)
     if (apply && !chained) {
         if (tall4) EH_REDUCE_GO(true, 256, 4, true); else if (tall) EH_REDUCE_GO(true, 256); else if (big) EH_REDUCE_GO(true, 64); else EH_REDUCE_GO(true, 16);
+        ++h->upd_site[tall4 ? EH_UPD_REDUCE256V4 : tall ? EH_UPD_REDUCE256 : big ? EH_UPD_REDUCE64 : EH_UPD_REDUCE16];
         h->sc_sel ^= 1;
     } else {
         if (tall4) EH_REDUCE_GO(false, 256, 4, true); else if (tall) EH_REDUCE_GO(false, 256); else if (big) EH_REDUCE_GO(false, 64); else EH_REDUCE_GO(false, 16);
@@ -2946,6 +2961,7 @@ int32_t eh_dp_apply(eh_handle* h, float* loss_out) {
         hipLaunchKernelGGL(eh_apply_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, h->gradbuf, nt, TH(h), MM(h), VV(h), sc_in, sc_out, h->opt,
                            h->loss_hist, h->img, h->net.loss, h->net.T, l2 ? h->l2val : nullptr, two_pass_mask(h->net) ? h->inv_n : nullptr, two_pass_mask(h->net));
         HIPCHK(h, hipGetLastError());
+        ++h->upd_site[EH_UPD_DP_APPLY];
     }
     h->sc_sel ^= 1;
     if (loss_out) {

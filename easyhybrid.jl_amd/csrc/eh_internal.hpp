@@ -99,6 +99,21 @@ constexpr long long EH_SHIFT_VALID = 4096;
 enum { EH_MECH_MAXROWS = 65536 };            // eh_mech_loss_vjp: rows of partials (workgroups of the streaming kernel) at most: 4 MiB
 enum { EH_LFORM_ROWS = 64 };                 // layer-wise form: partial slabs of the weight gradients (split over the samples of a minibatch)
 enum { EH_BNL_CHUNKS = 256, EH_BNL_CHUNK_ROWS = 128 };      // BatchNorm layers (eh_bnl.hpp): partial rows of the column sums at most; rows a chunk holds at least
+// the places an optimiser update is applied from (eh_handle_s::upd_site; eh_jit_status)
+enum {
+    EH_UPD_REDUCE16, EH_UPD_REDUCE64, EH_UPD_REDUCE256, EH_UPD_REDUCE256V4,      // eh_reduce_kernel<true, ...> behind a step or a sequence step
+    EH_UPD_DW_APPLY, EH_UPD_DW_APPLY64,                                           // the layer-wise epilogues eh_dw_apply_kernel / eh_dw_apply64_kernel
+    EH_UPD_FUSED_FLUSH, EH_UPD_ORD_FLUSH,                                         // eh_fused_flush_kernel / eh_ord_flush_kernel
+    EH_UPD_PROLOGUE, EH_UPD_ORD_PROLOGUE,                                         // a one-kernel step whose prologue applied the pending update (float-atomic / ordered)
+    EH_UPD_MULTI,                                                                 // steps of multi-step launches (eh_ms_apply)
+    EH_UPD_DP_APPLY, EH_UPD_CHAIN,                                                // eh_apply_kernel / the chain kernels
+    EH_UPD_SITES
+};
+static inline const char* eh_upd_site_name(int s) {
+    static const char* const n[EH_UPD_SITES] = {"reduce16", "reduce64", "reduce256", "reduce256v4", "dw_apply", "dw_apply64", "fused_flush", "ord_flush",
+                                                "prologue", "ord_prologue", "multi_step", "dp_apply", "chain"};
+    return n[s];
+}
 
 struct EhShift4 { float c[EH_MAX_TARG]; };   // the shifts as a kernel argument (eh_count_kernel, eh_moment_*_kernel)
 struct EhSplit {
@@ -255,6 +270,9 @@ struct eh_handle_s {
     int lean_last = -1;             // the last single-step train launch ran the lean (1) / the general (0) kernel; -1: none yet (eh_jit_status)
     const struct EhSpecKernel* spec_used = nullptr;      // ... the one the last launch ran (eh_jit_status reports it)
     long long ord_steps = 0;        // training steps that ran as the ordered one-kernel step (EH_MODE_TRAIN_ORD; eh_jit_status reports the count)
+    // optimiser updates launched per update site since the handle was created (host-side counts; eh_jit_status reports the non-zero ones as
+    // "update sites: <name> <count> ...", names in eh_upd_site_name): which kernel applied a step is decided in several places on the host
+    long long upd_site[EH_UPD_SITES] = {0};
     bool specialize_async = false;  // "specialize" = 2
     bool jit_on = true;             // "jit" option / EH_JIT=0: 0 = the interpreting kernels built ahead of time
     bool jit_failed = false;

@@ -617,8 +617,11 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
             if (ap.stamps) { hipMemsetAsync(ap.stamps + 28, 0xff, 8, h->stream); hipMemsetAsync(ap.stamps + 30, 0, 8, h->stream); }
 #endif
             hipLaunchKernelGGL(eh_dw_apply64_kernel, dim3((unsigned)(TG.t0[TG.n] + 8 * ((GG.t0[GG.n] + 7) / 8) + 1)), dim3(256), 0, h->stream, GG, TG, net, ap);
-        } else
+            if (!h->chain.n) ++h->upd_site[EH_UPD_DW_APPLY64];      // (under a chain the epilogue only leaves the gradient, eh_do_step)
+        } else {
         hipLaunchKernelGGL(eh_dw_apply_kernel, dim3((unsigned)(TG.t0[TG.n] + GG.t0[GG.n] + 1)), dim3(256), 0, h->stream, GG, TG, net, ap);
+        if (!h->chain.n) ++h->upd_site[EH_UPD_DW_APPLY];
+        }
         HIPCHK(h, hipGetLastError());
         h->l_applied = true;
         return EH_OK;

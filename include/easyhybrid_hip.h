@@ -653,7 +653,12 @@ int32_t eh_set_target_roles(eh_handle* h, const int32_t* roles, int32_t n);
  * library for a canonical descriptor (the BASELINE.json configurations, csrc/eh_spec.hip).  0 with a non-empty log = a build or a launch
  * was refused, or a compiled kernel disagreed with the one built ahead of time on the first batch (every kernel that merely replaces
  * a generic one is checked before it takes over), and the handle runs the generic / interpreting kernels instead (same results,
- * slower).  log (optional) receives the message, NUL-terminated. */
+ * slower).  log (optional) receives the message, NUL-terminated.  Behind that the log says what ran: "train step kernel: lean | general"
+ * (the last single-step train launch), "ordered steps: N", and "update sites: <name> <count> ..." -- how many optimiser updates each
+ * update site has applied on this handle (host-side counts of the launches, the non-zero ones): reduce16 | reduce64 | reduce256 |
+ * reduce256v4 (eh_reduce_kernel's variants), dw_apply | dw_apply64 (the layer-wise epilogues), fused_flush | ord_flush (a pending
+ * one-kernel step applied on its own), prologue | ord_prologue (applied by the next step's prologue), multi_step (steps of multi-step
+ * launches), dp_apply (eh_dp_apply) and chain (the optimiser-chain kernels). */
 int32_t eh_jit_status(eh_handle* h, int32_t* n_compiled, char* log, int64_t log_bytes);
 
 #ifdef __cplusplus
