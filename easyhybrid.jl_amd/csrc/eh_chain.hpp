@@ -112,7 +112,8 @@ __global__ __launch_bounds__(256) void eh_chain_apply_kernel(const float* __rest
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const EhChainHead hd = eh_chain_head(gradbuf, n_theta, s, im);
-    const bool use_m = o.rule == EH_OPT_ADAM || o.rule == EH_OPT_ADAMW, use_v = use_m || o.rule == EH_OPT_RMSPROP;
+    bool use_m, use_v;
+    eh_opt_keeps(o, use_m, use_v);
     const float bt1 = sc_in[0], bt2 = sc_in[1];
     const int stride = ONE ? 256 : gridDim.x * 256;
     float lam = 1.0f, nrm = 0.0f;
@@ -134,7 +135,8 @@ __global__ __launch_bounds__(256) void eh_chain_apply_kernel(const float* __rest
     const bool upd = hd.cnt > 0.0f && !(c.thr && !finite);
     if (upd) {
         for (int idx = blockIdx.x * 256 + tid; idx < n_theta; idx += stride) {
-            float th = theta[idx], mm = use_m ? m[idx] : 0.0f, vv = use_v ? v[idx] : 0.0f;
+            float th, mm, vv;
+            eh_opt_load_one(theta, m, v, idx, use_m, use_v, th, mm, vv);
             const float x = th;
             float dx = eh_chain_stages(c, 0, c.i_rule, eh_chain_grad(gradbuf, idx, x, s, hd, im), x, lam);
             if (c.i_rule + 1 == c.n) eh_opt_update_at(o, sc_in, idx, dx, bt1, bt2, th, mm, vv);      // the rule last: today's call, today's bits
@@ -151,15 +153,12 @@ __global__ __launch_bounds__(256) void eh_chain_apply_kernel(const float* __rest
                 dx = eh_chain_stages(c, c.i_rule + 1, c.n, dx, x, lam);
                 th = x - dx;
             }
-            theta[idx] = th;
-            if (use_m) m[idx] = mm;
-            if (use_v) v[idx] = vv;
+            eh_opt_store_one(theta, m, v, idx, use_m, use_v, th, mm, vv);
             eh_image_store(im, idx, th);
         }
     }
     if (blockIdx.x == 0 && tid == 0) {
-        sc_out[0] = upd ? bt1 * o.b1 : bt1;
-        sc_out[1] = upd ? bt2 * o.b2 : bt2;
+        eh_opt_advance_one(o, sc_out, upd, bt1, bt2);      // (a chain has one rule: no groups)
         if (s.raw && loss_slot) *loss_slot = hd.loss;      // (not raw: eh_reduce_kernel has written it)
         if (hd.cnt > 0.0f) {
             if (upd) { ctr[0] = ctr[0] + 1ull; if (lam < 1.0f) ctr[1] = ctr[1] + 1ull; }

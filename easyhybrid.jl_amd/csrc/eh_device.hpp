@@ -90,15 +90,19 @@ struct EhOptTab {
 //  left to the compiler the choice depended on the kernel the rule was inlined into -- Descent's `theta - eta * g` came out as one fma in
 //  the multi-step kernel and as two operations in the single-step one: one ulp per step apart, which plain SGD on single-sample
 //  minibatches amplifies to O(1) within a few hundred steps, tests/test_gpu_fuzz.py seed 296)
+// (RULE >= 0: the caller has looked at o.rule and says which it is -- eh_opt_update_all, eh_lform.hpp, does for N elements at once; the
+//  one body either way)
+template <int RULE = -1>
 __device__ __forceinline__ void eh_opt_update(const EhOpt& o, float g, float bt1, float bt2, float& th, float& m, float& v) {
 #pragma clang fp contract(off)
-    if (o.rule == EH_OPT_ADAM || o.rule == EH_OPT_ADAMW) {
+    const auto is = [&](int r) { return RULE < 0 ? o.rule == r : RULE == r; };
+    if (is(EH_OPT_ADAM) || is(EH_OPT_ADAMW)) {
         m = o.b1 * m + (1.0f - o.b1) * g;
         v = o.b2 * v + (1.0f - o.b2) * (g * g);
         float upd = m / (1.0f - bt1) / (sqrtf(v / (1.0f - bt2)) + o.eps) * o.lr;
-        if (o.rule == EH_OPT_ADAMW) upd += o.lr * o.wd * th;     // AdamW(couple = true)
+        if (is(EH_OPT_ADAMW)) upd += o.lr * o.wd * th;           // AdamW(couple = true)
         th -= upd;
-    } else if (o.rule == EH_OPT_RMSPROP) {                       // RMSProp(eta, rho = b1, eps)
+    } else if (is(EH_OPT_RMSPROP)) {                             // RMSProp(eta, rho = b1, eps)
         v = o.b1 * v + (1.0f - o.b1) * (g * g);
         th -= g * (o.lr / (sqrtf(v) + o.eps));
     } else {                                                     // Descent(eta)
@@ -114,6 +118,26 @@ __device__ __forceinline__ void eh_opt_update_at(const EhOpt& o, PB bt, long lon
     const int k = o.tab->gid[i];
     eh_opt_update(o.tab->r[k], g, bt[4 * k], bt[4 * k + 1], th, m, v);
 }
+// one element's state around that call, in place (PT: the caller's pointers, address space and all): theta and the moments the rule
+// keeps in, ... out; eh_opt_apply_one is the three in a row for a site with nothing in between, and returns the new theta
+template <class PT>
+__device__ __forceinline__ void eh_opt_load_one(PT theta, PT m, PT v, long long i, bool use_m, bool use_v, float& th, float& mm, float& vv) {
+    th = theta[i]; mm = use_m ? m[i] : 0.0f; vv = use_v ? v[i] : 0.0f;
+}
+template <class PT>
+__device__ __forceinline__ void eh_opt_store_one(PT theta, PT m, PT v, long long i, bool use_m, bool use_v, float th, float mm, float vv) {
+    theta[i] = th;
+    if (use_m) m[i] = mm;
+    if (use_v) v[i] = vv;
+}
+template <class PT, class PB>
+__device__ __forceinline__ float eh_opt_apply_one(const EhOpt& o, PB bt, PT theta, PT m, PT v, long long i, bool use_m, bool use_v, float g, float bt1, float bt2) {
+    float th, mm, vv;
+    eh_opt_load_one(theta, m, v, i, use_m, use_v, th, mm, vv);
+    eh_opt_update_at(o, bt, i, g, bt1, bt2, th, mm, vv);
+    eh_opt_store_one(theta, m, v, i, use_m, use_v, th, mm, vv);
+    return th;
+}
 // the running products of every group one step on (upd: the step had a valid sample; one thread): bt_in -> bt_out (they may be the same)
 template <class PI, class PO>
 __device__ __forceinline__ void eh_opt_advance_groups(const EhOptTab* tab, PI bt_in, PO bt_out, bool upd) {
@@ -123,6 +147,36 @@ __device__ __forceinline__ void eh_opt_advance_groups(const EhOptTab* tab, PI bt
         bt_out[4 * k] = upd ? p1 * tab->r[k].b1 : p1;
         bt_out[4 * k + 1] = upd ? p2 * tab->r[k].b2 : p2;
     }
+}
+// ... and the one rule's pair, from the values the caller has read (bt1, bt2)
+template <class PO>
+__device__ __forceinline__ void eh_opt_advance_one(const EhOpt& o, PO bt_out, bool upd, float bt1, float bt2) {
+    bt_out[0] = upd ? bt1 * o.b1 : bt1;
+    bt_out[1] = upd ? bt2 * o.b2 : bt2;
+}
+// what every update site's one thread does behind the updates: the groups' products, or the one rule's
+template <class PI, class PO>
+__device__ __forceinline__ void eh_opt_advance(const EhOpt& o, PI bt_in, PO bt_out, bool upd, float bt1, float bt2) {
+    if (o.tab) eh_opt_advance_groups(o.tab, bt_in, bt_out, upd);
+    else eh_opt_advance_one(o, bt_out, upd, bt1, bt2);
+}
+// the LDS parameter image behind a stepped element of the step kernels (wl: the image, in the caller's address space; meta = wl + phi_off;
+// mp: the element's map entry, fetched ahead): a network parameter to its padded place, a raw global to its physical value and sigmoid
+// slope (eh_image_store's arithmetic on the (lower, upper - lower) table of the image)
+template <class PW, class PM>
+__device__ __forceinline__ void eh_image_refresh_lds(PW wl, PM meta, int phi_off, int g_off, int idx, int mp, float th) {
+    if (idx < g_off) wl[mp] = th;
+    else {
+        const int j = __float_as_int(meta[EH_IMG_GPAR + idx - g_off]);
+        const float sg = 1.0f / (1.0f + expf(-th)), sc = meta[EH_IMG_SC + j];
+        wl[phi_off + EH_IMG_PHI + j] = meta[EH_IMG_LO + j] + sc * sg;
+        wl[phi_off + EH_IMG_DPHI + j] = sc * sg * (1.0f - sg);
+    }
+}
+// the state a rule keeps (a site loads and stores only that): RMSProp has no first moment, Descent none at all
+__device__ __forceinline__ void eh_opt_keeps(const EhOpt& o, bool& use_m, bool& use_v) {
+    use_m = o.rule == EH_OPT_ADAM || o.rule == EH_OPT_ADAMW;
+    use_v = use_m || o.rule == EH_OPT_RMSPROP;
 }
 
 // From the batch sums to the loss value and the factor that turns the accumulated un-normalised
@@ -1512,13 +1566,7 @@ __device__ __forceinline__ void eh_ms_apply(const NET& net, const EhStepArgs& a,
         if (upd) {
             eh_opt_update_at(z.opt, sc, idx, gsum[idx] * inv, bt1, bt2, th, mm, vv);
             P[idx] = th; P[nth + idx] = mm; P[2 * nth + idx] = vv;
-            if (idx < net.g_off) wl[mp] = th;
-            else {
-                const int j = __float_as_int(meta[EH_IMG_GPAR + idx - net.g_off]);
-                const float sg = 1.0f / (1.0f + expf(-th)), scl = meta[EH_IMG_SC + j];
-                wl[G::PHI_OFF + EH_IMG_PHI + j] = meta[EH_IMG_LO + j] + scl * sg;
-                wl[G::PHI_OFF + EH_IMG_DPHI + j] = scl * sg * (1.0f - sg);
-            }
+            eh_image_refresh_lds(wl, meta, G::PHI_OFF, net.g_off, idx, mp, th);
         }
     }
     // (no second barrier: the beta products were read before the barrier above, and the sums are overwritten -- plain stores, one writer per
@@ -1526,7 +1574,7 @@ __device__ __forceinline__ void eh_ms_apply(const NET& net, const EhStepArgs& a,
     if (grouped) __syncthreads();      // (per-branch rules: the updates above read every group's products from LDS, in place)
     if (tid == 0) {
         if (grouped) eh_opt_advance_groups(z.opt.tab, sc, sc, upd);
-        else if (upd) { sc[0] = bt1 * z.opt.b1; sc[1] = bt2 * z.opt.b2; }
+        else if (upd) eh_opt_advance_one(z.opt, sc, true, bt1, bt2);      // (in place: a step without a sample stores nothing)
         if (a.ms_loss) *a.ms_loss = lossv;
     }
 }
@@ -2035,14 +2083,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
             }
             if (upd) eh_opt_update_at(z.opt, z.pset + 6 * nth + 2 * z.sc_sel, idx, gs * inv, f_bt1, f_bt2, th, mm, vv);
             if (((unsigned)idx & gmask) == blockIdx.x) { pout[idx] = th; pout[nth + idx] = mm; pout[2 * nth + idx] = vv; }   // every workgroup holds the same values: spread the stores
-            if (idx < net.g_off) {
-                wl[mp] = th;
-            } else {
-                const int j = __float_as_int(meta[EH_IMG_GPAR + idx - net.g_off]);
-                const float sg = 1.0f / (1.0f + expf(-th)), sc = meta[EH_IMG_SC + j];
-                wl[G::PHI_OFF + EH_IMG_PHI + j] = meta[EH_IMG_LO + j] + sc * sg;
-                wl[G::PHI_OFF + EH_IMG_DPHI + j] = sc * sg * (1.0f - sg);
-            }
+            eh_image_refresh_lds(wl, meta, G::PHI_OFF, net.g_off, idx, mp, th);
         }
         EH_STAMP_PRO(7);
         // (the pending step's rows back to EH_ORD_EMPTY: stores issued behind every load of the prologue, so that no wait for a load
@@ -2050,11 +2091,7 @@ __device__ __forceinline__ void eh_step_body(const EhNet& net_rt, const EhStepAr
         if constexpr (ORDM) { if (own_direct) eh_ord_reset(a.ord, blockIdx.x, gridDim.x, tid, NTHR); }
         if (blockIdx.x == 0 && tid == 0) {
             float* const sc_out = z.pset + 6 * nth + 2 * (z.sc_sel ^ 1);
-            if (z.opt.tab) eh_opt_advance_groups(z.opt.tab, z.pset + 6 * nth + 2 * z.sc_sel, sc_out, upd);
-            else {
-                sc_out[0] = upd ? f_bt1 * z.opt.b1 : f_bt1;
-                sc_out[1] = upd ? f_bt2 * z.opt.b2 : f_bt2;
-            }
+            eh_opt_advance(z.opt, z.pset + 6 * nth + 2 * z.sc_sel, sc_out, upd, f_bt1, f_bt2);
             if (z.loss_slot && z.pending) *z.loss_slot = (ORDM && upd) ? lossv + 0.0f : lossv;      // (ORDM: as eh_reduce_kernel, which adds its extra-loss term 0)
         }
         if constexpr (!ORDM)       // (ORDM: the shards take no adds)

@@ -61,6 +61,13 @@ __device__ __forceinline__ void eh_image_store(const EhImg& im, int idx, float t
         im.image[im.phi_off + EH_IMG_DPHI + j] = (im.ghi[g] - im.glo[g]) * s * (1.0f - s);
     }
 }
+// the same store with the map entry fetched ahead, next to the element's state (a site that waits for ONE memory round trip):
+// eh_image_map with the loads, eh_image_refresh behind the update.  -1: nothing to store for a network parameter (no map, or no place)
+__device__ __forceinline__ int eh_image_map(const EhImg& im, int idx) { return (idx < im.g_off && im.imap) ? im.imap[idx] : -1; }
+__device__ __forceinline__ void eh_image_refresh(const EhImg& im, int idx, int mp, float th) {
+    if (idx < im.g_off) { if (mp >= 0) im.image[mp] = th; }
+    else eh_image_store(im, idx, th);
+}
 
 // an optimiser chain (eh_opt_init_chain; the kernels are in eh_chain.hpp): handed to them by value
 struct EhChain {

@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
     const bool full = VEC && idx0 + NC - 1 < n_theta;     // all of the thread's columns are parameters: the 16-byte path
     // optimiser inputs are independent of the slab: request them first so they arrive together (only the state the rule keeps:
     // RMSProp has no first moment, Descent none at all)
-    const bool use_m = o.rule == EH_OPT_ADAM || o.rule == EH_OPT_ADAMW, use_v = use_m || o.rule == EH_OPT_RMSPROP;
+    bool use_m, use_v;
+    eh_opt_keeps(o, use_m, use_v);
     float th[NC], mm[NC], vv[NC], bt1 = 0.0f, bt2 = 0.0f;
     int mp[NC];
 #pragma unroll
@@ -66,10 +67,9 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
             if (APPLY || l2val) { const f32x4u t4 = *reinterpret_cast<const f32x4u*>(theta + idx0); th[0] = t4[0]; th[1] = t4[1]; th[2] = t4[2]; th[3] = t4[3]; }
             if (APPLY && use_m) { const f32x4u t4 = *reinterpret_cast<const f32x4u*>(m + idx0); mm[0] = t4[0]; mm[1] = t4[1]; mm[2] = t4[2]; mm[3] = t4[3]; }
             if (APPLY && use_v) { const f32x4u t4 = *reinterpret_cast<const f32x4u*>(v + idx0); vv[0] = t4[0]; vv[1] = t4[1]; vv[2] = t4[2]; vv[3] = t4[3]; }
-            if (APPLY && im.imap) {
+            if (APPLY) {
 #pragma unroll
-                for (int j = 0; j < NC; ++j)
-                    if (idx0 + j < im.g_off) mp[j] = im.imap[idx0 + j];
+                for (int j = 0; j < NC; ++j) mp[j] = eh_image_map(im, idx0 + j);
             }
         }
     } else {
@@ -77,10 +77,8 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
         for (int j = 0; j < NC; ++j) {
             const int idx = idx0 + CS * j;
             if (APPLY && q == 0 && idx < n_theta) {
-                th[j] = theta[idx];
-                if (use_m) mm[j] = m[idx];
-                if (use_v) vv[j] = v[idx];
-                if (idx < im.g_off && im.imap) mp[j] = im.imap[idx];
+                eh_opt_load_one(theta, m, v, idx, use_m, use_v, th[j], mm[j], vv[j]);
+                mp[j] = eh_image_map(im, idx);
             }
             if (!APPLY && l2val && q == 0 && idx < n_theta) th[j] = theta[idx];
         }
@@ -200,10 +198,7 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
                 if (use_m) *reinterpret_cast<f32x4u*>(m + idx0) = f32x4u{mm[0], mm[1], mm[2], mm[3]};
                 if (use_v) *reinterpret_cast<f32x4u*>(v + idx0) = f32x4u{vv[0], vv[1], vv[2], vv[3]};
 #pragma unroll
-                for (int j = 0; j < NC; ++j) {
-                    if (idx0 + j < im.g_off) { if (mp[j] >= 0) im.image[mp[j]] = th[j]; }
-                    else eh_image_store(im, idx0 + j, th[j]);
-                }
+                for (int j = 0; j < NC; ++j) eh_image_refresh(im, idx0 + j, mp[j], th[j]);
             }
         }
     } else {
@@ -223,11 +218,8 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
                 gradbuf[idx] = g;
                 if (APPLY && ntot > 0.0f) {
                     eh_opt_update_at(o, sc_in, idx, g, bt1, bt2, th[j], mm[j], vv[j]);
-                    theta[idx] = th[j];
-                    if (use_m) m[idx] = mm[j];
-                    if (use_v) v[idx] = vv[j];
-                    if (idx < im.g_off) { if (mp[j] >= 0) im.image[mp[j]] = th[j]; }
-                    else eh_image_store(im, idx, th[j]);
+                    eh_opt_store_one(theta, m, v, idx, use_m, use_v, th[j], mm[j], vv[j]);
+                    eh_image_refresh(im, idx, mp[j], th[j]);
                 }
             } else if (idx == n_theta) {
                 const float loss = ntot > 0.0f ? (deferred ? dloss : tot + tp_loss) + (l2val ? *l2val : 0.0f) : __builtin_nanf("");      // agg = sum([loss, extra...]), compute_loss.jl:31-34
@@ -240,11 +232,7 @@ __global__ __launch_bounds__(256) void eh_reduce_kernel(const float* __restrict_
     }
     }
     if (APPLY && blockIdx.x == 0 && tid == 0) {
-        if (o.tab) eh_opt_advance_groups(o.tab, sc_in, sc_out, ntot > 0.0f);
-        else {
-            sc_out[0] = ntot > 0.0f ? sc_in[0] * o.b1 : sc_in[0];
-            sc_out[1] = ntot > 0.0f ? sc_in[1] * o.b2 : sc_in[1];
-        }
+        eh_opt_advance(o, sc_in, sc_out, ntot > 0.0f, sc_in[0], sc_in[1]);
     }
 }
 
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
     int mp0 = -1;
 #pragma unroll
     for (int sh = 0; sh < EH_GSHARDS; ++sh) gsv[sh] = (own && !p2p) ? g_prev[sh * n_acc + idx] : 0.0f;
-    if (own) { th0 = theta[idx]; mm0 = m[idx]; vv0 = v[idx]; if (idx < im.g_off && im.imap) mp0 = im.imap[idx]; }
+    if (own) { eh_opt_load_one(theta, m, v, idx, true, true, th0, mm0, vv0); mp0 = eh_image_map(im, idx); }
     const float sc0 = sc_in[0], sc1 = sc_in[1];
     if (p2p) {       // every rank's sums of the last step, straight from the receive shards (see EhP2P)
         // mode 1: nobody has published the last step yet -- block 0 does it for the peers; this rank's own sums come from its staging shards
@@ -320,18 +308,11 @@ __global__ __launch_bounds__(256) void eh_fused_flush_kernel(const float* g_prev
         const float gs = p2p ? gs_p2p : eh_fold8(gsv[0], gsv[1], gsv[2], gsv[3], gsv[4], gsv[5], gsv[6], gsv[7]);
         float mm = mm0, vv = vv0;
         eh_opt_update_at(o, sc_in, idx, gs * inv, sc0, sc1, th, mm, vv);
-        theta[idx] = th; m[idx] = mm; v[idx] = vv;
+        eh_opt_store_one(theta, m, v, idx, true, true, th, mm, vv);
     }
-    if (own) {
-        if (idx < im.g_off) { if (mp0 >= 0) im.image[mp0] = th; }
-        else eh_image_store(im, idx, th);
-    }
+    if (own) eh_image_refresh(im, idx, mp0, th);
     if (idx == 0) {
-        if (o.tab) eh_opt_advance_groups(o.tab, sc_in, sc_out, cnt > 0.0f);
-        else {
-            sc_out[0] = cnt > 0.0f ? sc0 * o.b1 : sc0;
-            sc_out[1] = cnt > 0.0f ? sc1 * o.b2 : sc1;
-        }
+        eh_opt_advance(o, sc_in, sc_out, cnt > 0.0f, sc0, sc1);
         if (loss_slot) *loss_slot = lossv;
     }
 }
@@ -351,7 +332,7 @@ __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_
     eh_ord_scalar_loads(o, lane, sv);
     float th = 0.0f, mm = 0.0f, vv = 0.0f;
     int mp = -1;
-    if (own) { th = theta[idx]; mm = m[idx]; vv = v[idx]; if (idx < im.g_off && im.imap) mp = im.imap[idx]; }
+    if (own) { eh_opt_load_one(theta, m, v, idx, true, true, th, mm, vv); mp = eh_image_map(im, idx); }
     const float bt1 = sc_in[0], bt2 = sc_in[1];
     const f32x4 t = eh_ord_scalar_fold(o, lane, sv);
     float inv = 1.0f, lossv = 0.0f;
@@ -359,18 +340,11 @@ __global__ __launch_bounds__(256) void eh_ord_flush_kernel(const EhOrd o, int n_
     const bool upd = t[1] > 0.0f;
     if (own && upd) {
         eh_opt_update_at(op, sc_in, idx, eh_ord_group_fold(gv) * inv, bt1, bt2, th, mm, vv);
-        theta[idx] = th; m[idx] = mm; v[idx] = vv;
+        eh_opt_store_one(theta, m, v, idx, true, true, th, mm, vv);
     }
-    if (own) {
-        if (idx < im.g_off) { if (mp >= 0) im.image[mp] = th; }
-        else eh_image_store(im, idx, th);
-    }
+    if (own) eh_image_refresh(im, idx, mp, th);
     if (idx == 0) {
-        if (op.tab) eh_opt_advance_groups(op.tab, sc_in, sc_out, upd);
-        else {
-            sc_out[0] = upd ? bt1 * op.b1 : bt1;
-            sc_out[1] = upd ? bt2 * op.b2 : bt2;
-        }
+        eh_opt_advance(op, sc_in, sc_out, upd, bt1, bt2);
         if (loss_slot) *loss_slot = upd ? lossv + 0.0f : __builtin_nanf("");
     }
 }
@@ -473,18 +447,15 @@ __global__ __launch_bounds__(256) void eh_apply_kernel(float* gradbuf, int n_the
     if (l2val && cnt > 0.0f) lossv += *l2val;                  // + lambda * weight_l2 of the (replicated) parameters: agg = sum([loss, extra...]), compute_loss.jl:31-34
     if (idx < n_theta && cnt > 0.0f) {
         float g = gradbuf[idx] * scale;
-        float th = theta[idx], mm = m[idx], vv = v[idx];
+        float th, mm, vv;
+        eh_opt_load_one(theta, m, v, idx, true, true, th, mm, vv);
         if (l2val) { const float c2 = eh_l2_coef(im, idx); if (c2 != 0.0f) g = fmaf(2.0f * c2, th, g); }
         eh_opt_update_at(o, sc_in, idx, g, sc_in[0], sc_in[1], th, mm, vv);
-        theta[idx] = th; m[idx] = mm; v[idx] = vv;
+        eh_opt_store_one(theta, m, v, idx, true, true, th, mm, vv);
         eh_image_store(im, idx, th);
     }
     if (idx == 0) {
-        if (o.tab) eh_opt_advance_groups(o.tab, sc_in, sc_out, cnt > 0.0f);
-        else {
-            sc_out[0] = cnt > 0.0f ? sc_in[0] * o.b1 : sc_in[0];
-            sc_out[1] = cnt > 0.0f ? sc_in[1] * o.b2 : sc_in[1];
-        }
+        eh_opt_advance(o, sc_in, sc_out, cnt > 0.0f, sc_in[0], sc_in[1]);
         if (loss_slot) *loss_slot = lossv;
     }
 }

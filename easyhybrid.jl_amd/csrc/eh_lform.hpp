@@ -61,37 +61,37 @@ struct EhLApplyS { float* slab; float* theta; float* m; float* v; EhOpt o; float
 //  flat load that had to be repeated behind every global store -- 13 k cycles for sixteen updates.  The epilogues take ONE copy into registers.)
 typedef __attribute__((address_space(1))) float eh_gfloat;      // (pointers that come out of an LDS copy are generic: say that they are global)
 __device__ __forceinline__ void eh_lapply_one(const EhLApplyS& S, const float* cslot, float gsum) {
-    const long long idx = cslot - S.slab;
-    eh_gfloat* const tp = (eh_gfloat*)S.theta; eh_gfloat* const mp = (eh_gfloat*)S.m; eh_gfloat* const vp = (eh_gfloat*)S.v;
-    float th = tp[idx], mm = S.use_m ? mp[idx] : 0.0f, vv = S.use_v ? vp[idx] : 0.0f;
-    eh_opt_update_at(S.o, S.bt, idx, gsum * S.scale, S.bt1, S.bt2, th, mm, vv);
-    tp[idx] = th;
-    if (S.use_m) mp[idx] = mm;
-    if (S.use_v) vp[idx] = vv;
+    eh_opt_apply_one(S.o, S.bt, (eh_gfloat*)S.theta, (eh_gfloat*)S.m, (eh_gfloat*)S.v, cslot - S.slab, S.use_m != 0, S.use_v != 0, gsum * S.scale, S.bt1, S.bt2);
+}
+// the N elements of a thread at ix[] (on[j]: the ones that exist -- an array, or a rule that costs no registers: EhOnAll, EhThinOn): every load of theta and of the moments the rule keeps issued in a row --
+// one round trip, not N --, and every store; the caller puts all its updates and the compiler fence between the two
+struct EhOnAll { __device__ __forceinline__ bool operator[](int) const { return true; } };
+template <int N, class ON>
+__device__ __forceinline__ void eh_lstate_load(eh_gfloat* tp, eh_gfloat* mp, eh_gfloat* vp, const long long (&ix)[N], const ON& on, bool use_m, bool use_v,
+                                               float (&th)[N], float (&mm)[N], float (&vv)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        th[j] = on[j] ? tp[ix[j]] : 0.0f;
+        mm[j] = (on[j] && use_m) ? mp[ix[j]] : 0.0f;
+        vv[j] = (on[j] && use_v) ? vp[ix[j]] : 0.0f;
+    }
+}
+template <int N, class ON>
+__device__ __forceinline__ void eh_lstate_store(eh_gfloat* tp, eh_gfloat* mp, eh_gfloat* vp, const long long (&ix)[N], const ON& on, bool use_m, bool use_v,
+                                                const float (&th)[N], const float (&mm)[N], const float (&vv)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+        if (on[j]) eh_opt_store_one(tp, mp, vp, ix[j], use_m, use_v, th[j], mm[j], vv[j]);
 }
 
 // N independent elements through the update rule, the rule looked at ONCE: inside eh_opt_update the rule is a branch per element, and
 // sixteen unrolled copies of it keep the compiler from interleaving the sixteen dependent chains (an IEEE square root and two IEEE
-// divisions each: 7.7 k cycles for the sixteen elements of a thread, one wave per SIMD).  Same arithmetic, op for op: this IS
-// eh_opt_update with the rule hoisted (tests/test_gpu_lform.py trains through both and meets the same oracle trajectory).
+// divisions each: 7.7 k cycles for the sixteen elements of a thread, one wave per SIMD).  The one body of the rule, eh_opt_update, told
+// which rule it is.
 template <int RULE, int N>
 __device__ __forceinline__ void eh_opt_update_n(const EhOpt& o, const float (&g)[N], float bt1, float bt2, float (&th)[N], float (&m)[N], float (&v)[N]) {
-#pragma clang fp contract(off)
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-        if constexpr (RULE == EH_OPT_ADAM || RULE == EH_OPT_ADAMW) {
-            m[i] = o.b1 * m[i] + (1.0f - o.b1) * g[i];
-            v[i] = o.b2 * v[i] + (1.0f - o.b2) * (g[i] * g[i]);
-            float upd = m[i] / (1.0f - bt1) / (sqrtf(v[i] / (1.0f - bt2)) + o.eps) * o.lr;
-            if constexpr (RULE == EH_OPT_ADAMW) upd += o.lr * o.wd * th[i];
-            th[i] -= upd;
-        } else if constexpr (RULE == EH_OPT_RMSPROP) {
-            v[i] = o.b1 * v[i] + (1.0f - o.b1) * (g[i] * g[i]);
-            th[i] -= g[i] * (o.lr / (sqrtf(v[i]) + o.eps));
-        } else {
-            th[i] -= o.lr * g[i];
-        }
-    }
+    for (int i = 0; i < N; ++i) eh_opt_update<RULE>(o, g[i], bt1, bt2, th[i], m[i], v[i]);
 }
 template <int N>
 __device__ __forceinline__ void eh_opt_update_all(const EhOpt& o, const float (&g)[N], float bt1, float bt2, float (&th)[N], float (&m)[N], float (&v)[N]) {
@@ -167,17 +167,14 @@ __device__ __forceinline__ void eh_gemm_tile(const EhGemmArgs& g, const int bx, 
     long long ap_ix[16];
     if constexpr (EPI == EH_GEPI_APPLY) {
         static_assert(EPI != EH_GEPI_APPLY || BT == 64, "apply epilogue: one MFMA tile per wave");
-        eh_gfloat* const tp = (eh_gfloat*)S.theta; eh_gfloat* const mp = (eh_gfloat*)S.m; eh_gfloat* const vp = (eh_gfloat*)S.v;
         const int n = min(n0 + wn * WT + l32, g.N - 1);
         const float* const Cb = g.C + (long long)bz * g.c_zstride;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = min(m0 + wm * WT + (r & 3) + 8 * (r >> 2) + 4 * lh, g.M - 1);
             ap_ix[r] = (Cb + (long long)m * g.ldc + n) - S.slab;
-            ap_th[r] = tp[ap_ix[r]];
-            ap_m[r] = S.use_m ? mp[ap_ix[r]] : 0.0f;
-            ap_v[r] = S.use_v ? vp[ap_ix[r]] : 0.0f;
         }
+        eh_lstate_load<16>((eh_gfloat*)S.theta, (eh_gfloat*)S.m, (eh_gfloat*)S.v, ap_ix, EhOnAll{}, S.use_m != 0, S.use_v != 0, ap_th, ap_m, ap_v);
     }
     const bool do_cs_v = (EPI == EH_GEPI_STORE || EPI == EH_GEPI_APPLY) && g.colsum != nullptr && by == 0 && tid < BN;
     float cs_v = 0.0f;
@@ -355,22 +352,16 @@ __device__ __forceinline__ void eh_gemm_tile(const EhGemmArgs& g, const int bx, 
                     // every update, then the stores -- a store between two updates made the next one wait for the store's acknowledgement
                     // (loads and stores share one counter and may complete out of order: the compiler waits for zero), sixteen round
                     // trips in a row: 13 k of the workgroup's 28 k cycles (tools/stamps_lform.py, EH_STAMP_DW)
-                    eh_gfloat* const tp = (eh_gfloat*)S.theta; eh_gfloat* const mp = (eh_gfloat*)S.m; eh_gfloat* const vp = (eh_gfloat*)S.v;
                     float gg[16];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) gg[r] = acc[i][j][r] * S.scale;
                     EH_LSTAMP(Sp, 3);
                     eh_opt_update_all_at<16>(S.o, S.bt, ap_ix, gg, S.bt1, S.bt2, ap_th, ap_m, ap_v);
                     asm volatile("" ::: "memory");
+                    bool ap_on[16];      // (the rows that exist: the loads took every element, rows beyond the matrix clamped)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int m = m0 + wm * WT + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (m < g.M) {
-                            tp[ap_ix[r]] = ap_th[r];
-                            if (S.use_m) mp[ap_ix[r]] = ap_m[r];
-                            if (S.use_v) vp[ap_ix[r]] = ap_v[r];
-                        }
-                    }
+                    for (int r = 0; r < 16; ++r) ap_on[r] = m0 + wm * WT + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh < g.M;
+                    eh_lstate_store<16>((eh_gfloat*)S.theta, (eh_gfloat*)S.m, (eh_gfloat*)S.v, ap_ix, ap_on, S.use_m != 0, S.use_v != 0, ap_th, ap_m, ap_v);
                 }
                 continue;
             }
@@ -428,6 +419,19 @@ struct EhThinArgs {
     float* C; long long c_col, c_j, c_z;
     float* cs_wide; float* cs_thin; long long cs_z;
 };
+// (optimiser in the epilogue) the nine elements of flat theta that the thread of column `col` owns: the J outputs of its column and the
+// column sum of `wide`; EhThinOn: the ones this product has (the others point at an element that exists and are neither loaded nor stored)
+struct EhThinOn {
+    int J; bool cs;
+    __device__ __forceinline__ bool operator[](int j) const { return j < 8 ? j < J : cs; }
+};
+__device__ __forceinline__ void eh_thin_slots(const EhThinArgs& a, int col, const float* slab, long long (&ix)[9]) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const float* const slot = j < 8 ? a.C + (long long)col * a.c_col + (long long)min(j, a.J - 1) * a.c_j : (a.cs_wide ? a.cs_wide + col : a.C);
+        ix[j] = slot - slab;
+    }
+}
 template <bool APPLY = false>
 __device__ __forceinline__ void eh_thin_gemm_tile(const EhThinArgs& a, const int bx, const int by, const EhLApplyS* const Sp = nullptr) {
     EhLApplyS S{};
@@ -479,32 +483,16 @@ __device__ __forceinline__ void eh_thin_gemm_tile(const EhThinArgs& a, const int
             if (q == 0 && live) {
                 // (all of the thread's parameters and moments requested before the first update, every update before the first store: see eh_gemm_tile)
                 long long ix[9];
+                const EhThinOn on{a.J, a.cs_wide != nullptr};
                 float th[9], mm[9], vv[9];
                 eh_gfloat* const tp = (eh_gfloat*)S.theta; eh_gfloat* const mp = (eh_gfloat*)S.m; eh_gfloat* const vp = (eh_gfloat*)S.v;
+                eh_thin_slots(a, col, S.slab, ix);
+                eh_lstate_load<9>(tp, mp, vp, ix, on, S.use_m != 0, S.use_v != 0, th, mm, vv);
 #pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                    const float* const slot = j < 8 ? a.C + (long long)col * a.c_col + (long long)min(j, a.J - 1) * a.c_j : (a.cs_wide ? a.cs_wide + col : a.C);
-                    ix[j] = slot - S.slab;
-                    th[j] = on ? tp[ix[j]] : 0.0f;
-                    mm[j] = (on && S.use_m) ? mp[ix[j]] : 0.0f;
-                    vv[j] = (on && S.use_v) ? vp[ix[j]] : 0.0f;
-                }
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                    if (on) eh_opt_update_at(S.o, S.bt, ix[j], ((red[0][cl][j] + red[1][cl][j]) + (red[2][cl][j] + red[3][cl][j])) * S.scale, S.bt1, S.bt2, th[j], mm[j], vv[j]);
-                }
+                for (int j = 0; j < 9; ++j)
+                    if (on[j]) eh_opt_update_at(S.o, S.bt, ix[j], ((red[0][cl][j] + red[1][cl][j]) + (red[2][cl][j] + red[3][cl][j])) * S.scale, S.bt1, S.bt2, th[j], mm[j], vv[j]);
                 asm volatile("" ::: "memory");
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                    if (on) {
-                        tp[ix[j]] = th[j];
-                        if (S.use_m) mp[ix[j]] = mm[j];
-                        if (S.use_v) vp[ix[j]] = vv[j];
-                    }
-                }
+                eh_lstate_store<9>(tp, mp, vp, ix, on, S.use_m != 0, S.use_v != 0, th, mm, vv);
             }
             if (a.cs_thin && bx == 0 && tid < a.J) eh_lapply_one(S, a.cs_thin + tid, (redt[0][tid] + redt[1][tid]) + (redt[2][tid] + redt[3][tid]));
         }
@@ -1631,6 +1619,25 @@ __global__ __launch_bounds__(EH_LTAIL_THREADS, 1) void eh_lform_tailchain_kernel
 // and puts its elements through the update rule; the last workgroup updates the global parameters, writes the loss and advances the
 // running beta products -- what eh_lform_tail_kernel + eh_reduce_kernel<APPLY> did in two more launches.  One target, a loss without
 // batch moments, no weight_l2 (the host checks; everything else takes the slab and the reduce kernel as before).
+// (the workgroup of both epilogue kernels that has no product: tot = the step's sums [grad of the raw globals (8) | S | n_t (4) | Sy | Syy] in LDS)
+__device__ __forceinline__ void eh_lapply_globals(const EhNet& net, const EhLApply& ap, const float* tot, int tid, float scale, float loss, bool go,
+                                                  bool use_m, bool use_v, float bt1, float bt2) {
+    const int ng = net.n_theta - net.g_off;
+    if (tid < ng && go) {
+        float gsum = 0.0f;
+#pragma unroll
+        for (int j = 0; j < EH_MAX_PARAMS; ++j)
+            if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL && (int)((net.par_idx >> (4 * j)) & 15u) == tid) gsum = tot[j];
+        const int idx = net.g_off + tid;
+        eh_image_store(ap.im, idx, eh_opt_apply_one(ap.o, ap.sc_in, ap.theta, ap.m, ap.v, idx, use_m, use_v, gsum * scale, bt1, bt2));
+    }
+    if (tid == 0) {
+        eh_opt_advance(ap.o, ap.sc_in, ap.sc_out, go, bt1, bt2);
+        ap.gradbuf[net.n_theta] = loss;                             // (what eh_reduce_kernel leaves behind the gradient: loss, count, Sy, Syy -- the gradient itself is not kept)
+        ap.gradbuf[net.n_theta + 1] = tot[9]; ap.gradbuf[net.n_theta + 2] = tot[13]; ap.gradbuf[net.n_theta + 3] = tot[14];
+        if (ap.loss_slot) *ap.loss_slot = loss;
+    }
+}
 __global__ __launch_bounds__(256) void eh_dw_apply_kernel(const EhGemmGroup G, const EhThinGroup T, const EhNet net, const EhLApply ap) {
     __shared__ float tot[EH_LMECH_PART], red[16][EH_LMECH_PART];
     __shared__ EhLApplyS S;
@@ -1659,38 +1666,16 @@ __global__ __launch_bounds__(256) void eh_dw_apply_kernel(const EhGemmGroup G, c
     if (tid == 0) {
         S.slab = ap.slab; S.theta = ap.theta; S.m = ap.m; S.v = ap.v; S.o = ap.o; S.scale = scale; S.bt1 = ap.sc_in[0]; S.bt2 = ap.sc_in[1]; S.bt = ap.sc_in;
         S.go = go ? 1 : 0;
-        S.use_m = (ap.o.rule == EH_OPT_ADAM || ap.o.rule == EH_OPT_ADAMW) ? 1 : 0;
-        S.use_v = (S.use_m || ap.o.rule == EH_OPT_RMSPROP) ? 1 : 0;
+        bool use_m, use_v;
+        eh_opt_keeps(ap.o, use_m, use_v);
+        S.use_m = use_m ? 1 : 0; S.use_v = use_v ? 1 : 0;
         S.stamps = (int)blockIdx.x == ap.stamp_wg ? ap.stamps : nullptr;
     }
     __syncthreads();
     EH_LSTAMP(&S, 1);
     const int nthin = T.t0[T.n], ntile = G.t0[G.n];
     if ((int)blockIdx.x == nthin + ntile) {                              // the global parameters, the loss, the beta products
-        const int ng = net.n_theta - net.g_off;
-        if (tid < ng && go) {
-            float gsum = 0.0f;
-#pragma unroll
-            for (int j = 0; j < EH_MAX_PARAMS; ++j)
-                if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL && (int)((net.par_idx >> (4 * j)) & 15u) == tid) gsum = tot[j];
-            const int idx = net.g_off + tid;
-            float th = ap.theta[idx], mm = S.use_m ? ap.m[idx] : 0.0f, vv = S.use_v ? ap.v[idx] : 0.0f;
-            eh_opt_update_at(ap.o, ap.sc_in, idx, gsum * scale, S.bt1, S.bt2, th, mm, vv);
-            ap.theta[idx] = th;
-            if (S.use_m) ap.m[idx] = mm;
-            if (S.use_v) ap.v[idx] = vv;
-            eh_image_store(ap.im, idx, th);
-        }
-        if (tid == 0) {
-            if (ap.o.tab) eh_opt_advance_groups(ap.o.tab, ap.sc_in, ap.sc_out, go);
-            else {
-                ap.sc_out[0] = go ? S.bt1 * ap.o.b1 : S.bt1;
-                ap.sc_out[1] = go ? S.bt2 * ap.o.b2 : S.bt2;
-            }
-            ap.gradbuf[net.n_theta] = loss;                             // (what eh_reduce_kernel leaves behind the gradient: loss, count, Sy, Syy -- the gradient itself is not kept)
-            ap.gradbuf[net.n_theta + 1] = tot[9]; ap.gradbuf[net.n_theta + 2] = tot[13]; ap.gradbuf[net.n_theta + 3] = tot[14];
-            if (ap.loss_slot) *ap.loss_slot = loss;
-        }
+        eh_lapply_globals(net, ap, tot, tid, scale, loss, go, S.use_m != 0, S.use_v != 0, S.bt1, S.bt2);
         return;
     }
     if ((int)blockIdx.x < nthin) {
@@ -1757,7 +1742,8 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
     EH_A64(12);
     const float tv = tid < EH_LMECH_PART ? ap.tot[tid] : 0.0f;
     const float bt1 = ap.sc_in[0], bt2 = ap.sc_in[1];
-    const bool use_m = ap.o.rule == EH_OPT_ADAM || ap.o.rule == EH_OPT_ADAMW, use_v = use_m || ap.o.rule == EH_OPT_RMSPROP;
+    bool use_m, use_v;
+    eh_opt_keeps(ap.o, use_m, use_v);
     eh_gfloat* const tp = (eh_gfloat*)ap.theta; eh_gfloat* const mp = (eh_gfloat*)ap.m; eh_gfloat* const vp = (eh_gfloat*)ap.v;
     // workgroup -> work: [0, 8 Q) tile slots, then the thin products, then one for the global parameters.  Slot s runs tile (s % 8) Q + s / 8:
     // consecutive workgroups land on consecutive XCDs, so XCD x works on tiles [x Q, (x + 1) Q) -- a contiguous range of rows of every
@@ -1773,30 +1759,7 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
         float scale, loss;
         eh_loss_finish(ap.loss_kind, totl[8], totl[9], totl[13], totl[14], scale, loss, ap.im.agg_a);
         const bool go = totl[9] > 0.0f;
-        const int ng = net.n_theta - net.g_off;
-        if (tid < ng && go) {
-            float gsum = 0.0f;
-#pragma unroll
-            for (int j = 0; j < EH_MAX_PARAMS; ++j)
-                if (j < net.n_par && ((net.par_kind >> (2 * j)) & 3u) == EH_PAR_GLOBAL && (int)((net.par_idx >> (4 * j)) & 15u) == tid) gsum = totl[j];
-            const int idx = net.g_off + tid;
-            float th = ap.theta[idx], mm = use_m ? ap.m[idx] : 0.0f, vv = use_v ? ap.v[idx] : 0.0f;
-            eh_opt_update_at(ap.o, ap.sc_in, idx, gsum * scale, bt1, bt2, th, mm, vv);
-            ap.theta[idx] = th;
-            if (use_m) ap.m[idx] = mm;
-            if (use_v) ap.v[idx] = vv;
-            eh_image_store(ap.im, idx, th);
-        }
-        if (tid == 0) {
-            if (ap.o.tab) eh_opt_advance_groups(ap.o.tab, ap.sc_in, ap.sc_out, go);
-            else {
-                ap.sc_out[0] = go ? bt1 * ap.o.b1 : bt1;
-                ap.sc_out[1] = go ? bt2 * ap.o.b2 : bt2;
-            }
-            ap.gradbuf[net.n_theta] = loss;
-            ap.gradbuf[net.n_theta + 1] = totl[9]; ap.gradbuf[net.n_theta + 2] = totl[13]; ap.gradbuf[net.n_theta + 3] = totl[14];
-            if (ap.loss_slot) *ap.loss_slot = loss;
-        }
+        eh_lapply_globals(net, ap, totl, tid, scale, loss, go, use_m, use_v, bt1, bt2);
         return;
     }
     if (wg >= slots) {
@@ -1810,17 +1773,11 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
         const int cl = lane, q = wave, col = bx * 64 + cl;
         const bool live = col < a.ncols;
         long long ix[9];
+        const EhThinOn on{a.J, a.cs_wide != nullptr};
         float th[9], mm[9], vv[9];
         if (q == 0 && live) {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                const float* const slot = j < 8 ? a.C + (long long)col * a.c_col + (long long)min(j, a.J - 1) * a.c_j : (a.cs_wide ? a.cs_wide + col : a.C);
-                ix[j] = slot - ap.slab;
-                th[j] = on ? tp[ix[j]] : 0.0f;
-                mm[j] = (on && use_m) ? mp[ix[j]] : 0.0f;
-                vv[j] = (on && use_v) ? vp[ix[j]] : 0.0f;
-            }
+            eh_thin_slots(a, col, ap.slab, ix);
+            eh_lstate_load<9>(tp, mp, vp, ix, on, use_m, use_v, th, mm, vv);
         }
         float w[16];
 #pragma unroll
@@ -1857,29 +1814,13 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
         if (!go) return;
         if (q == 0 && live) {
 #pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                if (on) eh_opt_update_at(ap.o, ap.sc_in, ix[j], ((redq[0][cl][j] + redq[1][cl][j]) + (redq[2][cl][j] + redq[3][cl][j])) * scale, bt1, bt2, th[j], mm[j], vv[j]);
-            }
+            for (int j = 0; j < 9; ++j)
+                if (on[j]) eh_opt_update_at(ap.o, ap.sc_in, ix[j], ((redq[0][cl][j] + redq[1][cl][j]) + (redq[2][cl][j] + redq[3][cl][j])) * scale, bt1, bt2, th[j], mm[j], vv[j]);
             asm volatile("" ::: "memory");
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const bool on = j < 8 ? j < a.J : a.cs_wide != nullptr;
-                if (on) {
-                    tp[ix[j]] = th[j];
-                    if (use_m) mp[ix[j]] = mm[j];
-                    if (use_v) vp[ix[j]] = vv[j];
-                }
-            }
+            eh_lstate_store<9>(tp, mp, vp, ix, on, use_m, use_v, th, mm, vv);
         }
-        if (a.cs_thin && bx == 0 && tid < a.J) {
-            const long long idx = (a.cs_thin + tid) - ap.slab;
-            float t1 = tp[idx], m1 = use_m ? mp[idx] : 0.0f, v1 = use_v ? vp[idx] : 0.0f;
-            eh_opt_update_at(ap.o, ap.sc_in, idx, ((redt[0][tid] + redt[1][tid]) + (redt[2][tid] + redt[3][tid])) * scale, bt1, bt2, t1, m1, v1);
-            tp[idx] = t1;
-            if (use_m) mp[idx] = m1;
-            if (use_v) vp[idx] = v1;
-        }
+        if (a.cs_thin && bx == 0 && tid < a.J)
+            eh_opt_apply_one(ap.o, ap.sc_in, tp, mp, vp, (a.cs_thin + tid) - ap.slab, use_m, use_v, ((redt[0][tid] + redt[1][tid]) + (redt[2][tid] + redt[3][tid])) * scale, bt1, bt2);
         return;
     }
     // ---- a 32 x 32 tile of dW_l^T [in x out] = H_{l-1}^T [in x B] * dZ_l [B x out]
@@ -1902,15 +1843,13 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
     for (int j = 0; j < 4; ++j) {
         const int m = min(pr0 + 8 * j, g.M - 1);
         ix[j] = (g.C + (long long)m * g.ldc + min(pc, g.N - 1)) - ap.slab;
-        th[j] = tp[ix[j]];
-        mm[j] = use_m ? mp[ix[j]] : 0.0f;
-        vv[j] = use_v ? vp[ix[j]] : 0.0f;
     }
+    eh_lstate_load<4>(tp, mp, vp, ix, EhOnAll{}, use_m, use_v, th, mm, vv);
     const bool do_cs = g.colsum != nullptr && by == 0;
     long long cix = 0; float cth = 0.0f, cm = 0.0f, cv = 0.0f;
     if (do_cs && tid < 32 && pcol) {
         cix = (g.colsum + pc) - ap.slab;
-        cth = tp[cix]; cm = use_m ? mp[cix] : 0.0f; cv = use_v ? vp[cix] : 0.0f;
+        eh_opt_load_one(tp, mp, vp, cix, use_m, use_v, cth, cm, cv);
     }
     const int kper = (((g.K + 3) >> 2) + 1) & ~1;                          // samples per wave (even, <= 16 for K <= 64)
     const int k0 = wave * kper, k1 = min(g.K, k0 + kper);
@@ -1969,18 +1908,11 @@ __global__ __launch_bounds__(256) void eh_dw_apply64_kernel(const EhGemmGroup G,
         eh_opt_update_at(ap.o, ap.sc_in, cix, s * scale, bt1, bt2, cth, cm, cv);
     }
     asm volatile("" ::: "memory");
+    bool on[4];          // (the elements that exist: the loads took every one, clamped into the matrix)
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (pcol && pr0 + 8 * j < g.M) {
-            tp[ix[j]] = th[j];
-            if (use_m) mp[ix[j]] = mm[j];
-            if (use_v) vp[ix[j]] = vv[j];
-        }
-    if (do_cs && tid < 32 && pcol) {
-        tp[cix] = cth;
-        if (use_m) mp[cix] = cm;
-        if (use_v) vp[cix] = cv;
-    }
+    for (int j = 0; j < 4; ++j) on[j] = pcol && pr0 + 8 * j < g.M;
+    eh_lstate_store<4>(tp, mp, vp, ix, on, use_m, use_v, th, mm, vv);
+    if (do_cs && tid < 32 && pcol) eh_opt_store_one(tp, mp, vp, cix, use_m, use_v, cth, cm, cv);
     EH_A64(6);
 #ifdef EH_STAMPS
     if (ap.stamps && tid == 0) atomicMax(ap.stamps + 30, (unsigned long long)wall_clock64());
