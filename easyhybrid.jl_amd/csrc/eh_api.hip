@@ -102,23 +102,14 @@ static int flush_one(eh_handle* h) {
 // Every trainable scalar of the model as (canonical flat index, layer, row, col) in the padded
 // block-diagonal MLP.  col < 0 marks a bias.  SingleNN = one net covering everything.
 struct EhEntry { int canon, l, row, col; };
-static std::vector<EhEntry> enumerate_entries(const eh_handle* h) {
+static std::vector<EhEntry> enumerate_entries(const EhPlan& p) {      // (fused families: every leaf is a Dense weight or bias)
     std::vector<EhEntry> v;
-    const int nl = h->desc.n_hidden;
-    int off = 0;
-    for (int k = 0; k < h->n_nets; ++k) {
-        int in = h->net_P[k];
-        for (int l = 0; l <= nl; ++l) {
-            const int o = l < nl ? h->net_w[k][l] : h->net_K[k];
-            const int r0 = h->net_r0[k][l], c0 = l == 0 ? h->net_c0[k] : h->net_r0[k][l - 1];
-            if (l < nl && l >= h->net_d[k]) continue;            // identity block of a shallower net
-            for (int col = 0; col < in; ++col)
-                for (int row = 0; row < o; ++row) v.push_back({off + row + o * col, l, r0 + row, c0 + col});
-            off += o * in;
-            for (int row = 0; row < o; ++row) v.push_back({off + row, l, r0 + row, -1});
-            off += o;
-            in = o;
-        }
+    const int nl = p.desc.n_hidden;
+    for (const EhLeaf& f : p.leaves) {
+        const int k = f.net, l = f.layer < p.net_d[k] ? f.layer : nl;      // (the output layer of a shallower net sits behind its identity blocks)
+        const int r0 = p.net_r0[k][l], c0 = l == 0 ? p.net_c0[k] : p.net_r0[k][l - 1];
+        for (int col = 0; col < std::max(f.cols, 1); ++col)
+            for (int row = 0; row < f.rows; ++row) v.push_back({f.off + row + f.rows * col, l, r0 + row, f.kind == EH_LEAF_WEIGHT ? c0 + col : -1});
     }
     return v;
 }
@@ -131,7 +122,7 @@ static int build_maps(eh_handle* h, bool with_imap) {
     const EhArchInfo* A = h->arch;
     const int nbi = A->nbi, nbh = A->nbh, nl = A->nl, fast = h->fast;
     const EhAccLayout L = eh_acc_layout(nbi, nbh, nl, fast);
-    const std::vector<EhEntry> ent = enumerate_entries(h);
+    const std::vector<EhEntry> ent = enumerate_entries(h->plan);
     const int nwv = A->wide ? A->var[h->variant].nw : 4;
     const EhWideLayout WL = eh_wide_layout(nbi, nbh, nl, nwv);
     std::vector<int> imap((size_t)n.n_theta, -1), rmap((size_t)h->n_acc, 0);
@@ -228,21 +219,6 @@ static int build_maps(eh_handle* h, bool with_imap) {
 static int fast_wanted(const EhArchInfo* A, int K, int P, int T, int mech) {
     if (!A->has_fast || T != 1 || K != 1 || mech == EH_MECH_PROGRAM) return 0;
     return 1 | (P <= 4 ? 2 : 0);
-}
-
-struct MechInfo { int n_par, n_forc, n_out; };
-static bool mech_info(int mech, MechInfo* mi, const eh_model_desc* d = nullptr) {
-    switch (mech) {
-        case EH_MECH_PROGRAM: if (!d) return false; *mi = {d->n_params, d->prog_n_forc, d->prog_n_out}; return true;
-        case EH_MECH_RBQ10: *mi = {2, 1, 1}; return true;
-        case EH_MECH_EXPO: *mi = {2, 1, 1}; return true;
-        case EH_MECH_LINEAR: *mi = {2, 1, 1}; return true;
-        case EH_MECH_EXPO2POOL: *mi = {4, 1, 1}; return true;
-        case EH_MECH_RS_COMPONENTS: *mi = {6, 1, 1}; return true;
-        case EH_MECH_RS_COMPONENTS3F: *mi = {6, 3, 1}; return true;
-        case EH_MECH_FLUXPART: *mi = {3, 2, 3}; return true;
-        default: return false;
-    }
 }
 
 static const EhArchInfo* find_arch(int nbi, int nbh, int nl) {
@@ -570,244 +546,34 @@ static void stream_pool_give(int device, hipStream_t s) {
     (void)hipStreamDestroy(s);
 }
 
-// Sequence models (EH_LAYER_LSTM, EH_LAYER_GRU or EH_LAYER_RNN + activation in the per-layer activation slots; the messages say "LSTM"
-// for every cell): 0 = the descriptor has no recurrent layer, 1 = the one shape that is built -- Dense(P -> I) -> cell(I -> H) ->
-// Dense(H -> H) -> Dense(H -> K), eh_seq.hpp --, otherwise the status of the refusal.
-static bool seq_layer_code(int a) { return a == EH_LAYER_LSTM || a == EH_LAYER_GRU || (a >= EH_LAYER_RNN && a <= EH_LAYER_RNN + EH_ACT_IDENTITY); }
-static int seq_desc_check(const eh_model_desc* d, int n_out, bool several_targets) {
-    if (d->activation != EH_ACT_PER_NET) return 0;
-    const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
-    int n_lstm = 0, at = -1;
-    for (int l = 0; l < na; ++l)
-        if (seq_layer_code(d->net_activation[l])) { if (at < 0) at = l; ++n_lstm; }
-    if (!n_lstm) return 0;
-    if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a MultiNN sequence model (EH_LAYER_LSTM with n_nets = %d)", d->n_nets);
-    if (at == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_LSTM at hidden layer 0: the LSTM layer takes the Dense layer in front of it");
-    if (n_lstm > 1) return fail(nullptr, EH_EINVAL, "eh_create: %d EH_LAYER_LSTM layers (one, at hidden layer 1: stacked Recurrence layers are not built)", n_lstm);
-    if (d->n_hidden != 3 || at != 1 || d->hidden[2] != d->hidden[1])
-        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for an LSTM layer at hidden layer %d of %d (built: n_hidden = 3, hidden = [I, H, H], the LSTM at layer 1)", at, d->n_hidden);
-    if (d->hidden[0] < 1 || d->hidden[1] < 1) return fail(nullptr, EH_EINVAL, "eh_create: hidden = [%d, %d, ..]", d->hidden[0], d->hidden[1]);
-    if (d->hidden[0] > 32 || d->hidden[1] > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for LSTM widths I = %d, H = %d (built: up to 32 each)", d->hidden[0], d->hidden[1]);
-    if (d->n_predictors > 32) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with P = %d predictors (built: up to 32)", d->n_predictors);
-    if (d->input_batchnorm) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for input BatchNorm on a sequence model (3-D input)");
-    if (d->n_targets < 1 || d->n_targets > EH_MAX_TARG) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets (built: 1..%d)", d->n_targets, (int)EH_MAX_TARG);
-    for (int t = 0; t < d->n_targets; ++t)
-        if (d->target_output[t] < 0 || d->target_output[t] >= n_out)
-            return fail(nullptr, EH_EINVAL, "eh_create: sequence model: target_output[%d] = %d names an output the model does not have (it has %d)", t, d->target_output[t], n_out);
-    if (d->n_targets > 1 && n_out < 2)
-        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets around a model with one output (every target would observe the same value)", d->n_targets);
-    // eh_create keeps what it has always answered to such a descriptor, for the one reason that the tests of the one-target kernels pin that
-    // answer (include/easyhybrid_hip.h, eh_create_seq_targets): several targets are asked for by name
-    if (d->n_targets > 1 && !several_targets)
-        return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model with %d targets behind this entry point (one target per sequence handle; several: eh_create_seq_targets)", d->n_targets);
-    // (around every mechanistic model: registry, several outputs, recorded closure; every target names its output, in any order -- two
-    //  targets on one output are taken as the feed-forward families take them)
-    return 1;
-}
-
-// BatchNorm layers inside the chain (EH_LAYER_BATCHNORM [+ EH_LAYER_BN_NOAFFINE] + activation in the per-layer activation slots): 0 = the
-// descriptor has none, 1 = well formed (one network, every such layer as wide as the layer in front of it), otherwise the status of the refusal
-static bool bnl_layer_code(int a) {
-    const int b = a - EH_LAYER_BATCHNORM;
-    return (b >= 0 && b <= EH_ACT_IDENTITY) || (b >= EH_LAYER_BN_NOAFFINE && b <= EH_LAYER_BN_NOAFFINE + EH_ACT_IDENTITY);
-}
-static int bnl_desc_check(const eh_model_desc* d) {
-    if (d->activation != EH_ACT_PER_NET) return 0;
-    const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
-    int n_bn = 0;
-    bool cell = false;
-    for (int l = 0; l < na; ++l) { n_bn += bnl_layer_code(d->net_activation[l]) ? 1 : 0; cell = cell || seq_layer_code(d->net_activation[l]); }
-    if (!n_bn) return 0;
-    if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for BatchNorm layers in a MultiNN model (EH_LAYER_BATCHNORM with n_nets = %d)", d->n_nets);
-    if (cell) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a chain that holds both a BatchNorm layer and a recurrent layer");
-    for (int l = 0; l < na; ++l) {
-        if (!bnl_layer_code(d->net_activation[l])) continue;
-        if (l == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_BATCHNORM at hidden layer 0: a BatchNorm layer normalises the layer in front of it (hidden layer 0 is a Dense layer)");
-        if (d->hidden[l] != d->hidden[l - 1]) return fail(nullptr, EH_EINVAL, "eh_create: BatchNorm layer %d has width %d, the layer in front of it %d", l, d->hidden[l], d->hidden[l - 1]);
-    }
-    return 1;
-}
-// LayerNorm layers inside the chain (EH_LAYER_LAYERNORM [+ EH_LAYER_LN_NOAFFINE] + activation): the same three answers
-static bool lnl_layer_code(int a) {
-    const int b = a - EH_LAYER_LAYERNORM;
-    return (b >= 0 && b <= EH_ACT_IDENTITY) || (b >= EH_LAYER_LN_NOAFFINE && b <= EH_LAYER_LN_NOAFFINE + EH_ACT_IDENTITY);
-}
-static int lnl_desc_check(const eh_model_desc* d) {
-    if (d->activation != EH_ACT_PER_NET) return 0;
-    const int na = std::min(d->n_nets > 0 ? d->n_nets : d->n_hidden, (int)EH_MAX_NETS);
-    int n_ln = 0;
-    bool cell = false;
-    for (int l = 0; l < na; ++l) { n_ln += lnl_layer_code(d->net_activation[l]) ? 1 : 0; cell = cell || seq_layer_code(d->net_activation[l]); }
-    if (!n_ln) return 0;
-    if (d->n_nets > 0) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for LayerNorm layers in a MultiNN model (EH_LAYER_LAYERNORM with n_nets = %d)", d->n_nets);
-    if (cell) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a chain that holds both a LayerNorm layer and a recurrent layer");
-    for (int l = 0; l < na; ++l) {
-        if (!lnl_layer_code(d->net_activation[l])) continue;
-        if (l == 0) return fail(nullptr, EH_EINVAL, "eh_create: EH_LAYER_LAYERNORM at hidden layer 0: a LayerNorm layer normalises the layer in front of it (hidden layer 0 is a Dense layer)");
-        if (d->hidden[l] != d->hidden[l - 1]) return fail(nullptr, EH_EINVAL, "eh_create: LayerNorm layer %d has width %d, the layer in front of it %d", l, d->hidden[l], d->hidden[l - 1]);
-        if (d->hidden[l] > EH_MAX_LAYERNORM_WIDTH) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a LayerNorm layer of width %d (built: up to %d, a row in one wave's registers)", d->hidden[l], EH_MAX_LAYERNORM_WIDTH);
-    }
-    return 1;
-}
-
 static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets);
 int32_t eh_create(const eh_model_desc* d, eh_handle** out) { return create_handle(d, out, false); }
 int32_t eh_create_seq_targets(const eh_model_desc* d, eh_handle** out) { return create_handle(d, out, true); }
 static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets) {
     if (!d || !out) return fail(nullptr, EH_EINVAL, "eh_create: null argument");
     *out = nullptr;
-    if (d->struct_size != (int32_t)sizeof(eh_model_desc)) return fail(nullptr, EH_EINVAL, "eh_create: struct_size %d != %zu", d->struct_size, sizeof(eh_model_desc));
-    MechInfo mi;
-    if (!mech_info(d->mech, &mi, d)) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown mechanistic model id %d (no silent fallback)", d->mech);
-    const bool desc_layers = d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS;
-    const int bnk = desc_layers ? bnl_desc_check(d) : 0;
-    if (bnk < 0) return bnk;
-    const bool bnl = bnk == 1;
-    const int lnk = desc_layers ? lnl_desc_check(d) : 0;
-    if (lnk < 0) return lnk;
-    const bool lnl = lnk == 1;
-    // (a normalisation layer of either kind: an entry of the chain that is no Dense layer)
-    auto norm_layer_code = [&](int a) { return (bnl && bnl_layer_code(a)) || (lnl && lnl_layer_code(a)); };
-    const int seqk = (desc_layers && !bnl && !lnl) ? seq_desc_check(d, mi.n_out, seq_several_targets) : 0;
-    if (seqk < 0) return seqk;
-    const bool seq = seqk == 1;
-    if (d->mech == EH_MECH_PROGRAM) {
-        // every operand must name a slot that holds a value when the instruction runs: the kernel indexes a per-lane array with them
-        if (d->n_params < 1 || d->n_params > EH_MAX_PARAMS) return fail(nullptr, EH_EINVAL, "eh_create: a program takes 1..%d parameters, descriptor has %d", EH_MAX_PARAMS, d->n_params);
-        if (d->prog_len < 1 || d->prog_len > EH_MAX_PROG) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: program of %d instructions (1..%d)", d->prog_len, EH_MAX_PROG);
-        if (d->prog_n_const < 0 || d->prog_n_const > EH_MAX_PROG_CONST) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: program with %d constants (0..%d)", d->prog_n_const, EH_MAX_PROG_CONST);
-        if (d->prog_n_forc < 0 || d->prog_n_forc > EH_MAX_FORC) return fail(nullptr, EH_EINVAL, "eh_create: program with %d forcings (0..%d)", d->prog_n_forc, EH_MAX_FORC);
-        if (d->prog_n_out < 1 || d->prog_n_out > EH_MAX_PROG_OUT) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: program with %d outputs (1..%d)", d->prog_n_out, EH_MAX_PROG_OUT);
-        auto slot_ok = [&](unsigned sl, int upto) {
-            if (sl < EH_PROG_SLOT_FORC) return (int)sl < d->n_params;
-            if (sl < EH_PROG_SLOT_CONST) return (int)sl - EH_PROG_SLOT_FORC < d->prog_n_forc;
-            if (sl < EH_PROG_SLOT_INSTR) return (int)sl - EH_PROG_SLOT_CONST < d->prog_n_const;
-            return (int)sl - EH_PROG_SLOT_INSTR < upto;
-        };
-        for (int i = 0; i < d->prog_len; ++i) {
-            const unsigned w = d->prog_code[i], op = w & 255u;
-            if (op >= EH_OP_COUNT) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: program instruction %d has unknown opcode %u", i, op);
-            const int nop = (op == EH_OP_SELECT) ? 3 : (op == EH_OP_NEG || op == EH_OP_EXP || op == EH_OP_LOG || op == EH_OP_SQRT || op == EH_OP_TANH ||
-                                                        op == EH_OP_SIGMOID || op == EH_OP_ABS || op == EH_OP_SIN || op == EH_OP_COS) ? 1 : 2;
-            const unsigned sl[3] = {(w >> 8) & 255u, (w >> 16) & 255u, w >> 24};
-            for (int k = 0; k < 3; ++k) {
-                if (k < nop ? !slot_ok(sl[k], i) : sl[k] != 0u)
-                    return fail(nullptr, EH_EINVAL, "eh_create: program instruction %d, operand %d names slot %u (undefined at that point, or a non-zero unused operand)", i, k, sl[k]);
-            }
-        }
-        for (int o = 0; o < d->prog_n_out; ++o)
-            if (d->prog_out[o] < 0 || !slot_ok((unsigned)d->prog_out[o], d->prog_len)) return fail(nullptr, EH_EINVAL, "eh_create: program output %d names slot %d", o, d->prog_out[o]);
-    }
-    if (d->activation < 0 || d->activation > EH_ACT_PER_NET) return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown activation id %d", d->activation);
-    int act = d->activation;
-    if (act == EH_ACT_PER_NET) {
-        // n_nets >= 1: activation::NamedTuple of the MultiNN constructor (GenericHybridModel.jl:168-176), one activation per network;
-        // n_nets == 0: `hidden_layers::Chain` of the single-network constructor (NNModels.jl:145-219: Dense layers that carry activations of
-        // their own), one activation per hidden LAYER.  Both run on kernels compiled at run time around eh_row_act(layer, row).
-        if (d->n_nets < 0 || d->n_nets > EH_MAX_NETS) return fail(nullptr, EH_EINVAL, "eh_create: n_nets = %d (0..%d)", d->n_nets, EH_MAX_NETS);
-        const int na = d->n_nets > 0 ? d->n_nets : d->n_hidden;
-        if (na < 1 || na > EH_MAX_HIDDEN) return fail(nullptr, EH_EINVAL, "eh_create: per-layer activations need 1..%d hidden layers (n_hidden = %d)", EH_MAX_HIDDEN, d->n_hidden);
-        bool same = true;
-        for (int k = 0; k < na; ++k) {
-            if (seq && seq_layer_code(d->net_activation[k])) { same = false; continue; }
-            if (norm_layer_code(d->net_activation[k])) { same = false; continue; }
-            if (d->net_activation[k] < 0 || d->net_activation[k] > EH_ACT_IDENTITY)
-                return fail(nullptr, EH_EUNSUPPORTED, "eh_create: unknown activation id %d for %s %d", d->net_activation[k], d->n_nets > 0 ? "net" : "hidden layer", k);
-            same = same && d->net_activation[k] == d->net_activation[0];
-        }
-        if (same) act = d->net_activation[0];          // one activation after all: the kernels built ahead of time
-    }
-    if (d->n_params != mi.n_par) return fail(nullptr, EH_EINVAL, "eh_create: model %d takes %d parameters, descriptor has %d", d->mech, mi.n_par, d->n_params);
-    if (d->n_predictors < 0 || d->n_hidden < 0 || d->n_hidden > EH_MAX_HIDDEN) return fail(nullptr, EH_EINVAL, "eh_create: n_predictors %d, n_hidden %d (0..%d)", d->n_predictors, d->n_hidden, EH_MAX_HIDDEN);
-    if (d->n_forcings < mi.n_forc || d->n_forcings > EH_MAX_FORC) return fail(nullptr, EH_EINVAL, "eh_create: n_forcings %d (model needs %d, max %d)", d->n_forcings, mi.n_forc, EH_MAX_FORC);
-    if (d->n_targets < 1 || d->n_targets > EH_MAX_TARG) return fail(nullptr, EH_EINVAL, "eh_create: n_targets must be 1..%d", EH_MAX_TARG);
-    int K = 0, G = 0, maxw = 0;
-    bool seenK[EH_MAX_PARAMS] = {}, seenG[EH_MAX_PARAMS] = {};
-    for (int j = 0; j < d->n_params; ++j) {
-        const int k = d->param_kind[j], ix = d->param_index[j];
-        if (k == EH_PAR_NEURAL || k == EH_PAR_GLOBAL) {
-            if (ix < 0 || ix >= EH_MAX_PARAMS) return fail(nullptr, EH_EINVAL, "eh_create: param_index[%d] = %d out of range", j, ix);
-            bool* seen = k == EH_PAR_NEURAL ? seenK : seenG;
-            if (seen[ix]) return fail(nullptr, EH_EINVAL, "eh_create: duplicate param_index %d", ix);
-            seen[ix] = true;
-            (k == EH_PAR_NEURAL ? K : G)++;
-            if (!(d->param_upper[j] > d->param_lower[j]) && (k == EH_PAR_GLOBAL || d->scale_nn_outputs))
-                return fail(nullptr, EH_EINVAL, "eh_create: parameter %d needs upper > lower for sigmoid scaling", j);
-        } else if (k != EH_PAR_FIXED) {
-            return fail(nullptr, EH_EINVAL, "eh_create: param_kind[%d] = %d", j, k);
-        }
-    }
-    for (int i = 0; i < K; ++i) if (!seenK[i]) return fail(nullptr, EH_EINVAL, "eh_create: neural param_index values must be 0..K-1");
-    for (int i = 0; i < G; ++i) if (!seenG[i]) return fail(nullptr, EH_EINVAL, "eh_create: global param_index values must be 0..G-1");
-    // No neural parameter: the reference builds no network at all (`NN = Chain()`, GenericHybridModel.jl:112-125) and its forward
-    // is global / fixed parameters -> M (:376-406).  Here: the layer-wise form with zero Dense layers (mechanistic stage + reduce).
-    const bool no_nn = K == 0;
-    if (no_nn) {
-        if (G < 1) return fail(nullptr, EH_EINVAL, "eh_create: a model with neither neural nor global parameters has nothing to train");
-        if (d->n_hidden != 0 || d->n_nets != 0 || d->input_batchnorm) return fail(nullptr, EH_EINVAL, "eh_create: no neural parameter: n_hidden, n_nets and input_batchnorm must be 0");
-    } else {
-        if (d->n_predictors < 1) return fail(nullptr, EH_EINVAL, "eh_create: n_predictors must be >= 1");
-        if (d->n_hidden < 1) return fail(nullptr, EH_EINVAL, "eh_create: n_hidden must be 1..%d", EH_MAX_HIDDEN);
-    }
-    // nets and their block placement (SingleNN = one net with K outputs)
-    const int nl = d->n_hidden;
-    int n_nets = 1, net_P[EH_MAX_NETS] = {0}, net_K[EH_MAX_NETS] = {0}, net_w[EH_MAX_NETS][EH_MAX_HIDDEN] = {{0}}, tot_w[EH_MAX_HIDDEN] = {0};
-    int net_d[EH_MAX_NETS];                  // hidden layers of net k; layers past them are identity blocks as wide as its last one
-    for (int k = 0; k < EH_MAX_NETS; ++k) net_d[k] = nl;
-    bool mixed_depth = false;
-    if (d->n_nets < 0 || d->n_nets > EH_MAX_NETS) return fail(nullptr, EH_EINVAL, "eh_create: n_nets = %d (0..%d)", d->n_nets, EH_MAX_NETS);
-    if (d->n_nets > 0) {
-        if (d->n_nets != K) return fail(nullptr, EH_EINVAL, "eh_create: MultiNN needs one net per neural parameter (%d nets, %d neural parameters)", d->n_nets, K);
-        n_nets = d->n_nets;
-        int ptot = 0;
-        for (int k = 0; k < n_nets; ++k) {
-            if (d->net_n_predictors[k] < 1) return fail(nullptr, EH_EINVAL, "eh_create: net %d has no predictors", k);
-            net_P[k] = d->net_n_predictors[k]; net_K[k] = 1; ptot += net_P[k];
-            if (d->net_depth[k] < 0 || d->net_depth[k] > nl) return fail(nullptr, EH_EINVAL, "eh_create: net_depth[%d] = %d (n_hidden = %d)", k, d->net_depth[k], nl);
-            if (d->net_depth[k] > 0) net_d[k] = d->net_depth[k];
-            mixed_depth = mixed_depth || net_d[k] != nl;
-            for (int l = 0; l < nl; ++l) {
-                if (l < net_d[k] && d->net_hidden[k][l] < 1) return fail(nullptr, EH_EINVAL, "eh_create: net_hidden[%d][%d] = %d", k, l, d->net_hidden[k][l]);
-                net_w[k][l] = d->net_hidden[k][l < net_d[k] ? l : net_d[k] - 1]; tot_w[l] += net_w[k][l];
-            }
-        }
-        if (mixed_depth) {
-            bool full = false;
-            for (int k = 0; k < n_nets; ++k) full = full || net_d[k] == nl;
-            if (!full) return fail(nullptr, EH_EINVAL, "eh_create: n_hidden = %d but no net is that deep", nl);
-            act = EH_ACT_PER_NET;            // the identity blocks need the row-dependent activation (kernels compiled at run time)
-        }
-        if (ptot != d->n_predictors) return fail(nullptr, EH_EINVAL, "eh_create: net_n_predictors sum to %d, n_predictors = %d", ptot, d->n_predictors);
-    } else {
-        net_P[0] = d->n_predictors; net_K[0] = K;
-        for (int l = 0; l < nl; ++l) {
-            if (d->hidden[l] < 1) return fail(nullptr, EH_EINVAL, "eh_create: hidden[%d] = %d", l, d->hidden[l]);
-            net_w[0][l] = d->hidden[l]; tot_w[l] = d->hidden[l];
-        }
-    }
-    for (int l = 0; l < nl; ++l) maxw = std::max(maxw, tot_w[l]);
-    for (int f = 0; f < mi.n_forc; ++f)
-        if (d->forcing_index[f] < 0 || d->forcing_index[f] >= d->n_forcings) return fail(nullptr, EH_EINVAL, "eh_create: forcing_index[%d] out of range", f);
-    for (int t = 0; t < d->n_targets; ++t)
-        if (d->target_output[t] < 0 || d->target_output[t] >= mi.n_out) return fail(nullptr, EH_EINVAL, "eh_create: target_output[%d] = %d (model has %d outputs)", t, d->target_output[t], mi.n_out);
-    const int nbi = (d->n_predictors + 15) / 16, nbh_raw = (maxw + 15) / 16;
-    const int nbh = nbh_raw <= 1 ? 1 : nbh_raw <= 2 ? 2 : nbh_raw <= 4 ? 4 : nbh_raw <= 8 ? 8 : 0;
-    const EhArchInfo* arch = (nbh && K <= 16 && !no_nn) ? find_arch(nbi, nbh, d->n_hidden) : nullptr;
-    const EhArchInfo* const wide_arch = (nbh && K <= 16 && !no_nn) ? find_wide(nbi, nbh, d->n_hidden) : nullptr;
-    if (!arch) arch = wide_arch;
-    bool lform = false;
+    // everything that needs no device: checks, block placement, the layout of flat theta, the family asked for, the EhNet (eh_plan.hpp)
+    EhPlan plan;
+    std::string why;
+    if (const int rc = eh_plan_model(d, seq_several_targets, &plan, &why)) return fail(nullptr, rc, "%s", why.c_str());
+    const bool no_nn = plan.family == EH_FAMILY_NONE, seq = plan.family == EH_FAMILY_SEQ;
+    const EhNet n = plan.net;
     // (EH_FORCE_LFORM: A/B switch of the measurement tools -- every feed-forward model layer by layer, the baseline tools/bench_bn_chain.py compares with)
     static const bool force_lform = getenv("EH_FORCE_LFORM") != nullptr;
-    if (bnl || lnl || (force_lform && !seq)) arch = nullptr;      // (a BatchNorm layer couples the samples of a minibatch: always layer by layer, eh_bnl.hpp; a LayerNorm layer runs as a pass of its own too, eh_lnl.hpp)
-    if (no_nn) { arch = &g_lform_arch; lform = true; }
-    else if (seq) arch = &g_lform_arch;      // (its own kernel family, eh_seq.hpp; of the "architecture" only the PHI block of the image is used)
+    // (normalisation layers never look for a fused kernel: a BatchNorm layer couples the samples of a minibatch, eh_bnl.hpp; a LayerNorm layer runs as a pass of its own too, eh_lnl.hpp)
+    const bool try_fused = plan.family == EH_FAMILY_FUSED && !force_lform && plan.nbh && n.K <= 16;
+    const EhArchInfo* const wide_arch = try_fused ? find_wide(plan.nbi, plan.nbh, d->n_hidden) : nullptr;
+    const EhArchInfo* arch = try_fused ? find_arch(plan.nbi, plan.nbh, d->n_hidden) : nullptr;
+    if (!arch) arch = wide_arch;
+    bool lform = no_nn;
+    if (no_nn || seq) arch = &g_lform_arch;      // (seq: its own kernel family, eh_seq.hpp; of the "architecture" only the PHI block of the image is used)
     else if (!arch) {
         // no fused kernel holds this network: run it layer by layer (eh_lform.hpp) where that form is built
         // (every activation, SingleNN and MultiNN alike: the layer-wise form runs each network as its own chain of products)
-        if (K > 16 || (d->input_batchnorm && d->n_predictors > 32))
+        if (n.K > 16 || (d->input_batchnorm && d->n_predictors > 32))
             return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for P=%d, hidden max width %d%s, %d hidden layers, K=%d, activation %d (fused kernels: P<=32, K<=16, "
                         "width<=64 with <=3 layers or width<=128 with <=2; layer-wise form: K<=16, input BatchNorm with P<=32)",
-                        d->n_predictors, maxw, d->n_nets > 0 ? " (nets side by side)" : "", d->n_hidden, K, act);
+                        d->n_predictors, plan.maxw, d->n_nets > 0 ? " (nets side by side)" : "", d->n_hidden, n.K, plan.act);
         arch = &g_lform_arch;
         lform = true;
     }
@@ -817,125 +583,20 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
     if (d->device < 0 || d->device >= ndev) return fail(nullptr, EH_EINVAL, "eh_create: device %d of %d", d->device, ndev);
 
     eh_handle* h = new eh_handle_s();
-    h->desc = *d;
-    if (d->n_nets > 0) {                     // the descriptor the run-time compiler reads: depths and identity-block widths spelled out
-        for (int k = 0; k < n_nets; ++k) {
-            h->desc.net_depth[k] = net_d[k];
-            for (int l = 0; l < nl; ++l) h->desc.net_hidden[k][l] = net_w[k][l];
-            if (act == EH_ACT_PER_NET) h->desc.net_activation[k] = d->activation == EH_ACT_PER_NET ? d->net_activation[k] : d->activation;
-        }
-        if (act == EH_ACT_PER_NET) h->desc.activation = EH_ACT_PER_NET;
+    h->plan = std::move(plan);
+    const EhPlan& p = h->plan;
+    h->desc = p.desc; h->net = p.net; h->act = p.act; h->n_acc = p.n_acc;
+    h->seq = seq; h->bnl = p.bnl; h->lnl = p.lnl;
+    for (int l = 0; l < p.l_net[0].nl; ++l) {      // eh_set_layer_norm's defaults
+        if (eh_is_norm(p.l_net[0].kind[l])) h->bnl_eps[l] = EH_BN_EPS;
+        if (eh_is_norm(p.l_net[0].kind[l]) && !eh_is_layernorm(p.l_net[0].kind[l])) h->bnl_mom[l] = EH_BN_MOMENTUM;
     }
     h->device = d->device;
     h->arch = arch;
     h->lform = lform;
     h->variant = (arch->nvar > 1 && !arch->wide) ? 1 : 0;   // narrow nets: two waves per SIMD hide the latency of the short tile
-    EhNet& n = h->net;
-    memset(&n, 0, sizeof n);
-    n.P = d->n_predictors; n.K = K; n.G = G; n.T = d->n_targets; n.F = d->n_forcings;
-    h->n_nets = n_nets;
-    {
-        int c0 = 0, r0[EH_MAX_HIDDEN] = {0};
-        for (int k = 0; k < n_nets; ++k) {
-            h->net_P[k] = net_P[k]; h->net_K[k] = net_K[k]; h->net_c0[k] = c0; c0 += net_P[k];
-            for (int l = 0; l < nl; ++l) { h->net_w[k][l] = net_w[k][l]; h->net_r0[k][l] = r0[l]; r0[l] += net_w[k][l]; }
-            h->net_r0[k][nl] = d->n_nets > 0 ? k : 0;            // output row
-            h->net_d[k] = net_d[k];
-        }
-        for (int l = 0; l < nl; ++l) h->tot_w[l] = tot_w[l];
-    }
-    int lw_off[EH_MAX_HIDDEN + 1], lb_off[EH_MAX_HIDDEN + 1];     // canonical offsets of net 0 (all there is for SingleNN)
-    int off = 0;
-    for (int k = 0; k < (no_nn ? 0 : n_nets); ++k) {
-        int in = net_P[k];
-        for (int l = 0; l <= nl; ++l) {
-            const int o = l < nl ? net_w[k][l] : net_K[k];
-            if (k == 0) lw_off[l] = off;
-            if (bnl && l < nl && bnl_layer_code(d->net_activation[l])) {      // a BatchNorm layer: scale and bias, or nothing (affine = false)
-                if (k == 0) lb_off[l] = off;
-                if (d->net_activation[l] - EH_LAYER_BATCHNORM < EH_LAYER_BN_NOAFFINE) off += 2 * o;
-                continue;
-            }
-            if (lnl && l < nl && lnl_layer_code(d->net_activation[l])) {      // a LayerNorm layer: bias and scale, or nothing
-                if (k == 0) lb_off[l] = off;
-                if (d->net_activation[l] - EH_LAYER_LAYERNORM < EH_LAYER_LN_NOAFFINE) off += 2 * o;
-                continue;
-            }
-            if (l < nl && l >= net_d[k]) { if (k == 0) lb_off[l] = off; continue; }       // identity block: nothing of it in theta
-            off += o * in;
-            if (k == 0) lb_off[l] = off;
-            off += o;
-            in = o;
-        }
-    }
-    if (seq) {      // Dense-in | weight_ih, weight_hh, bias_ih, bias_hh (NG gate blocks of H rows each) | head Dense | output Dense
-        const int P = d->n_predictors, I = d->hidden[0], H = d->hidden[1], code = d->net_activation[1];
-        h->seq_cell = code == EH_LAYER_LSTM ? EH_SEQ_CELL_LSTM : (code == EH_LAYER_GRU ? EH_SEQ_CELL_GRU : EH_SEQ_CELL_RNN);
-        h->seq_act_cell = h->seq_cell == EH_SEQ_CELL_RNN ? code - EH_LAYER_RNN : 0;
-        const int NG = eh_seq_gates(h->seq_cell);
-        int* o = h->seq_off;
-        o[EH_SEQ_WIN] = 0; o[EH_SEQ_BIN] = I * P; o[EH_SEQ_WIH] = o[EH_SEQ_BIN] + I; o[EH_SEQ_WHH] = o[EH_SEQ_WIH] + NG * H * I;
-        o[EH_SEQ_BIH] = o[EH_SEQ_WHH] + NG * H * H; o[EH_SEQ_BHH] = o[EH_SEQ_BIH] + NG * H; o[EH_SEQ_WHD] = o[EH_SEQ_BHH] + NG * H;
-        o[EH_SEQ_BHD] = o[EH_SEQ_WHD] + H * H; o[EH_SEQ_WOUT] = o[EH_SEQ_BHD] + H; o[EH_SEQ_BOUT] = o[EH_SEQ_WOUT] + K * H;
-        off = o[EH_SEQ_BOUT] + K;
-        h->seq = true; h->seq_I = I; h->seq_H = H; h->seq_nbi = (I + 15) / 16; h->seq_nbh = (H + 15) / 16;
-        h->seq_act_in = d->net_activation[0]; h->seq_act_hd = d->net_activation[2];
-    }
-    n.g_off = off;
-    n.n_theta = off + G;
-    if (lform && !no_nn) {    // Dense layers of every network: shapes and canonical offsets (no network: l_nnets stays 0)
-        h->l_nnets = n_nets;
-        int o2 = 0, c0 = 0;
-        for (int k = 0; k < n_nets; ++k) {
-            eh_handle_s::LNet& L = h->l_net[k];
-            L.nl = net_d[k] + 1; L.c0 = c0; L.orow = d->n_nets > 0 ? k : 0;
-            L.act = (d->n_nets > 0 && d->activation == EH_ACT_PER_NET) ? d->net_activation[k] : (act == EH_ACT_PER_NET ? d->activation : act);
-            for (int l = 0; l <= EH_MAX_HIDDEN; ++l)      // (an activation per hidden layer: the single network of a `hidden_layers::Chain`)
-                L.lact[l] = (d->n_nets == 0 && act == EH_ACT_PER_NET && l < nl) ? d->net_activation[l] : L.act;
-            int in = net_P[k];
-            for (int l = 0; l < L.nl; ++l) {
-                const int o = l + 1 < L.nl ? net_w[k][l] : net_K[k];
-                if (bnl && l + 1 < L.nl && bnl_layer_code(d->net_activation[l])) {
-                    const int b = d->net_activation[l] - EH_LAYER_BATCHNORM;
-                    const bool affine = b < EH_LAYER_BN_NOAFFINE;
-                    L.lbn[l] = affine ? 1 : 2; L.lact[l] = affine ? b : b - EH_LAYER_BN_NOAFFINE;
-                    L.in[l] = in; L.out[l] = in; L.woff[l] = o2; L.boff[l] = affine ? o2 + in : o2;
-                    if (affine) o2 += 2 * in;
-                    h->bnl = true; h->bnl_off[l] = h->bnl_maxn; h->bnl_maxn += 2 * in;      // (bnl_maxn: the running total here, the widest layer below)
-                    h->bnl_mom[l] = EH_BN_MOMENTUM; h->bnl_eps[l] = EH_BN_EPS;
-                    continue;
-                }
-                if (lnl && l + 1 < L.nl && lnl_layer_code(d->net_activation[l])) {      // (Lux orders a LayerNorm's leaves bias, scale)
-                    const int b = d->net_activation[l] - EH_LAYER_LAYERNORM;
-                    const bool affine = b < EH_LAYER_LN_NOAFFINE;
-                    L.lbn[l] = affine ? 3 : 4; L.lact[l] = affine ? b : b - EH_LAYER_LN_NOAFFINE;
-                    L.in[l] = in; L.out[l] = in; L.boff[l] = o2; L.woff[l] = affine ? o2 + in : o2;
-                    if (affine) o2 += 2 * in;
-                    h->lnl = true; h->bnl_eps[l] = EH_BN_EPS;
-                    continue;
-                }
-                L.in[l] = in; L.out[l] = o; L.woff[l] = o2; L.boff[l] = o2 + o * in;
-                o2 += o * in + o; in = o;
-            }
-            c0 += net_P[k];
-        }
-    }
-    h->act = act; n.scale_nn = d->scale_nn_outputs ? 1 : 0;
-    n.mech = d->mech; n.n_par = d->n_params;
-    for (int j = 0; j < d->n_params; ++j) {
-        n.par_kind |= (unsigned)d->param_kind[j] << (2 * j);
-        n.par_idx |= (unsigned)(d->param_kind[j] == EH_PAR_FIXED ? 0 : d->param_index[j]) << (4 * j);
-    }
-    for (int j = d->n_params; j < EH_MAX_PARAMS; ++j) n.par_kind |= (unsigned)EH_PAR_FIXED << (2 * j);
-    n.forc_col = 0xFFFFFFFFu;
-    for (int f = 0; f < mi.n_forc; ++f) n.forc_col = (n.forc_col & ~(0xFFu << (8 * f))) | ((unsigned)d->forcing_index[f] << (8 * f));
-    n.n_out = mi.n_out;
-    for (int t = 0; t < d->n_targets; ++t) n.targ_out |= (unsigned)d->target_output[t] << (2 * t);
-    h->fast = fast_wanted(arch, K, n.P, n.T, d->mech);
-    h->C = n.P + n.F + n.T;
-    h->n_par = d->n_params;
-    h->n_acc = n.n_theta + 1 + n.T + 2;      // [grad | S | n_valid per target | Sy | Syy]
-    if (seq && h->n_acc > eh_seq_row_cap(h->seq_nbi, h->seq_nbh, h->seq_cell)) {
+    h->fast = fast_wanted(arch, n.K, n.P, n.T, d->mech);
+    if (seq && h->n_acc > eh_seq_row_cap(p.seq_nbi, p.seq_nbh, p.seq_cell)) {
         delete h;
         return fail(nullptr, EH_EUNSUPPORTED, "eh_create: no kernel for a sequence model of %d parameters (the slab row is staged in LDS)", n.n_theta);
     }
@@ -949,7 +610,7 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
         h->variant = 0;
         h->fast = 0;
     }
-    h->arch_alt = (arch == wide_arch || seq || lform) ? nullptr : wide_arch;
+    h->arch_alt =(arch == wide_arch || seq || lform) ? nullptr : wide_arch;
 #define HIPCHK_C(expr)                                                            \
     do {                                                                          \
         hipError_t e_ = (expr);                                                   \
@@ -1005,20 +666,18 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
         HIPCHK_C(hipMemcpy(h->bn_run, run0, sizeof run0, hipMemcpyHostToDevice));
     }
     if (h->bnl || h->lnl) {   // BatchNorm layers: running statistics (LuxCore.initialstates: mean 0, var 1), the step's own; both kinds: the partial column sums
-        const int tot = h->bnl_maxn;          // (of the BatchNorm layers alone: a LayerNorm layer has no state)
-        int widest = 0;
-        for (int l = 0; l < h->l_net[0].nl; ++l) if (h->l_net[0].lbn[l]) widest = std::max(widest, h->l_net[0].out[l]);
-        h->bnl_maxn = widest;
+        const int tot = p.bnl_tot;          // (of the BatchNorm layers alone: a LayerNorm layer has no state)
+        const EhLNet& L = p.l_net[0];
         if (h->bnl) {
             std::vector<float> run0((size_t)tot, 0.0f);
-            for (int l = 0; l < h->l_net[0].nl; ++l)
-                if (h->l_net[0].lbn[l] == 1 || h->l_net[0].lbn[l] == 2) std::fill(run0.begin() + h->bnl_off[l] + h->l_net[0].out[l], run0.begin() + h->bnl_off[l] + 2 * h->l_net[0].out[l], 1.0f);
+            for (int l = 0; l < L.nl; ++l)
+                if (eh_is_norm(L.kind[l]) && !eh_is_layernorm(L.kind[l])) std::fill(run0.begin() + p.bnl_off[l] + L.out[l], run0.begin() + p.bnl_off[l] + 2 * L.out[l], 1.0f);
             HIPCHK_C(hipMalloc(&h->bnl_run, (size_t)tot * sizeof(float)));
             HIPCHK_C(hipMemcpy(h->bnl_run, run0.data(), (size_t)tot * sizeof(float), hipMemcpyHostToDevice));
             HIPCHK_C(hipMalloc(&h->bnl_stat, (size_t)2 * tot * sizeof(float)));
             HIPCHK_C(hipMemset(h->bnl_stat, 0, (size_t)2 * tot * sizeof(float)));
         }
-        HIPCHK_C(hipMalloc(&h->bnl_part, (size_t)(EH_BNL_CHUNKS + 1) * 2 * widest * sizeof(float)));
+        HIPCHK_C(hipMalloc(&h->bnl_part, (size_t)(EH_BNL_CHUNKS + 1) * 2 * p.norm_maxn * sizeof(float)));
     }
     if (!lform && !seq) {     // (the fused-update accumulators: that mode exists for the per-wave kernels only)
         HIPCHK_C(hipMalloc(&h->gacc, ((size_t)3 * EH_GSHARDS * h->n_acc + 4) * sizeof(float)));      // (+4: the fused prologue reads five tail floats of every shard whatever T is)
@@ -1045,21 +704,11 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
     HIPCHK_C(hipMemset(h->inv_n, 0, EH_TT * EH_MAX_TARG * sizeof(float)));
     HIPCHK_C(hipMemset(h->gradbuf, 0, (size_t)h->n_acc * sizeof(float)));
     tick("slab + small buffers");
-    if (seq) {                // (extract_weights.jl:69-91 matches the leaves named "weight": the three Dense matrices, not weight_ih / weight_hh)
+    if (!lform && !seq) { if (int rc = build_maps(h, true)) { g_create_err = h->err; eh_destroy(h); return rc; } }
+    else {                    // (no parameter image to tell a weight by: the leaves weight_l2 sums, flagged)
         std::vector<unsigned char> wf((size_t)n.n_theta, 0);
-        const int* o = h->seq_off;
-        std::fill(wf.begin() + o[EH_SEQ_WIN], wf.begin() + o[EH_SEQ_BIN], (unsigned char)1);
-        std::fill(wf.begin() + o[EH_SEQ_WHD], wf.begin() + o[EH_SEQ_BHD], (unsigned char)1);
-        std::fill(wf.begin() + o[EH_SEQ_WOUT], wf.begin() + o[EH_SEQ_BOUT], (unsigned char)1);
-        HIPCHK_C(hipMalloc(&h->wflag, wf.size()));
-        HIPCHK_C(hipMemcpy(h->wflag, wf.data(), wf.size(), hipMemcpyHostToDevice));
-    }
-    else if (!lform) { if (int rc = build_maps(h, true)) { g_create_err = h->err; eh_destroy(h); return rc; } }
-    else {
-        std::vector<unsigned char> wf((size_t)n.n_theta, 0);
-        for (int k = 0; k < h->l_nnets; ++k)
-            for (int l = 0; l < h->l_net[k].nl; ++l)
-                if (!h->l_net[k].lbn[l]) std::fill(wf.begin() + h->l_net[k].woff[l], wf.begin() + h->l_net[k].boff[l], (unsigned char)1);      // (a BatchNorm's scale is no weight)
+        for (const EhLeaf& f : p.leaves)
+            if (f.is_weight) std::fill(wf.begin() + f.off, wf.begin() + f.off + f.size(), (unsigned char)1);
         HIPCHK_C(hipMalloc(&h->wflag, wf.size()));
         HIPCHK_C(hipMemcpy(h->wflag, wf.data(), wf.size(), hipMemcpyHostToDevice));
     }
@@ -1071,15 +720,21 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
             img0[arch->phi_off + EH_IMG_LO + j] = d->param_lower[j];
             img0[arch->phi_off + EH_IMG_SC + j] = d->param_upper[j] - d->param_lower[j];
         }
-        for (int p = 0; p < 32; ++p) { img0[arch->phi_off + EH_IMG_BNM + p] = 0.0f; img0[arch->phi_off + EH_IMG_BNR + p] = d->input_batchnorm ? 1.0f / std::sqrt(1.0f + EH_BN_EPS) : 1.0f; }
-        for (int k = 0; k < (lform ? 0 : n_nets); ++k)      // identity blocks that carry a shallower net to the output layer (fused envelope only: the layer-wise form runs every net at its own depth)
-            for (int l = net_d[k]; l < nl; ++l)
-                for (int i = 0; i < net_w[k][l]; ++i)
-                    img0[arch->wh_off + (size_t)(l - 1) * arch->hp * arch->sh + (size_t)(h->net_r0[k][l] + i) * arch->sh + h->net_r0[k][l - 1] + i] = 1.0f;
+        for (int q = 0; q < 32; ++q) { img0[arch->phi_off + EH_IMG_BNM + q] = 0.0f; img0[arch->phi_off + EH_IMG_BNR + q] = d->input_batchnorm ? 1.0f / std::sqrt(1.0f + EH_BN_EPS) : 1.0f; }
+        const int nl = d->n_hidden;
+        for (int k = 0; k < (lform ? 0 : p.n_nets); ++k)      // identity blocks that carry a shallower net to the output layer (fused envelope only: the layer-wise form runs every net at its own depth)
+            for (int l = p.net_d[k]; l < nl; ++l)
+                for (int i = 0; i < p.net_w[k][l]; ++i)
+                    img0[arch->wh_off + (size_t)(l - 1) * arch->hp * arch->sh + (size_t)(p.net_r0[k][l] + i) * arch->sh + p.net_r0[k][l - 1] + i] = 1.0f;
         auto put_int = [&](int slot, int v) { memcpy(&img0[arch->phi_off + slot], &v, sizeof(int)); };
         if (!lform && !seq) { // (read by the fused kernels' end-of-kernel reduction only; sized for their four layers)
-            for (int l = 0; l <= d->n_hidden; ++l) { put_int(EH_IMG_WOFF + l, lw_off[l]); put_int(EH_IMG_BOFF + l, lb_off[l]); }
-            for (int l = 0; l < d->n_hidden; ++l) put_int(EH_IMG_WIDTH + l, tot_w[l]);
+            // canonical offsets of net 0 (all there is for SingleNN); an identity block of it: where its output layer starts, nothing of the block in theta
+            const EhLNet& L = p.l_net[0];
+            for (int l = 0; l <= nl; ++l) {
+                const int c = std::min(l, L.nl - 1);
+                put_int(EH_IMG_WOFF + l, L.woff[c]); put_int(EH_IMG_BOFF + l, (l < nl && l >= L.nl - 1) ? L.woff[c] : L.boff[c]);
+            }
+            for (int l = 0; l < nl; ++l) put_int(EH_IMG_WIDTH + l, p.tot_w[l]);
         }
         for (int j = 0; j < d->n_params; ++j)
             if (d->param_kind[j] == EH_PAR_GLOBAL) put_int(EH_IMG_GPAR + d->param_index[j], j);
@@ -1091,13 +746,6 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
         im.agg_a = 1.0f; im.l2s = 1.0f;          // agg = sum
         HIPCHK_C(hipMalloc(&h->l2val, sizeof(float)));
         HIPCHK_C(hipMemset(h->l2val, 0, sizeof(float)));
-        {
-            int nw = 0;
-            if (seq) nw = (h->seq_off[EH_SEQ_BIN] - h->seq_off[EH_SEQ_WIN]) + (h->seq_off[EH_SEQ_BHD] - h->seq_off[EH_SEQ_WHD]) + (h->seq_off[EH_SEQ_BOUT] - h->seq_off[EH_SEQ_WOUT]);
-            else if (lform) { for (int k = 0; k < h->l_nnets; ++k) for (int l = 0; l < h->l_net[k].nl; ++l) nw += h->l_net[k].lbn[l] ? 0 : h->l_net[k].in[l] * h->l_net[k].out[l]; }
-            else for (const EhEntry& e : enumerate_entries(h)) nw += e.col >= 0 ? 1 : 0;
-            h->n_weights = nw;
-        }
         for (int j = 0; j < d->n_params; ++j)
             if (d->param_kind[j] == EH_PAR_GLOBAL) {
                 const int g = d->param_index[j];
@@ -1310,7 +958,7 @@ int32_t eh_jit_status(eh_handle* h, int32_t* n_compiled, char* log, int64_t log_
 // A/B switches of the measurement tools are read once and mean the same to the "precision" and the "variant" option (advisor r05)
 static bool so_allowed(const eh_handle* h) {
     static const bool no_so = getenv("EH_NO_DIRECT_STORE") != nullptr || getenv("EH_NO_SAMPLE_OWNED") != nullptr;
-    return !no_so && h->n_nets == 1 && h->desc.n_nets == 0;
+    return !no_so && h->plan.n_nets == 1 && h->desc.n_nets == 0;
 }
 
 static int32_t set_option(eh_handle* h, const char* name, int64_t value);
@@ -1635,7 +1283,7 @@ static int eval_grid_for(const eh_handle* h, long long count) {
 // per-target weights of the minibatch (1 / n_t, 1 / sum (y - ybar)^2) -> inv_n; tcount (eh_dp_counts): the shard's raw sums as well
 int eh_launch_count(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, float* tcount) {
     const EhNet& net = h->net;
-    hipLaunchKernelGGL(eh_count_kernel, dim3(net.T), dim3(256), 0, h->stream, sp.recs, h->C, net.P + net.F, net.T, idx, first, count, h->inv_n, net.loss_t, sp.shift4(), h->img.agg_a, h->roles, h->img.l2s, tcount);
+    hipLaunchKernelGGL(eh_count_kernel, dim3(net.T), dim3(256), 0, h->stream, sp.recs, h->plan.C, net.P + net.F, net.T, idx, first, count, h->inv_n, net.loss_t, sp.shift4(), h->img.agg_a, h->roles, h->img.l2s, tcount);
     HIPCHK(h, hipGetLastError());
     return EH_OK;
 }
@@ -1670,7 +1318,7 @@ int eh_bn_prepare(eh_handle* h, const EhSplit& sp, const int* idx, long long fir
         return EH_OK;
     }
     const int nblk = (int)std::max<long long>(1, std::min<long long>(32, (count + 1023) / 1024));
-    hipLaunchKernelGGL(eh_bn_stats_kernel, dim3(nblk), dim3(1024), 0, h->stream, sp.recs, h->C, h->net.P, idx, (int)first, (int)count, h->bn_part, nullptr);
+    hipLaunchKernelGGL(eh_bn_stats_kernel, dim3(nblk), dim3(1024), 0, h->stream, sp.recs, h->plan.C, h->net.P, idx, (int)first, (int)count, h->bn_part, nullptr);
     HIPCHK(h, hipGetLastError());
     a->bn_part = h->bn_part; a->bn_nblk = nblk; a->bn_c = h->bn_part + nblk * 64; a->bn_update = update ? 1 : 0;
     return EH_OK;
@@ -1691,19 +1339,19 @@ constexpr long long EH_SEQ_WS_CAP = 256ll << 20;      // bytes of backward works
 static int seq_grid_for(const eh_handle* h, const EhSplit& sp, long long count, bool train) {
     const long long ntiles = (count + 15) / 16;
     long long grid = std::max<long long>(1, std::min<long long>((ntiles + EH_SEQ_NW - 1) / EH_SEQ_NW, std::min(h->max_blocks, h->slab_rows)));
-    if (train) grid = std::max<long long>(1, std::min<long long>(grid, EH_SEQ_WS_CAP / (4 * EH_SEQ_NW * eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow, h->seq_cell))));
+    if (train) grid = std::max<long long>(1, std::min<long long>(grid, EH_SEQ_WS_CAP / (4 * EH_SEQ_NW * eh_seq_ws_floats(h->plan.seq_nbh, sp.W, sp.ow, h->plan.seq_cell))));
     return (int)grid;
 }
 static EhSeqArgs seq_args(const eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
     EhSeqArgs a{};
-    a.recs = sp.recs; a.C = h->C; a.starts = sp.starts; a.idx = idx; a.first = first; a.count = count;
+    a.recs = sp.recs; a.C = h->plan.C; a.starts = sp.starts; a.idx = idx; a.first = first; a.count = count;
     a.W = sp.W; a.ow = sp.ow; a.lam = sp.lam;
     a.theta = TH(h); a.meta = h->image + h->arch->phi_off; a.slab = h->slab; a.n_acc = h->n_acc;
     a.shift = sp.shift[0];
     for (int t = 0; t < EH_MAX_TARG; ++t) a.shift_t[t] = sp.shift[t];
     a.inv_n = h->net.T > 1 ? h->inv_n : nullptr;
-    a.I = h->seq_I; a.H = h->seq_H; a.act_in = h->seq_act_in; a.act_hd = h->seq_act_hd; a.act_cell = h->seq_act_cell;
-    for (int k = 0; k < EH_SEQ_NOFF; ++k) a.off[k] = h->seq_off[k];
+    a.I = h->plan.seq_I; a.H = h->plan.seq_H; a.act_in = h->plan.seq_act_in; a.act_hd = h->plan.seq_act_hd; a.act_cell = h->plan.seq_act_cell;
+    for (int k = 0; k < EH_SEQ_NOFF; ++k) a.off[k] = h->plan.seq_off[k];
     a.prog = h->prog;
     return a;
 }
@@ -1716,7 +1364,7 @@ static eh_handle_s::JitEntry* seq_jit_entry(eh_handle* h) {
     h->jit.emplace_back(new eh_handle_s::JitEntry());
     eh_handle_s::JitEntry* je = h->jit.back().get();
     je->arch = h->arch; je->variant = 0; je->fast = 0; je->spec = false; je->p2p = false; je->net = h->net; je->loss_gen = 0;
-    const bool ok = eh_jit_build_seq(h->desc, h->seq_nbi, h->seq_nbh, h->seq_cell, h->net.T > 1, &je->k, &je->log);
+    const bool ok = eh_jit_build_seq(h->desc, h->plan.seq_nbi, h->plan.seq_nbh, h->plan.seq_cell, h->net.T > 1, &je->k, &je->log);
     je->state.store(ok ? 1 : -1, std::memory_order_release);
     if (!ok) { h->jit_log = je->log; h->jit_failed = true; return nullptr; }
     return je;
@@ -1735,7 +1383,7 @@ static void seq_jit_verify(eh_handle* h, eh_handle_s::JitEntry* je, int grid, co
     std::vector<float> part[2] = {std::vector<float>(n), std::vector<float>(n)};
     bool ran = true;
     for (int k = 0; k < 2 && ran; ++k) {
-        ran = (k == 0 ? eh_seq_launch(h->seq_nbi, h->seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a, h->seq_cell, net.T > 1)
+        ran = (k == 0 ? eh_seq_launch(h->plan.seq_nbi, h->plan.seq_nbh, EH_SEQ_TRAIN, EH_SEQ_HEAD_PROG, grid, h->stream, net, a, h->plan.seq_cell, net.T > 1)
                       : eh_jit_launch_seq(&je->k, EH_SEQ_TRAIN, grid, h->stream, &net, &a)) == hipSuccess &&
               hipMemcpyAsync(part[k].data(), a.slab, n * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
     }
@@ -1771,12 +1419,12 @@ static hipError_t seq_launch(eh_handle* h, int mode, int grid, const EhSeqArgs& 
         h->jit_log = std::string("launch of the run-time compiled sequence kernel failed: ") + hipGetErrorString(e);
     }
     const int head = h->net.mech == EH_MECH_PROGRAM ? EH_SEQ_HEAD_PROG : (h->net.n_out > 1 ? EH_SEQ_HEAD_MULTI : EH_SEQ_HEAD_MECH);
-    return eh_seq_launch(h->seq_nbi, h->seq_nbh, mode, head, grid, h->stream, h->net, a, h->seq_cell, h->net.T > 1);
+    return eh_seq_launch(h->plan.seq_nbi, h->plan.seq_nbh, mode, head, grid, h->stream, h->net, a, h->plan.seq_cell, h->net.T > 1);
 }
 // several targets: the per-target weights of this minibatch of windows -> inv_n (eh_seq_count_kernel), ahead of the training pass
 static int seq_launch_count(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
     const EhNet& net = h->net;
-    hipLaunchKernelGGL(eh_seq_count_kernel, dim3(net.T), dim3(EH_SEQ_COUNT_NT), 0, h->stream, sp.recs, h->C, net.P + net.F, sp.starts, idx, first, count, sp.W, sp.ow, sp.lam,
+    hipLaunchKernelGGL(eh_seq_count_kernel, dim3(net.T), dim3(EH_SEQ_COUNT_NT), 0, h->stream, sp.recs, h->plan.C, net.P + net.F, sp.starts, idx, first, count, sp.W, sp.ow, sp.lam,
                        h->inv_n, net.loss_t, sp.shift4(), h->img.agg_a);
     HIPCHK(h, hipGetLastError());
     return EH_OK;
@@ -1785,7 +1433,7 @@ static int seq_train(eh_handle* h, const EhSplit& sp, const int* idx, long long 
     if (!sp.starts) return fail(h, EH_ESTATE, "sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
     const int grid = seq_grid_for(h, sp, count, true);
     EhSeqArgs a = seq_args(h, sp, idx, first, count);
-    a.ws_wave = eh_seq_ws_floats(h->seq_nbh, sp.W, sp.ow, h->seq_cell);
+    a.ws_wave = eh_seq_ws_floats(h->plan.seq_nbh, sp.W, sp.ow, h->plan.seq_cell);
     const long long need = (long long)grid * EH_SEQ_NW * a.ws_wave;      // sized by the grid actually launched
     if (need > h->seq_ws_floats) { if (int rc = eh_grow(h, &h->seq_ws, &h->seq_ws_floats, need)) return rc; }
     a.ws = h->seq_ws;
@@ -1836,7 +1484,7 @@ static int launch_train_kernel(eh_handle* h, const EhSplit& sp, const int* idx, 
     // one network on a row-split bf16 kernel: the accumulators go to the slab row straight from the registers (canonical order is plain
     // column-major per layer; eh_wide_bf16.hpp) -- signalled by a null map
     static const bool no_direct = getenv("EH_NO_DIRECT_STORE") != nullptr;      // (A/B switch of the measurement tools)
-    if (!no_direct && h->arch->wide && h->arch->var[h->variant].bf16 && h->n_nets == 1 && h->desc.n_nets == 0) a.rmap = nullptr;
+    if (!no_direct && h->arch->wide && h->arch->var[h->variant].bf16 && h->plan.n_nets == 1 && h->desc.n_nets == 0) a.rmap = nullptr;
     a.stamps = h->stamps;
     a.fz.gacc = nullptr;
     if (h->drop_on) {
@@ -2105,7 +1753,7 @@ static int eval_host_acquire(eh_handle* h, size_t need) {
 static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count, double* stats, float* const* yhat, float* const* params) {
     if (!sp.starts) return fail(h, EH_ESTATE, "eh_eval: sequence model: no windows for this split (call eh_set_sequences after eh_set_data)");
     const int T = h->net.T, nst = EH_EVAL_STATS * T;
-    const long long nout = count * sp.ow, need = (long long)((yhat ? T : 0) + (params ? h->n_par : 0)) * nout;
+    const long long nout = count * sp.ow, need = (long long)((yhat ? T : 0) + (params ? h->plan.n_par : 0)) * nout;
     if (need > h->out_cap) { if (int rc2 = eh_grow(h, &h->out_buf, &h->out_cap, need)) return rc2; }
     EhSeqArgs a = seq_args(h, sp, nullptr, first, count);
     a.n_acc = nst;
@@ -2130,7 +1778,7 @@ static int seq_eval(eh_handle* h, EhSplit& sp, long long first, long long count,
         for (int t = 0; t < T; ++t)
             if (yhat[t]) { if (int rc = eh_copy_out(h, yhat[t], a.yhat + (long long)t * nout, (size_t)nout)) return rc; }
     if (params)
-        for (int j = 0; j < h->n_par; ++j)
+        for (int j = 0; j < h->plan.n_par; ++j)
             if (params[j]) { if (int rc = eh_copy_out(h, params[j], a.pout + (long long)j * nout, (size_t)nout)) return rc; }
     return EH_OK;
 }
@@ -2143,7 +1791,7 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
     if (rc) return rc;
     FLUSH(h);
     if (h->seq) return seq_eval(h, sp, first, count, stats, yhat, params);
-    const long long need = (long long)(yhat ? net.T : 0) * count + (long long)(params ? h->n_par : 0) * count;
+    const long long need = (long long)(yhat ? net.T : 0) * count + (long long)(params ? h->plan.n_par : 0) * count;
     if (need > h->out_cap) { if (int rc2 = eh_grow(h, &h->out_buf, &h->out_cap, need)) return rc2; }
     EhStepArgs a = eh_step_args(h, sp, nullptr, first, count);
     a.image = h->image; a.slab = h->slab; a.n_acc = EH_EVAL_STATS * net.T;
@@ -2195,7 +1843,7 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
         for (int t = 0; t < net.T; ++t)
             if (yhat[t]) { if (int rc2 = eh_copy_out(h, yhat[t], a.yhat + (long long)t * count, (size_t)count)) return rc2; }
     if (params)
-        for (int j = 0; j < h->n_par; ++j)
+        for (int j = 0; j < h->plan.n_par; ++j)
             if (params[j]) { if (int rc2 = eh_copy_out(h, params[j], a.pout + (long long)j * count, (size_t)count)) return rc2; }
     return EH_OK;
 }
@@ -2309,8 +1957,8 @@ int32_t eh_set_bn_state(eh_handle* h, const float* running_mean, const float* ru
 
 // running statistics of a BatchNorm layer inside the chain (eh_bnl.hpp)
 static int layer_state_check(eh_handle* h, const char* who, int32_t layer, int64_t n) {
-    if (!h->bnl || layer < 0 || layer >= h->l_net[0].nl || (h->l_net[0].lbn[layer] != 1 && h->l_net[0].lbn[layer] != 2)) return fail(h, EH_ESTATE, "%s: hidden layer %d is no BatchNorm layer", who, layer);
-    if (n != h->l_net[0].out[layer]) return fail(h, EH_EINVAL, "%s: n = %lld, the layer has %d units", who, (long long)n, h->l_net[0].out[layer]);
+    if (!h->bnl || layer < 0 || layer >= h->plan.l_net[0].nl || !eh_is_norm(h->plan.l_net[0].kind[layer]) || eh_is_layernorm(h->plan.l_net[0].kind[layer])) return fail(h, EH_ESTATE, "%s: hidden layer %d is no BatchNorm layer", who, layer);
+    if (n != h->plan.l_net[0].out[layer]) return fail(h, EH_EINVAL, "%s: n = %lld, the layer has %d units", who, (long long)n, h->plan.l_net[0].out[layer]);
     return EH_OK;
 }
 int32_t eh_get_layer_state(eh_handle* h, int32_t layer, float* running_mean, float* running_var, int64_t n) {
@@ -2319,8 +1967,8 @@ int32_t eh_get_layer_state(eh_handle* h, int32_t layer, float* running_mean, flo
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(running_mean, h->bnl_run + h->bnl_off[layer], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(running_var, h->bnl_run + h->bnl_off[layer] + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(running_mean, h->bnl_run + h->plan.bnl_off[layer], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(running_var, h->bnl_run + h->plan.bnl_off[layer] + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return EH_OK;
 }
 int32_t eh_set_layer_state(eh_handle* h, int32_t layer, const float* running_mean, const float* running_var, int64_t n) {
@@ -2329,14 +1977,14 @@ int32_t eh_set_layer_state(eh_handle* h, int32_t layer, const float* running_mea
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->bnl_run + h->bnl_off[layer], running_mean, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->bnl_run + h->bnl_off[layer] + n, running_var, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->bnl_run + h->plan.bnl_off[layer], running_mean, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->bnl_run + h->plan.bnl_off[layer] + n, running_var, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     return EH_OK;
 }
 int32_t eh_set_layer_norm(eh_handle* h, int32_t layer, float momentum, float epsilon) {
     if (!h) return EH_EINVAL;
-    const bool ln = h->lnl && layer >= 0 && layer < h->l_net[0].nl && h->l_net[0].lbn[layer] >= 3;      // (a LayerNorm layer: its epsilon; it has no momentum to set)
-    if (!ln) { if (int rc = layer_state_check(h, "eh_set_layer_norm", layer, h->bnl && layer >= 0 && layer < h->l_net[0].nl ? h->l_net[0].out[layer] : 0)) return rc; }
+    const bool ln = h->lnl && layer >= 0 && layer < h->plan.l_net[0].nl && eh_is_layernorm(h->plan.l_net[0].kind[layer]);      // (a LayerNorm layer: its epsilon; it has no momentum to set)
+    if (!ln) { if (int rc = layer_state_check(h, "eh_set_layer_norm", layer, h->bnl && layer >= 0 && layer < h->plan.l_net[0].nl ? h->plan.l_net[0].out[layer] : 0)) return rc; }
     if (!(momentum >= 0.0f && momentum <= 1.0f) || !(epsilon > 0.0f)) return fail(h, EH_EINVAL, "eh_set_layer_norm: momentum %g (0..1), epsilon %g (> 0)", (double)momentum, (double)epsilon);
     h->bnl_mom[layer] = momentum; h->bnl_eps[layer] = epsilon;      // (kernel arguments of the steps launched from now on)
     return EH_OK;
@@ -2752,7 +2400,7 @@ int32_t eh_set_weight_l2(eh_handle* h, float lambda, int32_t normalize) {
     if (lambda != 0.0f && h->fused) return fail(h, EH_EUNSUPPORTED, "eh_set_weight_l2: not built for the fused_update mode: switch it off first");
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
-    h->img.l2c = (normalize && h->n_weights > 0) ? lambda / (float)h->n_weights : lambda;
+    h->img.l2c = (normalize && h->plan.n_weights > 0) ? lambda / (float)h->plan.n_weights : lambda;
     h->img.l2w = nullptr;
     return EH_OK;
 }
@@ -2932,7 +2580,7 @@ int32_t eh_dp_bn_stats(eh_handle* h, int64_t first, int64_t count) {
     if (rc) return rc;
     const int* idx = h->perm_valid ? h->perm : nullptr;      // the same samples eh_dp_grad / eh_dp_fused_step will read
     const int nblk = (int)std::max<long long>(1, std::min<long long>(32, (count + 1023) / 1024));
-    hipLaunchKernelGGL(eh_bn_stats_kernel, dim3(nblk), dim3(1024), 0, h->stream, sp.recs, h->C, h->net.P, idx, (int)first, (int)count, h->bn_part, h->bn_shift);
+    hipLaunchKernelGGL(eh_bn_stats_kernel, dim3(nblk), dim3(1024), 0, h->stream, sp.recs, h->plan.C, h->net.P, idx, (int)first, (int)count, h->bn_part, h->bn_shift);
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(eh_bn_fold_kernel, dim3(1), dim3(64), 0, h->stream, h->bn_part, nblk, (int)count, h->bn_stat);
     HIPCHK(h, hipGetLastError());

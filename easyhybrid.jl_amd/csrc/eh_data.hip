@@ -60,7 +60,7 @@ int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, cons
     sp.recs = nullptr; sp.n = 0; sp.starts = nullptr; sp.nwin = 0;
     if (split == EH_SPLIT_TRAIN) h->perm_valid = false;
     if (n == 0) return EH_OK;
-    const int C = h->C;
+    const int C = h->plan.C;
     static const bool dbg_t = getenv("EH_DEBUG_SET_DATA") != nullptr;      // (diagnostic: where an upload's wall clock goes)
     const auto t_a = std::chrono::steady_clock::now();
     HIPCHK(h, hipMalloc(&sp.recs, (size_t)n * C * sizeof(float)));

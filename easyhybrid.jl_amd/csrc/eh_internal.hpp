@@ -1,5 +1,7 @@
 // Shared by the translation units of libeasyhybrid_hip.so: the handle behind the opaque eh_handle pointer, the error convention and the
 // functions that cross units.  The units, each the only instantiation of its kernels:
+//   eh_plan.hpp   (a header, no unit) the plan of a model: descriptor checks, block placement, the leaf table of flat theta, family, EhNet --
+//                 pure host code that eh_api.hip builds the handle from; eh_plan_dump.hip is a stand-alone program that prints it
 //   eh_api.hip    handle lifecycle, options, the training step and epoch, evaluation, the optimiser, graphs, the eh_dp_* seam
 //                 (kernels: eh_kernels.hpp, eh_chain.hpp)
 //   eh_data.hip   eh_set_data / eh_set_sequences, the pinned staging pair, the staged copies (eh_pack_kernel)
@@ -25,6 +27,7 @@
 
 #include "eh_arch.hpp"
 #include "eh_jit.hpp"
+#include "eh_plan.hpp"
 
 // Where the optimiser mirrors theta into the padded parameter image the step kernel stages.
 struct EhImg {
@@ -151,20 +154,13 @@ struct eh_handle_s {
     int* imap = nullptr;
     int* rmap = nullptr;            // reduction map for the current kernel family / variant / fast-path flags (v3: the inverse map)
     size_t rmap_cap = 0;
-    // block placement of every net inside the padded (block-diagonal) MLP
-    int n_nets = 1;                                     // 1 for SingleNN
-    int net_P[EH_MAX_NETS] = {0}, net_K[EH_MAX_NETS] = {0};
-    int net_w[EH_MAX_NETS][EH_MAX_HIDDEN] = {{0}};      // hidden widths of net k
-    int net_d[EH_MAX_NETS] = {0};                       // hidden layers of net k (layers past them: identity blocks, not in theta)
+    EhPlan plan;                    // what eh_plan_model made of the descriptor (eh_plan.hpp): block placement, the leaf table of flat theta, the layer tables; never changes
     char* mech_ws = nullptr;                            // eh_mech_loss_vjp: [counts | out | partial rows]
     size_t mech_ws_bytes = 0;
-    int net_c0[EH_MAX_NETS] = {0};                      // first predictor row of net k
-    int net_r0[EH_MAX_NETS][EH_MAX_HIDDEN + 1] = {{0}}; // first row of net k in layer l (l == n_hidden: output row)
-    int tot_w[EH_MAX_HIDDEN] = {0};                     // total (summed) hidden widths
     EhImg img{};
     int device = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;
-    int C = 0, n_acc = 0, n_par = 0;
+    int n_acc = 0;
     float *thb[2] = {nullptr, nullptr}, *mb[2] = {nullptr, nullptr}, *vb[2] = {nullptr, nullptr};   // parameter sets (fused mode ping-pongs them)
     float* pset = nullptr;          // backing allocation of thb/mb/vb/sc
     float* sc = nullptr;            // [EH_MAX_OPT_GROUPS][2][2] running beta products per optimiser group, ping-pong (group 0 = the one rule)
@@ -217,35 +213,25 @@ struct eh_handle_s {
     bool opt_ready = false;
     // sequence models (eh_seq.hpp): Dense-in -> LSTM -> head Dense -> output Dense over windows (EH_LAYER_LSTM); always the step + reduce pair
     bool seq = false;
-    int seq_I = 0, seq_H = 0, seq_nbi = 0, seq_nbh = 0, seq_act_in = 0, seq_act_hd = 0, seq_cell = 0, seq_act_cell = 0;      // (seq_cell: EH_SEQ_CELL_*)
-    int seq_off[10] = {0};           // canonical offsets of the ten leaves (EH_SEQ_WIN .. EH_SEQ_BOUT)
     float* seq_ws = nullptr;         // what the backward needs of every step, per wave of the grid (allocated outside graph capture)
     long long seq_ws_floats = 0;
     // layer-wise execution form (eh_lform.hpp): networks no fused kernel holds
     bool lform = false;
-    // one entry per network (SingleNN: one; MultiNN: one single-output network per neural parameter, each on its own predictor rows)
-    // (lbn[l] != 0: entry l is a BatchNorm layer, EH_LAYER_BATCHNORM -- 1 affine, 2 not --, or a LayerNorm layer, EH_LAYER_LAYERNORM -- 3 affine, 4 not;
-    //  in = out = its width, woff / boff = its scale / bias -- a LayerNorm's bias comes first in theta --, lact its activation)
-    struct LNet { int nl = 0, c0 = 0, orow = 0, act = 0; int lact[EH_MAX_HIDDEN + 1] = {0}; int in[EH_MAX_HIDDEN + 1] = {0}, out[EH_MAX_HIDDEN + 1] = {0}, woff[EH_MAX_HIDDEN + 1] = {0}, boff[EH_MAX_HIDDEN + 1] = {0}; int lbn[EH_MAX_HIDDEN + 1] = {0}; };
-    int l_nnets = 0;                                     // 0: no network at all (no neural parameter)
-    LNet l_net[EH_MAX_NETS];
     float* l_split = nullptr; size_t l_split_cap = 0;    // split-K partial products of the small-batch GEMMs
     unsigned* l_lprog = nullptr; int l_lprog_gen = -1;  // the recorded loss programs as the layer-wise form interprets them (device copy, generation it was made from)
     float* l_dk = nullptr; size_t l_dk_cap = 0;          // every layer's delta of a small-batch step (the weight gradients then run as one grouped launch)
     bool l_job_done = false;                              // lform_gemm -> eh_lform_train (eh_lform.hip): a few-rows product took the side job of summing the chain's partial rows
     EhLApply* l_apply = nullptr; bool l_applied = false;   // eh_do_step -> eh_lform_train: the optimiser may run in the epilogue of the grouped weight gradients / it did
     bool l_tail_fn[12] = {false};
-    // BatchNorm layers inside the chain (eh_bnl.hpp; one network, always this form, its few-rows fusions off): per layer l of l_net[0]
-    // with lbn[l] != 0, at bnl_off[l] floats into bnl_run: [running mean | running var]; at twice that into bnl_stat: [first row | mean about it | rstd]
-    // of the step, n each
+    // BatchNorm layers inside the chain (eh_bnl.hpp; one network, always this form, its few-rows fusions off): per BatchNorm layer l of
+    // plan.l_net[0], at plan.bnl_off[l] floats into bnl_run: [running mean | running var]; at twice that into bnl_stat: [first row | mean
+    // about it | rstd] of the step, n each
     // LayerNorm layers (eh_lnl.hpp) set `lnl` instead: the same form with the same fusions off, no state; they share bnl_eps and -- for the
-    // column sums of their leaves' gradients -- bnl_part / bnl_maxn, nothing else of this block
+    // column sums of their leaves' gradients -- bnl_part, as wide as plan.norm_maxn, nothing else of this block
     bool bnl = false, lnl = false;
-    int bnl_off[EH_MAX_HIDDEN + 1] = {0};
     float bnl_mom[EH_MAX_HIDDEN + 1] = {0}, bnl_eps[EH_MAX_HIDDEN + 1] = {0};      // eh_set_layer_norm (defaults: EH_BN_MOMENTUM, EH_BN_EPS)
     float *bnl_run = nullptr, *bnl_stat = nullptr;
     float* bnl_part = nullptr;                           // [EH_BNL_CHUNKS][2][widest] partial column sums, then [2][widest] their totals of the backward
-    int bnl_maxn = 0;
     float* l_ws = nullptr;                               // [Xb | H_0 .. H_{NL-1} | D0 | D1 | O | mech partial rows]
     long long l_cap = 0;                                 // samples the workspace holds
     unsigned char* wflag = nullptr;
@@ -293,7 +279,6 @@ struct eh_handle_s {
     unsigned long long drop_seed = 0, drop_step = 0;
     float* l2val = nullptr;         // lambda * weight_l2 of the current parameters (device scalar)
     float* l2w = nullptr;           // eh_set_weight_l2_coef: one coefficient per canonical entry (device)
-    int n_weights = 0;
     struct GraphRec { hipGraphExec_t exec; bool fused; int gslot, cur, sc_sel; bool pend_ord; int ord_grid; bool grouped; int chain_gen; };
     std::vector<GraphRec> graphs;         // eh_graph_*: captured step sequences + the rotation state they start (and must end) in
     bool capturing = false;
@@ -357,7 +342,7 @@ unsigned eh_two_pass_mask(const eh_handle* h);
 // what every pass over a window of a split hands its kernels: the fields all of them set alike, the rest zero
 inline EhStepArgs eh_step_args(const eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count) {
     EhStepArgs a{};
-    a.prog = h->prog; a.recs = sp.recs; a.C = h->C; a.idx = idx; a.first = first; a.count = count;
+    a.prog = h->prog; a.recs = sp.recs; a.C = h->plan.C; a.idx = idx; a.first = first; a.count = count;
     for (int t = 0; t < EH_MAX_TARG; ++t) a.shift[t] = sp.shift[t];
     return a;
 }

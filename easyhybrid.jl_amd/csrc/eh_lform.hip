@@ -14,11 +14,11 @@
 struct EhLWs { float *Xb, *H[EH_MAX_NETS][EH_MAX_HIDDEN], *Z[EH_MAX_NETS][EH_MAX_HIDDEN], *R[EH_MAX_HIDDEN], *D[2], *O, *part; long long ldo; };      // (R[l]: a LayerNorm layer's rstd, one per sample)
 static long long lform_floats_per_sample(const eh_handle* h) {
     long long w = h->net.P + 16, maxw = 0;
-    for (int k = 0; k < h->l_nnets; ++k)
-        for (int l = 0; l + 1 < h->l_net[k].nl; ++l) {
-            w += h->l_net[k].out[l] * ((h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) ? 2 : 1);      // swish keeps the pre-activation too, a BatchNorm / LayerNorm layer its normalised input
-            w += h->l_net[k].lbn[l] >= 3 ? 1 : 0;      // ... a LayerNorm layer its rows' rstd
-            maxw = std::max<long long>(maxw, h->l_net[k].out[l]);
+    for (int k = 0; k < h->plan.l_nnets; ++k)
+        for (int l = 0; l + 1 < h->plan.l_net[k].nl; ++l) {
+            w += h->plan.l_net[k].out[l] * ((h->plan.l_net[k].lact[l] == EH_ACT_SWISH || eh_is_norm(h->plan.l_net[k].kind[l])) ? 2 : 1);      // swish keeps the pre-activation too, a BatchNorm / LayerNorm layer its normalised input
+            w += eh_is_layernorm(h->plan.l_net[k].kind[l]) ? 1 : 0;      // ... a LayerNorm layer its rows' rstd
+            maxw = std::max<long long>(maxw, h->plan.l_net[k].out[l]);
         }
     return w + 2 * maxw;
 }
@@ -46,14 +46,14 @@ static int lform_workspace(eh_handle* h, long long count, EhLWs* W) {
     float* p = h->l_ws;
     long long maxw = 0;
     W->Xb = p; p += cap * h->net.P;
-    for (int k = 0; k < h->l_nnets; ++k)
-        for (int l = 0; l + 1 < h->l_net[k].nl; ++l) {
-            const long long o = h->l_net[k].out[l];
+    for (int k = 0; k < h->plan.l_nnets; ++k)
+        for (int l = 0; l + 1 < h->plan.l_net[k].nl; ++l) {
+            const long long o = h->plan.l_net[k].out[l];
             maxw = std::max(maxw, o);
             W->H[k][l] = p; p += cap * o;
             W->Z[k][l] = nullptr;
-            if (h->l_net[k].lact[l] == EH_ACT_SWISH || h->l_net[k].lbn[l]) { W->Z[k][l] = p; p += cap * o; }
-            if (k == 0) { W->R[l] = nullptr; if (h->l_net[k].lbn[l] >= 3) { W->R[l] = p; p += cap; } }      // (cap is a multiple of 128: what follows stays 16-byte aligned)
+            if (h->plan.l_net[k].lact[l] == EH_ACT_SWISH || eh_is_norm(h->plan.l_net[k].kind[l])) { W->Z[k][l] = p; p += cap * o; }
+            if (k == 0) { W->R[l] = nullptr; if (eh_is_layernorm(h->plan.l_net[k].kind[l])) { W->R[l] = p; p += cap; } }      // (cap is a multiple of 128: what follows stays 16-byte aligned)
         }
     W->D[0] = p; p += cap * maxw;
     W->D[1] = p; p += cap * maxw;
@@ -162,14 +162,14 @@ static int bnl_chunks(int B, int* chunk) {
 }
 static unsigned bnl_ew_grid(long long tot, bool vec) { return (unsigned)std::max<long long>(1, std::min<long long>(4096, ((vec ? tot / 4 : tot) + 255) / 256)); }
 static int bnl_forward_layer(eh_handle* h, int l, int B, bool train_mode, bool update, const EhLWs& W) {
-    const eh_handle_s::LNet& L = h->l_net[0];
+    const EhLNet& L = h->plan.l_net[0];
     const int n = L.out[l];
     const float* theta = TH(h);
-    const float* gamma = L.lbn[l] == 1 ? theta + L.woff[l] : nullptr;
-    const float* beta = L.lbn[l] == 1 ? theta + L.boff[l] : nullptr;
+    const float* gamma = eh_affine(L.kind[l]) ? theta + L.woff[l] : nullptr;
+    const float* beta = eh_affine(L.kind[l]) ? theta + L.boff[l] : nullptr;
     const float* X = W.H[0][l - 1];
-    float* stat = h->bnl_stat + 2 * h->bnl_off[l];      // [c | d | rstd]
-    float* run = h->bnl_run + h->bnl_off[l];
+    float* stat = h->bnl_stat + 2 * h->plan.bnl_off[l];      // [c | d | rstd]
+    float* run = h->bnl_run + h->plan.bnl_off[l];
     if (train_mode) {
         EhBnlArgs a{};
         a.X = X; a.part = h->bnl_part; a.B = B; a.n = n; a.act = L.lact[l];
@@ -188,22 +188,22 @@ static int bnl_forward_layer(eh_handle* h, int l, int B, bool train_mode, bool u
 }
 // ... its backward: dY [B x n] -> d scale / d bias into the slab (row 0; zeros in the other rows), dZ of the layer below into dX
 static int bnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float* dX, int rows, const EhLWs& W) {
-    const eh_handle_s::LNet& L = h->l_net[0];
+    const EhLNet& L = h->plan.l_net[0];
     const int n = L.out[l];
     const float* theta = TH(h);
-    const bool affine = L.lbn[l] == 1;
+    const bool affine = eh_affine(L.kind[l]);
     EhBnlArgs a{};
     a.X = dY; a.Xh = W.Z[0][l]; a.Y = W.H[0][l]; a.gamma = affine ? theta + L.woff[l] : nullptr; a.beta = affine ? theta + L.boff[l] : nullptr;
     a.part = h->bnl_part; a.B = B; a.n = n; a.act = L.lact[l];
     const int nchunk = bnl_chunks(B, &a.chunk);
-    float* sums = h->bnl_part + (size_t)EH_BNL_CHUNKS * 2 * h->bnl_maxn;
+    float* sums = h->bnl_part + (size_t)EH_BNL_CHUNKS * 2 * h->plan.norm_maxn;
     hipLaunchKernelGGL((eh_bnl_colsum_kernel<true>), dim3((unsigned)((n + 63) / 64), (unsigned)nchunk), dim3(256), 0, h->stream, a);
     hipLaunchKernelGGL(eh_bnl_fold_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->bnl_part, nchunk, n, sums,
                        affine ? h->slab + L.woff[l] : nullptr, affine ? h->slab + L.boff[l] : nullptr, rows, (long long)h->n_acc);
     EhBnlDxArgs d{};
-    d.dY = dY; d.Xh = a.Xh; d.Y = a.Y; d.gamma = a.gamma; d.beta = a.beta; d.rstd = h->bnl_stat + 2 * h->bnl_off[l] + 2 * n; d.sums = sums;
+    d.dY = dY; d.Xh = a.Xh; d.Y = a.Y; d.gamma = a.gamma; d.beta = a.beta; d.rstd = h->bnl_stat + 2 * h->plan.bnl_off[l] + 2 * n; d.sums = sums;
     // (the layer below: a Dense layer's act' from its output -- swish: its pre-activation --; a BatchNorm layer takes its own in its own backward)
-    d.act_below = L.lbn[l - 1] ? (int)EH_ACT_IDENTITY : L.lact[l - 1];
+    d.act_below = eh_is_norm(L.kind[l - 1]) ? (int)EH_ACT_IDENTITY : L.lact[l - 1];
     d.Hb = (d.act_below == EH_ACT_SWISH) ? W.Z[0][l - 1] : W.H[0][l - 1];
     d.dX = dX; d.tot = (long long)B * n; d.n = n; d.act = L.lact[l]; d.inv_b = 1.0f / (float)B;
     d.vec = bnl_vec_ok(n, {d.dY, d.Xh, d.Y, d.Hb, d.dX}) ? 1 : 0;
@@ -223,11 +223,11 @@ static void lnl_geometry(int n, int B, int* seg, int* per, unsigned* grid) {
     *grid = (unsigned)((B + rows_wg - 1) / rows_wg);
 }
 static int lnl_forward_layer(eh_handle* h, int l, int B, bool keep, const EhLWs& W) {
-    const eh_handle_s::LNet& L = h->l_net[0];
+    const EhLNet& L = h->plan.l_net[0];
     const float* theta = TH(h);
     EhLnlFwdArgs a{};
     a.X = W.H[0][l - 1]; a.Y = W.H[0][l]; a.Xh = keep ? W.Z[0][l] : nullptr; a.rstd = keep ? W.R[l] : nullptr;
-    a.scale = L.lbn[l] == 3 ? theta + L.woff[l] : nullptr; a.bias = L.lbn[l] == 3 ? theta + L.boff[l] : nullptr;
+    a.scale = eh_affine(L.kind[l]) ? theta + L.woff[l] : nullptr; a.bias = eh_affine(L.kind[l]) ? theta + L.boff[l] : nullptr;
     a.B = B; a.n = L.out[l]; a.act = L.lact[l]; a.eps = h->bnl_eps[l];
     int per; unsigned grid;
     lnl_geometry(a.n, B, &a.seg, &per, &grid);
@@ -245,14 +245,14 @@ static int lnl_forward_layer(eh_handle* h, int l, int B, bool keep, const EhLWs&
 // ... its backward: dY [B x n] -> dZ of the layer below into dX (one launch); affine: d scale / d bias as column sums over the rows, by the
 // BatchNorm layers' two kernels, into the slab (row 0; zeros in the other rows)
 static int lnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float* dX, int rows, const EhLWs& W) {
-    const eh_handle_s::LNet& L = h->l_net[0];
+    const EhLNet& L = h->plan.l_net[0];
     const int n = L.out[l];
     const float* theta = TH(h);
-    const bool affine = L.lbn[l] == 3;
+    const bool affine = eh_affine(L.kind[l]);
     EhLnlBwdArgs d{};
     d.dY = dY; d.Xh = W.Z[0][l]; d.Y = W.H[0][l]; d.rstd = W.R[l];
     d.scale = affine ? theta + L.woff[l] : nullptr; d.bias = affine ? theta + L.boff[l] : nullptr;
-    d.act_below = L.lbn[l - 1] ? (int)EH_ACT_IDENTITY : L.lact[l - 1];
+    d.act_below = eh_is_norm(L.kind[l - 1]) ? (int)EH_ACT_IDENTITY : L.lact[l - 1];
     d.Hb = (d.act_below == EH_ACT_SWISH) ? W.Z[0][l - 1] : W.H[0][l - 1];
     d.dX = dX; d.B = B; d.n = n; d.act = L.lact[l];
     int per; unsigned grid;
@@ -269,7 +269,7 @@ static int lnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float
         EhBnlArgs a{};
         a.X = dY; a.Xh = d.Xh; a.Y = d.Y; a.gamma = d.scale; a.beta = d.bias; a.part = h->bnl_part; a.B = B; a.n = n; a.act = L.lact[l];
         const int nchunk = bnl_chunks(B, &a.chunk);
-        float* sums = h->bnl_part + (size_t)EH_BNL_CHUNKS * 2 * h->bnl_maxn;      // (the totals: nothing reads them here, the leaves' gradients are all of them)
+        float* sums = h->bnl_part + (size_t)EH_BNL_CHUNKS * 2 * h->plan.norm_maxn;      // (the totals: nothing reads them here, the leaves' gradients are all of them)
         hipLaunchKernelGGL((eh_bnl_colsum_kernel<true>), dim3((unsigned)((n + 63) / 64), (unsigned)nchunk), dim3(256), 0, h->stream, a);
         hipLaunchKernelGGL(eh_bnl_fold_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)h->bnl_part, nchunk, n, sums,
                            h->slab + L.woff[l], h->slab + L.boff[l], rows, (long long)h->n_acc);
@@ -282,7 +282,7 @@ static int lnl_backward_layer(eh_handle* h, int l, int B, const float* dY, float
 static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, bool train_mode, bool bn_update, const EhLWs& W, int lstop = -1) {
     const EhNet& net = h->net;
     const int B = (int)count;
-    if (h->l_nnets == 0) return EH_OK;        // no network (no neural parameter): the mechanistic stage reads the records itself
+    if (h->plan.l_nnets == 0) return EH_OK;        // no network (no neural parameter): the mechanistic stage reads the records itself
     EhStepArgs bn{};
     // (small minibatches: the prep kernel takes the batch statistics itself -- one dependent launch fewer)
     static const bool nofuse_env = getenv("EH_LFORM_NOFUSE") != nullptr;
@@ -290,7 +290,7 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
     const bool bn_self = train_mode && h->bn_on && !h->bn_ext && count > 0 && count <= 256 && !nofuse;
     if (train_mode && !bn_self) { if (int rc = eh_bn_prepare(h, sp, idx, first, count, bn_update, &bn)) return rc; }
     EhLPrepArgs pa{};
-    pa.recs = sp.recs; pa.C = h->C; pa.P = net.P; pa.idx = idx; pa.first = first; pa.count = B; pa.Xb = W.Xb; pa.meta = h->image;
+    pa.recs = sp.recs; pa.C = h->plan.C; pa.P = net.P; pa.idx = idx; pa.first = first; pa.count = B; pa.Xb = W.Xb; pa.meta = h->image;
     pa.bn_part = bn.bn_part; pa.bn_nblk = bn.bn_nblk; pa.bn_c = bn.bn_c; pa.bn_n = bn.bn_n; pa.bn_update = bn.bn_update; pa.bn_run = h->bn_run;
     if (bn_self) { pa.bn_self = 1; pa.bn_update = bn_update ? 1 : 0; }
     static const bool stamp_first = getenv("EH_STAMP_FIRST") != nullptr;      // (diagnostic builds: the stamps of the first launch instead of the chain kernel's)
@@ -304,7 +304,7 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
         static const bool nofirst = getenv("EH_LFORM_NOFIRST") != nullptr;
         static const bool nofew = getenv("EH_GEMM_NOFEWROWS") != nullptr;
         static const int first_maxb = getenv("EH_LFORM_FIRST_MAXB") ? atoi(getenv("EH_LFORM_FIRST_MAXB")) : 64;   // every workgroup takes the statistics itself: a loss from ~128 rows up
-        const eh_handle_s::LNet& L0 = h->l_net[0];
+        const EhLNet& L0 = h->plan.l_net[0];
         const int stop = lstop >= 0 ? lstop : L0.nl;
         auto al16 = [](const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; };
         if (!nofirst && !nofuse && !nofew && !g_gemm_novec && L0.nl >= 3 && stop >= 2 && L0.in[0] <= 4 && B >= 1 && B <= first_maxb &&
@@ -328,7 +328,7 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
     // the first network's first layer rides along when it is one of the few-predictor products (K <= 8, hidden layer behind it)
     bool fused0 = false;
     if (!fused01) {
-        const eh_handle_s::LNet& L0 = h->l_net[0];
+        const EhLNet& L0 = h->plan.l_net[0];
         if (!nofuse && !g_gemm_novec && L0.nl >= 2 && L0.in[0] <= 8 && lstop != 0) {
             EhGemmArgs g{};
             g.A = nullptr; g.lda = net.P; g.B = theta + L0.woff[0]; g.ldb = L0.out[0];
@@ -341,13 +341,13 @@ static int lform_forward(eh_handle* h, const EhSplit& sp, const int* idx, long l
     }
     if (!fused0 && !fused01) hipLaunchKernelGGL((eh_lform_prep_kernel<false>), dim3((unsigned)std::max<long long>(1, std::min<long long>(1024, (tot + 255) / 256))), dim3(256), 0, h->stream, pa, EhGemmArgs{}, 0);
     HIPCHK(h, hipGetLastError());
-    for (int k = 0; k < h->l_nnets; ++k) {
-        const eh_handle_s::LNet& L = h->l_net[k];
+    for (int k = 0; k < h->plan.l_nnets; ++k) {
+        const EhLNet& L = h->plan.l_net[k];
         for (int l = 0; l < (lstop >= 0 ? lstop : L.nl); ++l) {
             if ((fused0 || fused01) && k == 0 && l == 0) continue;
             if (fused01 && k == 0 && l == 1) continue;
-            if (L.lbn[l] >= 3) { if (int rc = lnl_forward_layer(h, l, B, train_mode, W)) return rc; continue; }
-            if (L.lbn[l]) { if (int rc = bnl_forward_layer(h, l, B, train_mode, bn_update, W)) return rc; continue; }
+            if (eh_is_layernorm(L.kind[l])) { if (int rc = lnl_forward_layer(h, l, B, train_mode, W)) return rc; continue; }
+            if (eh_is_norm(L.kind[l])) { if (int rc = bnl_forward_layer(h, l, B, train_mode, bn_update, W)) return rc; continue; }
             EhGemmArgs g{};
             g.A = l == 0 ? W.Xb + L.c0 : W.H[k][l - 1]; g.lda = l == 0 ? net.P : L.in[l];      // (a network's predictors: its columns of the minibatch matrix)
             g.B = theta + L.woff[l]; g.ldb = L.out[l];                   // canonical (out, in) column-major == [in][out] row-major
@@ -383,15 +383,15 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     // Small minibatches: every layer's delta is kept (l_dk), the chain of delta products runs first and the weight gradients -- a
     // handful of tiles each, 4-6 us per dependent launch -- follow as ONE grouped launch of the tiled ones and one of the thin ones.
     static const long long lgroup_max = getenv("EH_LFORM_GROUP_MAX") ? atoll(getenv("EH_LFORM_GROUP_MAX")) : 4096;
-    bool grouped = count <= lgroup_max && h->l_nnets > 0 && !h->bnl && !h->lnl;      // (the kept-deltas groups and the tail chain behind them hold Dense layers only)
+    bool grouped = count <= lgroup_max && h->plan.l_nnets > 0 && !h->bnl && !h->lnl;      // (the kept-deltas groups and the tail chain behind them hold Dense layers only)
     long long dk_floats = 0;
     // (sized by THIS minibatch, rounded up to a power of two -- not by the largest one the path serves: a B = 64 step of a deep, wide
     //  MultiNN model used to ask for up to the 1 GiB cap; advisor, round 3.  A larger batch later re-grows it, outside a capture.)
     long long dk_rows = 64;
     while (dk_rows < count) dk_rows *= 2;
     if (grouped) {
-        for (int k = 0; k < h->l_nnets; ++k)
-            for (int l = 0; l + 1 < h->l_net[k].nl; ++l) dk_floats += dk_rows * h->l_net[k].out[l];
+        for (int k = 0; k < h->plan.l_nnets; ++k)
+            for (int l = 0; l + 1 < h->plan.l_net[k].nl; ++l) dk_floats += dk_rows * h->plan.l_net[k].out[l];
         if (dk_floats > (1ll << 28)) { grouped = false; h->jit_log = "layer-wise form: kept deltas of this minibatch exceed 1 GiB -- weight gradients run layer by layer (slower small-batch steps)"; }
         else if ((size_t)dk_floats > h->l_dk_cap) {
             if (h->capturing) return lform_alloc_in_capture(h, "kept deltas");
@@ -409,8 +409,8 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     //  per step at 96 / 128 / 192 / 256 rows against 70.9 / 74.2 / 80.1 / 86.6 with the products launched one by one.  With FOUR rows per
     //  workgroup, the form of the round's first half for more than 64 rows, it was slower than either: 75.5 / 78.6 / 90.2 / 96.7; those
     //  instantiations are gone.)
-    if (!notail && grouped && h->l_nnets == 1 && count <= 256 && !tpm && !g_gemm_novec) {
-        const eh_handle_s::LNet& L = h->l_net[0];
+    if (!notail && grouped && h->plan.l_nnets == 1 && count <= 256 && !tpm && !g_gemm_novec) {
+        const EhLNet& L = h->plan.l_net[0];
         long long wsum = 0;
         for (int l = L.nl - 1; l >= 0; --l) {
             if (L.in[l] > (int)EH_LTAIL_MAXW || L.out[l] > (int)EH_LTAIL_MAXW || wsum + (long long)L.in[l] * L.out[l] > (96ll << 10)) break;
@@ -467,7 +467,7 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
     if (mgrid == 1 && !nofuse) { m.slab = h->slab; m.nrows = rows; m.n_acc = (long long)h->n_acc; }      // one workgroup: it writes the slab's tail columns itself
     EhLTailJob tjob{nullptr, 0, nullptr, 0, 0};
     if (tail_s >= 0) {
-        const eh_handle_s::LNet& L = h->l_net[0];
+        const EhLNet& L = h->plan.l_net[0];
         const float* theta = TH(h);
         EhLTailArgs t{};
         t.nl = L.nl - tail_s;
@@ -543,16 +543,16 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
         TG.n = 0;
     };
     float* dkp = h->l_dk;
-    for (int k = 0; k < h->l_nnets; ++k) {
-        const eh_handle_s::LNet& L = h->l_net[k];
+    for (int k = 0; k < h->plan.l_nnets; ++k) {
+        const EhLNet& L = h->plan.l_net[k];
         const float* dZ = W.O + (long long)L.orow * W.ldo;
         bool dz_t = true;                      // dZ stored transposed ([out][B])
         int which = 0;
         for (int l = L.nl - 1; l >= 0; --l) {
             const int in = L.in[l], out = L.out[l];
-            if (L.lbn[l]) {                    // a BatchNorm / LayerNorm layer: dZ is d loss / d its output; its leaves' sums to the slab, the delta of the layer below to the other buffer
+            if (eh_is_norm(L.kind[l])) {                    // a BatchNorm / LayerNorm layer: dZ is d loss / d its output; its leaves' sums to the slab, the delta of the layer below to the other buffer
                 float* const dnext = W.D[which];
-                if (int rc = L.lbn[l] >= 3 ? lnl_backward_layer(h, l, B, dZ, dnext, rows, W) : bnl_backward_layer(h, l, B, dZ, dnext, rows, W)) return rc;
+                if (int rc = eh_is_layernorm(L.kind[l]) ? lnl_backward_layer(h, l, B, dZ, dnext, rows, W) : bnl_backward_layer(h, l, B, dZ, dnext, rows, W)) return rc;
                 dZ = dnext; dz_t = false; which ^= 1;
                 continue;
             }
@@ -589,7 +589,7 @@ int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long fi
                     }
                     b.C = dnext; b.ldc = in; b.M = B; b.N = in; b.K = out; b.kchunk = out; b.c_zstride = 0;
                     b.H = L.lact[l - 1] == EH_ACT_SWISH ? W.Z[k][l - 1] : W.H[k][l - 1]; b.ldh = in; b.act = L.lact[l - 1];
-                    if (L.lbn[l - 1]) { b.H = W.H[k][l - 1]; b.act = EH_ACT_IDENTITY; }      // (the layer below is a BatchNorm layer: its backward applies its own act')
+                    if (eh_is_norm(L.kind[l - 1])) { b.H = W.H[k][l - 1]; b.act = EH_ACT_IDENTITY; }      // (the layer below is a BatchNorm layer: its backward applies its own act')
                     if (dz_t) lform_gemm<true, true, EH_GEPI_DACT>(h, b, 1); else lform_gemm<false, true, EH_GEPI_DACT>(h, b, 1);
                     HIPCHK(h, hipGetLastError());
                 }
