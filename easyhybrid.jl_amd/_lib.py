@@ -13,6 +13,7 @@ EH_MAX_HIDDEN, EH_MAX_PARAMS, EH_MAX_FORC, EH_MAX_TARG, EH_MAX_NETS = 8, 8, 4, 4
 EH_MAX_PROG, EH_MAX_PROG_CONST, EH_MAX_PROG_OUT = 64, 16, 3
 EH_MAX_OPT_GROUPS = 16
 EH_MAX_OPT_STAGES = 8
+EH_ENS_MAX_MEMBERS = 4096
 EH_STAGE_RULE, EH_STAGE_CLIPGRAD, EH_STAGE_CLIPNORM, EH_STAGE_WEIGHTDECAY = 0, 1, 2, 3
 EH_MECH_PROGRAM = 6
 EH_LOSS_PROGRAM = 7
@@ -84,6 +85,7 @@ LIB_PATH = os.environ.get("EASYHYBRID_HIP_LIB") or os.path.join(os.path.dirname(
 _F = C.POINTER(C.c_float)
 _FP = C.POINTER(_F)
 _H = C.c_void_p
+_E = C.c_void_p
 
 # name -> (restype, argtypes); every symbol include/easyhybrid_hip.h declares
 SIGNATURES = {
@@ -170,6 +172,21 @@ SIGNATURES = {
     "eh_set_dropout": (C.c_int32, [_H, _F, C.c_int32, C.c_uint64, C.c_uint64]),
     "eh_get_dropout": (C.c_int32, [_H, _F, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "eh_dropout_mask": (C.c_int32, [_H, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
+    # ensembles (_E: the eh_ensemble pointer)
+    "eh_ens_create": (C.c_int32, [_H, C.c_int32, C.c_int64, C.POINTER(_E)]),
+    "eh_ens_destroy": (C.c_int32, [_E]),
+    "eh_ens_set_params": (C.c_int32, [_E, C.c_int32, _F, C.c_int64]),
+    "eh_ens_get_params": (C.c_int32, [_E, C.c_int32, _F, C.c_int64]),
+    "eh_ens_set_opt": (C.c_int32, [_E, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "eh_ens_get_opt_state": (C.c_int32, [_E, C.c_int32, _F, _F, C.c_int64, _F]),
+    "eh_ens_set_opt_state": (C.c_int32, [_E, C.c_int32, _F, _F, C.c_int64, _F]),
+    "eh_ens_get_bn_state": (C.c_int32, [_E, C.c_int32, _F, _F, C.c_int64]),
+    "eh_ens_set_bn_state": (C.c_int32, [_E, C.c_int32, _F, _F, C.c_int64]),
+    "eh_ens_set_rows": (C.c_int32, [_E, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]),
+    "eh_ens_train_epoch": (C.c_int32, [_E, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint8), _F, C.POINTER(C.c_int64)]),
+    "eh_ens_eval": (C.c_int32, [_E, C.c_int32, C.POINTER(TargetMetrics)]),
+    "eh_ens_load": (C.c_int32, [_E, C.c_int32]),
+    "eh_ens_store": (C.c_int32, [_E, C.c_int32]),
 }
 
 

@@ -771,6 +771,7 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
 
 int32_t eh_destroy(eh_handle* h) {
     if (!h) return EH_OK;
+    if (h->ens_live) return fail(h, EH_ESTATE, "eh_destroy: the handle carries an ensemble (eh_ens_destroy it first)");
     (void)hipSetDevice(h->device);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     for (auto e : h->ev) (void)hipEventDestroy(e);
@@ -963,6 +964,7 @@ static bool so_allowed(const eh_handle* h) {
 
 static int32_t set_option(eh_handle* h, const char* name, int64_t value);
 int32_t eh_set_option(eh_handle* h, const char* name, int64_t value) {
+    if (h && h->ens_live) return fail(h, EH_ESTATE, "eh_set_option: the handle carries an ensemble (eh_ens_destroy it first)");
     if (!h || !name) return EH_EINVAL;
     const int32_t rc = set_option(h, name, value);
     lean_refresh(h);                         // (an option may move the handle into or out of the lean kernels' contract)
@@ -1580,6 +1582,82 @@ static int do_fused_multi(eh_handle* h, const EhSplit& sp, const int* idx, long 
     return EH_OK;
 }
 
+// ---- the seam of eh_ens.hip: what an ensemble needs of this unit's launchers and kernels -------------------------------------------------
+// Why the handle cannot carry an ensemble at this batch size, one sentence per cause (empty: it can).  The conditions are multi_ok's --
+// an ensemble launch IS the multi-step launch, per member -- minus its one way out (a run-time compiled kernel), plus what the handle
+// types that never reach multi_ok would fail on.
+std::string eh_ens_refusal(eh_handle* h, long long batch) {
+    std::string w;
+    auto say = [&](const char* t) { if (!w.empty()) w += " "; w += t; };
+    if (h->seq) say("Sequence models train on windows with a kernel family of their own.");
+    if (h->lform) say("The model runs in the layer-wise form (no fused step kernel holds it: more than three hidden layers, normalisation layers, or widths above 128).");
+    if (!h->seq && !h->lform && h->arch->wide) say(h->arch->var[h->variant].bf16 ? "The model runs on the row-split bf16 kernels, whose step needs several workgroups." : "The model runs on the row-split kernels (hidden widths above 64), whose step is not the one-workgroup step.");
+    if (!h->fused) say("The handle is not in fused-update mode (option fused_update).");
+    if (!h->multi_step) say("The multi_step option is off.");
+    if (h->p2p_on || h->comm || h->lgroup) say("Data parallelism is set up on the handle.");
+    if (h->prof) say("Profiling is enabled on the handle.");
+    if (h->capturing) say("A graph is being captured.");
+    if (h->chain.n) say("An OptimiserChain is installed.");
+    if (h->drop_on) say("Dropout needs a step kernel compiled at run time.");
+    if (h->net.T != 1) say("Several targets need a counting pass ahead of every step.");
+    if (h->net.mech == EH_MECH_PROGRAM) say("A recorded mechanistic closure runs on kernels compiled at run time.");
+    if (h->net.loss == EH_LOSS_PROGRAM) say("A recorded loss runs on kernels compiled at run time.");
+    if (eh_two_pass_mask(h)) say("The two-pass losses (pearsonLoss, kgeLoss, pbkgeLoss) take two forward passes ahead of every step.");
+    if (h->act == EH_ACT_PER_NET) say("Per-net or per-layer activations run on kernels compiled at run time.");
+    if (h->bn_on && (h->bn_ext || h->bn_no_self || batch > EH_BN_SELF_MAX)) say("Input BatchNorm takes its statistics inside the step kernel only for minibatches up to 512 samples (and not with bn_in_kernel 0).");
+    if (!w.empty()) return w;
+    char b[256];
+    if (h->arch->var[h->variant].lds_bytes + sizeof(float) * (size_t)eh_ms_extra_floats(h->net.n_theta, h->n_acc, false) > EH_LDS_LIMIT) {
+        snprintf(b, sizeof b, "The %d parameters with their optimiser state do not fit the LDS behind the step's work space.", h->net.n_theta);
+        say(b);
+    }
+    if (grid_for(h, batch) != 1) {
+        const EhVariant& v = h->arch->var[h->variant];
+        snprintf(b, sizeof b, "A minibatch of %lld samples is more than one workgroup covers (%d).", batch, 16 * v.nt * (v.tiles ? v.tiles : v.nw));
+        say(b);
+    }
+    if (!spec_lookup(h) && jit_wanted(h, EH_MODE_TRAIN)) say("The handle runs kernels compiled at run time (option specialize).");
+    return w;
+}
+// the handle's optimiser rule was replaced from outside (eh_ens_load): what follows from it
+void eh_opt_changed(eh_handle* h) { if (h->lb) h->lb->active = false; h->chain = EhChain{}; h->chain_gen = 0; lean_refresh(h); }
+// one launch: `members` workgroups, each the multi-step launch of its record (eh_ens.hpp); the ahead-of-time specialised kernel where the handle runs one
+int eh_ens_launch_train(eh_handle* h, int members, const EhStepArgs* a, const EhEnsMember* mem) {
+    // (no way out to the generic kernel where the ahead-of-time one fails to launch: which kernel ran is part of a member's parity with an
+    //  ordinary handle, and a failure is the caller's to see)
+    const EhSpecKernel* sk = spec_lookup(h);
+    if (sk && sk->launch_ens) {
+        HIPCHK(h, sk->launch_ens(members, h->stream, &h->net, a, mem));
+        h->spec_used = sk;
+        return EH_OK;
+    }
+    const EhVariant& v = h->arch->var[h->variant];
+    if (!v.launch_ens) return fail(h, EH_EUNSUPPORTED, "eh_ens_train_epoch: no ensemble kernel for this kernel family");
+    HIPCHK(h, v.launch_ens(h->act, KFAST(h), members, h->stream, &h->net, a, mem));
+    return EH_OK;
+}
+// an evaluation pass of the handle's kernels on the arguments as given (a member's image and row list); *grid in: 0 = by count
+int eh_ens_launch_eval(eh_handle* h, const EhStepArgs* a, int grid) {
+    HIPCHK(h, step_launch(h, EH_MODE_EVAL, grid, a));
+    return EH_OK;
+}
+int eh_ens_eval_grid(const eh_handle* h, long long count) { return count > 0 ? eval_grid_for(h, count) : 1; }
+// theta -> a member's parameter image
+int eh_ens_launch_image(eh_handle* h, const float* theta, float* image) {
+    EhImg im = h->img;
+    im.image = image;
+    hipLaunchKernelGGL(eh_image_kernel, dim3((unsigned)((h->net.n_theta + 255) / 256)), dim3(256), 0, h->stream, theta, h->net.n_theta, im);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+// the epoch orders of all members in one launch: order[off_j + i] = rows_j[perm(n_j, seed_j)(i)] (eh_ens_order_kernel)
+int eh_ens_launch_order(eh_handle* h, const EhEnsOrder* ord, int members, long long max_n) {
+    if (max_n <= 0) return EH_OK;
+    hipLaunchKernelGGL(eh_ens_order_kernel, dim3((unsigned)((max_n + 255) / 256), (unsigned)members), dim3(256), 0, h->stream, ord);
+    HIPCHK(h, hipGetLastError());
+    return EH_OK;
+}
+
 // The chain kernels (eh_chain.hpp) on the gradient in h->gradbuf.  raw: the data-parallel seam's all-reduced sums (eh_dp_apply), whose
 // loss the apply pass writes to loss_slot; otherwise eh_reduce_kernel<false, ...> has written gradient and loss.
 static int launch_chain(eh_handle* h, bool raw, float* sc_in, float* sc_out, float* loss_slot) {
@@ -1848,24 +1926,12 @@ static int do_eval(eh_handle* h, int split, long long first, long long count, do
     return EH_OK;
 }
 
-extern "C" {
-
-int32_t eh_forward(eh_handle* h, int32_t split, int64_t first, int64_t count, float* const* yhat, float* const* params) {
-    if (!h) return EH_EINVAL;
-    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_forward: split %d", split);
-    return do_eval(h, split, first, count, nullptr, yhat, params);
-}
-
-int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_target_metrics* out, float* const* yhat, float* const* params) {
-    if (!h || !out) return EH_EINVAL;
-    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_eval: split %d", split);
-    double st[EH_MAX_TARG * EH_EVAL_STATS] = {0};
-    int rc = do_eval(h, split, first, count, st, yhat, params);
-    if (rc) return rc;
+// the metrics of eh_target_metrics from the EH_EVAL_STATS sums per target of an evaluation pass, taken about the shifts c_t (eh_eval, eh_ens_eval)
+void eh_metrics_from_sums(const double* st, const float* shift, int T, eh_target_metrics* out) {
     const double nan = std::nan("");
-    for (int t = 0; t < h->net.T; ++t) {
+    for (int t = 0; t < T; ++t) {
         const double* s = st + t * EH_EVAL_STATS;
-        const double c = h->split[split].shift[t];
+        const double c = shift[t];
         const double S = s[0], Sy = s[1], Syy = s[2], n = s[3], Sh = s[4], Shh = s[5], Shy = s[6], A = s[7];
         eh_target_metrics& o = out[t];
         o.n = n; o.sse = S;
@@ -1885,6 +1951,23 @@ int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_ta
         o.kge = 1.0 - std::sqrt((o.pearson - 1) * (o.pearson - 1) + (o.alpha - 1) * (o.alpha - 1) + (o.beta - 1) * (o.beta - 1));
         o.pbkge = 1.0 - std::sqrt((o.pearson - 1) * (o.pearson - 1) + (o.beta - 1) * (o.beta - 1));
     }
+}
+
+extern "C" {
+
+int32_t eh_forward(eh_handle* h, int32_t split, int64_t first, int64_t count, float* const* yhat, float* const* params) {
+    if (!h) return EH_EINVAL;
+    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_forward: split %d", split);
+    return do_eval(h, split, first, count, nullptr, yhat, params);
+}
+
+int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_target_metrics* out, float* const* yhat, float* const* params) {
+    if (!h || !out) return EH_EINVAL;
+    if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_eval: split %d", split);
+    double st[EH_MAX_TARG * EH_EVAL_STATS] = {0};
+    int rc = do_eval(h, split, first, count, st, yhat, params);
+    if (rc) return rc;
+    eh_metrics_from_sums(st, h->split[split].shift, h->net.T, out);
     return EH_OK;
 }
 
@@ -2004,6 +2087,7 @@ static int opt_restart(eh_handle* h, const float* sc, size_t sc_bytes) {
 }
 int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay) {
     if (!h) return EH_EINVAL;
+    if (h->ens_live) return fail(h, EH_ESTATE, "eh_opt_init: the handle carries an ensemble (eh_ens_destroy it first)");
     if (rule < EH_OPT_ADAM || rule > EH_OPT_DESCENT) return fail(h, EH_EUNSUPPORTED, "eh_opt_init: unknown rule %d", rule);
     HIPCHK(h, hipSetDevice(h->device));
     FLUSH(h);
@@ -2016,6 +2100,7 @@ int32_t eh_opt_init(eh_handle* h, int32_t rule, float lr, float beta1, float bet
 
 int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, int32_t n_groups, const int32_t* rule, const float* hyper) {
     if (!h) return EH_EINVAL;
+    if (h->ens_live) return fail(h, EH_ESTATE, "eh_opt_init_groups: the handle carries an ensemble (eh_ens_destroy it first)");
     if (!group || !rule || !hyper) return fail(h, EH_EINVAL, "eh_opt_init_groups: null table");
     if (n_theta != h->net.n_theta) return fail(h, EH_EINVAL, "eh_opt_init_groups: n_theta %lld, the model has %d", (long long)n_theta, h->net.n_theta);
     if (n_groups > EH_MAX_OPT_GROUPS) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_groups: %d groups (at most %d)", n_groups, EH_MAX_OPT_GROUPS);
@@ -2052,6 +2137,7 @@ int32_t eh_opt_init_groups(eh_handle* h, const uint8_t* group, int64_t n_theta, 
 
 int32_t eh_opt_init_chain(eh_handle* h, const eh_opt_stage* stages, int32_t n_stages, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay) {
     if (!h || !stages) return EH_EINVAL;
+    if (h->ens_live) return fail(h, EH_ESTATE, "eh_opt_init_chain: the handle carries an ensemble (eh_ens_destroy it first)");
     if (n_stages < 1) return fail(h, EH_EINVAL, "eh_opt_init_chain: %d stages", n_stages);
     if (n_stages > EH_MAX_OPT_STAGES) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: %d stages (at most %d, nested chains flattened)", n_stages, EH_MAX_OPT_STAGES);
     if (rule < EH_OPT_ADAM || rule > EH_OPT_DESCENT) return fail(h, EH_EUNSUPPORTED, "eh_opt_init_chain: unknown rule %d", rule);
@@ -2294,6 +2380,7 @@ int32_t eh_graph_begin(eh_handle* h) {
     if (h->drop_on) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: dropout: every step carries its own step count in its arguments, a recorded graph would replay one mask: not built");
     if (h->lb && h->lb->active) return fail(h, EH_EUNSUPPORTED, "eh_graph_begin: the handle is in L-BFGS mode (capture is not built for it): eh_opt_init* leaves the mode");
     if (h->capturing) return fail(h, EH_ESTATE, "eh_graph_begin: already capturing");
+    if (h->ens_live) return fail(h, EH_ESTATE, "eh_graph_begin: the handle carries an ensemble, whose launches read records that change with every epoch (eh_ens_destroy it first)");
     // a fused-mode step applies the update of the step before it: the recorded sequence has to start (and every replay
     // has to find the engine) with such an update pending, or its first kernel would skip / re-apply one
     if (h->fused && !h->pending) return fail(h, EH_ESTATE, "eh_graph_begin: fused_update mode: run one training step first (and do not synchronize before capturing)");

@@ -34,6 +34,11 @@ struct Var {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(&eh_step_kernel<EH_NBI, EH_NBH, EH_NL, NT, NW, ACT, EH_MODE_TRAIN_MULTI, FAST>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)EH_LDS_LIMIT);
     }
+    template <int ACT, int FAST>
+    static hipError_t prepe() {           // ... and so does the ensemble launch, a multi-step launch per member (eh_ens.hpp)
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&eh_ens_kernel<EH_NBI, EH_NBH, EH_NL, NT, NW, ACT, FAST>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)EH_LDS_LIMIT);
+    }
     template <int ACT>
     static hipError_t prep2() {
         hipError_t e = prep1<ACT, EH_MODE_TRAIN, 0>();
@@ -41,13 +46,16 @@ struct Var {
         if constexpr (HASP2P) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_P2P, 0>(); }
         if constexpr (HASP2P) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_ORD, 0>(); }
         if (e == hipSuccess) e = prepm<ACT, 0>();                     // several steps of one workgroup per launch (small minibatches)
+        if (e == hipSuccess) e = prepe<ACT, 0>();
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN, 4>();      // EH_MECH_PROGRAM kernels (no cross-GPU variant)
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_EVAL, 4>();
 #ifdef EH_FAST_PATHS
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN, 1>();
         if (e == hipSuccess) e = prepm<ACT, 1>();
+        if (e == hipSuccess) e = prepe<ACT, 1>();
         if constexpr (HASPS) { if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN, 3>(); }
         if constexpr (HASPS) { if (e == hipSuccess) e = prepm<ACT, 3>(); }
+        if constexpr (HASPS) { if (e == hipSuccess) e = prepe<ACT, 3>(); }
         if (e == hipSuccess) e = prep1<ACT, EH_MODE_EVAL, 1>();
         if constexpr (HASP2P) {
             if (e == hipSuccess) e = prep1<ACT, EH_MODE_TRAIN_P2P, 1>();
@@ -127,7 +135,31 @@ struct Var {
         }
         return hipGetLastError();
     }
-    static constexpr EhVariant info() { return EhVariant{NT, NW, LDS, NW * Geom::WAVE_WS, &prepare, &launch, 0, 0, 0, LDS_EVAL}; }
+    template <int ACT>
+    static void go_ens(int fast, int members, size_t lds_ms, hipStream_t stream, const EhNet* net, const EhStepArgs* args, const EhEnsMember* mem) {
+#define EH_GOE(FAST) hipLaunchKernelGGL((eh_ens_kernel<EH_NBI, EH_NBH, EH_NL, NT, NW, ACT, FAST>), dim3(1, members), dim3(64 * NW), lds_ms, stream, *net, *args, mem)
+#ifdef EH_FAST_PATHS
+        if constexpr (HASPS) { if (fast == 3) { EH_GOE(3); return; } }
+        if (fast & 1) { EH_GOE(1); return; }
+#endif
+        EH_GOE(0);
+#undef EH_GOE
+    }
+    static hipError_t launch_ens(int act, int fast, int members, hipStream_t stream, const EhNet* net, const EhStepArgs* args, const EhEnsMember* mem) {
+        const size_t lds_ms = LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, false);
+        if ((fast & 4) || (fast == 3 && !HASPS)) return hipErrorNotSupported;
+        if (members < 1 || members > 65535 || !mem || args->fz.opt.tab || lds_ms > EH_LDS_LIMIT) return hipErrorInvalidValue;
+        switch (act) {
+            case EH_ACT_TANH: go_ens<EH_ACT_TANH>(fast, members, lds_ms, stream, net, args, mem); break;
+            case EH_ACT_SIGMOID: go_ens<EH_ACT_SIGMOID>(fast, members, lds_ms, stream, net, args, mem); break;
+            case EH_ACT_RELU: go_ens<EH_ACT_RELU>(fast, members, lds_ms, stream, net, args, mem); break;
+            case EH_ACT_SWISH: go_ens<EH_ACT_SWISH>(fast, members, lds_ms, stream, net, args, mem); break;
+            case EH_ACT_IDENTITY: go_ens<EH_ACT_IDENTITY>(fast, members, lds_ms, stream, net, args, mem); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    static constexpr EhVariant info() { return EhVariant{NT, NW, LDS, NW * Geom::WAVE_WS, &prepare, &launch, 0, 0, 0, LDS_EVAL, &launch_ens}; }
 };
 
 using G0 = EhGeom<EH_NBI, EH_NBH, EH_NL, NT0, 4>;

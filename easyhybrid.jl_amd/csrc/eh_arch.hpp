@@ -8,6 +8,7 @@
 // image fits the 160 KiB of a gfx950 CU with a 4-wave workgroup).
 #pragma once
 #include "eh_device.hpp"
+#include "eh_ens.hpp"
 
 struct EhVariant {
     int nt, nw;
@@ -22,6 +23,8 @@ struct EhVariant {
     int so;                  // != 0: the TRAIN kernel is the sample-owned eh_bfs_kernel (eh_bf16_sample.hpp; one-network models only, 16 * nw-sample
                              // tiles: nt == nw); evaluation passes run eh_widebf_kernel with so x 16-sample tiles.  What "precision" selects.
     size_t lds_eval;         // != 0: dynamic LDS of the variant's forward / evaluation kernels (per-wave family: no hidden images); 0 = lds_bytes
+    // the ensemble launch (eh_ens.hpp): `members` workgroups, each the multi-step launch of its own record; nullptr: not built for the family
+    hipError_t (*launch_ens)(int act, int fast, int members, hipStream_t stream, const EhNet* net, const EhStepArgs* args, const EhEnsMember* mem);
 };
 
 struct EhArchInfo {
@@ -48,6 +51,7 @@ struct EhSpecKernel {
     // inside its contract only
     hipError_t (*launch)(int mode, int grid, hipStream_t stream, const EhNet* net, const EhStepArgs* args, bool lean);
     bool has_lean;
+    hipError_t (*launch_ens)(int members, hipStream_t stream, const EhNet* net, const EhStepArgs* args, const EhEnsMember* mem);      // nullptr: the unit holds no multi-step kernel
 };
 #define EH_SPEC_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)
 #define EH_SPEC_DECL(k) extern "C" const EhSpecKernel* eh_spec_##k(void);

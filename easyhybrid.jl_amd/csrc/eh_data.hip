@@ -47,6 +47,7 @@ extern "C" {
 int32_t eh_set_data(eh_handle* h, int32_t split, int64_t n, const float* x, const float* const* forcings, const float* const* targets,
                     int32_t on_device) {
     if (!h) return EH_EINVAL;
+    if (h->ens_live) return fail(h, EH_ESTATE, "eh_set_data: the handle carries an ensemble, whose row lists index this table (eh_ens_destroy it first)");
     if (split != EH_SPLIT_TRAIN && split != EH_SPLIT_VAL) return fail(h, EH_EINVAL, "eh_set_data: split %d", split);
     if (n < 0 || n > 0x7fffffffLL) return fail(h, EH_EINVAL, "eh_set_data: n = %lld", (long long)n);
     if (on_device & ~(EH_DATA_ON_DEVICE | EH_DATA_X_PLANES | EH_DATA_X_ROWS)) return fail(h, EH_EINVAL, "eh_set_data: flags %d", on_device);

@@ -9,6 +9,7 @@
 //   eh_lbfgs.hip  L-BFGS (eh_lbfgs.hpp)
 //   eh_mech.hip   the stand-alone mechanistic stage, eh_mech_loss_vjp
 //   eh_seq.hip    the sequence-model kernels (eh_seq.hpp)
+//   eh_ens.hip    ensembles: M models of one handle's architecture trained by one launch, a workgroup each (eh_ens.hpp)
 //   eh_comm.hip   the library's own collectives -- RCCL binding, local groups, the peer-to-peer exchange
 // Not installed; the public ABI is include/easyhybrid_hip.h.
 #pragma once
@@ -211,6 +212,7 @@ struct eh_handle_s {
     bool bn_ext = false;            // bn_stat holds the statistics of the step about to run
     bool bn_dp_update = false;
     bool opt_ready = false;
+    int ens_live = 0;               // ensembles hanging off the handle (eh_ens.hip): while there is one, its data, options and optimiser stay as they are
     // sequence models (eh_seq.hpp): Dense-in -> LSTM -> head Dense -> output Dense over windows (EH_LAYER_LSTM); always the step + reduce pair
     bool seq = false;
     float* seq_ws = nullptr;         // what the backward needs of every step, per wave of the grid (allocated outside graph capture)
@@ -359,6 +361,17 @@ int eh_launch_moment_coef(eh_handle* h, const EhSplit& sp, const float* rows, in
 // eh_lform.hip: one training step's gradient sums into *rows partial slab rows | forward + metric sums of a window, *rows rows of them in the slab
 int eh_lform_train(eh_handle* h, const EhSplit& sp, const int* idx, long long first, long long count, int* rows, bool bn_update);
 int eh_lform_eval(eh_handle* h, const EhSplit& sp, long long first, long long count, float* yhat, float* pout, int* rows);
+
+// eh_api.hip, for eh_ens.hip: the reasons a handle cannot carry an ensemble at a batch size (empty: it can), the ensemble launch, an
+// evaluation pass on arguments of the caller's making, theta -> a parameter image elsewhere, the epoch orders, sums -> metrics
+std::string eh_ens_refusal(eh_handle* h, long long batch);
+int eh_ens_launch_train(eh_handle* h, int members, const EhStepArgs* a, const EhEnsMember* mem);
+int eh_ens_launch_eval(eh_handle* h, const EhStepArgs* a, int grid);
+int eh_ens_eval_grid(const eh_handle* h, long long count);
+int eh_ens_launch_image(eh_handle* h, const float* theta, float* image);
+int eh_ens_launch_order(eh_handle* h, const EhEnsOrder* ord, int members, long long max_n);
+void eh_opt_changed(eh_handle* h);
+void eh_metrics_from_sums(const double* st, const float* shift, int T, eh_target_metrics* out);
 
 // eh_lbfgs.hip: eh_destroy's share
 void eh_lbfgs_release(eh_handle* h);

@@ -623,6 +623,15 @@ __global__ void eh_perm_kernel(int* idx, uint32_t n, int hb, uint64_t seed) {
     if (i < n) idx[i] = (int)eh_perm32(i, n, hb, seed);
 }
 
+// eh_ens_train_epoch: the same permutation for every member of an ensemble (blockIdx.y), composed with the member's row list
+__global__ __launch_bounds__(256) void eh_ens_order_kernel(const EhEnsOrder* __restrict__ ord) {
+    const EhEnsOrder o = ord[blockIdx.y];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= o.n) return;
+    const uint32_t p = eh_perm32(i, o.n, o.hb, o.seed);
+    o.out[i] = o.rows ? o.rows[p] : (int)p;
+}
+
 // eh_dropout_mask: keep[k][u] of (seed, step, layer) for k < count, u < width -- one thread per (sample, unit quad), through the keep
 // function the step kernels call (eh_drop_keep4) with LOGICAL coordinates: what the tests hold the step kernel's lane mapping against
 __global__ __launch_bounds__(256) void eh_dropout_mask_kernel(unsigned long long seed, unsigned long long step, int layer, int width, long long count, unsigned thr, uint8_t* keep) {

@@ -48,6 +48,7 @@ using Geom = EhGeom<NBI, NBH, NL, NT, NW>;
 constexpr bool HASP2P = (FAST & 4) == 0;
 constexpr bool HASMULTI = (FAST & 4) == 0 && EhNet{EH_SPEC_NET}.T == 1;
 constexpr bool HASORD = HASMULTI;      // (the ordered fused-update step: one target, no program)
+#define EH_SPEC_ENS_KERNEL eh_ens_kernel<NBI, NBH, NL, NT, NW, ACT, FAST>      // the ensemble launch (eh_ens.hpp), where the unit holds the multi-step kernel
 // -DEH_SPEC_LEAN (the headline descriptors): the lean form of the single-step train kernels as well (eh_lean_fold, eh_device.hpp)
 #ifdef EH_SPEC_LEAN
 #define EH_SPEC_KERNEL_LEAN(MODE) eh_step_kernel<NBI, NBH, NL, NT, NW, ACT, MODE, (FAST | EH_FAST_LEAN)>
@@ -69,6 +70,7 @@ hipError_t prepare() {
     if constexpr (HASP2P) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL(EH_MODE_TRAIN_P2P)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); }
     if constexpr (HASORD) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL(EH_MODE_TRAIN_ORD)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); }
     if constexpr (HASMULTI) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL(EH_MODE_TRAIN_MULTI)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EH_LDS_LIMIT); }
+    if constexpr (HASMULTI) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_ENS_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EH_LDS_LIMIT); }
 #ifdef EH_SPEC_LEAN
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&EH_SPEC_KERNEL_LEAN(EH_MODE_TRAIN_ORD)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
@@ -105,6 +107,20 @@ hipError_t launch(int mode, int grid, hipStream_t stream, const EhNet* net, cons
     else return hipErrorNotSupported;
     return hipGetLastError();
 }
+#if EH_SPEC_FAMILY == 0
+hipError_t launch_ens(int members, hipStream_t stream, const EhNet* net, const EhStepArgs* args, const EhEnsMember* mem) {
+    if constexpr (HASMULTI) {
+        const size_t lds_ms = LDS + sizeof(float) * (size_t)eh_ms_extra_floats(net->n_theta, args->n_acc, false);
+        if (members < 1 || members > 65535 || !mem || args->fz.opt.tab || lds_ms > EH_LDS_LIMIT) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((EH_SPEC_ENS_KERNEL), dim3(1, members), dim3(64 * NW), lds_ms, stream, *net, *args, mem);
+        return hipGetLastError();
+    }
+    return hipErrorNotSupported;
+}
+constexpr auto LAUNCH_ENS = HASMULTI ? &launch_ens : nullptr;
+#else
+constexpr decltype(EhSpecKernel::launch_ens) LAUNCH_ENS = nullptr;
+#endif
 #ifdef EH_SPEC_LEAN
 constexpr bool HAS_LEAN = true;
 #else
@@ -113,7 +129,7 @@ constexpr bool HAS_LEAN = false;
 #define EH_STR_(x) #x
 #define EH_STR(x) EH_STR_(x)
 const EhSpecKernel spec = {EhNet{EH_SPEC_NET}, EH_SPEC_FAMILY != 0, EH_SPEC_FAMILY >= 2 ? (EH_SPEC_NSPLIT == 3 ? 1 : 2) : 0, NBI, NBH, NL, NT, NW, ACT, FAST, EH_SPEC_FAMILY == 3 ? 1 : 0, LDS,
-                           "descriptor " EH_STR(EH_SPEC_ID) " of csrc/Makefile, specialised ahead of time", &prepare, &launch, HAS_LEAN};
+                           "descriptor " EH_STR(EH_SPEC_ID) " of csrc/Makefile, specialised ahead of time", &prepare, &launch, HAS_LEAN, LAUNCH_ENS};
 }   // namespace
 
 #define EH_CAT_(a) eh_spec_##a

@@ -119,7 +119,15 @@ class HybridEngine:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.eh_destroy(self._h)
+            for ens in list(getattr(self, "_ensembles", ())):      # (the library refuses to destroy a handle that still carries one)
+                ens.close()
+            # (the pointer leaves the object BEFORE anything that can raise: a close() that failed half way -- at interpreter shutdown the
+            #  module's names may be gone -- must not leave a freed handle behind for the finaliser's second close())
+            h, self._h = self._h, None
+            st = self._lib.eh_destroy(h)
+            if st != 0:                                            # refused (EH_ESTATE): the handle lives on and stays reachable
+                self._h = h
+                _raise(st, self._lib.eh_last_error(h).decode())
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -571,6 +579,16 @@ class HybridEngine:
         self._chk(self._lib.eh_train_step(self._h, ip, on_dev, first, count, C.byref(loss) if want_loss else None))
         return float(loss.value) if want_loss else None
 
+    def ensemble(self, members: int, batchsize: int) -> "Ensemble":
+        """`members` models of this engine's architecture over its TRAIN table, all trained by the same launches (Ensemble)"""
+        ens = Ensemble(self, members, batchsize)
+        # (strong references, dropped by Ensemble.close: weak ones are cleared before finalisers run when a cycle is collected or the
+        #  interpreter shuts down, and the engine could then not close its ensembles ahead of itself)
+        if not hasattr(self, "_ensembles"):
+            self._ensembles = []
+        self._ensembles.append(ens)
+        return ens
+
     # -- hipGraph capture of a step sequence (see include/easyhybrid_hip.h) --------------------------
     def graph_begin(self):
         self._chk(self._lib.eh_graph_begin(self._h))
@@ -800,3 +818,114 @@ class HybridEngine:
         n = C.c_int64(); a = C.c_double(); b = C.c_double()
         self._chk(self._lib.eh_profile_read(self._h, C.byref(n), C.byref(a), C.byref(b)))
         return int(n.value), float(a.value), float(b.value)
+
+
+class Ensemble:
+    """M models of one engine's architecture -- cross-validation folds, the points of a sweep over optimiser settings, repeated seeds --
+    trained side by side: one launch runs a chunk of every member's epoch, a workgroup per member (eh_ens_*).  The
+    members share the engine's descriptor, kernels and TRAIN table and differ in theta, in the rows they see (set_rows) and in the
+    optimiser's numbers (set_opt); each computes, bit for bit, what an engine of its own would.  While an ensemble is open the engine's
+    data, options and optimiser stay as they are; close() the ensemble before the engine."""
+
+    def __init__(self, engine: HybridEngine, members: int, batchsize: int):
+        self.engine, self._lib, self._e = engine, engine._lib, C.c_void_p()
+        self.members, self.batchsize = int(members), int(batchsize)
+        engine._chk(self._lib.eh_ens_create(engine._h, self.members, self.batchsize, C.byref(self._e)))
+
+    def _chk(self, st: int):
+        self.engine._chk(st)
+
+    def close(self):
+        if getattr(self, "_e", None) is not None and self._e.value:
+            self._lib.eh_ens_destroy(self._e)
+            self._e = C.c_void_p()
+            held = getattr(self.engine, "_ensembles", None)
+            if held is not None and self in held:
+                held.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_params(self, j: int, theta):
+        theta = np.ascontiguousarray(theta, np.float32)
+        self._chk(self._lib.eh_ens_set_params(self._e, j, _fptr(theta), theta.size))
+
+    def get_params(self, j: int) -> np.ndarray:
+        out = np.empty(self.engine.n_theta, np.float32)
+        self._chk(self._lib.eh_ens_get_params(self._e, j, _fptr(out), out.size))
+        return out
+
+    def set_opt(self, j: int, rule: str = "Adam", lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0):
+        """member j's rule and numbers (HybridEngine.opt_init's arguments); a fresh optimiser state"""
+        if rule not in L.OPT_RULES:
+            raise NotImplementedError(f"optimiser rule {rule} is not implemented on the device")
+        self._chk(self._lib.eh_ens_set_opt(self._e, j, L.OPT_RULES[rule], lr, beta1, beta2, eps, weight_decay))
+
+    def get_opt_state(self, j: int):
+        """(m, v, bt) of member j, as HybridEngine.get_opt_state"""
+        m = np.empty(self.engine.n_theta, np.float32); v = np.empty(self.engine.n_theta, np.float32); bt = np.empty(2, np.float32)
+        self._chk(self._lib.eh_ens_get_opt_state(self._e, j, _fptr(m), _fptr(v), m.size, _fptr(bt)))
+        return m, v, bt
+
+    def set_opt_state(self, j: int, m, v, bt):
+        m = np.ascontiguousarray(m, np.float32); v = np.ascontiguousarray(v, np.float32); bt = np.ascontiguousarray(bt, np.float32)
+        self._chk(self._lib.eh_ens_set_opt_state(self._e, j, _fptr(m), _fptr(v), m.size, _fptr(bt)))
+
+    def get_bn_state(self, j: int):
+        P = self.engine.desc.n_predictors
+        m = np.empty(P, np.float32); v = np.empty(P, np.float32)
+        self._chk(self._lib.eh_ens_get_bn_state(self._e, j, _fptr(m), _fptr(v), P))
+        return m, v
+
+    def set_bn_state(self, j: int, mean, var):
+        m = np.ascontiguousarray(mean, np.float32); v = np.ascontiguousarray(var, np.float32)
+        self._chk(self._lib.eh_ens_set_bn_state(self._e, j, _fptr(m), _fptr(v), m.size))
+
+    def set_rows(self, j: int, which: int, rows):
+        """which = 0: the rows of the engine's TRAIN table member j trains on, 1: the rows it is evaluated on; None: all of them"""
+        if rows is None:
+            self._chk(self._lib.eh_ens_set_rows(self._e, j, which, None, 0))
+            return
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        buf = rows if rows.size else np.zeros(1, np.int32)          # (no rows at all: a list of length 0, not "all of them")
+        self._chk(self._lib.eh_ens_set_rows(self._e, j, which, buf.ctypes.data_as(C.POINTER(C.c_int32)), rows.size))
+
+    def train_epoch(self, seeds=None, shuffle: bool = True, active=None, want_loss: bool = True):
+        """one epoch of every active member -> (mean losses (M,) or None, steps (M,)); seeds: one per member (None: 0)"""
+        M = self.members
+        sd = None if seeds is None else np.array([int(x) & (2**64 - 1) for x in seeds], np.uint64)
+        ac = None if active is None else np.ascontiguousarray(active, np.uint8)
+        if (sd is not None and sd.shape != (M,)) or (ac is not None and ac.shape != (M,)):
+            raise ValueError("seeds / active: one entry per member")
+        loss = np.empty(M, np.float32) if want_loss else None
+        ns = np.empty(M, np.int64)
+        self._chk(self._lib.eh_ens_train_epoch(self._e, sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, int(shuffle),
+                                               ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, _fptr(loss),
+                                               ns.ctypes.data_as(C.POINTER(C.c_int64))))
+        return loss, ns
+
+    def eval(self, which: int = 1):
+        """metrics[j][t]: every member over its `which` rows (0: training, 1: evaluation), as HybridEngine.eval's dicts"""
+        T = self.engine.n_targets_total
+        m = (L.TargetMetrics * (self.members * T))()
+        self._chk(self._lib.eh_ens_eval(self._e, which, m))
+        return [[{f: getattr(m[j * T + t], f) for f, _ in L.TargetMetrics._fields_} for t in range(len(self.engine.target_names))] for j in range(self.members)]
+
+    def load(self, j: int):
+        """member j's whole state into the engine: forward, eval, get_opt_state, train_step ... then serve the member"""
+        self._chk(self._lib.eh_ens_load(self._e, j))
+        self.engine._opt_groups = 1
+        self.engine._chain = None
+
+    def store(self, j: int):
+        """the engine's state into member j"""
+        self._chk(self._lib.eh_ens_store(self._e, j))

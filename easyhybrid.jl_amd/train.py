@@ -687,17 +687,9 @@ def _sequence_splits(model, data, cfg: DataConfig, rng: Optional[np.random.Gener
     return ((X, forc), targ), pick(idx[:k]), pick(idx[k:])
 
 
-def split_data(data, model, cfg: DataConfig = DataConfig(), rng: Optional[np.random.Generator] = None, sequence_kwargs: Optional[dict] = None):
-    """split_data.jl:8-79 -> (train, val) each ((X, forcings), targets).  With sequence_kwargs (or a model with an LSTM layer): each
-    ((X, forcings), targets, windows) -- the whole series and the split's windows (sequences.Sequences)."""
-    if sequence_kwargs is not None or cfg.sequence_kwargs is not None or getattr(model, "lstm_layer", None) is not None:
-        if sequence_kwargs is not None:
-            cfg = copy.copy(cfg); cfg.sequence_kwargs = sequence_kwargs
-        series, wtr, wva = _sequence_splits(model, data, cfg, rng)
-        return (series[0], series[1], wtr), (series[0], series[1], wva)
-    raw_cols = _columns(data) if not isinstance(data, tuple) else None
-    (X, forc), targ = prepare_data(model, data)
-    n = X.shape[1]
+def _split_rows(cfg: DataConfig, n: int, raw_cols, rng: Optional[np.random.Generator] = None):
+    """which of the n screened rows (prepare_data) train and which validate, each an index array or a slice: split_data.jl:8-79.  One
+    copy of the rules for split_data and for train_members, which hands the rows to the device as lists instead of gathering them."""
     if cfg.split_by_id is not None and cfg.folds is not None:
         raise ValueError("split_by_id and folds are not supported together; do the split when constructing folds")
     if cfg.split_by_id is not None:
@@ -726,6 +718,20 @@ def split_data(data, model, cfg: DataConfig = DataConfig(), rng: Optional[np.ran
             tr, va = idx[:k], idx[k:]
         else:
             tr, va = slice(0, k), slice(k, n)                           # contiguous halves: views, no gather
+    return tr, va
+
+
+def split_data(data, model, cfg: DataConfig = DataConfig(), rng: Optional[np.random.Generator] = None, sequence_kwargs: Optional[dict] = None):
+    """split_data.jl:8-79 -> (train, val) each ((X, forcings), targets).  With sequence_kwargs (or a model with an LSTM layer): each
+    ((X, forcings), targets, windows) -- the whole series and the split's windows (sequences.Sequences)."""
+    if sequence_kwargs is not None or cfg.sequence_kwargs is not None or getattr(model, "lstm_layer", None) is not None:
+        if sequence_kwargs is not None:
+            cfg = copy.copy(cfg); cfg.sequence_kwargs = sequence_kwargs
+        series, wtr, wva = _sequence_splits(model, data, cfg, rng)
+        return (series[0], series[1], wtr), (series[0], series[1], wva)
+    raw_cols = _columns(data) if not isinstance(data, tuple) else None
+    (X, forc), targ = prepare_data(model, data)
+    tr, va = _split_rows(cfg, X.shape[1], raw_cols, rng)
 
     def take(ix):
         return (np.ascontiguousarray(X[:, ix]), {k: v[ix] for k, v in forc.items()}), {k: v[ix] for k, v in targ.items()}
@@ -839,8 +845,14 @@ class TrainResults:                                                # TrainingCon
 def _losses(engine, split, targets, loss_types, agg="sum"):
     """(mse = (reco = .., sum = ..), r2 = (...)) as nested dicts, the aggregate under the name of `agg`; compute_loss.jl:55-66."""
     if engine.n_samples[split] == 0:
+        return _losses_of(None, targets, loss_types, agg)
+    return _losses_of(engine.eval(split)[0], targets, loss_types, agg)
+
+
+def _losses_of(metrics, targets, loss_types, agg="sum"):
+    """the same from one model's evaluated metrics (a list of dicts, one per target); None: nothing was evaluated (an empty split)"""
+    if metrics is None:
         return {lt: {**{t: float("nan") for t in targets}, agg: float("nan")} for lt in loss_types}
-    metrics, _ = engine.eval(split)
     out = {}
     for lt in loss_types:
         per = {t: metrics[i][lt] for i, t in enumerate(targets)}
@@ -1309,3 +1321,231 @@ def train(model: SingleNNHybridModel, data, save_ps=(), *, train_cfg: Optional[T
         if own and not keep_engine:
             eng.close()
         _freeze_gc_once(at_end=True)
+
+
+# ---------------------------------------------------------------------------------------------
+# groups of models trained side by side: cross-validation folds, sweeps over optimiser numbers, repeated seeds
+# ---------------------------------------------------------------------------------------------
+
+_MEMBER_KEYS = ("val_fold", "random_seed", "opt")
+
+
+def _member_configs(tc: TrainConfig, dc: DataConfig, members):
+    """the member dicts -> [(TrainConfig, DataConfig)], one pair per member: the common configuration with the member's overrides"""
+    if not isinstance(members, (list, tuple)) or not members:
+        raise ValueError("train_members: members must be a non-empty list of dicts")
+    out = []
+    for j, m in enumerate(members):
+        if not isinstance(m, dict):
+            raise ValueError(f"train_members: member {j} is {type(m).__name__}, not a dict")
+        extra = [k for k in m if k not in _MEMBER_KEYS]
+        if extra:
+            raise ValueError(f"train_members: member {j} has unknown key(s) {extra}; a member may override {list(_MEMBER_KEYS)}, everything else is common")
+        tcj, dcj = copy.copy(tc), copy.copy(dc)
+        if "random_seed" in m:
+            tcj.random_seed = m["random_seed"]
+        if "opt" in m:
+            tcj.opt = m["opt"]
+        if "val_fold" in m:
+            dcj.val_fold = m["val_fold"]
+        out.append((tcj, dcj))
+    kinds = {type(c.opt).__name__ for c, _ in out if isinstance(c.opt, _RULES)}
+    if len(kinds) > 1:
+        raise ValueError(f"train_members: the members mix optimiser rules {sorted(kinds)}: one rule type for all, its numbers are free per member")
+    return out
+
+
+def _per_net(model) -> bool:
+    """the descriptor asks for an activation per network / per layer (EH_ACT_PER_NET)"""
+    try:
+        return int(model.to_desc().activation) == L.EH_ACT_PER_NET
+    except Exception:
+        return False
+
+
+def _members_refusals(model, tc: TrainConfig, dc: DataConfig, cfgs):
+    """what train_members does not run, each with its reason, before anything is uploaded or trained"""
+    who = "train_members"
+    if tc.distributed is True or _want_distributed(tc):
+        raise NotImplementedError(f"{who}: distributed training (data parallelism) is not built for groups of models: the members already fill the device, a workgroup each")
+    for c, _ in cfgs:
+        if isinstance(c.opt, LBFGS):
+            raise NotImplementedError(f"{who}: LBFGS (the Optimization.jl driver, a line search per model) is not built for groups of models")
+        if isinstance(c.opt, OptimiserChain):
+            raise NotImplementedError(f"{who}: an OptimiserChain (ClipNorm needs the norm of the whole gradient ahead of the update) is not built for groups of models")
+        if isinstance(c.opt, dict) or (isinstance(c.opt, tuple) and hasattr(c.opt, "_asdict")):
+            raise NotImplementedError(f"{who}: a per-branch opt (a rule per branch of the parameter tree) is not built for groups of models: one rule per member")
+        if not isinstance(c.opt, _RULES):
+            _opt_args(c.opt)                         # (raises with the reason)
+    if getattr(model, "lstm_layer", None) is not None or dc.sequence_kwargs is not None:
+        raise NotImplementedError(f"{who}: sequence models (Recurrence layers, windows) are not built for groups of models")
+    if tc.extra_loss is not None:
+        raise NotImplementedError(f"{who}: an extra_loss runs on the step + reduce pair, not in the one-workgroup step a member trains with")
+    from .engine import PerTarget
+    tl = tc.training_loss
+    if callable(tl) or isinstance(tl, PerTarget) or isinstance(tl, (list, tuple)):
+        raise NotImplementedError(f"{who}: recorded losses (a function as training_loss), per-target losses and closures run on kernels compiled at run time, "
+                                  "which a group of models does not use")
+    if getattr(getattr(model, "mechanistic_model", None), "fn", None) is not None:
+        raise NotImplementedError(f"{who}: a recorded mechanistic closure runs on kernels compiled at run time, which a group of models does not use")
+    if isinstance(tl, str) and tl in ("pearsonLoss", "kgeLoss", "pbkgeLoss"):
+        raise NotImplementedError(f"{who}: the two-pass losses (pearsonLoss, kgeLoss, pbkgeLoss) take two forward passes for the batch moments ahead of every "
+                                  "step, which the one-workgroup step a member trains with does not run")
+    if model.config.get("precision", "f32") != "f32":
+        raise NotImplementedError(f"{who}: precision={model.config.get('precision')!r} runs on the row-split bf16 kernels, whose step needs several workgroups")
+    if len(model.targets) != 1:
+        raise NotImplementedError(f"{who}: several targets need a counting pass ahead of every step: not built for groups of models")
+    if getattr(model, "dropout", None) is not None:
+        raise NotImplementedError(f"{who}: Dropout layers run on a step kernel compiled at run time, which a group of models does not use")
+    if getattr(model, "bn_layers", None) or getattr(model, "ln_layers", None):
+        raise NotImplementedError(f"{who}: BatchNorm / LayerNorm layers inside hidden_layers run in the layer-wise form, not in the one-workgroup step")
+    if _per_net(model):
+        raise NotImplementedError(f"{who}: per-net or per-layer activations run on kernels compiled at run time, which a group of models does not use")
+    if tc.specialize is True:
+        raise NotImplementedError(f"{who}: specialize=True asks for kernels compiled at run time; a group of models runs the kernels built ahead of time "
+                                  "('auto' and False)")
+    if tc.fused_update is False:
+        raise NotImplementedError(f"{who}: fused_update=False asks for the step + reduce pair; a member trains with the one-workgroup multi-step launch")
+    if tc.train_from is not None:
+        raise NotImplementedError(f"{who}: train_from is not built for groups of models (every member starts from the parameters its seed draws)")
+
+
+def _member_rows(model, data, dc: DataConfig, rng, n: Optional[int] = None, raw_cols=None):
+    """one member's share of the screened table: (training rows, validation rows) as int32 index arrays, in the order split_data takes them.
+    n, raw_cols: the screened table's rows and the caller's columns where the caller has them already (train_members screens once)"""
+    if n is None:
+        raw_cols = _columns(data) if not isinstance(data, tuple) else None
+        n = prepare_data(model, data)[0][0].shape[1]
+    tr, va = _split_rows(dc, n, raw_cols, rng)
+    ix = np.arange(n, dtype=np.int32)
+    return ix[tr], ix[va]
+
+
+def train_members(model: SingleNNHybridModel, data, members, *, train_cfg: Optional[TrainConfig] = None, data_cfg: Optional[DataConfig] = None,
+                  **kwargs) -> List[Optional[TrainResults]]:
+    """Several train(model, data; ...) runs that share the model and the table, side by side on one engine: members = [{...}, ...], each
+    dict overriding `val_fold`, `random_seed` and / or `opt` (one rule type for all, numbers free) of the common configuration.  Member j's
+    data split and initial parameters are those of train(model, data, **common, **members[j]); the table is uploaded once and a fold
+    becomes two row lists; every epoch of all members is one launch (a workgroup per member), every evaluation one synchronisation.
+    Early stopping, the best-model snapshot and the histories follow train() per member; a stopped member sits out the later launches.
+    Returns one TrainResults per member (None where train() would return None: an empty training split), predictions computed eagerly.
+    Runs where one workgroup covers a minibatch of a one-target model on the kernels built ahead of time; everything else is refused
+    with its reason before any training."""
+    tc = copy.copy(train_cfg) if train_cfg else TrainConfig()
+    dc = copy.copy(data_cfg) if data_cfg else DataConfig()
+    for k, v in kwargs.items():
+        if hasattr(tc, k):
+            setattr(tc, k, v)
+        elif hasattr(dc, k):
+            setattr(dc, k, v)
+        else:
+            raise TypeError(f"train_members: unknown keyword {k!r}")
+    cfgs = _member_configs(tc, dc, members)
+    for c, _ in cfgs:
+        validate_config(c)
+    _members_refusals(model, tc, dc, cfgs)
+    if tc.predictions not in ("lazy", "eager"):
+        raise ValueError("predictions must be 'lazy' or 'eager'")
+    M = len(cfgs)
+    (X, forc), targ = prepare_data(model, data)
+    raw_cols = _columns(data) if not isinstance(data, tuple) else None
+    if X.shape[1] == 0:
+        return [None] * M
+    # per member, train()'s own order of draws: the split (shuffleobs), then theta_0, then the epoch seeds
+    rows, theta0, seed0 = [], [], []
+    for tcj, dcj in cfgs:
+        rng = np.random.default_rng(tcj.random_seed)
+        rows.append(_member_rows(model, data, dcj, rng, X.shape[1], raw_cols))
+        theta0.append(model.initialparameters(rng))
+        seed0.append(tcj.random_seed if tcj.random_seed is not None else int(rng.integers(2**31)))
+    live = [len(r[0]) > 0 for r in rows]
+    aggn = _agg_name(tc.agg)
+    first_lt = tc.loss_types[0]
+    has_bn = bool(model.config.get("input_batchnorm"))
+    eng = model.engine(tc.device)
+    ens = None
+    try:
+        eng.set_data(L.EH_SPLIT_TRAIN, X, [forc[f] for f in model.forcing], [targ[t] for t in model.targets])
+        eng.set_params(theta0[0])
+        eng.set_training_loss(tc.training_loss)
+        _apply_step_mode(eng, replace(tc, specialize=False))
+        ens = eng.ensemble(M, tc.batchsize)
+        for j, (tcj, _) in enumerate(cfgs):
+            ens.set_params(j, theta0[j])
+            ens.set_opt(j, **_opt_args(tcj.opt))
+            ens.set_rows(j, 0, rows[j][0])
+            ens.set_rows(j, 1, rows[j][1])
+
+        def snapshots():
+            mtr, mva = ens.eval(0), ens.eval(1)
+            return [EpochSnapshot(_losses_of(mtr[j] if len(rows[j][0]) else None, model.targets, tc.loss_types, aggn),
+                                  _losses_of(mva[j] if len(rows[j][1]) else None, model.targets, tc.loss_types, aggn)) for j in range(M)]
+        init = snapshots()
+        history = [[s] for s in init]
+        best_loss = [s.l_val[first_lt][aggn] for s in init]
+        best_ps = [t.copy() for t in theta0]
+        best_bn = [ens.get_bn_state(j) if has_bn else None for j in range(M)]
+        best_epoch, counter = [0] * M, [0] * M
+        active = list(live)
+        for epoch in range(1, tc.nepochs + 1):
+            if not any(active):
+                break
+            ens.train_epoch([s + epoch for s in seed0], shuffle=True, active=active, want_loss=False)      # run_epoch! of every member still training
+            snaps = snapshots()                                                                              # evaluate_epoch
+            for j in range(M):
+                if not active[j]:
+                    continue
+                snap = snaps[j]
+                if tc.keep_history:
+                    history[j].append(snap)
+                cur = snap.l_val[first_lt][aggn]
+                if isbetter(cur, best_loss[j], first_lt):                                                    # early_stopping.jl:16-42
+                    best_loss[j], best_ps[j], best_epoch[j], counter[j] = cur, ens.get_params(j), epoch, 0
+                    if has_bn:
+                        best_bn[j] = ens.get_bn_state(j)
+                    if not tc.keep_history:
+                        history[j][0] = snap
+                else:
+                    counter[j] += 1
+                if counter[j] >= tc.patience:
+                    active[j] = False
+        fixed = {f: np.float32(model.parameters.default(f)) for f in model.fixed_param_names}
+        results = []
+        for j in range(M):
+            if not live[j]:
+                results.append(None)                                                                          # train.jl:186
+                continue
+            ps = best_ps[j] if tc.return_model == "best" else ens.get_params(j)                               # best_or_final
+            bn_out = (best_bn[j] if tc.return_model == "best" else ens.get_bn_state(j)) if has_bn else None
+            ens.set_params(j, ps)
+            if has_bn:
+                ens.set_bn_state(j, *bn_out)
+            ens.load(j)                                   # the engine is member j: one forward pass over the table, the member's rows picked from it
+            o = eng.forward(L.EH_SPLIT_TRAIN)
+
+            def obs_pred(ix):
+                if len(ix) == 0:
+                    return {}, None
+                d = {t: targ[t][ix] for t in model.targets}
+                d.update({t + "_pred": o[t][ix] for t in model.targets})
+                return d, {k: v[ix] for k, v in o["parameters"].items()}
+            tr_op, tr_diff = obs_pred(rows[j][0])
+            va_op, va_diff = obs_pred(rows[j][1])
+            st = {"fixed": fixed}
+            if has_bn:
+                st["st_nn"] = {"running_mean": bn_out[0], "running_var": bn_out[1]}
+            h = history[j]
+            results.append(TrainResults([s.l_train for s in h], [s.l_val for s in h], h, tr_op, va_op, tr_diff, va_diff, ps, st, best_epoch[j], best_loss[j]))
+        return results
+    finally:
+        if ens is not None:
+            ens.close()
+        eng.close()
+
+
+def train_folds(model: SingleNNHybridModel, data, folds, **train_kwargs) -> List[Optional[TrainResults]]:
+    """k-fold cross-validation, the loop of docs/literate/tutorials/folds.jl in one call: one model per fold value v of `folds` (an array
+    with one entry per retained row, or a column name), validated on the rows with folds == v and trained on the rest, all side by side
+    (train_members).  Returns the results in the order of sorted(set(folds))."""
+    f = np.asarray(_columns(data)[folds] if isinstance(folds, str) else folds)
+    return train_members(model, data, [{"val_fold": v} for v in sorted(set(f.tolist()))], folds=folds, **train_kwargs)

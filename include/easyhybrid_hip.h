@@ -464,6 +464,45 @@ int32_t eh_graph_launch(eh_handle* h, int32_t graph_id);
 int32_t eh_eval(eh_handle* h, int32_t split, int64_t first, int64_t count, eh_target_metrics* out,
                 float* const* yhat, float* const* params);
 
+/* ---- ensembles: M models of one handle's architecture, trained by ONE launch with a workgroup per member ----------------------
+ * The folds of a cross-validation (docs/literate/tutorials/folds.jl), the points of a hyper-parameter sweep, repeated seeds: models
+ * that share the descriptor, the kernels and the resident table of a handle and differ in theta, in the rows they see and in the
+ * optimiser's numbers.  An ensemble hangs off an ordinary handle -- its descriptor, its TRAIN table (both row lists of a member index
+ * it: a fold model holds one table), its stream -- and every member computes, bit for bit, what a handle of its own would.
+ *   eh_ens_create       where the handle trains its epochs as multi-step launches at `batchsize` (one workgroup covers the minibatch,
+ *                       fused_update on, one target, a one-pass loss, no dropout / chain / recorded closure / data parallelism, kernels
+ *                       built ahead of time); otherwise EH_EUNSUPPORTED, eh_last_error(h) one sentence per cause.  Every member starts
+ *                       as a copy of the handle's state.  While an ensemble exists eh_set_data, eh_set_option, eh_opt_init*,
+ *                       eh_graph_begin and eh_destroy on the handle return EH_ESTATE; eh_ens_train_epoch and eh_ens_eval check the
+ *                       handle again on every call (EH_ESTATE + the causes, had another entry point moved it out of the above).
+ *   eh_ens_set_opt      one rule per member (a fresh optimiser state: zero moments, beta products at their start), before it trains
+ *   eh_ens_set_rows     which = 0: the rows the member trains on, 1: the rows it is evaluated on; int32 indices into the TRAIN table,
+ *                       range-checked; rows == NULL: all of them (the default); n == 0: none
+ *   eh_ens_train_epoch  member j walks rows_j o perm(n_j, seed[j]) (the permutation of eh_train_epoch; seed == NULL: 0 for all; shuffle
+ *                       == 0: rows_j as given) in minibatches of `batchsize`, all members in the same launches; active[j] == 0 (NULL: all
+ *                       active): the member sits the epoch out.  mean_loss[j] as eh_train_epoch's (NaN: no step, or none with a valid
+ *                       sample), n_steps[j]; both nullable; mean_loss == NULL: fully asynchronous.
+ *   eh_ens_eval         out[j * T + t]: the metrics of member j, target t over its `which` rows, one synchronisation whatever M is
+ *   eh_ens_load / store member j's whole state (theta, optimiser state and rule, BatchNorm statistics) into / out of the handle: eh_forward,
+ *                       eh_eval, eh_get_opt_state, eh_train_step ... then serve the member unchanged
+ * (added without a new EH_ABI_VERSION, like the entry points before them) */
+#define EH_ENS_MAX_MEMBERS 4096
+typedef struct eh_ensemble_s eh_ensemble;
+int32_t eh_ens_create(eh_handle* h, int32_t members, int64_t batchsize, eh_ensemble** out);
+int32_t eh_ens_destroy(eh_ensemble* e);
+int32_t eh_ens_set_params(eh_ensemble* e, int32_t member, const float* theta, int64_t n);
+int32_t eh_ens_get_params(eh_ensemble* e, int32_t member, float* theta, int64_t n);
+int32_t eh_ens_set_opt(eh_ensemble* e, int32_t member, int32_t rule, float lr, float beta1, float beta2, float eps, float weight_decay);
+int32_t eh_ens_get_opt_state(eh_ensemble* e, int32_t member, float* m, float* v, int64_t n, float* beta_t /* [2] */);
+int32_t eh_ens_set_opt_state(eh_ensemble* e, int32_t member, const float* m, const float* v, int64_t n, const float* beta_t);
+int32_t eh_ens_get_bn_state(eh_ensemble* e, int32_t member, float* running_mean, float* running_var, int64_t n_predictors);
+int32_t eh_ens_set_bn_state(eh_ensemble* e, int32_t member, const float* running_mean, const float* running_var, int64_t n_predictors);
+int32_t eh_ens_set_rows(eh_ensemble* e, int32_t member, int32_t which, const int32_t* rows, int64_t n);
+int32_t eh_ens_train_epoch(eh_ensemble* e, const uint64_t* seed, int32_t shuffle, const uint8_t* active, float* mean_loss, int64_t* n_steps);
+int32_t eh_ens_eval(eh_ensemble* e, int32_t which, eh_target_metrics* out);
+int32_t eh_ens_load(eh_ensemble* e, int32_t member);
+int32_t eh_ens_store(eh_ensemble* e, int32_t member);
+
 /* ---- data-parallel seam: one process per GPU, the host all-reduces EH_BUF_GRAD over RCCL ----------
  * eh_dp_grad   : local partial sums of the UN-normalised gradient, loss and valid counts into
  *                EH_BUF_GRAD  = [ grad (n_theta) | sum m (yhat-y)^2 | n_valid per target (T) | sum (y-c) | sum (y-c)^2 ]
