@@ -38,6 +38,7 @@ def test_mean_over_targets_on_every_kernel_family(hidden, T):
     lm, gm, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, agg="mean")
     assert nv == sum(nv0) and lm == pytest.approx(l0, rel=TOL) and util.relerr(gm, g0) <= TOL
+    util.check_gradient(gm, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, agg="mean"))
     assert lm == pytest.approx(ls / T, rel=2e-6) and util.relerr(gm * T, gs) <= 2e-6          # (and it is the sum over T)
     eng.set_agg("sum")
     l2, g2, _ = eng.loss_and_grad()
@@ -56,6 +57,7 @@ def test_mean_with_per_target_and_two_pass_losses(kinds):
     l0, g0, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=list(kinds), agg="mean")
     tol = 1e-4 if any(k in ("pearsonLoss", "kgeLoss", "pbkgeLoss") for k in kinds) else TOL
     assert lm == pytest.approx(l0, rel=tol) and util.relerr(gm, g0) <= tol
+    util.check_gradient(gm, g0, spec, tol, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=list(kinds), agg="mean"))
     eng.close()
 
 
@@ -87,6 +89,7 @@ def test_mean_with_extra_loss_terms(shape):
     ls, gsum, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, l2=oterms)
     assert l0 == pytest.approx(ls / (1 + len(oterms)), rel=1e-12)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, l2=oterms, agg="mean"))
     eng.opt_init("Adam", 0.003)
     batches = [(i * 300, 300) for i in range(3)] * 2
     losses = [eng.train_step(*b) for b in batches]
@@ -196,6 +199,7 @@ def test_extra_loss_of_the_predictions_the_references_own_case(hidden, agg):
     want = lm + np.sum(np.abs(res["NEE"])) + np.sum(np.abs(res["GPP"]))          # expected_loss = sum([main_loss, extra_loss_vals...])
     assert (agg != "sum" or l0 == pytest.approx(want, rel=1e-12)) and (agg != "mean" or l0 == pytest.approx((lm / 2 + want - lm) / 3, rel=1e-12))
     assert loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL, (loss, l0, util.relerr(grad, g0))
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, agg=agg, extra=extra))
     assert util.relerr(g0, gm) > 1e-2                                # the entries are not negligible here
     # the caller sees the data targets only
     m, yh = eng.eval(eh.EH_SPLIT_TRAIN, predictions=True)
@@ -218,6 +222,7 @@ def test_extra_loss_mean_entry_next_to_weight_l2_and_a_training_trajectory():
     loss, grad, _ = eng.loss_and_grad()
     l0, g0, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=["mae", "mse"], l2=(0.02, False), agg="mean", extra=extra)
     assert loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=["mae", "mse"], l2=(0.02, False), agg="mean", extra=extra))
     eng.opt_init("Adam", 0.003)
     batches = [(i * 300, 300) for i in range(6)]
     losses = [eng.train_step(*b) for b in batches]
@@ -271,6 +276,7 @@ def test_target_without_a_valid_sample_adds_nothing_to_the_gradient(hidden):
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y)
     assert nv0[1] == 0 and nv == nv0[0]
     assert loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL and np.isfinite(grad).all()
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y))
     # ... which is the one-target problem on NEE
     spec1 = ho.HybridSpec(spec.n_pred, list(hidden), "fluxpart", dict(spec.parameters), ["RUE", "Rb"], ["Q10"], ["NEE"], "tanh", True)
     l1, g1, _ = ho.loss_and_grad(spec1, theta.astype(np.float64), X, f, {"NEE": y["NEE"]})
@@ -382,6 +388,7 @@ def test_extra_loss_entries_over_two_predictions_and_global_parameters(hidden, a
     want = lm + sum(float(v) for v in ent.values()) if agg == "sum" else (lm + sum(float(v) for v in ent.values())) / 3
     assert l0 == pytest.approx(want, rel=2e-6), (l0, want)          # (the recorded program holds its constants -- 0.02, the bounds -- in fp32)
     assert loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL, (loss, l0, util.relerr(grad, g0))
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec_x, th64, X, f, y, agg=agg, extra=extra))      # (spec_x is spec with more outputs: the same leaves)
     # the oracle's gradient against central differences (fp64): the last NN bias, both global parameters, two weights
     for j in (0, 7, theta.size - 3, theta.size - 2, theta.size - 1):
         h = 1e-6 * max(1.0, abs(th64[j]))

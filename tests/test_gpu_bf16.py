@@ -40,6 +40,7 @@ def _check(eng, spec, theta, X, f, y, ltol=2e-5, gtol=5e-5):
     assert nv == sum(nv0)
     assert abs(loss - l0) <= ltol * abs(l0), (loss, l0)
     assert util.relerr(grad, g0) <= gtol, util.relerr(grad, g0)
+    util.check_gradient(grad, g0, spec, gtol, util.ref32_orders(spec, theta, X, f, y))      # (the oracle in the spec's own precision, fp32 against fp64)
     return loss, grad, l0, g0
 
 
@@ -54,6 +55,7 @@ def test_config5_loss_and_gradient_match_the_bf16_oracle(B):
     spec32 = ho.c5_spec(precision="f32")
     l32o, g32o, _ = ho.loss_and_grad(spec32, theta.astype(np.float64), X, f, y)
     assert abs(l32 - l32o) <= 1e-5 * abs(l32o) and util.relerr(g32, g32o) <= 1e-5
+    util.check_gradient(g32, g32o, spec32, 1e-5, util.ref32_orders(spec32, theta, X, f, y))
     assert abs(l32 - loss) > 1e-5 * abs(loss)
     eng.set_option("precision", 1)
     l2, g2, _ = eng.loss_and_grad()
@@ -75,6 +77,7 @@ def test_config5_bf16_operands_in_both_passes_match_the_oracle(B):
     # (the same forward FUNCTION; since round 5 the two modes run different kernels -- "bf16" the sample-owned one, csrc/eh_bf16_sample.hpp --
     #  so the loss sums agree to the order of summation, not bit for bit)
     assert abs(l1 - loss) <= 1e-6 * abs(loss) and util.relerr(g1, gf) <= 5e-5
+    util.check_gradient(g1, gf, specf, 5e-5, util.ref32_orders(specf, theta, X, f, y))
     assert util.relerr(grad, g1) > 5e-5, util.relerr(grad, g1)      # (a test that would not notice a kernel that ignored the option)
     # ... and the oracle sees the same distance between the two modes
     assert abs(util.relerr(g0, gf) - util.relerr(grad, g1)) <= 0.1 * util.relerr(g0, gf) + GTOL_BF16
@@ -191,6 +194,7 @@ def test_gathered_minibatch_matches_the_contiguous_one():
     loss, grad, nv = eng.loss_and_grad(idx=idx)
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, idx], {k: v[idx] for k, v in f.items()}, {k: v[idx] for k, v in y.items()})
     assert nv == sum(nv0) and abs(loss - l0) <= 2e-5 * abs(l0) and util.relerr(grad, g0) <= 5e-5
+    util.check_gradient(grad, g0, spec, 5e-5, util.ref32_orders(spec, theta, X[:, idx], {k: v[idx] for k, v in f.items()}, {k: v[idx] for k, v in y.items()}))
     eng.close()
 
 
@@ -271,16 +275,21 @@ def test_windows_and_gathered_minibatches_at_the_end_of_1e7_resident_samples(c5_
 
     def oracle(ix):
         return ho.loss_and_grad(sp, theta.astype(np.float64), X[:, ix], {k: v[ix] for k, v in f.items()}, {k: v[ix] for k, v in y.items()})
+
+    def ref32(ix):
+        return util.ref32_orders(sp, theta, X[:, ix], {k: v[ix] for k, v in f.items()}, {k: v[ix] for k, v in y.items()})
     for first, count in ((N - 4096, 4096), (N - 1001, 1001), (N // 2 + 3, 2000)):
         loss, grad, nv = eng.loss_and_grad(eh.EH_SPLIT_TRAIN, first, count)
         l0, g0, nv0 = oracle(np.arange(first, first + count))
         assert nv == sum(nv0) and abs(loss - l0) <= ltol * abs(l0) and util.relerr(grad, g0) <= gtol, (first, loss, l0, util.relerr(grad, g0))
+        util.check_gradient(grad, g0, sp, gtol, ref32(np.arange(first, first + count)))
     rng = np.random.default_rng(17)
     idx = rng.choice(np.arange(N - N // 100, N), 3000, replace=False).astype(np.int32)
     idx[:3] = (N - 1, N - N // 100, N - 2)                      # the very last record is in
     loss, grad, nv = eng.loss_and_grad(idx=idx)
     l0, g0, nv0 = oracle(idx)
     assert nv == sum(nv0) and abs(loss - l0) <= ltol * abs(l0) and util.relerr(grad, g0) <= gtol
+    util.check_gradient(grad, g0, sp, gtol, ref32(idx))
     with pytest.raises(ValueError):
         eng.loss_and_grad(eh.EH_SPLIT_TRAIN, N - 100, 101)      # one past the end
 
@@ -312,6 +321,17 @@ def test_training_steps_on_full_size_minibatches_from_the_last_percent(c5_reside
     # (a one-target model carries its deltas un-normalised -- also where the "bf16" mode rounds them -- so the gradient of the whole
     #  minibatch IS the count-weighted sum of the eighths', at the mode's own gradient tolerance)
     assert util.relerr(grad, acc_g / acc_n) <= PREC_TOL[precision][1], util.relerr(grad, acc_g / acc_n)
+
+    def ref32():
+        """the four orders of the fp32 oracle, each the count-weighted sum over the same eighths"""
+        acc = [0.0] * (util.REF32_ORDERS + 1)
+        for q in range(0, B, 8192):
+            ix = idx[q:q + 8192]
+            fq, yq = {k: v[ix] for k, v in f.items()}, {k: v[ix] for k, v in y.items()}
+            n = int((~np.isnan(yq["R_soil"])).sum())
+            acc = [a + g * n for a, g in zip(acc, util.ref32_orders(sp, theta, X[:, ix], fq, yq)())]
+        return [a / acc_n for a in acc]
+    util.check_gradient(grad, acc_g / acc_n, sp, PREC_TOL[precision][1], ref32)
     eng.opt_init("Descent", 0.05)
     step_loss = eng.train_step(0, B, idx=idx)
     assert step_loss == pytest.approx(loss, rel=1e-6)

@@ -59,6 +59,7 @@ def test_loss_gradient_and_forward_on_the_bench_inputs(bench_case, specialize):
         assert nv == sum(nv0) == count
         assert abs(loss - l0) <= 1e-5 * abs(l0), (first, count, loss, l0)
         assert util.relerr(grad, g0) <= 1e-5, (first, count, util.relerr(grad, g0))
+        util.check_gradient(grad, g0, spec, 1e-5, util.ref32_orders(spec, theta, *_slice(X, f, y, first, count)))
     out = eng.forward(eh.EH_SPLIT_TRAIN, 5 * B, B)
     ref = ho.forward(spec, theta.astype(np.float64), *_slice(X, f, y, 5 * B, B)[:2])
     assert util.relerr(out["reco"], ref["reco"]) <= 1e-5 and util.relerr(out["parameters"]["rb"], ref["parameters"]["rb"]) <= 1e-5
@@ -274,6 +275,7 @@ def test_canonical_descriptors_run_kernels_specialised_ahead_of_time():
             assert (n >= 1 and log.startswith("ahead-of-time")) == bool(aot), (name, aot, n, log[:200])
             if aot:
                 assert abs(loss - l_or) <= ltol * abs(l_or) and util.relerr(grad, g_or) <= gtol, (name, loss, l_or, util.relerr(grad, g_or))
+                util.check_gradient(grad, g_or, spec_o, gtol, util.ref32_orders(spec_o, model.initialparameters(3), X_, dict(zip(fnames, F_)), dict(zip(tnames, Y_))))
             res.append((loss, grad, m[0]["mse"]))
             eng.close()
         (l1, g1, m1), (l0, g0, m0) = res

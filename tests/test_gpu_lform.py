@@ -26,6 +26,7 @@ def _check(spec, theta, X, f, y, eng=None, bn_state=None, **kw):
     assert abs(loss - l0) <= TOL * abs(l0), (loss, l0)
     assert util.relerr(grad, g0) <= TOL, util.relerr(grad, g0)
     assert util.elem_relerr(grad, g0, 1e-3) <= 5e-4          # entry by entry, down to a thousandth of the largest one
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta, X, f, y, bn_state=bn_state))
     if own:
         eng.close()
 
@@ -357,6 +358,7 @@ def test_few_rows_products_and_grouped_weight_gradients(B):
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()})
     assert nv == sum(nv0) and abs(loss - l0) <= TOL * abs(l0) and util.relerr(grad, g0) <= TOL, (loss, l0, util.relerr(grad, g0))
     assert util.elem_relerr(grad, g0, 1e-3) <= 5e-4
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta, X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()}))
     idx = rng.permutation(n)[:B].astype(np.int32)
     _check(spec, theta, X, f, y, eng=eng, idx=idx)
     eng.close()

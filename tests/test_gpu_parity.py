@@ -31,6 +31,7 @@ def _check_grad(spec, theta, X, f, y, eng=None, **kw):
     assert nv == sum(nv0)
     assert abs(loss - l0) <= TOL * abs(l0)
     assert util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta, X, f, y))
     if own:
         eng.close()
 
@@ -38,16 +39,25 @@ def _check_grad(spec, theta, X, f, y, eng=None, **kw):
 # ----------------------------------------------------------------------------------------------
 # loss + gradient: activations x scaling x mask patterns x ragged sizes (RbQ10 = BASELINE configs 0/1)
 # ----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("act", ["tanh", "sigmoid", "relu", "swish"])
+GRID_ACTS = ["tanh", "sigmoid", "relu", "swish"]
+GRID_BATCHES = [(12, 0.0), (64, 0.2), (1024, 0.2), (1000, 0.05), (1, 0.0), (65, 0.5)]
+MLP_SHAPES = [(16,), (32, 32), (16, 16, 16), (24, 8), (64, 64), (48, 33, 16), (64,), (40, 64, 24)]
+
+
+@pytest.mark.parametrize("act", GRID_ACTS)
 @pytest.mark.parametrize("scale", [False, True])
-@pytest.mark.parametrize("B,nan_frac", [(12, 0.0), (64, 0.2), (1024, 0.2), (1000, 0.05), (1, 0.0), (65, 0.5)])
+@pytest.mark.parametrize("B,nan_frac", GRID_BATCHES)
 def test_rbq10_loss_and_grad(act, scale, B, nan_frac):
     _check_grad(*util.rbq10_case(B, act, scale, nan_frac))
 
 
-@pytest.mark.parametrize("hidden", [(16,), (32, 32), (16, 16, 16), (24, 8), (64, 64), (48, 33, 16), (64,), (40, 64, 24)])
+def mlp_shape_case(hidden):
+    return util.rbq10_case(300, "tanh", True, 0.1, hidden=hidden)
+
+
+@pytest.mark.parametrize("hidden", MLP_SHAPES)
 def test_other_mlp_shapes(hidden):
-    _check_grad(*util.rbq10_case(300, "tanh", True, 0.1, hidden=hidden))
+    _check_grad(*mlp_shape_case(hidden))
 
 
 def test_identity_activation():
@@ -56,11 +66,15 @@ def test_identity_activation():
     _check_grad(spec, theta, X, f, y)
 
 
-def test_expo2pool_config3_shape():
+def config3_case():
     # BASELINE.json configs[2]: MLP [8,64,64,4], four neural parameters, build-defined two-pool Expo model
     spec = ho.expo2pool_spec((64, 64), "tanh", True)
     X, f, y = ho.make_synth_expo2pool(1000, 5, 0.1)
-    _check_grad(spec, ho.init_theta(spec, 2, np.float32), X, f, y)
+    return spec, ho.init_theta(spec, 2, np.float32), X, f, y
+
+
+def test_expo2pool_config3_shape():
+    _check_grad(*config3_case())
 
 
 def test_reference_expo_model_one_predictor():
@@ -73,15 +87,17 @@ def test_reference_expo_model_one_predictor():
     _check_grad(spec, ho.init_theta(spec, 3, np.float32), SM[None], {"T": T}, {"Resp_obs": resp})
 
 
-@pytest.mark.parametrize("mech,neural,glob", [
+PARAMETER_SOURCES = [
     ("linear", ["alpha"], ["beta"]),
     ("linear", ["alpha", "beta"], []),
     ("rs_components", ["Rb_het", "Rb_root", "Rb_myc"], ["Q10_het", "Q10_root", "Q10_myc"]),
     ("rs_components", ["Rb_het", "Rb_root", "Rb_myc"], ["Q10_het"]),          # two Q10s fixed at their defaults
     ("rbq10", ["rb", "Q10"], []),                                             # Q10 predicted by the network too
     ("expo2pool", ["R0a", "R0b"], ["ka", "kb"]),
-])
-def test_parameter_sources_neural_global_fixed(mech, neural, glob):
+]
+
+
+def parameter_source_case(mech, neural, glob):
     mm = ho.MECH[mech][0]
     tabs = {"linear": {"alpha": (1.0, -2.0, 3.0), "beta": (0.5, -1.0, 2.0)}, "rbq10": dict(ho.RBQ10_PARAMS), "expo2pool": dict(ho.EXPO2POOL_PARAMS),
             "rs_components": {**{f"Rb_{c}": (1.0, 0.0, 5.0) for c in ("het", "root", "myc")}, **{f"Q10_{c}": (2.0 + i * 0.3, 1.0, 4.0) for i, c in enumerate(("het", "root", "myc"))}}}
@@ -92,7 +108,12 @@ def test_parameter_sources_neural_global_fixed(mech, neural, glob):
     frc = {mm.forcings[0]: rng.uniform(-5, 25, B).astype(np.float32)}
     yv = rng.uniform(0.5, 4, B).astype(np.float32)
     yv[rng.random(B) < 0.1] = np.nan
-    _check_grad(spec, ho.init_theta(spec, 4, np.float32), X, frc, {mm.outputs[0]: yv})
+    return spec, ho.init_theta(spec, 4, np.float32), X, frc, {mm.outputs[0]: yv}
+
+
+@pytest.mark.parametrize("mech,neural,glob", PARAMETER_SOURCES)
+def test_parameter_sources_neural_global_fixed(mech, neural, glob):
+    _check_grad(*parameter_source_case(mech, neural, glob))
 
 
 def test_wide_input_two_blocks():
@@ -308,6 +329,7 @@ def test_golden_fixture(path):
     assert nv == int(d["n_valid"].sum())
     assert abs(loss - float(d["loss"])) <= TOL * abs(float(d["loss"]))
     assert util.relerr(grad, d["grad"]) <= TOL
+    util.check_gradient(grad, d["grad"], spec, TOL, util.ref32_orders(spec, d["theta"], d["X"], f, y))
     for t in spec.targets:
         assert util.relerr(eng.forward(0, params=False)[t], d["yhat_" + t]) <= TOL
     n, batch = d["X"].shape[1], int(d["batch"])
@@ -461,6 +483,7 @@ def test_dp_seam_multi_target_virtual_shards(kinds):
     chk = util.load_engine(spec, theta, X, f, y); chk.set_training_loss(kinds)
     l1, g1, _ = chk.loss_and_grad()
     assert abs(l1 - l0) <= 1e-5 * abs(l0) and util.relerr(g1, g0) <= 1e-5
+    util.check_gradient(g1, g0, spec, 1e-5, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kinds))
     chk.close()
 
 
@@ -708,6 +731,7 @@ def test_set_data_layouts_agree():
         eng.close()
     l0, g0, n0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y)
     assert outs[0][0] == pytest.approx(l0, rel=TOL) and util.relerr(outs[0][1], g0) <= TOL
+    util.check_gradient(outs[0][1], g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y))
     for l, g, n in outs[1:]:
         assert l == outs[0][0] and np.array_equal(g, outs[0][1]) and n == outs[0][2]
     eng = util.model_from_spec(spec).engine()
@@ -762,6 +786,7 @@ def test_fused_update_mode_matches_two_kernel_mode():
     lg = c.loss_and_grad()                                     # a non-fused call in between flushes and stays consistent
     l0, g0, _ = ho.loss_and_grad(spec, c.get_params().astype(np.float64), X, f, y)
     assert lg[0] == pytest.approx(l0, rel=1e-5) and util.relerr(lg[1], g0) <= 1e-5
+    util.check_gradient(lg[1], g0, spec, 1e-5, util.ref32_orders(spec, c.get_params().astype(np.float64), X, f, y))
     a.close(); b.close(); c.close()
 
 
@@ -914,6 +939,7 @@ def test_other_training_losses(kind, fused):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kind)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kind))
     eng.opt_init("Adam", 0.01)
     eng.set_option("fused_update", fused)
     batches = [(i * 300, 300) for i in range(5)]
@@ -948,10 +974,12 @@ def test_input_batchnorm_train_mode_gradient_and_test_mode_forward():
     loss, grad, nv = eng.loss_and_grad()                                    # train mode: statistics of this batch
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, bn_state=ho.bn_init(spec))
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, bn_state=ho.bn_init(spec)))
     _check = eng.loss_and_grad(first=200, count=333)                        # other window -> other statistics
     sl = slice(200, 533)
     l1, g1, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, sl], {"ta": f["ta"][sl]}, {"reco": y["reco"][sl]})
     assert _check[0] == pytest.approx(l1, rel=TOL) and util.relerr(_check[1], g1) <= TOL
+    util.check_gradient(_check[1], g1, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X[:, sl], {"ta": f["ta"][sl]}, {"reco": y["reco"][sl]}))
     st = ho.bn_init(spec)                                                   # test mode before any step: running mean 0, var 1
     ref = ho.forward(spec, theta.astype(np.float64), X, f, bn_state=st, train_mode=False)
     assert util.relerr(eng.forward(0, params=False)["reco"], ref["reco"]) <= TOL
@@ -996,6 +1024,7 @@ def test_input_batchnorm_statistics_inside_the_step_kernel(B, fused):
         l, g, nv = eng.loss_and_grad(first=77, count=B)
         l0, g0, _ = ho.loss_and_grad(spec, th64, X[:, sl], {"ta": f["ta"][sl]}, {"reco": y["reco"][sl]})
         assert l == pytest.approx(l0, rel=TOL) and util.relerr(g, g0) <= TOL
+        util.check_gradient(g, g0, spec, TOL, util.ref32_orders(spec, th64, X[:, sl], {"ta": f["ta"][sl]}, {"reco": y["reco"][sl]}))
         eng.opt_init("Adam", 0.01); eng.set_option("fused_update", fused)
         rng = np.random.default_rng(5)
         ix = [rng.choice(2100, B, replace=False).astype(np.int32) for _ in range(4)]
@@ -1049,6 +1078,7 @@ def test_multinn_hybrid_model(nets, glob):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, {"reco": yv})
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, {"reco": yv}))
     eng.opt_init("Adam", 0.01)
     batches = [(i * 100, 100) for i in range(6)]
     for b in batches:
@@ -1093,6 +1123,7 @@ def test_single_network_with_an_activation_per_layer(hidden, acts, bn):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, {"reco": yv})
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, {"reco": yv}))
     if not bn:                                   # (with BatchNorm the forward of a fresh engine is in test mode on initial running statistics)
         ref = ho.forward(spec, theta.astype(np.float64), X, f)
         out = eng.forward(0)
@@ -1151,6 +1182,7 @@ def test_multinn_per_network_activations(nets, acts, glob):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, {tname: yv})
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, {tname: yv}))
     ref = ho.forward(spec, theta.astype(np.float64), X, f)
     out = eng.forward(0)
     assert util.relerr(out[tname], ref[tname]) <= TOL
@@ -1208,6 +1240,7 @@ def test_fluxpart_multi_target(targets, nets):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, yt)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, yt))
     out = eng.forward(0, params=False)
     ref = ho.forward(spec, theta.astype(np.float64), X, f)
     for t in targets:
@@ -1235,6 +1268,7 @@ def test_fluxpart_multi_target(targets, nets):
         l2, g2, n2 = eng2.loss_and_grad()
         l20, g20, n20 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, yt2)
         assert n2 == sum(n20) and l2 == pytest.approx(l20, rel=TOL) and util.relerr(g2, g20) <= TOL
+        util.check_gradient(g2, g20, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, yt2))
         eng2.close()
     eng.close()
 
@@ -1353,6 +1387,7 @@ def test_width_128_grid_independence_full_batch():
     l0, g0, _ = ho.loss_and_grad(spec, np.asarray(theta, np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()})
     l3, g3, _ = eng.loss_and_grad(first=0, count=4096)
     assert abs(l3 - l0) <= TOL * abs(l0) and util.relerr(g3, g0) <= TOL
+    util.check_gradient(g3, g0, spec, TOL, util.ref32_orders(spec, np.asarray(theta, np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()}))
     eng.close()
 
 
@@ -1487,6 +1522,7 @@ def test_width_128_other_training_losses(kind):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kind)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kind))
     eng.close()
 
 
@@ -1498,6 +1534,7 @@ def test_width_128_input_batchnorm():
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, bn_state=ho.bn_init(spec))
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, bn_state=ho.bn_init(spec)))
     eng.opt_init("Adam", 0.002)
     batches = [(i * 250, 250) for i in range(6)]
     losses = [eng.train_step(*b) for b in batches]
@@ -1527,6 +1564,7 @@ def test_width_128_fluxpart_multi_target_and_multinn(targets, nets):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, yt)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, yt))
     m, _ = eng.eval(0)
     ref = ho.forward(spec, theta.astype(np.float64), X, f)
     for i, t in enumerate(targets):
@@ -1622,11 +1660,13 @@ def test_moment_based_training_losses(kind, shape):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kind, bn_state=bn)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=1e-4) and util.relerr(grad, g0) <= 1e-4
+    util.check_gradient(grad, g0, spec, 1e-4, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kind, bn_state=bn))
     l1, g1, _ = eng.loss_and_grad(first=100, count=777)
     sl = slice(100, 877)
     l10, g10, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()},
                                    kind=kind, bn_state=ho.bn_init(spec) if bn is not None else None)
     assert l1 == pytest.approx(l10, rel=1e-4) and util.relerr(g1, g10) <= 1e-4
+    util.check_gradient(g1, g10, spec, 1e-4, util.ref32_orders(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()}, kind=kind, bn_state=ho.bn_init(spec) if bn is not None else None))
     eng.opt_init("Adam", 0.003)
     batches = [(i * 300, 300) for i in range(5)]
     losses = [eng.train_step(*b) for b in batches]
@@ -1675,6 +1715,7 @@ def test_weight_l2_extra_loss(normalize, shape):
     lp, gp, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y)
     assert util.relerr(g0, gp) > 2e-4                         # the term is not negligible in this test
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, l2=(lam, normalize)))
     eng.opt_init("Adam", 0.003)
     batches = [(i * 300, 300) for i in range(3)] * 2
     losses = [eng.train_step(*b) for b in batches]
@@ -1685,6 +1726,7 @@ def test_weight_l2_extra_loss(normalize, shape):
     l1, g1, _ = eng.loss_and_grad()
     l10, g10, _ = ho.loss_and_grad(spec, eng.get_params().astype(np.float64), X, f, y)
     assert l1 == pytest.approx(l10, rel=TOL) and util.relerr(g1, g10) <= TOL
+    util.check_gradient(g1, g10, spec, TOL, util.ref32_orders(spec, eng.get_params().astype(np.float64), X, f, y))
     if shape == "rbq10":
         eng.set_weight_l2(lam)
         with pytest.raises(NotImplementedError, match="weight_l2"):
@@ -1722,6 +1764,7 @@ def test_weight_l2_terms_per_network(shape):
     lp, gp, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y)
     assert util.relerr(g0, gp) > 2e-4                         # the terms are not negligible in this test
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, l2=oterms))
     eng.opt_init("Adam", 0.003)
     batches = [(i * 300, 300) for i in range(3)] * 2
     losses = [eng.train_step(*b) for b in batches]
@@ -1734,12 +1777,15 @@ def test_weight_l2_terms_per_network(shape):
     l1, g1, _ = eng.loss_and_grad()
     l10, g10, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, l2=(0.37, False))
     assert l1 == pytest.approx(l10, rel=TOL) and util.relerr(g1, g10) <= TOL
+    util.check_gradient(g1, g10, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, l2=(0.37, False)))
     eng.set_weight_l2_coef(coef)
     l2_, g2, _ = eng.loss_and_grad()
     assert l2_ == pytest.approx(l0, rel=TOL) and util.relerr(g2, g0) <= TOL
+    util.check_gradient(g2, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, l2=oterms))
     eng.set_weight_l2_coef(None)
     l3, g3, _ = eng.loss_and_grad()
     assert l3 == pytest.approx(lp, rel=TOL) and util.relerr(g3, gp) <= TOL
+    util.check_gradient(g3, gp, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y))
     with pytest.raises(ValueError):
         eng.set_weight_l2_coef(coef[:-1])
     with pytest.raises(ValueError):
@@ -1837,6 +1883,7 @@ def test_specialized_kernels_equal_the_kernels_built_ahead_of_time(case):
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()})
     assert na == nb == sum(nv0)
     assert abs(lb - l0) <= TOL * abs(l0) and util.relerr(gb, g0) <= TOL
+    util.check_gradient(gb, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()}))
     assert abs(la - lb) <= 1e-6 * abs(la) and util.relerr(gb, ga) <= 2e-6          # same arithmetic, possibly different contraction
     for eng in (a, b):
         eng.opt_init("Adam", 0.01)
@@ -1989,6 +2036,7 @@ def test_model_without_a_network_two_targets_and_per_target_losses():
         loss, grad, nv = eng.loss_and_grad()
         l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kinds)
         assert nv == sum(nv0) and abs(loss - l0) <= TOL * abs(l0) and util.relerr(grad, g0) <= TOL, (kinds, loss, l0, util.relerr(grad, g0))
+        util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kinds))
         eng.close()
 
 

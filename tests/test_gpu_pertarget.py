@@ -30,6 +30,7 @@ def test_per_target_losses(hidden, kinds):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kinds)
     assert nv == sum(nv0) and abs(loss - l0) <= 1e-5 * abs(l0) and util.relerr(grad, g0) <= 1e-5, (loss, l0, util.relerr(grad, g0))
+    util.check_gradient(grad, g0, spec, 1e-5, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kinds))
     eng.opt_init("Adam", 0.01)
     batches = [(0, 300), (300, 300), (600, 300)]
     losses = [eng.train_step(a, n) for a, n in batches]
@@ -71,6 +72,7 @@ def test_tuple_forms_of_a_custom_training_loss():
         eng.set_training_loss(form)
         loss, grad, _ = eng.loss_and_grad()
         assert abs(loss - l0) <= 1e-5 * abs(l0) and util.relerr(grad, g0) <= 2e-5
+        util.check_gradient(grad, g0, spec, 2e-5, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=name))
         eng.close()
 
 
@@ -95,10 +97,12 @@ def test_two_pass_losses_per_target(hidden, kinds):
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kinds)
     assert nv == sum(nv0) and abs(loss - l0) <= tol * abs(l0) and util.relerr(grad, g0) <= tol, (loss, l0, util.relerr(grad, g0))
+    util.check_gradient(grad, g0, spec, tol, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kinds))
     idx = np.random.default_rng(2).permutation(X.shape[1])[:500].astype(np.int32)
     loss, grad, nv = eng.loss_and_grad(idx=idx)
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, idx], {k: v[idx] for k, v in f.items()}, {k: v[idx] for k, v in y.items()}, kind=kinds)
     assert nv == sum(nv0) and abs(loss - l0) <= tol * abs(l0) and util.relerr(grad, g0) <= tol
+    util.check_gradient(grad, g0, spec, tol, util.ref32_orders(spec, theta.astype(np.float64), X[:, idx], {k: v[idx] for k, v in f.items()}, {k: v[idx] for k, v in y.items()}, kind=kinds))
     eng.opt_init("Descent", 0.02)
     batches = [(0, 300), (300, 300), (600, 300)]
     losses = [eng.train_step(a, n) for a, n in batches]
@@ -122,6 +126,7 @@ def test_one_target_without_a_valid_sample_adds_nothing():
     loss, grad, nv = eng.loss_and_grad()
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=("mse", "rmse"))
     assert nv == sum(nv0) and abs(loss - l0) <= 1e-5 * abs(l0) and util.relerr(grad, g0) <= 1e-5
+    util.check_gradient(grad, g0, spec, 1e-5, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=("mse", "rmse")))
     eng.close()
 
 
@@ -140,6 +145,7 @@ def test_recorded_loss_function_on_a_multi_target_model(hidden):
         loss, grad, nv = eng.loss_and_grad()
         l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=spec_kinds)
         assert nv == sum(nv0) and abs(loss - l0) <= 1e-5 * abs(l0) and util.relerr(grad, g0) <= 2e-5, (spec_kinds, loss, l0, util.relerr(grad, g0))
+        util.check_gradient(grad, g0, spec, 2e-5, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=spec_kinds))
         eng.close()
 
 

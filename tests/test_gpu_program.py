@@ -46,6 +46,7 @@ def _check(spec, theta, X, f, y, jit=1, **kw):
     assert nv == sum(nv0)
     assert abs(loss - l0) <= TOL * abs(l0)
     assert util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, np.asarray(theta, np.float64), X, f, y))
     return eng
 
 
@@ -65,6 +66,7 @@ def test_hand_written_rbq10_closure_equals_registry_model(hidden, act, jit):
     lr, gr, nr = eng_r.loss_and_grad()
     l0, g0, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y)
     assert nc == nr and abs(lc - l0) <= TOL * abs(l0) and util.relerr(gc, g0) <= TOL
+    util.check_gradient(gc, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y))
     assert abs(lc - lr) <= 2e-6 * abs(lr) and util.relerr(gc, gr) <= 4e-6        # the two device paths against each other
     eng_c.close(); eng_r.close()
 
@@ -135,6 +137,7 @@ def test_closure_with_other_training_losses(kind):
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=kind)
     tol = 1e-4 if kind == "kgeLoss" else TOL
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=tol) and util.relerr(grad, g0) <= tol
+    util.check_gradient(grad, g0, spec, tol, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kind))
     eng.close()
 
 
@@ -247,6 +250,7 @@ def test_random_closure_matches_the_oracle(seed, jit):
         assert abs(loss - l0) <= lbar * abs(l0) + 1e-9, info
         if np.max(np.abs(g0)) > 1e-7 * max(1.0, abs(l0)):
             assert util.relerr(grad, g0) <= gbar, info
+            util.check_gradient(grad, g0, spec, gbar, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=kind))
     eng.close()
 
 
@@ -275,10 +279,12 @@ def test_custom_training_loss(name, shape):
     assert eng.jit_status()[0] == 1, eng.jit_status()[1]
     l0, g0, nv0 = ho.loss_and_grad(spec, theta.astype(np.float64), X, f, y, kind=name)
     assert nv == sum(nv0) and loss == pytest.approx(l0, rel=TOL) and util.relerr(grad, g0) <= TOL
+    util.check_gradient(grad, g0, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X, f, y, kind=name))
     l1, g1, _ = eng.loss_and_grad(first=100, count=777)
     sl = slice(100, 877)
     l10, g10, _ = ho.loss_and_grad(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()}, kind=name)
     assert l1 == pytest.approx(l10, rel=TOL) and util.relerr(g1, g10) <= TOL
+    util.check_gradient(g1, g10, spec, TOL, util.ref32_orders(spec, theta.astype(np.float64), X[:, sl], {k: v[sl] for k, v in f.items()}, {k: v[sl] for k, v in y.items()}, kind=name))
     eng.close()
 
 
