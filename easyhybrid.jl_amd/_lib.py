@@ -24,6 +24,8 @@ EH_BUF_GRAD, EH_BUF_THETA, EH_BUF_OPT_M, EH_BUF_OPT_V, EH_BUF_GACC, EH_BUF_BNSTA
 
 ACTIVATIONS = {"tanh": 0, "sigmoid": 1, "relu": 2, "swish": 3, "identity": 4}
 EH_ACT_PER_NET = 5        # MultiNN: net k uses net_activation[k]
+EH_ACT_RECORDED = 8       # net_activation[k] = EH_ACT_RECORDED + j: the j-th recorded activation (eh_create_activations)
+EH_MAX_ACT_PROGS, EH_MAX_ACT_PROG, EH_MAX_ACT_CONST = 8, 32, 8
 EH_LAYER_LSTM = 16        # net_activation[l] of a hidden layer that is Recurrence(LSTMCell) (sequence models)
 EH_LAYER_GRU = 24         # ... Recurrence(GRUCell)
 EH_LAYER_RNN = 32         # ... Recurrence(RNNCell(.., act)): EH_LAYER_RNN + ACTIVATIONS[act]
@@ -53,6 +55,10 @@ class ModelDesc(C.Structure):
         ("prog_len", C.c_int32), ("prog_n_const", C.c_int32), ("prog_n_forc", C.c_int32), ("prog_n_out", C.c_int32),
         ("prog_out", C.c_int32 * EH_MAX_PROG_OUT), ("prog_code", C.c_uint32 * EH_MAX_PROG), ("prog_const", C.c_float * EH_MAX_PROG_CONST),
     ]
+
+
+class ActProgram(C.Structure):
+    _fields_ = [("n_instr", C.c_int32), ("n_const", C.c_int32), ("out_slot", C.c_int32), ("code", C.c_uint32 * EH_MAX_ACT_PROG), ("consts", C.c_float * EH_MAX_ACT_CONST)]
 
 
 class TargetMetrics(C.Structure):
@@ -93,6 +99,10 @@ SIGNATURES = {
     "eh_last_error": (C.c_char_p, [_H]),
     "eh_create": (C.c_int32, [C.POINTER(ModelDesc), C.POINTER(_H)]),
     "eh_create_seq_targets": (C.c_int32, [C.POINTER(ModelDesc), C.POINTER(_H)]),
+    # (the eh_act_program arrays go over as void*, like the option structs of eh_lbfgs_init: an `ActProgram * n` array is passed as it is)
+    "eh_create_activations": (C.c_int32, [C.POINTER(ModelDesc), C.c_void_p, C.c_int32, C.POINTER(_H)]),
+    "eh_activation_apply": (C.c_int32, [_H, C.c_int32, _F, C.c_int64, _F, _F]),
+    "eh_activation_source": (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     "eh_destroy": (C.c_int32, [_H]),
     "eh_n_theta": (C.c_int32, [_H, C.POINTER(C.c_int64)]),
     "eh_set_stream": (C.c_int32, [_H, C.c_void_p]),

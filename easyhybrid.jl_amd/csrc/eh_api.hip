@@ -305,7 +305,7 @@ static eh_handle_s::JitEntry* jit_entry(eh_handle* h) {
         return nullptr;
     }
     const bool ok = eh_jit_build(h->desc, h->arch, h->variant, h->act, kf, spec ? &h->net : nullptr, want_p2p, closs ? &h->loss_prog : nullptr, &je->k, &je->log,
-                                 /*allow_slp*/ true, h->drop_on ? je->drop : nullptr);
+                                 /*allow_slp*/ true, h->drop_on ? je->drop : nullptr, h->plan.acts.empty() ? nullptr : &h->plan.acts);
     je->state.store(ok ? 1 : -1, std::memory_order_release);
     if (!ok) { h->jit_log = je->log; h->jit_failed = true; return nullptr; }
     return je;
@@ -546,16 +546,21 @@ static void stream_pool_give(int device, hipStream_t s) {
     (void)hipStreamDestroy(s);
 }
 
-static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets);
+static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets, const eh_act_program* acts = nullptr, int n_acts = 0);
 int32_t eh_create(const eh_model_desc* d, eh_handle** out) { return create_handle(d, out, false); }
 int32_t eh_create_seq_targets(const eh_model_desc* d, eh_handle** out) { return create_handle(d, out, true); }
-static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets) {
+int32_t eh_create_activations(const eh_model_desc* d, const eh_act_program* progs, int32_t n_progs, eh_handle** out) {
+    if (n_progs != 0 && !progs) return fail(nullptr, EH_EINVAL, "eh_create_activations: null argument");
+    if (n_progs < 0) return fail(nullptr, EH_EINVAL, "eh_create_activations: %d activation programs (0..%d)", (int)n_progs, (int)EH_MAX_ACT_PROGS);
+    return create_handle(d, out, false, progs, n_progs);
+}
+static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_several_targets, const eh_act_program* acts, int n_acts) {
     if (!d || !out) return fail(nullptr, EH_EINVAL, "eh_create: null argument");
     *out = nullptr;
     // everything that needs no device: checks, block placement, the layout of flat theta, the family asked for, the EhNet (eh_plan.hpp)
     EhPlan plan;
     std::string why;
-    if (const int rc = eh_plan_model(d, seq_several_targets, &plan, &why)) return fail(nullptr, rc, "%s", why.c_str());
+    if (const int rc = eh_plan_model(d, seq_several_targets, &plan, &why, acts, n_acts)) return fail(nullptr, rc, "%s", why.c_str());
     const bool no_nn = plan.family == EH_FAMILY_NONE, seq = plan.family == EH_FAMILY_SEQ;
     const EhNet n = plan.net;
     // (EH_FORCE_LFORM: A/B switch of the measurement tools -- every feed-forward model layer by layer, the baseline tools/bench_bn_chain.py compares with)
@@ -577,6 +582,9 @@ static int32_t create_handle(const eh_model_desc* d, eh_handle** out, bool seq_s
         arch = &g_lform_arch;
         lform = true;
     }
+    // (the planner has refused the shapes no fused kernel holds; this answers what is left: EH_FORCE_LFORM, a shape the library was built without)
+    if (n_acts > 0 && (lform || seq))
+        return fail(nullptr, EH_EUNSUPPORTED, "eh_create_activations: recorded activations are built for the fused kernels, not for the layer-wise form this network runs on");
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, EH_EHIP, "eh_create: no HIP device (this library has no CPU path)");
@@ -777,6 +785,7 @@ int32_t eh_destroy(eh_handle* h) {
     for (auto e : h->ev) (void)hipEventDestroy(e);
     for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
     for (auto& e : h->jit) { if (e->worker.joinable()) e->worker.join(); eh_jit_release(&e->k); }
+    eh_jit_release(&h->act_apply);
     eh_comm_release(h);             // communicator / local group / peer-to-peer mappings and buffers (eh_comm.hip)
     (void)hipSetDevice(h->device);
     (void)hipFree(h->pset); (void)hipFree(h->opt_tab);
@@ -2255,6 +2264,7 @@ int32_t eh_set_dropout(eh_handle* h, const float* rate, int32_t n_hidden, uint64
         else if (h->arch->wide) why = "the row-split kernels (hidden widths above 64, or the row_split option)";
         else if (h->p2p_on || h->p2p_alloc || h->comm || h->lgroup) why = "data parallelism (a communicator or a peer-to-peer exchange is set up on this handle)";
         else if (h->capturing) why = "a handle that is recording a graph";
+        else if (!h->plan.acts.empty()) why = "recorded activations (eh_create_activations: the mask would have to go through the recorded derivative's kernels, not built)";
         if (why) return fail(h, EH_EUNSUPPORTED, "eh_set_dropout: dropout is built for the fp32 per-wave fused kernels of single-network models, not for %s", why);
         if (!h->jit_on) return fail(h, EH_EUNSUPPORTED, "eh_set_dropout: the dropout kernels are compiled at run time and the jit option is off (EH_JIT=0)");
     }
@@ -2298,6 +2308,49 @@ int32_t eh_dropout_mask(eh_handle* h, int32_t layer, uint64_t step, int64_t coun
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     (void)hipFree(dev);
     HIPCHK(h, e);
+    return EH_OK;
+}
+
+// ---- recorded activations (eh_device.hpp: EH_JIT_ACTPROG) ------------------------------------------------
+// j >= 0: recorded activation j; -1 - id (id = EH_ACT_TANH .. EH_ACT_IDENTITY): the built-in one, through the same two device functions
+int32_t eh_activation_apply(eh_handle* h, int32_t j, const float* z, int64_t n, float* a, float* da) {
+    if (!h || !z || (!a && !da)) return EH_EINVAL;
+    const int nprog = (int)h->plan.acts.size();
+    if (!nprog) return fail(h, EH_ESTATE, "eh_activation_apply: the handle has no recorded activations (eh_create_activations)");
+    if (j >= nprog || j < -1 - (int)EH_ACT_IDENTITY) return fail(h, EH_EINVAL, "eh_activation_apply: activation %d (recorded: 0..%d; built-in id: -1 - id)", (int)j, nprog - 1);
+    if (n < 0 || n > (1LL << 28)) return fail(h, EH_EINVAL, "eh_activation_apply: n = %lld", (long long)n);
+    if (n == 0) return EH_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->act_apply.fn[0]) {
+        std::string log;
+        if (!eh_jit_build_act_apply(h->plan.acts, &h->act_apply, &log)) return fail(h, EH_EUNSUPPORTED, "eh_activation_apply: the kernel failed to build: %.600s", log.c_str());
+    }
+    float* dev = nullptr;
+    HIPCHK(h, hipMalloc(&dev, (size_t)3 * (size_t)n * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(dev, z, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        int id = j >= 0 ? (int)EH_ACT_RECORDED + (int)j : -1 - (int)j;
+        const float* zd = dev;
+        long long cnt = n;
+        float *ad = a ? dev + n : nullptr, *dd = da ? dev + 2 * n : nullptr;
+        void* params[] = {&id, &zd, &cnt, &ad, &dd};
+        e = hipModuleLaunchKernel(h->act_apply.fn[0], (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, h->stream, params, nullptr);
+    }
+    if (e == hipSuccess && a) e = hipMemcpyAsync(a, dev + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && da) e = hipMemcpyAsync(da, dev + 2 * n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(dev);
+    HIPCHK(h, e);
+    return EH_OK;
+}
+
+int32_t eh_activation_source(const eh_act_program* progs, int32_t n_progs, char* buf, int64_t bytes) {
+    std::string why;
+    if (n_progs < 1) return fail(nullptr, EH_EINVAL, "eh_activation_source: %d activation programs (1..%d)", (int)n_progs, (int)EH_MAX_ACT_PROGS);
+    if (const int rc = eh_act_programs_check(progs, n_progs, "eh_activation_source", &why)) return fail(nullptr, rc, "%s", why.c_str());
+    const std::string s = eh_jit_act_source(progs, n_progs);
+    if (!buf || bytes < (int64_t)s.size() + 1) return (int32_t)s.size() + 1;
+    memcpy(buf, s.c_str(), s.size() + 1);
     return EH_OK;
 }
 

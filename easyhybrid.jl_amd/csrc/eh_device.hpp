@@ -941,7 +941,16 @@ template <int ACT> struct EhStoresZ { static constexpr bool value = ACT == EH_AC
 // kernels, found by the fuzz in round 3; the system compiler of ROCm 7.2 builds the same source).  Pinning the value to a VGPR costs
 // at most the v_accvgpr_read the store would need on older parts anyway.
 __device__ __forceinline__ float eh_vgpr(float v) { asm volatile("" : "+v"(v)); return v; }
+// Recorded activations (eh_create_activations), in kernels compiled at run time with EH_JIT_ACTPROG only: id = EH_ACT_RECORDED + j is the
+// j-th recorded closure, whose forward tape (eh_jit_act) and forward tape + reverse sweep (eh_jit_dact) the generated header holds.  Both
+// take the pre-activation, which these kernels keep for every row (EhStoresZ).
+#ifdef EH_JIT_ACTPROG
+#include "eh_jit_act.inc"
+#endif
 __device__ __forceinline__ float eh_act_id(int id, float z) {
+#ifdef EH_JIT_ACTPROG
+    if (id >= EH_ACT_RECORDED) return eh_jit_act(id - EH_ACT_RECORDED, z);
+#endif
     switch (id) {
         case EH_ACT_TANH: return eh_tanh(z);
         case EH_ACT_SIGMOID: return eh_sigmoid(z);
@@ -951,6 +960,9 @@ __device__ __forceinline__ float eh_act_id(int id, float z) {
     }
 }
 __device__ __forceinline__ float eh_dact_z_id(int id, float z) {       // act'(z) from the pre-activation
+#ifdef EH_JIT_ACTPROG
+    if (id >= EH_ACT_RECORDED) return eh_jit_dact(id - EH_ACT_RECORDED, z);
+#endif
     switch (id) {
         case EH_ACT_TANH: { const float t = eh_tanh(z); return 1.0f - t * t; }
         case EH_ACT_SIGMOID: { const float g = eh_sigmoid(z); return g * (1.0f - g); }

@@ -273,6 +273,7 @@ struct eh_handle_s {
     bool jit_failed = false;
     bool specialize = false;        // "specialize" option: every model gets kernels compiled around its descriptor
     EhLossProg loss_prog;           // eh_set_loss_program (EH_LOSS_PROGRAM)
+    EhJitKernel act_apply;          // eh_activation_apply's kernel, built on first use (the programs: plan.acts -- fixed for the handle's life, so no part of a JitEntry's key)
     std::string jit_log;
     // eh_set_dropout: Lux Dropout(drop[l]) behind hidden layer l in the training passes (per-wave kernels compiled at run time with the
     // rates in them; eh_device.hpp EH_JIT_DROPOUT).  drop_step counts the training steps launched since, applied or not

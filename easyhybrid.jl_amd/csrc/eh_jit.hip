@@ -216,8 +216,53 @@ std::string eh_jit_loss_source(const EhLossProg& lp) {
     return s;
 }
 
-namespace {
-}   // namespace
+// eh_jit_act.inc: per recorded activation j the forward tape, eh_jit_act_<j>(z) = act(z), and the forward tape followed by the reverse sweep
+// seeded with 1, eh_jit_dact_<j>(z) = act'(z) -- the pattern of eh_jit_loss_one; value slot 0 = z -- and the two dispatchers the kernels
+// call (eh_act_id / eh_dact_z_id, eh_device.hpp) with an index that is a constant wherever the layer loop is unrolled
+std::string eh_jit_act_source(const eh_act_program* acts, int n_acts) {
+    auto val = [](unsigned sl) -> std::string {
+        char b[32];
+        if (sl < EH_PROG_SLOT_CONST) return "z";
+        if (sl < EH_PROG_SLOT_INSTR) snprintf(b, sizeof b, "c%u", sl - EH_PROG_SLOT_CONST);
+        else snprintf(b, sizeof b, "t[%u]", sl - EH_PROG_SLOT_INSTR);
+        return b;
+    };
+    auto adj = [](unsigned sl) -> std::string {
+        char b[32];
+        if (sl < EH_PROG_SLOT_CONST) return "az";
+        if (sl < EH_PROG_SLOT_INSTR) return "ac";
+        snprintf(b, sizeof b, "at[%u]", sl - EH_PROG_SLOT_INSTR);
+        return b;
+    };
+    std::string s = "__device__ __forceinline__ float eh_pow(float b, float e);\n";      // (defined further down in eh_device.hpp)
+    char b[160];
+    for (int j = 0; j < n_acts; ++j) {
+        const eh_act_program& a = acts[j];
+        const int n = a.n_instr;
+        const std::string consts = const_decls(a.consts, a.n_const);
+        std::string fwd;
+        for (int i = 0; i < n; ++i) { snprintf(b, sizeof b, "    t[%d] = ", i); fwd += b + fwd_expr(a.code[i], val) + ";\n"; }
+        snprintf(b, sizeof b, "__device__ __forceinline__ float eh_jit_act_%d(float z) {\n", j);
+        s += b + consts;
+        snprintf(b, sizeof b, "    float t[%d];\n", n);
+        s += b + fwd + "    return " + val((unsigned)a.out_slot) + ";\n}\n";
+        snprintf(b, sizeof b, "__device__ __forceinline__ float eh_jit_dact_%d(float z) {\n", j);
+        s += b + consts;
+        snprintf(b, sizeof b, "    float t[%d], at[%d] = {}, az = 0.0f, ac = 0.0f;\n", n, n);
+        s += b + fwd + "    " + adj((unsigned)a.out_slot) + " += 1.0f;\n";
+        for (int i = n - 1; i >= 0; --i) {
+            snprintf(b, sizeof b, "    { const float g = at[%d], r = t[%d]; ", i, i);
+            s += b + rev_stmts(a.code[i], val, adj) + " (void)r; }\n";
+        }
+        s += "    (void)ac;\n    return az;\n}\n";
+    }
+    for (const char* f : {"act", "dact"}) {
+        s += std::string("__device__ __forceinline__ float eh_jit_") + f + "(int j, float z) {\n    switch (j) {\n";
+        for (int j = 0; j < n_acts; ++j) { snprintf(b, sizeof b, "        case %d: return eh_jit_%s_%d(z);\n", j, f, j); s += b; }
+        s += std::string("        default: return ") + (f[0] == 'a' ? "z" : "1.0f") + ";\n    }\n}\n";
+    }
+    return s;
+}
 
 std::string eh_jit_mech_source(const eh_model_desc& d) {
     const int n = d.prog_len;
@@ -357,7 +402,7 @@ static std::string eh_jit_dropout_source(const float* drop, int n_hidden) {
 // none: these models have no kernel built ahead of time.
 static thread_local int g_jit_level = 0;
 bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int act, int fast, const EhNet* spec, bool with_p2p,
-                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp, const float* drop) {
+                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp, const float* drop, const std::vector<eh_act_program>* acts) {
     const EhVariant& V = A->var[variant];
     const bool prog = d.mech == EH_MECH_PROGRAM;
     const std::string mech = prog ? eh_jit_mech_source(d) : std::string();
@@ -365,6 +410,8 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     const bool rowact = act == EH_ACT_PER_NET;
     const std::string rsrc = rowact ? eh_jit_rowact_source(d) : std::string();
     const std::string dsrc = drop ? eh_jit_dropout_source(drop, d.n_hidden) : std::string();
+    const bool actprog = rowact && acts && !acts->empty();
+    const std::string asrc = actprog ? eh_jit_act_source(acts->data(), (int)acts->size()) : std::string();
     // (hiprtc has the HIP device runtime built in but no C library headers)
     std::string src = "typedef signed char int8_t; typedef unsigned char uint8_t; typedef int int32_t; typedef unsigned int uint32_t;\n"
                       "typedef long long int64_t; typedef unsigned long long uint64_t;\n";
@@ -385,6 +432,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     if (prog) src += "#define EH_JIT_MECH 1\n";
     if (loss) src += "#define EH_JIT_LOSS 1\n";
     if (rowact) src += "#define EH_JIT_ROWACT 1\n";
+    if (actprog) src += "#define EH_JIT_ACTPROG 1\n";
     if (drop) src += "#define EH_JIT_DROPOUT 1\n";
     if (spec) {
         char b[512];
@@ -393,13 +441,14 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
         src += b;
     }
     src += V.so ? "#include \"eh_bf16_sample.hpp\"\n" : V.bf16 ? "#include \"eh_wide_bf16.hpp\"\n" : A->wide ? "#include \"eh_wide.hpp\"\n" : "#include \"eh_device.hpp\"\n";
-    const char* hnames[9] = {"eh_device.hpp", "eh_wide.hpp", "easyhybrid_hip.h", "eh_wide_bf16.hpp", "eh_bf16_sample.hpp", nullptr, nullptr, nullptr, nullptr};
-    const char* hsrc[9] = {eh_src_device, eh_src_wide, eh_src_public, eh_src_widebf, eh_src_bfs, nullptr, nullptr, nullptr, nullptr};
+    const char* hnames[10] = {"eh_device.hpp", "eh_wide.hpp", "easyhybrid_hip.h", "eh_wide_bf16.hpp", "eh_bf16_sample.hpp", nullptr, nullptr, nullptr, nullptr, nullptr};
+    const char* hsrc[10] = {eh_src_device, eh_src_wide, eh_src_public, eh_src_widebf, eh_src_bfs, nullptr, nullptr, nullptr, nullptr, nullptr};
     int nh = 5;
     if (prog) { hnames[nh] = "eh_jit_mech.inc"; hsrc[nh++] = mech.c_str(); }
     if (loss) { hnames[nh] = "eh_jit_loss.inc"; hsrc[nh++] = lsrc.c_str(); }
     if (rowact) { hnames[nh] = "eh_jit_rowact.inc"; hsrc[nh++] = rsrc.c_str(); }
     if (drop) { hnames[nh] = "eh_jit_dropout.inc"; hsrc[nh++] = dsrc.c_str(); }
+    if (actprog) { hnames[nh] = "eh_jit_act.inc"; hsrc[nh++] = asrc.c_str(); }
     hiprtcProgram hp = nullptr;
     if (hiprtcCreateProgram(&hp, src.c_str(), "eh_jit.hip", nh, hsrc, hnames) != HIPRTC_SUCCESS) { *log = "hiprtcCreateProgram failed"; return false; }
     // which kernels: train + eval, the cross-GPU train kernel when asked for, and -- per-wave family, registry model with its descriptor
@@ -460,7 +509,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
             hiprtcVersion(&ver[0], &ver[1]);
             h = fnv(h, ver, sizeof ver);
             h = fnv(h, src.data(), src.size()); h = fnv(h, mech.data(), mech.size()); h = fnv(h, lsrc.data(), lsrc.size()); h = fnv(h, rsrc.data(), rsrc.size());
-            h = fnv(h, dsrc.data(), dsrc.size());
+            h = fnv(h, dsrc.data(), dsrc.size()); h = fnv(h, asrc.data(), asrc.size());      // (asrc: the recorded activations, words and constants)
             h = fnv(h, eh_src_device, sizeof eh_src_device); h = fnv(h, eh_src_wide, sizeof eh_src_wide); h = fnv(h, eh_src_public, sizeof eh_src_public);
             h = fnv(h, eh_src_widebf, sizeof eh_src_widebf); h = fnv(h, eh_src_bfs, sizeof eh_src_bfs);
             for (int m = 0; m < nmode; ++m) h = fnv(h, name[m], strlen(name[m]));
@@ -488,7 +537,7 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
                 const std::string first = log->substr(0, 240);
                 const int saved = g_jit_level;
                 g_jit_level = next;
-                const bool ok2 = eh_jit_build(d, A, variant, act, fast, spec, with_p2p, loss, out, log, allow_slp, drop);
+                const bool ok2 = eh_jit_build(d, A, variant, act, fast, spec, with_p2p, loss, out, log, allow_slp, drop, acts);
                 g_jit_level = saved;
                 if (ok2 && log->empty()) *log = std::string(next == 1 ? "(compiled with -fno-slp-vectorize" : "(compiled at -O1") + " after the first build failed: " + first + ")";
                 return ok2;
@@ -512,6 +561,54 @@ bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int 
     out->nw = V.nw;
     out->lds_bytes = V.lds_bytes;
     out->lds_eval_bytes = V.lds_eval;
+    return true;
+}
+
+// eh_activation_apply's kernel: a[i] = eh_act_id(id, z[i]), da[i] = eh_dact_z_id(id, z[i]) around the generated eh_jit_act.inc -- the two
+// functions, and through them the generated code, that the step kernels call; fn[0].  Same flags, same disk cache as the step kernels.
+bool eh_jit_build_act_apply(const std::vector<eh_act_program>& acts, EhJitKernel* out, std::string* log) {
+    const std::string asrc = eh_jit_act_source(acts.data(), (int)acts.size());
+    const std::string src = "typedef signed char int8_t; typedef unsigned char uint8_t; typedef int int32_t; typedef unsigned int uint32_t;\n"
+                            "typedef long long int64_t; typedef unsigned long long uint64_t;\n"
+                            "#define EH_JIT_ACTPROG 1\n#include \"eh_device.hpp\"\n"
+                            "extern \"C\" __global__ __launch_bounds__(256) void eh_act_apply_kernel(int id, const float* z, long long n, float* a, float* da) {\n"
+                            "    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;\n"
+                            "    if (i >= n) return;\n"
+                            "    const float v = z[i];\n"
+                            "    if (a) a[i] = eh_act_id(id, v);\n"
+                            "    if (da) da[i] = eh_dact_z_id(id, v);\n"
+                            "}\n";
+    const char* hnames[3] = {"eh_device.hpp", "easyhybrid_hip.h", "eh_jit_act.inc"};
+    const char* hsrc[3] = {eh_src_device, eh_src_public, asrc.c_str()};
+    hiprtcProgram hp = nullptr;
+    if (hiprtcCreateProgram(&hp, src.c_str(), "eh_jit_act_apply.hip", 3, hsrc, hnames) != HIPRTC_SUCCESS) { *log = "hiprtcCreateProgram failed"; return false; }
+    const std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17"};      // the flags of the Makefile
+    std::string cpath;
+    {
+        const std::string dir = cache_dir();
+        if (!dir.empty()) {
+            unsigned long long h = 1469598103934665603ull;
+            int ver[2] = {0, 0};
+            hiprtcVersion(&ver[0], &ver[1]);
+            h = fnv(h, ver, sizeof ver);
+            h = fnv(h, src.data(), src.size()); h = fnv(h, asrc.data(), asrc.size());
+            h = fnv(h, eh_src_device, sizeof eh_src_device); h = fnv(h, eh_src_public, sizeof eh_src_public);
+            for (const char* o : opts) h = fnv(h, o, strlen(o));
+            char fn[64];
+            snprintf(fn, sizeof fn, "/%016llx.eco", h);
+            cpath = dir + fn;
+        }
+    }
+    std::vector<std::string> lowered;
+    std::vector<char> code;
+    const bool from_cache = !cpath.empty() && cache_load(cpath, 0, &lowered, &code);
+    if (getenv("EH_JIT_TRACE")) fprintf(stderr, "eh_jit: eh_act_apply_kernel | %s | cache %s\n", cpath.c_str(), from_cache ? "hit" : "miss");
+    if (!from_cache && !compile_and_cache(hp, opts, nullptr, 0, cpath, &lowered, &code, log)) { hiprtcDestroyProgram(&hp); return false; }
+    const bool ok = hipModuleLoadData(&out->mod, code.data()) == hipSuccess && hipModuleGetFunction(&out->fn[0], out->mod, "eh_act_apply_kernel") == hipSuccess;
+    if (!ok && from_cache) (void)unlink(cpath.c_str());       // a stale or damaged entry: gone, the next build compiles
+    (void)hipGetLastError();
+    hiprtcDestroyProgram(&hp);
+    if (!ok) { *log = "hipModuleLoadData / hipModuleGetFunction failed for the compiled activation kernel"; eh_jit_release(out); return false; }
     return true;
 }
 

@@ -41,7 +41,14 @@ std::string eh_jit_mech_source(const eh_model_desc& d);
 // allow_slp = false: never the SLP vectoriser (the flags of the kernels built ahead of time: a kernel that REPLACES one of those in the
 // middle of a run -- "specialize" = 2 -- must give the same bits)
 bool eh_jit_build(const eh_model_desc& d, const EhArchInfo* A, int variant, int act, int fast, const EhNet* spec, bool with_p2p,
-                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp = true, const float* drop = nullptr);
+                  const EhLossProg* loss, EhJitKernel* out, std::string* log, bool allow_slp = true, const float* drop = nullptr,
+                  const std::vector<eh_act_program>* acts = nullptr);
+// (acts: the programs of recorded activations, validated (eh_plan.hpp) -- compiled in under EH_JIT_ACTPROG with the generated eh_jit_act.inc,
+//  next to EH_JIT_ROWACT whose eh_row_act hands out the ids EH_ACT_RECORDED + j that name them)
+// the generated eh_jit_act.inc: eh_jit_act_<j>(z), eh_jit_dact_<j>(z) per program and the dispatchers eh_jit_act(j, z), eh_jit_dact(j, z)
+std::string eh_jit_act_source(const eh_act_program* acts, int n_acts);
+// eh_activation_apply's kernel (fn[0]): value and derivative of activation id -- built-in or EH_ACT_RECORDED + j -- through eh_act_id / eh_dact_z_id
+bool eh_jit_build_act_apply(const std::vector<eh_act_program>& acts, EhJitKernel* out, std::string* log);
 // (drop: dropout rates per hidden layer, d.n_hidden of them, or nullptr -- compiled in under EH_JIT_DROPOUT with the generated
 //  eh_jit_dropout.inc; such kernels are single-step only)
 // threshold of the keep test (a word below it drops the unit) and the factor on a kept unit for rate p in [0, 1): one definition for the

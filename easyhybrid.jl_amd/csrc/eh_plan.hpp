@@ -69,6 +69,7 @@ struct EhPlan {
     // sequence models: Dense(P -> I) -> cell(I -> H) -> Dense(H -> H) -> Dense(H -> K); seq_off: the ten leaves' offsets (EH_SEQ_WIN .. EH_SEQ_BOUT)
     int seq_cell = 0, seq_act_cell = 0, seq_I = 0, seq_H = 0, seq_nbi = 0, seq_nbh = 0, seq_act_in = 0, seq_act_hd = 0;
     int seq_off[EH_SEQ_NOFF] = {0};
+    std::vector<eh_act_program> acts;                   // recorded activations (eh_create_activations): program j is what net_activation = EH_ACT_RECORDED + j names
 };
 
 inline int eh_plan_fail(std::string* msg, int code, const char* fmt, ...) {
@@ -80,6 +81,8 @@ inline int eh_plan_fail(std::string* msg, int code, const char* fmt, ...) {
     *msg = buf;
     return code;
 }
+
+#include "eh_plan_act.hpp"      // what eh_create_activations adds to the checks below (eh_plan_fail is its way out too)
 
 struct EhMechInfo { int n_par, n_forc, n_out; };
 inline bool eh_mech_info(int mech, EhMechInfo* mi, const eh_model_desc* d = nullptr) {
@@ -165,10 +168,13 @@ inline int eh_norm_desc_check(const eh_model_desc* d, const EhNormKind* nk, std:
     return 1;
 }
 
-inline int eh_plan_model(const eh_model_desc* d, bool seq_several_targets, EhPlan* out, std::string* msg) {
+// acts / n_acts: the programs of recorded activations (eh_create_activations); eh_create passes none, and then answers the ids that name
+// them as it always has
+inline int eh_plan_model(const eh_model_desc* d, bool seq_several_targets, EhPlan* out, std::string* msg, const eh_act_program* acts = nullptr, int n_acts = 0) {
     *out = EhPlan();
     EhPlan& p = *out;
     if (d->struct_size != (int32_t)sizeof(eh_model_desc)) return eh_plan_fail(msg, EH_EINVAL, "eh_create: struct_size %d != %zu", d->struct_size, sizeof(eh_model_desc));
+    if (const int rc = eh_act_programs_check(acts, n_acts, "eh_create_activations", msg)) return rc;
     EhMechInfo mi;
     if (!eh_mech_info(d->mech, &mi, d)) return eh_plan_fail(msg, EH_EUNSUPPORTED, "eh_create: unknown mechanistic model id %d (no silent fallback)", d->mech);
     const bool desc_layers = d->activation == EH_ACT_PER_NET && d->n_hidden >= 0 && d->n_hidden <= EH_MAX_HIDDEN && d->n_nets >= 0 && d->n_nets <= EH_MAX_NETS;
@@ -180,6 +186,7 @@ inline int eh_plan_model(const eh_model_desc* d, bool seq_several_targets, EhPla
     const int seqk = (desc_layers && !norm) ? eh_seq_desc_check(d, mi.n_out, seq_several_targets, msg) : 0;
     if (seqk < 0) return seqk;
     const bool seq = seqk == 1;
+    if (const int rc = eh_act_family_check(d, n_acts, seq, norm, msg)) return rc;
     if (d->mech == EH_MECH_PROGRAM) {
         // every operand must name a slot that holds a value when the instruction runs: the kernel indexes a per-lane array with them
         if (d->n_params < 1 || d->n_params > EH_MAX_PARAMS) return eh_plan_fail(msg, EH_EINVAL, "eh_create: a program takes 1..%d parameters, descriptor has %d", EH_MAX_PARAMS, d->n_params);
@@ -216,15 +223,21 @@ inline int eh_plan_model(const eh_model_desc* d, bool seq_several_targets, EhPla
         if (d->n_nets < 0 || d->n_nets > EH_MAX_NETS) return eh_plan_fail(msg, EH_EINVAL, "eh_create: n_nets = %d (0..%d)", d->n_nets, EH_MAX_NETS);
         const int na = d->n_nets > 0 ? d->n_nets : d->n_hidden;
         if (na < 1 || na > EH_MAX_HIDDEN) return eh_plan_fail(msg, EH_EINVAL, "eh_create: per-layer activations need 1..%d hidden layers (n_hidden = %d)", EH_MAX_HIDDEN, d->n_hidden);
-        bool same = true;
+        bool same = true, used[EH_MAX_ACT_PROGS] = {};
         for (int k = 0; k < na; ++k) {
             if (seq && eh_seq_layer_code(d->net_activation[k])) { same = false; continue; }
             if (norm && eh_norm_kind(d->net_activation[k])) { same = false; continue; }
+            if (const int ra = eh_act_entry_check(d, k, n_acts, used, msg)) {      // names a recorded activation
+                if (ra < 0) return ra;
+                same = false;          // (never one of the kernels built ahead of time, even where every layer names the same program)
+                continue;
+            }
             if (d->net_activation[k] < 0 || d->net_activation[k] > EH_ACT_IDENTITY)
                 return eh_plan_fail(msg, EH_EUNSUPPORTED, "eh_create: unknown activation id %d for %s %d", d->net_activation[k], d->n_nets > 0 ? "net" : "hidden layer", k);
             same = same && d->net_activation[k] == d->net_activation[0];
         }
         if (same) act = d->net_activation[0];          // one activation after all: the kernels built ahead of time
+        if (const int rc = eh_act_used_check(d, n_acts, used, msg)) return rc;
     }
     if (d->n_params != mi.n_par) return eh_plan_fail(msg, EH_EINVAL, "eh_create: model %d takes %d parameters, descriptor has %d", d->mech, mi.n_par, d->n_params);
     if (d->n_predictors < 0 || d->n_hidden < 0 || d->n_hidden > EH_MAX_HIDDEN) return eh_plan_fail(msg, EH_EINVAL, "eh_create: n_predictors %d, n_hidden %d (0..%d)", d->n_predictors, d->n_hidden, EH_MAX_HIDDEN);
@@ -299,6 +312,9 @@ inline int eh_plan_model(const eh_model_desc* d, bool seq_several_targets, EhPla
     for (int t = 0; t < d->n_targets; ++t)
         if (d->target_output[t] < 0 || d->target_output[t] >= mi.n_out) return eh_plan_fail(msg, EH_EINVAL, "eh_create: target_output[%d] = %d (model has %d outputs)", t, d->target_output[t], mi.n_out);
 
+    // recorded activations live in the fused kernels compiled at run time; the layer-wise form applies its activations in kernels built ahead of time
+    if (const int rc = eh_act_shape_check(d, n_acts, p.maxw, K, msg)) return rc;
+
     // ---- accepted: from here on nothing is refused -------------------------------------------------------------------------------
     p.act = act; p.K = K; p.G = G;
     p.family = no_nn ? EH_FAMILY_NONE : seq ? EH_FAMILY_SEQ : norm ? EH_FAMILY_NORM : EH_FAMILY_FUSED;
@@ -306,6 +322,7 @@ inline int eh_plan_model(const eh_model_desc* d, bool seq_several_targets, EhPla
     p.nbi = (d->n_predictors + 15) / 16;
     p.nbh = nbh_raw <= 1 ? 1 : nbh_raw <= 2 ? 2 : nbh_raw <= 4 ? 4 : nbh_raw <= 8 ? 8 : 0;
     p.desc = *d;
+    p.acts.assign(acts, acts + n_acts);
     if (d->n_nets > 0) {
         for (int k = 0; k < p.n_nets; ++k) {
             p.desc.net_depth[k] = p.net_d[k];

@@ -82,7 +82,7 @@ def lbfgs_trace_row(r) -> dict:
 class HybridEngine:
     """Device-resident hybrid model: parameters, optimiser state and datasets live in HBM."""
 
-    def __init__(self, desc: L.ModelDesc, n_par: int, target_names: Sequence[str], param_names: Sequence[str], n_pseudo: int = 0):
+    def __init__(self, desc: L.ModelDesc, n_par: int, target_names: Sequence[str], param_names: Sequence[str], n_pseudo: int = 0, act_programs=None):
         self._lib = L.lib()
         self._h = C.c_void_p()
         self.desc = desc
@@ -90,7 +90,11 @@ class HybridEngine:
         seq = desc.activation == L.EH_ACT_PER_NET and desc.n_nets == 0 and any(
             desc.net_activation[l] in (L.EH_LAYER_LSTM, L.EH_LAYER_GRU) or L.EH_LAYER_RNN <= desc.net_activation[l] <= L.EH_LAYER_RNN + 4 for l in range(min(desc.n_hidden, L.EH_MAX_HIDDEN)))
         create = self._lib.eh_create_seq_targets if seq and desc.n_targets > 1 else self._lib.eh_create
-        st = create(C.byref(desc), C.byref(self._h))
+        self.act_programs = act_programs                  # (recorded activations: an array of L.ActProgram, or None)
+        if act_programs is not None:
+            st = self._lib.eh_create_activations(C.byref(desc), act_programs, len(act_programs), C.byref(self._h))
+        else:
+            st = create(C.byref(desc), C.byref(self._h))
         if st != L.EH_OK:
             self._h = C.c_void_p()
             _raise(st, self._lib.eh_last_error(None).decode())
@@ -135,6 +139,15 @@ class HybridEngine:
             self.close()
         except Exception:
             pass
+
+    def activation_apply(self, j: int, z: np.ndarray):
+        """(act_j(z), act_j'(z)) of recorded activation j, computed on the device by the generated functions the step kernels call
+        (j = -1 - id: the built-in activation `id`, through the same two device functions)"""
+        z = np.ascontiguousarray(z, np.float32).ravel()
+        a, da = np.empty_like(z), np.empty_like(z)
+        fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self._lib.eh_activation_apply(self._h, int(j), fp(z), z.size, fp(a), fp(da)))
+        return a, da
 
     def set_stream(self, stream_ptr: int):
         self._chk(self._lib.eh_set_stream(self._h, C.c_void_p(stream_ptr)))

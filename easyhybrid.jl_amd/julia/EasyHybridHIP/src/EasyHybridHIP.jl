@@ -369,6 +369,25 @@ function check(e::HybridEngine, st::Integer)
     error(msg)                                              # EH_EHIP / EH_ESTATE
 end
 
+# Recorded activations (include/easyhybrid_hip.h: eh_create_activations).  UNTESTED: written against the header, never run (no julia where
+# this was built).  net_activation[k] = EH_ACT_RECORDED + j names program j of the vector handed to create_activations.
+const EH_ACT_RECORDED = Int32(8)
+const EH_MAX_ACT_PROGS, EH_MAX_ACT_PROG, EH_MAX_ACT_CONST = 8, 32, 8
+struct EhActProgram
+    n_instr::Int32
+    n_const::Int32
+    out_slot::Int32
+    code::NTuple{32, UInt32}
+    consts::NTuple{8, Float32}
+end
+"""handle of a model whose descriptor names recorded activations; `progs` as recorded by the caller (slot 0 = z).  UNTESTED."""
+function create_activations(d::Ref{EhModelDesc}, progs::Vector{EhActProgram})
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    st = @ccall LIB[].eh_create_activations(d::Ref{EhModelDesc}, progs::Ptr{EhActProgram}, Int32(length(progs))::Int32, h::Ref{Ptr{Cvoid}})::Int32
+    st == 0 || error(unsafe_string(@ccall LIB[].eh_last_error(C_NULL::Ptr{Cvoid})::Cstring))
+    return h[]
+end
+
 function HybridEngine(m::SingleNNHybridModel; device::Integer = 0)
     d = Ref(descriptor(m; device))
     h = Ref{Ptr{Cvoid}}(C_NULL)

@@ -192,6 +192,79 @@ def _act_name(a) -> str:
     return _ACT_ALIASES[name]
 
 
+class RecordedActivation(str):
+    """An activation given as a closure, recorded as a device program (program.trace_activation).  It stands where the name of a built-in
+    activation stands -- model.activation, layer_activations, net_activations, config -- and is a string itself, "recorded:<name>:<digest
+    of the program's words and constants>", so that everything that carries, compares, copies or prints those entries keeps working; the
+    program rides along as `.program`.  Two closures that record to the same words and constants carry the same digest."""
+
+    def __new__(cls, value, program=None):
+        s = super().__new__(cls, value)
+        s.program = program
+        return s
+
+    def __getnewargs__(self):                  # (copy / deepcopy / pickle)
+        return (str(self), self.program)
+
+    @classmethod
+    def record(cls, fn):
+        import hashlib
+        from .program import trace_activation
+        prog = trace_activation(fn)
+        key = hashlib.sha1(repr((prog.words(), [np.float32(c).tobytes().hex() for c in prog.consts], prog.out)).encode()).hexdigest()[:12]
+        name = getattr(fn, "__name__", type(fn).__name__).strip("<>")
+        return cls(f"recorded:{name}:{key}", prog)
+
+    def same_program(self, other) -> bool:
+        p, q = self.program, other.program
+        return p.words() == q.words() and [np.float32(c).tobytes() for c in p.consts] == [np.float32(c).tobytes() for c in q.consts] and p.out == q.out
+
+
+def _is_recorded(a) -> bool:
+    return isinstance(a, RecordedActivation)
+
+
+def _act_of(a):
+    """an `activation` argument -> the name of a built-in activation (strings and callables named like one, `np.tanh`: exactly as
+    _act_name answers them), or the RecordedActivation of any other callable"""
+    if isinstance(a, RecordedActivation):
+        return a
+    if isinstance(a, str) or not callable(a) or getattr(a, "__name__", None) in _ACT_ALIASES:
+        return _act_name(a)
+    return RecordedActivation.record(a)
+
+
+def _act_gain(a) -> float:
+    return 1.0 if _is_recorded(a) else _ACT_GAIN[a]       # (Lux: kaiming_uniform's default gain for a function it does not know)
+
+
+# the common Lux / NNlib activations beyond the five built-in ones, as plain closures: they record like a user's own
+def softplus(x):
+    # NNlib: log1p(exp(-abs(x))) + relu(x), with relu written as (x + |x|) / 2: the reverse sweep takes |x|' = 0 at x = 0, which gives
+    # softplus'(0) = 1/2 exactly (max(x, 0) would hand the whole derivative to one side there)
+    return 0.5 * (x + abs(x)) + np.log(1.0 + np.exp(-abs(x)))
+
+
+def elu(x):
+    return np.where(x > 0.0, x, np.exp(np.minimum(x, 0.0)) - 1.0)         # alpha = 1; (the minimum keeps the branch not taken finite)
+
+
+def leakyrelu(x):
+    return np.where(x > 0.0, x, 0.01 * x)
+
+
+def gelu_tanh(x):
+    # 0.5 x (1 + tanh u), u = sqrt(2/pi) (x + 0.044715 x^3), in NNlib's form x sigmoid(2 u), the logistic written with its exponential:
+    # the reverse sweep then never forms 1 - tanh(u)^2, whose cancellation gelu's chain rule would multiply by up to 5 (x near 4).
+    # (the minimum keeps exp finite for x below -9, where the value is -0 and the derivative 0)
+    v = 1.5957691216057308 * x * (1.0 + 0.044715 * x * x)
+    return x / (1.0 + np.exp(np.minimum(-v, 80.0)))
+
+
+def hard_sigmoid_act(x):
+    return np.clip(0.2 * x + 0.5, 0.0, 1.0)                               # (hard_sigmoid above, without its np.asarray: that one is for parameter values)
+
+
 class Dense:
     """Lux `Dense(in => out, activation)` as a DESCRIPTION of a layer (no weights): what `hidden_layers = Chain(...)` is made of."""
 
@@ -421,6 +494,8 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
             # Dense(in_dim, I, act) -> Recurrence(LSTMCell(I => H)) -> RecurrenceOutputDense(H => H, act) -> Dense(H, out_dim), per time step
             if not per_layer:
                 raise NotImplementedError("hidden_layers Chain: Recurrence layers in a MultiNN model have no device kernel (sequence models are single-network)")
+            if _is_recorded(act):
+                raise NotImplementedError("a recorded activation (a closure) around a Recurrence: the sequence kernels are built ahead of time around the five built-in activations")
             if len(ls) != 1:
                 raise NotImplementedError(f"hidden_layers Chain: {len(ls)} layers around a Recurrence; the device kernel holds Chain(Recurrence(LSTMCell(I => H))) "
                                           "alone (stacked or non-final Recurrence layers are not built)")
@@ -435,7 +510,7 @@ def _hidden_widths(hidden_layers, act: str, per_layer: bool = False):
         for i, l in enumerate(ls):
             if not isinstance(l, Dense):
                 raise NotImplementedError(f"hidden_layers Chain: layer {i + 1} is {type(l).__name__}; only Dense layers have a device kernel")
-            acts.append(_act_name(l.activation))
+            acts.append(_act_of(l.activation))
             if acts[-1] != act and not per_layer:
                 raise NotImplementedError(f"hidden_layers Chain: layer {i + 1} uses {acts[-1]!r}, the model {act!r}: the networks of a MultiNN model "
                                           "apply ONE activation to all their hidden layers (per NETWORK activations exist: activation = {...}; "
@@ -461,6 +536,9 @@ def _bn_chain_widths(ls, act: str, per_layer: bool):
         raise NotImplementedError(f"hidden_layers Chain: a {what} layer next to a Recurrence has no device kernel (sequence models take no {what})")
     if any(isinstance(l, Dropout) for l in ls):
         raise NotImplementedError(f"hidden_layers Chain: a {what} layer next to a Dropout has no device kernel (dropout runs on the fused per-wave kernels, {what} layer by layer)")
+    if _is_recorded(act) or any(isinstance(l, Dense) and _is_recorded(_act_of(l.activation)) for l in ls):
+        raise NotImplementedError(f"hidden_layers Chain: a recorded activation (a closure) next to a {what} layer has no device kernel ({what} chains run layer by layer, "
+                                  "on kernels built ahead of time around the five built-in activations)")
     first = ls[0].dims if isinstance(ls[0], (BatchNorm, LayerNorm)) else getattr(ls[0], "in_dims", None)
     widths, acts, w = [first], [act], first
     for i, l in enumerate(ls):
@@ -481,6 +559,32 @@ def _bn_chain_widths(ls, act: str, per_layer: bool):
             raise NotImplementedError(f"hidden_layers Chain: layer {i + 1} is {type(l).__name__}; only Dense, BatchNorm and LayerNorm layers have a device kernel here")
         widths.append(w)
     return widths, acts
+
+
+def _distinct_recorded(acts):
+    seen: List[RecordedActivation] = []
+    for a in acts:
+        if _is_recorded(a) and not any(r.same_program(a) for r in seen):
+            seen.append(a)
+            yield a
+
+
+def _recorded_refusals(acts, widths, n_pred: int, n_out: int, kwargs: dict, dropout):
+    """where a recorded activation does not run, each with its reason, ahead of any upload (the library's planner answers the same
+    descriptors the same way: csrc/eh_plan.hpp)"""
+    n_rec = sum(1 for _ in _distinct_recorded(acts))
+    if n_rec > L.EH_MAX_ACT_PROGS:
+        raise NotImplementedError(f"{n_rec} distinct recorded activations in one model (device limit {L.EH_MAX_ACT_PROGS}; identical programs count once)")
+    if kwargs.get("precision", "f32") != "f32":
+        raise NotImplementedError(f"precision = {kwargs['precision']!r} with a recorded activation: the bf16 kernels keep only the rounded activation, "
+                                  "a recorded activation takes value and derivative from the pre-activation (fp32 only)")
+    if dropout is not None:
+        raise NotImplementedError("hidden_layers Chain: Dropout next to a recorded activation has no device kernel (the dropout kernels are built around the five built-in activations)")
+    w, nl = max(widths), len(widths)
+    if w > 128 or nl > 3 or (w > 64 and nl > 2) or n_pred > 32 or n_out > 16:
+        raise NotImplementedError(f"a recorded activation on hidden layers {list(widths)} ({n_pred} predictors, {n_out} outputs): recorded activations are built for the fused "
+                                  "kernels (up to 32 predictors and 16 outputs; widths up to 64 with at most 3 hidden layers, or up to 128 with at most 2), this network would run "
+                                  "in the layer-wise form, whose activations live in kernels built ahead of time")
 
 
 @dataclass
@@ -604,7 +708,7 @@ class SingleNNHybridModel:
                     bh = 1 / math.sqrt(o)
                     parts += [rng.uniform(-bh, bh, shape).astype(np.float32).flatten(order="F") for _, l2, _, shape in self.leaves() if l2 == li]
                     continue
-                gain = _ACT_GAIN[self.activation_of(k, li)] if li < len(net) - 1 else 1.0      # (a Dense layer in front of a BatchNorm keeps the gain of its own activation)
+                gain = _act_gain(self.activation_of(k, li)) if li < len(net) - 1 else 1.0      # (a Dense layer in front of a BatchNorm keeps the gain of its own activation)
                 bw = gain * math.sqrt(3.0 / i)
                 parts.append(rng.uniform(-bw, bw, (o, i)).astype(np.float32).flatten(order="F"))
                 parts.append(rng.uniform(-1 / math.sqrt(i), 1 / math.sqrt(i), o).astype(np.float32))
@@ -701,6 +805,32 @@ class SingleNNHybridModel:
             off += 1
         return out
 
+    def act_programs(self) -> List["RecordedActivation"]:
+        """the model's distinct recorded activations in order of first appearance; identical programs (same words and constants) count once"""
+        cands = list(self.net_activations or self.layer_activations or [])
+        if not cands and _is_recorded(self.config.get("activation")):
+            cands = [self.config["activation"]]
+        out: List[RecordedActivation] = []
+        for a in cands:
+            if _is_recorded(a) and not any(r.same_program(a) for r in out):
+                out.append(a)
+        return out
+
+    def act_program_structs(self):
+        """the eh_act_program array eh_create_activations takes, or None"""
+        progs = self.act_programs()
+        if not progs:
+            return None
+        arr = (L.ActProgram * len(progs))()
+        for j, r in enumerate(progs):
+            pg = r.program
+            arr[j].n_instr, arr[j].n_const, arr[j].out_slot = len(pg.code), len(pg.consts), pg.out[0]
+            for i, w in enumerate(pg.words()):
+                arr[j].code[i] = w
+            for i, c in enumerate(pg.consts):
+                arr[j].consts[i] = c
+        return arr
+
     # -- C descriptor ----------------------------------------------------------------------------
     def to_desc(self, device: int = 0, extra_outputs=(), mech: Optional[MechSpec] = None) -> L.ModelDesc:
         ms = mech if mech is not None else self.mechanistic_model      # (mech: the model's closure with the extra loss's entries as outputs of their own)
@@ -724,14 +854,22 @@ class SingleNNHybridModel:
                 d.net_depth[k] = len(net) - 1
                 for l, (o, _) in enumerate(net[:-1]):
                     d.net_hidden[k][l] = o
+        progs = self.act_programs()                # recorded activations: program j is what the id EH_ACT_RECORDED + j names
+
+        def code(a):
+            return L.EH_ACT_RECORDED + next(j for j, r in enumerate(progs) if r.same_program(a)) if _is_recorded(a) else _layer_code(a)
         if self.net_activations is not None:       # per-net activations: kernels compiled at run time around the descriptor
             d.activation = L.EH_ACT_PER_NET
             for k, a in enumerate(self.net_activations):
-                d.net_activation[k] = L.ACTIVATIONS[a]
+                d.net_activation[k] = code(a)
         elif self.layer_activations is not None:   # an activation per hidden layer (n_nets = 0): net_activation[l] is layer l's
             d.activation = L.EH_ACT_PER_NET
             for l, a in enumerate(self.layer_activations):
-                d.net_activation[l] = _layer_code(a)
+                d.net_activation[l] = code(a)
+        elif _is_recorded(self.activation):        # one recorded activation for all: still the per-net / per-layer form, every entry naming it
+            d.activation = L.EH_ACT_PER_NET
+            for k in range(len(self.NNs) if self.NNs is not None else len(hl)):
+                d.net_activation[k] = code(self.activation)
         else:
             d.activation = L.ACTIVATIONS[self.activation]
         d.scale_nn_outputs = int(self.scale_nn_outputs)
@@ -792,7 +930,7 @@ class SingleNNHybridModel:
                 prog, entries = trace_extra_loss_mixed(ms.fn, extra_fn, list(ms.params), list(self.forcing), list(self.targets), list(self.global_param_names), bounds)
                 mech = MechSpec(ms.id, ms.name, prog.params, prog.forcings, prog.outputs, prog, ms.fn)
         eng = HybridEngine(self.to_desc(device, [e[1] for e in entries], mech), len(self.mechanistic_model.params), self.targets,
-                           list(self.mechanistic_model.params), n_pseudo=len(entries))
+                           list(self.mechanistic_model.params), n_pseudo=len(entries), act_programs=self.act_program_structs())
         if entries:
             eng.set_extra_entries(entries)
         prec = self.config.get("precision", "f32")
@@ -832,12 +970,12 @@ def _construct_multi(predictors: Dict[str, Sequence[str]], forcing, targets, mec
     if isinstance(activation, dict):               # activation::NamedTuple (GenericHybridModel.jl:168-176)
         if not isinstance(hidden_layers, dict):    # the reference reads activation[nn_name] only next to hidden_layers[nn_name]
             raise TypeError("activation given per network needs hidden_layers given per network as well")
-        net_acts = [_act_name(activation[k]) for k in neural]
+        net_acts = [_act_of(activation[k]) for k in neural]
         act = net_acts[0]
         if len(set(net_acts)) == 1:
             net_acts = None
     else:
-        act = _act_name(activation)
+        act = _act_of(activation)
     acts_k = dict(zip(neural, net_acts)) if net_acts is not None else {k: act for k in neural}
     for hl_k in (hidden_layers.values() if isinstance(hidden_layers, dict) else [hidden_layers]):
         if isinstance(hl_k, Chain) and any(isinstance(l, Dropout) for l in hl_k.layers) and not any(isinstance(l, Recurrence) for l in hl_k.layers):
@@ -845,6 +983,9 @@ def _construct_multi(predictors: Dict[str, Sequence[str]], forcing, targets, mec
     hl = ({k: _hidden_widths(hidden_layers[k], acts_k[k]) for k in neural} if isinstance(hidden_layers, dict)
           else {k: _hidden_widths(hidden_layers, acts_k[k]) for k in neural})
     hidden_layers = hl if isinstance(hidden_layers, dict) else next(iter(hl.values()), [])
+    if any(_is_recorded(a) for a in acts_k.values()):
+        nl_ = max((len(v) for v in hl.values()), default=0)
+        _recorded_refusals(list(acts_k.values()), [sum(hl[k][min(l, len(hl[k]) - 1)] for k in neural) for l in range(nl_)], sum(len(predictors[k]) for k in neural), len(neural), kwargs, None)
     if any(len(v) < 1 for v in hl.values()):
         raise NotImplementedError("a network without a hidden layer")
     for p in ms.params:
@@ -918,7 +1059,7 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
     for t in targets:
         if t not in ms.outputs:
             raise ValueError(f"target {t!r} is not an output of {ms.name} {ms.outputs}")
-    act = _act_name(activation)
+    act = _act_of(activation)
     chain = hidden_layers
     hidden_layers, dropout = _split_dropout(hidden_layers)
     hidden_layers, layer_acts = _hidden_widths(hidden_layers, act, per_layer=True)
@@ -937,6 +1078,8 @@ def constructHybridModel(predictors, forcing: Sequence[str], targets: Sequence[s
     if dropout is not None and (len(hidden_layers) > DROPOUT_MAX_LAYERS or max(hidden_layers) > DROPOUT_MAX_WIDTH):
         raise NotImplementedError(f"hidden_layers Chain: Dropout on hidden layers {hidden_layers}: the dropout kernels are the per-wave fused family, "
                                   f"1..{DROPOUT_MAX_LAYERS} hidden layers of at most {DROPOUT_MAX_WIDTH} units")
+    if not no_nn and (_is_recorded(act) or any(_is_recorded(a) for a in (layer_acts or ()))):
+        _recorded_refusals([act] if layer_acts is None else layer_acts, hidden_layers, len(predictors), len(neural_param_names), kwargs, dropout)
     dims = [len(predictors)] + hidden_layers + [len(neural_param_names)]
     NN = [] if no_nn else [(dims[i + 1], dims[i]) for i in range(len(dims) - 1)]
     if no_nn:

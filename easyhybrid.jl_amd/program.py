@@ -38,6 +38,7 @@ class Program:
     consts: Tuple[float, ...]
     code: Tuple[Tuple[int, int, int, int], ...]     # (op, a, b, c) slots
     out: Tuple[int, ...]               # slot of each output
+    consts64: Tuple[float, ...] = ()   # recorded activations: the constants as the closure spelled them, for the fp64 host evaluation (the device takes `consts`)
 
     def words(self) -> List[int]:
         return [op | a << 8 | b << 16 | c << 24 for op, a, b, c in self.code]
@@ -52,6 +53,7 @@ class _Graph:
     def __init__(self):
         self.nodes: List[tuple] = []          # ("par", j) | ("frc", name) | ("const", value) | (op, a, b, c) node ids
         self.key: Dict[tuple, int] = {}
+        self.exact: Dict[float, float] = {}   # fp32 constant -> the value it was written as (first spelling; eval_activation's fp64 run)
 
     def node(self, *k) -> int:
         if k not in self.key:
@@ -60,7 +62,8 @@ class _Graph:
         return self.key[k]
 
     def const(self, v) -> int:
-        v = float(np.float32(v))
+        x, v = v, float(np.float32(v))
+        self.exact.setdefault(v, float(x))
         if math.isnan(v) or math.isinf(v):
             raise ValueError(f"constant {v} in a mechanistic program")
         return self.node("const", v)
@@ -194,7 +197,7 @@ _UFUNCS = {
     "power": lambda a, b: (a ** b) if isinstance(a, Sym) else b.__rpow__(a), "float_power": lambda a, b: (a ** b) if isinstance(a, Sym) else b.__rpow__(a),
     "negative": lambda a: -a, "positive": lambda a: a, "absolute": abs, "fabs": abs,
     "exp": exp, "log": log, "sqrt": sqrt, "tanh": tanh, "sin": sin, "cos": cos, "maximum": maximum, "minimum": minimum,
-    "square": lambda a: a * a, "reciprocal": lambda a: 1.0 / a,
+    "square": lambda a: a * a, "reciprocal": lambda a: 1.0 / a, "log1p": lambda a: log(1.0 + a), "expm1": lambda a: exp(a) - 1.0,
     "exp2": lambda a: 2.0 ** a, "log2": lambda a: log(a) * (1.0 / math.log(2.0)), "log10": lambda a: log(a) * (1.0 / math.log(10.0)),
     "greater": lambda a, b: _sym_of(a, b)._lift(a) > b, "less": lambda a, b: _sym_of(a, b)._lift(a) < b,
     "greater_equal": lambda a, b: _sym_of(a, b)._lift(a) >= b, "less_equal": lambda a, b: _sym_of(a, b)._lift(a) <= b,
@@ -425,6 +428,131 @@ def trace_loss(fn: Callable) -> Program:
     if len(consts) > MAX_CONST or len(code) > MAX_PROG:
         raise NotImplementedError(f"the loss has {len(code)} operations / {len(consts)} constants (device limits {MAX_PROG} / {MAX_CONST})")
     return Program(("yhat", "y"), (), ("loss",), tuple(consts), tuple(code), (out,))
+
+
+ACT_MAX_PROG, ACT_MAX_CONST, ACT_MAX_PROGS = 32, 8, 8      # EH_MAX_ACT_PROG, EH_MAX_ACT_CONST, EH_MAX_ACT_PROGS
+
+
+def _logistic(g: _Graph, nid: int, memo: Dict[int, int]) -> int:
+    """the logistic function written out, 1 / (1 + exp(-x)), as the one `sigmoid` operation: an activation spelled that way runs the
+    device's own sigmoid, the instructions of the built-in activation"""
+    if nid in memo:
+        return memo[nid]
+    n = g.nodes[nid]
+    out = nid
+    if n[0] not in ("par", "frc", "const"):
+        args = [_logistic(g, a, memo) for a in n[1:]]
+        out = g.node(n[0], *args)
+        one = lambda a: g.nodes[a] == ("const", 1.0)
+        if n[0] == "div" and one(args[0]) and g.nodes[args[1]][0] == "add":
+            for a, b in (g.nodes[args[1]][1:], g.nodes[args[1]][:0:-1]):
+                if one(a) and g.nodes[b][0] == "exp" and g.nodes[g.nodes[b][1]][0] == "neg":
+                    out = g.node("sigmoid", g.nodes[g.nodes[b][1]][1])
+    memo[nid] = out
+    return out
+
+
+def trace_activation(fn: Callable) -> Program:
+    """Record an activation function `fn(z)` (the reference hands `activation` to Lux's Dense unchanged, so any Julia function is one:
+    `Dense(15, 3, x -> x^2)`).  One traced argument, the pre-activation, and one elementwise result; the operations, the constant
+    folding and the encoding are those of trace_loss.  Value slot 0 = z.  The step kernels take the derivative from the reverse sweep
+    over the same tape."""
+    import inspect
+    name = getattr(fn, "__name__", "the activation")
+    try:
+        req = [p for p in inspect.signature(fn).parameters.values() if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD) and p.default is p.empty]
+        npar = len(req)
+    except (TypeError, ValueError):
+        npar = 1
+    if npar != 1:
+        raise NotImplementedError(f"activation {name!r} takes {npar} arguments: an activation is a function of one argument, the pre-activation (constants belong inside a closure)")
+    g = _Graph()
+    res = fn(Sym(g, g.node("par", 0)))
+    if isinstance(res, MeanOf):
+        raise NotImplementedError(f"numpy.mean / numpy.sum in activation {name!r}: an activation is elementwise, a reduction over the samples or units has no per-element device form")
+    if not isinstance(res, Sym):
+        raise TypeError(f"activation {name!r} returned a {type(res).__name__}, not a traced per-sample value: it must compute its result from its argument with the "
+                        "operations of a device program (+ - * / **, exp log sqrt tanh sigmoid sin cos abs maximum minimum where)")
+    root = _logistic(g, _fold(g, res.nid, {}), {})
+    consts: List[float] = []
+    code: List[Tuple[int, int, int, int]] = []
+    slot: Dict[int, int] = {}
+
+    def emit(nid: int) -> int:
+        if nid in slot:
+            return slot[nid]
+        n = g.nodes[nid]
+        if n[0] == "par":
+            s = SLOT_PAR
+        elif n[0] == "const":
+            if n[1] not in consts:
+                consts.append(n[1])
+            s = SLOT_CONST + consts.index(n[1])
+        else:
+            ops = [emit(a) for a in n[1:]] + [0, 0]
+            code.append((OPS[n[0]], ops[0], ops[1], ops[2]))
+            s = SLOT_INSTR + len(code) - 1
+        slot[nid] = s
+        return s
+
+    out = emit(root)
+    if out < SLOT_INSTR:                       # the identity, or a constant: an instruction of its own
+        zero = emit(g.const(0.0))
+        code.append((OPS["add"], out, zero, 0))
+        out = SLOT_INSTR + len(code) - 1
+    if len(consts) > ACT_MAX_CONST or len(code) > ACT_MAX_PROG:
+        raise NotImplementedError(f"activation {name!r} has {len(code)} operations / {len(consts)} constants (device limits {ACT_MAX_PROG} / {ACT_MAX_CONST})")
+    return Program(("z",), (), ("a",), tuple(consts), tuple(code), (out,), tuple(g.exact.get(c, c) for c in consts))
+
+
+def eval_activation(prog: Program, z) -> Tuple[np.ndarray, np.ndarray]:
+    """(act(z), act'(z)) of a recorded activation in fp64 on the host: the forward tape and the reverse sweep seeded with 1, statement by
+    statement what the generated device functions do (csrc/eh_jit.hip: fwd_expr / rev_stmts) -- for tests and for looking at a program;
+    the engine never calls it.  Constants: as the closure spelled them (Program.consts64) where the recorder kept that, so that the result
+    is the closure's own to fp64 rounding; the device computes with their fp32 values."""
+    z = np.asarray(z, np.float64)
+    cs = prog.consts64 if len(prog.consts64) == len(prog.consts) else prog.consts
+    n = len(prog.code)
+    with np.errstate(all="ignore"):
+        def val(s):
+            return z if s < SLOT_CONST else (np.float64(cs[s - SLOT_CONST]) if s < SLOT_INSTR else t[s - SLOT_INSTR])
+        t: List[np.ndarray] = []
+        for op, a, b, c in prog.code:
+            x, y, w = val(a), val(b), val(c)
+            k = OP_NAMES[op]
+            t.append(np.broadcast_to(np.asarray(
+                {"add": lambda: x + y, "sub": lambda: x - y, "mul": lambda: x * y, "div": lambda: x / y, "neg": lambda: -x, "exp": lambda: np.exp(x),
+                 "log": lambda: np.log(x), "pow": lambda: np.power(x, y), "sqrt": lambda: np.sqrt(x), "tanh": lambda: np.tanh(x),
+                 "sigmoid": lambda: 1.0 / (1.0 + np.exp(-x)), "max": lambda: np.maximum(x, y), "min": lambda: np.minimum(x, y), "abs": lambda: np.abs(x),
+                 "sin": lambda: np.sin(x), "cos": lambda: np.cos(x), "select": lambda: np.where(x > 0, y, w), "gt": lambda: (x > y).astype(np.float64)}[k](), np.float64), z.shape))
+        adj = {s: np.zeros(z.shape) for s in [SLOT_PAR] + [SLOT_INSTR + i for i in range(n)]}
+
+        def acc(s, v):
+            if s in adj:                       # (constants have no adjoint)
+                adj[s] = adj[s] + v
+        acc(prog.out[0], 1.0)
+        for i in range(n - 1, -1, -1):
+            op, a, b, c = prog.code[i]
+            x, y, g, r = val(a), val(b), adj[SLOT_INSTR + i], t[i]
+            k = OP_NAMES[op]
+            if k == "add": acc(a, g); acc(b, g)
+            elif k == "sub": acc(a, g); acc(b, -g)
+            elif k == "mul": acc(a, g * y); acc(b, g * x)
+            elif k == "div": acc(a, g / y); acc(b, -(g / y) * r)
+            elif k == "neg": acc(a, -g)
+            elif k == "exp": acc(a, g * r)
+            elif k == "log": acc(a, g / x)
+            elif k == "pow": acc(a, g * y * r / x); acc(b, g * r * np.log(x))
+            elif k == "sqrt": acc(a, g * 0.5 / r)
+            elif k == "tanh": acc(a, g * (1.0 - r * r))
+            elif k == "sigmoid": acc(a, g * r * (1.0 - r))
+            elif k == "max": acc(a, np.where(x >= y, g, 0.0)); acc(b, np.where(x >= y, 0.0, g))
+            elif k == "min": acc(a, np.where(x <= y, g, 0.0)); acc(b, np.where(x <= y, 0.0, g))
+            elif k == "abs": acc(a, np.where(x > 0, g, np.where(x < 0, -g, 0.0)))
+            elif k == "sin": acc(a, g * np.cos(x))
+            elif k == "cos": acc(a, -g * np.sin(x))
+            elif k == "select": acc(b, np.where(x > 0, g, 0.0)); acc(c, np.where(x > 0, 0.0, g))
+        return np.array(val(prog.out[0]), np.float64), adj[SLOT_PAR]
 
 
 def trace_extra_loss(fn: Callable, outputs: Sequence[str]):

@@ -236,6 +236,40 @@ int32_t eh_create(const eh_model_desc* desc, eh_handle** out);
  * (Added without a new EH_ABI_VERSION, like the entry points before it: nothing that existed changes, and eh_version() == 4 is what
  * callers -- and the suite -- check for.) */
 int32_t eh_create_seq_targets(const eh_model_desc* desc, eh_handle** out);
+
+/* Recorded activations: the activation of a Dense layer as a closure (the reference hands `activation` to Lux's Dense unchanged, so any
+ * Julia function is one: `Dense(15, 3, x -> x^2)`).  A host binding records the closure once, as it records a training loss, and hands the
+ * programs to eh_create_activations next to the descriptor, in which net_activation[k] = EH_ACT_RECORDED + j (activation ==
+ * EH_ACT_PER_NET; per net, or per hidden layer when n_nets == 0) names program j.  One recorded activation for all layers is
+ * EH_ACT_PER_NET with every entry EH_ACT_RECORDED + j.  Instruction words and value slots are those of eh_set_loss_program: slot 0 = the
+ * pre-activation z, slot 1 unused, constants from EH_PROG_SLOT_CONST, the result of instruction i at EH_PROG_SLOT_INSTR + i.  The step
+ * kernels of such a model are compiled at run time around two generated device functions per program, the forward tape and the forward
+ * tape followed by its reverse sweep seeded with 1 (act(z) and act'(z), both from the stored z); built-in and recorded activations mix.
+ * Checked before any device is looked for: counts within the limits, opcodes below EH_OP_COUNT, operands defined before use, every id
+ * has a program, no program without an id.  Runs wherever a model with an activation per layer runs on the fused kernels (per-wave and
+ * row-split, loss_and_grad / forward / eval, "fused_update" 0 1 2, eh_train_epoch, input BatchNorm, MultiNN with identity blocks, recorded
+ * mechanistic closures and losses, eh_dp_grad / eh_dp_apply).  Refused with the reason: networks only the layer-wise form holds (widths
+ * above 128, more than three hidden layers, BatchNorm / LayerNorm layers: its activations live in kernels built ahead of time), sequence
+ * models, "precision" other than 0, dropout, ensembles (eh_ens_create), the peer-to-peer step.
+ * eh_create itself keeps answering a descriptor that carries such ids as it always has ("unknown activation id").
+ * (Added without a new EH_ABI_VERSION, like the entry points before them.) */
+#define EH_ACT_RECORDED 8      /* net_activation[k] = EH_ACT_RECORDED + j, j = 0 .. EH_MAX_ACT_PROGS - 1 */
+#define EH_MAX_ACT_PROGS 8     /* distinct recorded activations of a model */
+#define EH_MAX_ACT_PROG 32     /* instructions of one */
+#define EH_MAX_ACT_CONST 8     /* its literal constants */
+typedef struct eh_act_program {
+    int32_t n_instr, n_const, out_slot;
+    uint32_t code[EH_MAX_ACT_PROG];
+    float consts[EH_MAX_ACT_CONST];
+} eh_act_program;
+int32_t eh_create_activations(const eh_model_desc* desc, const eh_act_program* progs, int32_t n_progs, eh_handle** out);
+/* a[i] = act_j(z[i]), da[i] = act_j'(z[i]) for i < n (host arrays; a or da may be NULL): a small kernel of its own, compiled at run time
+ * around the same generated device functions the step kernels call -- what a test holds the generated code against */
+int32_t eh_activation_apply(eh_handle* h, int32_t j, const float* z, int64_t n, float* a, float* da);
+/* the generated device source (eh_jit_act.inc) of `progs` as text, NUL-terminated, into buf; needs no handle and no device.  Returns the
+ * number of bytes the text needs (with its NUL) when buf is NULL or too small, 0 when it was written, a negative eh_status when the
+ * programs are malformed (eh_last_error(NULL) says why) */
+int32_t eh_activation_source(const eh_act_program* progs, int32_t n_progs, char* buf, int64_t bytes);
 int32_t eh_destroy(eh_handle* h);
 int32_t eh_n_theta(const eh_handle* h, int64_t* n);
 
